@@ -1,18 +1,21 @@
-"""Statistical anchor to the reference's own output (build container only: needs /root/reference and PIL).
+"""Statistical anchor to the reference's own output, through the figures of it stored in tests/golden/reference_final_scene_image.npz.
 
 The reference ships no vectors and is unseeded, so nothing here can be bit-exact — PARITY STAYS UNPINNED. What this does
 pin, against the one artefact the reference holds for BASELINE's headline scene (output/book2/Finanscene.jpg, 800x800,
 rendered by the reference's authors with unknown spp / seed / code version): that the oracle's radiometry is in the
 right place — where the light is, how bright the lit and the unlit parts are relative to each other, that the fog, the
 glass, the earth texture and the box of spheres land where the reference's do. Random box heights and sphere positions
-differ between the two (different RNG), so the comparison is on 8x8 block means of luminance, not pixels."""
+differ between the two (different RNG), so the comparison is on 8x8 block means of luminance, not pixels.
+
+The fixture holds what this test reads of that image (decoded to RGB8 by PIL): its shape, luminance_blocks() of it, and the mean
+RGB of the earth patch [400:560, 40:200]."""
 import os
 
 import numpy as np
-import pytest
 
-REF = "/root/reference/output/book2/Finanscene.jpg"
-ASSETS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets")
+HERE = os.path.dirname(os.path.abspath(__file__))
+REF = os.path.join(HERE, "golden", "reference_final_scene_image.npz")
+ASSETS = os.path.join(os.path.dirname(HERE), "assets")
 
 
 def luminance_blocks(rgb8, n=8):
@@ -21,9 +24,7 @@ def luminance_blocks(rgb8, n=8):
     return lum.reshape(n, lum.shape[0] // n, n, lum.shape[1] // n).mean(axis=(1, 3))
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="the reference's output images are only in the build container")
 def test_final_scene_agrees_with_the_reference_image_in_the_large(rt, O):
-    Image = pytest.importorskip("PIL.Image")
     W = H = 800
     spp = 8
     s = rt.HostScene("final_scene", seed=2022, assets_dir=ASSETS if os.path.isdir(ASSETS) else None)
@@ -31,9 +32,9 @@ def test_final_scene_agrees_with_the_reference_image_in_the_large(rt, O):
     p = rt.make_params(W, H, spp, 50, bg, seed=2022)
     rows = np.arange(H, dtype=np.uint32)
     img = rt.fill_image(O.render_cpu(s.desc, cam, p, rows, n_threads=os.cpu_count() or 4), rows, W, H, spp)
-    ref = np.asarray(Image.open(REF).convert("RGB"))
-    assert ref.shape == img.shape == (H, W, 3)
-    A, B = luminance_blocks(img), luminance_blocks(ref)
+    ref = np.load(REF)
+    assert tuple(ref["shape"]) == img.shape == (H, W, 3)
+    A, B = luminance_blocks(img), ref["luminance_blocks"]
     # the ceiling light: same blocks of the top row saturate in both, and nothing else does
     assert np.array_equal(A > 200, B > 200) and (A > 200).sum() == 3 and (A > 200)[0].sum() == 3
     # the layout in the large: block means correlate (measured 0.985 at 16 spp; unrelated scenes give < 0.5)
@@ -48,6 +49,5 @@ def test_final_scene_agrees_with_the_reference_image_in_the_large(rt, O):
     # image's floor is read off the image itself — its darkest block — and what lies above the floor agrees (measured: 1.9 levels apart)
     assert abs((A.mean() - A.min()) - (B.mean() - B.min())) < 8.0, (A.mean(), A.min(), B.mean(), B.min())
     # the earth texture (left, rows 4-5) is blue-green in both: blue and green exceed red there
-    for im in (img, ref):
-        patch = np.asarray(im[400:560, 40:200], dtype=np.float64).mean(axis=(0, 1))
+    for patch in (np.asarray(img[400:560, 40:200], dtype=np.float64).mean(axis=(0, 1)), ref["earth_patch_rgb"]):
         assert patch[2] > patch[0] and patch[1] > patch[0], patch

@@ -1,14 +1,16 @@
 #!/bin/bash
 # A/B of run-time switches with ONE library in ONE GPU call: tools/ab_env.sh "<VAR=val ...>" "<VAR=val ...>" ... -- <bench args>
 # runs bench.py once per environment setting and prints value / ms per step / per-kernel device time for each.
+OUT=${OUT:-out}
+mkdir -p $OUT
 settings=()
 while [ $# -gt 0 ] && [ "$1" != "--" ]; do settings+=("$1"); shift; done
 shift
 i=0
 for st in "${settings[@]}"; do
   i=$((i+1))
-  env $st timeout -k 10 300 python bench.py --no-cpu-baseline --no-pmc --no-plain "$@" > gpurun_out/abenv_$i.log 2>&1 || { echo "[$st]: bench failed, stopping"; tail -3 gpurun_out/abenv_$i.log; exit 1; }
-  python3 - "$st" gpurun_out/abenv_$i.log <<'PY'
+  env $st timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-pmc --no-plain "$@" > $OUT/abenv_$i.log 2>&1 || { echo "[$st]: bench failed, stopping"; tail -3 $OUT/abenv_$i.log; exit 1; }
+  python3 - "$st" $OUT/abenv_$i.log <<'PY'
 import sys, json
 n, f = sys.argv[1], sys.argv[2]
 try:
