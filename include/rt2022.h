@@ -355,6 +355,70 @@ int rt_scene_set_create(const rt_scene_desc *desc, uint64_t device_mask, rt_scen
 int rt_scene_set_destroy(rt_scene_set *set);
 int rt_render_multi(rt_scene_set *set, const rt_camera *cam, const rt_params *params, double *out_rgb_sum, rt_stats *stats);
 
+/* ---- closest-hit queries ------------------------------------------------------------------------
+ * `world.hit(r, t_min, t_max)` (hittable/mod.rs, bvh/mod.rs:86-101) for a batch of rays on the device scene, without
+ * rendering: picking, visibility and ambient-occlusion rays, scene debugging, other integrators above this ABI.
+ *
+ * Closest hit, per ray: the answer is the hit of the scene's root (rt_scene_desc.root: a BvhNode, a HittableList or a
+ * single object) over (t_min, t_max), with the reference's traversal order, so it is the CPU oracle's rto_hit(desc,
+ * desc.root, ray, t_min, t_max, rng_state) bit for bit:
+ *   - hit: t, u, v, p, normal, front_face, mat and rng_draws are the winning candidate's HitRecord, carried out through
+ *     its movers and FlipFace refs; prim is the winning leaf's ref as it appears in rt_scene_desc (flip bit included);
+ *   - miss: hit == 0, prim == RT_REF_NONE, rng_draws as drawn, every other field 0.
+ * That holds for any ray, hostile ones included: direction components of exactly 0 (infinite slab inverses),
+ * t_max <= t_min, t_max = +inf, NaN components (NaN comes out where the oracle's does).
+ * Every scene rt_scene_create accepts is covered: all primitive kinds, movers up to RT_MAX_XFORM_DEPTH, lists, FlipFace
+ * refs, ConstantMedium (its draws come from the ray's rng_state, constantmedium.rs:60) and moving spheres at the ray's time.
+ *
+ * RT_FLAG_ANY_HIT: traversal stops at the first candidate it accepts, in the reference's order. `hit` then equals the
+ * closest-hit query's `hit` on every ray (the two traversals are the same up to the first acceptance); on a hit the
+ * record is that candidate's: t lies in [t_closest, t_max), prim and mat are that leaf's. A scene holding a
+ * ConstantMedium (n_media > 0) refuses it with RT_ERR_UNSUPPORTED: a medium's verdict depends on the draws and on the
+ * closest distance so far, so an early stop has no reference meaning.
+ *
+ * rt_stats (may be NULL): rays = n_rays; with RT_FLAG_COUNTERS node_visits, prim_tests[] and rng_draws are the sums of
+ * the oracle's counters over the same rays (0 otherwise); paths, light_pdf_tests, passes, pool_slots, partial_bytes,
+ * trace_ms and shade_ms are 0; ms is the device time of the call.
+ *
+ * Arguments: n_rays == 0 is RT_OK with no launch. A null scene, or a null ray or hit buffer with n_rays > 0, or a flag
+ * bit other than RT_FLAG_COUNTERS / RT_FLAG_ANY_HIT is RT_ERR_INVALID with rt_last_error() set; so is a device buffer of
+ * rt_intersect_device that is not 16-byte aligned (records are read and written in 16-byte pieces).
+ * The call makes the scene's device current and restores the caller's, like rt_render_device.
+ *
+ * Independence from renders: a query owns its own device scratch (a work counter and a counter block per (scene,
+ * stream)) and never touches a render's pool, tape or pending stats; it may run on any stream while an RT_FLAG_ASYNC
+ * render of the same scene is in flight, and both keep their serial results bit for bit. Queries are re-entrant on one
+ * scene. rt_scene_destroy waits for queries still in flight before it frees anything. */
+typedef struct rt_query_ray {         /* 80 B */
+    double   origin[3];
+    double   direction[3];
+    double   time;                    /* Ray::tm (moving spheres) */
+    double   t_min, t_max;            /* per ray; t_max may be +inf */
+    uint64_t rng_state;               /* seeds the draws of ConstantMedium::hit, exactly as rto_hit's rng_state */
+} rt_query_ray;
+
+typedef struct rt_hit {               /* 96 B */
+    double   t, u, v;
+    double   p[3], normal[3];
+    uint32_t hit;                     /* 1: something was hit in (t_min, t_max) */
+    uint32_t front_face;
+    uint32_t mat;                     /* the caller's material index */
+    uint32_t prim;                    /* ref of the winning leaf as in rt_scene_desc, flip bit included; RT_REF_NONE on a miss */
+    uint32_t rng_draws;               /* 64-bit words drawn from rng_state */
+    uint32_t _pad;
+} rt_hit;
+
+#define RT_REF_NONE     0xFFFFFFFFu
+#define RT_FLAG_ANY_HIT 0x8u          /* rt_intersect*: stop at the first accepted candidate (see above) */
+
+/* Host buffers; synchronous. stats may be NULL. */
+int rt_intersect(rt_scene *scene, const rt_query_ray *rays, uint64_t n_rays, uint32_t flags,
+                 rt_hit *out_hits, rt_stats *stats);
+/* Device buffers, enqueued on hip_stream (NULL = default stream). With stats == NULL the call returns after the
+ * enqueue, with no host synchronisation. With stats it synchronises hip_stream and fills stats. */
+int rt_intersect_device(rt_scene *scene, const rt_query_ray *d_rays, uint64_t n_rays, uint32_t flags,
+                        rt_hit *d_out_hits, void *hip_stream, rt_stats *stats);
+
 /* write_color (main.rs:280-299): NaN→0, sqrt(c/spp), clamp [0,0.999], *255.999, floor. */
 void rt_write_color(const double rgb_sum[3], int32_t spp, uint8_t out_rgb[3]);
 /* Device form over n_pixels sums → n_pixels*3 bytes, on hip_stream. */

@@ -7,6 +7,8 @@ library has not been built — there is no Python or CPU fallback for the path.
 import ctypes as C
 import os
 
+import numpy as np
+
 RT2022_ABI_VERSION = 3
 
 RT_REF_FLIP = 0x80000000
@@ -23,6 +25,8 @@ RT_MAX_XFORM_DEPTH = 4
 RT_FLAG_COUNTERS = 0x1
 RT_FLAG_KERNEL_TIMES = 0x2
 RT_FLAG_ASYNC = 0x4
+RT_FLAG_ANY_HIT = 0x8
+RT_REF_NONE = 0xFFFFFFFF
 RT_OK, RT_ERR_INVALID, RT_ERR_UNSUPPORTED, RT_ERR_DEVICE, RT_ERR_NOMEM = 0, -1, -2, -3, -4
 
 KIND_NAMES = ["node", "sphere", "moving_sphere", "rect", "box", "triangle", "ring", "medium",
@@ -152,8 +156,27 @@ class rt_stats(C.Structure):
                 "rng_draws": self.rng_draws}
 
 
+class rt_query_ray(C.Structure):
+    _fields_ = [("origin", d3), ("direction", d3), ("time", C.c_double), ("t_min", C.c_double), ("t_max", C.c_double),
+                ("rng_state", C.c_uint64)]
+
+
+class rt_hit(C.Structure):
+    _fields_ = [("t", C.c_double), ("u", C.c_double), ("v", C.c_double), ("p", d3), ("normal", d3),
+                ("hit", C.c_uint32), ("front_face", C.c_uint32), ("mat", C.c_uint32), ("prim", C.c_uint32),
+                ("rng_draws", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+# numpy twins of rt_query_ray / rt_hit (same byte layout: arrays of them go to rt_intersect as they are)
+QUERY_RAY_DTYPE = np.dtype([("origin", "<f8", (3,)), ("direction", "<f8", (3,)), ("time", "<f8"), ("t_min", "<f8"),
+                            ("t_max", "<f8"), ("rng_state", "<u8")])
+HIT_DTYPE = np.dtype([("t", "<f8"), ("u", "<f8"), ("v", "<f8"), ("p", "<f8", (3,)), ("normal", "<f8", (3,)),
+                      ("hit", "<u4"), ("front_face", "<u4"), ("mat", "<u4"), ("prim", "<u4"), ("rng_draws", "<u4"),
+                      ("_pad", "<u4")])
+
 ABI_STRUCTS = [rt_bvh_node, rt_sphere, rt_moving_sphere, rt_rect, rt_box, rt_triangle, rt_ring, rt_medium, rt_xform,
-               rt_list, rt_material, rt_texture, rt_image, rt_perlin, rt_scene_desc, rt_camera, rt_params, rt_stats]
+               rt_list, rt_material, rt_texture, rt_image, rt_perlin, rt_scene_desc, rt_camera, rt_params, rt_stats,
+               rt_query_ray, rt_hit]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RT2022_LIB") or os.path.join(_HERE, "librt2022.so")   # (RT2022_LIB: A/B builds of the same library, tools/ab.sh)
@@ -162,6 +185,7 @@ LIB_PATH = os.environ.get("RT2022_LIB") or os.path.join(_HERE, "librt2022.so")  
 ABI_SYMBOLS = [
     "rt_scene_create", "rt_scene_destroy", "rt_render", "rt_render_device", "rt_render_wait", "rt_write_color",
     "rt_tonemap_device", "rt_last_error", "rt_abi_version", "rt_scene_set_create", "rt_scene_set_destroy", "rt_render_multi",
+    "rt_intersect", "rt_intersect_device",
     "rtb_scene_build", "rtb_scene_free", "rtb_scene_desc", "rtb_scene_default_view", "rtb_camera_new",
     "rtb_shuffled_rows", "rtb_bvh_build", "rtb_fill_image", "rtb_write_ppm", "rtb_write_jpeg", "rtb_image_load",
     "rtb_last_error", "rtb_abi_sizes",
@@ -196,6 +220,8 @@ def lib():
     L.rt_scene_set_create.argtypes = [P(rt_scene_desc), u64, P(vp)]
     L.rt_scene_set_destroy.argtypes = [vp]
     L.rt_render_multi.argtypes = [vp, P(rt_camera), P(rt_params), P(dbl), P(rt_stats)]
+    L.rt_intersect.argtypes = [vp, vp, u64, u32, vp, P(rt_stats)]
+    L.rt_intersect_device.argtypes = [vp, vp, u64, u32, vp, vp, P(rt_stats)]
     L.rtb_scene_build.argtypes = [C.c_char_p, u64, C.c_char_p, i32, P(vp)]
     L.rtb_scene_free.argtypes = [vp]
     L.rtb_scene_free.restype = None

@@ -203,6 +203,17 @@ constexpr int kPrimNodes = 600, kPrimSpheres = 256, kPrimMoving = 512;
 #endif
 constexpr int kTraceBlocksPerCU = RT2022_TRACE_BLOCKS_PER_CU;   // resident traversal workgroups per CU the lean kernels are built for
 
+// ---- closest-hit queries (pt_query.hip, rt_intersect*) ------------------------------
+struct QueryArgs {
+    const rt_query_ray *rays;          // device, 16-byte aligned
+    rt_hit *hits;                      // device, 16-byte aligned
+    uint64_t n_rays;
+    unsigned long long *counter;       // rays handed out so far (zeroed before launch)
+    StatsDev *stats;                   // counter instances only
+};
+hipError_t launch_query(const SceneDev &scene, const QueryArgs &args, uint32_t stack_need, bool counters, bool any_hit,
+                        hipStream_t stream);
+
 // Launchers (pt_kernel.hip). `stack_need` = entries the scene needs (host-computed).
 hipError_t launch_render(const SceneDev &scene, const RenderArgs &args, uint32_t stack_need, bool counters,
                          int n_blocks_hint, hipStream_t stream);

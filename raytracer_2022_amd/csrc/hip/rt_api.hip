@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -304,6 +305,15 @@ struct Workspace {
     std::string async_err;
 };
 
+// Scratch of the closest-hit queries on one (scene, stream): the ray counter of the persistent grid, a counter block
+// and two events. Nothing of a render's Workspace: a query may run beside an asynchronous render of the same scene.
+struct QueryScratch {
+    std::mutex mu;                    // one call at a time enqueues — and, with stats, reads back — on this (scene, stream)
+    unsigned long long *counter = nullptr;
+    StatsDev *stats = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+};
+
 } // namespace
 
 struct rt_scene {
@@ -327,6 +337,8 @@ struct rt_scene {
     int n_cus = 0;                    // compute units of `device`
     std::mutex mu;
     std::map<hipStream_t, Workspace> ws;
+    std::mutex qmu;                   // guards `qs`
+    std::map<hipStream_t, std::unique_ptr<QueryScratch>> qs;
 };
 
 namespace {
@@ -627,6 +639,68 @@ void enqueue(rt_scene *sc, const rt_camera *cam, const rt_params *p, const uint3
     }
 }
 
+QueryScratch &query_scratch_for(rt_scene *sc, hipStream_t stream) {
+    std::lock_guard<std::mutex> lock(sc->qmu);
+    std::unique_ptr<QueryScratch> &q = sc->qs[stream];
+    if (!q) {
+        std::unique_ptr<QueryScratch> n(new QueryScratch());
+        try {
+            RT_HIP(hipMalloc((void **)&n->counter, sizeof(unsigned long long)));
+            RT_HIP(hipMalloc((void **)&n->stats, sizeof(StatsDev)));
+            RT_HIP(hipEventCreate(&n->ev0));
+            RT_HIP(hipEventCreate(&n->ev1));
+        } catch (...) {
+            if (n->counter) (void)hipFree(n->counter);
+            if (n->stats) (void)hipFree(n->stats);
+            if (n->ev0) (void)hipEventDestroy(n->ev0);
+            if (n->ev1) (void)hipEventDestroy(n->ev1);
+            throw;
+        }
+        q = std::move(n);
+    }
+    return *q;
+}
+
+void check_query(const rt_scene *scene, const void *rays, uint64_t n_rays, uint32_t flags, const void *hits, const char *who) {
+    RT_REQUIRE(scene, RT_ERR_INVALID, std::string(who) + ": null scene");
+    RT_REQUIRE(n_rays == 0 || (rays && hits), RT_ERR_INVALID, std::string(who) + ": null ray or hit buffer");
+    RT_REQUIRE(!(flags & ~(RT_FLAG_COUNTERS | RT_FLAG_ANY_HIT)), RT_ERR_INVALID, std::string(who) + ": unknown flag bits");
+    RT_REQUIRE(!(flags & RT_FLAG_ANY_HIT) || scene->dev.n_media == 0, RT_ERR_UNSUPPORTED,
+               std::string(who) + ": RT_FLAG_ANY_HIT on a scene with a ConstantMedium (its verdict depends on the closest hit so far)");
+}
+
+// Enqueue one query on `stream` (the scene's device is current); with stats, wait for it and fill them.
+void run_query(rt_scene *sc, const rt_query_ray *d_rays, uint64_t n_rays, uint32_t flags, rt_hit *d_hits, hipStream_t stream,
+               rt_stats *stats) {
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (n_rays == 0) return;
+    QueryScratch &q = query_scratch_for(sc, stream);
+    std::lock_guard<std::mutex> lock(q.mu);
+    const bool counters = stats && (flags & RT_FLAG_COUNTERS);
+    QueryArgs a{d_rays, d_hits, n_rays, q.counter, counters ? q.stats : nullptr};
+    RT_HIP(hipMemsetAsync(q.counter, 0, sizeof(unsigned long long), stream));
+    if (counters) RT_HIP(hipMemsetAsync(q.stats, 0, sizeof(StatsDev), stream));
+    if (stats) RT_HIP(hipEventRecord(q.ev0, stream));
+    RT_HIP(launch_query(sc->dev, a, sc->stack_need, counters, (flags & RT_FLAG_ANY_HIT) != 0, stream));
+    if (!stats) return;
+    RT_HIP(hipEventRecord(q.ev1, stream));
+    RT_HIP(hipStreamSynchronize(stream));
+    rt_stats out;
+    std::memset(&out, 0, sizeof out);
+    out.rays = n_rays;
+    if (counters) {
+        StatsDev h;
+        RT_HIP(hipMemcpy(&h, q.stats, sizeof h, hipMemcpyDeviceToHost));
+        out.node_visits = h.node_visits;
+        for (int k = 0; k < RT_KIND_COUNT; k++) out.prim_tests[k] = h.prim_tests[k];
+        out.rng_draws = h.rng_draws;
+    }
+    float ms = 0.f;
+    RT_HIP(hipEventElapsedTime(&ms, q.ev0, q.ev1));
+    out.ms = (double)ms;
+    *stats = out;
+}
+
 void finish(rt_scene *sc, hipStream_t stream) {
     Workspace &w = workspace_for(sc, stream);
     RT_HIP(hipStreamSynchronize(stream));
@@ -850,6 +924,13 @@ int rt_scene_destroy(rt_scene *scene) {
             if (w.ev0) (void)hipEventDestroy(w.ev0);
             if (w.ev1) (void)hipEventDestroy(w.ev1);
         }
+        for (auto &kv : scene->qs) {
+            QueryScratch &q = *kv.second;
+            if (q.counter) (void)hipFree(q.counter);
+            if (q.stats) (void)hipFree(q.stats);
+            if (q.ev0) (void)hipEventDestroy(q.ev0);
+            if (q.ev1) (void)hipEventDestroy(q.ev1);
+        }
         for (void *p : scene->owned) (void)hipFree(p);
         delete scene;
         return RT_OK;
@@ -914,6 +995,50 @@ int rt_render_wait(rt_scene *scene, void *hip_stream) {
         const int rc = join_async(scene, (hipStream_t)hip_stream, &err);
         RT_REQUIRE(rc == RT_OK, rc, err);
         finish(scene, (hipStream_t)hip_stream);
+        return RT_OK;
+    });
+}
+
+int rt_intersect(rt_scene *scene, const rt_query_ray *rays, uint64_t n_rays, uint32_t flags, rt_hit *out_hits, rt_stats *stats) {
+    return guarded([&]() -> int {
+        check_query(scene, rays, n_rays, flags, out_hits, "rt_intersect");
+        if (n_rays == 0) {
+            if (stats) std::memset(stats, 0, sizeof *stats);
+            return RT_OK;
+        }
+        RT_REQUIRE(n_rays <= (1ull << 40), RT_ERR_INVALID, "rt_intersect: n_rays too large");
+        DeviceGuard guard(scene->device);
+        rt_query_ray *d_rays = nullptr;
+        rt_hit *d_hits = nullptr;
+        int rc = RT_OK;
+        try {
+            RT_HIP(hipMalloc((void **)&d_rays, n_rays * sizeof(rt_query_ray)));
+            RT_HIP(hipMalloc((void **)&d_hits, n_rays * sizeof(rt_hit)));
+            RT_HIP(hipMemcpy(d_rays, rays, n_rays * sizeof(rt_query_ray), hipMemcpyHostToDevice));
+            run_query(scene, d_rays, n_rays, flags, d_hits, nullptr, stats);
+            RT_HIP(hipMemcpy(out_hits, d_hits, n_rays * sizeof(rt_hit), hipMemcpyDeviceToHost));
+        } catch (const Fail &e) {
+            set_error(e.msg);
+            rc = e.code;
+        }
+        if (d_rays) (void)hipFree(d_rays);
+        if (d_hits) (void)hipFree(d_hits);
+        return rc;
+    });
+}
+
+int rt_intersect_device(rt_scene *scene, const rt_query_ray *d_rays, uint64_t n_rays, uint32_t flags, rt_hit *d_out_hits,
+                        void *hip_stream, rt_stats *stats) {
+    return guarded([&]() -> int {
+        check_query(scene, d_rays, n_rays, flags, d_out_hits, "rt_intersect_device");
+        RT_REQUIRE(n_rays == 0 || !(((uintptr_t)d_rays | (uintptr_t)d_out_hits) & 15u), RT_ERR_INVALID,
+                   "rt_intersect_device: ray and hit buffers must be 16-byte aligned");
+        if (n_rays == 0) {
+            if (stats) std::memset(stats, 0, sizeof *stats);
+            return RT_OK;
+        }
+        DeviceGuard guard(scene->device);
+        run_query(scene, d_rays, n_rays, flags, d_out_hits, (hipStream_t)hip_stream, stats);
         return RT_OK;
     });
 }

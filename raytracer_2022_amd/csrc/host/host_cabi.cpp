@@ -175,7 +175,8 @@ int rtb_abi_sizes(uint32_t *out, uint32_t n) {
     const uint32_t sizes[] = {sizeof(rt_bvh_node), sizeof(rt_sphere), sizeof(rt_moving_sphere), sizeof(rt_rect), sizeof(rt_box),
                               sizeof(rt_triangle), sizeof(rt_ring), sizeof(rt_medium), sizeof(rt_xform), sizeof(rt_list),
                               sizeof(rt_material), sizeof(rt_texture), sizeof(rt_image), sizeof(rt_perlin), sizeof(rt_scene_desc),
-                              sizeof(rt_camera), sizeof(rt_params), sizeof(rt_stats)};
+                              sizeof(rt_camera), sizeof(rt_params), sizeof(rt_stats),
+                              sizeof(rt_query_ray), sizeof(rt_hit)};
     const uint32_t count = sizeof(sizes) / sizeof(sizes[0]);
     for (uint32_t i = 0; i < n && i < count; i++) out[i] = sizes[i];
     return (int)count;

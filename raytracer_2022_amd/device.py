@@ -6,6 +6,27 @@ import numpy as np
 from . import _ffi as F
 
 
+def query_rays(origins, directions, time=0.0, t_min=0.001, t_max=np.inf, rng_state=None):
+    """An array of QUERY_RAY_DTYPE records (rt_query_ray) for rt_intersect: `origins` / `directions` are (n, 3) or (3,),
+    the other fields arrays of n or scalars, all broadcast to n rays. t_min defaults to ray_color's 0.001 (main.rs:243),
+    t_max to +inf. rng_state=None gives ray i the state i (the draws of a ConstantMedium on its path)."""
+    o = np.asarray(origins, dtype=np.float64)
+    d = np.asarray(directions, dtype=np.float64)
+    if o.shape[-1:] != (3,) or d.shape[-1:] != (3,) or o.ndim > 2 or d.ndim > 2:
+        raise ValueError("origins and directions must be (n, 3) or (3,)")
+    n = np.broadcast_shapes(o.shape[:-1], d.shape[:-1], np.shape(time), np.shape(t_min), np.shape(t_max),
+                            np.shape(rng_state) if rng_state is not None else ())
+    n = n[0] if n else 1
+    rays = np.zeros(n, dtype=F.QUERY_RAY_DTYPE)
+    rays["origin"] = np.broadcast_to(o, (n, 3))
+    rays["direction"] = np.broadcast_to(d, (n, 3))
+    rays["time"] = np.broadcast_to(np.asarray(time, dtype=np.float64), (n,))
+    rays["t_min"] = np.broadcast_to(np.asarray(t_min, dtype=np.float64), (n,))
+    rays["t_max"] = np.broadcast_to(np.asarray(t_max, dtype=np.float64), (n,))
+    rays["rng_state"] = np.arange(n, dtype=np.uint64) if rng_state is None else np.broadcast_to(np.asarray(rng_state, dtype=np.uint64), (n,))
+    return rays
+
+
 class DeviceScene:
     """rt_scene: the flattened scene copied into HBM on the current HIP device."""
 
@@ -79,6 +100,27 @@ class DeviceScene:
 
     def wait(self, stream_ptr=None):
         F.check(F.lib().rt_render_wait(self._h, C.c_void_p(stream_ptr or 0)))
+
+    def intersect(self, rays, any_hit=False, want_stats=False):
+        """rt_intersect: closest hit (or, any_hit=True, the first accepted) of every ray of `rays` (QUERY_RAY_DTYPE, see
+        query_rays) → array of HIT_DTYPE records [, rt_stats with the counters]."""
+        r = np.ascontiguousarray(rays, dtype=F.QUERY_RAY_DTYPE)
+        out = np.zeros(len(r), dtype=F.HIT_DTYPE)
+        flags = (F.RT_FLAG_ANY_HIT if any_hit else 0) | (F.RT_FLAG_COUNTERS if want_stats else 0)
+        st = F.rt_stats()
+        F.check(F.lib().rt_intersect(self._h, r.ctypes.data if len(r) else None, len(r), flags, out.ctypes.data if len(r) else None,
+                                     C.byref(st)))
+        return (out, st) if want_stats else out
+
+    def intersect_device(self, d_rays_ptr, n, d_hits_ptr, stream_ptr=None, any_hit=False, stats=None):
+        """rt_intersect_device: device pointers in (n rt_query_ray records, room for n rt_hit), enqueued on `stream_ptr`
+        (hipStream_t as int). stats=None returns after the enqueue, with no host synchronisation; an rt_stats makes the
+        call synchronise the stream and fill it, counters included."""
+        flags = F.RT_FLAG_ANY_HIT if any_hit else 0
+        if stats is not None:
+            flags |= F.RT_FLAG_COUNTERS
+        F.check(F.lib().rt_intersect_device(self._h, C.c_void_p(d_rays_ptr), n, flags, C.c_void_p(d_hits_ptr),
+                                            C.c_void_p(stream_ptr or 0), C.byref(stats) if stats is not None else None))
 
     def close(self):
         if self._h:

@@ -1,0 +1,378 @@
+"""Closest-hit queries (rt_intersect / rt_intersect_device) against the CPU oracle's rto_hit, ray by ray and bit for bit:
+float fields by their bit patterns (NaN where the oracle has NaN), flags, material, RNG draws, and the summed counters."""
+import ctypes as C
+import json
+import os
+
+import numpy as np
+import pytest
+
+from raytracer_2022_amd import _ffi as F
+
+pytestmark = pytest.mark.gpu
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ASSETS = os.path.join(os.path.dirname(HERE), "assets")
+INDEX = json.load(open(os.path.join(HERE, "golden", "golden_index.json")))
+BUILDERS = sorted({c["scene"] for c in INDEX.values()})
+FLOATS = ("t", "u", "v", "p", "normal")
+LEAF_POOLS = {F.RT_KIND_SPHERE: "spheres", F.RT_KIND_MOVING_SPHERE: "moving_spheres", F.RT_KIND_RECT: "rects",
+              F.RT_KIND_BOX: "boxes", F.RT_KIND_TRIANGLE: "triangles", F.RT_KIND_RING: "rings", F.RT_KIND_MEDIUM: "media"}
+
+
+def oracle_hits(O, desc, rays):
+    """rto_hit(desc, desc.root, ray, ...) for every ray → (HIT_DTYPE records without prim, summed rt_stats)."""
+    out = np.zeros(len(rays), dtype=F.HIT_DTYPE)
+    st = F.rt_stats()
+    for i, r in enumerate(rays):
+        rec = O.hit(desc, desc.root, r["origin"], r["direction"], tm=float(r["time"]), t_min=float(r["t_min"]),
+                    t_max=float(r["t_max"]), rng_state=int(r["rng_state"]), stats=st)
+        o = out[i]
+        o["hit"], o["front_face"], o["rng_draws"] = rec.hit, rec.front_face, rec.rng_draws
+        if rec.hit:
+            o["t"], o["u"], o["v"], o["mat"] = rec.t, rec.u, rec.v, rec.mat
+            o["p"], o["normal"] = rec.p[:], rec.normal[:]
+    return out, st
+
+
+def same_bits(a, b):
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return np.array_equal(np.isnan(a), np.isnan(b)) and np.array_equal(np.where(np.isnan(a), 0, a).view(np.uint64),
+                                                                       np.where(np.isnan(b), 0, b).view(np.uint64))
+
+
+def assert_records_equal(dev, ref, what=""):
+    assert np.array_equal(dev["hit"], ref["hit"]), what
+    assert np.array_equal(dev["rng_draws"], ref["rng_draws"]), what
+    h = ref["hit"] == 1
+    for f in FLOATS:
+        assert same_bits(dev[f][h], ref[f][h]), (what, f)
+    assert np.array_equal(dev["front_face"][h], ref["front_face"][h]), what
+    assert np.array_equal(dev["mat"][h], ref["mat"][h]), what
+    m = ~h
+    assert np.all(dev["prim"][m] == F.RT_REF_NONE), what
+    for f in FLOATS + ("front_face", "mat"):
+        assert not np.any(dev[f][m]), (what, f)
+
+
+def assert_prims_consistent(desc, hits):
+    for rec in hits[hits["hit"] == 1]:
+        kind, idx = F.ref_kind(int(rec["prim"])), F.ref_index(int(rec["prim"]))
+        assert kind in LEAF_POOLS, kind
+        assert idx < getattr(desc, "n_" + LEAF_POOLS[kind])
+        assert getattr(desc, LEAF_POOLS[kind])[idx].mat == rec["mat"]
+
+
+def counters(st, hits=None):
+    """The counters a query reports; with `hits`, rng_draws is the sum of the per-ray draws (what rto_hit reports per ray)."""
+    return st.node_visits, list(st.prim_tests), int(hits["rng_draws"].sum()) if hits is not None else st.rng_draws
+
+
+@pytest.fixture(scope="module", autouse=True)
+def torch_first():
+    """Bring torch's HIP context up before the library's first call, as the other GPU test modules do."""
+    import torch
+    assert torch.cuda.is_available(), "gpu tests need a GPU: the HIP path has no fallback"
+    torch.zeros(1, device="cuda")
+
+
+def scene_bounds(desc):
+    if F.ref_kind(desc.root) == F.RT_KIND_NODE:
+        n = desc.nodes[F.ref_index(desc.root)]
+        lo, hi = np.array(n.bmin[:]), np.array(n.bmax[:])
+        if np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)):
+            return lo, hi
+    return np.full(3, -8.0), np.full(3, 8.0)
+
+
+def unit_vectors(g, n):
+    v = g.normal(size=(n, 3))
+    return v / np.linalg.norm(v, axis=1, keepdims=True)
+
+
+def camera_rays(rt, cam, n, g, time=None):
+    """Pinhole rays of the camera's view (get_ray without the lens), at random points of the image."""
+    s, t = g.random(n), g.random(n)
+    o = np.array(cam.origin[:])
+    d = (np.array(cam.lower_left_corner[:]) + s[:, None] * np.array(cam.horizontal[:]) + t[:, None] * np.array(cam.vertical[:]) - o)
+    return rt.query_rays(o, d, time=g.uniform(cam.time0, cam.time1, n) if time is None else time)
+
+
+def bounce_rays(rt, hits, g, n):
+    h = hits[hits["hit"] == 1][:n]
+    d = h["normal"] + unit_vectors(g, len(h))
+    return rt.query_rays(h["p"], d, time=g.random(len(h)))
+
+
+def mixed_rays(rt, desc, cam, n, seed):
+    """Camera rays, one bounce from their hits, and random rays through the scene's bounds, with random per-ray windows,
+    times and RNG states (t_max = inf included)."""
+    g = np.random.default_rng(seed)
+    cam_r = camera_rays(rt, cam, n // 3, g)
+    lo, hi = scene_bounds(desc)
+    span = hi - lo
+    rnd_o = lo - 0.25 * span + g.random((n // 3, 3)) * 1.5 * span
+    rnd_r = rt.query_rays(rnd_o, unit_vectors(g, n // 3))
+    first = np.concatenate([cam_r, rnd_r])
+    return first, g
+
+
+def randomise_windows(rays, g):
+    n = len(rays)
+    rays["time"] = g.random(n)
+    rays["t_min"] = g.choice([0.001, 0.0, 1e-9, 0.5], n)
+    tmax = g.choice([np.inf, 1e300, 0.0], n, p=[0.6, 0.2, 0.2])
+    far = tmax == 0.0
+    rays["t_max"] = np.where(far, rays["t_min"] + g.exponential(50.0, n), tmax)
+    rays["rng_state"] = g.integers(0, 2**63, n, dtype=np.uint64)
+    return rays
+
+
+def check_scene(rt, O, desc, cam, n, seed, dev=None):
+    dev = dev or rt.DeviceScene(desc)
+    first, g = mixed_rays(rt, desc, cam, n, seed)
+    h0 = dev.intersect(first)
+    rays = np.concatenate([first, bounce_rays(rt, h0, g, n // 3)])
+    rays = randomise_windows(rays, g)
+    got, st = dev.intersect(rays, want_stats=True)
+    ref, st_ref = oracle_hits(O, desc, rays)
+    assert_records_equal(got, ref)
+    assert_prims_consistent(desc, got)
+    assert st.rays == len(rays) and counters(st) == counters(st_ref, ref)
+    assert st.paths == 0 and st.passes == 0 and st.pool_slots == 0 and st.partial_bytes == 0 and st.ms > 0
+    assert np.array_equal(dev.intersect(rays).view(np.uint8), got.view(np.uint8))          # the plain kernel instance
+    return got, rays
+
+
+def every_kind_scene(rt, with_medium=True):
+    """The hand-built scene of tests/test_gpu_parity.py: one of each hittable kind under a HittableList root."""
+    b = rt.DescBuilder()
+    lam = b.lambertian((0.6, 0.5, 0.4))
+    img = (np.arange(8 * 4 * 3, dtype=np.uint8).reshape(4, 8, 3) * 7) % 251
+    refs = [
+        b.sphere((0, -100, 0), 100.0, b.lambertian(tex=b.checker(b.solid((0.2, 0.3, 0.1)), b.solid((0.9, 0.9, 0.9))))),
+        b.sphere((0, 1, 0), 1.0, b.lambertian(tex=b.image(img))),
+        b.moving_sphere((2.5, 0.5, 0), (2.5, 1.0, 0), 0, 1, 0.5, b.metal((0.8, 0.7, 0.6), 0.3)),
+        b.sphere((-2.5, 1, 0), 1.0, b.dielectric(1.5)),
+        b.triangle((-1, 0.01, 2), (1, 0.01, 2), (0, 1.5, 2.5), lam),
+        b.translate(b.ring(1.5, 0.3, lam), (0, 0.5, -3)),
+        b.translate(b.rotate_y(b.zoom(b.box((-0.5, 0, -0.5), (0.5, 1, 0.5), lam), 1.5), 0.5, 0.8660254037844386), (4.5, 0, 2)),
+        b.list([b.rect(F.RT_RECT_XZ, -1, 1, -1, 1, 6.0, b.diffuse_light((8, 8, 8)), flip=True),
+                b.rect(F.RT_RECT_XY, -6, 6, 0, 4, -6.0, lam)]),
+    ]
+    if with_medium:
+        refs.append(b.medium(b.sphere((-4, 1, 2), 1.0, b.dielectric(1.5)), 0.8, b.isotropic((0.3, 0.3, 0.9))))
+    refs.append(b.sphere((5, 6, -2), 0.7, b.diffuse_light((20, 18, 15))))
+    b.set_root(b.list(refs))
+    cam = rt.camera_new((9, 4, 9), (0, 1, 0), (0, 1, 0), 35.0, 56 / 40, 0.0, 12.0, 0.0, 1.0)
+    return b, b.desc(), cam
+
+
+def composite_boundary_scene(rt):
+    """A medium whose boundary is a BVH of a box and a sphere: its two boundary queries are traversals of their own."""
+    b = rt.DescBuilder()
+    glass = b.dielectric(1.5)
+    shell = b.node((-3, -3, -8), (3, 3, -2), b.box((-2, -1, -7), (0.5, 1, -4), glass), b.sphere((1.0, 0, -5), 1.5, glass))
+    fog = b.medium(shell, 0.9, b.isotropic((0.8, 0.5, 0.3)))
+    floor_ = b.rect(F.RT_RECT_XZ, -20, 20, -20, 20, -1.5, b.lambertian((0.5, 0.5, 0.5)))
+    b.set_root(b.list([fog, floor_]))
+    cam = rt.camera_new((0, 1, 4), (0, 0, -5), (0, 1, 0), 45.0, 48 / 36, 0.0, 9.0, 0.0, 1.0)
+    return b.desc(), cam
+
+
+@pytest.mark.parametrize("name", BUILDERS)
+def test_every_scene_builder_matches_the_oracle(rt, O, name):
+    s = rt.HostScene(name, seed=2022)
+    cam, _ = s.default_view(1.5)
+    got, _ = check_scene(rt, O, s.desc, cam, 3000, seed=len(name))
+    assert got["hit"].sum() > 100 and (got["hit"] == 0).sum() > 0
+
+
+def test_every_object_kind_and_composite_boundaries(rt, O):
+    _, d, cam = every_kind_scene(rt)
+    got, rays = check_scene(rt, O, d, cam, 4000, seed=5)
+    kinds = {F.ref_kind(int(p)) for p in got["prim"][got["hit"] == 1]}
+    assert {F.RT_KIND_SPHERE, F.RT_KIND_MOVING_SPHERE, F.RT_KIND_RECT, F.RT_KIND_BOX, F.RT_KIND_TRIANGLE, F.RT_KIND_RING,
+            F.RT_KIND_MEDIUM} <= kinds
+    assert np.any(got["prim"][got["hit"] == 1] & F.RT_REF_FLIP)                  # the flipped light
+    d2, cam2 = composite_boundary_scene(rt)
+    got2, _ = check_scene(rt, O, d2, cam2, 3000, seed=6)
+    assert np.any([F.ref_kind(int(p)) == F.RT_KIND_MEDIUM for p in got2["prim"][got2["hit"] == 1]])
+
+
+@pytest.mark.parametrize("name", ["cornell_smoke", "final_scene"])
+def test_media_draws_and_hits(rt, O, name):
+    """Rays through the fog (and the subsurface ball) of the final scene and the two media of cornell_smoke: per-ray draws
+    and verdicts, rays that cross a medium and miss included."""
+    s = rt.HostScene(name, seed=2022)
+    d = s.desc
+    dev = rt.DeviceScene(d)
+    g = np.random.default_rng(17)
+    cam, _ = s.default_view(1.0)
+    rays = camera_rays(rt, cam, 4000, g)
+    rays["rng_state"] = g.integers(0, 2**63, len(rays), dtype=np.uint64)
+    got, st = dev.intersect(rays, want_stats=True)
+    ref, st_ref = oracle_hits(O, d, rays)
+    assert_records_equal(got, ref)
+    assert counters(st) == counters(st_ref, ref)
+    drew = got["rng_draws"] > 0
+    in_medium = (got["hit"] == 1) & ((got["prim"] >> F.RT_REF_KIND_SHIFT) & 0xF == F.RT_KIND_MEDIUM)
+    assert drew.sum() > 100 and in_medium.sum() > 0
+    assert np.any(drew & ~in_medium)                   # crossed a medium without scattering in it
+
+
+def test_hostile_rays(rt, O):
+    _, d, _ = every_kind_scene(rt)
+    rays = []
+    for o in [(0, 1, 8), (0.0, 0.5, 0.0), (4.5, 0.5, 2.0), (-4, 1, 2), (0, 0, 0)]:
+        for dvec in [(0, 0, -1), (0, -1, 0), (1, 0, 0), (0, 0, 1), (0, 0, 0), (1e-300, 0, -1), (-0.0, -1, 0),
+                     (np.nan, 0, -1), (0, np.nan, 0), (np.inf, 0, 0), (1, 1, 1)]:
+            for t_min, t_max in [(0.001, np.inf), (5.0, 5.0), (5.0, 1.0), (-np.inf, np.inf), (np.nan, np.inf), (0.001, np.nan),
+                                 (0.0, 3.0)]:
+                rays.append((o, dvec, t_min, t_max))
+    rays += [((np.nan, 0, 0), (0, 0, -1), 0.001, np.inf), ((0, np.inf, 0), (0, -1, 0), 0.001, np.inf)]
+    q = np.concatenate([rt.query_rays(o, dv, time=0.3, t_min=a, t_max=b, rng_state=i) for i, (o, dv, a, b) in enumerate(rays)])
+    dev = rt.DeviceScene(d)
+    got, st = dev.intersect(q, want_stats=True)
+    ref, st_ref = oracle_hits(O, d, q)
+    assert_records_equal(got, ref)
+    assert counters(st) == counters(st_ref, ref)
+    assert got["hit"].sum() > 0 and (got["hit"] == 0).sum() > 0 and np.isnan(got["t"][got["hit"] == 1]).any()
+
+
+@pytest.mark.parametrize("scene,param,assets", [("wwscene", 3, True), ("random_scene", 158, False)])
+def test_big_scenes_on_the_timed_instances(rt, O, scene, param, assets):
+    """The C5 mesh (0.84 M triangles under three movers, 30-entry stacks) and the 1e5-sphere scene (a node table far
+    beyond LDS): 20 000 rays each."""
+    if assets and not os.path.isdir(ASSETS):
+        pytest.skip("assets/ not present")
+    s = rt.HostScene(scene, seed=2022, param=param, assets_dir=ASSETS if assets else None)
+    d = s.desc
+    dev = rt.DeviceScene(d)
+    assert d.n_nodes > 100_000
+    cam, _ = s.default_view(1.5)
+    g = np.random.default_rng(param)
+    first = camera_rays(rt, cam, 12_000, g)
+    h0 = dev.intersect(first)
+    rays = np.concatenate([first, bounce_rays(rt, h0, g, 8_000)])
+    rays = np.concatenate([rays, camera_rays(rt, cam, 20_000 - len(rays), g)]) if len(rays) < 20_000 else rays
+    got, st = dev.intersect(rays, want_stats=True)
+    ref, st_ref = oracle_hits(O, d, rays)
+    assert_records_equal(got, ref)
+    assert counters(st) == counters(st_ref, ref)
+    assert_prims_consistent(d, got)
+    assert np.array_equal(dev.intersect(rays).view(np.uint8), got.view(np.uint8))
+
+
+def test_device_variant_on_torch_buffers(rt, O):
+    import torch
+    s = rt.HostScene("cornell_box", seed=2022)
+    dev = rt.DeviceScene(s.desc)
+    cam, _ = s.default_view(1.0)
+    g = np.random.default_rng(3)
+    stream = torch.cuda.Stream()
+    for n in (0, 1, 63, 65, 1_000_003):
+        rays = camera_rays(rt, cam, n, g) if n else np.zeros(0, dtype=rt.QUERY_RAY_DTYPE)
+        if n:
+            rays["rng_state"] = g.integers(0, 2**63, n, dtype=np.uint64)
+        host = dev.intersect(rays)
+        d_rays = torch.from_numpy(rays.view(np.uint8)).cuda()
+        d_hits = torch.full((max(n, 1) * 96,), 0xAB, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        dev.intersect_device(d_rays.data_ptr(), n, d_hits.data_ptr(), stream.cuda_stream)        # stats=None: no sync
+        stream.synchronize()
+        out = d_hits.cpu().numpy()[: n * 96].view(rt.HIT_DTYPE)
+        assert np.array_equal(out.view(np.uint8), host.view(np.uint8)), n
+        if n == 0:
+            assert np.all(d_hits.cpu().numpy() == 0xAB)                                         # nothing launched
+        if 0 < n < 100:
+            ref, _ = oracle_hits(O, s.desc, rays)
+            assert_records_equal(out, ref, n)
+    st = F.rt_stats()
+    dev.intersect_device(d_rays.data_ptr(), n, d_hits.data_ptr(), stream.cuda_stream, stats=st)
+    assert st.rays == n and st.node_visits > n and st.ms > 0
+
+
+def test_queries_beside_an_asynchronous_render(rt, O):
+    import torch
+    s = rt.HostScene("final_scene", seed=2022)
+    W, H, spp = 64, 48, 4
+    cam, bg = s.default_view(W / H)
+    rows = rt.shuffled_rows(H, 3)
+    p = rt.make_params(W, H, spp, 50, bg, seed=2022, spp_chunk=1)
+    dev = rt.DeviceScene(s.desc)
+    ref_render = dev.render(cam, p, rows)
+    g = np.random.default_rng(9)
+    batches = [camera_rays(rt, cam, 30_000, g) for _ in range(3)]
+    for b_ in batches:
+        b_["rng_state"] = g.integers(0, 2**63, len(b_), dtype=np.uint64)
+    serial = [dev.intersect(b_) for b_ in batches]
+    a_stream, b_stream = torch.cuda.Stream(), torch.cuda.Stream()
+    d_rows = torch.from_numpy(rows.view(np.int32)).cuda()
+    out = torch.full((H, W, 3), float("nan"), dtype=torch.float64, device="cuda")
+    d_rays = [torch.from_numpy(b_.view(np.uint8)).cuda() for b_ in batches]
+    d_hits = [torch.zeros(len(b_) * 96, dtype=torch.uint8, device="cuda") for b_ in batches]
+    torch.cuda.synchronize()
+    dev.render_device(cam, p, d_rows.data_ptr(), H, out.data_ptr(), a_stream.cuda_stream, None, asynchronous=True)
+    for r_, h_, b_ in zip(d_rays, d_hits, batches):
+        dev.intersect_device(r_.data_ptr(), len(b_), h_.data_ptr(), b_stream.cuda_stream)
+    b_stream.synchronize()
+    dev.wait(a_stream.cuda_stream)
+    assert np.array_equal(out.cpu().numpy().view(np.uint64), ref_render.view(np.uint64))
+    for h_, want in zip(d_hits, serial):
+        assert np.array_equal(h_.cpu().numpy(), want.view(np.uint8))
+
+
+@pytest.mark.parametrize("name", ["random_scene", "cornell_box", "every_kind", "wwscene"])
+def test_any_hit(rt, O, name):
+    if name == "every_kind":
+        _, d, cam = every_kind_scene(rt, with_medium=False)
+    else:
+        s = rt.HostScene(name, seed=2022)
+        d = s.desc
+        cam, _ = s.default_view(1.5)
+    assert d.n_media == 0
+    dev = rt.DeviceScene(d)
+    first, g = mixed_rays(rt, d, cam, 6000, seed=21)
+    rays = np.concatenate([first, bounce_rays(rt, dev.intersect(first), g, 2000)])
+    closest, st_c = dev.intersect(rays, want_stats=True)
+    anyh, st_a = dev.intersect(rays, any_hit=True, want_stats=True)
+    assert np.array_equal(anyh["hit"], closest["hit"])
+    h = closest["hit"] == 1
+    assert h.sum() > 100
+    assert np.all(anyh["t"][h] >= closest["t"][h]) and np.all(anyh["t"][h] < rays["t_max"][h])
+    assert_prims_consistent(d, anyh)
+    assert np.all(anyh["prim"][~h] == F.RT_REF_NONE)
+    assert st_a.node_visits <= st_c.node_visits
+    if name == "random_scene":
+        assert st_a.node_visits < st_c.node_visits and np.any(anyh["t"][h] > closest["t"][h])
+    # the plain instance agrees with the counter instance
+    assert np.array_equal(dev.intersect(rays, any_hit=True).view(np.uint8), anyh.view(np.uint8))
+    # a scene with a ConstantMedium refuses it
+    smoke = rt.DeviceScene(rt.HostScene("cornell_smoke", seed=2022).desc)
+    with pytest.raises(rt.RtError) as e:
+        smoke.intersect(rays[:10], any_hit=True)
+    assert e.value.code == F.RT_ERR_UNSUPPORTED and "ConstantMedium" in str(e.value)
+
+
+def test_argument_errors(rt):
+    s = rt.HostScene("cornell_box", seed=2022)
+    dev = rt.DeviceScene(s.desc)
+    L = rt.lib()
+    rays = rt.query_rays((278, 278, -800), (0, 0, 1))
+    hits = np.zeros(1, dtype=rt.HIT_DTYPE)
+    assert L.rt_intersect(dev._h, None, 1, 0, hits.ctypes.data, None) == F.RT_ERR_INVALID
+    assert "null ray or hit buffer" in L.rt_last_error().decode()
+    assert L.rt_intersect(dev._h, rays.ctypes.data, 1, 0, None, None) == F.RT_ERR_INVALID
+    for bad in (F.RT_FLAG_ASYNC, F.RT_FLAG_KERNEL_TIMES, 0x100):
+        assert L.rt_intersect(dev._h, rays.ctypes.data, 1, bad, hits.ctypes.data, None) == F.RT_ERR_INVALID
+        assert "unknown flag" in L.rt_last_error().decode()
+    assert L.rt_intersect_device(dev._h, None, 5, 0, None, None, None) == F.RT_ERR_INVALID
+    import torch
+    buf = torch.zeros(200 * 96, dtype=torch.uint8, device="cuda")
+    assert L.rt_intersect_device(dev._h, buf.data_ptr() + 8, 1, 0, buf.data_ptr() + 4096, None, None) == F.RT_ERR_INVALID
+    assert "aligned" in L.rt_last_error().decode()
+    st = F.rt_stats()
+    st.rays = 77
+    assert L.rt_intersect(dev._h, None, 0, 0, None, C.byref(st)) == F.RT_OK and st.rays == 0
+    assert dev.intersect(rays)["hit"][0] == 1                                     # the scene is still fine
