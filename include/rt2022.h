@@ -419,6 +419,69 @@ int rt_intersect(rt_scene *scene, const rt_query_ray *rays, uint64_t n_rays, uin
 int rt_intersect_device(rt_scene *scene, const rt_query_ray *d_rays, uint64_t n_rays, uint32_t flags,
                         rt_hit *d_out_hits, void *hip_stream, rt_stats *stats);
 
+/* ---- path-traced radiance of caller rays ----------------------------------------------------------
+ * `ray_color(r, background, world, lights, depth)` (main.rs:233-278) for rays the caller chooses instead of the camera's:
+ * other cameras (panoramas, orthographic, stereo), light probes and irradiance baking, progressive or adaptive sampling,
+ * integrators built on rt_intersect. The work runs in the render's own wavefront engine: the only difference is where a
+ * new path's first ray comes from.
+ *
+ * Result, per ray i: out_rgb_sum[3i .. 3i+3) = 0 + L_0 + L_1 + ... + L_{spp-1}, added in sample order, where
+ * L_s = ray_color(ray_i, background, t_min, max_depth) drawing from Rng(path_key(ray_i.rng_state, 0, 0, s)) — the render's
+ * keying (rt_math.h) with the ray's rng_state in place of the seed. Not divided by spp, like a render's sums:
+ * rt_tonemap_device / rt_write_color apply as they are. So it is the CPU oracle's rto_ray_color(desc, ray, background,
+ * t_min, max_depth, rto_path_key(rng_state, 0, 0, s)) summed over s, bit for bit, on every scene rt_scene_create accepts
+ * (lights or the n_lights == 0 cosine mode, media, movers, moving spheres at the ray's time, every texture kind), and
+ * for rays no camera makes: zero direction components, a zero direction, +-inf or NaN components, origins inside a medium's
+ * boundary or a dielectric (NaN comes out where the oracle's does). Ray contents are never validated. A ray's result does
+ * not depend on the order of the rays or on the size of the batch.
+ *
+ * rt_stats (may be NULL): paths = n_rays * spp; with RT_FLAG_COUNTERS rays, node_visits, prim_tests[], light_pdf_tests and
+ * rng_draws are the sums of the oracle's counters over the same samples (no camera draws are involved; 0 otherwise); ms,
+ * passes, pool_slots, partial_bytes and (RT_FLAG_KERNEL_TIMES) trace_ms / shade_ms mean what they mean for a render;
+ * spp_chunk is 1 (one sample per work item, always).
+ *
+ * Arguments: n_rays == 0, spp == 0 and max_depth == 0 are RT_OK (the last two write zeros, with no kernel of the engine).
+ * RT_ERR_INVALID with rt_last_error() set, before anything reaches the device: a null scene or params; a null ray or
+ * output buffer with n_rays > 0; a flag bit other than RT_FLAG_COUNTERS / RT_FLAG_KERNEL_TIMES (RT_FLAG_ASYNC and
+ * RT_FLAG_ANY_HIT included); a device buffer of rt_radiance_device that is not 16-byte aligned; n_rays > RT_RADIANCE_MAX_RAYS
+ * (a path slot keeps its ray's index in a 32-bit field) or n_rays * spp > RT_RADIANCE_MAX_ITEMS = 2^58 (the partial sums take
+ * 24 B per work item and their byte counts must fit 64 bits with a margin, as must the engine's work item numbering with
+ * the work counter's overshoot). Within the limits, a call whose planes do not fit the device takes the ring of planes or
+ * fails with RT_ERR_DEVICE; it never writes outside what it allocated. A scene switched to the A/B megakernel engine
+ * (rt_debug_set_engine) is RT_ERR_UNSUPPORTED. There is no rt_scene_set form, no progress callback and no RT_FLAG_ASYNC.
+ *
+ * Workspace: the call runs in the render's per-(scene, stream) workspace (path pool, partial-sum planes — the ring of
+ * planes included, under the same threshold — and tape) and behaves on its stream like one more rt_render_device: an
+ * RT_FLAG_ASYNC render in flight on the same (scene, stream) is joined and finished first (its stats filled, as
+ * rt_render_wait would), and renders after it keep their results bit for bit. rt_radiance_device synchronises hip_stream
+ * before it returns and fills stats itself. rt_radiance stages the rays and sums through device buffers the workspace
+ * keeps, on the default stream. The call makes the scene's device current and restores the caller's. */
+typedef struct rt_radiance_ray {      /* 64 B: the engine's own ray record {ox, oy, oz, dx, dy, dz, tm, rng} */
+    double   origin[3];
+    double   direction[3];
+    double   time;                    /* Ray::tm (moving spheres) */
+    uint64_t rng_state;               /* keys the ray's sample streams: path_key(rng_state, 0, 0, sample) */
+} rt_radiance_ray;
+
+typedef struct rt_radiance_params {   /* 48 B */
+    double   background[3];
+    double   t_min;                   /* 0.001 in main.rs:243, for every bounce */
+    uint32_t max_depth;               /* ray_color's depth */
+    uint32_t spp;                     /* samples per ray; 0 = zeros */
+    uint32_t flags;                   /* RT_FLAG_COUNTERS | RT_FLAG_KERNEL_TIMES only */
+    uint32_t _pad;
+} rt_radiance_params;
+
+#define RT_RADIANCE_MAX_RAYS  0xFFFFFFFFull          /* n_rays limit */
+#define RT_RADIANCE_MAX_ITEMS (1ull << 58)           /* n_rays * spp limit: 24 B of partial sums per item, in 64-bit byte counts */
+
+/* Host buffers (n_rays records in, 3 * n_rays sums out); synchronous. stats may be NULL. */
+int rt_radiance(rt_scene *scene, const rt_radiance_ray *rays, uint64_t n_rays, const rt_radiance_params *p,
+                double *out_rgb_sum, rt_stats *stats);
+/* Device buffers, 16-byte aligned, enqueued on hip_stream (NULL = default stream); returns once the call is complete. */
+int rt_radiance_device(rt_scene *scene, const rt_radiance_ray *d_rays, uint64_t n_rays, const rt_radiance_params *p,
+                       double *d_out_rgb_sum, void *hip_stream, rt_stats *stats);
+
 /* write_color (main.rs:280-299): NaN→0, sqrt(c/spp), clamp [0,0.999], *255.999, floor. */
 void rt_write_color(const double rgb_sum[3], int32_t spp, uint8_t out_rgb[3]);
 /* Device form over n_pixels sums → n_pixels*3 bytes, on hip_stream. */

@@ -60,6 +60,8 @@ int rtb_image_load(const char *path, uint32_t *width, uint32_t *height, uint8_t 
 const char *rtb_last_error(void);
 /* sizeof of each ABI structure (binding layout check); returns how many there are. */
 int rtb_abi_sizes(uint32_t *out, uint32_t n);
+/* The same for the rt_radiance* structures: {rt_radiance_ray, rt_radiance_params}; returns 2. */
+int rtb_radiance_abi_sizes(uint32_t *out, uint32_t n);
 
 #ifdef __cplusplus
 }

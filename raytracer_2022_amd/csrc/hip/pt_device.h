@@ -106,6 +106,10 @@ struct RenderArgs {
     uint32_t node_quorum;              // lanes that must want a node step for the fast path (1..64)
     uint32_t vote_weights;             // 4 bits per operation label: the vote picks max(lanes * weight)
     StatsDev *stats;                   // may be null
+    // rt_radiance* (device, null for a render): the caller's rays take the place of the camera. The "pixels" are the
+    // rays (n_pixels = n_rays, width = 1, no row ids), one sample per work item, the path of sample s of ray i keyed
+    // path_key(rays[i].rng_state, 0, 0, s); wf_shade's rays instances read them in its fresh-path sweep.
+    const rt_radiance_ray *rays;
 };
 
 // ---- wavefront engine (pt_wavefront.hip) -------------------------------------------

@@ -311,7 +311,9 @@ RT_DEV Vec3 texture_value_top(const SceneDev &s, uint32_t tex, uint32_t tex_kind
 #endif
 // RING: the partial-sum ring of RenderArgs::ring is in use (a build of its own: the default instance carries none of its
 // bookkeeping — bounded claims, starved slots, the oldest item in flight).
-template <bool STATS, bool RING = false>
+// RAYS: a new path's first ray is the caller's (RenderArgs::rays, rt_radiance*) instead of the camera's: "pixel" = ray index,
+// no row ids, no camera draws. Everything else — the first sweep, the unwinding, the planes and the ring — is the render's.
+template <bool STATS, bool RING = false, bool RAYS = false>
 __global__ void __launch_bounds__(kBlock, RT2022_SHADE_WAVES) wf_shade(const SceneDev s, const RenderArgs *__restrict__ ap, const WfPool pool, const uint32_t parity) {
     __shared__ uint32_t hist[SK_COUNT];
     __shared__ uint32_t cursor[SK_COUNT];
@@ -676,13 +678,17 @@ __global__ void __launch_bounds__(kBlock, RT2022_SHADE_WAVES) wf_shade(const Sce
                                 yi = pix_slot / a.width;
                                 px = (uint32_t)(pix_slot - yi * a.width);
                             }
-                            uint32_t g = a.row_ids[yi];
-                            uint32_t frame = g / a.height;
-                            uint32_t py = g - frame * a.height;
                             smp = chunk_id * a.chunk;
                             smp_end = smp + a.chunk < a.spp ? smp + a.chunk : a.spp;
                             stt.item = (uint64_t)(RING ? chunk_id % a.ring : chunk_id) * a.n_pixels + pix_slot;     // (kept as the item's place in the partial sums: ring mode, plane = sample mod R)
-                            stt.px = px; stt.py = py; stt.frame = frame;
+                            if constexpr (RAYS) {                       // (width 1: pix_slot is the ray; n_rays < 2^32, checked by the host)
+                                stt.px = (uint32_t)pix_slot; stt.py = 0; stt.frame = 0;
+                            } else {
+                                uint32_t g = a.row_ids[yi];
+                                uint32_t frame = g / a.height;
+                                uint32_t py = g - frame * a.height;
+                                stt.px = px; stt.py = py; stt.frame = frame;
+                            }
                             if (!single) {
                                 double2 *ps = reinterpret_cast<double2 *>(pool.pixel_sum + (uint64_t)slot * 4);
                                 ps[0] = make_double2(0.0, 0.0);
@@ -694,19 +700,29 @@ __global__ void __launch_bounds__(kBlock, RT2022_SHADE_WAVES) wf_shade(const Sce
                 }
                 if (!have_item) break;                                // no work left: the slot goes idle
                 if (smp == smp_end) continue;                         // empty chunk (spp == 0): store zeros next turn
-                uint32_t px = stt.px, py = stt.py, frame = stt.frame;
-                uint64_t pixel = (uint64_t)py * a.width + px;
-                rng = Rng(rtm::path_key(a.seed, frame, pixel, smp));  // main.rs:144-149
-                double rand_u = rng.gen_f64();
-                double rand_v = rng.gen_f64();
-                double u = ((double)px + rand_u) / (double)(a.width - 1);
-                double v = ((double)py + rand_v) / (double)(a.height - 1);
-                r = get_ray(a.cam, u, v, rng);
-                depth = a.max_depth;
-                smp++;
-                cnt.path();
-                cnt.draws(rng.draws);                                 // words drawn while aiming the camera ray
-                rng.draws = 0;
+                if constexpr (RAYS) {                                 // the caller's ray record, the engine's own layout: four 16-byte loads
+                    const double2 *q = reinterpret_cast<const double2 *>(a.rays + stt.px);
+                    const double2 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
+                    r = Ray(Vec3(q0.x, q0.y, q1.x), Vec3(q1.y, q2.x, q2.y), q3.x);
+                    rng = Rng(rtm::path_key(rtm::d2u(q3.y), 0u, 0ull, smp));
+                    depth = a.max_depth;
+                    smp++;
+                    cnt.path();
+                } else {
+                    uint32_t px = stt.px, py = stt.py, frame = stt.frame;
+                    uint64_t pixel = (uint64_t)py * a.width + px;
+                    rng = Rng(rtm::path_key(a.seed, frame, pixel, smp));  // main.rs:144-149
+                    double rand_u = rng.gen_f64();
+                    double rand_v = rng.gen_f64();
+                    double u = ((double)px + rand_u) / (double)(a.width - 1);
+                    double v = ((double)py + rand_v) / (double)(a.height - 1);
+                    r = get_ray(a.cam, u, v, rng);
+                    depth = a.max_depth;
+                    smp++;
+                    cnt.path();
+                    cnt.draws(rng.draws);                             // words drawn while aiming the camera ray
+                    rng.draws = 0;
+                }
                 if (depth == 0) continue;                             // MAX_DEPTH == 0: black at once
                 alive = true;
                 break;
@@ -2030,10 +2046,14 @@ struct WfLaunch {
     uint32_t blocks;            // segments of the group
     hipStream_t stream;
     bool ring = false;          // RenderArgs::ring in use: the shade pass's ring build
+    bool rays = false;          // RenderArgs::rays in use: the shade pass's caller-ray build (rt_radiance*)
 };
 template <bool STATS>
 static void launch_shade(const WfLaunch &w, uint32_t parity) {
-    if (w.ring) hipLaunchKernelGGL((wf_shade<STATS, true>), dim3(w.blocks), dim3(kBlock), 0, w.stream, w.scene, w.d_args, w.pool, parity);
+    if (w.rays) {
+        if (w.ring) hipLaunchKernelGGL((wf_shade<STATS, true, true>), dim3(w.blocks), dim3(kBlock), 0, w.stream, w.scene, w.d_args, w.pool, parity);
+        else hipLaunchKernelGGL((wf_shade<STATS, false, true>), dim3(w.blocks), dim3(kBlock), 0, w.stream, w.scene, w.d_args, w.pool, parity);
+    } else if (w.ring) hipLaunchKernelGGL((wf_shade<STATS, true>), dim3(w.blocks), dim3(kBlock), 0, w.stream, w.scene, w.d_args, w.pool, parity);
     else hipLaunchKernelGGL((wf_shade<STATS, false>), dim3(w.blocks), dim3(kBlock), 0, w.stream, w.scene, w.d_args, w.pool, parity);
 }
 // Ring mode: out[i] = (first plane of the frame ? 0 : out[i]) + partial[first mod R][i] + ... in sample order — pixel_color += ...,
@@ -2236,7 +2256,8 @@ static hipError_t render_passes(const SceneDev &scene, const RenderArgs &args, c
         v.n_active = pool.n_active + 2 * g;
         v.next_chunk = pool.next_chunk + g;
         v.max_list = pool.max_list + 2 * g;
-        w[g] = WfLaunch{scene, v, d_args, args.t_min, args.node_quorum, args.vote_weights, args.stats, n_segs, G == 1 ? stream : gs.stream[g], ringed};
+        w[g] = WfLaunch{scene, v, d_args, args.t_min, args.node_quorum, args.vote_weights, args.stats, n_segs, G == 1 ? stream : gs.stream[g], ringed,
+                        args.rays != nullptr};
     }
     if (G > 1) {                                // the groups start after what the caller's stream holds so far
         if ((e = hipEventRecord(gs.ev[0][0], stream)) != hipSuccess) return e;

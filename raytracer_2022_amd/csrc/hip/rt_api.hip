@@ -298,6 +298,10 @@ struct Workspace {
     uint32_t *h_rows_max = nullptr;   // ... and the pinned word it is copied to
     unsigned long long *d_limit = nullptr;   // ring mode: RenderArgs::claim_limit
     uint64_t used_partial_bytes = 0;
+    // rt_radiance (host buffers): the device copies of the caller's rays and of the sums, grown as needed
+    rt_radiance_ray *rad_rays = nullptr;
+    double *rad_out = nullptr;
+    uint64_t rad_cap = 0;             // rays both buffers hold
     // RT_FLAG_ASYNC: the host thread that drives the passes of the call in flight on this (scene, stream), and what it ended with
     // (read by rt_render_wait after the join).
     std::thread async_worker;
@@ -450,9 +454,19 @@ void end_check_device_rows(Workspace &w, const rt_params *p) {      // (after a 
     RT_REQUIRE((uint64_t)*w.h_rows_max < (uint64_t)p->height * p->n_frames, RT_ERR_INVALID, "rt_render_device: row id out of range");
 }
 
-// Enqueue one render on `stream`; row ids and output are device pointers.
+// Where the paths of an rt_radiance* call start: the caller's rays (device) instead of the camera's rows.
+struct RaySource {
+    const rt_radiance_ray *d_rays;
+    uint64_t n_rays;
+};
+static_assert(sizeof(rt_radiance_ray) == 64 && offsetof(rt_radiance_ray, time) == 48 && offsetof(rt_radiance_ray, rng_state) == 56,
+              "rt_radiance_ray is the path slot's ray record {ox, oy, oz, dx, dy, dz, tm, rng}: wf_shade reads it in four 16-byte pieces");
+
+// Enqueue one render on `stream`; row ids and output are device pointers. With `src` the call is an rt_radiance*: its
+// "pixels" are the rays of src (p: width 1, no rows, spp_chunk 1; cam unused).
 void enqueue(rt_scene *sc, const rt_camera *cam, const rt_params *p, const uint32_t *d_rows, double *d_out,
-             hipStream_t stream, rt_stats *stats, bool check_rows = false /* the row ids came from the caller's HBM: range-check them */) {
+             hipStream_t stream, rt_stats *stats, bool check_rows = false /* the row ids came from the caller's HBM: range-check them */,
+             const RaySource *src = nullptr) {
     Workspace &w = workspace_for(sc, stream);
     RenderArgs a{};
     a.cam = *cam;
@@ -466,9 +480,14 @@ void enqueue(rt_scene *sc, const rt_camera *cam, const rt_params *p, const uint3
     a.t_min = p->t_min;
     std::memcpy(a.split, sc->split, sizeof a.split);
     a.seed = p->seed;
-    a.n_pixels = (uint64_t)p->n_rows * p->width;
+    a.n_pixels = src ? src->n_rays : (uint64_t)p->n_rows * p->width;
     a.n_items = a.n_pixels * a.n_chunks;
+    // The partial sums' byte counts below (24 B per work item) must not wrap: a wrapped size would allocate too little and the
+    // shade pass would write past it. (rt_radiance*'s own limit, RT_RADIANCE_MAX_ITEMS, keeps its calls far below this.)
+    RT_REQUIRE(a.n_pixels == 0 || (a.n_items / a.n_pixels == a.n_chunks && a.n_items <= (~0ull >> 1) / (3 * sizeof(double))),
+               RT_ERR_INVALID, "work items of the call overflow the partial sums' 64-bit byte counts");
     a.row_ids = d_rows;
+    a.rays = src ? src->d_rays : nullptr;
     bool counters = stats && (p->flags & RT_FLAG_COUNTERS);
     const bool want_kt = stats && (p->flags & RT_FLAG_KERNEL_TIMES) && sc->engine == 1;
     // Ring of partial-sum planes (pt_device.h, RenderArgs::ring): one-sample work items of the wavefront engine only. Automatic
@@ -701,6 +720,24 @@ void run_query(rt_scene *sc, const rt_query_ray *d_rays, uint64_t n_rays, uint32
     *stats = out;
 }
 
+// The arguments of rt_radiance* (host side only, before the scene is looked at: the scene comes last so that a bad argument
+// is reported as such whatever the scene). `device`: the buffers are rt_radiance_device's, read and written in 16-byte pieces.
+void check_radiance(const rt_scene *scene, const void *rays, uint64_t n_rays, const rt_radiance_params *p, const void *out,
+                    bool device, const char *who) {
+    const std::string w(who);
+    RT_REQUIRE(p, RT_ERR_INVALID, w + ": null params");
+    RT_REQUIRE(!(p->flags & ~(RT_FLAG_COUNTERS | RT_FLAG_KERNEL_TIMES)), RT_ERR_INVALID,
+               w + ": flag bits other than RT_FLAG_COUNTERS / RT_FLAG_KERNEL_TIMES");
+    RT_REQUIRE(n_rays == 0 || (rays && out), RT_ERR_INVALID, w + ": null ray or output buffer");
+    RT_REQUIRE(!device || n_rays == 0 || !(((uintptr_t)rays | (uintptr_t)out) & 15u), RT_ERR_INVALID,
+               w + ": ray and output buffers must be 16-byte aligned");
+    RT_REQUIRE(n_rays <= RT_RADIANCE_MAX_RAYS, RT_ERR_INVALID, w + ": n_rays > RT_RADIANCE_MAX_RAYS");
+    // (a division, not a product: n_rays * spp itself may not fit 64 bits)
+    RT_REQUIRE(p->spp == 0 || n_rays <= RT_RADIANCE_MAX_ITEMS / p->spp, RT_ERR_INVALID, w + ": n_rays * spp > RT_RADIANCE_MAX_ITEMS");
+    RT_REQUIRE(scene, RT_ERR_INVALID, w + ": null scene");
+    RT_REQUIRE(scene->engine == 1, RT_ERR_UNSUPPORTED, w + ": only the wavefront engine traces caller rays (rt_debug_set_engine)");
+}
+
 void finish(rt_scene *sc, hipStream_t stream) {
     Workspace &w = workspace_for(sc, stream);
     RT_HIP(hipStreamSynchronize(stream));
@@ -917,6 +954,8 @@ int rt_scene_destroy(rt_scene *scene) {
             if (w.gs.h_work) (void)hipHostFree(w.gs.h_work);
             if (w.gs.h_oldest) (void)hipHostFree(w.gs.h_oldest);
             if (w.d_limit) (void)hipFree(w.d_limit);
+            if (w.rad_rays) (void)hipFree(w.rad_rays);
+            if (w.rad_out) (void)hipFree(w.rad_out);
             for (int g = 0; g < kMaxGroups; g++) {
                 if (w.gs.stream[g]) (void)hipStreamDestroy(w.gs.stream[g]);
                 for (int b = 0; b < 2; b++) if (w.gs.ev[g][b]) (void)hipEventDestroy(w.gs.ev[g][b]);
@@ -995,6 +1034,85 @@ int rt_render_wait(rt_scene *scene, void *hip_stream) {
         const int rc = join_async(scene, (hipStream_t)hip_stream, &err);
         RT_REQUIRE(rc == RT_OK, rc, err);
         finish(scene, (hipStream_t)hip_stream);
+        return RT_OK;
+    });
+}
+
+// An rt_radiance* call runs in the render's workspace of (scene, stream): an asynchronous render still in flight there (its host
+// thread drives passes on that workspace) is joined and finished first, as rt_render_device does. Each entry point calls this
+// once, before it touches the workspace in any way — rt_radiance before its staging buffers, which live in the workspace too.
+static void join_before_radiance(rt_scene *sc, hipStream_t stream, const char *who) {
+    std::string err;
+    bool joined = false;
+    const int rc = join_async(sc, stream, &err, &joined);
+    RT_REQUIRE(rc == RT_OK, rc, std::string(who) + ": the previous asynchronous call on this stream failed: " + err);
+    if (joined) finish(sc, stream);
+}
+
+// One rt_radiance* call on `stream` (the scene's device is current, the arguments checked, join_before_radiance done): the
+// passes, and stats.
+static void run_radiance(rt_scene *sc, const rt_radiance_ray *d_rays, uint64_t n_rays, const rt_radiance_params *rp, double *d_out,
+                         hipStream_t stream, rt_stats *stats) {
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (n_rays == 0) {
+        if (stats) stats->spp_chunk = 1;
+        return;
+    }
+    if (rp->spp == 0 || rp->max_depth == 0) {                 // ray_color at depth 0 is black, no sample is black: zeros, no pass
+        RT_HIP(hipMemsetAsync(d_out, 0, n_rays * 3 * sizeof(double), stream));
+        RT_HIP(hipStreamSynchronize(stream));
+        if (stats) { stats->paths = n_rays * rp->spp; stats->spp_chunk = 1; }
+        return;
+    }
+    rt_camera cam;
+    std::memset(&cam, 0, sizeof cam);
+    rt_params p;
+    std::memset(&p, 0, sizeof p);
+    p.width = 1; p.height = 1; p.n_frames = 1;                 // (one "pixel" per ray: RenderArgs::rays)
+    p.spp = rp->spp; p.max_depth = rp->max_depth;
+    std::memcpy(p.background, rp->background, sizeof p.background);
+    p.t_min = rp->t_min;
+    p.spp_chunk = 1;                                           // one sample per work item: the sum is 0 + L_0 + L_1 + ... in order
+    p.flags = rp->flags;
+    const RaySource src{d_rays, n_rays};
+    enqueue(sc, &cam, &p, nullptr, d_out, stream, stats, false, &src);
+    finish(sc, stream);
+    if (stats) stats->paths = n_rays * rp->spp;               // (the counter block's own count, also without RT_FLAG_COUNTERS)
+}
+
+int rt_radiance(rt_scene *scene, const rt_radiance_ray *rays, uint64_t n_rays, const rt_radiance_params *p, double *out_rgb_sum,
+                rt_stats *stats) {
+    return guarded([&]() -> int {
+        check_radiance(scene, rays, n_rays, p, out_rgb_sum, false, "rt_radiance");
+        DeviceGuard guard(scene->device);
+        join_before_radiance(scene, nullptr, "rt_radiance");       // (first: the staging buffers below belong to the workspace)
+        Workspace &w = workspace_for(scene, nullptr);
+        if (n_rays > w.rad_cap) {                              // staging buffers of the workspace, kept for the next call
+            if (w.rad_rays) RT_HIP(hipFree(w.rad_rays));        // (the calls that used them were synchronous: nothing is in flight)
+            if (w.rad_out) RT_HIP(hipFree(w.rad_out));
+            w.rad_rays = nullptr; w.rad_out = nullptr; w.rad_cap = 0;
+            RT_HIP(hipMalloc((void **)&w.rad_rays, n_rays * sizeof(rt_radiance_ray)));
+            RT_HIP(hipMalloc((void **)&w.rad_out, n_rays * 3 * sizeof(double)));
+            w.rad_cap = n_rays;
+        }
+        if (n_rays) {
+            RT_HIP(hipMemcpy(w.rad_rays, rays, n_rays * sizeof(rt_radiance_ray), hipMemcpyHostToDevice));
+            // Poison the output so an unwritten sum cannot pass for a result.
+            RT_HIP(hipMemset(w.rad_out, 0xFF, n_rays * 3 * sizeof(double)));
+        }
+        run_radiance(scene, w.rad_rays, n_rays, p, w.rad_out, nullptr, stats);
+        if (n_rays) RT_HIP(hipMemcpy(out_rgb_sum, w.rad_out, n_rays * 3 * sizeof(double), hipMemcpyDeviceToHost));
+        return RT_OK;
+    });
+}
+
+int rt_radiance_device(rt_scene *scene, const rt_radiance_ray *d_rays, uint64_t n_rays, const rt_radiance_params *p,
+                       double *d_out_rgb_sum, void *hip_stream, rt_stats *stats) {
+    return guarded([&]() -> int {
+        check_radiance(scene, d_rays, n_rays, p, d_out_rgb_sum, true, "rt_radiance_device");
+        DeviceGuard guard(scene->device);
+        join_before_radiance(scene, (hipStream_t)hip_stream, "rt_radiance_device");
+        run_radiance(scene, d_rays, n_rays, p, d_out_rgb_sum, (hipStream_t)hip_stream, stats);
         return RT_OK;
     });
 }

@@ -27,6 +27,32 @@ def query_rays(origins, directions, time=0.0, t_min=0.001, t_max=np.inf, rng_sta
     return rays
 
 
+def radiance_rays(origins, directions, time=0.0, rng_state=None):
+    """An array of RADIANCE_RAY_DTYPE records (rt_radiance_ray) for rt_radiance: `origins` / `directions` are (n, 3) or (3,),
+    `time` and `rng_state` arrays of n or scalars, all broadcast to n rays. rng_state=None gives ray i the state i (its samples
+    draw from path_key(i, 0, 0, s))."""
+    o = np.asarray(origins, dtype=np.float64)
+    d = np.asarray(directions, dtype=np.float64)
+    if o.shape[-1:] != (3,) or d.shape[-1:] != (3,) or o.ndim > 2 or d.ndim > 2:
+        raise ValueError("origins and directions must be (n, 3) or (3,)")
+    n = np.broadcast_shapes(o.shape[:-1], d.shape[:-1], np.shape(time), np.shape(rng_state) if rng_state is not None else ())
+    n = n[0] if n else 1
+    rays = np.zeros(n, dtype=F.RADIANCE_RAY_DTYPE)
+    rays["origin"] = np.broadcast_to(o, (n, 3))
+    rays["direction"] = np.broadcast_to(d, (n, 3))
+    rays["time"] = np.broadcast_to(np.asarray(time, dtype=np.float64), (n,))
+    rays["rng_state"] = np.arange(n, dtype=np.uint64) if rng_state is None else np.broadcast_to(np.asarray(rng_state, dtype=np.uint64), (n,))
+    return rays
+
+
+def radiance_params(spp=1, background=(0.0, 0.0, 0.0), t_min=0.001, max_depth=50, flags=0):
+    """rt_radiance_params: samples per ray, ray_color's background, t_min (main.rs:243) and depth, RT_FLAG_* bits."""
+    p = F.rt_radiance_params()
+    p.background[:] = [float(c) for c in background]
+    p.t_min, p.max_depth, p.spp, p.flags = t_min, max_depth, spp, flags
+    return p
+
+
 class DeviceScene:
     """rt_scene: the flattened scene copied into HBM on the current HIP device."""
 
@@ -121,6 +147,25 @@ class DeviceScene:
             flags |= F.RT_FLAG_COUNTERS
         F.check(F.lib().rt_intersect_device(self._h, C.c_void_p(d_rays_ptr), n, flags, C.c_void_p(d_hits_ptr),
                                             C.c_void_p(stream_ptr or 0), C.byref(stats) if stats is not None else None))
+
+    def radiance(self, rays, spp=1, background=(0.0, 0.0, 0.0), t_min=0.001, max_depth=50, want_stats=False, kernel_times=False):
+        """rt_radiance: the sum over spp samples of ray_color for every ray of `rays` (RADIANCE_RAY_DTYPE, see radiance_rays)
+        → (n, 3) float64 sums, not divided by spp [, rt_stats with the counters]."""
+        r = np.ascontiguousarray(rays, dtype=F.RADIANCE_RAY_DTYPE)
+        out = np.zeros((len(r), 3), dtype=np.float64)
+        flags = (F.RT_FLAG_COUNTERS if want_stats else 0) | (F.RT_FLAG_KERNEL_TIMES if kernel_times else 0)
+        p = radiance_params(spp, background, t_min, max_depth, flags)
+        st = F.rt_stats()
+        F.check(F.lib().rt_radiance(self._h, r.ctypes.data if len(r) else None, len(r), C.byref(p), out.ctypes.data if len(r) else None,
+                                    C.byref(st)))
+        return (out, st) if want_stats else out
+
+    def radiance_device(self, d_rays_ptr, n, d_out_ptr, params, stream_ptr=None, stats=None):
+        """rt_radiance_device: device pointers in (n rt_radiance_ray records, room for 3n doubles), `params` an
+        rt_radiance_params (radiance_params), run on `stream_ptr` (hipStream_t as int); returns when the sums are written.
+        An rt_stats is filled (its counters with RT_FLAG_COUNTERS in params.flags)."""
+        F.check(F.lib().rt_radiance_device(self._h, C.c_void_p(d_rays_ptr), n, C.byref(params), C.c_void_p(d_out_ptr),
+                                           C.c_void_p(stream_ptr or 0), C.byref(stats) if stats is not None else None))
 
     def close(self):
         if self._h:
