@@ -1,5 +1,5 @@
-// pt_common.hpp — device functions shared by the megakernel (pt_kernel.hip) and the
-// wavefront engine (pt_wavefront.hip): movers, primitive tests, the winner's hit record,
+// pt_common.hpp — device functions shared by the megakernel (pt_kernel.hip), the query
+// kernel (pt_query.hip) and the wavefront engine (pt_wavefront.hip): movers, primitive tests, the winner's hit record,
 // textures, samplers, light pdfs, camera — each one the f64 restatement of the reference
 // lines cited next to it, through rt_math.h so that results are bit-identical to the oracle.
 #ifndef RT2022_PT_COMMON_HPP
@@ -291,47 +291,6 @@ RT_DEV bool ring_t(const rt_ring &g, const XRay &r, double t_min, double t_max, 
     if (d < g.dis_min || d > g.dis_max) return false;
     t = tt;
     return true;
-}
-
-// dyn Hittable::hit for the leaf kinds SPHERE..RING.
-RT_DEV bool prim_t(const SceneDev &s, uint32_t kind, uint32_t idx, const XRay &r, double tm,
-                   double t_min, double t_max, double &t, uint32_t &face) {
-    switch (kind) {
-        case RT_KIND_SPHERE: {
-            const rt_sphere &q = s.spheres[idx];
-            return sphere_t(ld3(q.center), q.radius, r, r.d.length_sqr(), t_min, t_max, t);
-        }
-        case RT_KIND_MOVING_SPHERE: {
-            const rt_moving_sphere &q = s.moving_spheres[idx];
-            return sphere_t(moving_center(q, tm), q.radius, r, r.d.length_sqr(), t_min, t_max, t);
-        }
-        case RT_KIND_RECT: {
-            const rt_rect &q = s.rects[idx];
-            return rect_t(q.axis, q.a0, q.a1, q.b0, q.b1, q.k, r, t_min, t_max, t);
-        }
-        case RT_KIND_BOX: return box_t(s.boxes[idx], r, t_min, t_max, t, face);
-        case RT_KIND_TRIANGLE: return triangle_t(s.triangles[idx], r, t_min, t_max, t);
-        case RT_KIND_RING: return ring_t(s.rings[idx], r, t_min, t_max, t);
-        default: return false;
-    }
-}
-
-// boundary.hit(r, t_min, t_max).t for a medium boundary: movers around one primitive.
-template <bool STATS>
-RT_DEV bool boundary_t(const SceneDev &s, uint32_t ref, XRay r, double tm, double t_min, double t_max, double &t,
-                       Counters<STATS> &cnt) {
-    for (int lvl = 0; lvl <= RT_MAX_XFORM_DEPTH; lvl++) {
-        uint32_t kind = RT_REF_KIND(ref);
-        cnt.prim(kind);
-        if (kind >= RT_KIND_TRANSLATE && kind <= RT_KIND_ZOOM) {
-            r = xform_ray(s, ref, r);
-            ref = s.xforms[RT_REF_INDEX(ref)].child;
-            continue;
-        }
-        uint32_t face;
-        return prim_t(s, kind, RT_REF_INDEX(ref), r, tm, t_min, t_max, t, face);
-    }
-    return false;
 }
 
 // ---- traversal state --------------------------------------------------------------------

@@ -6,35 +6,25 @@
 // lane moves to the next sample of its work item (pixel x sample-chunk), and when the
 // item ends the wave refills the idle lanes from a global work counter with one atomic
 // per wave (__ballot / __popcll / __shfl). The wave schedules itself: lanes are labelled
-// with their next operation and the most common one runs (see "The megakernel" below).
-// BVH traversal uses an explicit per-lane stack in LDS ([depth][lane] -> bank = lane,
-// conflict-free), visits nodes in exactly the reference's order (left subtree, then right
-// with t_max = closest so far, hittable/bvh/mod.rs:86-101) because ConstantMedium::hit
+// with their next operation and the most common one runs. The traversal arms are the ones
+// the query kernel shares (pt_traverse.hpp); this file adds the shade-and-refill arm. They
+// keep an explicit per-lane stack in LDS ([depth][lane] -> bank = lane, conflict-free),
+// visit nodes in exactly the reference's order (left subtree, then right with t_max
+// = closest so far, hittable/bvh/mod.rs:86-101) because ConstantMedium::hit
 // draws from the RNG during traversal (constantmedium.rs:60), and defers the hit record
 // (normal, uv) to the single winning candidate. All arithmetic is f64 through rt_math.h,
 // so every path is bit-identical to the CPU oracle's.
 //
 // No MFMA: this is branchy scalar f64, not a contraction.
-#include "pt_common.hpp"
+#include "pt_traverse.hpp"
 
 namespace rt2022 {
 
 namespace {
 
-// =====================================================================================
-// The megakernel: an in-wave scheduled state machine.
-//
-// Every lane carries one path and a label `op` naming the next thing it has to do:
-// test the BVH node on top of its stack, test a sphere / rect / box / medium leaf,
-// enter or leave a mover, or shade. Lanes of a wave are at different points of
-// different paths, so a plain "each lane runs its own switch" loop executes every
-// arm serially with a handful of lanes each (measured: 8 % lane utilisation). Here the
-// wave votes instead: it counts the lanes per label (__ballot + __popcll), runs the
-// most popular arm once with all the lanes that wait for it, and lets the others
-// stay parked — a lane's own sequence of operations (and therefore its RNG stream
-// and hit order) never changes, only when it gets its turn.
-// =====================================================================================
-struct Lane {
+// The megakernel's lane: the shared traversal state (pt_traverse.hpp) plus the path and its work item. The done arm of
+// the scheduler is op_shade: shade the finished traversal, then start the next ray, sample or item.
+struct Lane : TravLane {
     // work item: pixel slot x sample chunk
     uint64_t slot;
     uint32_t chunk_id, smp, smp_end, px, py, frame;
@@ -44,156 +34,7 @@ struct Lane {
     Ray r;                 // the ray being traced (world frame)
     int depth;             // remaining depth (ray_color's `depth`)
     uint32_t nb;           // bounce records on the tape
-    Rng rng;
-    // traversal
-    XRay cur;              // r inside the enclosing movers
-    Vec3 inv;              // 1 / cur.d (aabb.rs:19, hoisted: same value at every node)
-    double a_len;          // cur.d.length_sqr() (sphere.rs:41, hoisted likewise)
-    double closest;
-    bool found;
-    Winner win;
-    Chain ctx;
-    int sp;
-    uint32_t top;          // entry being processed (popped from the stack)
-    uint32_t op;
 };
-
-template <int STACK>
-struct Stack {
-    uint32_t *col;         // this lane's column: entry d at col[d * kBlock]
-    RT_DEV void push(Lane &L, uint32_t ref) { if (L.sp < STACK) { col[L.sp * kBlock] = ref; L.sp++; } }
-    RT_DEV uint32_t pop(Lane &L) { if (L.sp > 0) { L.sp--; return col[L.sp * kBlock]; } return REF_EMPTY; }
-};
-
-RT_DEV void set_cur(Lane &L, const XRay &c) {
-    L.cur = c;
-    L.inv = Vec3(1.0 / c.d.x, 1.0 / c.d.y, 1.0 / c.d.z);
-    L.a_len = c.d.length_sqr();
-}
-RT_DEV void accept(Lane &L, double t, uint32_t face) {
-    L.closest = t;
-    L.found = true;
-    L.win.t = t; L.win.leaf = L.top; L.win.face = face; L.win.chain = L.ctx;
-}
-template <int STACK>
-RT_DEV void next_entry(Lane &L, Stack<STACK> &st) {
-    L.top = st.pop(L);
-    L.op = classify(L.top);
-}
-
-// BvhNode::hit, bvh/mod.rs:86-101 + AABB::hit, aabb.rs:15-32. Left child is taken at once,
-// the right one waits on the stack and is tested against the then-closest hit.
-template <int STACK, bool STATS>
-RT_DEV void op_node(const SceneDev &s, Lane &L, Stack<STACK> &st, double t_min, Counters<STATS> &cnt) {
-    cnt.node();
-    const rt_bvh_node &n = s.nodes[RT_REF_INDEX(L.top)];
-    double tmn = t_min, tmx = L.closest;
-    bool miss = false;
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-        double inv_d = L.inv[i];
-        double t0 = (n.bmin[i] - L.cur.o[i]) * inv_d;
-        double t1 = (n.bmax[i] - L.cur.o[i]) * inv_d;
-        if (inv_d < 0.0) { double tmp = t0; t0 = t1; t1 = tmp; }
-        tmn = t0 > tmn ? t0 : tmn;
-        tmx = t1 < tmx ? t1 : tmx;
-        miss = miss || (tmx <= tmn);
-    }
-    if (!miss) {
-        st.push(L, n.right);
-        L.top = n.left;
-        L.op = classify(L.top);
-    } else {
-        next_entry(L, st);
-    }
-}
-
-template <int STACK, bool STATS>
-RT_DEV void op_sphere(const SceneDev &s, Lane &L, Stack<STACK> &st, double t_min, Counters<STATS> &cnt) {
-    uint32_t kind = RT_REF_KIND(L.top), idx = RT_REF_INDEX(L.top);
-    cnt.prim(kind);
-    Vec3 center;
-    double radius;
-    if (kind == RT_KIND_SPHERE) { const rt_sphere &q = s.spheres[idx]; center = ld3(q.center); radius = q.radius; }
-    else { const rt_moving_sphere &q = s.moving_spheres[idx]; center = moving_center(q, L.r.tm); radius = q.radius; }
-    double t;
-    if (sphere_t(center, radius, L.cur, L.a_len, t_min, L.closest, t)) accept(L, t, 0);
-    next_entry(L, st);
-}
-template <int STACK, bool STATS>
-RT_DEV void op_rect(const SceneDev &s, Lane &L, Stack<STACK> &st, double t_min, Counters<STATS> &cnt) {
-    cnt.prim(RT_KIND_RECT);
-    const rt_rect &q = s.rects[RT_REF_INDEX(L.top)];
-    double t;
-    if (rect_t(q.axis, q.a0, q.a1, q.b0, q.b1, q.k, L.cur, t_min, L.closest, t)) accept(L, t, 0);
-    next_entry(L, st);
-}
-template <int STACK, bool STATS>
-RT_DEV void op_box(const SceneDev &s, Lane &L, Stack<STACK> &st, double t_min, Counters<STATS> &cnt) {
-    cnt.prim(RT_KIND_BOX);
-    double t;
-    uint32_t face = 0;
-    if (box_t(s.boxes[RT_REF_INDEX(L.top)], L.cur, t_min, L.closest, t, face)) accept(L, t, face);
-    next_entry(L, st);
-}
-template <int STACK, bool STATS>
-RT_DEV void op_misc(const SceneDev &s, Lane &L, Stack<STACK> &st, double t_min, Counters<STATS> &cnt) {
-    uint32_t kind = RT_REF_KIND(L.top), idx = RT_REF_INDEX(L.top);
-    cnt.prim(kind);
-    double t;
-    bool h = kind == RT_KIND_TRIANGLE ? triangle_t(s.triangles[idx], L.cur, t_min, L.closest, t)
-                                      : ring_t(s.rings[idx], L.cur, t_min, L.closest, t);
-    if (h) accept(L, t, 0);
-    next_entry(L, st);
-}
-// ConstantMedium::hit, constantmedium.rs:49-83.
-template <int STACK, bool STATS>
-RT_DEV void op_medium(const SceneDev &s, Lane &L, Stack<STACK> &st, double t_min, Counters<STATS> &cnt) {
-    cnt.prim(RT_KIND_MEDIUM);
-    const rt_medium &m = s.media[RT_REF_INDEX(L.top)];
-    double t1, t2;
-    if (boundary_t<STATS>(s, m.boundary, L.cur, L.r.tm, -rtm::INF, rtm::INF, t1, cnt) &&
-        boundary_t<STATS>(s, m.boundary, L.cur, L.r.tm, t1 + 0.0001, rtm::INF, t2, cnt)) {
-        t1 = rtm::fmax_(t1, t_min);
-        t2 = rtm::fmin_(t2, L.closest);
-        if (!(t1 >= t2)) {
-            t1 = rtm::fmax_(t1, 0.0);
-            double ray_length = L.cur.d.length();
-            double distance_inside_boundary = (t2 - t1) * ray_length;
-            double rnd = L.rng.gen_f64();
-            double hit_distance = m.neg_inv_density * (rtm::log_(rnd) / rtm::log_(rtm::E_));
-            if (!(hit_distance > distance_inside_boundary)) accept(L, t1 + hit_distance / ray_length, 0);
-        }
-    }
-    next_entry(L, st);
-}
-// Translate / RotateY / Zoom entry and exit; HittableList expansion (mod.rs:90-100).
-template <int STACK, bool STATS>
-RT_DEV void op_ctx(const SceneDev &s, Lane &L, Stack<STACK> &st, Counters<STATS> &cnt) {
-    if (L.top == REF_POPCTX) {
-        L.ctx.n--;
-        set_cur(L, ray_at_level(s, L.ctx, L.ctx.n, XRay{L.r.orig, L.r.dir}));
-        next_entry(L, st);
-        return;
-    }
-    uint32_t kind = RT_REF_KIND(L.top), idx = RT_REF_INDEX(L.top);
-    cnt.prim(kind);
-    if (kind == RT_KIND_LIST) {
-        const rt_list &l = s.lists[idx];
-        for (uint32_t i = l.count; i > 0; i--) st.push(L, s.list_items[l.first + i - 1]);
-        next_entry(L, st);
-        return;
-    }
-    if (L.ctx.n < RT_MAX_XFORM_DEPTH) {
-        L.ctx.push(L.top);
-        set_cur(L, xform_ray(s, L.top, L.cur));
-        st.push(L, REF_POPCTX);
-        L.top = s.xforms[idx].child;
-        L.op = classify(L.top);
-    } else {
-        next_entry(L, st);
-    }
-}
 
 // One bounce record of the reference's recursion (main.rs:246-271):
 //   specular:  L = w * L_next                         stored with p = 1 ((w*L)/1 == w*L)
@@ -221,14 +62,13 @@ struct Tape {
 
 // Shade the finished traversal (main.rs:243-277), then — if the path ended — add it to the
 // pixel, move on to the next sample / item (main.rs:144-152) and aim the next camera ray.
-template <int STACK, bool STATS>
-RT_DEV void op_shade(const SceneDev &s, const RenderArgs &a, Lane &L, Stack<STACK> &st, Tape &tape, unsigned lane,
-                     Counters<STATS> &cnt) {
+template <bool STATS>
+RT_DEV void op_shade(const SceneDev &s, const RenderArgs &a, Lane &L, Tape &tape, unsigned lane, Counters<STATS> &cnt) {
     const Vec3 background = ld3(a.background);
     if (L.alive) {
         bool end_path = false;
         Vec3 Lterm(0.0, 0.0, 0.0);
-        if (!L.found) {
+        if (!(L.flags & kFound)) {
             Lterm = background;
             end_path = true;
         } else {
@@ -351,9 +191,11 @@ RT_DEV void op_shade(const SceneDev &s, const RenderArgs &a, Lane &L, Stack<STAC
 
     // world.hit(r, 0.001, f64::MAX), main.rs:243
     cnt.ray();
-    set_cur(L, XRay{L.r.orig, L.r.dir});
+    L.tm = L.r.tm;
+    trav_set_cur(L, XRay{L.r.orig, L.r.dir});
+    L.t_min = L.t_lo = a.t_min;
     L.closest = rtm::F64_MAX;
-    L.found = false;
+    L.flags = 0;
     L.ctx.n = 0;
     L.sp = 0;
     L.top = s.root;
@@ -365,47 +207,47 @@ RT_DEV void op_shade(const SceneDev &s, const RenderArgs &a, Lane &L, Stack<STAC
 template <int STACK, bool STATS>
 __global__ void __launch_bounds__(kBlock) pt_megakernel(const SceneDev s, const RenderArgs a) {
     __shared__ uint32_t stack_lds[STACK * kBlock];
-    Stack<STACK> st{stack_lds + threadIdx.x};
+    TravStack<STACK, kBlock> st{stack_lds + threadIdx.x};
     const unsigned lane = threadIdx.x & 63u;
     Counters<STATS> cnt;
     Tape tape{a.tape, (uint64_t)gridDim.x * kBlock, (uint64_t)blockIdx.x * kBlock + threadIdx.x};
 
     Lane L;
-    L.have_item = false; L.alive = false; L.found = false;
+    L.have_item = false; L.alive = false;
     L.slot = 0; L.chunk_id = 0; L.smp = 0; L.smp_end = 0; L.px = 0; L.py = 0; L.frame = 0;
-    L.depth = 0; L.nb = 0; L.sp = 0; L.top = REF_EMPTY; L.op = OP_SHADE;
-    L.closest = rtm::F64_MAX; L.a_len = 0.0;
+    L.depth = 0; L.nb = 0; L.sp = 0; L.top = REF_EMPTY; L.op = OP_SHADE; L.flags = 0;
+    L.tm = 0.0; L.t_min = L.t_lo = a.t_min; L.closest = rtm::F64_MAX; L.a_len = 0.0;
+    L.sub_closest = L.med_t1 = 0.0; L.med_ref = 0;
     L.ctx.c0 = L.ctx.c1 = L.ctx.c2 = L.ctx.c3 = 0; L.ctx.n = 0;
     L.win.t = 0.0; L.win.leaf = 0; L.win.face = 0; L.win.chain = L.ctx;
-    const double t_min = a.t_min;
     const int node_quorum = (int)(a.node_quorum & 0xFFu);          // (the upper bits are wavefront-engine tuning)
 
+    const auto world = [&] { return XRay{L.r.orig, L.r.dir}; };   // the world ray a mover exit starts from: the lane's own
     for (;;) {
         // Fast path: keep stepping nodes while enough lanes want to.
         for (;;) {
-            bool isn = L.op == OP_NODE;
-            int nn = __popcll(__ballot(isn));
-            if (nn < node_quorum) break;
-            if (isn) op_node<STACK, STATS>(s, L, st, t_min, cnt);
+            const bool isn = L.op == OP_NODE;
+            if ((int)__popcll(__ballot(isn)) < node_quorum) break;
+            if (isn) trav_node<false, STACK, kBlock, 0, STATS>(s, nullptr, 0u, L, st, cnt);
         }
-        // Vote: the label most lanes are waiting on (ties -> lowest id).
+        // Vote: the label with the most lanes (ties -> lowest id).
         int best = -1, best_n = 0;
 #pragma unroll
         for (int o = 0; o < (int)OP_COUNT; o++) {
-            int n = __popcll(__ballot(L.op == (uint32_t)o));
+            const int n = __popcll(__ballot(L.op == (uint32_t)o));
             if (n > best_n) { best_n = n; best = o; }
         }
-        if (best < 0) break;                                      // every lane idle
+        if (best < 0) break;                               // every lane idle
         if (L.op == (uint32_t)best) {
             switch (best) {
-                case OP_NODE: op_node<STACK, STATS>(s, L, st, t_min, cnt); break;
-                case OP_SPHERE: op_sphere<STACK, STATS>(s, L, st, t_min, cnt); break;
-                case OP_RECT: op_rect<STACK, STATS>(s, L, st, t_min, cnt); break;
-                case OP_BOX: op_box<STACK, STATS>(s, L, st, t_min, cnt); break;
-                case OP_MEDIUM: op_medium<STACK, STATS>(s, L, st, t_min, cnt); break;
-                case OP_MISC: op_misc<STACK, STATS>(s, L, st, t_min, cnt); break;
-                case OP_CTX: op_ctx<STACK, STATS>(s, L, st, cnt); break;
-                default: op_shade<STACK, STATS>(s, a, L, st, tape, lane, cnt); break;
+                case OP_NODE: trav_node<false, STACK, kBlock, 0, STATS>(s, nullptr, 0u, L, st, cnt); break;
+                case OP_SPHERE: trav_sphere<false>(s, L, st, cnt); break;
+                case OP_RECT: trav_rect<false>(s, L, st, cnt); break;
+                case OP_BOX: trav_box<false>(s, L, st, cnt); break;
+                case OP_MEDIUM: trav_medium<false>(s, L, st, cnt); break;
+                case OP_MISC: trav_misc<false>(s, L, st, cnt); break;
+                case OP_CTX: trav_ctx<false>(s, L, st, cnt, world); break;
+                default: op_shade<STATS>(s, a, L, tape, lane, cnt); break;
             }
         }
     }

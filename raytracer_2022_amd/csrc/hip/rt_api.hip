@@ -108,8 +108,8 @@ struct Validator {
             check_mat(d.media[i].mat, "medium");
             RT_REQUIRE(d.materials[d.media[i].mat].kind == RT_MAT_ISOTROPIC, RT_ERR_INVALID, "medium: phase function must be Isotropic");
             check_ref(d.media[i].boundary, "medium.boundary");
-            // A boundary that is one primitive under movers is what the megakernel engine handles;
-            // anything else (a box of boxes, a BVH, a list) needs the wavefront engine's sub-queries.
+            // A boundary that is one primitive under movers is what the megakernel engine accepts;
+            // anything else (a box of boxes, a BVH, a list) takes the wavefront engine.
             uint32_t ref = d.media[i].boundary;
             int lvl = 0;
             bool simple = true;
@@ -329,7 +329,7 @@ struct rt_scene {
     bool boxes_plain = false;         // every node box finite with min <= max: the short node step applies
     double split[3] = {0.0, 0.0, 0.0};         // centre of the root's box (list ordering)
     uint32_t node_quorum = 18u | (1u << 8) | (2u << 12) | ((uint32_t)(8 * 4096 / kSlotsPerBlock > 0 ? 8 * 4096 / kSlotsPerBlock : 1) << 16) | (2u << 20) | (0u << 24);   // fast-path quorum 18 lanes; one extra sphere test per turn; tail factor 2; pool of 8 segments per resident trace workgroup (4 per CU: 8192 segments = 33.5 M slots); list classes of 4 node steps; groups of segments: the library's choice (0)
-    uint32_t vote_weights = 0;                 // 0: the engine's own default (kWfVoteWeights / kMegaVoteWeights, pt_device.h)
+    uint32_t vote_weights = 0;                 // 0: the wavefront engine's default (kWfVoteWeights, pt_device.h)
     int engine = 1;                   // 0 = megakernel, 1 = wavefront (shade / trace passes)
     unsigned long long census_rounds[9] = {}, census_lanes[9] = {};   // of the last counter run
     int max_pool_blocks = 0;          // 0 = 5 x CUs x segments per trace workgroup
@@ -531,7 +531,7 @@ void enqueue(rt_scene *sc, const rt_camera *cam, const rt_params *p, const uint3
     }
     // bit 31: boxes are plain (see wf_trace's fast path); bit 30 of the tuning word forces the literal step
     a.node_quorum = (sc->node_quorum & 0x7FFFFFFFu) | ((sc->boxes_plain && !(sc->node_quorum & (1u << 30))) ? (1u << 31) : 0u);
-    a.vote_weights = sc->vote_weights ? sc->vote_weights : (sc->engine == 1 ? kWfVoteWeights : kMegaVoteWeights);
+    a.vote_weights = sc->vote_weights ? sc->vote_weights : kWfVoteWeights;      // (read by the wavefront engine only)
     a.work_counter = w.work_counter;
     a.stats = counters ? w.stats : nullptr;
     if (sc->engine == 1) {
