@@ -85,7 +85,6 @@ struct RenderArgs {
     uint32_t chunk, n_chunks;          // samples per work item, items per pixel
     double background[3];
     double t_min;
-    double split[3];                   // centre of the root's bounding box (ordering of the ray lists only)
     uint64_t seed;
     uint64_t n_pixels;                 // n_rows * width
     uint64_t n_items;                  // n_pixels * n_chunks
@@ -137,10 +136,7 @@ constexpr uint32_t kMatKindShift = 24, kMatIndexMask = (1u << kMatKindShift) - 1
 
 // A pool of path slots in HBM, one array of records per field; segment b (= shade workgroup b) owns
 // the slots [b*kSlotsPerBlock, (b+1)*kSlotsPerBlock) for the whole frame.
-#ifndef RT2022_SLOTS_PER_SEGMENT
-#define RT2022_SLOTS_PER_SEGMENT 4096
-#endif
-constexpr int kSlotsPerBlock = RT2022_SLOTS_PER_SEGMENT;     // (a multiple of 256, at most 32768: list entries are u16)
+constexpr int kSlotsPerBlock = 4096;     // (a multiple of 256, at most 32768: list entries are u16)
 constexpr uint64_t kRecBytes = 128, kRecDoubles = kRecBytes / 8, kRecWords = kRecBytes / 4;      // the slot record
 struct WfPool {
     uint32_t n_slots;
@@ -191,20 +187,14 @@ constexpr uint32_t kWfVoteWeights = 0x24444442u;      // wavefront engine: node 
 // entries (64 KiB), and the first kNodeCache node records in the remaining LDS (56 bytes each: 97 440 B).
 constexpr int kCacheBlock = 1024;
 constexpr int kStackTiny = 16;
-#ifndef RT2022_NODE_CACHE
-#define RT2022_NODE_CACHE 1740
-#endif
-constexpr int kNodeCache = RT2022_NODE_CACHE;
+constexpr int kNodeCache = 1740;
 // The all-in-LDS instance for small sphere-only scenes: 600 node records (33 600 B), 256 Sphere records (36 B each) and
 // 512 MovingSphere records (80 B each) beside the 64 KiB of stacks.
 constexpr int kPrimNodes = 600, kPrimSpheres = 256, kPrimMoving = 512;
 // Four traversal workgroups per CU = 4 waves per SIMD = a budget of 128 VGPRs: the kernel then needs 116 and spills
 // nothing. Five (96 VGPRs, 27 spilled, 84 B of scratch per lane) measured 3 % slower in the same run, three 8-9 %
 // slower (profiles/r2_ab_occupancy.log): the kernel is bound by instruction issue far more than by latency.
-#ifndef RT2022_TRACE_BLOCKS_PER_CU
-#define RT2022_TRACE_BLOCKS_PER_CU 4
-#endif
-constexpr int kTraceBlocksPerCU = RT2022_TRACE_BLOCKS_PER_CU;   // resident traversal workgroups per CU the lean kernels are built for
+constexpr int kTraceBlocksPerCU = 4;   // resident traversal workgroups per CU the lean kernels are built for
 
 // ---- closest-hit queries (pt_query.hip, rt_intersect*) ------------------------------
 struct QueryArgs {
@@ -271,7 +261,8 @@ hipError_t launch_rng_probe(uint64_t state, int mode, double lo, double hi, uint
 // Which traversal variant the wavefront engine launches for a scene without counters: {threads per workgroup, stack entries, nodes kept in LDS}.
 void trace_variant(const SceneDev &scene, uint32_t stack_need, uint32_t tuning, unsigned features, uint32_t out[4]);
 // {fast-path node steps that took the single-precision slab test, those it left undecided, 1 if this build counts (-DRT2022_F32_CENSUS),
-// RT2022_F32_SLABS of the build, verdicts that differed from the double-precision test's (census builds make both)}; clears the counters.
+// 1 (2 in a census build: the test in every whole-table instance without meshes), verdicts that differed from the double-precision
+// test's (census builds make both)}; clears the counters.
 hipError_t f32_slab_census(unsigned long long out[5]);
 // Occupancy-derived persistent grid size for the given variant.
 int render_grid_blocks(uint32_t stack_need, bool counters);

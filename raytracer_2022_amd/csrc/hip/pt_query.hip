@@ -99,18 +99,12 @@ RT_DEV void q_refill(const SceneDev &s, const QueryArgs &a, QLane &L, unsigned l
 
 // Lanes that must want a node step for the wave to keep taking the fast path. 8 rather than the render kernels' 18: measured
 // with the weights below, +8 % on the headline's bounce rays and +9 % on C2's, -3 % on C5's (12: +2 %, +5 %, +-0).
-#ifndef RT2022_QUERY_QUORUM
-#define RT2022_QUERY_QUORUM 8
-#endif
-constexpr int kQueryNodeQuorum = RT2022_QUERY_QUORUM;
+constexpr int kQueryNodeQuorum = 8;
 // Vote weights, four bits per label from the lowest nibble up (node, sphere, rect, box, medium, misc, ctx, done): the wave
 // runs the label with the largest lanes x weight. Node steps and the refill yield to the leaf arms, like wf_trace's weights:
 // measured against plain counts on the workloads of tools/query_bench.py, +20 % on the headline's bounce rays, +5-10 % on the
 // others; a refill weighted up (done x 2) was 1-20 % slower.
-#ifndef RT2022_QUERY_WEIGHTS
-#define RT2022_QUERY_WEIGHTS 0x24444442u
-#endif
-constexpr uint32_t kQueryVoteWeights = RT2022_QUERY_WEIGHTS;
+constexpr uint32_t kQueryVoteWeights = 0x24444442u;
 
 // STACK: traversal stack entries; WG: threads per workgroup; CACHE: node records kept in LDS (0: none);
 // STATS: counter instance; ANY: RT_FLAG_ANY_HIT.
@@ -198,16 +192,11 @@ hipError_t launch_flags(const SceneDev &scene, const QueryArgs &args, bool count
 
 } // namespace
 
-#ifndef RT2022_QUERY_CACHE
-#define RT2022_QUERY_CACHE 1
-#endif
-constexpr bool kQueryCache = RT2022_QUERY_CACHE;   // 0: no node-table instance (every scene takes the 256-thread kernels)
-
 hipError_t launch_query(const SceneDev &scene, const QueryArgs &args, uint32_t stack_need, bool counters, bool any_hit,
                         hipStream_t stream) {
     if (args.n_rays == 0) return hipSuccess;
     if (stack_need > (uint32_t)kStackLarge) return hipErrorInvalidValue;
-    if (kQueryCache && stack_need <= (uint32_t)kStackTiny) return launch_flags<kStackTiny, kCacheBlock, kNodeCache>(scene, args, counters, any_hit, stream);
+    if (stack_need <= (uint32_t)kStackTiny) return launch_flags<kStackTiny, kCacheBlock, kNodeCache>(scene, args, counters, any_hit, stream);
     if (stack_need <= (uint32_t)kStackSmall) return launch_flags<kStackSmall, kBlock, 0>(scene, args, counters, any_hit, stream);
     if (stack_need <= (uint32_t)kStackMid) return launch_flags<kStackMid, kBlock, 0>(scene, args, counters, any_hit, stream);
     return launch_flags<kStackLarge, kBlock, 0>(scene, args, counters, any_hit, stream);

@@ -37,23 +37,15 @@ namespace rt2022 {
 namespace {
 
 constexpr int S = kSlotsPerBlock;
-#ifndef RT2022_CHUNK
-#define RT2022_CHUNK 256
-#endif
-#ifndef RT2022_LIST_OCTANTS
-#define RT2022_LIST_OCTANTS 1
-#endif
-#ifndef RT2022_LIST_ORIGIN
-#define RT2022_LIST_ORIGIN 1           // 0: no third key; 1: four classes (camera / sphere / box, rect / medium); 2: eight (the leaf kind itself)
-#endif
-// list order: 16 classes of expected length x classes of where the ray starts x 8 direction octants
-constexpr uint32_t kOriginClasses = RT2022_LIST_ORIGIN == 2 ? 8u : RT2022_LIST_ORIGIN ? 4u : 1u;
-#ifndef RT2022_LIST_SPATIAL
-#define RT2022_LIST_SPATIAL 0          // a fourth key — 1: the quadrant (x, z about the centre of the root's box) the ray starts in; 2: the dominant axis of its direction
-#endif
-constexpr uint32_t kSpatialClasses = RT2022_LIST_SPATIAL ? 4u : 1u;
-constexpr uint32_t kListBins = 16 * kOriginClasses * 8 * kSpatialClasses;
-constexpr uint32_t kChunk = RT2022_CHUNK;           // list entries a wave claims at a time
+// list order: 16 classes of expected length x classes of where the ray starts (camera / sphere / box, rect / medium) x 8 direction octants
+constexpr uint32_t kOriginClasses = 4u;
+constexpr uint32_t kListBins = 16 * kOriginClasses * 8;
+constexpr uint32_t kChunk = 256;           // list entries a wave claims at a time
+constexpr int kShadeWaves = 3;             // resident shade workgroups per CU = waves per SIMD (168 VGPRs; four: 128 VGPRs, 51 spilled)
+constexpr int kLeanBlocks = 5;             // resident traversal workgroups per CU of the sphere-only kernels (FEAT = 0, 256 threads)
+// Operations of one kind a wf_trace lane takes in one turn of a voted arm, where its next entry is of the same kind again:
+// the sphere and box arms take a span-2 leaf pair (three spheres: -1.6 % on the headline, -3 % on C2 in one A/B call).
+constexpr int kSphereReps = 2, kNodeReps = 1, kBoxReps = 2, kMiscReps = 2;
 
 // Records are fetched whole and at once — a few 16-byte loads issued back to back and waited for together — never
 // field by field as the arithmetic gets to them: left to itself the compiler sinks each field's load into the branch
@@ -64,17 +56,6 @@ typedef double f64x2_a8 __attribute__((ext_vector_type(2), aligned(8)));     // 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-#ifndef RT2022_F32_GLOBAL
-#define RT2022_F32_GLOBAL 1            // the same test on 32-byte single-precision node records from HBM / L2 (wf_trace, kF32G): 1 the sphere scenes too large
-                                       // for LDS and the triangle meshes, 2 every instance without boxes / media (A/B, census), 0 none
-#endif
-#ifndef RT2022_STASH
-#define RT2022_STASH 1                 // keep 1/d.x, 1/d.z of the frame a RotateY is entered from (0: two divisions at its exit instead — five registers fewer)
-#endif
-#ifndef RT2022_F32_SLABS
-#define RT2022_F32_SLABS 1             // node table in LDS: single-precision slab test with a double-precision second opinion (wf_trace, t_slabs32):
-                                       // 1 the all-in-LDS instance of sphere-only scenes, 2 every instance that holds the whole table (A/B, census), 0 none
-#endif
 template <class T>
 RT_DEV void t_pin(T &v) { asm volatile("" : "+v"(v)); }
 // The wave's vote as the hardware gives it (a v_cmp into an SGPR pair); HIP's __ballot materialises the predicate as 0 / 1 first.
@@ -306,15 +287,12 @@ RT_DEV Vec3 texture_value_top(const SceneDev &s, uint32_t tex, uint32_t tex_kind
 #define SP_FLUSH() do {} while (0)
 #endif
 
-#ifndef RT2022_SHADE_WAVES
-#define RT2022_SHADE_WAVES 3           // resident shade workgroups per CU = waves per SIMD (168 VGPRs; four: 128 VGPRs, 51 spilled)
-#endif
 // RING: the partial-sum ring of RenderArgs::ring is in use (a build of its own: the default instance carries none of its
 // bookkeeping — bounded claims, starved slots, the oldest item in flight).
 // RAYS: a new path's first ray is the caller's (RenderArgs::rays, rt_radiance*) instead of the camera's: "pixel" = ray index,
 // no row ids, no camera draws. Everything else — the first sweep, the unwinding, the planes and the ring — is the render's.
 template <bool STATS, bool RING = false, bool RAYS = false>
-__global__ void __launch_bounds__(kBlock, RT2022_SHADE_WAVES) wf_shade(const SceneDev s, const RenderArgs *__restrict__ ap, const WfPool pool, const uint32_t parity) {
+__global__ void __launch_bounds__(kBlock, kShadeWaves) wf_shade(const SceneDev s, const RenderArgs *__restrict__ ap, const WfPool pool, const uint32_t parity) {
     __shared__ uint32_t hist[SK_COUNT];
     __shared__ uint32_t cursor[SK_COUNT];
     __shared__ uint32_t sorted[S];
@@ -563,14 +541,10 @@ __global__ void __launch_bounds__(kBlock, RT2022_SHADE_WAVES) wf_shade(const Sce
             store_state(pool, slot, stt, false);
             uint32_t cls = step_shift ? (expect >> step_shift) : 0u;
             new_kind[slot - base] = (uint8_t)(SK_TRACE | ((cls > 15u ? 15u : cls) << 4));
-            // (third key, RT2022_LIST_ORIGIN: what the ray starts from — a sphere, a box / rect, a medium)
+            // (third key: what the ray starts from — a sphere, a box / rect, a medium)
             const uint32_t lk = RT_REF_KIND(w.leaf);
-            const uint32_t org = RT2022_LIST_ORIGIN == 2 ? (lk & 7u)
-                               : RT2022_LIST_ORIGIN ? ((lk == RT_KIND_SPHERE || lk == RT_KIND_MOVING_SPHERE) ? 1u : (lk == RT_KIND_BOX || lk == RT_KIND_RECT) ? 2u : lk == RT_KIND_MEDIUM ? 3u : 0u) : 0u;
-            const double adx = rtm::fabs_(r.dir.x), ady = rtm::fabs_(r.dir.y), adz = rtm::fabs_(r.dir.z);
-            const uint32_t quad = RT2022_LIST_SPATIAL == 2 ? ((adx >= ady && adx >= adz) ? 0u : (ady >= adz ? 1u : 2u))
-                                : RT2022_LIST_SPATIAL ? ((r.orig.x < a.split[0] ? 1u : 0u) | (r.orig.z < a.split[2] ? 2u : 0u)) : 0u;
-            new_oct[slot - base] = (uint8_t)((RT2022_LIST_OCTANTS ? ((r.dir.x < 0.0 ? 1u : 0u) | (r.dir.y < 0.0 ? 2u : 0u) | (r.dir.z < 0.0 ? 4u : 0u)) : 0u) | (org << 3) | (quad << 6));
+            const uint32_t org = (lk == RT_KIND_SPHERE || lk == RT_KIND_MOVING_SPHERE) ? 1u : (lk == RT_KIND_BOX || lk == RT_KIND_RECT) ? 2u : lk == RT_KIND_MEDIUM ? 3u : 0u;
+            new_oct[slot - base] = (uint8_t)((r.dir.x < 0.0 ? 1u : 0u) | (r.dir.y < 0.0 ? 2u : 0u) | (r.dir.z < 0.0 ? 4u : 0u) | (org << 3));
         }
     }
 
@@ -580,14 +554,11 @@ __global__ void __launch_bounds__(kBlock, RT2022_SHADE_WAVES) wf_shade(const Sce
     __syncthreads();
     const uint32_t n_want = n_fresh;
     // One sample per item: every slot on the queue takes a new item, so the segment claims them with ONE atomic instead
-    // of one per wave and sweep turn (RT2022_ITEM_BATCH; which slot gets which item changes nothing, §5 of DESIGN.md).
-#ifndef RT2022_ITEM_BATCH
-#define RT2022_ITEM_BATCH 1
-#endif
+    // of one per wave and sweep turn (which slot gets which item changes nothing, §5 of DESIGN.md).
     __shared__ unsigned long long seg_items;
     __shared__ uint32_t seg_take;        // (ring mode) how many of the n_want items the segment really got
     __shared__ uint32_t seg_more;        // (ring mode) 1: work items remain beyond the ring's limit — the slots left without one ask again
-    const bool batch = (RT2022_ITEM_BATCH || RING) && single;
+    const bool batch = single;
     if (batch) {
         if (tid == 0) {
             if (!RING) {
@@ -735,7 +706,7 @@ __global__ void __launch_bounds__(kBlock, RT2022_SHADE_WAVES) wf_shade(const Sce
                 stt.depth = depth;                                    // (a fresh tape: nothing tainted)
                 store_state(pool, slot, stt, true);
                 new_kind[slot - base] = (uint8_t)SK_TRACE;            // (a camera ray goes with the short ones: list class 0)
-                new_oct[slot - base] = (uint8_t)(RT2022_LIST_OCTANTS ? ((r.dir.x < 0.0 ? 1u : 0u) | (r.dir.y < 0.0 ? 2u : 0u) | (r.dir.z < 0.0 ? 4u : 0u)) : 0u);
+                new_oct[slot - base] = (uint8_t)((r.dir.x < 0.0 ? 1u : 0u) | (r.dir.y < 0.0 ? 2u : 0u) | (r.dir.z < 0.0 ? 4u : 0u));
                 if (RING) { const unsigned long long grp = (smp - 1u) / a.ring_group; my_oldest = grp < my_oldest ? grp : my_oldest; }
             } else if (RING && starved) {
                 new_kind[slot - base] = (uint8_t)SK_FRESH;            // (not a ray: listed behind the rays, see below)
@@ -766,15 +737,11 @@ __global__ void __launch_bounds__(kBlock, RT2022_SHADE_WAVES) wf_shade(const Sce
         if (RING) my_starved[i] = e == (uint32_t)SK_FRESH ? atomicAdd(&n_starved_out, 1u) : 0xFFFFFFFFu;
         // (second key: rays that point into the same octant meet the boxes in a similar pattern, and the lanes of a
         // wave draw neighbouring list entries)
-        // (new_oct: octant | origin class << 3 | quadrant << 6 — contiguous fields when every key is in use)
+        // (new_oct: octant | origin class << 3; key: origin and octant first, expected length within. Bits 6-7 of new_oct held a
+        // fourth key once and are always 0: the key still folds them in, which keeps the compiled shade pass as it was measured.)
         if ((e & 0xFu) == SK_TRACE) {
             const uint32_t o8 = new_oct[i * kBlock + tid];
-#ifndef RT2022_LIST_MAJOR
-#define RT2022_LIST_MAJOR 1            // 0: expected length first, then origin and octant; 1: origin and octant first, length within; 2: octant, origin, length
-#endif
-            if (RT2022_LIST_MAJOR == 1) key = ((o8 >> 6) * (8u * kOriginClasses) + (o8 & 63u)) * 16u + (15u - (e >> 4));
-            else if (RT2022_LIST_MAJOR == 2) key = (((o8 >> 6) * 8u + (o8 & 7u)) * kOriginClasses + ((o8 >> 3) & 7u)) * 16u + (15u - (e >> 4));
-            else key = ((15u - (e >> 4)) * kSpatialClasses + (o8 >> 6)) * (8u * kOriginClasses) + (o8 & 63u);
+            key = ((o8 >> 6) * (8u * kOriginClasses) + (o8 & 63u)) * 16u + (15u - (e >> 4));
             atomicAdd(&bins[key], 1u);
         }
         my_key[i] = key;
@@ -864,10 +831,10 @@ struct TLane {
     uint32_t win_mat;      // material word of the winning leaf (index | slot kind << kMatKindShift), taken from the record at hand
     double stash_ix, stash_iz;   // 1/d.x, 1/d.z of the frame a RotateY was entered from (they change only there) ...
     uint32_t stash_level;        // ... and that frame's mover depth (0xFFFFFFFF: nothing stashed)
-    // (node table in LDS, RT2022_SIGNED_SLABS) byte addresses, within the table's record 0, of the box coordinate the ray meets
+    // (node table in LDS, kSlabs) byte addresses, within the table's record 0, of the box coordinate the ray meets
     // first / last on each axis: bmin / bmax by the sign of 1/d — set wherever inv is (t_slabs)
     uint32_t near_at[3], far_at[3];
-    // (single-precision slab test, RT2022_F32_SLABS) per axis {(float)(1/d), (float)(-o/d)} — one operand pair of the packed
+    // (single-precision slab test, kF32 / kF32G) per axis {(float)(1/d), (float)(-o/d)} — one operand pair of the packed
     // multiply-add that gives the axis' two slab distances — and the ray's share of the test's error bound; set with near_at
     f32x2 p32[3];
     float e_ray;
@@ -912,7 +879,7 @@ RT_DEV void t_slabs(TLane &L, uint32_t table_at) {
         L.far_at[i] = table_at + (neg ? 0u : 24u) + 8u * (uint32_t)i;
     }
 }
-// The single-precision slab test of the node table in LDS (RT2022_F32_SLABS; see the fast path). A node record there is eleven
+// The single-precision slab test of the node table in LDS (kF32; see the fast path). A node record there is eleven
 // words: per axis {(float)bmin, (float)bmax, (float)bmin} — so that ONE two-word read at `base` or at `base + 4` delivers the
 // pair in the order (first met, last met) for either sign of 1/d — then the left child and the push ref.
 constexpr uint32_t kNode32Words = 11, kNode32Bytes = 4 * kNode32Words;
@@ -1086,11 +1053,8 @@ __device__ unsigned long long g_f32_census[3];
 
 // Resident traversal workgroups per CU a variant is built and launched for (= waves per SIMD = its VGPR budget):
 // the sphere-only kernel needs 82 VGPRs and runs five (C2: +4 % over four; six would spill), the full kernels four.
-#ifndef RT2022_LEAN_BLOCKS
-#define RT2022_LEAN_BLOCKS 5           // resident workgroups per CU of the sphere-only kernels (FEAT = 0, 256 threads)
-#endif
 constexpr int trace_blocks_per_cu(int stack, bool stats, unsigned feat) {
-    return stack > 32 ? 2 : stats ? 3 : (stack > kStackSmall || (feat & kFeatMisc)) ? 4 : feat == 0 ? RT2022_LEAN_BLOCKS : kTraceBlocksPerCU;
+    return stack > 32 ? 2 : stats ? 3 : (stack > kStackSmall || (feat & kFeatMisc)) ? 4 : feat == 0 ? kLeanBlocks : kTraceBlocksPerCU;
 }
 // The node-cache variant (WG = kCacheBlock threads, one workgroup per CU, CACHE = kNodeCache records): the BVH's first
 // CACHE node records live in LDS — 48 bytes of box and 8 of child refs each — beside the traversal stacks of the
@@ -1106,10 +1070,40 @@ constexpr int trace_blocks_per_cu(int stack, bool stats, unsigned feat) {
 constexpr int trace_waves_per_simd(int stack, bool stats, unsigned feat, int wg) {
     return wg == kBlock ? trace_blocks_per_cu(stack, stats, feat) : wg / 256;
 }
+// Which wf_trace instances test node boxes in single precision, from the instance's template facts: wf_trace takes kF32 and
+// kF32G from these two, trace_variant asks them the same at run time.
+// f32_lds (kF32): the single-precision records of t_slabs32 in the node table in LDS — the all-in-LDS instance of sphere-only
+// scenes, and the whole-table instance of the sphere-only scenes too large for it (601 to 1 740 nodes). Why sphere-only scenes:
+// what the float test cannot decide is a ray leaving a surface against a box that surface lies on the face of (the verdict hangs
+// on t_min = 0.001 against a distance of zero); a sphere touches its box in six points, a rect or a box lies in its faces: one
+// node step in 96 000 on the random spheres, one in 194 on the book-2 final scene, one in 27 in the Cornell box
+// (tools/f32_census.py) — measured, the random spheres' traversal kernel 6-7 % faster, the final scene's 1 % and the Cornell
+// box's 6 % slower, whether the undecided lanes fetch the double-precision box on the spot or hand the step to the voted arm
+// (profiles/r3q_ab_f32_slabs.log). A census build (-DRT2022_F32_CENSUS) puts the test into every whole-table instance without
+// meshes instead, to count what it leaves undecided there.
+constexpr bool f32_lds(unsigned feat, bool cache, bool partial, bool prims, bool spheres) {
+#ifdef RT2022_F32_CENSUS
+    return cache && !partial && !(feat & kFeatMisc);
+#else
+    return prims || (spheres && feat == 0 && cache && !partial);
+#endif
+}
+// f32_hbm (kF32G): the same test in the plain kernels, for sphere scenes too large for those instances: 32-byte single-precision
+// records {min.x, max.x, min.y, max.y | min.z, max.z, left, push ref} — SceneDev::nodes32 — fetched as two 16-byte loads from
+// L2 / HBM: half the bytes of the double-precision record per node step. (These scenes take the plain kernels even where the
+// partial-table instance would apply: with the first 3 045 of these records in LDS that instance — four waves per SIMD against
+// the plain kernel's five — measured 10 % slower on the 1e4-sphere scene, node_cache_mode.)
+// ... and for the triangle meshes (kFeatMisc, no boxes or media): a triangle touches its box in its corners, one node step in
+// 1 348 of wwscene is left undecided (its rings lie in the faces of theirs); C5's traversal kernel -3.2 % — once the ten VGPRs
+// the test needs were found: the RotateY stash is dropped in these instances (two divisions at a RotateY's exit instead;
+// measured alone: no cost).
+constexpr bool f32_hbm(unsigned feat, bool cache, bool prims, bool spheres, bool stats, bool probe) {
+    return ((feat == 0 && spheres) || ((feat & kFeatMisc) && !(feat & kFeatVolumes))) && !prims && !stats && !probe && !cache;
+}
 // FEAT: which arms the scene can reach (kFeat* bits); the others are compiled out, which is
 // worth 20-60 VGPRs — the difference between 3 and 4-5 resident waves per SIMD.
-// SPHERES: every primitive of the scene is a sphere (FEAT 0 and no rects) — the scenes whose node boxes are tested in single precision
-// (a rect lies in the faces of its box, where that test decides nothing: see kF32 below).
+// SPHERES: every primitive of the scene is a sphere (sphere_only) — the scenes whose node boxes are tested in single precision
+// (a rect lies in the faces of its box, where that test decides nothing: see f32_lds).
 template <int STACK, bool STATS, unsigned FEAT, bool PROBE = false, int WG = kBlock, int CACHE = 0, bool PARTIAL = false, bool PRIMS = false, bool SPHERES = false>
 __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, WG)) wf_trace(const SceneDev s, const WfPool pool,
                                                    const double t_min, const uint32_t node_quorum_u, const uint32_t parity, StatsDev *stats,
@@ -1123,40 +1117,18 @@ __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, W
     // (The deeper-stack variants have no LDS to spare at four workgroups per CU: they fetch it from the pool again.)
     constexpr bool kStash = (FEAT & kFeatMovers) != 0 && STACK <= kStackSmall && CACHE == 0;
     __shared__ double wray_lds[kStash ? 6 * WG : 6];
-    // Node cache (CACHE > 0): boxes as three 16-byte words per node, child refs as one 8-byte word per node — or (kF32: the
-    // all-in-LDS instance of sphere-only scenes) the single-precision records of t_slabs32, 44 bytes per node; the double-precision
-    // boxes then stay in L2 for the few node steps the single-precision test cannot decide. Why sphere-only scenes: what the
-    // float test cannot decide is a ray leaving a surface against a box that surface lies on the face of (the verdict hangs on
-    // t_min = 0.001 against a distance of zero); a sphere touches its box in six points, a rect or a box lies in its faces:
-    // one node step in 96 000 on the random spheres, one in 194 on the book-2 final scene, one in 27 in the Cornell box
-    // (tools/f32_census.py) — measured, the random spheres' traversal kernel 6-7 % faster, the final scene's 1 % and the
-    // Cornell box's 6 % slower, whether the undecided lanes fetch the double-precision box on the spot or hand the step to the
-    // voted arm (profiles/r3q_ab_f32_slabs.log).
-    // (... and the whole-table instance of the sphere-only scenes too large for the all-in-LDS one: 601 to 1 740 nodes.)
-    constexpr bool kF32 = RT2022_F32_SLABS == 2 ? (CACHE > 0 && !PARTIAL && !(FEAT & kFeatMisc))
-                                                : (RT2022_F32_SLABS == 1 && (PRIMS || (SPHERES && FEAT == 0 && CACHE > 0 && !PARTIAL)));
-    // (kF32G) The same test in the plain kernels, for sphere scenes too large for that instance (SPHERES):
-    // 32-byte single-precision records {min.x, max.x, min.y, max.y | min.z, max.z, left, push ref} — SceneDev::nodes32 — fetched as
-    // two 16-byte loads from L2 / HBM: half the bytes of the double-precision record per node step. (These scenes take the plain
-    // kernels even where the partial-table instance would apply: with the first 3 045 of these records in LDS that instance —
-    // four waves per SIMD against the plain kernel's five — measured 10 % slower on the 1e4-sphere scene, node_cache_mode.)
-    // ... and for the triangle meshes (FEAT with kFeatMisc, no boxes or media): a triangle touches its box in its corners, one node step
-    // in 1 348 of wwscene is left undecided (its rings lie in the faces of theirs); C5's traversal kernel -3.2 % — once the ten VGPRs the
-    // test needs were found: the RotateY stash is dropped in these instances (two divisions at a RotateY's exit instead; measured alone: no cost).
-    constexpr bool kF32G = RT2022_F32_GLOBAL && RT2022_F32_SLABS >= 1 &&
-                           (RT2022_F32_GLOBAL == 2 ? !(FEAT & kFeatVolumes) : ((FEAT == 0 && SPHERES) || ((FEAT & kFeatMisc) && !(FEAT & kFeatVolumes)))) &&
-                           !PRIMS && !STATS && !PROBE && CACHE == 0 && !kF32;
-    constexpr bool kStashInv = RT2022_STASH && !(kF32G && (FEAT & kFeatMovers));
+    // Node cache (CACHE > 0): boxes as three 16-byte words per node, child refs as one 8-byte word per node — or (kF32) the
+    // single-precision records of t_slabs32, 44 bytes per node; the double-precision boxes then stay in L2 for the few node steps
+    // the single-precision test cannot decide. (kF32G: the plain kernels' test on SceneDev::nodes32; see f32_lds / f32_hbm.)
+    constexpr bool kF32 = f32_lds(FEAT, CACHE > 0, PARTIAL, PRIMS, SPHERES);
+    constexpr bool kF32G = f32_hbm(FEAT, CACHE > 0, PRIMS, SPHERES, STATS, PROBE);
+    constexpr bool kStashInv = !(kF32G && (FEAT & kFeatMovers));
     __shared__ f64x2 nc_box[CACHE > 0 && !kF32 && !kF32G ? 3 * CACHE : 1];
     __shared__ u32x2 nc_ref[CACHE > 0 && !kF32 && !kF32G ? CACHE : 1];
     __shared__ uint32_t nc32[kF32 ? kNode32Words * CACHE : 1];
     // ... and, in every variant (384 bytes), the first records of the two small tables the arms go to most: movers (32 B
     // each) and media (MediumDev, 64 B each) — two of each in the book-2 final scene.
-#ifndef RT2022_SMALL_TABLES_EVERYWHERE
-#define RT2022_SMALL_TABLES_EVERYWHERE 1
-#endif
-    constexpr bool kSmall = CACHE > 0 || RT2022_SMALL_TABLES_EVERYWHERE;
-    constexpr uint32_t kLdsXforms = kSmall && (FEAT & kFeatMovers) ? 8u : 0u, kLdsMedia = kSmall && (FEAT & kFeatVolumes) ? 2u : 0u;
+    constexpr uint32_t kLdsXforms = (FEAT & kFeatMovers) ? 8u : 0u, kLdsMedia = (FEAT & kFeatVolumes) ? 2u : 0u;
     __shared__ u32x4 xf_lds[kLdsXforms ? 2 * kLdsXforms : 1];
     __shared__ f64x2 md_lds[kLdsMedia ? 4 * kLdsMedia : 1];
     // PRIMS (sphere-only scenes small enough, C2): the sphere pools too — 32 B of centre and radius + 4 B of material
@@ -1246,12 +1218,6 @@ __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, W
     bool dry_seen = false;
     if (probe) t_start = wall_clock64();
 
-#ifndef RT2022_REFILL_TOUCH
-#define RT2022_REFILL_TOUCH 0
-#endif
-#if RT2022_REFILL_TOUCH
-    uint32_t touch_word = 0;
-#endif
     TP_DECL;
 #ifdef RT2022_F32_CENSUS
     unsigned f32_steps = 0, f32_undecided = 0, f32_wrong = 0;
@@ -1264,10 +1230,6 @@ __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, W
     L.win_chain = L.ctx; L.win_leaf = REF_EMPTY; L.win_face = 0; L.win_mat = 0;
     L.stash_ix = 0.0; L.stash_iz = 0.0; L.stash_level = 0xFFFFFFFFu;
     const int node_quorum = (int)(node_quorum_u & 0xFFu);
-#ifndef RT2022_SPHERE_REPS
-#define RT2022_SPHERE_REPS 2
-#endif
-    constexpr int sphere_reps = RT2022_SPHERE_REPS;                   // (a span-2 leaf pair in one turn; three: -1.6 % on the headline, -3 % on C2 in one A/B call)
     constexpr int tail_factor = 2;
     const bool boxes_plain = (node_quorum_u >> 31) != 0;             // host: every node box finite with min <= max
     unsigned census_rounds[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, census_lanes[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -1278,10 +1240,8 @@ __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, W
     unsigned long long ctab = kClassifyTable;
     uint32_t ref_empty = REF_EMPTY;
     asm volatile("" : "+s"(ctab), "+v"(ref_empty));                  // (a select takes one scalar operand, and that is its lane mask)
-#ifndef RT2022_SIGNED_SLABS
-#define RT2022_SIGNED_SLABS 1          // node table in LDS: the near / far box coordinate of each axis fetched by the sign of 1/d (no min / max per axis)
-#endif
-    constexpr bool kSlabs = RT2022_SIGNED_SLABS && CACHE > 0 && !PARTIAL && !(FEAT & kFeatMisc) && !kF32;      // (a partial table mixes both sources in one wave; the triangle kernels have no six registers to spare)
+    // (kSlabs: node table in LDS, the near / far box coordinate of each axis fetched by the sign of 1/d — no min / max per axis)
+    constexpr bool kSlabs = CACHE > 0 && !PARTIAL && !(FEAT & kFeatMisc) && !kF32;      // (a partial table mixes both sources in one wave; the triangle kernels have no six registers to spare)
     typedef const __attribute__((address_space(3))) f64x2 *LdsBoxPtr;
     typedef const __attribute__((address_space(3))) u32x2 *LdsRefPtr;
     LdsBoxPtr ncb = (LdsBoxPtr)nc_box;
@@ -1542,11 +1502,8 @@ __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, W
         } else if (best == OP_NODE) {
             // (a node step below the fast path's quorum — a handful of lanes: those whose next entry is a node again take it in the
             // same turn, like the leaf arms do with their pairs)
-#ifndef RT2022_NODE_REPS
-#define RT2022_NODE_REPS 1
-#endif
 #pragma unroll 1
-            for (int rep = 0; rep < RT2022_NODE_REPS && L.op == OP_NODE; rep++) {
+            for (int rep = 0; rep < kNodeReps && L.op == OP_NODE; rep++) {
             cnt.node();
             L.steps++;
             const uint32_t nidx = RT_REF_INDEX(L.top);
@@ -1616,7 +1573,7 @@ __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, W
             // BVH leaves come in pairs (span-2 nodes): a lane whose next entry is a sphere again takes
             // it here and now rather than waiting for another round.
 #pragma unroll 1
-            for (int rep = 0; rep < sphere_reps && L.op == OP_SPHERE; rep++) {
+            for (int rep = 0; rep < kSphereReps && L.op == OP_SPHERE; rep++) {
                 uint32_t kind = RT_REF_KIND(L.top), idx = RT_REF_INDEX(L.top);
                 cnt.prim(kind);
                 Vec3 center;
@@ -1631,17 +1588,6 @@ __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, W
                         mat_word = s.spheres[idx].mat;
                     }
                     t_pin(q0); t_pin(q1); t_pin(mat_word);
-#ifdef RT2022_WHATIF_SPHERE_FETCH
-                    // (diagnostic build: the record fetched a second time, behind the first — one more memory round trip per turn
-                    // of this arm, same values: how much of the kernel's time is this arm's fetch latency? profiles/r3e_whatif_arms.log)
-                    if (!PRIMS) {
-                        uint32_t z;
-                        asm volatile("v_and_b32 %0, 0, %1" : "=v"(z) : "v"((uint32_t)rtm::d2u(q0.x)));     // 0 — once q0 has arrived
-                        const f64x2_a8 *qp2 = reinterpret_cast<const f64x2_a8 *>(s.spheres + (idx + z));
-                        q0 = qp2[0]; q1 = qp2[1];
-                        t_pin(q0); t_pin(q1);
-                    }
-#endif
                     center = Vec3(q0.x, q0.y, q1.x); radius = q1.y;
                 } else {                                              // rt_moving_sphere, 80 B: center0, center1, time0, time1, radius, mat
                     const f64x2 *qp = PRIMS ? ms_lds + 5 * idx : reinterpret_cast<const f64x2 *>(s.moving_spheres + idx);
@@ -1654,16 +1600,6 @@ __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, W
                 }
                 double t;
                 bool h = sphere_t(center, radius, L.cur, L.a_len, L.t_lo, t_hi(L), t);
-#ifdef RT2022_WHATIF_SPHERE
-                // (diagnostic build: the arm's arithmetic N times over, same result — how much of the kernel's time is this arm's
-                // arithmetic? profiles/r3d_whatif_arms.log)
-                for (int k = 1; k < RT2022_WHATIF_SPHERE; k++) {
-                    Vec3 c2 = center; double r2 = radius, t2;
-                    asm volatile("" : "+v"(c2.x), "+v"(c2.y), "+v"(c2.z), "+v"(r2));
-                    const bool h2 = sphere_t(c2, r2, L.cur, L.a_len, L.t_lo, t_hi(L), t2);
-                    h = h && h2; t = h ? t2 : t;
-                }
-#endif
                 if (h) t_accept(L, t, 0, mat_word);
                 T_NEXT();
             }
@@ -1678,37 +1614,17 @@ __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, W
             T_NEXT();
         } else if ((FEAT & kFeatVolumes) && best == OP_BOX) {
             // (like the spheres: the leaves of a box BVH come in pairs, a lane whose next entry is a box again takes it in the same turn)
-#ifndef RT2022_BOX_REPS
-#define RT2022_BOX_REPS 2
-#endif
 #pragma unroll 1
-            for (int rep = 0; rep < RT2022_BOX_REPS && L.op == OP_BOX; rep++) {
+            for (int rep = 0; rep < kBoxReps && L.op == OP_BOX; rep++) {
             cnt.prim(RT_KIND_BOX);
             const uint32_t bidx = RT_REF_INDEX(L.top);
             const f64x2_a8 *bp = reinterpret_cast<const f64x2_a8 *>(s.boxes + bidx);                // rt_box, 56 B: p0, p1, mat
             f64x2 b0 = bp[0], b1 = bp[1], b2 = bp[2];
             uint32_t mat_word = s.boxes[bidx].mat;
             t_pin(b0); t_pin(b1); t_pin(b2); t_pin(mat_word);
-#ifdef RT2022_WHATIF_BOX_FETCH
-            {
-                uint32_t z;
-                asm volatile("v_and_b32 %0, 0, %1" : "=v"(z) : "v"((uint32_t)rtm::d2u(b0.x)));
-                const f64x2_a8 *bp2 = reinterpret_cast<const f64x2_a8 *>(s.boxes + (bidx + z));
-                b0 = bp2[0]; b1 = bp2[1]; b2 = bp2[2];
-                t_pin(b0); t_pin(b1); t_pin(b2);
-            }
-#endif
             double t;
             uint32_t face = 0;
             bool h = t_box(b0.x, b0.y, b1.x, b1.y, b2.x, b2.y, L.cur, L.t_lo, t_hi(L), t, face);
-#ifdef RT2022_WHATIF_BOX
-            for (int k = 1; k < RT2022_WHATIF_BOX; k++) {
-                f64x2 e0 = b0, e1 = b1, e2 = b2; double t2; uint32_t f2 = 0;
-                asm volatile("" : "+v"(e0), "+v"(e1), "+v"(e2));
-                const bool h2 = t_box(e0.x, e0.y, e1.x, e1.y, e2.x, e2.y, L.cur, L.t_lo, t_hi(L), t2, f2);
-                h = h && h2; t = h ? t2 : t; face = h ? f2 : face;
-            }
-#endif
             if (h) t_accept(L, t, face, mat_word);
             T_NEXT();
             }
@@ -1781,11 +1697,8 @@ __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, W
                 T_NEXT();
             }
         } else if ((FEAT & kFeatMisc) && best == OP_MISC) {                                 // Triangle, Ring
-#ifndef RT2022_MISC_REPS
-#define RT2022_MISC_REPS 2
-#endif
 #pragma unroll 1
-            for (int rep = 0; rep < RT2022_MISC_REPS && L.op == OP_MISC; rep++) {
+            for (int rep = 0; rep < kMiscReps && L.op == OP_MISC; rep++) {
             uint32_t kind = RT_REF_KIND(L.top), idx = RT_REF_INDEX(L.top);
             cnt.prim(kind);
             double t;
@@ -1795,15 +1708,6 @@ __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, W
                 const f64x2 *qp = reinterpret_cast<const f64x2 *>(s.triangles + idx);
                 f64x2 q0 = qp[0], q1 = qp[1], q2 = qp[2], q3 = qp[3], q4 = qp[4];
                 t_pin(q0); t_pin(q1); t_pin(q2); t_pin(q3); t_pin(q4);
-#ifdef RT2022_WHATIF_TRI_FETCH
-                {   // (diagnostic build: the record fetched a second time behind the first — what is one memory round trip of this arm worth?)
-                    uint32_t z;
-                    asm volatile("v_and_b32 %0, 0, %1" : "=v"(z) : "v"((uint32_t)rtm::d2u(q0.x)));
-                    const f64x2 *qp2 = reinterpret_cast<const f64x2 *>(s.triangles + (idx + z));
-                    q0 = qp2[0]; q1 = qp2[1]; q2 = qp2[2]; q3 = qp2[3]; q4 = qp2[4];
-                    t_pin(q0); t_pin(q1); t_pin(q2); t_pin(q3); t_pin(q4);
-                }
-#endif
                 rt_triangle tr;
                 tr.a[0] = q0.x; tr.a[1] = q0.y; tr.a[2] = q1.x; tr.b[0] = q1.y; tr.b[1] = q2.x; tr.b[2] = q2.y;
                 tr.c[0] = q3.x; tr.c[1] = q3.y; tr.c[2] = q4.x;
@@ -1820,9 +1724,6 @@ __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, W
             // 1/d of the ray changes only where d does: RotateY (x and z). Translate and Zoom leave the direction alone
             // (hittable/mod.rs:165-167,321-323), so entering or leaving them keeps inv and a_len — the same values the
             // three divisions would give again.
-#ifndef RT2022_CTX_CHAINS
-#define RT2022_CTX_CHAINS 1            // movers nested directly in one another (Translate(RotateY(Zoom(..))), scene.rs:320-322,403-412) are entered, and left, in ONE turn
-#endif
             if (L.top == REF_POPCTX) {
                 // Leaving a mover. When the next stack entry is the exit of the enclosing mover too — the movers were nested directly,
                 // nothing else waits in the frames between — all of them are left in this turn: only the outermost frame's ray is ever
@@ -1833,7 +1734,7 @@ __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, W
                     L.ctx.n--;
                     rotated = rotated || RT_REF_KIND(L.ctx.at(L.ctx.n)) == RT_KIND_ROTATE_Y;           // (a mover being left)
                     L.top = st.pop(L);
-                } while (RT2022_CTX_CHAINS && L.top == REF_POPCTX && L.ctx.n > 0u && ++levels < RT_MAX_XFORM_DEPTH);
+                } while (L.top == REF_POPCTX && L.ctx.n > 0u && ++levels < RT_MAX_XFORM_DEPTH);
                 // the world ray from this lane's LDS column (written at refill), then back down to the enclosing frame
                 XRay world;
                 if (kStash) {
@@ -1890,7 +1791,7 @@ __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, W
                         st.push(L, REF_POPCTX);
                         L.top = x0.y;
                         kind = RT_REF_KIND(L.top); idx = RT_REF_INDEX(L.top);
-                        if (!(RT2022_CTX_CHAINS && kind >= RT_KIND_TRANSLATE && kind <= RT_KIND_ZOOM && L.ctx.n < RT_MAX_XFORM_DEPTH)) break;
+                        if (!(kind >= RT_KIND_TRANSLATE && kind <= RT_KIND_ZOOM && L.ctx.n < RT_MAX_XFORM_DEPTH)) break;
                     }
                     t_flags(L, boxes_plain);
                     if (kSlabs) t_slabs(L, table_at); if (kF32) t_slabs32(L, table_at); if (kF32G) t_slabs32g(L);
@@ -1920,9 +1821,6 @@ __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, W
             const int leader = __ffsll((long long)m) - 1;
             uint32_t need = (uint32_t)__popcll(m);
             uint32_t rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-#if RT2022_REFILL_TOUCH
-            const uint32_t rank0 = rank;
-#endif
             uint32_t entry_idx = 0xFFFFFFFFu;                         // index into pool.list of the entry this lane takes
             const u32x4 cs_now = *cs;
             uint32_t ch_base = cs_now.x, ch_n = cs_now.y, ch_taken = cs_now.z;
@@ -1949,30 +1847,12 @@ __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, W
             }
             if ((int)lane == leader) *cs = (u32x4){ch_base, ch_n, ch_taken, drained ? 1u : 0u};
             if (probe && !dry_seen && drained) { dry_seen = true; t_dry = wall_clock64(); }
-#if RT2022_REFILL_TOUCH
-            // (Off by default: measured +0.3 % on the headline and +2 % on C2, for 35 % more HBM reads by the counters.)
-            // Touch-ahead: the entries this wave's NEXT refill round will hand out follow the ones handed out now; each
-            // refilling lane asks for one word of the ray record of the entry `its rank` places further on, beside its own
-            // fetches (same two dependent round trips, issued in parallel) — the next round's records then come from L2 or
-            // the Infinity Cache instead of HBM. The word is never used: the empty asm at the head of the next refill
-            // gives the load a consumer.
-            asm volatile("" :: "v"(touch_word));
-            const uint32_t touch_entry = ch_base + ch_taken + rank0;
-            const bool touch = touch_entry < ch_base + ch_n;
-            uint32_t touch_local = 0;
-            if (touch) touch_local = pool.list[touch_entry];
-#endif
             if (entry_idx != 0xFFFFFFFFu) {
                 const uint32_t sbase = entry_idx & ~((uint32_t)S - 1u);
                 L.entry = entry_idx;
                 L.slot = sbase + pool.list[entry_idx];
                 uint64_t rs;
                 Ray wr = pv.load_ray(L.slot, rs);
-#if RT2022_REFILL_TOUCH
-                asm volatile("" ::: "memory");
-                if (touch) touch_word = *reinterpret_cast<const uint32_t *>(pool.ray + (uint64_t)((touch_entry & ~((uint32_t)S - 1u)) + touch_local) * kRecDoubles);
-                asm volatile("" ::: "memory");
-#endif
                 L.tm = wr.tm;
                 L.rng = Rng(rs);
                 t_set_cur(L, XRay{wr.orig, wr.dir}, boxes_plain);
@@ -2068,6 +1948,8 @@ __global__ void __launch_bounds__(256) ring_accumulate_kernel(const double *part
     }
 }
 __global__ void ring_set_limit_kernel(unsigned long long *limit, unsigned long long value) { *limit = value; }
+// A scene whose every primitive is a sphere: the launchers' SPHERES (see f32_lds).
+static bool sphere_only(const SceneDev &scene, unsigned features) { return features == 0 && scene.n_rects == 0; }
 template <int STACK, bool STATS, unsigned FEAT, bool PROBE = false>
 static void launch_trace(const WfLaunch &w, uint32_t parity) {
     // A persistent grid: as many workgroups as the kernel's launch bounds keep resident, never more than the work
@@ -2077,7 +1959,7 @@ static void launch_trace(const WfLaunch &w, uint32_t parity) {
     const uint32_t most = w.blocks * ((uint32_t)S / kChunk / 4u);
     if (grid > most) grid = most;
     if constexpr (FEAT == 0 && !STATS && !PROBE) {
-        if (w.scene.n_rects == 0) {                                   // a sphere-only scene: the instance that tests node boxes in single precision (kF32G)
+        if (sphere_only(w.scene, FEAT)) {                             // the instance that tests node boxes in single precision (kF32G)
             hipLaunchKernelGGL((wf_trace<STACK, STATS, FEAT, PROBE, kBlock, 0, false, false, true>), dim3(grid), dim3(kBlock), 0, w.stream, w.scene, w.pool, w.t_min,
                                w.node_quorum, parity, w.stats, w.vote_weights);
             return;
@@ -2093,7 +1975,7 @@ static void launch_trace_cached(const WfLaunch &w, uint32_t parity) {
     const uint32_t most = std::max(1u, w.blocks * ((uint32_t)S / kChunk) / (uint32_t)(kCacheBlock / 64));
     if (grid > most) grid = most;
     if constexpr (FEAT == 0 && !PARTIAL) {
-        if (w.scene.n_rects == 0) {                                   // (a sphere-only scene: the single-precision records of t_slabs32 in the table)
+        if (sphere_only(w.scene, FEAT)) {                             // (the single-precision records of t_slabs32 in the table)
             hipLaunchKernelGGL((wf_trace<STACK, false, FEAT, false, kCacheBlock, CACHE, PARTIAL, false, true>), dim3(grid), dim3(kCacheBlock), 0, w.stream,
                                w.scene, w.pool, w.t_min, w.node_quorum, parity, w.stats, w.vote_weights);
             return;
@@ -2130,14 +2012,13 @@ static void launch_trace_cached_feat(unsigned feat, const WfLaunch &w, uint32_t 
 // sphere-only scene whose node table and sphere pools all fit (RT2022_PRIM_TABLES=0 in the environment: mode 1 instead).
 // The scenes whose plain kernels test node boxes in single precision on SceneDev::nodes32 (wf_trace: kF32G).
 static bool f32_from_hbm(const SceneDev &scene, unsigned features) {
-    return RT2022_F32_SLABS >= 1 && (RT2022_F32_GLOBAL == 2 ? !(features & kFeatVolumes)
-           : (RT2022_F32_GLOBAL == 1 && ((features == 0 && scene.n_rects == 0) || ((features & kFeatMisc) && !(features & kFeatVolumes)))));
+    return f32_hbm(features, false, false, sphere_only(scene, features), false, false);
 }
 static int node_cache_mode(const SceneDev &scene, uint32_t stack_need, uint32_t tuning, unsigned features) {
     static const bool enabled = [] { const char *e = getenv("RT2022_NODE_CACHE"); return !(e && e[0] == '0'); }();
     static const bool prims = [] { const char *e = getenv("RT2022_PRIM_TABLES"); return !(e && e[0] == '0'); }();
     if (!enabled || (tuning & (1u << 28)) || stack_need > (uint32_t)kStackTiny) return 0;
-    if (prims && features == 0 && scene.n_rects == 0 && scene.n_nodes <= (uint32_t)kPrimNodes && scene.n_spheres <= (uint32_t)kPrimSpheres &&
+    if (prims && sphere_only(scene, features) && scene.n_nodes <= (uint32_t)kPrimNodes && scene.n_spheres <= (uint32_t)kPrimSpheres &&
         scene.n_moving_spheres <= (uint32_t)kPrimMoving) return 3;
     if (scene.n_nodes <= (uint32_t)kNodeCache) return 1;
     // A scene whose nodes are tested in single precision from 32-byte records (sphere-only, or a triangle mesh: wf_trace, kF32G) takes
@@ -2398,21 +2279,20 @@ hipError_t f32_slab_census(unsigned long long out[5]) {
     e = hipMemcpyToSymbol(HIP_SYMBOL(g_f32_census), zero, sizeof(zero));
     out[0] = c[0]; out[1] = c[1]; out[4] = c[2];
 #ifdef RT2022_F32_CENSUS
-    out[2] = 1;
+    out[2] = 1; out[3] = 2;
 #else
-    out[2] = 0;
+    out[2] = 0; out[3] = 1;
 #endif
-    out[3] = RT2022_F32_SLABS;
     return e;
 }
 
 void trace_variant(const SceneDev &scene, uint32_t stack_need, uint32_t tuning, unsigned features, uint32_t out[4]) {
     out[3] = 0;
     const int table = node_cache_mode(scene, stack_need, tuning, features);
-    // Which instances test node boxes in single precision (wf_trace: kF32, kF32G) — bit 1 of out[3]
-    const bool f32 = table == 3 ? RT2022_F32_SLABS == 1 || RT2022_F32_SLABS == 2
-                   : table == 1 ? (RT2022_F32_SLABS == 2 && !(features & kFeatMisc)) || (RT2022_F32_SLABS == 1 && features == 0 && scene.n_rects == 0)
-                   : table == 0 ? f32_from_hbm(scene, features) : false;
+    // Whether the instance launch_pass picks tests node boxes in single precision (wf_trace: kF32, kF32G) — bit 1 of out[3] — from the
+    // facts it passes that instance as template arguments: mode 3 is PRIMS, 2 PARTIAL, and SPHERES is set by mode 1's launcher only.
+    const bool f32 = table == 0 ? f32_from_hbm(scene, features)
+                   : f32_lds(features, true, table == 2, table == 3, table == 1 && sphere_only(scene, features));
     if (table) {
         out[0] = (uint32_t)kCacheBlock; out[1] = (uint32_t)kStackTiny; out[2] = scene.n_nodes < (uint32_t)kNodeCache ? scene.n_nodes : (uint32_t)kNodeCache;
         out[3] = (table == 3 ? 1u : 0u) | (f32 ? 2u : 0u);

@@ -2,8 +2,9 @@
 
     RT2022_LIB=$PWD/raytracer_2022_amd/variants_lean/C_f32_census.so python3 tools/f32_census.py [scene W H spp [param]] ...
 
-Needs a library built with -DRT2022_F32_CENSUS (make EXTRA='-DRT2022_F32_CENSUS -DRT2022_F32_SLABS=2': the test in every
-instance that holds the whole node table, not only the sphere-only one): rt_debug_f32_slabs then returns the node steps of
+Needs a library built with -DRT2022_F32_CENSUS (make EXTRA=-DRT2022_F32_CENSUS: the test in every instance that holds the
+whole node table, meshes excepted, not only the sphere-only ones; up to 7803b5b that took -DRT2022_F32_SLABS=2 as well,
+a switch since retired): rt_debug_f32_slabs then returns the node steps of
 the fast path that took the single-precision test and those it left undecided, over the timed (counter-free) render made here.
 """
 import ctypes as C

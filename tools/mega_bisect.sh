@@ -20,6 +20,5 @@ build() {  # name, MEGA_OPT, MEGA_EXTRA
 build O1 -O1 ""
 build O2 -O2 ""
 build O3 -O3 ""
-build O3_packed -O3 "-DRT2022_CHAIN_PACKED=1"
 build O3_sgprmem -O3 "-mllvm -amdgpu-spill-sgpr-to-vgpr=0"
 build O3_noslp -O3 "-fno-slp-vectorize -fno-vectorize"
