@@ -15,10 +15,11 @@ extern "C" {
 int rt_debug_math_device(int op, const double *a, const double *b, double *out, uint64_t n);
 /* n draws from Rng(state): mode 0 next_u64, 1 gen_f64 (bits), 2 gen_range(lo,hi) (bits), 3 gen_index(bound). */
 int rt_debug_rng_device(uint64_t state, int mode, double lo, double hi, uint64_t bound, uint64_t *out, uint64_t n);
-/* Scheduler knobs of the engines. node_quorum, a bit field:
+/* Scheduler knobs of the engines. node_quorum is the tuning word, a bit field (the same list, with its accessors: namespace tune
+ * in csrc/hip/pt_device.h):
  *   0-7   lanes that must want a BVH-node step before the wave takes the node fast path without a
  *         vote (1..64);
- *   8-15  (unused: two sphere tests per turn and a tail factor of 2 are built in);
+ *   8-15  accepted and ignored (two sphere tests per turn and a tail factor of 2 are built in);
  *   16-19 pool size of the wavefront engine: segments of 4096 path slots per resident traversal
  *         workgroup (1..8, default 8);
  *   20-23 s: every segment's ray list is ordered longest-first by (expected node steps) >> s, 0 = slot order;

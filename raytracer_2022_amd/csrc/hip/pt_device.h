@@ -102,7 +102,7 @@ struct RenderArgs {
     // for bit (pixel_color += ..., main.rs:150, in sample order).
     uint32_t ring, ring_group;
     const unsigned long long *claim_limit;
-    uint32_t node_quorum;              // lanes that must want a node step for the fast path (1..64)
+    uint32_t tuning;                   // the tuning word (namespace tune below), bit 31 set by the host
     uint32_t vote_weights;             // 4 bits per operation label: the vote picks max(lanes * weight)
     StatsDev *stats;                   // may be null
     // rt_radiance* (device, null for a render): the caller's rays take the place of the camera. The "pixels" are the
@@ -175,6 +175,42 @@ struct WfPool {
     unsigned long long *dbg;
 };
 
+// ---- the tuning word ----------------------------------------------------------------
+// rt_scene::tuning / RenderArgs::tuning, set by rt_debug_set_tuning (its node_quorum argument): scheduler knobs of the engines,
+// speed only, never results. This is the one description of its fields; every reader goes through these accessors.
+//   0-7    quorum: lanes that must want a BVH-node step before the wave takes the node fast path without a vote (1..64; the
+//          one field the megakernel and nothing else of the word reads)
+//   8-15   accepted and ignored: extra sphere tests per turn (8-11) and the tail factor (12-15) went with the build switches
+//          that read them (two sphere tests per turn and a tail factor of 2 are built in); callers still pass 1 and 2 here
+//   16-19  segments: pool size of the wavefront engine, segments of kSlotsPerBlock path slots per resident traversal workgroup (1..8)
+//   20-23  class_shift s: every segment's ray list is ordered longest-first by (expected node steps) >> s, 0 = slot order
+//   24-27  groups the pool is cut into, each alternating its passes on a stream of its own (1..kMaxGroups; 0: the library's choice)
+//   28     kNoNodeTable: the plain traversal kernels even where a node-table variant applies (A/B runs, bit-parity tests)
+//   29     kPassTiming: run the pass-timing probe (rt_debug_pass_timing)
+//   30     kLiteralStep: take the literal AABB step only (test hook)
+//   31     kBoxesPlain: every node box finite with min <= max, the short node step applies — set by the host for the kernels
+//          (for_kernels), whatever the caller passed
+namespace tune {
+constexpr uint32_t kSegmentsShift = 16, kClassShift = 20, kGroupsShift = 24;
+constexpr uint32_t kNoNodeTable = 1u << 28, kPassTiming = 1u << 29, kLiteralStep = 1u << 30, kBoxesPlain = 1u << 31;
+constexpr uint32_t quorum(uint32_t word) { return word & 0xFFu; }
+constexpr uint32_t segments(uint32_t word) { return (word >> kSegmentsShift) & 0xFu; }
+constexpr uint32_t class_shift(uint32_t word) { return (word >> kClassShift) & 0xFu; }
+constexpr uint32_t groups(uint32_t word) { return (word >> kGroupsShift) & 0xFu; }
+constexpr bool no_node_table(uint32_t word) { return (word & kNoNodeTable) != 0; }
+constexpr bool pass_timing(uint32_t word) { return (word & kPassTiming) != 0; }
+constexpr bool literal_step(uint32_t word) { return (word & kLiteralStep) != 0; }
+constexpr bool boxes_plain(uint32_t word) { return (word >> 31) != 0; }
+// The word as the kernels get it: the scene's, with bit 31 = the host's finding about the node boxes unless bit 30 forbids it.
+constexpr uint32_t for_kernels(uint32_t word, bool plain) { return (word & ~kBoxesPlain) | (plain && !literal_step(word) ? kBoxesPlain : 0u); }
+// The default: fast-path quorum 18 lanes; (retired: one extra sphere test per turn, tail factor 2); pool of 8 segments per resident
+// trace workgroup (4 per CU: 8192 segments = 33.5 M slots); list classes of 4 node steps; groups of segments: the library's choice (0).
+constexpr uint32_t kRetiredDefault = (1u << 8) | (2u << 12);
+constexpr uint32_t kDefault = 18u | kRetiredDefault | ((uint32_t)(8 * 4096 / kSlotsPerBlock > 0 ? 8 * 4096 / kSlotsPerBlock : 1) << kSegmentsShift) |
+                              (2u << kClassShift) | (0u << kGroupsShift);
+static_assert(kDefault == 0x00282112u, "the default tuning word");
+} // namespace tune
+
 // Traversal-stack capacities the megakernel is instantiated for.
 constexpr int kStackSmall = 22;   // 22 KiB of LDS per workgroup; the lean kernels run four workgroups per CU (VGPR-bound)
 constexpr int kStackMid = 30;     // million-triangle meshes need ~26 entries; built for four workgroups per CU
@@ -237,24 +273,36 @@ struct KernelTimes {
     std::vector<hipEvent_t> ev;        // grown on demand, reused from call to call
     double shade_ms = 0.0, trace_ms = 0.0;
 };
-struct RingCtl;                        // (below)
-// Wavefront engine: alternates shade / trace passes over the pool until it drains.
-// Blocks the calling thread (polls `n_active`). d_args is the device-resident copy of `args`.
-hipError_t launch_render_wavefront(const SceneDev &scene, const RenderArgs &args, const RenderArgs *d_args,
-                                   const WfPool &pool, uint32_t stack_need, unsigned features, bool counters,
-                                   const WfStreams &gs, hipStream_t stream, uint32_t *out_iterations,
-                                   double *timing /* null, or [5]: see rt_debug_pass_timing */,
-                                   uint32_t *out_fault /* WfPool::fault after the last pass */,
-                                   KernelTimes *kt /* null, or where to put the per-kernel times (three HIP events per pass pair on its group's stream) */,
-                                   const Progress *progress = nullptr, const RingCtl *ring = nullptr);
-hipError_t launch_chunk_sum(const double *partial, double *out, uint64_t n_values, uint32_t n_chunks, hipStream_t stream);
-// Ring mode: what launch_render_wavefront needs to consume planes as the frame goes.
+// Ring mode: what the engine needs to consume planes as the frame goes.
 struct RingCtl {
     uint32_t planes = 0;               // 0 = off
     double *out = nullptr;             // [n_pixels * 3] the call's output: finished planes are added to it in sample order
     unsigned long long *d_limit = nullptr;   // device word behind RenderArgs::claim_limit
     uint32_t max_passes = 0;           // watchdog: more pass pairs than this is an engine error, not a long frame
 };
+// One render of the wavefront engine: what launch_render_wavefront is given, and what it reports.
+struct WfRender {
+    const SceneDev *scene = nullptr;
+    const RenderArgs *args = nullptr;
+    const RenderArgs *d_args = nullptr;    // the device-resident copy of *args
+    const WfPool *pool = nullptr;
+    uint32_t stack_need = 1;
+    unsigned features = 7;
+    bool counters = false;
+    const WfStreams *gs = nullptr;
+    hipStream_t stream = nullptr;
+    Progress progress;                     // (cb null: nobody to report to)
+    RingCtl ring;                          // (planes 0: off)
+    double *timing = nullptr;              // null, or [5]: see rt_debug_pass_timing
+    KernelTimes *kt = nullptr;             // null, or where to put the per-kernel times (three HIP events per pass pair on its group's stream)
+    // out
+    uint32_t passes = 0;                   // pass pairs enqueued
+    uint32_t fault = 0;                    // WfPool::fault after the last pass
+};
+// Wavefront engine: alternates shade / trace passes over the pool until it drains.
+// Blocks the calling thread (polls `n_active`).
+hipError_t launch_render_wavefront(WfRender &r);
+hipError_t launch_chunk_sum(const double *partial, double *out, uint64_t n_values, uint32_t n_chunks, hipStream_t stream);
 hipError_t launch_tonemap(const double *rgb_sum, uint64_t n_pixels, int32_t spp, uint8_t *rgb8, hipStream_t stream);
 hipError_t launch_math_probe(int op, const double *a, const double *b, double *out, uint64_t n, hipStream_t stream);
 hipError_t launch_rng_probe(uint64_t state, int mode, double lo, double hi, uint64_t bound, uint64_t *out, uint64_t n, hipStream_t stream);

@@ -220,7 +220,7 @@ __global__ void __launch_bounds__(kBlock) pt_megakernel(const SceneDev s, const 
     L.sub_closest = L.med_t1 = 0.0; L.med_ref = 0;
     L.ctx.c0 = L.ctx.c1 = L.ctx.c2 = L.ctx.c3 = 0; L.ctx.n = 0;
     L.win.t = 0.0; L.win.leaf = 0; L.win.face = 0; L.win.chain = L.ctx;
-    const int node_quorum = (int)(a.node_quorum & 0xFFu);          // (the upper bits are wavefront-engine tuning)
+    const int node_quorum = (int)tune::quorum(a.tuning);            // (the other fields are wavefront-engine tuning)
 
     const auto world = [&] { return XRay{L.r.orig, L.r.dir}; };   // the world ray a mover exit starts from: the lane's own
     for (;;) {

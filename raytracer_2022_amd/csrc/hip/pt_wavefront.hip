@@ -28,6 +28,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 #include <vector>
 
 #include "pt_common.hpp"
@@ -361,7 +362,7 @@ __global__ void __launch_bounds__(kBlock, kShadeWaves) wf_shade(const SceneDev s
     // One sample per work item (spp_chunk = 1): the item's running sum needs no place of its own in the pool.
     const bool single = a.chunk == 1 && a.spp > 0 && a.max_depth > 0;
     const bool small_job = a.n_items <= 0xFFFFFFFFull;
-    const uint32_t step_shift = (a.node_quorum >> 20) & 0xFu;         // list class = expected steps >> shift (0 = slot order)
+    const uint32_t step_shift = tune::class_shift(a.tuning);          // list class = expected steps >> shift (0 = slot order)
 
     unsigned long long my_oldest = ~0ull;                            // (ring mode) the oldest work item among this thread's paths that go on
     for (uint32_t j0 = 0; j0 < total; j0 += kBlock) {
@@ -1092,7 +1093,7 @@ constexpr bool f32_lds(unsigned feat, bool cache, bool partial, bool prims, bool
 // records {min.x, max.x, min.y, max.y | min.z, max.z, left, push ref} — SceneDev::nodes32 — fetched as two 16-byte loads from
 // L2 / HBM: half the bytes of the double-precision record per node step. (These scenes take the plain kernels even where the
 // partial-table instance would apply: with the first 3 045 of these records in LDS that instance — four waves per SIMD against
-// the plain kernel's five — measured 10 % slower on the 1e4-sphere scene, node_cache_mode.)
+// the plain kernel's five — measured 10 % slower on the 1e4-sphere scene, choose_trace.)
 // ... and for the triangle meshes (kFeatMisc, no boxes or media): a triangle touches its box in its corners, one node step in
 // 1 348 of wwscene is left undecided (its rings lie in the faces of theirs); C5's traversal kernel -3.2 % — once the ten VGPRs
 // the test needs were found: the RotateY stash is dropped in these instances (two divisions at a RotateY's exit instead;
@@ -1106,7 +1107,7 @@ constexpr bool f32_hbm(unsigned feat, bool cache, bool prims, bool spheres, bool
 // (a rect lies in the faces of its box, where that test decides nothing: see f32_lds).
 template <int STACK, bool STATS, unsigned FEAT, bool PROBE = false, int WG = kBlock, int CACHE = 0, bool PARTIAL = false, bool PRIMS = false, bool SPHERES = false>
 __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, WG)) wf_trace(const SceneDev s, const WfPool pool,
-                                                   const double t_min, const uint32_t node_quorum_u, const uint32_t parity, StatsDev *stats,
+                                                   const double t_min, const uint32_t tuning, const uint32_t parity, StatsDev *stats,
                                                    const uint32_t vote_weights) {
     // (Scene and pool by value: pointer members of kernel arguments are known to be global
     // memory, so node / ray fetches compile to global_load instead of flat_load, and none of
@@ -1229,9 +1230,9 @@ __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, W
     L.ctx.c0 = L.ctx.c1 = L.ctx.c2 = L.ctx.c3 = 0; L.ctx.n = 0;
     L.win_chain = L.ctx; L.win_leaf = REF_EMPTY; L.win_face = 0; L.win_mat = 0;
     L.stash_ix = 0.0; L.stash_iz = 0.0; L.stash_level = 0xFFFFFFFFu;
-    const int node_quorum = (int)(node_quorum_u & 0xFFu);
+    const int node_quorum = (int)tune::quorum(tuning);
     constexpr int tail_factor = 2;
-    const bool boxes_plain = (node_quorum_u >> 31) != 0;             // host: every node box finite with min <= max
+    const bool boxes_plain = tune::boxes_plain(tuning);              // host: every node box finite with min <= max
     unsigned census_rounds[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, census_lanes[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     // What the node fast path keeps in registers across its turns (r3). The library is built without MachineLICM (Makefile:
     // hoisted f64 literals were being spilled), so nothing hoists a loop's constants any more — and in THIS loop every
@@ -1920,7 +1921,7 @@ struct WfLaunch {
     WfPool pool;                // this group's view of the pool
     const RenderArgs *d_args;
     double t_min;
-    uint32_t node_quorum;
+    uint32_t tuning;
     uint32_t vote_weights;
     StatsDev *stats;
     uint32_t blocks;            // segments of the group
@@ -1928,6 +1929,10 @@ struct WfLaunch {
     bool ring = false;          // RenderArgs::ring in use: the shade pass's ring build
     bool rays = false;          // RenderArgs::rays in use: the shade pass's caller-ray build (rt_radiance*)
 };
+using TraceKernel = void (*)(SceneDev, WfPool, double, uint32_t, uint32_t, StatsDev *, uint32_t);
+// The all-in-LDS instance for sphere-only scenes (FEAT = 0): node table of kPrimNodes records and both sphere pools. (Named ahead of
+// the shade launcher: kernels go into the code object in the order the host code first mentions them, and this keeps that order.)
+constexpr TraceKernel kTraceAllInLds = wf_trace<kStackTiny, false, 0, false, kCacheBlock, kPrimNodes, false, true>;
 template <bool STATS>
 static void launch_shade(const WfLaunch &w, uint32_t parity) {
     if (w.rays) {
@@ -1936,6 +1941,7 @@ static void launch_shade(const WfLaunch &w, uint32_t parity) {
     } else if (w.ring) hipLaunchKernelGGL((wf_shade<STATS, true>), dim3(w.blocks), dim3(kBlock), 0, w.stream, w.scene, w.d_args, w.pool, parity);
     else hipLaunchKernelGGL((wf_shade<STATS, false>), dim3(w.blocks), dim3(kBlock), 0, w.stream, w.scene, w.d_args, w.pool, parity);
 }
+static void launch_shade(const WfLaunch &w, bool stats, uint32_t parity) { stats ? launch_shade<true>(w, parity) : launch_shade<false>(w, parity); }
 // Ring mode: out[i] = (first plane of the frame ? 0 : out[i]) + partial[first mod R][i] + ... in sample order — pixel_color += ...,
 // main.rs:150, continued where the last call of this kernel left off (chunk_sum_kernel's sum, taken a few planes at a time).
 __global__ void __launch_bounds__(256) ring_accumulate_kernel(const double *partial, double *out, uint64_t n_values, uint32_t first, uint32_t count, uint32_t ring) {
@@ -1948,184 +1954,217 @@ __global__ void __launch_bounds__(256) ring_accumulate_kernel(const double *part
     }
 }
 __global__ void ring_set_limit_kernel(unsigned long long *limit, unsigned long long value) { *limit = value; }
-// A scene whose every primitive is a sphere: the launchers' SPHERES (see f32_lds).
+
+// ---- which traversal kernel a call gets: one choice (choose_trace), one dispatch (launch_trace) ----
+// The facts that pick a wf_trace instance, as that instance has them for template arguments.
+enum TraceTable { kTablePlain, kTableWhole, kTablePartial, kTablePrims };
+struct TraceChoice {
+    // Node table in LDS (the 1024-thread variants, stacks of kStackTiny): none — the plain kernels; the whole table; its first
+    // kNodeCache records; or a sphere-only scene whose node table and sphere pools all fit (the all-in-LDS instance).
+    TraceTable table;
+    int stack;                  // STACK
+    unsigned feat;              // FEAT as instantiated (7 where the counters / the probe exist for the full kernel only)
+    bool stats, probe;          // STATS, PROBE
+    bool spheres;               // SPHERES: the scene is sphere-only and the instance exists in that flavour
+};
+// A scene whose every primitive is a sphere (see f32_lds).
 static bool sphere_only(const SceneDev &scene, unsigned features) { return features == 0 && scene.n_rects == 0; }
-template <int STACK, bool STATS, unsigned FEAT, bool PROBE = false>
-static void launch_trace(const WfLaunch &w, uint32_t parity) {
-    // A persistent grid: as many workgroups as the kernel's launch bounds keep resident, never more than the work
-    // (a segment holds at most 4096 / kChunk chunks for the 4 waves of a workgroup).
-    constexpr uint32_t per_cu = trace_blocks_per_cu(STACK, STATS, FEAT);
-    uint32_t grid = per_cu * (w.pool.n_cus ? w.pool.n_cus : 1u);
-    const uint32_t most = w.blocks * ((uint32_t)S / kChunk / 4u);
-    if (grid > most) grid = most;
-    if constexpr (FEAT == 0 && !STATS && !PROBE) {
-        if (sphere_only(w.scene, FEAT)) {                             // the instance that tests node boxes in single precision (kF32G)
-            hipLaunchKernelGGL((wf_trace<STACK, STATS, FEAT, PROBE, kBlock, 0, false, false, true>), dim3(grid), dim3(kBlock), 0, w.stream, w.scene, w.pool, w.t_min,
-                               w.node_quorum, parity, w.stats, w.vote_weights);
-            return;
-        }
-    }
-    hipLaunchKernelGGL((wf_trace<STACK, STATS, FEAT, PROBE>), dim3(grid), dim3(kBlock), 0, w.stream, w.scene, w.pool, w.t_min,
-                       w.node_quorum, parity, w.stats, w.vote_weights);
-}
-// The node-cache variant: one workgroup of kCacheBlock threads per CU (see wf_trace).
-template <unsigned FEAT, int STACK, int CACHE, bool PARTIAL>
-static void launch_trace_cached(const WfLaunch &w, uint32_t parity) {
-    uint32_t grid = w.pool.n_cus ? w.pool.n_cus : 1u;
-    const uint32_t most = std::max(1u, w.blocks * ((uint32_t)S / kChunk) / (uint32_t)(kCacheBlock / 64));
-    if (grid > most) grid = most;
-    if constexpr (FEAT == 0 && !PARTIAL) {
-        if (sphere_only(w.scene, FEAT)) {                             // (the single-precision records of t_slabs32 in the table)
-            hipLaunchKernelGGL((wf_trace<STACK, false, FEAT, false, kCacheBlock, CACHE, PARTIAL, false, true>), dim3(grid), dim3(kCacheBlock), 0, w.stream,
-                               w.scene, w.pool, w.t_min, w.node_quorum, parity, w.stats, w.vote_weights);
-            return;
-        }
-    }
-    hipLaunchKernelGGL((wf_trace<STACK, false, FEAT, false, kCacheBlock, CACHE, PARTIAL>), dim3(grid), dim3(kCacheBlock), 0, w.stream,
-                       w.scene, w.pool, w.t_min, w.node_quorum, parity, w.stats, w.vote_weights);
-}
-// The all-in-LDS instance for sphere-only scenes (FEAT = 0): node table of kPrimNodes records and both sphere pools.
-static void launch_trace_prims(const WfLaunch &w, uint32_t parity) {
-    uint32_t grid = w.pool.n_cus ? w.pool.n_cus : 1u;
-    const uint32_t most = std::max(1u, w.blocks * ((uint32_t)S / kChunk) / (uint32_t)(kCacheBlock / 64));
-    if (grid > most) grid = most;
-    hipLaunchKernelGGL((wf_trace<kStackTiny, false, 0, false, kCacheBlock, kPrimNodes, false, true>), dim3(grid), dim3(kCacheBlock), 0, w.stream,
-                       w.scene, w.pool, w.t_min, w.node_quorum, parity, w.stats, w.vote_weights);
-}
-template <int STACK, int CACHE, bool PARTIAL>
-static void launch_trace_cached_feat(unsigned feat, const WfLaunch &w, uint32_t parity) {
-    switch (feat & 7u) {
-        case 0: launch_trace_cached<0, STACK, CACHE, PARTIAL>(w, parity); break;
-        case 1: launch_trace_cached<1, STACK, CACHE, PARTIAL>(w, parity); break;
-        case 2: launch_trace_cached<2, STACK, CACHE, PARTIAL>(w, parity); break;
-        case 3: launch_trace_cached<3, STACK, CACHE, PARTIAL>(w, parity); break;
-        case 4: launch_trace_cached<4, STACK, CACHE, PARTIAL>(w, parity); break;
-        case 5: launch_trace_cached<5, STACK, CACHE, PARTIAL>(w, parity); break;
-        case 6: launch_trace_cached<6, STACK, CACHE, PARTIAL>(w, parity); break;
-        default: launch_trace_cached<7, STACK, CACHE, PARTIAL>(w, parity); break;
-    }
-}
-// Whether a scene takes the node-cache variant: its stacks fit the variant's, and its node table fits the cache whole.
-// (Bit 28 of the tuning word — rt_debug_set_tuning — or RT2022_NODE_CACHE=0 in the environment keeps the plain kernels:
-// A/B runs, and the test that the two give the same bits.)
-// 0: the plain kernels; 1: the whole table (stacks of 16); 2: its first kNodeCache records (stacks of 16); 3: a
-// sphere-only scene whose node table and sphere pools all fit (RT2022_PRIM_TABLES=0 in the environment: mode 1 instead).
-// The scenes whose plain kernels test node boxes in single precision on SceneDev::nodes32 (wf_trace: kF32G).
-static bool f32_from_hbm(const SceneDev &scene, unsigned features) {
-    return f32_hbm(features, false, false, sphere_only(scene, features), false, false);
-}
-static int node_cache_mode(const SceneDev &scene, uint32_t stack_need, uint32_t tuning, unsigned features) {
+// Which instance runs a scene's traversal passes: a constant of the call. Counters exist for FEAT = 7 only and never with a node
+// table; the probe exists per feature set for the small stack only, as FEAT = 7 for the deeper ones, never with a node table.
+// A scene takes a node-table variant when its stacks fit the variant's, and its node table fits the cache whole or — see below — in part.
+// (tune::kNoNodeTable — rt_debug_set_tuning — or RT2022_NODE_CACHE=0 in the environment keeps the plain kernels: A/B runs, and
+// the test that the two give the same bits. RT2022_PRIM_TABLES=0 in the environment: the whole table instead of all-in-LDS.)
+static TraceChoice choose_trace(const SceneDev &scene, uint32_t stack_need, uint32_t word, unsigned features, bool counters, bool probe) {
     static const bool enabled = [] { const char *e = getenv("RT2022_NODE_CACHE"); return !(e && e[0] == '0'); }();
     static const bool prims = [] { const char *e = getenv("RT2022_PRIM_TABLES"); return !(e && e[0] == '0'); }();
-    if (!enabled || (tuning & (1u << 28)) || stack_need > (uint32_t)kStackTiny) return 0;
-    if (prims && sphere_only(scene, features) && scene.n_nodes <= (uint32_t)kPrimNodes && scene.n_spheres <= (uint32_t)kPrimSpheres &&
-        scene.n_moving_spheres <= (uint32_t)kPrimMoving) return 3;
-    if (scene.n_nodes <= (uint32_t)kNodeCache) return 1;
-    // A scene whose nodes are tested in single precision from 32-byte records (sphere-only, or a triangle mesh: wf_trace, kF32G) takes
-    // the plain kernels when its table does not fit whole: five waves per SIMD there against four here, and half the bytes per node
-    // step either way — the partial table measured 10 % slower (1e4 spheres: 1 854 against 2 039 Mrays/s, profiles/r3zp_partial_vs_plain.log).
-    if (f32_from_hbm(scene, features)) return 0;
-    return 2;
+    const bool spheres = sphere_only(scene, features), lean = !counters && !probe;
+    TraceChoice c{kTablePlain, 0, features & 7u, counters, probe && !counters, false};
+    if (lean && enabled && !tune::no_node_table(word) && stack_need <= (uint32_t)kStackTiny) {
+        if (prims && spheres && scene.n_nodes <= (uint32_t)kPrimNodes && scene.n_spheres <= (uint32_t)kPrimSpheres &&
+            scene.n_moving_spheres <= (uint32_t)kPrimMoving) c.table = kTablePrims;
+        else if (scene.n_nodes <= (uint32_t)kNodeCache) c.table = kTableWhole;
+        // A scene whose nodes are tested in single precision from 32-byte records (sphere-only, or a triangle mesh: wf_trace, kF32G) takes
+        // the plain kernels when its table does not fit whole: five waves per SIMD there against four here, and half the bytes per node
+        // step either way — the partial table measured 10 % slower (1e4 spheres: 1 854 against 2 039 Mrays/s, profiles/r3zp_partial_vs_plain.log).
+        else if (!f32_hbm(features, false, false, spheres, false, false)) c.table = kTablePartial;
+    }
+    c.stack = c.table != kTablePlain ? kStackTiny : stack_need <= (uint32_t)kStackSmall ? kStackSmall : stack_need <= (uint32_t)kStackMid ? kStackMid : kStackLarge;
+    if (counters || (probe && c.stack != kStackSmall)) c.feat = 7;
+    // SPHERES: the instance that tests node boxes in single precision — on SceneDev::nodes32 in the plain kernels (kF32G), on the
+    // single-precision records of t_slabs32 in the whole table (the all-in-LDS instance has them as PRIMS).
+    c.spheres = spheres && lean && (c.table == kTablePlain || c.table == kTableWhole);
+    return c;
 }
-template <int STACK, bool PROBE = false>
-static void launch_trace_feat(unsigned feat, const WfLaunch &w, uint32_t parity) {
+// make(FEAT as a type) for a run-time feature set: the one place it becomes a template argument.
+template <class Make>
+static TraceKernel by_feat(unsigned feat, Make make) {
     switch (feat & 7u) {
-        case 0: launch_trace<STACK, false, 0, PROBE>(w, parity); break;
-        case 1: launch_trace<STACK, false, 1, PROBE>(w, parity); break;
-        case 2: launch_trace<STACK, false, 2, PROBE>(w, parity); break;
-        case 3: launch_trace<STACK, false, 3, PROBE>(w, parity); break;
-        case 4: launch_trace<STACK, false, 4, PROBE>(w, parity); break;
-        case 5: launch_trace<STACK, false, 5, PROBE>(w, parity); break;
-        case 6: launch_trace<STACK, false, 6, PROBE>(w, parity); break;
-        default: launch_trace<STACK, false, 7, PROBE>(w, parity); break;
+        case 0: return make(std::integral_constant<unsigned, 0>{});
+        case 1: return make(std::integral_constant<unsigned, 1>{});
+        case 2: return make(std::integral_constant<unsigned, 2>{});
+        case 3: return make(std::integral_constant<unsigned, 3>{});
+        case 4: return make(std::integral_constant<unsigned, 4>{});
+        case 5: return make(std::integral_constant<unsigned, 5>{});
+        case 6: return make(std::integral_constant<unsigned, 6>{});
+        default: return make(std::integral_constant<unsigned, 7>{});
     }
 }
-static void launch_pass(const WfLaunch &w, uint32_t parity, uint32_t stack_need, unsigned features, bool counters, bool probe,
-                        hipEvent_t between = nullptr) {
-    if (counters) launch_shade<true>(w, parity);
-    else launch_shade<false>(w, parity);
-    if (between) (void)hipEventRecord(between, w.stream);
-    const int table = (counters || probe) ? 0 : node_cache_mode(w.scene, stack_need, w.node_quorum, features);
-    if (table == 3) {
-        launch_trace_prims(w, parity);
-    } else if (table == 1) {
-        launch_trace_cached_feat<kStackTiny, kNodeCache, false>(features, w, parity);
-    } else if (table == 2) {
-        launch_trace_cached_feat<kStackTiny, kNodeCache, true>(features, w, parity);
-    } else if (stack_need <= (uint32_t)kStackSmall) {
-        if (counters) launch_trace<kStackSmall, true, 7>(w, parity);
-        else if (probe) launch_trace_feat<kStackSmall, true>(features, w, parity);   // (the probe exists per feature set for the small stack only)
-        else launch_trace_feat<kStackSmall>(features, w, parity);
-    } else if (stack_need <= (uint32_t)kStackMid) {
-        if (counters) launch_trace<kStackMid, true, 7>(w, parity);
-        else if (probe) launch_trace<kStackMid, false, 7, true>(w, parity);
-        else launch_trace_feat<kStackMid>(features, w, parity);
-    } else {
-        if (counters) launch_trace<kStackLarge, true, 7>(w, parity);
-        else if (probe) launch_trace<kStackLarge, false, 7, true>(w, parity);
-        else launch_trace_feat<kStackLarge>(features, w, parity);
+// Only the combinations named here are instantiated (58: each costs over a second of compile time).
+template <int STACK>
+static TraceKernel plain_kernel(const TraceChoice &c) {
+    if (c.stats) return wf_trace<STACK, true, 7>;
+    if (c.probe) {
+        if constexpr (STACK == kStackSmall) return by_feat(c.feat, [](auto f) -> TraceKernel { return wf_trace<STACK, false, decltype(f)::value, true>; });
+        else return wf_trace<STACK, false, 7, true>;
     }
+    if (c.spheres) return wf_trace<STACK, false, 0, false, kBlock, 0, false, false, true>;
+    return by_feat(c.feat, [](auto f) -> TraceKernel { return wf_trace<STACK, false, decltype(f)::value>; });
+}
+static TraceKernel trace_kernel(const TraceChoice &c) {
+    switch (c.table) {
+        case kTablePrims: return kTraceAllInLds;
+        case kTableWhole:
+            if (c.spheres) return wf_trace<kStackTiny, false, 0, false, kCacheBlock, kNodeCache, false, false, true>;
+            return by_feat(c.feat, [](auto f) -> TraceKernel { return wf_trace<kStackTiny, false, decltype(f)::value, false, kCacheBlock, kNodeCache, false>; });
+        case kTablePartial:
+            return by_feat(c.feat, [](auto f) -> TraceKernel { return wf_trace<kStackTiny, false, decltype(f)::value, false, kCacheBlock, kNodeCache, true>; });
+        default: break;
+    }
+    return c.stack == kStackSmall ? plain_kernel<kStackSmall>(c) : c.stack == kStackMid ? plain_kernel<kStackMid>(c) : plain_kernel<kStackLarge>(c);
+}
+// A persistent grid: as many workgroups as the kernel's launch bounds keep resident, never more than the work (a segment holds
+// at most 4096 / kChunk chunks for the 4 waves of a workgroup). The node-table variants: one workgroup of kCacheBlock threads
+// per CU (see wf_trace).
+static void launch_trace(const TraceChoice &c, const WfLaunch &w, uint32_t parity) {
+    const bool plain = c.table == kTablePlain;
+    const uint32_t cus = w.pool.n_cus ? w.pool.n_cus : 1u;
+    const uint32_t most = plain ? w.blocks * ((uint32_t)S / kChunk / 4u) : std::max(1u, w.blocks * ((uint32_t)S / kChunk) / (uint32_t)(kCacheBlock / 64));
+    const uint32_t grid = std::min(plain ? (uint32_t)trace_blocks_per_cu(c.stack, c.stats, c.feat) * cus : cus, most);
+    hipLaunchKernelGGL(trace_kernel(c), dim3(grid), dim3(plain ? kBlock : kCacheBlock), 0, w.stream, w.scene, w.pool, w.t_min,
+                       w.tuning, parity, w.stats, w.vote_weights);
+}
+static void launch_pass(const TraceChoice &c, const WfLaunch &w, uint32_t parity, hipEvent_t between = nullptr) {
+    launch_shade(w, c.stats, parity);
+    if (between) (void)hipEventRecord(between, w.stream);
+    launch_trace(c, w, parity);
 }
 
+// ---- the pass driver ----
+namespace {
 // The pool is cut into groups of segments, each on a stream of its own and alternating shade / trace passes
 // at its own pace: nothing couples the groups but the work counter, so while the last long rays of one
 // group's trace pass keep a few waves busy, the other groups' kernels fill the rest of the chip. (Measured
 // with one group: the mean wave lives 0.41 of a trace pass — rt_debug_pass_timing.)
-static hipError_t render_passes(const SceneDev &scene, const RenderArgs &args, const RenderArgs *d_args,
-                                const WfPool &pool, uint32_t stack_need, unsigned features, bool counters,
-                                const WfStreams &gs, hipStream_t stream, uint32_t *out_iterations, double *timing, KernelTimes *kt,
-                                const Progress *progress, const RingCtl *ring) {
-    if (stack_need > (uint32_t)kStackLarge) return hipErrorInvalidValue;
-    const bool report = progress && progress->cb && gs.h_work;
-    unsigned long long reported = 0;
+struct PassDriver {
+    struct Group {
+        WfLaunch w;
+        uint32_t iter = 0;      // passes enqueued
+        uint32_t batches = 0;   // batches enqueued
+        uint32_t waited = 0;    // batches whose answer has been read
+        bool drained = false;
+    };
+    WfRender &r;
+    const RenderArgs &args;
+    const WfPool &pool;
+    const WfStreams &gs;
+    double *const timing;
+    KernelTimes *const kt;
+    const bool report;
     // Ring of partial-sum planes (RenderArgs::ring): planes consumed so far, and the claim limit that follows them.
-    const bool ringed = ring && ring->planes > 0 && args.ring == ring->planes && gs.h_work && gs.h_oldest && args.ring_group > 0 &&
-                        args.ring % args.ring_group == 0 && args.n_chunks % args.ring_group == 0;
-    if (ring && ring->planes > 0 && !ringed) return hipErrorInvalidValue;
-    uint32_t consumed = 0;                      // planes added to the output so far (a multiple of the sample group)
-    const uint64_t n_values = args.n_pixels * 3;
-    const uint64_t per_group = ringed ? args.n_pixels * args.ring_group : 1;         // work items of one sample group
-    auto ring_limit = [&](uint32_t done) {      // the groups whose planes are free: those consumed, and R planes' worth beyond them
-        const unsigned long long lim = ((unsigned long long)done + ring->planes) / args.ring_group * per_group;
-        return lim < args.n_items ? lim : (unsigned long long)args.n_items;
-    };
-    auto ring_consume = [&](uint32_t upto, hipStream_t st) -> hipError_t {          // planes [consumed, upto) are complete
-        if (upto <= consumed) return hipSuccess;
-        const uint64_t want = (n_values + 255) / 256;
-        hipLaunchKernelGGL(ring_accumulate_kernel, dim3((unsigned)(want > 2048 ? 2048 : (want ? want : 1))), dim3(256), 0, st,
-                           args.partial, ring->out, n_values, consumed, upto - consumed, ring->planes);
-        consumed = upto;
-        hipLaunchKernelGGL(ring_set_limit_kernel, dim3(1), dim3(1), 0, st, ring->d_limit, ring_limit(consumed));
-        return hipGetLastError();
-    };
-    const uint32_t blocks = pool.n_blocks;
+    const bool ringed;
+    uint32_t consumed = 0;      // planes added to the output so far (a multiple of the sample group)
+    const uint64_t n_values, per_group;         // doubles of a plane; work items of one sample group
+    unsigned long long reported = 0;
+    TraceChoice choice{};
+    int G = 1;
+    Group grp[kMaxGroups];
+    uint32_t poll_every = 4, iterations = 0;
+
+    explicit PassDriver(WfRender &r_)
+        : r(r_), args(*r_.args), pool(*r_.pool), gs(*r_.gs), timing(r_.timing), kt(r_.kt), report(r_.progress.cb && gs.h_work),
+          ringed(r_.ring.planes > 0 && args.ring == r_.ring.planes && gs.h_work && gs.h_oldest && args.ring_group > 0 &&
+                 args.ring % args.ring_group == 0 && args.n_chunks % args.ring_group == 0),
+          n_values(args.n_pixels * 3), per_group(ringed ? args.n_pixels * args.ring_group : 1) {}
+    hipError_t run();
+    hipError_t init_pool();
+    hipError_t cut_groups();
+    hipError_t enqueue_batch(int g);
+    void report_progress(unsigned long long items);
+    hipError_t read_pass_timing(const Group &q, uint32_t rays);
+    void log_pass(const Group &q, const unsigned long long h[5], uint32_t rays);
+    unsigned long long ring_limit(uint32_t done) const;
+    hipError_t ring_consume(uint32_t upto, hipStream_t st);
+    hipError_t ring_advance(const Group &q, unsigned long long work, unsigned long long oldest);
+    hipError_t sum_kernel_times();
+};
+hipError_t PassDriver::run() {
+    if (r.stack_need > (uint32_t)kStackLarge) return hipErrorInvalidValue;
+    if (r.ring.planes > 0 && !ringed) return hipErrorInvalidValue;
+    choice = choose_trace(*r.scene, r.stack_need, args.tuning, r.features, r.counters, timing != nullptr);
     hipError_t e;
-    // Slots in use start FRESH (at most one work item per slot is ever needed at a time).
-    {
-        uint64_t per_block = (args.n_items + blocks - 1) / blocks;
-        uint32_t used = (uint32_t)(per_block > (uint64_t)S ? (uint64_t)S : (per_block + 63) / 64 * 64);
-        if (used < 64) used = 64;
-        uint32_t n = blocks * (uint32_t)S;
-        hipLaunchKernelGGL(wf_init, dim3((n + 255) / 256), dim3(256), 0, stream, pool.kind, pool.list, pool.list_n, n, used);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        if ((e = hipMemsetAsync(pool.n_active, 0, 2 * kMaxGroups * sizeof(uint32_t), stream)) != hipSuccess) return e;
-        if ((e = hipMemsetAsync(pool.max_list, 0, 2 * kMaxGroups * sizeof(uint32_t), stream)) != hipSuccess) return e;
-        if ((e = hipMemsetAsync(pool.fault, 0, sizeof(uint32_t), stream)) != hipSuccess) return e;
-        if (ringed) {
-            if ((e = hipMemsetAsync(pool.oldest, 0xFF, 2 * sizeof(unsigned long long), stream)) != hipSuccess) return e;
-            if ((e = hipMemsetAsync(pool.starved_n, 0, blocks * sizeof(uint32_t), stream)) != hipSuccess) return e;
-            hipLaunchKernelGGL(ring_set_limit_kernel, dim3(1), dim3(1), 0, stream, ring->d_limit, ring_limit(0));
-            if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = init_pool()) != hipSuccess) return e;
+    if ((e = cut_groups()) != hipSuccess) return e;
+    poll_every = timing ? 1 : 4;
+    // One batch = poll_every passes + a read-back of the group's "rays handed on" counter. Two batches per group
+    // are kept in flight so that a group's stream never runs empty while the host looks at the previous answer.
+    for (int g = 0; g < G; g++) {
+        if ((e = enqueue_batch(g)) != hipSuccess) return e;
+        if (!timing && (e = enqueue_batch(g)) != hipSuccess) return e;
+    }
+    int live = G;
+    while (live > 0) {
+        for (int g = 0; g < G; g++) {
+            Group &q = grp[g];
+            if (q.drained) continue;
+            const uint32_t at = 2 * g + (q.waited & 1u);            // the batch's words in the pinned arrays
+            if ((e = hipEventSynchronize(gs.ev[g][q.waited & 1u])) != hipSuccess) return e;
+            q.waited++;
+            if (report) report_progress(gs.h_work[at]);
+            if (timing && (e = read_pass_timing(q, gs.h_active[at])) != hipSuccess) return e;
+            if (ringed && (e = ring_advance(q, gs.h_work[at], gs.h_oldest[at])) != hipSuccess) return e;
+            if (gs.h_active[at] == 0) {         // the batch's last shade pass handed no ray on: the group has drained
+                q.drained = true;
+                live--;
+                continue;
+            }
+            if (q.iter > (1u << 26)) return hipErrorUnknown;
+            if ((e = enqueue_batch(g)) != hipSuccess) return e;
         }
     }
-    const uint32_t trace_blocks = blocks / pool.segs;
-    int G = (timing || kt || ringed) ? 1 : gs.n;       // (per-kernel times: one group, so that a launch's duration is its own; with several, launches of different groups overlap)
+    if (ringed && (e = ring_consume(args.n_chunks, grp[0].w.stream)) != hipSuccess) return e;      // (nothing is in flight any more)
+    for (int g = 0; g < G; g++)                 // (a drained group may still have an idle batch queued)
+        if ((e = hipStreamSynchronize(grp[g].w.stream)) != hipSuccess) return e;
+    if (kt && (e = sum_kernel_times()) != hipSuccess) return e;
+    r.passes = iterations;
+    return hipSuccess;
+}
+// Slots in use start FRESH (at most one work item per slot is ever needed at a time).
+hipError_t PassDriver::init_pool() {
+    const uint32_t blocks = pool.n_blocks;
+    hipError_t e;
+    uint64_t per_block = (args.n_items + blocks - 1) / blocks;
+    uint32_t used = (uint32_t)(per_block > (uint64_t)S ? (uint64_t)S : (per_block + 63) / 64 * 64);
+    if (used < 64) used = 64;
+    uint32_t n = blocks * (uint32_t)S;
+    hipLaunchKernelGGL(wf_init, dim3((n + 255) / 256), dim3(256), 0, r.stream, pool.kind, pool.list, pool.list_n, n, used);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(pool.n_active, 0, 2 * kMaxGroups * sizeof(uint32_t), r.stream)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(pool.max_list, 0, 2 * kMaxGroups * sizeof(uint32_t), r.stream)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(pool.fault, 0, sizeof(uint32_t), r.stream)) != hipSuccess) return e;
+    if (ringed) {
+        if ((e = hipMemsetAsync(pool.oldest, 0xFF, 2 * sizeof(unsigned long long), r.stream)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(pool.starved_n, 0, blocks * sizeof(uint32_t), r.stream)) != hipSuccess) return e;
+        hipLaunchKernelGGL(ring_set_limit_kernel, dim3(1), dim3(1), 0, r.stream, r.ring.d_limit, ring_limit(0));
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+// Every group's view of the pool, and its stream behind the caller's.
+hipError_t PassDriver::cut_groups() {
+    const uint32_t trace_blocks = pool.n_blocks / pool.segs;
+    G = (timing || kt || ringed) ? 1 : gs.n;    // (per-kernel times: one group, so that a launch's duration is its own; with several, launches of different groups overlap)
     if (G < 1) G = 1;
     if ((uint32_t)G > trace_blocks) G = (int)trace_blocks;
-    WfLaunch w[kMaxGroups];
-    uint32_t iter[kMaxGroups] = {};
-    uint32_t batches[kMaxGroups] = {};          // batches enqueued
-    bool drained[kMaxGroups] = {};
     for (int g = 0; g < G; g++) {
         const uint32_t tb0 = (uint32_t)((uint64_t)trace_blocks * g / G), tb1 = (uint32_t)((uint64_t)trace_blocks * (g + 1) / G);
         const uint32_t seg_begin = tb0 * pool.segs, n_segs = (tb1 - tb0) * pool.segs;
@@ -2137,139 +2176,141 @@ static hipError_t render_passes(const SceneDev &scene, const RenderArgs &args, c
         v.n_active = pool.n_active + 2 * g;
         v.next_chunk = pool.next_chunk + g;
         v.max_list = pool.max_list + 2 * g;
-        w[g] = WfLaunch{scene, v, d_args, args.t_min, args.node_quorum, args.vote_weights, args.stats, n_segs, G == 1 ? stream : gs.stream[g], ringed,
-                        args.rays != nullptr};
+        grp[g].w = WfLaunch{*r.scene, v, r.d_args, args.t_min, args.tuning, args.vote_weights, args.stats, n_segs,
+                            G == 1 ? r.stream : gs.stream[g], ringed, args.rays != nullptr};
     }
+    hipError_t e;
     if (G > 1) {                                // the groups start after what the caller's stream holds so far
-        if ((e = hipEventRecord(gs.ev[0][0], stream)) != hipSuccess) return e;
+        if ((e = hipEventRecord(gs.ev[0][0], r.stream)) != hipSuccess) return e;
         for (int g = 0; g < G; g++)
             if ((e = hipStreamWaitEvent(gs.stream[g], gs.ev[0][0], 0)) != hipSuccess) return e;
         if ((e = hipEventSynchronize(gs.ev[0][0])) != hipSuccess) return e;     // (the event is reused below)
     }
-    const uint32_t poll_every = timing ? 1 : 4;
-    uint32_t iterations = 0;
-    // One batch = poll_every passes + a read-back of the group's "rays handed on" counter. Two batches per group
-    // are kept in flight so that a group's stream never runs empty while the host looks at the previous answer.
-    auto enqueue_batch = [&](int g) -> hipError_t {
-        for (uint32_t k = 0; k < poll_every; k++) {
-            if (timing) {
-                if ((e = hipMemsetAsync(pool.dbg, 0xFF, sizeof(unsigned long long), w[g].stream)) != hipSuccess) return e;
-                if ((e = hipMemsetAsync(pool.dbg + 1, 0, 4 * sizeof(unsigned long long), w[g].stream)) != hipSuccess) return e;
-            }
-            // (kernel times: three events per pass pair k, on the stream of its group — 3k before its shade pass, 3k+1 between its shade
-            // and trace pass, 3k+2 after: with several groups the pairs of different groups overlap, each launch's own duration is what
-            // is summed)
-            hipEvent_t mid = nullptr;
-            if (kt) {
-                while (kt->ev.size() < 3 * (size_t)iterations + 3) {
-                    hipEvent_t ne = nullptr;
-                    if ((e = hipEventCreate(&ne)) != hipSuccess) return e;
-                    kt->ev.push_back(ne);
-                }
-                if ((e = hipEventRecord(kt->ev[3 * iterations], w[g].stream)) != hipSuccess) return e;
-                mid = kt->ev[3 * iterations + 1];
-            }
-            launch_pass(w[g], iter[g] & 1u, stack_need, features, counters, timing != nullptr, mid);
-            if (kt && (e = hipEventRecord(kt->ev[3 * iterations + 2], w[g].stream)) != hipSuccess) return e;
-            iter[g]++;
-            iterations++;
-        }
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        const uint32_t b = batches[g]++ & 1u;   // ring of two: batches of a group complete in order
-        if ((e = hipMemcpyAsync(gs.h_active + 2 * g + b, w[g].pool.n_active + ((iter[g] - 1) & 1u), sizeof(uint32_t),
-                                hipMemcpyDeviceToHost, w[g].stream)) != hipSuccess) return e;
-        if ((report || ringed) && (e = hipMemcpyAsync(gs.h_work + 2 * g + b, args.work_counter, sizeof(unsigned long long),
-                                                      hipMemcpyDeviceToHost, w[g].stream)) != hipSuccess) return e;
-        if (ringed && (e = hipMemcpyAsync(gs.h_oldest + 2 * g + b, w[g].pool.oldest + ((iter[g] - 1) & 1u), sizeof(unsigned long long),
-                                          hipMemcpyDeviceToHost, w[g].stream)) != hipSuccess) return e;
-        return hipEventRecord(gs.ev[g][b], w[g].stream);
-    };
-    uint32_t waited[kMaxGroups] = {};           // batches whose answer has been read
-    for (int g = 0; g < G; g++) {
-        if ((e = enqueue_batch(g)) != hipSuccess) return e;
-        if (!timing && (e = enqueue_batch(g)) != hipSuccess) return e;
-    }
-    int live = G;
-    while (live > 0) {
-        for (int g = 0; g < G; g++) {
-            if (drained[g]) continue;
-            const uint32_t b = waited[g] & 1u;
-            if ((e = hipEventSynchronize(gs.ev[g][b])) != hipSuccess) return e;
-            waited[g]++;
-            if (report) {                       // work items handed out so far -> camera paths started (main.rs:154-155: the bar's inc)
-                unsigned long long items = gs.h_work[2 * g + b];
-                if (items > args.n_items) items = args.n_items;       // (the counter overshoots at the end of the work)
-                unsigned long long paths = items * progress->per_item;
-                if (paths > progress->total) paths = progress->total;
-                if (paths > reported && paths < progress->total) { reported = paths; progress->cb(progress->user, 0u, paths, progress->total); }
-            }
-            if (timing) {
-                unsigned long long h[5];
-                if ((e = hipMemcpy(h, pool.dbg, sizeof h, hipMemcpyDeviceToHost)) != hipSuccess) return e;
-                if (h[4]) {
-                    timing[0] += (double)(h[1] - h[0]);                // span of the pass
-                    timing[1] += (double)h[2] / (double)h[4];          // mean wave lifetime
-                    timing[2] += (double)h[3] / (double)h[4];          // mean wave time after its list ran dry
-                    timing[3] += 1.0;
-                    timing[4] += (double)h[4];
-                    if (getenv("RT2022_PASS_LOG") && (iter[g] == 50 || iter[g] == 51 || iter[g] == 80)) {      // wave 0 of every workgroup
-                        const uint32_t nb = (uint32_t)(h[4] / 4);                 // (workgroups of the persistent grid that ran)
-                        std::vector<unsigned long long> bt(2 * nb);
-                        if (hipMemcpy(bt.data(), pool.dbg + 8, bt.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess) {
-                            std::vector<double> st_, en_;
-                            for (uint32_t b = 0; b < nb; b++) {
-                                st_.push_back((double)(bt[2 * b] - h[0]) / 100.0); en_.push_back((double)(bt[2 * b + 1] - h[0]) / 100.0);
-                            }
-                            if (const char *dump = getenv("RT2022_BLOCK_DUMP")) {
-                                char name[512];
-                                snprintf(name, sizeof name, "%s.%u", dump, iter[g]);
-                                if (FILE *f = fopen(name, "w")) { for (uint32_t b = 0; b < nb; b++) fprintf(f, "%u %.1f %.1f\n", b, st_[b], en_[b]); fclose(f); }
-                            }
-                            std::sort(st_.begin(), st_.end()); std::sort(en_.begin(), en_.end());
-                            fprintf(stderr, "pass %u workgroups %u: start us p0 %.1f p50 %.1f p100 %.1f | end us p0 %.1f p10 %.1f p50 %.1f p90 %.1f p100 %.1f\n", iter[g], nb,
-                                    st_[0], st_[nb / 2], st_[nb - 1], en_[0], en_[nb / 10], en_[nb / 2], en_[nb * 9 / 10], en_[nb - 1]);
-                        }
-                    }
-                    if (getenv("RT2022_PASS_LOG"))
-                        fprintf(stderr, "pass %u span_us %.1f life/span %.3f dry/life %.3f waves %llu rays %u\n", iter[g], (double)(h[1] - h[0]) / 100.0,
-                                (double)h[2] / (double)h[4] / (double)(h[1] - h[0]), (double)h[3] / (double)(h[2] ? h[2] : 1), h[4], gs.h_active[2 * g + b]);
-                }
-            }
-            if (ringed) {
-                // Everything below the oldest item in flight (and below the counter: items not handed out yet are not in flight
-                // either) is finished: whole planes under that frontier go to the output, and the limit follows them. (The words
-                // were copied behind the batch's last shade pass; the kernels launched here run behind the batches already queued,
-                // whose claims still obey the old limit.)
-                unsigned long long groups_done = (gs.h_work[2 * g + b] < args.n_items ? gs.h_work[2 * g + b] : (unsigned long long)args.n_items) / per_group;
-                if (gs.h_oldest[2 * g + b] < groups_done) groups_done = gs.h_oldest[2 * g + b];
-                if ((e = ring_consume((uint32_t)groups_done * args.ring_group, w[g].stream)) != hipSuccess) return e;
-                if (ring->max_passes && iterations > ring->max_passes) return hipErrorUnknown;     // (a frame cannot take this long: never spin)
-            }
-            if (gs.h_active[2 * g + b] == 0) {  // the batch's last shade pass handed no ray on: the group has drained
-                drained[g] = true;
-                live--;
-                continue;
-            }
-            if (iter[g] > (1u << 26)) return hipErrorUnknown;
-            if ((e = enqueue_batch(g)) != hipSuccess) return e;
-        }
-    }
-    if (ringed && (e = ring_consume(args.n_chunks, w[0].stream)) != hipSuccess) return e;      // (nothing is in flight any more)
-    for (int g = 0; g < G; g++)                 // (a drained group may still have an idle batch queued)
-        if ((e = hipStreamSynchronize(w[g].stream)) != hipSuccess) return e;
-    if (kt) {                                   // device time of the shade passes and of the trace passes
-        kt->shade_ms = kt->trace_ms = 0.0;
-        for (uint32_t k = 0; k < iterations; k++) {
-            float a = 0.f, b = 0.f;
-            if ((e = hipEventElapsedTime(&a, kt->ev[3 * k], kt->ev[3 * k + 1])) != hipSuccess) return e;
-            if ((e = hipEventElapsedTime(&b, kt->ev[3 * k + 1], kt->ev[3 * k + 2])) != hipSuccess) return e;
-            kt->shade_ms += (double)a;
-            kt->trace_ms += (double)b;
-        }
-    }
-    if (out_iterations) *out_iterations = iterations;
     return hipSuccess;
 }
+hipError_t PassDriver::enqueue_batch(int g) {
+    Group &q = grp[g];
+    const hipStream_t st = q.w.stream;
+    hipError_t e;
+    for (uint32_t k = 0; k < poll_every; k++) {
+        if (timing) {
+            if ((e = hipMemsetAsync(pool.dbg, 0xFF, sizeof(unsigned long long), st)) != hipSuccess) return e;
+            if ((e = hipMemsetAsync(pool.dbg + 1, 0, 4 * sizeof(unsigned long long), st)) != hipSuccess) return e;
+        }
+        // (kernel times: three events per pass pair k, on the stream of its group — 3k before its shade pass, 3k+1 between its shade
+        // and trace pass, 3k+2 after: with several groups the pairs of different groups overlap, each launch's own duration is what
+        // is summed)
+        hipEvent_t mid = nullptr;
+        if (kt) {
+            while (kt->ev.size() < 3 * (size_t)iterations + 3) {
+                hipEvent_t ne = nullptr;
+                if ((e = hipEventCreate(&ne)) != hipSuccess) return e;
+                kt->ev.push_back(ne);
+            }
+            if ((e = hipEventRecord(kt->ev[3 * iterations], st)) != hipSuccess) return e;
+            mid = kt->ev[3 * iterations + 1];
+        }
+        launch_pass(choice, q.w, q.iter & 1u, mid);
+        if (kt && (e = hipEventRecord(kt->ev[3 * iterations + 2], st)) != hipSuccess) return e;
+        q.iter++;
+        iterations++;
+    }
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    const uint32_t b = q.batches++ & 1u, at = 2 * g + b;     // ring of two: batches of a group complete in order
+    const uint32_t parity = (q.iter - 1) & 1u;  // (of the batch's last pass)
+    if ((e = hipMemcpyAsync(gs.h_active + at, q.w.pool.n_active + parity, sizeof(uint32_t), hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+    if ((report || ringed) && (e = hipMemcpyAsync(gs.h_work + at, args.work_counter, sizeof(unsigned long long),
+                                                  hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+    if (ringed && (e = hipMemcpyAsync(gs.h_oldest + at, q.w.pool.oldest + parity, sizeof(unsigned long long),
+                                      hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+    return hipEventRecord(gs.ev[g][b], st);
+}
+// Work items handed out so far -> camera paths started (main.rs:154-155: the bar's inc).
+void PassDriver::report_progress(unsigned long long items) {
+    if (items > args.n_items) items = args.n_items;       // (the counter overshoots at the end of the work)
+    unsigned long long paths = items * r.progress.per_item;
+    if (paths > r.progress.total) paths = r.progress.total;
+    if (paths > reported && paths < r.progress.total) { reported = paths; r.progress.cb(r.progress.user, 0u, paths, r.progress.total); }
+}
+// The probe's words of the pass just waited for (poll_every is 1), added to rt_debug_pass_timing's sums.
+hipError_t PassDriver::read_pass_timing(const Group &q, uint32_t rays) {
+    unsigned long long h[5];
+    hipError_t e;
+    if ((e = hipMemcpy(h, pool.dbg, sizeof h, hipMemcpyDeviceToHost)) != hipSuccess) return e;
+    if (!h[4]) return hipSuccess;
+    timing[0] += (double)(h[1] - h[0]);                // span of the pass
+    timing[1] += (double)h[2] / (double)h[4];          // mean wave lifetime
+    timing[2] += (double)h[3] / (double)h[4];          // mean wave time after its list ran dry
+    timing[3] += 1.0;
+    timing[4] += (double)h[4];
+    if (getenv("RT2022_PASS_LOG")) log_pass(q, h, rays);
+    return hipSuccess;
+}
+// RT2022_PASS_LOG: one line per pass; for three passes also when wave 0 of every workgroup started and ended (RT2022_BLOCK_DUMP=
+// file prefix: every workgroup's pair).
+void PassDriver::log_pass(const Group &q, const unsigned long long h[5], uint32_t rays) {
+    if (q.iter == 50 || q.iter == 51 || q.iter == 80) {
+        const uint32_t nb = (uint32_t)(h[4] / 4);                 // (workgroups of the persistent grid that ran)
+        std::vector<unsigned long long> bt(2 * nb);
+        if (hipMemcpy(bt.data(), pool.dbg + 8, bt.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess) {
+            std::vector<double> st_, en_;
+            for (uint32_t b = 0; b < nb; b++) {
+                st_.push_back((double)(bt[2 * b] - h[0]) / 100.0); en_.push_back((double)(bt[2 * b + 1] - h[0]) / 100.0);
+            }
+            if (const char *dump = getenv("RT2022_BLOCK_DUMP")) {
+                char name[512];
+                snprintf(name, sizeof name, "%s.%u", dump, q.iter);
+                if (FILE *f = fopen(name, "w")) { for (uint32_t b = 0; b < nb; b++) fprintf(f, "%u %.1f %.1f\n", b, st_[b], en_[b]); fclose(f); }
+            }
+            std::sort(st_.begin(), st_.end()); std::sort(en_.begin(), en_.end());
+            fprintf(stderr, "pass %u workgroups %u: start us p0 %.1f p50 %.1f p100 %.1f | end us p0 %.1f p10 %.1f p50 %.1f p90 %.1f p100 %.1f\n", q.iter, nb,
+                    st_[0], st_[nb / 2], st_[nb - 1], en_[0], en_[nb / 10], en_[nb / 2], en_[nb * 9 / 10], en_[nb - 1]);
+        }
+    }
+    fprintf(stderr, "pass %u span_us %.1f life/span %.3f dry/life %.3f waves %llu rays %u\n", q.iter, (double)(h[1] - h[0]) / 100.0,
+            (double)h[2] / (double)h[4] / (double)(h[1] - h[0]), (double)h[3] / (double)(h[2] ? h[2] : 1), h[4], rays);
+}
+// The groups whose planes are free: those consumed, and R planes' worth beyond them.
+unsigned long long PassDriver::ring_limit(uint32_t done) const {
+    const unsigned long long lim = ((unsigned long long)done + r.ring.planes) / args.ring_group * per_group;
+    return lim < args.n_items ? lim : (unsigned long long)args.n_items;
+}
+// Planes [consumed, upto) are complete: add them to the output and raise the claim limit behind them.
+hipError_t PassDriver::ring_consume(uint32_t upto, hipStream_t st) {
+    if (upto <= consumed) return hipSuccess;
+    const uint64_t want = (n_values + 255) / 256;
+    hipLaunchKernelGGL(ring_accumulate_kernel, dim3((unsigned)(want > 2048 ? 2048 : (want ? want : 1))), dim3(256), 0, st,
+                       args.partial, r.ring.out, n_values, consumed, upto - consumed, r.ring.planes);
+    consumed = upto;
+    hipLaunchKernelGGL(ring_set_limit_kernel, dim3(1), dim3(1), 0, st, r.ring.d_limit, ring_limit(consumed));
+    return hipGetLastError();
+}
+// Everything below the oldest item in flight (and below the counter: items not handed out yet are not in flight
+// either) is finished: whole planes under that frontier go to the output, and the limit follows them. (The words
+// were copied behind the batch's last shade pass; the kernels launched here run behind the batches already queued,
+// whose claims still obey the old limit.)
+hipError_t PassDriver::ring_advance(const Group &q, unsigned long long work, unsigned long long oldest) {
+    unsigned long long groups_done = (work < args.n_items ? work : (unsigned long long)args.n_items) / per_group;
+    if (oldest < groups_done) groups_done = oldest;
+    hipError_t e;
+    if ((e = ring_consume((uint32_t)groups_done * args.ring_group, q.w.stream)) != hipSuccess) return e;
+    if (r.ring.max_passes && iterations > r.ring.max_passes) return hipErrorUnknown;     // (a frame cannot take this long: never spin)
+    return hipSuccess;
+}
+// Device time of the shade passes and of the trace passes.
+hipError_t PassDriver::sum_kernel_times() {
+    hipError_t e;
+    kt->shade_ms = kt->trace_ms = 0.0;
+    for (uint32_t k = 0; k < iterations; k++) {
+        float a = 0.f, b = 0.f;
+        if ((e = hipEventElapsedTime(&a, kt->ev[3 * k], kt->ev[3 * k + 1])) != hipSuccess) return e;
+        if ((e = hipEventElapsedTime(&b, kt->ev[3 * k + 1], kt->ev[3 * k + 2])) != hipSuccess) return e;
+        kt->shade_ms += (double)a;
+        kt->trace_ms += (double)b;
+    }
+    return hipSuccess;
+}
+} // namespace
 
 hipError_t f32_slab_census(unsigned long long out[5]) {
     unsigned long long c[3] = {0, 0, 0};
@@ -2286,66 +2327,63 @@ hipError_t f32_slab_census(unsigned long long out[5]) {
     return e;
 }
 
+// From the same choice as the launches, asking f32_lds / f32_hbm with the choice's own template facts (bit 1 of out[3]: the
+// instance tests node boxes in single precision — wf_trace: kF32, kF32G).
 void trace_variant(const SceneDev &scene, uint32_t stack_need, uint32_t tuning, unsigned features, uint32_t out[4]) {
-    out[3] = 0;
-    const int table = node_cache_mode(scene, stack_need, tuning, features);
-    // Whether the instance launch_pass picks tests node boxes in single precision (wf_trace: kF32, kF32G) — bit 1 of out[3] — from the
-    // facts it passes that instance as template arguments: mode 3 is PRIMS, 2 PARTIAL, and SPHERES is set by mode 1's launcher only.
-    const bool f32 = table == 0 ? f32_from_hbm(scene, features)
-                   : f32_lds(features, true, table == 2, table == 3, table == 1 && sphere_only(scene, features));
-    if (table) {
-        out[0] = (uint32_t)kCacheBlock; out[1] = (uint32_t)kStackTiny; out[2] = scene.n_nodes < (uint32_t)kNodeCache ? scene.n_nodes : (uint32_t)kNodeCache;
-        out[3] = (table == 3 ? 1u : 0u) | (f32 ? 2u : 0u);
-        return;
-    }
-    out[0] = (uint32_t)kBlock;
-    out[1] = stack_need <= (uint32_t)kStackSmall ? (uint32_t)kStackSmall : stack_need <= (uint32_t)kStackMid ? (uint32_t)kStackMid : (uint32_t)kStackLarge;
-    out[2] = 0;
-    out[3] = f32 ? 2u : 0u;
+    const TraceChoice c = choose_trace(scene, stack_need, tuning, features, false, false);
+    const bool table = c.table != kTablePlain;
+    const bool f32 = table ? f32_lds(c.feat, true, c.table == kTablePartial, c.table == kTablePrims, c.spheres)
+                           : f32_hbm(c.feat, false, false, c.spheres, c.stats, c.probe);
+    out[0] = (uint32_t)(table ? kCacheBlock : kBlock);
+    out[1] = (uint32_t)c.stack;
+    out[2] = !table ? 0u : scene.n_nodes < (uint32_t)kNodeCache ? scene.n_nodes : (uint32_t)kNodeCache;
+    out[3] = (c.table == kTablePrims ? 1u : 0u) | (f32 ? 2u : 0u);
 }
 
-hipError_t launch_render_wavefront(const SceneDev &scene, const RenderArgs &args, const RenderArgs *d_args,
-                                   const WfPool &pool, uint32_t stack_need, unsigned features, bool counters,
-                                   const WfStreams &gs, hipStream_t stream, uint32_t *out_iterations, double *timing,
-                                   uint32_t *out_fault, KernelTimes *kt, const Progress *progress, const RingCtl *ring) {
-    hipError_t e = render_passes(scene, args, d_args, pool, stack_need, features, counters, gs, stream, out_iterations, timing, kt, progress, ring);
+// Diagnostic builds: what the section clocks of the traversal / shade kernels added up to over the render.
+#ifdef RT2022_TRACE_PROBE
+static void print_trace_probe(const WfPool &pool) {
+    unsigned long long h[12];
+    if (hipMemcpy(h, pool.dbg + 96, sizeof h, hipMemcpyDeviceToHost) == hipSuccess) {
+        static const char *const names[12] = {"node_fast", "vote", "node", "sphere", "rect", "box", "medium", "misc", "ctx", "done", "rest", "-"};
+        double tot = 0; for (int i = 0; i < 11; i++) tot += (double)h[i];
+        fprintf(stderr, "trace probe (shader-clock ticks of all waves and passes; share):");
+        for (int i = 0; i < 11; i++) fprintf(stderr, " %s %.3f", names[i], tot > 0 ? (double)h[i] / tot : 0.0);
+        fprintf(stderr, "  total %.3e ticks\n", tot);
+    }
+    (void)hipMemset(pool.dbg + 96, 0, 12 * sizeof(unsigned long long));
+}
+#endif
+#ifdef RT2022_SHADE_PROBE
+static void print_shade_probe(const WfPool &pool) {
+    unsigned long long h[10];
+    if (hipMemcpy(h, pool.dbg + 64, sizeof h, hipMemcpyDeviceToHost) == hipSuccess) {
+        double tot = 0; for (int i = 0; i < 8; i++) tot += (double)h[i];
+        fprintf(stderr, "shade probe (ticks of wave 0, all workgroups and passes; share):");
+        for (int i = 0; i < 8; i++) fprintf(stderr, " [%d] %.3f", i, tot > 0 ? (double)h[i] / tot : 0.0);
+        fprintf(stderr, "  total %.3e ticks\n", tot);
+    }
+    (void)hipMemset(pool.dbg + 64, 0, 10 * sizeof(unsigned long long));
+}
+#endif
+
+hipError_t launch_render_wavefront(WfRender &r) {
+    hipError_t e = PassDriver(r).run();
     if (e != hipSuccess) {
         // Passes may still be queued or running against the pool on the group streams: let them finish (best
         // effort) before the caller sees the error and possibly frees or reuses the pool.
         for (int g = 0; g < kMaxGroups; g++)
-            if (gs.stream[g]) (void)hipStreamSynchronize(gs.stream[g]);
-        (void)hipStreamSynchronize(stream);
+            if (r.gs->stream[g]) (void)hipStreamSynchronize(r.gs->stream[g]);
+        (void)hipStreamSynchronize(r.stream);
         return e;
     }
 #ifdef RT2022_TRACE_PROBE
-    if (pool.dbg) {
-        unsigned long long h[12];
-        if (hipMemcpy(h, pool.dbg + 96, sizeof h, hipMemcpyDeviceToHost) == hipSuccess) {
-            static const char *const names[12] = {"node_fast", "vote", "node", "sphere", "rect", "box", "medium", "misc", "ctx", "done", "rest", "-"};
-            double tot = 0; for (int i = 0; i < 11; i++) tot += (double)h[i];
-            fprintf(stderr, "trace probe (shader-clock ticks of all waves and passes; share):");
-            for (int i = 0; i < 11; i++) fprintf(stderr, " %s %.3f", names[i], tot > 0 ? (double)h[i] / tot : 0.0);
-            fprintf(stderr, "  total %.3e ticks\n", tot);
-        }
-        (void)hipMemset(pool.dbg + 96, 0, 12 * sizeof(unsigned long long));
-    }
+    if (r.pool->dbg) print_trace_probe(*r.pool);
 #endif
 #ifdef RT2022_SHADE_PROBE
-    if (pool.dbg) {
-        unsigned long long h[10];
-        if (hipMemcpy(h, pool.dbg + 64, sizeof h, hipMemcpyDeviceToHost) == hipSuccess) {
-            double tot = 0; for (int i = 0; i < 8; i++) tot += (double)h[i];
-            fprintf(stderr, "shade probe (ticks of wave 0, all workgroups and passes; share):");
-            for (int i = 0; i < 8; i++) fprintf(stderr, " [%d] %.3f", i, tot > 0 ? (double)h[i] / tot : 0.0);
-            fprintf(stderr, "  total %.3e ticks\n", tot);
-        }
-        (void)hipMemset(pool.dbg + 64, 0, 10 * sizeof(unsigned long long));
-    }
+    if (r.pool->dbg) print_shade_probe(*r.pool);
 #endif
-    uint32_t fault = 0;
-    if ((e = hipMemcpy(&fault, pool.fault, sizeof fault, hipMemcpyDeviceToHost)) != hipSuccess) return e;
-    if (out_fault) *out_fault = fault;
-    return hipSuccess;
+    return hipMemcpy(&r.fault, r.pool->fault, sizeof r.fault, hipMemcpyDeviceToHost);
 }
 
 } // namespace rt2022

@@ -327,7 +327,7 @@ struct rt_scene {
     unsigned features = 7;
     bool general_boundaries = false;
     bool boxes_plain = false;         // every node box finite with min <= max: the short node step applies
-    uint32_t node_quorum = 18u | (1u << 8) | (2u << 12) | ((uint32_t)(8 * 4096 / kSlotsPerBlock > 0 ? 8 * 4096 / kSlotsPerBlock : 1) << 16) | (2u << 20) | (0u << 24);   // fast-path quorum 18 lanes; one extra sphere test per turn; tail factor 2; pool of 8 segments per resident trace workgroup (4 per CU: 8192 segments = 33.5 M slots); list classes of 4 node steps; groups of segments: the library's choice (0)
+    uint32_t tuning = tune::kDefault;          // the tuning word (pt_device.h, namespace tune)
     uint32_t vote_weights = 0;                 // 0: the wavefront engine's default (kWfVoteWeights, pt_device.h)
     int engine = 1;                   // 0 = megakernel, 1 = wavefront (shade / trace passes)
     unsigned long long census_rounds[9] = {}, census_lanes[9] = {};   // of the last counter run
@@ -461,6 +461,71 @@ struct RaySource {
 static_assert(sizeof(rt_radiance_ray) == 64 && offsetof(rt_radiance_ray, time) == 48 && offsetof(rt_radiance_ray, rng_state) == 56,
               "rt_radiance_ray is the path slot's ray record {ox, oy, oz, dx, dy, dz, tm, rng}: wf_shade reads it in four 16-byte pieces");
 
+// Ring of partial-sum planes (pt_device.h, RenderArgs::ring): one-sample work items of the wavefront engine only. Automatic
+// when all spp planes would take more than 40 % of the device's memory (115 GB on an MI355X: C5's 99.5 GB stay below it —
+// the ring's work-item order costs its traversal 10 %, the headline's 1.4 %: profiles/r3j_ring.log): then at most 24 GiB
+// of planes; rt_debug_set_partial_ring forces a size (tests: down to one plane) or switches it off.
+struct RingPlan { uint32_t planes = 0, group = 1; };       // RenderArgs::ring, ring_group (0 planes: no ring)
+RingPlan plan_ring(uint32_t chunk, uint32_t n_chunks, uint64_t n_pixels, uint64_t n_items, int forced_planes, int forced_group, uint64_t threshold_bytes) {
+    RingPlan r;
+    if (chunk != 1 || n_chunks <= 1 || n_pixels == 0 || forced_planes < 0) return r;
+    uint32_t want = 0;
+    const uint64_t plane = n_pixels * 3 * sizeof(double);
+    if (forced_planes > 0) want = (uint32_t)forced_planes;
+    else if (n_items * 3 * sizeof(double) > threshold_bytes) want = (uint32_t)std::max<uint64_t>(8, (24ull << 30) / plane);
+    if (!want || want >= n_chunks) return r;
+    // samples are taken in groups: the largest divisor of spp up to 25 (and up to a quarter of the ring, so that it holds
+    // a few groups); the ring is a whole number of groups. (A group's planes are free again only when its last straggler
+    // has ended, ~60 passes after its first claim: the ring must hold what is claimed meanwhile — measured on C5: five
+    // groups of 50 stall every pool fill, twenty of 25 never.)
+    uint32_t grp = 1;
+    const uint32_t group_max = forced_group > 0 ? (uint32_t)forced_group : 25u;
+    for (uint32_t d = 1; d <= group_max && d * 4u <= std::max(want, 4u); d++) if (n_chunks % d == 0) grp = d;
+    if (grp > want) grp = 1;
+    r.group = grp;
+    r.planes = want / grp * grp;
+    if (r.planes == 0 || r.planes >= n_chunks) r = RingPlan{};
+    return r;
+}
+
+// Pool of the wavefront engine = segments of 4096 path slots (one shade workgroup each). The trace pass is a persistent grid of
+// kTraceBlocksPerCU workgroups per CU that draws on all segments' ray lists; the pool holds `segs` segments
+// per such workgroup (default 8: 33.5 M slots, ~62 GB with a depth-50 tape — measured optimum of 2.5-10 K
+// segments on the headline scene; sized for 288 GB of HBM). `segs`: tune::segments; `forced_blocks`: rt_debug_set_engine's
+// max_pool_blocks; `have_slots`: the pool there is; `free_bytes()`: device memory free right now (asked only if the pool must grow).
+struct PoolPlan { uint32_t segs, blocks; };                 // WfPool::segs, n_blocks
+template <class FreeBytes>
+PoolPlan plan_pool(uint64_t n_items, uint32_t n_cus, uint32_t max_depth, uint32_t segs, int forced_blocks, uint64_t have_slots, FreeBytes free_bytes) {
+    if (segs < 1) segs = 1;
+    if (segs > 8) segs = 8;
+    uint32_t max_blocks = forced_blocks > 0 ? (uint32_t)forced_blocks : (uint32_t)kTraceBlocksPerCU * n_cus * segs;
+    // Use every workgroup slot of the chip even for small jobs (64 paths per workgroup at least).
+    uint64_t want = (n_items + 63) / 64;
+    uint32_t blocks = (uint32_t)(want < 1 ? 1 : (want > max_blocks ? max_blocks : want));
+    // A job of about as many paths as the pool has slots is better served by half the pool: every path starts in the first pass
+    // either way, the passes are as many (a path lives its dozen bounces), and each shade pass sweeps half the segments
+    // (book-1 final 400x225x100, four frames per call — 36 M paths for 33.5 M slots: +11 %, profiles/r3zh_segs.log). Two paths per
+    // slot at least, for jobs large enough to fill the chip anyway; larger jobs keep the whole pool (they lose with a smaller one).
+    const uint64_t two_per_slot = n_items / (2ull * (uint64_t)kSlotsPerBlock);
+    const uint64_t floor_blocks = (uint64_t)kTraceBlocksPerCU * (uint64_t)n_cus * 2ull;      // (never below two segments per resident traversal workgroup)
+    if (forced_blocks <= 0 && two_per_slot < blocks && blocks > floor_blocks)
+        blocks = (uint32_t)(two_per_slot > floor_blocks ? two_per_slot : floor_blocks);
+    // (deep paths: keep the bounce tape under 56 GB by taking fewer segments)
+    const uint64_t tape_per_block = (uint64_t)kSlotsPerBlock * (max_depth ? max_depth : 1) * 4 * sizeof(double);
+    while (blocks > segs && (uint64_t)blocks * tape_per_block > (56ull << 30)) blocks -= segs;
+    // (and never plan for more than 60 % of the memory that is free right now: other scenes, other users of the GPU)
+    if ((uint64_t)blocks * kSlotsPerBlock > have_slots) {
+        const uint64_t free_b = free_bytes();                 // (~0: unknown, no limit)
+        if (free_b != ~0ull) {
+            const uint64_t per_block = (uint64_t)kSlotsPerBlock * 176 + tape_per_block;      // records + tape, bytes
+            const uint64_t budget = (uint64_t)((double)free_b * 0.6) + have_slots / kSlotsPerBlock * per_block;
+            while (blocks > segs && (uint64_t)blocks * per_block > budget) blocks -= segs;
+        }
+    }
+    if (blocks < segs) segs = blocks;
+    return PoolPlan{segs, blocks / segs * segs};
+}
+
 // Enqueue one render on `stream`; row ids and output are device pointers. With `src` the call is an rt_radiance*: its
 // "pixels" are the rays of src (p: width 1, no rows, spp_chunk 1; cam unused).
 void enqueue(rt_scene *sc, const rt_camera *cam, const rt_params *p, const uint32_t *d_rows, double *d_out,
@@ -488,30 +553,9 @@ void enqueue(rt_scene *sc, const rt_camera *cam, const rt_params *p, const uint3
     a.rays = src ? src->d_rays : nullptr;
     bool counters = stats && (p->flags & RT_FLAG_COUNTERS);
     const bool want_kt = stats && (p->flags & RT_FLAG_KERNEL_TIMES) && sc->engine == 1;
-    // Ring of partial-sum planes (pt_device.h, RenderArgs::ring): one-sample work items of the wavefront engine only. Automatic
-    // when all spp planes would take more than 40 % of the device's memory (115 GB on an MI355X: C5's 99.5 GB stay below it —
-    // the ring's work-item order costs its traversal 10 %, the headline's 1.4 %: profiles/r3j_ring.log): then at most 24 GiB
-    // of planes; rt_debug_set_partial_ring forces a size (tests: down to one plane) or switches it off.
-    a.ring = 0; a.ring_group = 1;
-    if (sc->engine == 1 && a.chunk == 1 && a.n_chunks > 1 && a.n_pixels > 0 && sc->partial_ring >= 0) {
-        uint32_t want = 0;
-        const uint64_t plane = a.n_pixels * 3 * sizeof(double);
-        if (sc->partial_ring > 0) want = (uint32_t)sc->partial_ring;
-        else if (a.n_items * 3 * sizeof(double) > sc->ring_threshold_bytes) want = (uint32_t)std::max<uint64_t>(8, (24ull << 30) / plane);
-        if (want && want < a.n_chunks) {
-            // samples are taken in groups: the largest divisor of spp up to 25 (and up to a quarter of the ring, so that it holds
-            // a few groups); the ring is a whole number of groups. (A group's planes are free again only when its last straggler
-            // has ended, ~60 passes after its first claim: the ring must hold what is claimed meanwhile — measured on C5: five
-            // groups of 50 stall every pool fill, twenty of 25 never.)
-            uint32_t grp = 1;
-            const uint32_t group_max = sc->partial_ring_group > 0 ? (uint32_t)sc->partial_ring_group : 25u;
-            for (uint32_t d = 1; d <= group_max && d * 4u <= std::max(want, 4u); d++) if (a.n_chunks % d == 0) grp = d;
-            if (grp > want) grp = 1;
-            a.ring_group = grp;
-            a.ring = want / grp * grp;
-            if (a.ring == 0 || a.ring >= a.n_chunks) { a.ring = 0; a.ring_group = 1; }
-        }
-    }
+    const RingPlan rp = sc->engine == 1 ? plan_ring(a.chunk, a.n_chunks, a.n_pixels, a.n_items, sc->partial_ring, sc->partial_ring_group, sc->ring_threshold_bytes)
+                                        : RingPlan{};
+    a.ring = rp.planes; a.ring_group = rp.group;
     if (a.n_chunks > 1) {
         uint64_t bytes = (a.ring ? (uint64_t)a.ring * a.n_pixels : a.n_items) * 3 * sizeof(double);
         w.used_partial_bytes = bytes;
@@ -527,58 +571,27 @@ void enqueue(rt_scene *sc, const rt_camera *cam, const rt_params *p, const uint3
         a.partial = d_out;
         w.used_partial_bytes = 0;
     }
-    // bit 31: boxes are plain (see wf_trace's fast path); bit 30 of the tuning word forces the literal step
-    a.node_quorum = (sc->node_quorum & 0x7FFFFFFFu) | ((sc->boxes_plain && !(sc->node_quorum & (1u << 30))) ? (1u << 31) : 0u);
+    a.tuning = tune::for_kernels(sc->tuning, sc->boxes_plain);       // (see wf_trace's fast path)
     a.vote_weights = sc->vote_weights ? sc->vote_weights : kWfVoteWeights;      // (read by the wavefront engine only)
     a.work_counter = w.work_counter;
     a.stats = counters ? w.stats : nullptr;
     if (sc->engine == 1) {
         // Wavefront engine: pool of path slots, shade / trace passes until it drains.
-        // Pool = segments of 4096 path slots (one shade workgroup each). The trace pass is a persistent grid of
-        // kTraceBlocksPerCU workgroups per CU that draws on all segments' ray lists; the pool holds `segs` segments
-        // per such workgroup (default 8: 33.5 M slots, ~62 GB with a depth-50 tape — measured optimum of 2.5-10 K
-        // segments on the headline scene; sized for 288 GB of HBM).
-        uint32_t segs = (sc->node_quorum >> 16) & 0xFu;
-        if (segs < 1) segs = 1;
-        if (segs > 8) segs = 8;
-        uint32_t max_blocks = sc->max_pool_blocks > 0 ? (uint32_t)sc->max_pool_blocks : (uint32_t)kTraceBlocksPerCU * (uint32_t)sc->n_cus * segs;
-        // Use every workgroup slot of the chip even for small jobs (64 paths per workgroup at least).
-        uint64_t want = (a.n_items + 63) / 64;
-        uint32_t blocks = (uint32_t)(want < 1 ? 1 : (want > max_blocks ? max_blocks : want));
-        // A job of about as many paths as the pool has slots is better served by half the pool: every path starts in the first pass
-        // either way, the passes are as many (a path lives its dozen bounces), and each shade pass sweeps half the segments
-        // (book-1 final 400x225x100, four frames per call — 36 M paths for 33.5 M slots: +11 %, profiles/r3zh_segs.log). Two paths per
-        // slot at least, for jobs large enough to fill the chip anyway; larger jobs keep the whole pool (they lose with a smaller one).
-        {
-            const uint64_t two_per_slot = a.n_items / (2ull * (uint64_t)kSlotsPerBlock);
-            const uint64_t floor_blocks = (uint64_t)kTraceBlocksPerCU * (uint64_t)sc->n_cus * 2ull;      // (never below two segments per resident traversal workgroup)
-            if (sc->max_pool_blocks <= 0 && two_per_slot < blocks && blocks > floor_blocks)
-                blocks = (uint32_t)(two_per_slot > floor_blocks ? two_per_slot : floor_blocks);
-        }
-        // (deep paths: keep the bounce tape under 56 GB by taking fewer segments)
-        const uint64_t tape_per_block = (uint64_t)kSlotsPerBlock * (p->max_depth ? p->max_depth : 1) * 4 * sizeof(double);
-        while (blocks > segs && (uint64_t)blocks * tape_per_block > (56ull << 30)) blocks -= segs;
-        // (and never plan for more than 60 % of the memory that is free right now: other scenes, other users of the GPU)
-        if ((uint64_t)blocks * kSlotsPerBlock > w.pool_slots) {
+        const PoolPlan pp = plan_pool(a.n_items, (uint32_t)sc->n_cus, p->max_depth, tune::segments(sc->tuning), sc->max_pool_blocks, w.pool_slots, [] {
             size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-                const uint64_t per_block = (uint64_t)kSlotsPerBlock * 176 + tape_per_block;      // records + tape, bytes
-                const uint64_t budget = (uint64_t)((double)free_b * 0.6) + (uint64_t)w.pool_slots / kSlotsPerBlock * per_block;
-                while (blocks > segs && (uint64_t)blocks * per_block > budget) blocks -= segs;
-            }
-        }
-        if (blocks < segs) segs = blocks;
-        blocks = blocks / segs * segs;
+            return hipMemGetInfo(&free_b, &total_b) == hipSuccess ? (uint64_t)free_b : ~0ull;
+        });
+        const uint32_t segs = pp.segs, blocks = pp.blocks;
         ensure_pool(w, blocks, p->max_depth, stream);
         a.claim_limit = w.d_limit;
         w.pool.segs = segs;
         w.pool.n_cus = (uint32_t)sc->n_cus;
-        const bool timing = (sc->node_quorum & (1u << 29)) != 0;
+        const bool timing = tune::pass_timing(sc->tuning);
         // Groups of pool segments passing independently, each on a stream of its own: one group's shade pass then runs beside another's
         // traversal pass and fills what its stragglers leave idle. 0 in the tuning word = the library's choice: two — measured
         // (profiles/r3ze_groups.log, bench.py --groups): 1e5 random spheres +18 %, Cornell box +3 %, random spheres +1 %, book-2 final
         // +0.4 % — except for meshes (wwscene: -3 % at two, -7 % at three), which keep one.
-        w.gs.n = (int)((sc->node_quorum >> 24) & 0xFu);
+        w.gs.n = (int)tune::groups(sc->tuning);
         if (w.gs.n < 1) w.gs.n = (sc->features & kFeatMisc) ? 1 : 2;
         if (w.gs.n > kMaxGroups) w.gs.n = kMaxGroups;
         w.pool.dbg = timing ? w.pool_dbg : nullptr;
@@ -595,20 +608,23 @@ void enqueue(rt_scene *sc, const rt_camera *cam, const rt_params *p, const uint3
         RT_HIP(hipStreamSynchronize(stream));      // the three structs above live on this thread's stack
         if (check_rows) end_check_device_rows(w, p);
         RT_HIP(hipEventRecord(w.ev0, stream));
-        Progress prog;
-        prog.cb = p->progress_cb; prog.user = p->progress_user;
-        prog.total = a.n_pixels * p->spp; prog.per_item = a.chunk;
-        RingCtl ring;
-        ring.planes = a.ring; ring.out = d_out; ring.d_limit = w.d_limit;
+        WfRender r;
+        r.scene = &sc->dev; r.args = &a; r.d_args = w.d_args; r.pool = &w.pool;
+        r.stack_need = sc->stack_need; r.features = sc->features; r.counters = counters;
+        r.gs = &w.gs; r.stream = stream;
+        r.progress.cb = p->progress_cb; r.progress.user = p->progress_user;
+        r.progress.total = a.n_pixels * p->spp; r.progress.per_item = a.chunk;
+        r.ring.planes = a.ring; r.ring.out = d_out; r.ring.d_limit = w.d_limit;
         // (watchdog of the ring's pass loop: a frame needs about items / slots pool fills of at most max_depth + 1 passes each)
         // (... plus one drain per ring-full of planes when the ring is small)
-        ring.max_passes = (uint32_t)std::min<uint64_t>(1u << 26, 64 + 8 * (a.n_items / ((uint64_t)w.pool.n_blocks * kSlotsPerBlock) + 2 + (a.ring ? a.n_chunks / a.ring : 0)) *
-                                                                     ((uint64_t)p->max_depth + 2));
+        r.ring.max_passes = (uint32_t)std::min<uint64_t>(1u << 26, 64 + 8 * (a.n_items / ((uint64_t)w.pool.n_blocks * kSlotsPerBlock) + 2 + (a.ring ? a.n_chunks / a.ring : 0)) *
+                                                                       ((uint64_t)p->max_depth + 2));
+        r.timing = timing ? sc->pass_timing : nullptr;
+        r.kt = want_kt ? &w.kt : nullptr;
         if (a.n_items > 0) {
-            uint32_t fault = 0;
-            RT_HIP(launch_render_wavefront(sc->dev, a, w.d_args, w.pool, sc->stack_need, sc->features, counters, w.gs, stream, &w.iterations,
-                                           timing ? sc->pass_timing : nullptr, &fault, want_kt ? &w.kt : nullptr, &prog, a.ring ? &ring : nullptr));
-            RT_REQUIRE(fault == 0, RT_ERR_DEVICE, "wavefront engine: a path slot reached the shade pass without having been traced (internal error; the frame is incomplete)");
+            RT_HIP(launch_render_wavefront(r));
+            w.iterations = r.passes;
+            RT_REQUIRE(r.fault == 0, RT_ERR_DEVICE, "wavefront engine: a path slot reached the shade pass without having been traced (internal error; the frame is incomplete)");
             if (a.n_chunks > 1 && !a.ring) RT_HIP(launch_chunk_sum(a.partial, d_out, a.n_pixels * 3, a.n_chunks, stream));
         }
         RT_HIP(hipEventRecord(w.ev1, stream));
@@ -617,7 +633,7 @@ void enqueue(rt_scene *sc, const rt_camera *cam, const rt_params *p, const uint3
         w.used_chunk = a.chunk; w.used_passes = w.iterations; w.used_slots = (uint64_t)w.pool.n_blocks * kSlotsPerBlock;
         w.used_kt = want_kt && a.n_items > 0;
         // (every pass of the frame has been issued and observed: the render is complete up to the chunk sums queued behind it)
-        if (prog.cb) prog.cb(prog.user, 0u, prog.total, prog.total);
+        if (r.progress.cb) r.progress.cb(r.progress.user, 0u, r.progress.total, r.progress.total);
         return;
     }
     // Megakernel engine. Bounce tape: max_depth records of 4 doubles for every lane of the persistent grid.
@@ -654,6 +670,13 @@ void enqueue(rt_scene *sc, const rt_camera *cam, const rt_params *p, const uint3
         RT_HIP(hipStreamSynchronize(stream));
         p->progress_cb(p->progress_user, 0u, a.n_pixels * p->spp, a.n_pixels * p->spp);
     }
+}
+
+// The counter block of a run, as rt_stats reports it.
+void copy_counters(const StatsDev &h, rt_stats &out) {
+    out.paths = h.paths; out.rays = h.rays; out.node_visits = h.node_visits;
+    for (int k = 0; k < RT_KIND_COUNT; k++) out.prim_tests[k] = h.prim_tests[k];
+    out.light_pdf_tests = h.light_pdf_tests; out.rng_draws = h.rng_draws;
 }
 
 QueryScratch &query_scratch_for(rt_scene *sc, hipStream_t stream) {
@@ -708,9 +731,8 @@ void run_query(rt_scene *sc, const rt_query_ray *d_rays, uint64_t n_rays, uint32
     if (counters) {
         StatsDev h;
         RT_HIP(hipMemcpy(&h, q.stats, sizeof h, hipMemcpyDeviceToHost));
-        out.node_visits = h.node_visits;
-        for (int k = 0; k < RT_KIND_COUNT; k++) out.prim_tests[k] = h.prim_tests[k];
-        out.rng_draws = h.rng_draws;
+        copy_counters(h, out);
+        out.rays = n_rays;                         // (a query counts no paths, rays or light tests of its own)
     }
     float ms = 0.f;
     RT_HIP(hipEventElapsedTime(&ms, q.ev0, q.ev1));
@@ -745,9 +767,7 @@ void finish(rt_scene *sc, hipStream_t stream) {
         if (w.pending_counters) {
             StatsDev h;
             RT_HIP(hipMemcpy(&h, w.stats, sizeof h, hipMemcpyDeviceToHost));
-            out.paths = h.paths; out.rays = h.rays; out.node_visits = h.node_visits;
-            for (int k = 0; k < RT_KIND_COUNT; k++) out.prim_tests[k] = h.prim_tests[k];
-            out.light_pdf_tests = h.light_pdf_tests; out.rng_draws = h.rng_draws;
+            copy_counters(h, out);
             {
                 std::lock_guard<std::mutex> lock(sc->mu);
                 for (int o = 0; o < 9; o++) { sc->census_rounds[o] = h.op_rounds[o]; sc->census_lanes[o] = h.op_lanes[o]; }
@@ -1482,10 +1502,11 @@ int rt_debug_valu_probe(int mode, uint32_t iters) {
 int rt_debug_set_tuning(rt_scene *scene, uint32_t node_quorum, uint32_t vote_weights) {
     return guarded([&]() -> int {
         RT_REQUIRE(scene, RT_ERR_INVALID, "rt_debug_set_tuning: null scene");
-        RT_REQUIRE((node_quorum & 0xFFu) >= 1 && (node_quorum & 0xFFu) <= 64 && true, RT_ERR_INVALID, "rt_debug_set_tuning: node_quorum must be 1..64 (+ extra sphere repeats << 8, + tail factor << 12, + segments per trace workgroup << 16, + long-first class shift << 20, + groups << 24, + 1 << 29: pass-timing probe, + 1 << 30: literal node step only)");
+        RT_REQUIRE(tune::quorum(node_quorum) >= 1 && tune::quorum(node_quorum) <= 64, RT_ERR_INVALID,
+                   "rt_debug_set_tuning: the quorum (bits 0-7 of node_quorum) must be 1..64; the other fields: include/rt2022_debug.h");
         if (vote_weights != 0)                  // (0 = the engine's default)
             for (int o = 0; o < 8; o++) RT_REQUIRE(((vote_weights >> (4 * o)) & 0xFu) != 0, RT_ERR_INVALID, "rt_debug_set_tuning: a vote weight is 0");
-        scene->node_quorum = node_quorum;
+        scene->tuning = node_quorum;
         scene->vote_weights = vote_weights;
         return RT_OK;
     });
@@ -1543,7 +1564,7 @@ int rt_debug_trace_variant(const rt_scene *scene, uint32_t *workgroup_threads, u
     return guarded([&]() -> int {
         RT_REQUIRE(scene, RT_ERR_INVALID, "rt_debug_trace_variant: null scene");
         uint32_t v[4] = {0, 0, 0, 0};
-        if (scene->engine == 1) trace_variant(scene->dev, scene->stack_need, scene->node_quorum, scene->features, v);
+        if (scene->engine == 1) trace_variant(scene->dev, scene->stack_need, scene->tuning, scene->features, v);
         if (workgroup_threads) *workgroup_threads = v[0];
         if (stack_entries) *stack_entries = v[1];
         if (nodes_in_lds) *nodes_in_lds = v[2];
