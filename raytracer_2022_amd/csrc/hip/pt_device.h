@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../../include/rt2022.h"
+#include "hip_owned.hpp"
 
 namespace rt2022 {
 
@@ -251,15 +252,22 @@ constexpr unsigned kFeatMisc = 1;      // triangles, rings
 constexpr unsigned kFeatMovers = 2;    // Translate / RotateY / Zoom, HittableList objects
 constexpr unsigned kFeatVolumes = 4;   // Boxes, ConstantMedium
 
-// Streams the wavefront engine runs its groups of segments on (owned by the caller).
+// Streams the wavefront engine runs its groups of segments on, with their events and pinned words: all created when
+// one is constructed (the caller keeps it from render to render).
 constexpr int kMaxGroups = 8;
 struct WfStreams {
     int n = 0;                         // groups wanted (1 = everything on the caller's stream)
-    hipStream_t stream[kMaxGroups] = {};
-    hipEvent_t ev[kMaxGroups][2] = {};
-    uint32_t *h_active = nullptr;      // pinned, [kMaxGroups][2]
-    unsigned long long *h_work = nullptr;   // pinned, [kMaxGroups][2]: the work counter as of the same batches (progress callback, ring mode)
-    unsigned long long *h_oldest = nullptr; // pinned, [kMaxGroups][2]: WfPool::oldest as of the same batches (ring mode)
+    Stream stream[kMaxGroups];
+    Event ev[kMaxGroups][2];
+    PinnedBuf<uint32_t> h_active{2 * kMaxGroups};             // [kMaxGroups][2]
+    PinnedBuf<unsigned long long> h_work{2 * kMaxGroups};     // [kMaxGroups][2]: the work counter as of the same batches (progress callback, ring mode)
+    PinnedBuf<unsigned long long> h_oldest{2 * kMaxGroups};   // [kMaxGroups][2]: WfPool::oldest as of the same batches (ring mode)
+    WfStreams() {
+        for (int g = 0; g < kMaxGroups; g++) {
+            stream[g] = Stream(hipStreamNonBlocking);
+            for (int b = 0; b < 2; b++) ev[g][b] = Event(hipEventDisableTiming);
+        }
+    }
 };
 // rt_params::progress_cb as the engine sees it (host side only).
 struct Progress {
@@ -270,7 +278,7 @@ struct Progress {
 };
 // Per-kernel device time of one render (RT_FLAG_KERNEL_TIMES): HIP events on the launch stream around every pass.
 struct KernelTimes {
-    std::vector<hipEvent_t> ev;        // grown on demand, reused from call to call
+    std::vector<Event> ev;             // grown on demand, reused from call to call
     double shade_ms = 0.0, trace_ms = 0.0;
 };
 // Ring mode: what the engine needs to consume planes as the frame goes.

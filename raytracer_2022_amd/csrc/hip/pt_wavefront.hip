@@ -2202,11 +2202,7 @@ hipError_t PassDriver::enqueue_batch(int g) {
         // is summed)
         hipEvent_t mid = nullptr;
         if (kt) {
-            while (kt->ev.size() < 3 * (size_t)iterations + 3) {
-                hipEvent_t ne = nullptr;
-                if ((e = hipEventCreate(&ne)) != hipSuccess) return e;
-                kt->ev.push_back(ne);
-            }
+            while (kt->ev.size() < 3 * (size_t)iterations + 3) kt->ev.emplace_back(hipEventDefault);     // (throws Fail)
             if ((e = hipEventRecord(kt->ev[3 * iterations], st)) != hipSuccess) return e;
             mid = kt->ev[3 * iterations + 1];
         }
@@ -2368,15 +2364,16 @@ static void print_shade_probe(const WfPool &pool) {
 #endif
 
 hipError_t launch_render_wavefront(WfRender &r) {
-    hipError_t e = PassDriver(r).run();
-    if (e != hipSuccess) {
-        // Passes may still be queued or running against the pool on the group streams: let them finish (best
-        // effort) before the caller sees the error and possibly frees or reuses the pool.
+    // Passes may still be queued or running against the pool on the group streams: let them finish (best
+    // effort) before the caller sees the error and possibly frees or reuses the pool.
+    const auto drain = [&r] {
         for (int g = 0; g < kMaxGroups; g++)
             if (r.gs->stream[g]) (void)hipStreamSynchronize(r.gs->stream[g]);
         (void)hipStreamSynchronize(r.stream);
-        return e;
-    }
+    };
+    hipError_t e;
+    try { e = PassDriver(r).run(); } catch (...) { drain(); throw; }       // (a kernel-time event that could not be created)
+    if (e != hipSuccess) { drain(); return e; }
 #ifdef RT2022_TRACE_PROBE
     if (r.pool->dbg) print_trace_probe(*r.pool);
 #endif

@@ -19,18 +19,12 @@
 #include "../../../include/rt2022.h"
 #include "../../../include/rt2022_debug.h"
 #include "../host/rt_error.hpp"
+#include "hip_owned.hpp"
 #include "pt_device.h"
 
 using namespace rt2022;
 
 namespace {
-
-struct Fail {
-    int code;
-    std::string msg;
-};
-#define RT_REQUIRE(cond, code, msg) do { if (!(cond)) throw Fail{code, msg}; } while (0)
-#define RT_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) throw Fail{RT_ERR_DEVICE, std::string(#expr ": ") + hipGetErrorString(e_)}; } while (0)
 
 template <class F>
 int guarded(F &&f) {
@@ -257,51 +251,53 @@ std::vector<uint32_t> breadth_first_nodes(const rt_scene_desc &d) {
 }
 
 template <class T>
-T *upload(const T *src, uint64_t n, std::vector<void *> &owned) {
+T *upload(const T *src, uint64_t n, std::vector<DeviceBuf<char>> &owned) {
     // Never hand the kernels a null pool: an empty pool gets one zeroed element.
     // (128 bytes of zeroed slack behind every pool: the shading kernel fetches a fixed 80 bytes from the winning
     // primitive's record whatever its kind, the last record of a pool included)
     uint64_t bytes = (n ? n : 1) * sizeof(T) + 128;
-    void *p = nullptr;
-    RT_HIP(hipMalloc(&p, bytes));
-    owned.push_back(p);
+    owned.emplace_back(bytes);
+    void *p = owned.back().p;
     RT_HIP(hipMemset(p, 0, bytes));
     if (n) RT_HIP(hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice));
     return (T *)p;
 }
 
+// What the wavefront engine needs whatever the size of its pool; all of it is created when one is constructed.
+struct EngineFixed {
+    DeviceBuf<SceneDev> d_scene{1};
+    DeviceBuf<RenderArgs> d_args{1};
+    DeviceBuf<WfPool> d_pool{1};
+    DeviceBuf<unsigned long long> d_limit{1};   // ring mode: RenderArgs::claim_limit
+    WfStreams gs;                     // group streams / events / pinned words
+};
+
+// What one (scene, stream) keeps from render to render. Its members own their HIP resources; the ones every call needs —
+// work counter, counter block, two events — are created when it is constructed.
 struct Workspace {
-    unsigned long long *work_counter = nullptr;
-    StatsDev *stats = nullptr;
-    double *partial = nullptr;
-    uint64_t partial_bytes = 0;
-    double *tape = nullptr;
-    uint64_t tape_bytes = 0;
+    DeviceBuf<unsigned long long> work_counter{1};
+    DeviceBuf<StatsDev> stats{1};
+    DeviceBuf<double> partial, tape;  // partial sums (wavefront and megakernel), bounce tape (megakernel): grown as needed
     // wavefront engine
     WfPool pool{};
-    std::vector<void *> pool_owned;
+    std::vector<DeviceBuf<char>> pool_owned;
     uint32_t pool_slots = 0, pool_depth = 0;
-    unsigned long long *pool_dbg = nullptr;
-    SceneDev *d_scene = nullptr;
-    RenderArgs *d_args = nullptr;
-    WfPool *d_pool = nullptr;
-    WfStreams gs{};                   // group streams / events / pinned words (created on first use)
+    unsigned long long *pool_dbg = nullptr;    // (one of pool_owned)
+    std::unique_ptr<EngineFixed> fx;  // (created on first use)
     uint32_t iterations = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    Event ev0{hipEventDefault}, ev1{hipEventDefault};
     rt_stats *pending = nullptr;      // host stats to fill at rt_render_wait
     bool pending_counters = false;
     KernelTimes kt;                   // RT_FLAG_KERNEL_TIMES
     bool used_kt = false;
     uint32_t used_chunk = 0, used_passes = 0;
     uint64_t used_slots = 0;
-    uint32_t *rows_max = nullptr;     // device word: largest row id of the call being checked
-    uint32_t *h_rows_max = nullptr;   // ... and the pinned word it is copied to
-    unsigned long long *d_limit = nullptr;   // ring mode: RenderArgs::claim_limit
+    DeviceBuf<uint32_t> rows_max;     // device word: largest row id of the call being checked
+    PinnedBuf<uint32_t> h_rows_max;   // ... and the pinned word it is copied to
     uint64_t used_partial_bytes = 0;
     // rt_radiance (host buffers): the device copies of the caller's rays and of the sums, grown as needed
-    rt_radiance_ray *rad_rays = nullptr;
-    double *rad_out = nullptr;
-    uint64_t rad_cap = 0;             // rays both buffers hold
+    DeviceBuf<rt_radiance_ray> rad_rays;
+    DeviceBuf<double> rad_out;
     // RT_FLAG_ASYNC: the host thread that drives the passes of the call in flight on this (scene, stream), and what it ended with
     // (read by rt_render_wait after the join).
     std::thread async_worker;
@@ -310,19 +306,20 @@ struct Workspace {
 };
 
 // Scratch of the closest-hit queries on one (scene, stream): the ray counter of the persistent grid, a counter block
-// and two events. Nothing of a render's Workspace: a query may run beside an asynchronous render of the same scene.
+// and two events, created when it is constructed. Nothing of a render's Workspace: a query may run beside an asynchronous
+// render of the same scene.
 struct QueryScratch {
     std::mutex mu;                    // one call at a time enqueues — and, with stats, reads back — on this (scene, stream)
-    unsigned long long *counter = nullptr;
-    StatsDev *stats = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    DeviceBuf<unsigned long long> counter{1};
+    DeviceBuf<StatsDev> stats{1};
+    Event ev0{hipEventDefault}, ev1{hipEventDefault};
 };
 
 } // namespace
 
 struct rt_scene {
     SceneDev dev{};
-    std::vector<void *> owned;
+    std::vector<DeviceBuf<char>> owned;        // the pools behind `dev`
     uint32_t stack_need = 1;
     unsigned features = 7;
     bool general_boundaries = false;
@@ -348,14 +345,7 @@ namespace {
 
 Workspace &workspace_for(rt_scene *sc, hipStream_t stream) {
     std::lock_guard<std::mutex> lock(sc->mu);
-    Workspace &w = sc->ws[stream];
-    if (!w.work_counter) {
-        RT_HIP(hipMalloc((void **)&w.work_counter, sizeof(unsigned long long)));
-        RT_HIP(hipMalloc((void **)&w.stats, sizeof(StatsDev)));
-        RT_HIP(hipEventCreate(&w.ev0));
-        RT_HIP(hipEventCreate(&w.ev1));
-    }
-    return w;
+    return sc->ws.try_emplace(stream).first->second;      // (a new one is in the map once it is complete, or not at all)
 }
 
 void check_params(const rt_scene *scene, const rt_camera *cam, const rt_params *p) {
@@ -368,33 +358,19 @@ void check_params(const rt_scene *scene, const rt_camera *cam, const rt_params *
 
 template <class T>
 T *pool_alloc(Workspace &w, uint64_t count) {
-    void *p = nullptr;
-    RT_HIP(hipMalloc(&p, (count ? count : 1) * sizeof(T)));
-    w.pool_owned.push_back(p);
-    return (T *)p;
+    w.pool_owned.emplace_back((count ? count : 1) * sizeof(T));
+    return (T *)w.pool_owned.back().p;
 }
 
 // (Re)allocate the wavefront pool for `blocks` workgroups and `depth` tape records.
 void ensure_pool(Workspace &w, uint32_t blocks, uint32_t depth, hipStream_t stream) {
     uint32_t slots = blocks * (uint32_t)kSlotsPerBlock;
     if (depth == 0) depth = 1;
-    if (w.d_scene == nullptr) {
-        RT_HIP(hipMalloc((void **)&w.d_scene, sizeof(SceneDev)));
-        RT_HIP(hipMalloc((void **)&w.d_args, sizeof(RenderArgs)));
-        RT_HIP(hipMalloc((void **)&w.d_pool, sizeof(WfPool)));
-        RT_HIP(hipHostMalloc((void **)&w.gs.h_active, 2 * kMaxGroups * sizeof(uint32_t)));
-        RT_HIP(hipHostMalloc((void **)&w.gs.h_work, 2 * kMaxGroups * sizeof(unsigned long long)));
-        RT_HIP(hipHostMalloc((void **)&w.gs.h_oldest, 2 * kMaxGroups * sizeof(unsigned long long)));
-        RT_HIP(hipMalloc((void **)&w.d_limit, sizeof(unsigned long long)));
-        for (int g = 0; g < kMaxGroups; g++) {
-            RT_HIP(hipStreamCreateWithFlags(&w.gs.stream[g], hipStreamNonBlocking));
-            for (int b = 0; b < 2; b++) RT_HIP(hipEventCreateWithFlags(&w.gs.ev[g][b], hipEventDisableTiming));
-        }
-    }
+    if (!w.fx) w.fx.reset(new EngineFixed());              // (stored once it is complete, or not at all)
     if (slots <= w.pool_slots && depth <= w.pool_depth) { w.pool.n_blocks = blocks; w.pool.n_slots = w.pool_slots; return; }
+    // The pool is replaced as a whole — more slots may come with a shorter tape — behind everything that may still use it.
     RT_HIP(hipStreamSynchronize(stream));
-    for (int g = 0; g < kMaxGroups; g++) RT_HIP(hipStreamSynchronize(w.gs.stream[g]));    // (passes of an earlier call that failed half-way)
-    for (void *p : w.pool_owned) RT_HIP(hipFree(p));
+    for (int g = 0; g < kMaxGroups; g++) RT_HIP(hipStreamSynchronize(w.fx->gs.stream[g]));    // (passes of an earlier call that failed half-way)
     w.pool_owned.clear();
     w.pool_slots = 0; w.pool_depth = 0;
     if (slots < w.pool.n_slots) slots = w.pool.n_slots;
@@ -438,19 +414,19 @@ __global__ void __launch_bounds__(256) row_ids_max_kernel(const uint32_t *rows, 
 // mis-keys a frame — so nothing is lost by finding out a moment later.)
 void begin_check_device_rows(Workspace &w, const rt_params *p, hipStream_t stream) {
     if (p->n_rows == 0) return;
-    if (!w.rows_max) {
-        RT_HIP(hipMalloc((void **)&w.rows_max, sizeof(uint32_t)));
-        RT_HIP(hipHostMalloc((void **)&w.h_rows_max, sizeof(uint32_t)));
+    if (!w.h_rows_max) {                           // (keyed on the one created last: a failure half-way is made good by the next call)
+        w.rows_max = DeviceBuf<uint32_t>(1);
+        w.h_rows_max = PinnedBuf<uint32_t>(1);
     }
     RT_HIP(hipMemsetAsync(w.rows_max, 0, sizeof(uint32_t), stream));
     uint32_t blocks = (p->n_rows + 255u) / 256u;
-    hipLaunchKernelGGL(row_ids_max_kernel, dim3(blocks > 64 ? 64 : blocks), dim3(256), 0, stream, p->row_ids, p->n_rows, w.rows_max);
+    hipLaunchKernelGGL(row_ids_max_kernel, dim3(blocks > 64 ? 64 : blocks), dim3(256), 0, stream, p->row_ids, p->n_rows, w.rows_max.p);
     RT_HIP(hipGetLastError());
     RT_HIP(hipMemcpyAsync(w.h_rows_max, w.rows_max, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
 }
 void end_check_device_rows(Workspace &w, const rt_params *p) {      // (after a synchronisation of the stream)
     if (p->n_rows == 0) return;
-    RT_REQUIRE((uint64_t)*w.h_rows_max < (uint64_t)p->height * p->n_frames, RT_ERR_INVALID, "rt_render_device: row id out of range");
+    RT_REQUIRE((uint64_t)*w.h_rows_max.p < (uint64_t)p->height * p->n_frames, RT_ERR_INVALID, "rt_render_device: row id out of range");
 }
 
 // Where the paths of an rt_radiance* call start: the caller's rays (device) instead of the camera's rows.
@@ -559,13 +535,7 @@ void enqueue(rt_scene *sc, const rt_camera *cam, const rt_params *p, const uint3
     if (a.n_chunks > 1) {
         uint64_t bytes = (a.ring ? (uint64_t)a.ring * a.n_pixels : a.n_items) * 3 * sizeof(double);
         w.used_partial_bytes = bytes;
-        if (bytes > w.partial_bytes) {
-            RT_HIP(hipStreamSynchronize(stream));
-            if (w.partial) RT_HIP(hipFree(w.partial));
-            w.partial = nullptr; w.partial_bytes = 0;
-            RT_HIP(hipMalloc((void **)&w.partial, bytes));
-            w.partial_bytes = bytes;
-        }
+        w.partial.reserve(bytes / sizeof(double), &stream, 1);     // (an earlier call on the stream may still be summing the old ones)
         a.partial = w.partial;
     } else {
         a.partial = d_out;
@@ -574,7 +544,7 @@ void enqueue(rt_scene *sc, const rt_camera *cam, const rt_params *p, const uint3
     a.tuning = tune::for_kernels(sc->tuning, sc->boxes_plain);       // (see wf_trace's fast path)
     a.vote_weights = sc->vote_weights ? sc->vote_weights : kWfVoteWeights;      // (read by the wavefront engine only)
     a.work_counter = w.work_counter;
-    a.stats = counters ? w.stats : nullptr;
+    a.stats = counters ? w.stats.p : nullptr;
     if (sc->engine == 1) {
         // Wavefront engine: pool of path slots, shade / trace passes until it drains.
         const PoolPlan pp = plan_pool(a.n_items, (uint32_t)sc->n_cus, p->max_depth, tune::segments(sc->tuning), sc->max_pool_blocks, w.pool_slots, [] {
@@ -583,7 +553,8 @@ void enqueue(rt_scene *sc, const rt_camera *cam, const rt_params *p, const uint3
         });
         const uint32_t segs = pp.segs, blocks = pp.blocks;
         ensure_pool(w, blocks, p->max_depth, stream);
-        a.claim_limit = w.d_limit;
+        EngineFixed &fx = *w.fx;
+        a.claim_limit = fx.d_limit;
         w.pool.segs = segs;
         w.pool.n_cus = (uint32_t)sc->n_cus;
         const bool timing = tune::pass_timing(sc->tuning);
@@ -591,9 +562,9 @@ void enqueue(rt_scene *sc, const rt_camera *cam, const rt_params *p, const uint3
         // traversal pass and fills what its stragglers leave idle. 0 in the tuning word = the library's choice: two — measured
         // (profiles/r3ze_groups.log, bench.py --groups): 1e5 random spheres +18 %, Cornell box +3 %, random spheres +1 %, book-2 final
         // +0.4 % — except for meshes (wwscene: -3 % at two, -7 % at three), which keep one.
-        w.gs.n = (int)tune::groups(sc->tuning);
-        if (w.gs.n < 1) w.gs.n = (sc->features & kFeatMisc) ? 1 : 2;
-        if (w.gs.n > kMaxGroups) w.gs.n = kMaxGroups;
+        fx.gs.n = (int)tune::groups(sc->tuning);
+        if (fx.gs.n < 1) fx.gs.n = (sc->features & kFeatMisc) ? 1 : 2;
+        if (fx.gs.n > kMaxGroups) fx.gs.n = kMaxGroups;
         w.pool.dbg = timing ? w.pool_dbg : nullptr;
 #if defined(RT2022_SHADE_PROBE) || defined(RT2022_TRACE_PROBE)
         w.pool.dbg = w.pool_dbg;                                  // (diagnostic builds: the section clocks of the shade / traversal kernels)
@@ -603,18 +574,18 @@ void enqueue(rt_scene *sc, const rt_camera *cam, const rt_params *p, const uint3
         a.tape = nullptr;
         RT_HIP(hipMemsetAsync(w.work_counter, 0, sizeof(unsigned long long), stream));
         if (counters) RT_HIP(hipMemsetAsync(w.stats, 0, sizeof(StatsDev), stream));
-        RT_HIP(hipMemcpyAsync(w.d_args, &a, sizeof(RenderArgs), hipMemcpyHostToDevice, stream));
+        RT_HIP(hipMemcpyAsync(fx.d_args, &a, sizeof(RenderArgs), hipMemcpyHostToDevice, stream));
         if (check_rows) begin_check_device_rows(w, p, stream);
         RT_HIP(hipStreamSynchronize(stream));      // the three structs above live on this thread's stack
         if (check_rows) end_check_device_rows(w, p);
         RT_HIP(hipEventRecord(w.ev0, stream));
         WfRender r;
-        r.scene = &sc->dev; r.args = &a; r.d_args = w.d_args; r.pool = &w.pool;
+        r.scene = &sc->dev; r.args = &a; r.d_args = fx.d_args; r.pool = &w.pool;
         r.stack_need = sc->stack_need; r.features = sc->features; r.counters = counters;
-        r.gs = &w.gs; r.stream = stream;
+        r.gs = &fx.gs; r.stream = stream;
         r.progress.cb = p->progress_cb; r.progress.user = p->progress_user;
         r.progress.total = a.n_pixels * p->spp; r.progress.per_item = a.chunk;
-        r.ring.planes = a.ring; r.ring.out = d_out; r.ring.d_limit = w.d_limit;
+        r.ring.planes = a.ring; r.ring.out = d_out; r.ring.d_limit = fx.d_limit;
         // (watchdog of the ring's pass loop: a frame needs about items / slots pool fills of at most max_depth + 1 passes each)
         // (... plus one drain per ring-full of planes when the ring is small)
         r.ring.max_passes = (uint32_t)std::min<uint64_t>(1u << 26, 64 + 8 * (a.n_items / ((uint64_t)w.pool.n_blocks * kSlotsPerBlock) + 2 + (a.ring ? a.n_chunks / a.ring : 0)) *
@@ -642,13 +613,7 @@ void enqueue(rt_scene *sc, const rt_camera *cam, const rt_params *p, const uint3
     if ((uint64_t)blocks > want_blocks) blocks = (int)(want_blocks ? want_blocks : 1);
     uint64_t tape_bytes = (uint64_t)blocks * kBlock * (uint64_t)(p->max_depth ? p->max_depth : 1) * 4 * sizeof(double);
     RT_REQUIRE(tape_bytes <= (32ull << 30), RT_ERR_UNSUPPORTED, "max_depth too large for the bounce tape");
-    if (tape_bytes > w.tape_bytes) {
-        RT_HIP(hipStreamSynchronize(stream));
-        if (w.tape) RT_HIP(hipFree(w.tape));
-        w.tape = nullptr; w.tape_bytes = 0;
-        RT_HIP(hipMalloc((void **)&w.tape, tape_bytes));
-        w.tape_bytes = tape_bytes;
-    }
+    w.tape.reserve(tape_bytes / sizeof(double), &stream, 1);
     a.tape = w.tape;
     if (check_rows) {                              // (the A/B engine enqueues without a synchronisation of its own)
         begin_check_device_rows(w, p, stream);
@@ -672,32 +637,27 @@ void enqueue(rt_scene *sc, const rt_camera *cam, const rt_params *p, const uint3
     }
 }
 
-// The counter block of a run, as rt_stats reports it.
-void copy_counters(const StatsDev &h, rt_stats &out) {
-    out.paths = h.paths; out.rays = h.rays; out.node_visits = h.node_visits;
-    for (int k = 0; k < RT_KIND_COUNT; k++) out.prim_tests[k] = h.prim_tests[k];
-    out.light_pdf_tests = h.light_pdf_tests; out.rng_draws = h.rng_draws;
+// rt_stats of a finished call (its stream has been synchronised): the time between its two events and, with `d_stats`, the
+// counter block of the run as rt_stats reports it (the whole block is left in `h` for the caller that wants more of it).
+rt_stats read_stats(hipEvent_t ev0, hipEvent_t ev1, const StatsDev *d_stats, StatsDev &h) {
+    rt_stats out;
+    std::memset(&out, 0, sizeof out);
+    if (d_stats) {
+        RT_HIP(hipMemcpy(&h, d_stats, sizeof h, hipMemcpyDeviceToHost));
+        out.paths = h.paths; out.rays = h.rays; out.node_visits = h.node_visits;
+        for (int k = 0; k < RT_KIND_COUNT; k++) out.prim_tests[k] = h.prim_tests[k];
+        out.light_pdf_tests = h.light_pdf_tests; out.rng_draws = h.rng_draws;
+    }
+    float ms = 0.f;
+    RT_HIP(hipEventElapsedTime(&ms, ev0, ev1));
+    out.ms = (double)ms;
+    return out;
 }
 
 QueryScratch &query_scratch_for(rt_scene *sc, hipStream_t stream) {
     std::lock_guard<std::mutex> lock(sc->qmu);
     std::unique_ptr<QueryScratch> &q = sc->qs[stream];
-    if (!q) {
-        std::unique_ptr<QueryScratch> n(new QueryScratch());
-        try {
-            RT_HIP(hipMalloc((void **)&n->counter, sizeof(unsigned long long)));
-            RT_HIP(hipMalloc((void **)&n->stats, sizeof(StatsDev)));
-            RT_HIP(hipEventCreate(&n->ev0));
-            RT_HIP(hipEventCreate(&n->ev1));
-        } catch (...) {
-            if (n->counter) (void)hipFree(n->counter);
-            if (n->stats) (void)hipFree(n->stats);
-            if (n->ev0) (void)hipEventDestroy(n->ev0);
-            if (n->ev1) (void)hipEventDestroy(n->ev1);
-            throw;
-        }
-        q = std::move(n);
-    }
+    if (!q) q.reset(new QueryScratch());                   // (stored once it is complete, or not at all)
     return *q;
 }
 
@@ -717,7 +677,7 @@ void run_query(rt_scene *sc, const rt_query_ray *d_rays, uint64_t n_rays, uint32
     QueryScratch &q = query_scratch_for(sc, stream);
     std::lock_guard<std::mutex> lock(q.mu);
     const bool counters = stats && (flags & RT_FLAG_COUNTERS);
-    QueryArgs a{d_rays, d_hits, n_rays, q.counter, counters ? q.stats : nullptr};
+    QueryArgs a{d_rays, d_hits, n_rays, q.counter, counters ? q.stats.p : nullptr};
     RT_HIP(hipMemsetAsync(q.counter, 0, sizeof(unsigned long long), stream));
     if (counters) RT_HIP(hipMemsetAsync(q.stats, 0, sizeof(StatsDev), stream));
     if (stats) RT_HIP(hipEventRecord(q.ev0, stream));
@@ -725,18 +685,9 @@ void run_query(rt_scene *sc, const rt_query_ray *d_rays, uint64_t n_rays, uint32
     if (!stats) return;
     RT_HIP(hipEventRecord(q.ev1, stream));
     RT_HIP(hipStreamSynchronize(stream));
-    rt_stats out;
-    std::memset(&out, 0, sizeof out);
-    out.rays = n_rays;
-    if (counters) {
-        StatsDev h;
-        RT_HIP(hipMemcpy(&h, q.stats, sizeof h, hipMemcpyDeviceToHost));
-        copy_counters(h, out);
-        out.rays = n_rays;                         // (a query counts no paths, rays or light tests of its own)
-    }
-    float ms = 0.f;
-    RT_HIP(hipEventElapsedTime(&ms, q.ev0, q.ev1));
-    out.ms = (double)ms;
+    StatsDev h;
+    rt_stats out = read_stats(q.ev0, q.ev1, counters ? q.stats.p : nullptr, h);
+    out.rays = n_rays;                             // (a query counts no paths, rays or light tests of its own)
     *stats = out;
 }
 
@@ -762,20 +713,12 @@ void finish(rt_scene *sc, hipStream_t stream) {
     Workspace &w = workspace_for(sc, stream);
     RT_HIP(hipStreamSynchronize(stream));
     if (w.pending) {
-        rt_stats out;
-        std::memset(&out, 0, sizeof out);
+        StatsDev h;
+        rt_stats out = read_stats(w.ev0, w.ev1, w.pending_counters ? w.stats.p : nullptr, h);
         if (w.pending_counters) {
-            StatsDev h;
-            RT_HIP(hipMemcpy(&h, w.stats, sizeof h, hipMemcpyDeviceToHost));
-            copy_counters(h, out);
-            {
-                std::lock_guard<std::mutex> lock(sc->mu);
-                for (int o = 0; o < 9; o++) { sc->census_rounds[o] = h.op_rounds[o]; sc->census_lanes[o] = h.op_lanes[o]; }
-            }
+            std::lock_guard<std::mutex> lock(sc->mu);
+            for (int o = 0; o < 9; o++) { sc->census_rounds[o] = h.op_rounds[o]; sc->census_lanes[o] = h.op_lanes[o]; }
         }
-        float ms = 0.f;
-        RT_HIP(hipEventElapsedTime(&ms, w.ev0, w.ev1));
-        out.ms = (double)ms;
         out.spp_chunk = w.used_chunk; out.passes = w.used_passes; out.pool_slots = w.used_slots;
         out.partial_bytes = w.used_partial_bytes;
         if (w.used_kt) { out.trace_ms = w.kt.trace_ms; out.shade_ms = w.kt.shade_ms; }
@@ -802,144 +745,138 @@ int rt_scene_create(const rt_scene_desc *desc, rt_scene **out) {
         int ndev = 0;
         hipError_t e = hipGetDeviceCount(&ndev);
         RT_REQUIRE(e == hipSuccess && ndev > 0, RT_ERR_DEVICE, "rt_scene_create: no HIP device available (the path has no CPU fallback)");
-        rt_scene *sc = new rt_scene();
+        std::unique_ptr<rt_scene> sc(new rt_scene());         // (an error below frees what has been uploaded so far)
         if (const char *eg = getenv("RT2022_RING_GROUP")) sc->partial_ring_group = atoi(eg);
-        try {
-            RT_HIP(hipGetDevice(&sc->device));
-            RT_HIP(hipDeviceGetAttribute(&sc->n_cus, hipDeviceAttributeMultiprocessorCount, sc->device));
-            RT_REQUIRE(sc->n_cus > 0, RT_ERR_DEVICE, "rt_scene_create: device reports no compute units");
-            {
-                size_t free_b = 0, total_b = 0;
-                if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && total_b) sc->ring_threshold_bytes = (uint64_t)((double)total_b * 0.4);
-            }
-            SceneDev &s = sc->dev;
-            // Node refs of the device copy follow the breadth-first numbering (breadth_first_nodes).
-            const std::vector<uint32_t> new_of = breadth_first_nodes(*desc);
-            auto node_ref = [&](uint32_t ref) {
-                return RT_REF_KIND(ref) == RT_KIND_NODE ? (ref & ~RT_REF_INDEX_MASK) | new_of[RT_REF_INDEX(ref)] : ref;
-            };
-            {
-                std::vector<rt_bvh_node> nodes(desc->n_nodes);
-                for (uint32_t i = 0; i < desc->n_nodes; i++) {
-                    rt_bvh_node q = desc->nodes[i];
-                    q.left = node_ref(q.left); q.right = node_ref(q.right);
-                    // The PUSH REF of the node, for the wavefront traversal kernels (third word of the record's last 16 bytes): what
-                    // goes on the stack when the box is hit — the right child, or "nothing" (14 << 27, their REF_EMPTY) for a span-1
-                    // node holding the same plain primitive twice (bvh/mod.rs:44-47), whose second test finds the first one's hit again
-                    // (counted, not repeated). Media, movers, lists and nodes are really visited twice: they draw from the RNG or recurse.
-                    const uint32_t lk = RT_REF_KIND(q.left);
-                    q._pad[0] = (q.left == q.right && lk >= RT_KIND_SPHERE && lk <= RT_KIND_RING) ? (14u << RT_REF_KIND_SHIFT) : q.right;
-                    nodes[new_of[i]] = q;
-                }
-                s.nodes = upload(nodes.data(), nodes.size(), sc->owned);
-                std::vector<uint32_t> n32((size_t)8 * nodes.size() + 8);         // (never empty: upload of nothing is a null pointer)
-                for (size_t i = 0; i < nodes.size(); i++) {
-                    const rt_bvh_node &q = nodes[i];
-                    for (int ax = 0; ax < 3; ax++) {
-                        const float lo = (float)q.bmin[ax], hi = (float)q.bmax[ax];
-                        std::memcpy(&n32[8 * i + 2 * ax], &lo, 4);
-                        std::memcpy(&n32[8 * i + 2 * ax + 1], &hi, 4);
-                    }
-                    n32[8 * i + 6] = q.left; n32[8 * i + 7] = q._pad[0];
-                }
-                s.nodes32 = upload(n32.data(), n32.size(), sc->owned);
-            }
-            // Primitive pools go up with the slot kind of their material packed above the material index (pt_device.h).
-            RT_REQUIRE(desc->n_materials <= kMatIndexMask, RT_ERR_UNSUPPORTED, "more than 2^24 materials");
-            auto packed = [&](auto *src, uint64_t n) {
-                using T = std::remove_const_t<std::remove_pointer_t<decltype(src)>>;
-                std::vector<T> v(src, src + n);
-                for (T &q : v) {
-                    const rt_material &m = desc->materials[q.mat];
-                    uint32_t sk = m.kind == RT_MAT_DIFFUSE_LIGHT ? SK_LIGHT : m.kind == RT_MAT_METAL ? SK_METAL : m.kind == RT_MAT_DIELECTRIC ? SK_DIELECTRIC
-                                : m.kind == RT_MAT_ISOTROPIC ? SK_ISOTROPIC : (uint32_t)SK_LAMB_SOLID + desc->textures[m.tex].kind;
-                    q.mat |= sk << kMatKindShift;
-                }
-                return upload(v.data(), n, sc->owned);
-            };
-            s.spheres = packed(desc->spheres, desc->n_spheres);
-            s.moving_spheres = packed(desc->moving_spheres, desc->n_moving_spheres);
-            s.rects = packed(desc->rects, desc->n_rects);
-            s.boxes = packed(desc->boxes, desc->n_boxes);
-            s.triangles = packed(desc->triangles, desc->n_triangles);
-            s.rings = packed(desc->rings, desc->n_rings);
-            {
-                std::vector<rt_medium> media(desc->media, desc->media + desc->n_media);
-                for (rt_medium &m : media) m.boundary = node_ref(m.boundary);
-                s.media = packed(media.data(), media.size());
-            }
-            {
-                std::vector<MediumDev> md(desc->n_media);
-                uint32_t n_sph = 0;
-                for (uint32_t i = 0; i < desc->n_media; i++) {
-                    const rt_medium &m = desc->media[i];
-                    MediumDev &q = md[i];
-                    std::memset(&q, 0, sizeof q);
-                    q.neg_inv_density = m.neg_inv_density;
-                    q.boundary = node_ref(m.boundary);
-                    q.mat = m.mat | ((uint32_t)SK_ISOTROPIC << kMatKindShift);
-                    if (RT_REF_KIND(m.boundary) == RT_KIND_SPHERE && !(m.boundary & RT_REF_FLIP)) {
-                        const rt_sphere &sp = desc->spheres[RT_REF_INDEX(m.boundary)];
-                        q.center[0] = sp.center[0]; q.center[1] = sp.center[1]; q.center[2] = sp.center[2]; q.radius = sp.radius;
-                        q.sphere_boundary = 1;
-                        n_sph++;
-                    }
-                }
-                s.media_dev = upload(md.data(), md.size(), sc->owned);
-                s.media_mode = n_sph == 0 ? 0u : n_sph == desc->n_media ? 1u : 2u;
-            }
-            {
-                std::vector<rt_xform> xforms(desc->xforms, desc->xforms + desc->n_xforms);
-                for (rt_xform &x : xforms) x.child = node_ref(x.child);
-                s.xforms = upload(xforms.data(), xforms.size(), sc->owned);
-                std::vector<uint32_t> items(desc->list_items, desc->list_items + desc->n_list_items);
-                for (uint32_t &r : items) r = node_ref(r);
-                s.list_items = upload(items.data(), items.size(), sc->owned);
-            }
-            s.lists = upload(desc->lists, desc->n_lists, sc->owned);
-            s.lights = upload(desc->lights, desc->n_lights, sc->owned);
-            s.materials = upload(desc->materials, desc->n_materials, sc->owned);
-            s.textures = upload(desc->textures, desc->n_textures, sc->owned);
-            {
-                std::vector<MaterialDev> md(desc->n_materials);
-                for (uint32_t i = 0; i < desc->n_materials; i++) {
-                    const rt_material &m = desc->materials[i];
-                    MaterialDev &q = md[i];
-                    std::memset(&q, 0, sizeof q);
-                    q.tex = m.tex;
-                    std::memcpy(q.albedo, m.albedo, sizeof q.albedo);
-                    q.param = m.param;
-                    if (m.kind == RT_MAT_LAMBERTIAN || m.kind == RT_MAT_DIFFUSE_LIGHT || m.kind == RT_MAT_ISOTROPIC) {
-                        const rt_texture &t = desc->textures[m.tex];
-                        q.tex_kind = t.kind; q.tex_a = t.a; q.tex_b = t.b; q.tex_scale = t.scale;
-                        std::memcpy(q.tex_color, t.color, sizeof q.tex_color);
-                    }
-                }
-                s.materials_dev = upload(md.data(), md.size(), sc->owned);
-            }
-            s.images = upload(desc->images, desc->n_images, sc->owned);
-            s.image_data = upload(desc->image_data, desc->image_data_bytes, sc->owned);
-            s.perlins = upload(desc->perlins, desc->n_perlins, sc->owned);
-            s.root = node_ref(desc->root);
-            s.n_lights = desc->n_lights;
-            s.n_nodes = desc->n_nodes;
-            s.n_xforms = desc->n_xforms;
-            s.n_media = desc->n_media;
-            s.n_spheres = desc->n_spheres;
-            s.n_moving_spheres = desc->n_moving_spheres;
-            s.n_rects = desc->n_rects;
-            sc->stack_need = (uint32_t)need;
-            sc->general_boundaries = v.general_boundaries;
-            sc->boxes_plain = v.boxes_plain();
-            sc->features = ((desc->n_triangles || desc->n_rings) ? kFeatMisc : 0u) |
-                           ((desc->n_xforms || desc->n_lists) ? kFeatMovers : 0u) |
-                           ((desc->n_boxes || desc->n_media) ? kFeatVolumes : 0u);
-        } catch (...) {
-            for (void *p : sc->owned) (void)hipFree(p);
-            delete sc;
-            throw;
+        RT_HIP(hipGetDevice(&sc->device));
+        RT_HIP(hipDeviceGetAttribute(&sc->n_cus, hipDeviceAttributeMultiprocessorCount, sc->device));
+        RT_REQUIRE(sc->n_cus > 0, RT_ERR_DEVICE, "rt_scene_create: device reports no compute units");
+        {
+            size_t free_b = 0, total_b = 0;
+            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && total_b) sc->ring_threshold_bytes = (uint64_t)((double)total_b * 0.4);
         }
-        *out = sc;
+        SceneDev &s = sc->dev;
+        // Node refs of the device copy follow the breadth-first numbering (breadth_first_nodes).
+        const std::vector<uint32_t> new_of = breadth_first_nodes(*desc);
+        auto node_ref = [&](uint32_t ref) {
+            return RT_REF_KIND(ref) == RT_KIND_NODE ? (ref & ~RT_REF_INDEX_MASK) | new_of[RT_REF_INDEX(ref)] : ref;
+        };
+        {
+            std::vector<rt_bvh_node> nodes(desc->n_nodes);
+            for (uint32_t i = 0; i < desc->n_nodes; i++) {
+                rt_bvh_node q = desc->nodes[i];
+                q.left = node_ref(q.left); q.right = node_ref(q.right);
+                // The PUSH REF of the node, for the wavefront traversal kernels (third word of the record's last 16 bytes): what
+                // goes on the stack when the box is hit — the right child, or "nothing" (14 << 27, their REF_EMPTY) for a span-1
+                // node holding the same plain primitive twice (bvh/mod.rs:44-47), whose second test finds the first one's hit again
+                // (counted, not repeated). Media, movers, lists and nodes are really visited twice: they draw from the RNG or recurse.
+                const uint32_t lk = RT_REF_KIND(q.left);
+                q._pad[0] = (q.left == q.right && lk >= RT_KIND_SPHERE && lk <= RT_KIND_RING) ? (14u << RT_REF_KIND_SHIFT) : q.right;
+                nodes[new_of[i]] = q;
+            }
+            s.nodes = upload(nodes.data(), nodes.size(), sc->owned);
+            std::vector<uint32_t> n32((size_t)8 * nodes.size() + 8);         // (never empty: upload of nothing is a null pointer)
+            for (size_t i = 0; i < nodes.size(); i++) {
+                const rt_bvh_node &q = nodes[i];
+                for (int ax = 0; ax < 3; ax++) {
+                    const float lo = (float)q.bmin[ax], hi = (float)q.bmax[ax];
+                    std::memcpy(&n32[8 * i + 2 * ax], &lo, 4);
+                    std::memcpy(&n32[8 * i + 2 * ax + 1], &hi, 4);
+                }
+                n32[8 * i + 6] = q.left; n32[8 * i + 7] = q._pad[0];
+            }
+            s.nodes32 = upload(n32.data(), n32.size(), sc->owned);
+        }
+        // Primitive pools go up with the slot kind of their material packed above the material index (pt_device.h).
+        RT_REQUIRE(desc->n_materials <= kMatIndexMask, RT_ERR_UNSUPPORTED, "more than 2^24 materials");
+        auto packed = [&](auto *src, uint64_t n) {
+            using T = std::remove_const_t<std::remove_pointer_t<decltype(src)>>;
+            std::vector<T> v(src, src + n);
+            for (T &q : v) {
+                const rt_material &m = desc->materials[q.mat];
+                uint32_t sk = m.kind == RT_MAT_DIFFUSE_LIGHT ? SK_LIGHT : m.kind == RT_MAT_METAL ? SK_METAL : m.kind == RT_MAT_DIELECTRIC ? SK_DIELECTRIC
+                            : m.kind == RT_MAT_ISOTROPIC ? SK_ISOTROPIC : (uint32_t)SK_LAMB_SOLID + desc->textures[m.tex].kind;
+                q.mat |= sk << kMatKindShift;
+            }
+            return upload(v.data(), n, sc->owned);
+        };
+        s.spheres = packed(desc->spheres, desc->n_spheres);
+        s.moving_spheres = packed(desc->moving_spheres, desc->n_moving_spheres);
+        s.rects = packed(desc->rects, desc->n_rects);
+        s.boxes = packed(desc->boxes, desc->n_boxes);
+        s.triangles = packed(desc->triangles, desc->n_triangles);
+        s.rings = packed(desc->rings, desc->n_rings);
+        {
+            std::vector<rt_medium> media(desc->media, desc->media + desc->n_media);
+            for (rt_medium &m : media) m.boundary = node_ref(m.boundary);
+            s.media = packed(media.data(), media.size());
+        }
+        {
+            std::vector<MediumDev> md(desc->n_media);
+            uint32_t n_sph = 0;
+            for (uint32_t i = 0; i < desc->n_media; i++) {
+                const rt_medium &m = desc->media[i];
+                MediumDev &q = md[i];
+                std::memset(&q, 0, sizeof q);
+                q.neg_inv_density = m.neg_inv_density;
+                q.boundary = node_ref(m.boundary);
+                q.mat = m.mat | ((uint32_t)SK_ISOTROPIC << kMatKindShift);
+                if (RT_REF_KIND(m.boundary) == RT_KIND_SPHERE && !(m.boundary & RT_REF_FLIP)) {
+                    const rt_sphere &sp = desc->spheres[RT_REF_INDEX(m.boundary)];
+                    q.center[0] = sp.center[0]; q.center[1] = sp.center[1]; q.center[2] = sp.center[2]; q.radius = sp.radius;
+                    q.sphere_boundary = 1;
+                    n_sph++;
+                }
+            }
+            s.media_dev = upload(md.data(), md.size(), sc->owned);
+            s.media_mode = n_sph == 0 ? 0u : n_sph == desc->n_media ? 1u : 2u;
+        }
+        {
+            std::vector<rt_xform> xforms(desc->xforms, desc->xforms + desc->n_xforms);
+            for (rt_xform &x : xforms) x.child = node_ref(x.child);
+            s.xforms = upload(xforms.data(), xforms.size(), sc->owned);
+            std::vector<uint32_t> items(desc->list_items, desc->list_items + desc->n_list_items);
+            for (uint32_t &r : items) r = node_ref(r);
+            s.list_items = upload(items.data(), items.size(), sc->owned);
+        }
+        s.lists = upload(desc->lists, desc->n_lists, sc->owned);
+        s.lights = upload(desc->lights, desc->n_lights, sc->owned);
+        s.materials = upload(desc->materials, desc->n_materials, sc->owned);
+        s.textures = upload(desc->textures, desc->n_textures, sc->owned);
+        {
+            std::vector<MaterialDev> md(desc->n_materials);
+            for (uint32_t i = 0; i < desc->n_materials; i++) {
+                const rt_material &m = desc->materials[i];
+                MaterialDev &q = md[i];
+                std::memset(&q, 0, sizeof q);
+                q.tex = m.tex;
+                std::memcpy(q.albedo, m.albedo, sizeof q.albedo);
+                q.param = m.param;
+                if (m.kind == RT_MAT_LAMBERTIAN || m.kind == RT_MAT_DIFFUSE_LIGHT || m.kind == RT_MAT_ISOTROPIC) {
+                    const rt_texture &t = desc->textures[m.tex];
+                    q.tex_kind = t.kind; q.tex_a = t.a; q.tex_b = t.b; q.tex_scale = t.scale;
+                    std::memcpy(q.tex_color, t.color, sizeof q.tex_color);
+                }
+            }
+            s.materials_dev = upload(md.data(), md.size(), sc->owned);
+        }
+        s.images = upload(desc->images, desc->n_images, sc->owned);
+        s.image_data = upload(desc->image_data, desc->image_data_bytes, sc->owned);
+        s.perlins = upload(desc->perlins, desc->n_perlins, sc->owned);
+        s.root = node_ref(desc->root);
+        s.n_lights = desc->n_lights;
+        s.n_nodes = desc->n_nodes;
+        s.n_xforms = desc->n_xforms;
+        s.n_media = desc->n_media;
+        s.n_spheres = desc->n_spheres;
+        s.n_moving_spheres = desc->n_moving_spheres;
+        s.n_rects = desc->n_rects;
+        sc->stack_need = (uint32_t)need;
+        sc->general_boundaries = v.general_boundaries;
+        sc->boxes_plain = v.boxes_plain();
+        sc->features = ((desc->n_triangles || desc->n_rings) ? kFeatMisc : 0u) |
+                       ((desc->n_xforms || desc->n_lists) ? kFeatMovers : 0u) |
+                       ((desc->n_boxes || desc->n_media) ? kFeatVolumes : 0u);
+        *out = sc.release();
         return RT_OK;
     });
 }
@@ -951,41 +888,7 @@ int rt_scene_destroy(rt_scene *scene) {
         for (auto &kv : scene->ws)                    // (asynchronous calls still in flight: let their host threads finish)
             if (kv.second.async_worker.joinable()) kv.second.async_worker.join();
         (void)hipDeviceSynchronize();                 // (every stream of the scene's device, the group streams included)
-        for (auto &kv : scene->ws) {
-            Workspace &w = kv.second;
-            if (w.rows_max) (void)hipFree(w.rows_max);
-            if (w.h_rows_max) (void)hipHostFree(w.h_rows_max);
-            for (hipEvent_t ev : w.kt.ev) (void)hipEventDestroy(ev);
-            if (w.work_counter) (void)hipFree(w.work_counter);
-            if (w.stats) (void)hipFree(w.stats);
-            if (w.partial) (void)hipFree(w.partial);
-            if (w.tape) (void)hipFree(w.tape);
-            for (void *p : w.pool_owned) (void)hipFree(p);
-            if (w.d_scene) (void)hipFree(w.d_scene);
-            if (w.d_args) (void)hipFree(w.d_args);
-            if (w.d_pool) (void)hipFree(w.d_pool);
-            if (w.gs.h_active) (void)hipHostFree(w.gs.h_active);
-            if (w.gs.h_work) (void)hipHostFree(w.gs.h_work);
-            if (w.gs.h_oldest) (void)hipHostFree(w.gs.h_oldest);
-            if (w.d_limit) (void)hipFree(w.d_limit);
-            if (w.rad_rays) (void)hipFree(w.rad_rays);
-            if (w.rad_out) (void)hipFree(w.rad_out);
-            for (int g = 0; g < kMaxGroups; g++) {
-                if (w.gs.stream[g]) (void)hipStreamDestroy(w.gs.stream[g]);
-                for (int b = 0; b < 2; b++) if (w.gs.ev[g][b]) (void)hipEventDestroy(w.gs.ev[g][b]);
-            }
-            if (w.ev0) (void)hipEventDestroy(w.ev0);
-            if (w.ev1) (void)hipEventDestroy(w.ev1);
-        }
-        for (auto &kv : scene->qs) {
-            QueryScratch &q = *kv.second;
-            if (q.counter) (void)hipFree(q.counter);
-            if (q.stats) (void)hipFree(q.stats);
-            if (q.ev0) (void)hipEventDestroy(q.ev0);
-            if (q.ev1) (void)hipEventDestroy(q.ev1);
-        }
-        for (void *p : scene->owned) (void)hipFree(p);
-        delete scene;
+        delete scene;                                 // (its workspaces, query scratch and pools free themselves, this device current)
         return RT_OK;
     });
 }
@@ -1002,6 +905,16 @@ static int join_async(rt_scene *scene, hipStream_t stream, std::string *err, boo
     return rc;
 }
 
+// One call at a time per (scene, stream): an asynchronous one still in flight there is joined and finished first — its rt_stats,
+// as rt_render_wait would have filled them — and its failure is the failure of `who`, the call that found it.
+static void finish_previous_async(rt_scene *sc, hipStream_t stream, const char *who) {
+    std::string err;
+    bool joined = false;
+    const int rc = join_async(sc, stream, &err, &joined);
+    RT_REQUIRE(rc == RT_OK, rc, std::string(who) + ": the previous asynchronous call on this stream failed: " + err);
+    if (joined) finish(sc, stream);
+}
+
 int rt_render_device(rt_scene *scene, const rt_camera *cam, const rt_params *params,
                      double *d_out_rgb_sum, void *hip_stream, rt_stats *stats) {
     return guarded([&]() -> int {
@@ -1009,13 +922,7 @@ int rt_render_device(rt_scene *scene, const rt_camera *cam, const rt_params *par
         RT_REQUIRE(d_out_rgb_sum || params->n_rows == 0, RT_ERR_INVALID, "rt_render_device: output is null");
         DeviceGuard guard(scene->device);
         const hipStream_t stream = (hipStream_t)hip_stream;
-        {   // one call at a time per (scene, stream): an asynchronous one still in flight is finished first
-            std::string err;
-            bool joined = false;
-            const int rc = join_async(scene, stream, &err, &joined);
-            RT_REQUIRE(rc == RT_OK, rc, "rt_render_device: the previous asynchronous call on this stream failed: " + err);
-            if (joined) finish(scene, stream);        // (its rt_stats, as rt_render_wait would have filled them)
-        }
+        finish_previous_async(scene, stream, "rt_render_device");
         if (!(params->flags & RT_FLAG_ASYNC)) {
             enqueue(scene, cam, params, params->row_ids, d_out_rgb_sum, stream, stats, true);
             return RT_OK;
@@ -1053,17 +960,11 @@ int rt_render_wait(rt_scene *scene, void *hip_stream) {
 }
 
 // An rt_radiance* call runs in the render's workspace of (scene, stream): an asynchronous render still in flight there (its host
-// thread drives passes on that workspace) is joined and finished first, as rt_render_device does. Each entry point calls this
-// once, before it touches the workspace in any way — rt_radiance before its staging buffers, which live in the workspace too.
-static void join_before_radiance(rt_scene *sc, hipStream_t stream, const char *who) {
-    std::string err;
-    bool joined = false;
-    const int rc = join_async(sc, stream, &err, &joined);
-    RT_REQUIRE(rc == RT_OK, rc, std::string(who) + ": the previous asynchronous call on this stream failed: " + err);
-    if (joined) finish(sc, stream);
-}
+// thread drives passes on that workspace) is joined and finished first (finish_previous_async), as rt_render_device does. Each
+// entry point does so once, before it touches the workspace in any way — rt_radiance before its staging buffers, which live in
+// the workspace too.
 
-// One rt_radiance* call on `stream` (the scene's device is current, the arguments checked, join_before_radiance done): the
+// One rt_radiance* call on `stream` (the scene's device is current, the arguments checked, finish_previous_async done): the
 // passes, and stats.
 static void run_radiance(rt_scene *sc, const rt_radiance_ray *d_rays, uint64_t n_rays, const rt_radiance_params *rp, double *d_out,
                          hipStream_t stream, rt_stats *stats) {
@@ -1099,16 +1000,11 @@ int rt_radiance(rt_scene *scene, const rt_radiance_ray *rays, uint64_t n_rays, c
     return guarded([&]() -> int {
         check_radiance(scene, rays, n_rays, p, out_rgb_sum, false, "rt_radiance");
         DeviceGuard guard(scene->device);
-        join_before_radiance(scene, nullptr, "rt_radiance");       // (first: the staging buffers below belong to the workspace)
+        finish_previous_async(scene, nullptr, "rt_radiance");       // (first: the staging buffers below belong to the workspace)
         Workspace &w = workspace_for(scene, nullptr);
-        if (n_rays > w.rad_cap) {                              // staging buffers of the workspace, kept for the next call
-            if (w.rad_rays) RT_HIP(hipFree(w.rad_rays));        // (the calls that used them were synchronous: nothing is in flight)
-            if (w.rad_out) RT_HIP(hipFree(w.rad_out));
-            w.rad_rays = nullptr; w.rad_out = nullptr; w.rad_cap = 0;
-            RT_HIP(hipMalloc((void **)&w.rad_rays, n_rays * sizeof(rt_radiance_ray)));
-            RT_HIP(hipMalloc((void **)&w.rad_out, n_rays * 3 * sizeof(double)));
-            w.rad_cap = n_rays;
-        }
+        // staging buffers of the workspace, kept for the next call (the calls that used them were synchronous: nothing is in flight)
+        w.rad_rays.reserve(n_rays);
+        w.rad_out.reserve(n_rays * 3);
         if (n_rays) {
             RT_HIP(hipMemcpy(w.rad_rays, rays, n_rays * sizeof(rt_radiance_ray), hipMemcpyHostToDevice));
             // Poison the output so an unwritten sum cannot pass for a result.
@@ -1125,7 +1021,7 @@ int rt_radiance_device(rt_scene *scene, const rt_radiance_ray *d_rays, uint64_t 
     return guarded([&]() -> int {
         check_radiance(scene, d_rays, n_rays, p, d_out_rgb_sum, true, "rt_radiance_device");
         DeviceGuard guard(scene->device);
-        join_before_radiance(scene, (hipStream_t)hip_stream, "rt_radiance_device");
+        finish_previous_async(scene, (hipStream_t)hip_stream, "rt_radiance_device");
         run_radiance(scene, d_rays, n_rays, p, d_out_rgb_sum, (hipStream_t)hip_stream, stats);
         return RT_OK;
     });
@@ -1140,22 +1036,12 @@ int rt_intersect(rt_scene *scene, const rt_query_ray *rays, uint64_t n_rays, uin
         }
         RT_REQUIRE(n_rays <= (1ull << 40), RT_ERR_INVALID, "rt_intersect: n_rays too large");
         DeviceGuard guard(scene->device);
-        rt_query_ray *d_rays = nullptr;
-        rt_hit *d_hits = nullptr;
-        int rc = RT_OK;
-        try {
-            RT_HIP(hipMalloc((void **)&d_rays, n_rays * sizeof(rt_query_ray)));
-            RT_HIP(hipMalloc((void **)&d_hits, n_rays * sizeof(rt_hit)));
-            RT_HIP(hipMemcpy(d_rays, rays, n_rays * sizeof(rt_query_ray), hipMemcpyHostToDevice));
-            run_query(scene, d_rays, n_rays, flags, d_hits, nullptr, stats);
-            RT_HIP(hipMemcpy(out_hits, d_hits, n_rays * sizeof(rt_hit), hipMemcpyDeviceToHost));
-        } catch (const Fail &e) {
-            set_error(e.msg);
-            rc = e.code;
-        }
-        if (d_rays) (void)hipFree(d_rays);
-        if (d_hits) (void)hipFree(d_hits);
-        return rc;
+        DeviceBuf<rt_query_ray> d_rays(n_rays);                // (after the guard: freed with the scene's device current)
+        DeviceBuf<rt_hit> d_hits(n_rays);
+        RT_HIP(hipMemcpy(d_rays, rays, n_rays * sizeof(rt_query_ray), hipMemcpyHostToDevice));
+        run_query(scene, d_rays, n_rays, flags, d_hits, nullptr, stats);
+        RT_HIP(hipMemcpy(out_hits, d_hits, n_rays * sizeof(rt_hit), hipMemcpyDeviceToHost));
+        return RT_OK;
     });
 }
 
@@ -1183,25 +1069,15 @@ int rt_render(rt_scene *scene, const rt_camera *cam, const rt_params *params, do
             RT_REQUIRE(params->row_ids[i] < (uint64_t)params->height * params->n_frames, RT_ERR_INVALID, "rt_render: row id out of range");
         uint64_t n_values = (uint64_t)params->n_rows * params->width * 3;
         DeviceGuard guard(scene->device);
-        uint32_t *d_rows = nullptr;
-        double *d_out = nullptr;
-        int rc = RT_OK;
-        try {
-            RT_HIP(hipMalloc((void **)&d_rows, (params->n_rows ? params->n_rows : 1) * sizeof(uint32_t)));
-            RT_HIP(hipMalloc((void **)&d_out, (n_values ? n_values : 1) * sizeof(double)));
-            if (params->n_rows) RT_HIP(hipMemcpy(d_rows, params->row_ids, params->n_rows * sizeof(uint32_t), hipMemcpyHostToDevice));
-            // Poison the output so an unwritten pixel cannot pass for a result.
-            RT_HIP(hipMemset(d_out, 0xFF, (n_values ? n_values : 1) * sizeof(double)));
-            enqueue(scene, cam, params, d_rows, d_out, nullptr, stats);
-            finish(scene, nullptr);
-            if (n_values) RT_HIP(hipMemcpy(out_rgb_sum, d_out, n_values * sizeof(double), hipMemcpyDeviceToHost));
-        } catch (const Fail &e) {
-            set_error(e.msg);
-            rc = e.code;
-        }
-        if (d_rows) (void)hipFree(d_rows);
-        if (d_out) (void)hipFree(d_out);
-        return rc;
+        DeviceBuf<uint32_t> d_rows(params->n_rows ? params->n_rows : 1);     // (after the guard: freed with the scene's device current)
+        DeviceBuf<double> d_out(n_values ? n_values : 1);
+        if (params->n_rows) RT_HIP(hipMemcpy(d_rows, params->row_ids, params->n_rows * sizeof(uint32_t), hipMemcpyHostToDevice));
+        // Poison the output so an unwritten pixel cannot pass for a result.
+        RT_HIP(hipMemset(d_out, 0xFF, (n_values ? n_values : 1) * sizeof(double)));
+        enqueue(scene, cam, params, d_rows, d_out, nullptr, stats);
+        finish(scene, nullptr);
+        if (n_values) RT_HIP(hipMemcpy(out_rgb_sum, d_out, n_values * sizeof(double), hipMemcpyDeviceToHost));
+        return RT_OK;
     });
 }
 
@@ -1326,37 +1202,24 @@ int rt_tonemap_device(const double *d_rgb_sum, uint64_t n_pixels, int32_t spp, u
 int rt_debug_math_device(int op, const double *a, const double *b, double *out, uint64_t n) {
     return guarded([&]() -> int {
         RT_REQUIRE(a && out, RT_ERR_INVALID, "rt_debug_math_device: null argument");
-        double *da = nullptr, *db = nullptr, *dout = nullptr;
-        int rc = RT_OK;
-        try {
-            RT_HIP(hipMalloc((void **)&da, n * 8 + 8));
-            RT_HIP(hipMalloc((void **)&dout, n * 8 + 8));
-            RT_HIP(hipMemcpy(da, a, n * 8, hipMemcpyHostToDevice));
-            if (b) { RT_HIP(hipMalloc((void **)&db, n * 8 + 8)); RT_HIP(hipMemcpy(db, b, n * 8, hipMemcpyHostToDevice)); }
-            RT_HIP(launch_math_probe(op, da, db, dout, n, nullptr));
-            RT_HIP(hipDeviceSynchronize());
-            RT_HIP(hipMemcpy(out, dout, n * 8, hipMemcpyDeviceToHost));
-        } catch (const Fail &e) { set_error(e.msg); rc = e.code; }
-        if (da) (void)hipFree(da);
-        if (db) (void)hipFree(db);
-        if (dout) (void)hipFree(dout);
-        return rc;
+        DeviceBuf<double> da(n + 1), dout(n + 1), db;
+        RT_HIP(hipMemcpy(da, a, n * 8, hipMemcpyHostToDevice));
+        if (b) { db.reserve(n + 1); RT_HIP(hipMemcpy(db, b, n * 8, hipMemcpyHostToDevice)); }
+        RT_HIP(launch_math_probe(op, da, db, dout, n, nullptr));
+        RT_HIP(hipDeviceSynchronize());
+        RT_HIP(hipMemcpy(out, dout, n * 8, hipMemcpyDeviceToHost));
+        return RT_OK;
     });
 }
 
 int rt_debug_rng_device(uint64_t state, int mode, double lo, double hi, uint64_t bound, uint64_t *out, uint64_t n) {
     return guarded([&]() -> int {
         RT_REQUIRE(out, RT_ERR_INVALID, "rt_debug_rng_device: null argument");
-        uint64_t *dout = nullptr;
-        int rc = RT_OK;
-        try {
-            RT_HIP(hipMalloc((void **)&dout, n * 8 + 8));
-            RT_HIP(launch_rng_probe(state, mode, lo, hi, bound, dout, n, nullptr));
-            RT_HIP(hipDeviceSynchronize());
-            RT_HIP(hipMemcpy(out, dout, n * 8, hipMemcpyDeviceToHost));
-        } catch (const Fail &e) { set_error(e.msg); rc = e.code; }
-        if (dout) (void)hipFree(dout);
-        return rc;
+        DeviceBuf<uint64_t> dout(n + 1);
+        RT_HIP(launch_rng_probe(state, mode, lo, hi, bound, dout, n, nullptr));
+        RT_HIP(hipDeviceSynchronize());
+        RT_HIP(hipMemcpy(out, dout, n * 8, hipMemcpyDeviceToHost));
+        return RT_OK;
     });
 }
 
@@ -1403,31 +1266,25 @@ extern "C" {
 int rt_debug_traffic_probe(int mode, uint64_t buffer_bytes, uint64_t n_access, uint64_t seed) {
     return guarded([&]() -> int {
         RT_REQUIRE(mode >= 0 && mode <= 6 && buffer_bytes >= 4096, RT_ERR_INVALID, "rt_debug_traffic_probe: bad arguments");
-        probe_u32x4 *buf = nullptr;
-        uint32_t *sink = nullptr;
-        int rc = RT_OK;
-        try {
-            RT_HIP(hipMalloc((void **)&buf, buffer_bytes));
-            RT_HIP(hipMalloc((void **)&sink, 4));
-            RT_HIP(hipMemset(buf, 1, buffer_bytes));
-            RT_HIP(hipDeviceSynchronize());
-            const uint64_t n_records = buffer_bytes / 128;
-            if (mode == 0 || mode == 3) n_access = buffer_bytes / 16;
-            switch (mode) {
-                case 0: launch_probe<0>(buf, n_records, n_access, seed, sink); break;
-                case 1: launch_probe<1>(buf, n_records, n_access, seed, sink); break;
-                case 2: launch_probe<2>(buf, n_records, n_access, seed, sink); break;
-                case 3: launch_probe<3>(buf, n_records, n_access, seed, sink); break;
-                case 4: launch_probe<4>(buf, n_records, n_access, seed, sink); break;
-                case 5: launch_probe<5>(buf, n_records, n_access, seed, sink); break;
-                default: launch_probe<6>(buf, n_records, n_access, seed, sink); break;
-            }
-            RT_HIP(hipGetLastError());
-            RT_HIP(hipDeviceSynchronize());
-        } catch (const Fail &e) { set_error(e.msg); rc = e.code; }
-        if (buf) (void)hipFree(buf);
-        if (sink) (void)hipFree(sink);
-        return rc;
+        DeviceBuf<char> buf_owner(buffer_bytes);
+        DeviceBuf<uint32_t> sink(1);
+        probe_u32x4 *const buf = reinterpret_cast<probe_u32x4 *>(buf_owner.p);
+        RT_HIP(hipMemset(buf, 1, buffer_bytes));
+        RT_HIP(hipDeviceSynchronize());
+        const uint64_t n_records = buffer_bytes / 128;
+        if (mode == 0 || mode == 3) n_access = buffer_bytes / 16;
+        switch (mode) {
+            case 0: launch_probe<0>(buf, n_records, n_access, seed, sink); break;
+            case 1: launch_probe<1>(buf, n_records, n_access, seed, sink); break;
+            case 2: launch_probe<2>(buf, n_records, n_access, seed, sink); break;
+            case 3: launch_probe<3>(buf, n_records, n_access, seed, sink); break;
+            case 4: launch_probe<4>(buf, n_records, n_access, seed, sink); break;
+            case 5: launch_probe<5>(buf, n_records, n_access, seed, sink); break;
+            default: launch_probe<6>(buf, n_records, n_access, seed, sink); break;
+        }
+        RT_HIP(hipGetLastError());
+        RT_HIP(hipDeviceSynchronize());
+        return RT_OK;
     });
 }
 
@@ -1478,24 +1335,19 @@ int rt_debug_valu_probe(int mode, uint32_t iters) {
         RT_HIP(hipGetDevice(&dev));
         RT_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
         const uint32_t blocks = (uint32_t)cus * (mode == 4 ? 1u : 8u);       // 8 workgroups of 4 waves per CU = 8 waves per SIMD (mode 4: one)
-        double *out = nullptr;
-        int rc = RT_OK;
-        try {
-            RT_HIP(hipMalloc((void **)&out, (uint64_t)blocks * 256 * sizeof(double)));
-            const double b = 0.9999999, c = 1e-9;
-            const uint32_t k = 0x9E3779B9u;
-            switch (mode) {
-                case 0: hipLaunchKernelGGL((valu_probe_kernel<0>), dim3(blocks), dim3(256), 0, nullptr, out, iters, b, c, k); break;
-                case 1: hipLaunchKernelGGL((valu_probe_kernel<1>), dim3(blocks), dim3(256), 0, nullptr, out, iters, b, c, k); break;
-                case 2: hipLaunchKernelGGL((valu_probe_kernel<2>), dim3(blocks), dim3(256), 0, nullptr, out, iters, b, c, k); break;
-                case 3: hipLaunchKernelGGL((valu_probe_kernel<3>), dim3(blocks), dim3(256), 0, nullptr, out, iters, b, c, k); break;
-                default: hipLaunchKernelGGL((valu_probe_kernel<4>), dim3(blocks), dim3(256), 0, nullptr, out, iters, b, c, k); break;
-            }
-            RT_HIP(hipGetLastError());
-            RT_HIP(hipDeviceSynchronize());
-        } catch (const Fail &e) { set_error(e.msg); rc = e.code; }
-        if (out) (void)hipFree(out);
-        return rc;
+        DeviceBuf<double> out((uint64_t)blocks * 256);
+        const double b = 0.9999999, c = 1e-9;
+        const uint32_t k = 0x9E3779B9u;
+        switch (mode) {
+            case 0: hipLaunchKernelGGL((valu_probe_kernel<0>), dim3(blocks), dim3(256), 0, nullptr, out.p, iters, b, c, k); break;
+            case 1: hipLaunchKernelGGL((valu_probe_kernel<1>), dim3(blocks), dim3(256), 0, nullptr, out.p, iters, b, c, k); break;
+            case 2: hipLaunchKernelGGL((valu_probe_kernel<2>), dim3(blocks), dim3(256), 0, nullptr, out.p, iters, b, c, k); break;
+            case 3: hipLaunchKernelGGL((valu_probe_kernel<3>), dim3(blocks), dim3(256), 0, nullptr, out.p, iters, b, c, k); break;
+            default: hipLaunchKernelGGL((valu_probe_kernel<4>), dim3(blocks), dim3(256), 0, nullptr, out.p, iters, b, c, k); break;
+        }
+        RT_HIP(hipGetLastError());
+        RT_HIP(hipDeviceSynchronize());
+        return RT_OK;
     });
 }
 
