@@ -482,6 +482,69 @@ int rt_radiance(rt_scene *scene, const rt_radiance_ray *rays, uint64_t n_rays, c
 int rt_radiance_device(rt_scene *scene, const rt_radiance_ray *d_rays, uint64_t n_rays, const rt_radiance_params *p,
                        double *d_out_rgb_sum, void *hip_stream, rt_stats *stats);
 
+/* ---- first-hit feature buffers of a render's view ---------------------------------------------------
+ * The guide buffers of a frame — per-pixel albedo, shading normal, depth and coverage — for exactly the camera rays
+ * rt_render shoots with the same rt_camera and rt_params: what a denoiser, an adaptive sampler, an edge-aware upscaler or
+ * a compositor reads beside the radiance sums. Only the first segment of every path is traced; nothing bounces.
+ *
+ * For each entry g of params->row_ids (frame g / height, image row py = g % height, as for a render), each px in
+ * [0, width) and each sample s in [0, spp): rng = Rng(path_key(seed, frame, py * width + px, s)); rand_u, rand_v =
+ * rng.gen_f64() twice; r = get_ray(cam, (px + rand_u) / (width - 1), (py + rand_v) / (height - 1), rng) — the render's
+ * own code (main.rs:144-149) — and rec = world.hit(r, t_min, f64::MAX) on the scene's root with the SAME rng continuing,
+ * so a ConstantMedium draws the words the render's first ray draws. The sample's features:
+ *
+ *   field      hit                                                                             miss
+ *   albedo[3]  by the kind of rec.mat — LAMBERTIAN / ISOTROPIC: texture_value(tex, rec.u,      params->background
+ *              rec.v, rec.p); METAL: its albedo; DIELECTRIC: (1, 1, 1); DIFFUSE_LIGHT:
+ *              texture_value(tex, u, v, p) on the front face, (0, 0, 0) on the back — scatter's
+ *              attenuation where the material scatters, emitted where it does not (material/mod.rs)
+ *   normal[3]  rec.normal: face-oriented, carried out through movers and FlipFace refs;          0
+ *              a medium's (1, 0, 0) as it is
+ *   depth      rec.t                                                                            0
+ *   hits       1                                                                                0
+ *
+ * Each field of a pixel's record is 0 + f_0 + f_1 + ... + f_{spp-1}, added in sample order and NOT divided by spp, like a
+ * render's sums (rt_tonemap_device / rt_write_color do not apply): hits / spp is coverage, depth / hits the mean depth over
+ * the hits. Records come in row_ids order, n_rows * width of them. Every sum is the CPU oracle's composition rto_path_key
+ * -> rto_get_ray -> rto_hit -> rto_texture_value bit for bit (NaN where the oracle gives NaN — width == 1 or height == 1
+ * divide by zero as the render does) on every scene rt_scene_create accepts.
+ *
+ * rt_params: the render's struct, so one struct describes both calls of a frame. Used: width, height, spp, background,
+ * t_min, seed, n_frames, n_rows, row_ids, flags. IGNORED: max_depth (features are defined for a depth-0 render too),
+ * spp_chunk, progress_cb / progress_user. row_ids is host memory for rt_features, device memory for rt_features_device.
+ *
+ * Arguments: spp == 0 or n_rows == 0 is RT_OK (zeros or nothing written, no kernel). RT_ERR_INVALID with rt_last_error()
+ * set, before any kernel: a null scene, cam or params; null rows or output with work to do; a flag bit other than
+ * RT_FLAG_COUNTERS; a device output that is not 16-byte aligned or device rows that are not 4-byte aligned; width, height
+ * or n_frames equal to 0 (or cam->time0 >= cam->time1, as for a render); a row id >= height * n_frames (device rows are
+ * checked by the small reduction kernel rt_render_device uses, behind one synchronisation of hip_stream before the
+ * feature kernel is enqueued).
+ *
+ * rt_stats (may be NULL): paths = rays = n_rows * width * spp; with RT_FLAG_COUNTERS node_visits and prim_tests[] are the
+ * sums of rto_hit's counters and rng_draws the camera's words (2 + what rto_get_ray returns) plus the hit's; ms is the
+ * device time of the call; everything else is 0.
+ *
+ * Independence: a call owns its scratch per (scene, stream) — a work counter, a counter block, two events — and uses
+ * neither engine, so it works whichever is selected, never touches a render's pool, tape or pending stats, and may run on
+ * another stream beside an RT_FLAG_ASYNC render or a query of the same scene; all of them keep their serial results bit
+ * for bit. rt_scene_destroy waits for it. The call makes the scene's device current and restores the caller's. There is
+ * no rt_scene_set form. One lane works one pixel through all its samples: a job of a few pixels at a huge spp balances
+ * poorly — the intended use is a whole frame at modest spp. */
+typedef struct rt_feature {           /* 64 B: four 16-byte pieces */
+    double   albedo[3];
+    double   normal[3];
+    double   depth;
+    double   hits;
+} rt_feature;
+
+/* Host buffers (n_rows * width records out); synchronous. stats may be NULL. */
+int rt_features(rt_scene *scene, const rt_camera *cam, const rt_params *params,
+                rt_feature *out_features, rt_stats *stats);
+/* Device buffers, enqueued on hip_stream (NULL = default stream). With stats == NULL the call returns once the kernel is
+ * enqueued; with stats it synchronises hip_stream and fills stats, like rt_intersect_device. */
+int rt_features_device(rt_scene *scene, const rt_camera *cam, const rt_params *params,
+                       rt_feature *d_out_features, void *hip_stream, rt_stats *stats);
+
 /* write_color (main.rs:280-299): NaN→0, sqrt(c/spp), clamp [0,0.999], *255.999, floor. */
 void rt_write_color(const double rgb_sum[3], int32_t spp, uint8_t out_rgb[3]);
 /* Device form over n_pixels sums → n_pixels*3 bytes, on hip_stream. */

@@ -62,6 +62,8 @@ const char *rtb_last_error(void);
 int rtb_abi_sizes(uint32_t *out, uint32_t n);
 /* The same for the rt_radiance* structures: {rt_radiance_ray, rt_radiance_params}; returns 2. */
 int rtb_radiance_abi_sizes(uint32_t *out, uint32_t n);
+/* The same for the rt_features* record: {rt_feature}; returns 1. */
+int rtb_features_abi_sizes(uint32_t *out, uint32_t n);
 
 #ifdef __cplusplus
 }

@@ -190,6 +190,17 @@ RT_RADIANCE_MAX_ITEMS = 1 << 58
 # The rt_radiance* structures, in the order of rtb_radiance_abi_sizes (ABI_STRUCTS below keeps its own list as it was).
 RADIANCE_ABI_STRUCTS = [rt_radiance_ray, rt_radiance_params]
 
+
+
+class rt_feature(C.Structure):
+    _fields_ = [("albedo", d3), ("normal", d3), ("depth", C.c_double), ("hits", C.c_double)]
+
+
+# numpy twin of rt_feature (arrays of it come back from rt_features as they are)
+FEATURE_DTYPE = np.dtype([("albedo", "<f8", (3,)), ("normal", "<f8", (3,)), ("depth", "<f8"), ("hits", "<f8")])
+# The rt_features* record, in the order of rtb_features_abi_sizes.
+FEATURES_ABI_STRUCTS = [rt_feature]
+
 ABI_STRUCTS = [rt_bvh_node, rt_sphere, rt_moving_sphere, rt_rect, rt_box, rt_triangle, rt_ring, rt_medium, rt_xform,
                rt_list, rt_material, rt_texture, rt_image, rt_perlin, rt_scene_desc, rt_camera, rt_params, rt_stats,
                rt_query_ray, rt_hit]
@@ -202,9 +213,10 @@ ABI_SYMBOLS = [
     "rt_scene_create", "rt_scene_destroy", "rt_render", "rt_render_device", "rt_render_wait", "rt_write_color",
     "rt_tonemap_device", "rt_last_error", "rt_abi_version", "rt_scene_set_create", "rt_scene_set_destroy", "rt_render_multi",
     "rt_intersect", "rt_intersect_device", "rt_radiance", "rt_radiance_device",
+    "rt_features", "rt_features_device",
     "rtb_scene_build", "rtb_scene_free", "rtb_scene_desc", "rtb_scene_default_view", "rtb_camera_new",
     "rtb_shuffled_rows", "rtb_bvh_build", "rtb_fill_image", "rtb_write_ppm", "rtb_write_jpeg", "rtb_image_load",
-    "rtb_last_error", "rtb_abi_sizes", "rtb_radiance_abi_sizes",
+    "rtb_last_error", "rtb_abi_sizes", "rtb_radiance_abi_sizes", "rtb_features_abi_sizes",
     "rt_debug_math_device", "rt_debug_rng_device", "rt_debug_scene_info", "rt_debug_trace_variant", "rt_debug_set_tuning", "rt_debug_set_engine", "rt_debug_census", "rt_debug_pass_timing", "rt_debug_traffic_probe", "rt_debug_valu_probe", "rt_debug_set_partial_ring", "rt_debug_f32_slabs",
 ]
 
@@ -240,6 +252,8 @@ def lib():
     L.rt_intersect_device.argtypes = [vp, vp, u64, u32, vp, vp, P(rt_stats)]
     L.rt_radiance.argtypes = [vp, vp, u64, P(rt_radiance_params), vp, P(rt_stats)]
     L.rt_radiance_device.argtypes = [vp, vp, u64, P(rt_radiance_params), vp, vp, P(rt_stats)]
+    L.rt_features.argtypes = [vp, P(rt_camera), P(rt_params), vp, P(rt_stats)]
+    L.rt_features_device.argtypes = [vp, P(rt_camera), P(rt_params), vp, vp, P(rt_stats)]
     L.rtb_scene_build.argtypes = [C.c_char_p, u64, C.c_char_p, i32, P(vp)]
     L.rtb_scene_free.argtypes = [vp]
     L.rtb_scene_free.restype = None
@@ -256,6 +270,7 @@ def lib():
     L.rtb_last_error.restype = C.c_char_p
     L.rtb_abi_sizes.argtypes = [P(u32), u32]
     L.rtb_radiance_abi_sizes.argtypes = [P(u32), u32]
+    L.rtb_features_abi_sizes.argtypes = [P(u32), u32]
     L.rt_debug_math_device.argtypes = [C.c_int, P(dbl), P(dbl), P(dbl), u64]
     L.rt_debug_rng_device.argtypes = [u64, C.c_int, dbl, dbl, u64, P(u64), u64]
     L.rt_debug_scene_info.argtypes = [vp, P(u32), P(i32)]

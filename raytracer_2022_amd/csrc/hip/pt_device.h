@@ -244,6 +244,21 @@ struct QueryArgs {
 hipError_t launch_query(const SceneDev &scene, const QueryArgs &args, uint32_t stack_need, bool counters, bool any_hit,
                         hipStream_t stream);
 
+// ---- first-hit feature buffers (pt_features.hip, rt_features*) ----------------------
+struct FeatureArgs {
+    rt_camera cam;
+    uint32_t width, height, spp, n_rows;
+    double background[3];
+    double t_min;
+    uint64_t seed;
+    uint64_t n_pixels;                 // n_rows * width
+    const uint32_t *row_ids;           // device
+    rt_feature *out;                   // device, 16-byte aligned: n_pixels records in row_ids order
+    unsigned long long *counter;       // pixels handed out so far (zeroed before launch)
+    StatsDev *stats;                   // counter instances only
+};
+hipError_t launch_features(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, hipStream_t stream);
+
 // Launchers (pt_kernel.hip). `stack_need` = entries the scene needs (host-computed).
 hipError_t launch_render(const SceneDev &scene, const RenderArgs &args, uint32_t stack_need, bool counters,
                          int n_blocks_hint, hipStream_t stream);

@@ -1,0 +1,230 @@
+// pt_features.hip — first-hit feature buffers of a render's view (rt_features*, include/rt2022.h).
+//
+// For every pixel of the row list and every sample, the camera ray the render aims (the fresh-path code of wf_shade: the
+// same key, sub-pixel jitter, lens sample and shutter time) and `world.hit(r, t_min, f64::MAX)` on it with the SAME RNG
+// stream continuing into the hit; then the winner's albedo, normal and depth, summed per pixel in sample order. No bounce,
+// no light sampling: the megakernel's traversal (pt_traverse.hpp) on its own, like the query kernel. What is this kernel's own:
+//   - persistent grid, wave64, the work item is ONE PIXEL: a lane runs its pixel's samples in order and then takes the
+//     next pixel from a global counter, one atomic per wave for all the lanes that refill together;
+//   - the lane owns its pixel's 64-byte record: each sample is added into it as four 16-byte load / add / store pieces,
+//     the first sample stores (0 + f_0), so there are no atomics, no memset pass, and the order is the sample order;
+//   - the world-frame ray is not kept in registers: the few steps that need it — leaving a mover, the winner's record —
+//     aim it again from (row, px, sample), which is cheap beside a traversal (q_world's trick, pt_query.hip);
+//   - pt_query's scheduler tuning, stack-depth dispatch and LDS node prefix, as they are (nobody has measured others here).
+// One lane per pixel means a few-pixel x huge-spp job balances poorly; the intended use is a whole frame at modest spp.
+// All arithmetic is f64 through rt_math.h with -ffp-contract=off, so every sum is the CPU oracle's composition bit for bit.
+#include "pt_traverse.hpp"
+
+namespace rt2022 {
+
+namespace {
+
+constexpr uint32_t kFHasPixel = 1u;    // lane flag: the lane carries a pixel (a sample of it is in flight)
+
+struct FLane : TravLane {
+    uint32_t row, px;      // the pixel: entry of the row list, column
+    uint32_t smp;          // the sample in flight
+};
+
+// The camera ray of (row, px, sample) and the RNG behind it, as wf_shade's fresh-path code aims it (main.rs:144-149).
+RT_DEV Ray f_camera(const FeatureArgs &a, uint32_t row, uint32_t px, uint32_t smp, Rng &rng) {
+    const uint32_t g = a.row_ids[row];
+    const uint32_t frame = g / a.height, py = g - frame * a.height;
+    rng = Rng(rtm::path_key(a.seed, frame, (uint64_t)py * a.width + px, smp));
+    const double rand_u = rng.gen_f64();
+    const double rand_v = rng.gen_f64();
+    const double u = ((double)px + rand_u) / (double)(a.width - 1);
+    const double v = ((double)py + rand_v) / (double)(a.height - 1);
+    return get_ray(a.cam, u, v, rng);
+}
+RT_DEV Ray f_world(const FeatureArgs &a, const FLane &L) {
+    Rng unused;
+    return f_camera(a, L.row, L.px, L.smp, unused);
+}
+
+// scatter's attenuation where the material scatters, emitted where it does not (material/mod.rs).
+RT_DEV Vec3 f_albedo(const SceneDev &s, const HitRec &rec) {
+    const rt_material &m = s.materials[rec.mat & kMatIndexMask];
+    const uint32_t kind = m.kind;
+    if (kind == RT_MAT_METAL) return ld3(m.albedo);
+    if (kind == RT_MAT_DIELECTRIC) return Vec3(1.0, 1.0, 1.0);
+    if (kind == RT_MAT_DIFFUSE_LIGHT && !rec.front_face) return Vec3(0.0, 0.0, 0.0);
+    return texture_value(s, m.tex, rec.u, rec.v, rec.p);
+}
+
+// The finished sample's features, added into the lane's own record: {a.x, a.y} {a.z, n.x} {n.y, n.z} {depth, hits}.
+RT_DEV void f_accumulate(const SceneDev &s, const FeatureArgs &a, const FLane &L) {
+    Vec3 alb = ld3(a.background), n(0.0, 0.0, 0.0);
+    double depth = 0.0, hits = 0.0;
+    if (L.flags & kFound) {
+        HitRec rec;
+        winner_record(s, f_world(a, L), L.win, rec, true);
+        alb = f_albedo(s, rec);
+        n = rec.normal; depth = rec.t; hits = 1.0;
+    }
+    double2 *o = reinterpret_cast<double2 *>(a.out + ((uint64_t)L.row * a.width + L.px));
+    double2 s0 = make_double2(0.0, 0.0), s1 = s0, s2 = s0, s3 = s0;
+    if (L.smp > 0) { s0 = o[0]; s1 = o[1]; s2 = o[2]; s3 = o[3]; }
+    o[0] = make_double2(s0.x + alb.x, s0.y + alb.y);
+    o[1] = make_double2(s1.x + alb.z, s1.y + n.x);
+    o[2] = make_double2(s2.x + n.y, s2.y + n.z);
+    o[3] = make_double2(s3.x + depth, s3.y + hits);
+}
+
+// Aim sample L.smp of the lane's pixel and start its traversal at the root (`have` false: nothing left, the lane idles).
+RT_DEV void f_aim(const SceneDev &s, const FeatureArgs &a, FLane &L, bool have) {
+    Rng rng;
+    Ray r(Vec3(0.0, 0.0, 0.0), Vec3(0.0, 0.0, 0.0), 0.0);
+    if (have) r = f_camera(a, L.row, L.px, L.smp, rng);
+    L.tm = r.tm;
+    trav_set_cur(L, XRay{r.orig, r.dir});
+    L.t_min = a.t_min;
+    L.t_lo = a.t_min;
+    L.closest = rtm::F64_MAX;
+    L.sub_closest = 0.0;
+    L.med_t1 = 0.0;
+    L.med_ref = 0;
+    L.rng = rng;                                           // (its draws so far are the camera's: the hit's come on top)
+    L.win.t = 0.0; L.win.leaf = 0; L.win.face = 0;
+    L.ctx.c0 = L.ctx.c1 = L.ctx.c2 = L.ctx.c3 = 0; L.ctx.n = 0;
+    L.win.chain = L.ctx;
+    L.sp = 0;
+    L.flags = have ? kFHasPixel : 0u;
+    L.top = have ? s.root : REF_EMPTY;
+    L.op = have ? classify(L.top) : (uint32_t)OP_IDLE;
+}
+
+// Done: add the finished sample into the pixel's record, then aim the pixel's next sample — or take the next pixel (one
+// atomic per wave for every lane that refills).
+template <bool STATS>
+RT_DEV void f_done(const SceneDev &s, const FeatureArgs &a, FLane &L, unsigned lane, Counters<STATS> &cnt) {
+    bool refill = true;
+    if (L.flags & kFHasPixel) {
+        f_accumulate(s, a, L);
+        cnt.draws(L.rng.draws);
+        L.smp++;
+        refill = L.smp >= a.spp;
+    }
+    const unsigned long long m = __ballot(refill);
+    bool have = true;
+    if (refill) {
+        const int leader = __ffsll((long long)m) - 1;
+        unsigned long long base = 0;
+        if ((int)lane == leader) base = atomicAdd(a.counter, (unsigned long long)__popcll(m));
+        base = __shfl(base, leader);
+        const unsigned long long i = base + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
+        have = i < a.n_pixels;
+        const unsigned long long ii = have ? i : 0ull;
+        L.row = (uint32_t)(ii / a.width);
+        L.px = (uint32_t)(ii - (unsigned long long)L.row * a.width);
+        L.smp = 0;
+    }
+    f_aim(s, a, L, have);
+}
+
+} // namespace
+
+// pt_query's tuning constants (pt_query.hip: measured there on caller rays); camera rays of neighbouring pixels are more
+// coherent than those, and nothing has been measured here that would justify other values.
+constexpr int kFeatNodeQuorum = 8;
+constexpr uint32_t kFeatVoteWeights = 0x24444442u;
+
+// Waves per SIMD the instances are built for. The 1024-thread LDS-prefix instance has no choice: one workgroup is 16 waves
+// per CU = 4 per SIMD (128 VGPRs; its done arm spills into scratch: profiles/features_kernel_resources.txt). The 256-thread
+// instances take 3 (168 VGPRs) where pt_query takes 4 — measured at 4 / 3 / 2 on the 800x800 default views at 4 spp: C5's
+// mesh 169 / 333 / 291 Mrays/s, 1e5 spheres 143 / 299 / 278 (profiles/features_ab_occupancy.log).
+constexpr int feat_waves(int stack, int wg) { return wg > 256 ? 4 : stack > 32 ? 2 : 3; }
+// STACK: traversal stack entries; WG: threads per workgroup; CACHE: node records kept in LDS (0: none); STATS: counter instance.
+template <int STACK, int WG, int CACHE, bool STATS>
+__global__ void __launch_bounds__(WG, feat_waves(STACK, WG)) pt_features(const SceneDev s, const FeatureArgs a) {
+    __shared__ uint32_t stack_lds[STACK * WG];
+    __shared__ double node_lds[CACHE > 0 ? CACHE * kTravNodeDoubles : 1];
+    const uint32_t n_cached = CACHE > 0 ? (s.n_nodes < (uint32_t)CACHE ? s.n_nodes : (uint32_t)CACHE) : 0u;
+    if (CACHE > 0) {                                       // prefix copy: the top levels of the BVHs (breadth-first numbering)
+        for (uint32_t i = threadIdx.x; i < n_cached; i += WG) {
+            const rt_bvh_node &q = s.nodes[i];
+            double *d = node_lds + (size_t)i * kTravNodeDoubles;
+            d[0] = q.bmin[0]; d[1] = q.bmin[1]; d[2] = q.bmin[2];
+            d[3] = q.bmax[0]; d[4] = q.bmax[1]; d[5] = q.bmax[2];
+            d[6] = rtm::u2d((uint64_t)q.left | ((uint64_t)q.right << 32));
+        }
+        __syncthreads();
+    }
+    TravStack<STACK, WG> st{stack_lds + threadIdx.x};
+    const unsigned lane = threadIdx.x & 63u;
+    Counters<STATS> cnt;
+
+    FLane L;
+    L.tm = 0.0;
+    trav_set_cur(L, XRay{Vec3(0.0, 0.0, 0.0), Vec3(0.0, 0.0, 0.0)});
+    L.t_min = L.t_lo = L.closest = L.sub_closest = L.med_t1 = 0.0;
+    L.med_ref = 0;
+    L.ctx.c0 = L.ctx.c1 = L.ctx.c2 = L.ctx.c3 = 0; L.ctx.n = 0;
+    L.win.t = 0.0; L.win.leaf = 0; L.win.face = 0; L.win.chain = L.ctx;
+    L.row = 0; L.px = 0; L.smp = 0; L.sp = 0; L.top = REF_EMPTY; L.op = OP_SHADE; L.flags = 0;
+
+    const auto world = [&] { const Ray w = f_world(a, L); return XRay{w.orig, w.dir}; };
+    for (;;) {
+        // Fast path: keep stepping nodes while enough lanes want to.
+        for (;;) {
+            const bool isn = L.op == OP_NODE;
+            if (__popcll(__ballot(isn)) < kFeatNodeQuorum) break;
+            if (isn) trav_node<false, STACK, WG, CACHE, STATS>(s, node_lds, n_cached, L, st, cnt);
+        }
+        // Vote: the label with the largest lanes x weight (ties -> lowest id).
+        int best = -1, best_n = 0;
+#pragma unroll
+        for (int o = 0; o < (int)OP_COUNT; o++) {
+            const int n = __popcll(__ballot(L.op == (uint32_t)o)) * (int)((kFeatVoteWeights >> (4 * o)) & 0xFu);
+            if (n > best_n) { best_n = n; best = o; }
+        }
+        if (best < 0) break;                               // every lane idle: no pixels left
+        if (L.op == (uint32_t)best) {
+            switch (best) {
+                case OP_NODE: trav_node<false, STACK, WG, CACHE, STATS>(s, node_lds, n_cached, L, st, cnt); break;
+                case OP_SPHERE: trav_sphere<false>(s, L, st, cnt); break;
+                case OP_RECT: trav_rect<false>(s, L, st, cnt); break;
+                case OP_BOX: trav_box<false>(s, L, st, cnt); break;
+                case OP_MEDIUM: trav_medium<false>(s, L, st, cnt); break;
+                case OP_MISC: trav_misc<false>(s, L, st, cnt); break;
+                case OP_CTX: trav_ctx<false>(s, L, st, cnt, world); break;
+                default: f_done<STATS>(s, a, L, lane, cnt); break;
+            }
+        }
+    }
+    if (STATS) cnt.flush_wave(a.stats);
+}
+
+namespace {
+
+template <int STACK, int WG, int CACHE, bool STATS>
+hipError_t launch_one(const SceneDev &scene, const FeatureArgs &args, hipStream_t stream) {
+    int per_cu = 0, dev = 0, cus = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pt_features<STACK, WG, CACHE, STATS>, WG, 0);
+    if (e != hipSuccess) return e;
+    if (per_cu < 1) per_cu = 1;
+    const uint64_t want = (args.n_pixels + WG - 1) / WG;
+    uint64_t blocks = (uint64_t)per_cu * (uint64_t)(cus > 0 ? cus : 1);
+    if (blocks > want) blocks = want ? want : 1;
+    hipLaunchKernelGGL((pt_features<STACK, WG, CACHE, STATS>), dim3((unsigned)blocks), dim3(WG), 0, stream, scene, args);
+    return hipGetLastError();
+}
+template <int STACK, int WG, int CACHE>
+hipError_t launch_flags(const SceneDev &scene, const FeatureArgs &args, bool counters, hipStream_t stream) {
+    return counters ? launch_one<STACK, WG, CACHE, true>(scene, args, stream) : launch_one<STACK, WG, CACHE, false>(scene, args, stream);
+}
+
+} // namespace
+
+hipError_t launch_features(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, hipStream_t stream) {
+    if (args.n_pixels == 0 || args.spp == 0) return hipSuccess;
+    if (stack_need > (uint32_t)kStackLarge) return hipErrorInvalidValue;
+    if (stack_need <= (uint32_t)kStackTiny) return launch_flags<kStackTiny, kCacheBlock, kNodeCache>(scene, args, counters, stream);
+    if (stack_need <= (uint32_t)kStackSmall) return launch_flags<kStackSmall, kBlock, 0>(scene, args, counters, stream);
+    if (stack_need <= (uint32_t)kStackMid) return launch_flags<kStackMid, kBlock, 0>(scene, args, counters, stream);
+    return launch_flags<kStackLarge, kBlock, 0>(scene, args, counters, stream);
+}
+
+} // namespace rt2022

@@ -315,6 +315,12 @@ struct QueryScratch {
     Event ev0{hipEventDefault}, ev1{hipEventDefault};
 };
 
+// The same for the feature calls (rt_features*) on one (scene, stream), plus the words of the device-resident row check.
+struct FeatureScratch : QueryScratch {
+    DeviceBuf<uint32_t> rows_max{1};  // device word: largest row id of the call being checked
+    PinnedBuf<uint32_t> h_rows_max{1};
+};
+
 } // namespace
 
 struct rt_scene {
@@ -339,6 +345,7 @@ struct rt_scene {
     std::map<hipStream_t, Workspace> ws;
     std::mutex qmu;                   // guards `qs`
     std::map<hipStream_t, std::unique_ptr<QueryScratch>> qs;
+    std::map<hipStream_t, std::unique_ptr<FeatureScratch>> fs;      // (under qmu too)
 };
 
 namespace {
@@ -688,6 +695,85 @@ void run_query(rt_scene *sc, const rt_query_ray *d_rays, uint64_t n_rays, uint32
     StatsDev h;
     rt_stats out = read_stats(q.ev0, q.ev1, counters ? q.stats.p : nullptr, h);
     out.rays = n_rays;                             // (a query counts no paths, rays or light tests of its own)
+    *stats = out;
+}
+
+FeatureScratch &feature_scratch_for(rt_scene *sc, hipStream_t stream) {
+    std::lock_guard<std::mutex> lock(sc->qmu);
+    std::unique_ptr<FeatureScratch> &q = sc->fs[stream];
+    if (!q) q.reset(new FeatureScratch());                 // (stored once it is complete, or not at all)
+    return *q;
+}
+
+// The arguments of rt_features* (host side only; the scene comes last so that a bad argument is reported as such whatever
+// the scene). `device`: rows and output are rt_features_device's — the rows are range-checked on the device later.
+void check_features(const rt_scene *scene, const rt_camera *cam, const rt_params *p, const void *out, bool device, const char *who) {
+    const std::string w(who);
+    RT_REQUIRE(p, RT_ERR_INVALID, w + ": null params");
+    RT_REQUIRE(cam, RT_ERR_INVALID, w + ": null camera");
+    RT_REQUIRE(!(p->flags & ~RT_FLAG_COUNTERS), RT_ERR_INVALID, w + ": flag bits other than RT_FLAG_COUNTERS");
+    RT_REQUIRE(p->width > 0 && p->height > 0 && p->n_frames > 0, RT_ERR_INVALID, w + ": empty image (width, height or n_frames is 0)");
+    RT_REQUIRE(cam->time0 < cam->time1, RT_ERR_INVALID, w + ": camera time0 >= time1 (gen_range panics in the reference, camera.rs:71)");
+    RT_REQUIRE((uint64_t)p->height * p->n_frames <= 0xFFFFFFFFull, RT_ERR_INVALID, w + ": height * n_frames overflows a row id");
+    const bool need_rows = p->n_rows > 0 && p->spp > 0;
+    RT_REQUIRE(p->n_rows == 0 || out, RT_ERR_INVALID, w + ": null output");
+    RT_REQUIRE(!need_rows || p->row_ids, RT_ERR_INVALID, w + ": null row_ids");
+    RT_REQUIRE((uint64_t)p->n_rows * p->width <= (1ull << 40), RT_ERR_INVALID, w + ": n_rows * width too large");
+    if (device) {
+        RT_REQUIRE(p->n_rows == 0 || !((uintptr_t)out & 15u), RT_ERR_INVALID, w + ": the output must be 16-byte aligned");
+        RT_REQUIRE(!need_rows || !((uintptr_t)p->row_ids & 3u), RT_ERR_INVALID, w + ": row_ids must be 4-byte aligned");
+    } else if (need_rows) {
+        for (uint32_t i = 0; i < p->n_rows; i++)
+            RT_REQUIRE(p->row_ids[i] < (uint64_t)p->height * p->n_frames, RT_ERR_INVALID, w + ": row id out of range");
+    }
+    RT_REQUIRE(scene, RT_ERR_INVALID, w + ": null scene");
+}
+
+// Enqueue one feature call on `stream` (the scene's device is current, the arguments checked); with stats, wait for it and
+// fill them. `check_rows`: the row ids came from the caller's HBM — range-check them first (one synchronisation of the stream).
+void run_features(rt_scene *sc, const rt_camera *cam, const rt_params *p, const uint32_t *d_rows, rt_feature *d_out,
+                  hipStream_t stream, rt_stats *stats, bool check_rows, const char *who) {
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    const uint64_t n_pixels = (uint64_t)p->n_rows * p->width;
+    if (n_pixels == 0) return;
+    if (p->spp == 0) {                                     // no sample: zeros, no kernel
+        RT_HIP(hipMemsetAsync(d_out, 0, n_pixels * sizeof(rt_feature), stream));
+        if (stats) RT_HIP(hipStreamSynchronize(stream));
+        return;
+    }
+    FeatureScratch &q = feature_scratch_for(sc, stream);
+    std::lock_guard<std::mutex> lock(q.mu);
+    if (check_rows) {
+        RT_HIP(hipMemsetAsync(q.rows_max, 0, sizeof(uint32_t), stream));
+        const uint32_t blocks = (p->n_rows + 255u) / 256u;
+        hipLaunchKernelGGL(row_ids_max_kernel, dim3(blocks > 64 ? 64 : blocks), dim3(256), 0, stream, d_rows, p->n_rows, q.rows_max.p);
+        RT_HIP(hipGetLastError());
+        RT_HIP(hipMemcpyAsync(q.h_rows_max, q.rows_max, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        RT_HIP(hipStreamSynchronize(stream));
+        RT_REQUIRE((uint64_t)*q.h_rows_max.p < (uint64_t)p->height * p->n_frames, RT_ERR_INVALID, std::string(who) + ": row id out of range");
+    }
+    const bool counters = stats && (p->flags & RT_FLAG_COUNTERS);
+    FeatureArgs a{};
+    a.cam = *cam;
+    a.width = p->width; a.height = p->height; a.spp = p->spp; a.n_rows = p->n_rows;
+    std::memcpy(a.background, p->background, sizeof a.background);
+    a.t_min = p->t_min;
+    a.seed = p->seed;
+    a.n_pixels = n_pixels;
+    a.row_ids = d_rows;
+    a.out = d_out;
+    a.counter = q.counter;
+    a.stats = counters ? q.stats.p : nullptr;
+    RT_HIP(hipMemsetAsync(q.counter, 0, sizeof(unsigned long long), stream));
+    if (counters) RT_HIP(hipMemsetAsync(q.stats, 0, sizeof(StatsDev), stream));
+    if (stats) RT_HIP(hipEventRecord(q.ev0, stream));
+    RT_HIP(launch_features(sc->dev, a, sc->stack_need, counters, stream));
+    if (!stats) return;
+    RT_HIP(hipEventRecord(q.ev1, stream));
+    RT_HIP(hipStreamSynchronize(stream));
+    StatsDev h;
+    rt_stats out = read_stats(q.ev0, q.ev1, counters ? q.stats.p : nullptr, h);
+    out.paths = out.rays = n_pixels * p->spp;              // (one camera path, one world.hit per sample; the kernel counts neither)
     *stats = out;
 }
 
@@ -1057,6 +1143,45 @@ int rt_intersect_device(rt_scene *scene, const rt_query_ray *d_rays, uint64_t n_
         }
         DeviceGuard guard(scene->device);
         run_query(scene, d_rays, n_rays, flags, d_out_hits, (hipStream_t)hip_stream, stats);
+        return RT_OK;
+    });
+}
+
+int rt_features(rt_scene *scene, const rt_camera *cam, const rt_params *params, rt_feature *out_features, rt_stats *stats) {
+    return guarded([&]() -> int {
+        check_features(scene, cam, params, out_features, false, "rt_features");
+        const uint64_t n_pixels = (uint64_t)params->n_rows * params->width;
+        if (n_pixels == 0) {
+            if (stats) std::memset(stats, 0, sizeof *stats);
+            return RT_OK;
+        }
+        if (params->spp == 0) {                                // zeros, and nothing for the device to do
+            if (stats) std::memset(stats, 0, sizeof *stats);
+            std::memset(out_features, 0, n_pixels * sizeof(rt_feature));
+            return RT_OK;
+        }
+        DeviceGuard guard(scene->device);
+        DeviceBuf<uint32_t> d_rows(params->n_rows);            // (after the guard: freed with the scene's device current)
+        DeviceBuf<rt_feature> d_out(n_pixels);
+        RT_HIP(hipMemcpy(d_rows, params->row_ids, params->n_rows * sizeof(uint32_t), hipMemcpyHostToDevice));
+        // Poison the output so an unwritten record cannot pass for a result.
+        RT_HIP(hipMemset(d_out, 0xFF, n_pixels * sizeof(rt_feature)));
+        run_features(scene, cam, params, d_rows, d_out, nullptr, stats, false, "rt_features");
+        RT_HIP(hipMemcpy(out_features, d_out, n_pixels * sizeof(rt_feature), hipMemcpyDeviceToHost));
+        return RT_OK;
+    });
+}
+
+int rt_features_device(rt_scene *scene, const rt_camera *cam, const rt_params *params, rt_feature *d_out_features, void *hip_stream,
+                       rt_stats *stats) {
+    return guarded([&]() -> int {
+        check_features(scene, cam, params, d_out_features, true, "rt_features_device");
+        if ((uint64_t)params->n_rows * params->width == 0) {
+            if (stats) std::memset(stats, 0, sizeof *stats);
+            return RT_OK;
+        }
+        DeviceGuard guard(scene->device);
+        run_features(scene, cam, params, params->row_ids, d_out_features, (hipStream_t)hip_stream, stats, true, "rt_features_device");
         return RT_OK;
     });
 }

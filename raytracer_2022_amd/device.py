@@ -167,6 +167,33 @@ class DeviceScene:
         F.check(F.lib().rt_radiance_device(self._h, C.c_void_p(d_rays_ptr), n, C.byref(params), C.c_void_p(d_out_ptr),
                                            C.c_void_p(stream_ptr or 0), C.byref(stats) if stats is not None else None))
 
+    def features(self, cam, params, row_ids, want_stats=False):
+        """rt_features with host buffers: the first-hit guide buffers of the camera rays a render of (cam, params, row_ids)
+        shoots → array of FEATURE_DTYPE records of shape (n_rows, width) — fields albedo (3), normal (3), depth, hits: sums
+        over the spp samples, not divided by spp [, rt_stats]. params.max_depth, spp_chunk and progress_cb are ignored."""
+        rows = np.ascontiguousarray(row_ids, dtype=np.uint32)
+        p = F.rt_params.from_buffer_copy(params)
+        p.n_rows = len(rows)
+        p.row_ids = rows.ctypes.data
+        p.progress_cb = None
+        p.flags = F.RT_FLAG_COUNTERS if want_stats else 0
+        out = np.zeros((len(rows), p.width), dtype=F.FEATURE_DTYPE)
+        st = F.rt_stats()
+        F.check(F.lib().rt_features(self._h, C.byref(cam), C.byref(p), out.ctypes.data if out.size else None, C.byref(st)))
+        return (out, st) if want_stats else out
+
+    def features_device(self, cam, params, d_row_ids_ptr, n_rows, d_out_ptr, stream_ptr=None, stats=None):
+        """rt_features_device: device pointers in (n_rows row ids, room for n_rows * width rt_feature records, 16-byte
+        aligned), enqueued on `stream_ptr` (hipStream_t as int). stats=None returns once the kernel is enqueued; an rt_stats
+        makes the call synchronise the stream and fill it, counters included."""
+        p = F.rt_params.from_buffer_copy(params)
+        p.n_rows = n_rows
+        p.row_ids = d_row_ids_ptr
+        p.progress_cb = None
+        p.flags = F.RT_FLAG_COUNTERS if stats is not None else 0
+        F.check(F.lib().rt_features_device(self._h, C.byref(cam), C.byref(p), C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr or 0),
+                                           C.byref(stats) if stats is not None else None))
+
     def close(self):
         if self._h:
             F.lib().rt_scene_destroy(self._h)
