@@ -3,14 +3,18 @@
 // For every pixel of the row list and every sample, the camera ray the render aims (the fresh-path code of wf_shade: the
 // same key, sub-pixel jitter, lens sample and shutter time) and `world.hit(r, t_min, f64::MAX)` on it with the SAME RNG
 // stream continuing into the hit; then the winner's albedo, normal and depth, summed per pixel in sample order. No bounce,
-// no light sampling: the megakernel's traversal (pt_traverse.hpp) on its own, like the query kernel. What is this kernel's own:
-//   - persistent grid, wave64, the work item is ONE PIXEL: a lane runs its pixel's samples in order and then takes the
-//     next pixel from a global counter, one atomic per wave for all the lanes that refill together;
+// no light sampling: the megakernel's traversal (pt_traverse.hpp) on its own, in the query kernel's shell (pt_traverse.hpp
+// too: persistent wave64 grid, one-atomic-per-wave claim, start of a ray, scheduler tuning, instance by stack need —
+// pt_query.hip describes it). What is this kernel's own:
+//   - the work item is ONE PIXEL: a lane runs its pixel's samples in order and only then claims the next pixel;
 //   - the lane owns its pixel's 64-byte record: each sample is added into it as four 16-byte load / add / store pieces,
 //     the first sample stores (0 + f_0), so there are no atomics, no memset pass, and the order is the sample order;
 //   - the world-frame ray is not kept in registers: the few steps that need it — leaving a mover, the winner's record —
 //     aim it again from (row, px, sample), which is cheap beside a traversal (q_world's trick, pt_query.hip);
-//   - pt_query's scheduler tuning, stack-depth dispatch and LDS node prefix, as they are (nobody has measured others here).
+//   - the waves per SIMD its instances are built for (feat_waves below);
+//   - the scheduler loop, written out here as in every kernel (pt_traverse.hpp says why) — and with it the LDS node
+//     prefix and the lane's state before the loop, pt_query's line for line: through trav_cache_nodes / trav_lane_clear
+//     the 1024-thread instance spills differently, and nobody has measured that.
 // One lane per pixel means a few-pixel x huge-spp job balances poorly; the intended use is a whole frame at modest spp.
 // All arithmetic is f64 through rt_math.h with -ffp-contract=off, so every sum is the CPU oracle's composition bit for bit.
 #include "pt_traverse.hpp"
@@ -76,22 +80,8 @@ RT_DEV void f_aim(const SceneDev &s, const FeatureArgs &a, FLane &L, bool have) 
     Rng rng;
     Ray r(Vec3(0.0, 0.0, 0.0), Vec3(0.0, 0.0, 0.0), 0.0);
     if (have) r = f_camera(a, L.row, L.px, L.smp, rng);
-    L.tm = r.tm;
-    trav_set_cur(L, XRay{r.orig, r.dir});
-    L.t_min = a.t_min;
-    L.t_lo = a.t_min;
-    L.closest = rtm::F64_MAX;
-    L.sub_closest = 0.0;
-    L.med_t1 = 0.0;
-    L.med_ref = 0;
-    L.rng = rng;                                           // (its draws so far are the camera's: the hit's come on top)
-    L.win.t = 0.0; L.win.leaf = 0; L.win.face = 0;
-    L.ctx.c0 = L.ctx.c1 = L.ctx.c2 = L.ctx.c3 = 0; L.ctx.n = 0;
-    L.win.chain = L.ctx;
-    L.sp = 0;
-    L.flags = have ? kFHasPixel : 0u;
-    L.top = have ? s.root : REF_EMPTY;
-    L.op = have ? classify(L.top) : (uint32_t)OP_IDLE;
+    trav_begin(s, L, have, XRay{r.orig, r.dir}, r.tm, a.t_min, rtm::F64_MAX, rng);   // (rng's draws so far are the camera's: the hit's come on top)
+    if (have) L.flags = kFHasPixel;
 }
 
 // Done: add the finished sample into the pixel's record, then aim the pixel's next sample — or take the next pixel (one
@@ -108,11 +98,7 @@ RT_DEV void f_done(const SceneDev &s, const FeatureArgs &a, FLane &L, unsigned l
     const unsigned long long m = __ballot(refill);
     bool have = true;
     if (refill) {
-        const int leader = __ffsll((long long)m) - 1;
-        unsigned long long base = 0;
-        if ((int)lane == leader) base = atomicAdd(a.counter, (unsigned long long)__popcll(m));
-        base = __shfl(base, leader);
-        const unsigned long long i = base + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
+        const unsigned long long i = wave_claim(a.counter, m, lane);
         have = i < a.n_pixels;
         const unsigned long long ii = have ? i : 0ull;
         L.row = (uint32_t)(ii / a.width);
@@ -123,11 +109,6 @@ RT_DEV void f_done(const SceneDev &s, const FeatureArgs &a, FLane &L, unsigned l
 }
 
 } // namespace
-
-// pt_query's tuning constants (pt_query.hip: measured there on caller rays); camera rays of neighbouring pixels are more
-// coherent than those, and nothing has been measured here that would justify other values.
-constexpr int kFeatNodeQuorum = 8;
-constexpr uint32_t kFeatVoteWeights = 0x24444442u;
 
 // Waves per SIMD the instances are built for. The 1024-thread LDS-prefix instance has no choice: one workgroup is 16 waves
 // per CU = 4 per SIMD (128 VGPRs; its done arm spills into scratch: profiles/features_kernel_resources.txt). The 256-thread
@@ -168,14 +149,14 @@ __global__ void __launch_bounds__(WG, feat_waves(STACK, WG)) pt_features(const S
         // Fast path: keep stepping nodes while enough lanes want to.
         for (;;) {
             const bool isn = L.op == OP_NODE;
-            if (__popcll(__ballot(isn)) < kFeatNodeQuorum) break;
+            if (__popcll(__ballot(isn)) < kQueryNodeQuorum) break;
             if (isn) trav_node<false, STACK, WG, CACHE, STATS>(s, node_lds, n_cached, L, st, cnt);
         }
         // Vote: the label with the largest lanes x weight (ties -> lowest id).
         int best = -1, best_n = 0;
 #pragma unroll
         for (int o = 0; o < (int)OP_COUNT; o++) {
-            const int n = __popcll(__ballot(L.op == (uint32_t)o)) * (int)((kFeatVoteWeights >> (4 * o)) & 0xFu);
+            const int n = __popcll(__ballot(L.op == (uint32_t)o)) * (int)((kQueryVoteWeights >> (4 * o)) & 0xFu);
             if (n > best_n) { best_n = n; best = o; }
         }
         if (best < 0) break;                               // every lane idle: no pixels left
@@ -195,36 +176,14 @@ __global__ void __launch_bounds__(WG, feat_waves(STACK, WG)) pt_features(const S
     if (STATS) cnt.flush_wave(a.stats);
 }
 
-namespace {
-
-template <int STACK, int WG, int CACHE, bool STATS>
-hipError_t launch_one(const SceneDev &scene, const FeatureArgs &args, hipStream_t stream) {
-    int per_cu = 0, dev = 0, cus = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pt_features<STACK, WG, CACHE, STATS>, WG, 0);
-    if (e != hipSuccess) return e;
-    if (per_cu < 1) per_cu = 1;
-    const uint64_t want = (args.n_pixels + WG - 1) / WG;
-    uint64_t blocks = (uint64_t)per_cu * (uint64_t)(cus > 0 ? cus : 1);
-    if (blocks > want) blocks = want ? want : 1;
-    hipLaunchKernelGGL((pt_features<STACK, WG, CACHE, STATS>), dim3((unsigned)blocks), dim3(WG), 0, stream, scene, args);
-    return hipGetLastError();
-}
-template <int STACK, int WG, int CACHE>
-hipError_t launch_flags(const SceneDev &scene, const FeatureArgs &args, bool counters, hipStream_t stream) {
-    return counters ? launch_one<STACK, WG, CACHE, true>(scene, args, stream) : launch_one<STACK, WG, CACHE, false>(scene, args, stream);
-}
-
-} // namespace
-
 hipError_t launch_features(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, hipStream_t stream) {
     if (args.n_pixels == 0 || args.spp == 0) return hipSuccess;
-    if (stack_need > (uint32_t)kStackLarge) return hipErrorInvalidValue;
-    if (stack_need <= (uint32_t)kStackTiny) return launch_flags<kStackTiny, kCacheBlock, kNodeCache>(scene, args, counters, stream);
-    if (stack_need <= (uint32_t)kStackSmall) return launch_flags<kStackSmall, kBlock, 0>(scene, args, counters, stream);
-    if (stack_need <= (uint32_t)kStackMid) return launch_flags<kStackMid, kBlock, 0>(scene, args, counters, stream);
-    return launch_flags<kStackLarge, kBlock, 0>(scene, args, counters, stream);
+    return trav_dispatch(stack_need, [&](auto shape) {
+        using S = decltype(shape);
+        void (*const kernel)(SceneDev, FeatureArgs) =
+            counters ? pt_features<S::stack, S::wg, S::cache, true> : pt_features<S::stack, S::wg, S::cache, false>;
+        return launch_persistent(kernel, S::wg, args.n_pixels, scene, args, stream);
+    });
 }
 
 } // namespace rt2022

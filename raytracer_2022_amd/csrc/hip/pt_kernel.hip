@@ -148,12 +148,8 @@ RT_DEV void op_shade(const SceneDev &s, const RenderArgs &a, Lane &L, Tape &tape
         }
         unsigned long long m = __ballot(need);
         if (m) {
-            int leader = __ffsll((long long)m) - 1;
-            unsigned long long base = 0;
-            if ((int)lane == leader) base = atomicAdd(a.work_counter, (unsigned long long)__popcll(m));
-            base = __shfl(base, leader);
+            const unsigned long long item = wave_claim(a.work_counter, m, lane);
             if (need) {
-                unsigned long long item = base + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
                 if (item < a.n_items) {
                     L.slot = item / a.n_chunks;
                     L.chunk_id = (uint32_t)(item - L.slot * a.n_chunks);

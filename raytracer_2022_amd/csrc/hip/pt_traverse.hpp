@@ -1,6 +1,11 @@
-// pt_traverse.hpp — the f64 closest-hit traversal of the megakernel (pt_kernel.hip) and the query kernel (pt_query.hip):
-// the lane's traversal state, its LDS stack and the arms of the in-wave voted scheduler. The caller owns the world-frame
-// ray, the done arm and the scheduler loop. (wf_trace, pt_wavefront.hip, has its own tuned copy.)
+// pt_traverse.hpp — the f64 closest-hit traversal of the megakernel (pt_kernel.hip), the query kernel (pt_query.hip) and
+// the feature kernel (pt_features.hip): the lane's traversal state, its LDS stack and the arms of the in-wave voted
+// scheduler. The caller owns the world-frame ray, the done arm and the scheduler loop. (wf_trace, pt_wavefront.hip, has
+// its own tuned copy.) At the end, the shell the two persistent closest-hit kernels share around their loops: the LDS
+// node prefix, the lane's state before the loop and at the start of a ray, the one-atomic-per-wave claim of work (the
+// megakernel's too), their scheduler tuning, and the launch side (occupancy-sized grid, instance by stack need). A helper
+// is used where it leaves the kernel's register allocation as it was (tools/kernel_resources.py): the feature kernel,
+// whose 1024-thread instance spills, keeps the node prefix and the lane's first state written out.
 //
 // The scheduler: every lane carries a label naming its next operation (node step, sphere, rect, box, medium, misc leaf,
 // mover / list, done) and the wave runs the label that weighs most, with all the lanes that wait for it, and a fast path
@@ -248,6 +253,114 @@ RT_DEV void trav_ctx(const SceneDev &s, TravLane &L, TravStack<STACK, WG> &st, C
     } else {
         trav_next<ANY>(L, st);
     }
+}
+
+// ---- the shell of the persistent closest-hit kernels (pt_query, pt_features) --------------------------------------
+
+// Lanes that must want a node step for the wave to keep taking the fast path. 8 rather than the render kernels' 18: measured
+// with the weights below, +8 % on the headline's bounce rays and +9 % on C2's, -3 % on C5's (12: +2 %, +5 %, +-0).
+constexpr int kQueryNodeQuorum = 8;
+// Vote weights, four bits per label from the lowest nibble up (node, sphere, rect, box, medium, misc, ctx, done): the wave
+// runs the label with the largest lanes x weight. Node steps and the refill yield to the leaf arms, like wf_trace's weights:
+// measured against plain counts on the workloads of tools/query_bench.py, +20 % on the headline's bounce rays, +5-10 % on the
+// others; a refill weighted up (done x 2) was 1-20 % slower.
+// (Measured on the query kernel's caller rays. The feature kernel takes both as they are: camera rays of neighbouring
+// pixels are more coherent than those, and nothing has been measured there that would justify other values.)
+constexpr uint32_t kQueryVoteWeights = 0x24444442u;
+
+// The first CACHE node records into LDS, by the whole workgroup (the nodes are numbered breadth-first at upload: a prefix
+// copy is the top levels of the BVHs). Returns how many there are; CACHE 0: none, and nothing is done.
+template <int WG, int CACHE>
+RT_DEV uint32_t trav_cache_nodes(const SceneDev &s, double *node_lds) {
+    const uint32_t n_cached = CACHE > 0 ? (s.n_nodes < (uint32_t)CACHE ? s.n_nodes : (uint32_t)CACHE) : 0u;
+    if (CACHE > 0) {
+        for (uint32_t i = threadIdx.x; i < n_cached; i += WG) {
+            const rt_bvh_node &q = s.nodes[i];
+            double *d = node_lds + (size_t)i * kTravNodeDoubles;
+            d[0] = q.bmin[0]; d[1] = q.bmin[1]; d[2] = q.bmin[2];
+            d[3] = q.bmax[0]; d[4] = q.bmax[1]; d[5] = q.bmax[2];
+            d[6] = rtm::u2d((uint64_t)q.left | ((uint64_t)q.right << 32));
+        }
+        __syncthreads();
+    }
+    return n_cached;
+}
+
+// The lane before the loop: no ray, waiting for the done arm. (The kernel zeroes the fields it adds.)
+RT_DEV void trav_lane_clear(TravLane &L) {
+    L.tm = 0.0;
+    trav_set_cur(L, XRay{Vec3(0.0, 0.0, 0.0), Vec3(0.0, 0.0, 0.0)});
+    L.t_min = L.t_lo = L.closest = L.sub_closest = L.med_t1 = 0.0;
+    L.med_ref = 0;
+    L.ctx.c0 = L.ctx.c1 = L.ctx.c2 = L.ctx.c3 = 0; L.ctx.n = 0;
+    L.win.t = 0.0; L.win.leaf = 0; L.win.face = 0; L.win.chain = L.ctx;
+    L.sp = 0; L.top = REF_EMPTY; L.op = OP_SHADE; L.flags = 0;
+}
+
+// The start of world.hit(r, t_min, t_max) at the root, r = (cur, tm) with `rng` behind it — or, `have` false, nothing left:
+// the lane idles. Every field of TravLane is written on both paths (the finished ray's state is dead from here on); flag
+// bit 0 is the caller's to set afterwards.
+RT_DEV void trav_begin(const SceneDev &s, TravLane &L, bool have, const XRay &cur, double tm, double t_min, double t_max,
+                       const Rng &rng) {
+    L.tm = tm;
+    trav_set_cur(L, cur);
+    L.t_min = t_min;
+    L.t_lo = t_min;
+    L.closest = t_max;
+    L.sub_closest = 0.0;
+    L.med_t1 = 0.0;
+    L.med_ref = 0;
+    L.rng = rng;
+    L.win.t = 0.0; L.win.leaf = 0; L.win.face = 0;
+    L.ctx.c0 = L.ctx.c1 = L.ctx.c2 = L.ctx.c3 = 0; L.ctx.n = 0;
+    L.win.chain = L.ctx;
+    L.sp = 0;
+    L.flags = 0;
+    L.top = have ? s.root : REF_EMPTY;
+    L.op = have ? classify(L.top) : (uint32_t)OP_IDLE;
+}
+
+// One work item for every lane of the wave that wants one, by one atomic per wave: the first such lane adds their number to
+// *counter, and each takes its place behind the base. `m`: their __ballot, not empty — the caller's, because where it
+// is taken against the caller's branches is a matter of register allocation there. (The answer of a lane that wants none
+// means nothing.)
+RT_DEV unsigned long long wave_claim(unsigned long long *counter, unsigned long long m, unsigned lane) {
+    const int leader = __ffsll((long long)m) - 1;
+    unsigned long long base = 0;
+    if ((int)lane == leader) base = atomicAdd(counter, (unsigned long long)__popcll(m));
+    base = __shfl(base, leader);
+    return base + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
+}
+
+// A persistent grid of `kernel` (workgroups of `wg` threads): as many workgroups as the device holds at once, at most what
+// n_work items at one per lane ask for.
+template <class Args>
+hipError_t launch_persistent(void (*kernel)(SceneDev, Args), int wg, uint64_t n_work, const SceneDev &scene, const Args &args,
+                             hipStream_t stream) {
+    int per_cu = 0, dev = 0, cus = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, wg, 0);
+    if (e != hipSuccess) return e;
+    if (per_cu < 1) per_cu = 1;
+    const uint64_t want = (n_work + wg - 1) / wg;
+    uint64_t blocks = (uint64_t)per_cu * (uint64_t)(cus > 0 ? cus : 1);
+    if (blocks > want) blocks = want ? want : 1;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(wg), 0, stream, scene, args);
+    return hipGetLastError();
+}
+
+// The instance a scene's stack need selects: f(TravShape<STACK, WG, CACHE>) launches it. Where the stacks fit in kStackTiny
+// entries, one kCacheBlock-thread workgroup per CU with the first kNodeCache node records in LDS.
+template <int STACK, int WG, int CACHE>
+struct TravShape { static constexpr int stack = STACK, wg = WG, cache = CACHE; };
+template <class F>
+hipError_t trav_dispatch(uint32_t stack_need, F f) {
+    if (stack_need > (uint32_t)kStackLarge) return hipErrorInvalidValue;
+    if (stack_need <= (uint32_t)kStackTiny) return f(TravShape<kStackTiny, kCacheBlock, kNodeCache>{});
+    if (stack_need <= (uint32_t)kStackSmall) return f(TravShape<kStackSmall, kBlock, 0>{});
+    if (stack_need <= (uint32_t)kStackMid) return f(TravShape<kStackMid, kBlock, 0>{});
+    return f(TravShape<kStackLarge, kBlock, 0>{});
 }
 
 } // namespace

@@ -272,6 +272,39 @@ struct EngineFixed {
     WfStreams gs;                     // group streams / events / pinned words
 };
 
+// Largest of n device-resident row ids.
+__global__ void __launch_bounds__(256) row_ids_max_kernel(const uint32_t *rows, uint32_t n, uint32_t *out) {
+    uint32_t m = 0;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) m = rows[i] > m ? rows[i] : m;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) { uint32_t o = (uint32_t)__shfl_xor((int)m, d); m = o > m ? o : m; }
+    if ((threadIdx.x & 63u) == 0 && m) atomicMax(out, m);
+}
+// The range check of row ids that came from the caller's HBM (rt_render_device's and rt_features_device's twin of the
+// host-side check): the largest of them is reduced on the device and copied to a pinned word. Two halves, so that the
+// check costs a render no synchronisation of its own: begin() is enqueued with the call's other preparations,
+// and end() looks at the answer behind the synchronisation the call makes anyway before its first pass. (A row id out of
+// range cannot fault a kernel — it only mis-keys a frame — so nothing is lost by finding out a moment later.) Every begin()
+// starts from zero: a call that fails at either half leaves nothing the next call on the stream would trip over.
+struct RowCheck {
+    DeviceBuf<uint32_t> d_max;        // device word: largest row id of the call being checked (created on first use)
+    PinnedBuf<uint32_t> h_max;        // ... and the pinned word it is copied to
+    void begin(const uint32_t *d_rows, uint32_t n, hipStream_t stream) {      // n > 0
+        if (!h_max) {                                  // (keyed on the one created last: a failure half-way is made good by the next call)
+            d_max = DeviceBuf<uint32_t>(1);
+            h_max = PinnedBuf<uint32_t>(1);
+        }
+        RT_HIP(hipMemsetAsync(d_max, 0, sizeof(uint32_t), stream));
+        const uint32_t blocks = (n + 255u) / 256u;
+        hipLaunchKernelGGL(row_ids_max_kernel, dim3(blocks > 64 ? 64 : blocks), dim3(256), 0, stream, d_rows, n, d_max.p);
+        RT_HIP(hipGetLastError());
+        RT_HIP(hipMemcpyAsync(h_max, d_max, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    }
+    void end(uint64_t limit, const char *who) const {      // (after a synchronisation of the stream)
+        RT_REQUIRE((uint64_t)*h_max.p < limit, RT_ERR_INVALID, std::string(who) + ": row id out of range");
+    }
+};
+
 // What one (scene, stream) keeps from render to render. Its members own their HIP resources; the ones every call needs —
 // work counter, counter block, two events — are created when it is constructed.
 struct Workspace {
@@ -292,8 +325,7 @@ struct Workspace {
     bool used_kt = false;
     uint32_t used_chunk = 0, used_passes = 0;
     uint64_t used_slots = 0;
-    DeviceBuf<uint32_t> rows_max;     // device word: largest row id of the call being checked
-    PinnedBuf<uint32_t> h_rows_max;   // ... and the pinned word it is copied to
+    RowCheck rows;                    // rt_render_device's row ids
     uint64_t used_partial_bytes = 0;
     // rt_radiance (host buffers): the device copies of the caller's rays and of the sums, grown as needed
     DeviceBuf<rt_radiance_ray> rad_rays;
@@ -305,20 +337,15 @@ struct Workspace {
     std::string async_err;
 };
 
-// Scratch of the closest-hit queries on one (scene, stream): the ray counter of the persistent grid, a counter block
-// and two events, created when it is constructed. Nothing of a render's Workspace: a query may run beside an asynchronous
-// render of the same scene.
+// Scratch of the closest-hit calls — queries (rt_intersect*) or feature buffers (rt_features*) — on one (scene, stream): the
+// work counter of the persistent grid, a counter block and two events, created when it is constructed. Nothing of a render's
+// Workspace: such a call may run beside an asynchronous render of the same scene.
 struct QueryScratch {
     std::mutex mu;                    // one call at a time enqueues — and, with stats, reads back — on this (scene, stream)
     DeviceBuf<unsigned long long> counter{1};
     DeviceBuf<StatsDev> stats{1};
     Event ev0{hipEventDefault}, ev1{hipEventDefault};
-};
-
-// The same for the feature calls (rt_features*) on one (scene, stream), plus the words of the device-resident row check.
-struct FeatureScratch : QueryScratch {
-    DeviceBuf<uint32_t> rows_max{1};  // device word: largest row id of the call being checked
-    PinnedBuf<uint32_t> h_rows_max{1};
+    RowCheck rows;                    // rt_features_device's row ids
 };
 
 } // namespace
@@ -343,9 +370,9 @@ struct rt_scene {
     int n_cus = 0;                    // compute units of `device`
     std::mutex mu;
     std::map<hipStream_t, Workspace> ws;
-    std::mutex qmu;                   // guards `qs`
-    std::map<hipStream_t, std::unique_ptr<QueryScratch>> qs;
-    std::map<hipStream_t, std::unique_ptr<FeatureScratch>> fs;      // (under qmu too)
+    std::mutex qmu;                   // guards `qs` and `fs`
+    // (two maps: a query and a feature call on one stream share no mutex and no counter, and run side by side)
+    std::map<hipStream_t, std::unique_ptr<QueryScratch>> qs, fs;    // of rt_intersect*, of rt_features*
 };
 
 namespace {
@@ -355,12 +382,18 @@ Workspace &workspace_for(rt_scene *sc, hipStream_t stream) {
     return sc->ws.try_emplace(stream).first->second;      // (a new one is in the map once it is complete, or not at all)
 }
 
+// The view of a render or a feature call: an image, a shutter interval, row ids that fit 32 bits. (`empty_note`: what the
+// caller's message adds to "empty image".)
+void check_view(const rt_camera *cam, const rt_params *p, const std::string &prefix, const char *empty_note) {
+    RT_REQUIRE(p->width > 0 && p->height > 0 && p->n_frames > 0, RT_ERR_INVALID, prefix + "empty image" + empty_note);
+    RT_REQUIRE(cam->time0 < cam->time1, RT_ERR_INVALID, prefix + "camera time0 >= time1 (gen_range panics in the reference, camera.rs:71)");
+    RT_REQUIRE((uint64_t)p->height * p->n_frames <= 0xFFFFFFFFull, RT_ERR_INVALID, prefix + "height * n_frames overflows a row id");
+}
+
 void check_params(const rt_scene *scene, const rt_camera *cam, const rt_params *p) {
     RT_REQUIRE(scene && cam && p, RT_ERR_INVALID, "null argument");
-    RT_REQUIRE(p->width > 0 && p->height > 0 && p->n_frames > 0, RT_ERR_INVALID, "empty image");
-    RT_REQUIRE(cam->time0 < cam->time1, RT_ERR_INVALID, "camera time0 >= time1 (gen_range panics in the reference, camera.rs:71)");
+    check_view(cam, p, "", "");
     RT_REQUIRE(p->n_rows == 0 || p->row_ids, RT_ERR_INVALID, "row_ids is null");
-    RT_REQUIRE((uint64_t)p->height * p->n_frames <= 0xFFFFFFFFull, RT_ERR_INVALID, "height * n_frames overflows a row id");
 }
 
 template <class T>
@@ -405,35 +438,6 @@ void ensure_pool(Workspace &w, uint32_t blocks, uint32_t depth, hipStream_t stre
     w.pool_dbg = pool_alloc<unsigned long long>(w, 8 + 2 * 65536);
     w.pool_slots = slots;
     w.pool_depth = depth;
-}
-
-// Largest of n device-resident row ids (rt_render_device's twin of rt_render's host-side range check).
-__global__ void __launch_bounds__(256) row_ids_max_kernel(const uint32_t *rows, uint32_t n, uint32_t *out) {
-    uint32_t m = 0;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) m = rows[i] > m ? rows[i] : m;
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) { uint32_t o = (uint32_t)__shfl_xor((int)m, d); m = o > m ? o : m; }
-    if ((threadIdx.x & 63u) == 0 && m) atomicMax(out, m);
-}
-// Two halves, so that the check costs a render no synchronisation of its own: the reduction and the copy of
-// its answer to a pinned word are enqueued with the call's other preparations, and the answer is looked at behind the
-// synchronisation the call makes anyway before its first pass. (A row id out of range cannot fault a kernel — it only
-// mis-keys a frame — so nothing is lost by finding out a moment later.)
-void begin_check_device_rows(Workspace &w, const rt_params *p, hipStream_t stream) {
-    if (p->n_rows == 0) return;
-    if (!w.h_rows_max) {                           // (keyed on the one created last: a failure half-way is made good by the next call)
-        w.rows_max = DeviceBuf<uint32_t>(1);
-        w.h_rows_max = PinnedBuf<uint32_t>(1);
-    }
-    RT_HIP(hipMemsetAsync(w.rows_max, 0, sizeof(uint32_t), stream));
-    uint32_t blocks = (p->n_rows + 255u) / 256u;
-    hipLaunchKernelGGL(row_ids_max_kernel, dim3(blocks > 64 ? 64 : blocks), dim3(256), 0, stream, p->row_ids, p->n_rows, w.rows_max.p);
-    RT_HIP(hipGetLastError());
-    RT_HIP(hipMemcpyAsync(w.h_rows_max, w.rows_max, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-}
-void end_check_device_rows(Workspace &w, const rt_params *p) {      // (after a synchronisation of the stream)
-    if (p->n_rows == 0) return;
-    RT_REQUIRE((uint64_t)*w.h_rows_max.p < (uint64_t)p->height * p->n_frames, RT_ERR_INVALID, "rt_render_device: row id out of range");
 }
 
 // Where the paths of an rt_radiance* call start: the caller's rays (device) instead of the camera's rows.
@@ -515,6 +519,8 @@ void enqueue(rt_scene *sc, const rt_camera *cam, const rt_params *p, const uint3
              hipStream_t stream, rt_stats *stats, bool check_rows = false /* the row ids came from the caller's HBM: range-check them */,
              const RaySource *src = nullptr) {
     Workspace &w = workspace_for(sc, stream);
+    if (p->n_rows == 0) check_rows = false;
+    const uint64_t row_limit = (uint64_t)p->height * p->n_frames;
     RenderArgs a{};
     a.cam = *cam;
     a.width = p->width; a.height = p->height; a.spp = p->spp; a.max_depth = p->max_depth;
@@ -582,9 +588,9 @@ void enqueue(rt_scene *sc, const rt_camera *cam, const rt_params *p, const uint3
         RT_HIP(hipMemsetAsync(w.work_counter, 0, sizeof(unsigned long long), stream));
         if (counters) RT_HIP(hipMemsetAsync(w.stats, 0, sizeof(StatsDev), stream));
         RT_HIP(hipMemcpyAsync(fx.d_args, &a, sizeof(RenderArgs), hipMemcpyHostToDevice, stream));
-        if (check_rows) begin_check_device_rows(w, p, stream);
+        if (check_rows) w.rows.begin(p->row_ids, p->n_rows, stream);
         RT_HIP(hipStreamSynchronize(stream));      // the three structs above live on this thread's stack
-        if (check_rows) end_check_device_rows(w, p);
+        if (check_rows) w.rows.end(row_limit, "rt_render_device");
         RT_HIP(hipEventRecord(w.ev0, stream));
         WfRender r;
         r.scene = &sc->dev; r.args = &a; r.d_args = fx.d_args; r.pool = &w.pool;
@@ -623,9 +629,9 @@ void enqueue(rt_scene *sc, const rt_camera *cam, const rt_params *p, const uint3
     w.tape.reserve(tape_bytes / sizeof(double), &stream, 1);
     a.tape = w.tape;
     if (check_rows) {                              // (the A/B engine enqueues without a synchronisation of its own)
-        begin_check_device_rows(w, p, stream);
+        w.rows.begin(p->row_ids, p->n_rows, stream);
         RT_HIP(hipStreamSynchronize(stream));
-        end_check_device_rows(w, p);
+        w.rows.end(row_limit, "rt_render_device");
     }
     RT_HIP(hipMemsetAsync(w.work_counter, 0, sizeof(unsigned long long), stream));
     if (counters) RT_HIP(hipMemsetAsync(w.stats, 0, sizeof(StatsDev), stream));
@@ -661,11 +667,27 @@ rt_stats read_stats(hipEvent_t ev0, hipEvent_t ev1, const StatsDev *d_stats, Sta
     return out;
 }
 
-QueryScratch &query_scratch_for(rt_scene *sc, hipStream_t stream) {
+// The scratch of `stream` in sc->qs or sc->fs.
+QueryScratch &scratch_for(rt_scene *sc, std::map<hipStream_t, std::unique_ptr<QueryScratch>> &of, hipStream_t stream) {
     std::lock_guard<std::mutex> lock(sc->qmu);
-    std::unique_ptr<QueryScratch> &q = sc->qs[stream];
+    std::unique_ptr<QueryScratch> &q = of[stream];
     if (!q) q.reset(new QueryScratch());                   // (stored once it is complete, or not at all)
     return *q;
+}
+
+// One closest-hit call on `stream`, q locked: the counters reset, `launch()` — the kernel, on q.counter and, with `counters`,
+// q.stats — and with stats the wait for it and what read_stats makes of it.
+template <class Launch>
+void run_counted(QueryScratch &q, bool counters, hipStream_t stream, rt_stats *stats, Launch launch) {
+    RT_HIP(hipMemsetAsync(q.counter, 0, sizeof(unsigned long long), stream));
+    if (counters) RT_HIP(hipMemsetAsync(q.stats, 0, sizeof(StatsDev), stream));
+    if (stats) RT_HIP(hipEventRecord(q.ev0, stream));
+    RT_HIP(launch());
+    if (!stats) return;
+    RT_HIP(hipEventRecord(q.ev1, stream));
+    RT_HIP(hipStreamSynchronize(stream));
+    StatsDev h;
+    *stats = read_stats(q.ev0, q.ev1, counters ? q.stats.p : nullptr, h);
 }
 
 void check_query(const rt_scene *scene, const void *rays, uint64_t n_rays, uint32_t flags, const void *hits, const char *who) {
@@ -681,28 +703,12 @@ void run_query(rt_scene *sc, const rt_query_ray *d_rays, uint64_t n_rays, uint32
                rt_stats *stats) {
     if (stats) std::memset(stats, 0, sizeof *stats);
     if (n_rays == 0) return;
-    QueryScratch &q = query_scratch_for(sc, stream);
+    QueryScratch &q = scratch_for(sc, sc->qs, stream);
     std::lock_guard<std::mutex> lock(q.mu);
     const bool counters = stats && (flags & RT_FLAG_COUNTERS);
-    QueryArgs a{d_rays, d_hits, n_rays, q.counter, counters ? q.stats.p : nullptr};
-    RT_HIP(hipMemsetAsync(q.counter, 0, sizeof(unsigned long long), stream));
-    if (counters) RT_HIP(hipMemsetAsync(q.stats, 0, sizeof(StatsDev), stream));
-    if (stats) RT_HIP(hipEventRecord(q.ev0, stream));
-    RT_HIP(launch_query(sc->dev, a, sc->stack_need, counters, (flags & RT_FLAG_ANY_HIT) != 0, stream));
-    if (!stats) return;
-    RT_HIP(hipEventRecord(q.ev1, stream));
-    RT_HIP(hipStreamSynchronize(stream));
-    StatsDev h;
-    rt_stats out = read_stats(q.ev0, q.ev1, counters ? q.stats.p : nullptr, h);
-    out.rays = n_rays;                             // (a query counts no paths, rays or light tests of its own)
-    *stats = out;
-}
-
-FeatureScratch &feature_scratch_for(rt_scene *sc, hipStream_t stream) {
-    std::lock_guard<std::mutex> lock(sc->qmu);
-    std::unique_ptr<FeatureScratch> &q = sc->fs[stream];
-    if (!q) q.reset(new FeatureScratch());                 // (stored once it is complete, or not at all)
-    return *q;
+    const QueryArgs a{d_rays, d_hits, n_rays, q.counter, counters ? q.stats.p : nullptr};
+    run_counted(q, counters, stream, stats, [&] { return launch_query(sc->dev, a, sc->stack_need, counters, (flags & RT_FLAG_ANY_HIT) != 0, stream); });
+    if (stats) stats->rays = n_rays;               // (a query counts no paths, rays or light tests of its own)
 }
 
 // The arguments of rt_features* (host side only; the scene comes last so that a bad argument is reported as such whatever
@@ -712,9 +718,7 @@ void check_features(const rt_scene *scene, const rt_camera *cam, const rt_params
     RT_REQUIRE(p, RT_ERR_INVALID, w + ": null params");
     RT_REQUIRE(cam, RT_ERR_INVALID, w + ": null camera");
     RT_REQUIRE(!(p->flags & ~RT_FLAG_COUNTERS), RT_ERR_INVALID, w + ": flag bits other than RT_FLAG_COUNTERS");
-    RT_REQUIRE(p->width > 0 && p->height > 0 && p->n_frames > 0, RT_ERR_INVALID, w + ": empty image (width, height or n_frames is 0)");
-    RT_REQUIRE(cam->time0 < cam->time1, RT_ERR_INVALID, w + ": camera time0 >= time1 (gen_range panics in the reference, camera.rs:71)");
-    RT_REQUIRE((uint64_t)p->height * p->n_frames <= 0xFFFFFFFFull, RT_ERR_INVALID, w + ": height * n_frames overflows a row id");
+    check_view(cam, p, w + ": ", " (width, height or n_frames is 0)");
     const bool need_rows = p->n_rows > 0 && p->spp > 0;
     RT_REQUIRE(p->n_rows == 0 || out, RT_ERR_INVALID, w + ": null output");
     RT_REQUIRE(!need_rows || p->row_ids, RT_ERR_INVALID, w + ": null row_ids");
@@ -741,16 +745,12 @@ void run_features(rt_scene *sc, const rt_camera *cam, const rt_params *p, const 
         if (stats) RT_HIP(hipStreamSynchronize(stream));
         return;
     }
-    FeatureScratch &q = feature_scratch_for(sc, stream);
+    QueryScratch &q = scratch_for(sc, sc->fs, stream);
     std::lock_guard<std::mutex> lock(q.mu);
     if (check_rows) {
-        RT_HIP(hipMemsetAsync(q.rows_max, 0, sizeof(uint32_t), stream));
-        const uint32_t blocks = (p->n_rows + 255u) / 256u;
-        hipLaunchKernelGGL(row_ids_max_kernel, dim3(blocks > 64 ? 64 : blocks), dim3(256), 0, stream, d_rows, p->n_rows, q.rows_max.p);
-        RT_HIP(hipGetLastError());
-        RT_HIP(hipMemcpyAsync(q.h_rows_max, q.rows_max, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        q.rows.begin(d_rows, p->n_rows, stream);
         RT_HIP(hipStreamSynchronize(stream));
-        RT_REQUIRE((uint64_t)*q.h_rows_max.p < (uint64_t)p->height * p->n_frames, RT_ERR_INVALID, std::string(who) + ": row id out of range");
+        q.rows.end((uint64_t)p->height * p->n_frames, who);
     }
     const bool counters = stats && (p->flags & RT_FLAG_COUNTERS);
     FeatureArgs a{};
@@ -764,17 +764,8 @@ void run_features(rt_scene *sc, const rt_camera *cam, const rt_params *p, const 
     a.out = d_out;
     a.counter = q.counter;
     a.stats = counters ? q.stats.p : nullptr;
-    RT_HIP(hipMemsetAsync(q.counter, 0, sizeof(unsigned long long), stream));
-    if (counters) RT_HIP(hipMemsetAsync(q.stats, 0, sizeof(StatsDev), stream));
-    if (stats) RT_HIP(hipEventRecord(q.ev0, stream));
-    RT_HIP(launch_features(sc->dev, a, sc->stack_need, counters, stream));
-    if (!stats) return;
-    RT_HIP(hipEventRecord(q.ev1, stream));
-    RT_HIP(hipStreamSynchronize(stream));
-    StatsDev h;
-    rt_stats out = read_stats(q.ev0, q.ev1, counters ? q.stats.p : nullptr, h);
-    out.paths = out.rays = n_pixels * p->spp;              // (one camera path, one world.hit per sample; the kernel counts neither)
-    *stats = out;
+    run_counted(q, counters, stream, stats, [&] { return launch_features(sc->dev, a, sc->stack_need, counters, stream); });
+    if (stats) stats->paths = stats->rays = n_pixels * p->spp;     // (one camera path, one world.hit per sample; the kernel counts neither)
 }
 
 // The arguments of rt_radiance* (host side only, before the scene is looked at: the scene comes last so that a bad argument

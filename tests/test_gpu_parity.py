@@ -789,6 +789,43 @@ def test_device_resident_row_ids_are_checked(rt):
     assert torch.isfinite(d_out).all()
 
 
+@pytest.mark.parametrize("call", ["render", "features"])
+def test_a_rejected_row_id_leaves_the_stream_working(rt, call):
+    """rt_render_device and rt_features_device share the device-side row check: on one stream, a device-resident row id
+    equal to height * n_frames is RT_ERR_INVALID "row id out of range", and the next call there with valid rows succeeds
+    with the bits of the host-buffer form of the same call."""
+    import torch
+    W, H, n_frames = 8, 8, 2
+    s = rt.HostScene("two_spheres")
+    cam, bg = s.default_view(W / H)
+    dev = rt.DeviceScene(s.desc)
+    p = rt.make_params(W, H, 1, 5, bg, n_frames=n_frames)
+    rows = np.array([0, 9, 3, 15, 7, 8, 12, 5], dtype=np.uint32)              # both frames, out of order
+    if call == "render":
+        host = dev.render(cam, p, rows)
+        d_out = torch.full((len(rows), W, 3), float("nan"), dtype=torch.float64, device="cuda")
+        run = dev.render_device
+    else:
+        host = dev.features(cam, p, rows).reshape(-1).view(np.float64)
+        d_out = torch.full((len(rows) * W * 8,), float("nan"), dtype=torch.float64, device="cuda")
+        run = dev.features_device
+    stream = torch.cuda.Stream()
+    bad = rows.copy()
+    bad[6] = H * n_frames                                                     # one past the last row of the last frame
+    d_rows = torch.from_numpy(bad.view(np.int32)).cuda()
+    torch.cuda.synchronize()
+    with pytest.raises(rt.RtError) as e:
+        run(cam, p, d_rows.data_ptr(), len(rows), d_out.data_ptr(), stream.cuda_stream)
+    assert e.value.code == F.RT_ERR_INVALID and "row id out of range" in str(e.value)
+    d_rows.copy_(torch.from_numpy(rows.view(np.int32)))
+    torch.cuda.synchronize()
+    run(cam, p, d_rows.data_ptr(), len(rows), d_out.data_ptr(), stream.cuda_stream)
+    if call == "render":
+        dev.wait(stream.cuda_stream)
+    stream.synchronize()
+    assert np.array_equal(bits(d_out.cpu().numpy()), bits(host))
+
+
 @pytest.mark.parametrize("scene,W,H,param,assets", [
     ("random_scene", 1200, 800, 0, False),        # BASELINE config 2
     ("cornell_box", 600, 600, 0, False),          # BASELINE config 4
