@@ -545,6 +545,77 @@ int rt_features(rt_scene *scene, const rt_camera *cam, const rt_params *params,
 int rt_features_device(rt_scene *scene, const rt_camera *cam, const rt_params *params,
                        rt_feature *d_out_features, void *hip_stream, rt_stats *stats);
 
+/* ---- edge-avoiding denoiser over the feature buffers ----------------------------------------------------
+ * The consumer of rt_features*: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) on albedo-demodulated
+ * radiance, guided by the frame's first-hit albedo, normal and depth — the step between a render and its tone map,
+ *   rt_render_device -> rt_features_device -> rt_denoise_device -> rt_tonemap_device,
+ * all in HBM on one stream. It needs no variance estimate and no rt_scene, and never touches a render's sums or RNG.
+ * The edge-stopping function is rational, 1 / (1 + d / sigma^2), not exp: every operation below is an IEEE + - * / of
+ * doubles in the stated order, with no contraction, so the result is defined bit for bit.
+ *
+ * The image has width x height pixels. Per pixel p the inputs are S[3], a render's sums, and F, its rt_feature record,
+ * both sums of `spp` samples. With sp = (double)spp:
+ *   c_j = (S_j is NaN ? 0 : S_j) / sp          (write_color's rule for NaN)
+ *   a_j = F.albedo_j / sp,  n_j = F.normal_j / sp,  z = F.depth / sp      (F.hits is unused: misses count as depth 0)
+ *   m_j = a_j > albedo_floor ? a_j : albedo_floor   (a NaN albedo gives the floor); RT_DENOISE_NO_DEMODULATE: m_j = 1.0
+ *   e0_j = c_j / m_j
+ * On the host, in doubles: inv_n = 1.0 / (sigma_normal * sigma_normal), inv_z and inv_a likewise from sigma_depth and
+ * sigma_albedo; a sigma of +inf gives 0 and switches its term off.
+ * Iteration k = 0 .. n_iter-1: step s = 2^k, sigma_k = sigma_color * 2^-k (an exact scaling), inv_c = 1.0 / (sigma_k *
+ * sigma_k), h = {1/16, 1/4, 3/8, 1/4, 1/16}:
+ *   sw = 0.0; sv = (0, 0, 0)
+ *   for j = -2 .. 2 (rows), for i = -2 .. 2 (columns), in that order:
+ *       q = (x + i*s, y + j*s); a tap outside the image is skipped (it adds nothing)
+ *       dc = (d0*d0 + d1*d1) + d2*d2      with d = ek(p) - ek(q);   dn, da the same on n and a;   dz = z(p) - z(q)
+ *       den = (((1.0 + dc*inv_c) * (1.0 + dn*inv_n)) * (1.0 + (dz*dz)*inv_z)) * (1.0 + da*inv_a)
+ *       w = (h[j+2] * h[i+2]) / den
+ *       sw = sw + w;  sv_c = sv_c + w * ek_c(q)
+ *   e(k+1)_c(p) = sv_c / sw               (the centre tap makes sw >= 9/64)
+ * Output: out_c = (e(n_iter)_c * m_c) * sp — sums like a render's, so rt_tonemap_device and rt_write_color apply as they
+ * are. NaN or inf in a guide field propagates where IEEE arithmetic carries it; buffer contents are never validated.
+ * (x, y) are the column and the image row; tap offsets i * 2^k are computed in 64 bits.
+ *
+ * Row order: row_ids == NULL means buffer row i is image row i. Otherwise row_ids holds `height` entries and buffer row i
+ * is image row row_ids[i], as rt_render / rt_features wrote it for ONE frame; the output comes in the same order. A list
+ * that is not a permutation of [0, height) is RT_ERR_INVALID with the output untouched: rt_denoise checks it on the host;
+ * rt_denoise_device builds the inverse map in the workspace with one small kernel that counts bad and repeated ids, and
+ * reads the count behind one synchronisation of hip_stream before anything else is enqueued. With NULL rows
+ * rt_denoise_device is a pure enqueue with no host synchronisation.
+ *
+ * Workspace: rt_denoise_device allocates nothing. The caller gives it rt_denoise_workspace_bytes(p) bytes of device memory
+ * (the packed guides, two colour planes, the inverse row map), whose contents before the call mean nothing and which may
+ * be reused by the next call on the stream. d_out_rgb_sum may alias d_rgb_sum: every sum is read before any output is
+ * written. d_rgb_sum, d_features, d_out_rgb_sum and the workspace must be 16-byte aligned, device rows 4-byte aligned.
+ * rt_denoise stages host buffers through device memory of its own on the current device's default stream (out_rgb_sum may
+ * be rgb_sum) and reports the device time of the filter in *ms.
+ *
+ * RT_ERR_INVALID with rt_last_error() set, before any device call: a null params, buffer or workspace; width, height or
+ * spp equal to 0; n_iter > RT_DENOISE_MAX_ITER; a sigma or floor that is <= 0 or NaN, or an infinite floor; a flag bit
+ * other than RT_DENOISE_NO_DEMODULATE; a misaligned device pointer; width * height > RT_DENOISE_MAX_PIXELS. */
+typedef struct rt_denoise_params {    /* 64 B */
+    uint32_t width, height;
+    uint32_t spp;                     /* divisor of the sums, >= 1 */
+    uint32_t n_iter;                  /* 0 .. RT_DENOISE_MAX_ITER */
+    double   sigma_color, sigma_normal, sigma_depth, sigma_albedo;   /* > 0; +inf = term off */
+    double   albedo_floor;            /* > 0, finite */
+    uint32_t flags;                   /* RT_DENOISE_NO_DEMODULATE */
+    uint32_t _pad;
+} rt_denoise_params;
+
+#define RT_DENOISE_MAX_ITER      16
+#define RT_DENOISE_NO_DEMODULATE 0x1u                /* filter the radiance itself: m = 1 */
+#define RT_DENOISE_MAX_PIXELS    (1ull << 36)        /* width * height limit (a 1-D grid of 256-pixel workgroups) */
+
+/* Bytes of device workspace rt_denoise_device needs for p's image; 0 on invalid params. */
+uint64_t rt_denoise_workspace_bytes(const rt_denoise_params *p);
+/* Device buffers (width * height * 3 sums in and out, width * height records, NULL or `height` row ids), enqueued on
+ * hip_stream (NULL = default stream). */
+int rt_denoise_device(const double *d_rgb_sum, const rt_feature *d_features, const uint32_t *d_row_ids,
+                      const rt_denoise_params *p, double *d_out_rgb_sum, void *d_workspace, void *hip_stream);
+/* Host buffers; synchronous. ms may be NULL. */
+int rt_denoise(const double *rgb_sum, const rt_feature *features, const uint32_t *row_ids,
+               const rt_denoise_params *p, double *out_rgb_sum, double *ms);
+
 /* write_color (main.rs:280-299): NaN→0, sqrt(c/spp), clamp [0,0.999], *255.999, floor. */
 void rt_write_color(const double rgb_sum[3], int32_t spp, uint8_t out_rgb[3]);
 /* Device form over n_pixels sums → n_pixels*3 bytes, on hip_stream. */

@@ -64,6 +64,8 @@ int rtb_abi_sizes(uint32_t *out, uint32_t n);
 int rtb_radiance_abi_sizes(uint32_t *out, uint32_t n);
 /* The same for the rt_features* record: {rt_feature}; returns 1. */
 int rtb_features_abi_sizes(uint32_t *out, uint32_t n);
+/* The same for the rt_denoise* structure: {rt_denoise_params}; returns 1. */
+int rtb_denoise_abi_sizes(uint32_t *out, uint32_t n);
 
 #ifdef __cplusplus
 }

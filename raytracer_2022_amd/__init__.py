@@ -9,9 +9,11 @@ from . import _ffi
 from ._ffi import RtError, lib, make_ref, ref_index, ref_kind  # noqa: F401
 from .host import (DescBuilder, HostScene, camera_new, fill_image, load_image, make_params, shuffled_rows,  # noqa: F401
                    write_color, write_jpeg)
-from .device import DeviceScene, DeviceSceneSet, query_rays, radiance_params, radiance_rays  # noqa: F401
+from .device import (DeviceScene, DeviceSceneSet, denoise, denoise_device, denoise_params, denoise_workspace_bytes,  # noqa: F401
+                     query_rays, radiance_params, radiance_rays)
 from ._ffi import FEATURE_DTYPE, HIT_DTYPE, QUERY_RAY_DTYPE, RADIANCE_RAY_DTYPE  # noqa: F401
 
 __all__ = ["DescBuilder", "HostScene", "DeviceScene", "DeviceSceneSet", "camera_new", "fill_image", "make_params", "shuffled_rows",
            "write_color", "write_jpeg", "load_image", "RtError", "lib", "make_ref", "ref_kind", "ref_index", "query_rays",
-           "QUERY_RAY_DTYPE", "HIT_DTYPE", "radiance_rays", "radiance_params", "RADIANCE_RAY_DTYPE", "FEATURE_DTYPE"]
+           "QUERY_RAY_DTYPE", "HIT_DTYPE", "radiance_rays", "radiance_params", "RADIANCE_RAY_DTYPE", "FEATURE_DTYPE",
+           "denoise", "denoise_device", "denoise_params", "denoise_workspace_bytes"]

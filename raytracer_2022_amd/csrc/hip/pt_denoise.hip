@@ -1,0 +1,184 @@
+// pt_denoise.hip — edge-avoiding a-trous denoiser over a render's sums and its feature buffers (rt_denoise*,
+// include/rt2022.h has the definition: every + - * / below is one of its operations, in its order; -ffp-contract=off).
+//
+// Three kernels, all on the caller's workspace (denoise_layout):
+//   dn_rows     one workgroup: the inverse of the caller's row list (image row -> buffer row) and the count of ids that
+//               are out of range or repeated. An id's slot is written by plain stores and read back behind a barrier: the
+//               entry that lost the race to a repeated id finds another's index there. The count is the only atomic.
+//   dn_prepare  buffer order -> image order: NaN -> 0, / sp, demodulation; writes the packed guides and colour plane 0
+//               (with no iteration: the output).
+//   dn_atrous   one launch per iteration, plane k & 1 -> plane ~k & 1; the last one remodulates and writes the output in
+//               buffer order.
+// Layout: a pixel's ten doubles are five 16-byte pieces, each piece a plane of its own — {n0, n1} {n2, z} {a0, a1} never
+// change, {e0, e1} {e2, a2} ping-pong (a2 rides in the colour's spare half, so a tap is five loads with nothing wasted).
+// A workgroup is 64 x 4 pixels and a wave 64 consecutive pixels of one image row, so every tap of a wave is five
+// contiguous 1 KiB loads, served by the caches: neighbouring lanes, waves and workgroups read the same lines. The centre
+// pixel stays in registers; a tap costs one division. (Staging steps 1 and 2 through an LDS tile with a halo was built and
+// measured: 0.36-0.38 ms against 0.39-0.41 ms per 800x800 frame of five iterations, beside a 38 ms render — not worth two
+// more instances and a 69 KB LDS opt-in: profiles/denoise_bench.log)
+#include "pt_device.h"
+
+namespace rt2022 {
+
+namespace {
+
+constexpr int kDnBlock = 256;          // 4 waves: rows y .. y+3 of a 64-pixel column strip
+constexpr uint32_t kDnNoRow = 0xFFFFFFFFu;
+
+#define DN_DEV __device__ __forceinline__
+
+struct DnPixel { double e[3], n[3], a[3], z; };
+
+// The pixel at index i of five planes `stride` apart (guides: g, colour: c).
+DN_DEV DnPixel dn_load(const double2 *g, const double2 *c, uint64_t stride, uint64_t i) {
+    const double2 g0 = g[i], g1 = g[stride + i], g2 = g[2 * stride + i], c0 = c[i], c1 = c[stride + i];
+    DnPixel p;
+    p.n[0] = g0.x; p.n[1] = g0.y; p.n[2] = g1.x; p.z = g1.y; p.a[0] = g2.x; p.a[1] = g2.y;
+    p.e[0] = c0.x; p.e[1] = c0.y; p.e[2] = c1.x; p.a[2] = c1.y;
+    return p;
+}
+
+DN_DEV double dn_dist(const double p[3], const double q[3]) {
+    const double d0 = p[0] - q[0], d1 = p[1] - q[1], d2 = p[2] - q[2];
+    return (d0 * d0 + d1 * d1) + d2 * d2;
+}
+
+constexpr double dn_h(int t) { return (t == 0 || t == 4) ? 1.0 / 16.0 : t == 2 ? 3.0 / 8.0 : 1.0 / 4.0; }
+
+DN_DEV double dn_modulation(const DenoiseArgs &a, double albedo) {
+    return a.demodulate ? (albedo > a.albedo_floor ? albedo : a.albedo_floor) : 1.0;
+}
+
+// The workgroup's pixel strip: columns x0 .. x0+63, rows y0 .. y0+3.
+DN_DEV void dn_block_origin(const DenoiseArgs &a, uint32_t &x0, uint32_t &y0) {
+    const uint32_t nbx = (a.width + 63u) / 64u;
+    const uint32_t by = blockIdx.x / nbx, bx = blockIdx.x - by * nbx;
+    x0 = bx * 64u; y0 = by * 4u;
+}
+
+__global__ void __launch_bounds__(1024) dn_rows(const uint32_t *rows, uint32_t height, uint32_t *inv, uint32_t *bad) {
+    for (uint32_t i = threadIdx.x; i < height; i += blockDim.x) inv[i] = kDnNoRow;
+    if (threadIdx.x == 0) *bad = 0u;
+    __syncthreads();
+    uint32_t n_bad = 0;
+    for (uint32_t i = threadIdx.x; i < height; i += blockDim.x) {
+        const uint32_t g = rows[i];
+        if (g < height) inv[g] = i; else n_bad++;
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < height; i += blockDim.x) {
+        const uint32_t g = rows[i];
+        if (g < height && inv[g] != i) n_bad++;
+    }
+    if (n_bad) atomicAdd(bad, n_bad);
+}
+
+__global__ void __launch_bounds__(kDnBlock) dn_prepare(const DenoiseArgs a, double2 *guides, double2 *colour, const uint32_t *inv, bool final) {
+    uint32_t x0, y0;
+    dn_block_origin(a, x0, y0);
+    const uint32_t x = x0 + (threadIdx.x & 63u), y = y0 + (threadIdx.x >> 6);
+    if (x >= a.width || y >= a.height) return;
+    const uint64_t n = (uint64_t)a.width * a.height, i = (uint64_t)y * a.width + x;
+    const uint64_t src = (uint64_t)(inv ? inv[y] : y) * a.width + x;
+    const double2 *f = reinterpret_cast<const double2 *>(a.feat + src);
+    const double2 f0 = f[0], f1 = f[1], f2 = f[2], f3 = f[3];           // {a0, a1} {a2, n0} {n1, n2} {depth, hits}
+    const double alb[3] = {f0.x / a.sp, f0.y / a.sp, f1.x / a.sp};
+    double e[3], m[3];
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const double s = a.sum[3 * src + c];
+        m[c] = dn_modulation(a, alb[c]);
+        e[c] = ((s != s ? 0.0 : s) / a.sp) / m[c];
+    }
+    if (final) {                                           // no iteration: e0 goes straight back out
+#pragma unroll
+        for (int c = 0; c < 3; c++) a.out[3 * src + c] = (e[c] * m[c]) * a.sp;
+        return;
+    }
+    guides[i] = make_double2(f1.y / a.sp, f2.x / a.sp);
+    guides[n + i] = make_double2(f2.y / a.sp, f3.x / a.sp);
+    guides[2 * n + i] = make_double2(alb[0], alb[1]);
+    colour[i] = make_double2(e[0], e[1]);
+    colour[n + i] = make_double2(e[2], alb[2]);
+}
+
+// One iteration at step s. LAST: the result is remodulated and written to a.out in buffer order instead of the other
+// colour plane.
+template <bool LAST>
+__global__ void __launch_bounds__(kDnBlock) dn_atrous(const DenoiseArgs a, const double2 *guides, const double2 *cin, double2 *cout,
+                                                      const uint32_t *inv, uint32_t s, double inv_c) {
+    uint32_t x0, y0;
+    dn_block_origin(a, x0, y0);
+    const uint32_t x = x0 + (threadIdx.x & 63u), y = y0 + (threadIdx.x >> 6);
+    if (x >= a.width || y >= a.height) return;
+    const int64_t W = a.width, H = a.height, step = s;
+    const uint64_t n = (uint64_t)a.width * a.height;
+    const DnPixel p = dn_load(guides, cin, n, (uint64_t)y * a.width + x);
+    double sw = 0.0, sv[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int j = -2; j <= 2; j++) {
+        const int64_t qy = (int64_t)y + (int64_t)j * step;
+#pragma unroll
+        for (int i = -2; i <= 2; i++) {
+            const int64_t qx = (int64_t)x + (int64_t)i * step;
+            if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+            const DnPixel q = dn_load(guides, cin, n, (uint64_t)qy * a.width + (uint64_t)qx);
+            const double dc = dn_dist(p.e, q.e), dn = dn_dist(p.n, q.n), da = dn_dist(p.a, q.a), dz = p.z - q.z;
+            const double den = (((1.0 + dc * inv_c) * (1.0 + dn * a.inv_n)) * (1.0 + (dz * dz) * a.inv_z)) * (1.0 + da * a.inv_a);
+            const double w = (dn_h(j + 2) * dn_h(i + 2)) / den;
+            sw = sw + w;
+#pragma unroll
+            for (int c = 0; c < 3; c++) sv[c] = sv[c] + w * q.e[c];
+        }
+    }
+    const double e[3] = {sv[0] / sw, sv[1] / sw, sv[2] / sw};
+    if (LAST) {
+        const uint64_t dst = (uint64_t)(inv ? inv[y] : y) * a.width + x;
+#pragma unroll
+        for (int c = 0; c < 3; c++) a.out[3 * dst + c] = (e[c] * dn_modulation(a, p.a[c])) * a.sp;
+    } else {
+        const uint64_t i = (uint64_t)y * a.width + x;
+        cout[i] = make_double2(e[0], e[1]);
+        cout[n + i] = make_double2(e[2], p.a[2]);
+    }
+}
+
+} // namespace
+
+DenoiseLayout denoise_layout(uint32_t width, uint32_t height) {
+    const uint64_t n = (uint64_t)width * height;
+    DenoiseLayout l;
+    l.guides = 0;
+    l.colour[0] = 3 * n * sizeof(double2);
+    l.colour[1] = l.colour[0] + 2 * n * sizeof(double2);
+    l.inv_rows = l.colour[1] + 2 * n * sizeof(double2);
+    l.bad_rows = l.inv_rows + ((uint64_t)height * sizeof(uint32_t) + 15u) / 16u * 16u;
+    l.bytes = l.bad_rows + 16u;
+    return l;
+}
+
+hipError_t launch_denoise_rows(const DenoiseArgs &a, hipStream_t stream) {
+    const DenoiseLayout l = denoise_layout(a.width, a.height);
+    hipLaunchKernelGGL(dn_rows, dim3(1), dim3(1024), 0, stream, a.rows, a.height, reinterpret_cast<uint32_t *>(a.ws + l.inv_rows),
+                       reinterpret_cast<uint32_t *>(a.ws + l.bad_rows));
+    return hipGetLastError();
+}
+
+hipError_t launch_denoise(const DenoiseArgs &a, uint32_t n_iter, const double *inv_c, hipStream_t stream) {
+    const DenoiseLayout l = denoise_layout(a.width, a.height);
+    double2 *const guides = reinterpret_cast<double2 *>(a.ws + l.guides);
+    double2 *const colour[2] = {reinterpret_cast<double2 *>(a.ws + l.colour[0]), reinterpret_cast<double2 *>(a.ws + l.colour[1])};
+    const uint32_t *const inv = a.rows ? reinterpret_cast<const uint32_t *>(a.ws + l.inv_rows) : nullptr;
+    const dim3 grid((a.width + 63u) / 64u * ((a.height + 3u) / 4u)), block(kDnBlock);
+    hipLaunchKernelGGL(dn_prepare, grid, block, 0, stream, a, guides, colour[0], inv, n_iter == 0);
+    hipError_t e = hipGetLastError();
+    for (uint32_t k = 0; k < n_iter && e == hipSuccess; k++) {
+        const uint32_t s = 1u << k;
+        hipLaunchKernelGGL(k + 1 == n_iter ? dn_atrous<true> : dn_atrous<false>, grid, block, 0, stream, a, guides, colour[k & 1u], colour[~k & 1u],
+                           inv, s, inv_c[k]);
+        e = hipGetLastError();
+    }
+    return e;
+}
+
+} // namespace rt2022

@@ -259,6 +259,33 @@ struct FeatureArgs {
 };
 hipError_t launch_features(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, hipStream_t stream);
 
+// ---- edge-avoiding denoiser (pt_denoise.hip, rt_denoise*) ----------------------------
+// Where the pieces of the caller's workspace lie (byte offsets, each a multiple of 16) — the one place that knows.
+struct DenoiseLayout {
+    uint64_t guides;                   // 3 planes of n_pixels double2: {n0, n1} {n2, z} {a0, a1}, image order
+    uint64_t colour[2];                // ping-pong, each 2 planes of n_pixels double2: {e0, e1} {e2, a2}
+    uint64_t inv_rows;                 // height x uint32: image row -> buffer row
+    uint64_t bad_rows;                 // one uint32: bad or repeated row ids of the call's list
+    uint64_t bytes;
+};
+DenoiseLayout denoise_layout(uint32_t width, uint32_t height);
+struct DenoiseArgs {
+    uint32_t width, height;
+    double sp;                         // (double)spp
+    double inv_n, inv_z, inv_a;        // 1 / sigma^2 of normal, depth, albedo
+    double albedo_floor;
+    bool demodulate;
+    const double *sum;                 // device: the render's sums, buffer order
+    const rt_feature *feat;            // device, 16-byte aligned, buffer order
+    const uint32_t *rows;              // device: buffer row -> image row (null: the identity)
+    double *out;                       // device: the filtered sums, buffer order (may be `sum`)
+    char *ws;                          // the workspace, 16-byte aligned
+};
+// The row kernel on a.rows (not null): the inverse map and the count of bad ids, both in the workspace.
+hipError_t launch_denoise_rows(const DenoiseArgs &a, hipStream_t stream);
+// prepare + n_iter a-trous passes; inv_c[k] = 1 / sigma_k^2.
+hipError_t launch_denoise(const DenoiseArgs &a, uint32_t n_iter, const double *inv_c, hipStream_t stream);
+
 // Launchers (pt_kernel.hip). `stack_need` = entries the scene needs (host-computed).
 hipError_t launch_render(const SceneDev &scene, const RenderArgs &args, uint32_t stack_need, bool counters,
                          int n_blocks_hint, hipStream_t stream);

@@ -786,6 +786,56 @@ void check_radiance(const rt_scene *scene, const void *rays, uint64_t n_rays, co
     RT_REQUIRE(scene->engine == 1, RT_ERR_UNSUPPORTED, w + ": only the wavefront engine traces caller rays (rt_debug_set_engine)");
 }
 
+// What is wrong with the parameters of rt_denoise* (null: nothing) — rt_denoise_workspace_bytes answers 0 to the same faults.
+const char *denoise_params_fault(const rt_denoise_params *p) {
+    if (!p) return "null params";
+    if (p->width == 0 || p->height == 0) return "empty image (width or height is 0)";
+    if (p->spp == 0) return "spp is 0";
+    if (p->n_iter > RT_DENOISE_MAX_ITER) return "n_iter > RT_DENOISE_MAX_ITER";
+    for (double s : {p->sigma_color, p->sigma_normal, p->sigma_depth, p->sigma_albedo})
+        if (!(s > 0.0)) return "a sigma is <= 0 or NaN";
+    if (!(p->albedo_floor > 0.0) || std::isinf(p->albedo_floor)) return "albedo_floor is <= 0, NaN or infinite";
+    if (p->flags & ~RT_DENOISE_NO_DEMODULATE) return "flag bits other than RT_DENOISE_NO_DEMODULATE";
+    if ((uint64_t)p->width * p->height > RT_DENOISE_MAX_PIXELS) return "width * height > RT_DENOISE_MAX_PIXELS";
+    return nullptr;
+}
+
+void check_denoise(const double *sum, const rt_feature *feat, const rt_denoise_params *p, const double *out, const std::string &w) {
+    const char *fault = denoise_params_fault(p);
+    RT_REQUIRE(!fault, RT_ERR_INVALID, w + ": " + (fault ? fault : ""));
+    RT_REQUIRE(sum && feat && out, RT_ERR_INVALID, w + ": null sums, features or output");
+}
+
+// Enqueue one denoise on `stream`: device buffers, the arguments checked. `check_rows`: the row list came from the caller's
+// HBM — its fault count is read behind one synchronisation of the stream before anything that writes the output is enqueued.
+void run_denoise(const double *d_sum, const rt_feature *d_feat, const uint32_t *d_rows, const rt_denoise_params *p, double *d_out,
+                 char *d_ws, hipStream_t stream, bool check_rows, const std::string &w) {
+    DenoiseArgs a{};
+    a.width = p->width; a.height = p->height;
+    a.sp = (double)p->spp;
+    a.inv_n = 1.0 / (p->sigma_normal * p->sigma_normal);
+    a.inv_z = 1.0 / (p->sigma_depth * p->sigma_depth);
+    a.inv_a = 1.0 / (p->sigma_albedo * p->sigma_albedo);
+    a.albedo_floor = p->albedo_floor;
+    a.demodulate = !(p->flags & RT_DENOISE_NO_DEMODULATE);
+    a.sum = d_sum; a.feat = d_feat; a.rows = d_rows; a.out = d_out; a.ws = d_ws;
+    double inv_c[RT_DENOISE_MAX_ITER];
+    for (uint32_t k = 0; k < p->n_iter; k++) {
+        const double sigma_k = std::ldexp(p->sigma_color, -(int)k);
+        inv_c[k] = 1.0 / (sigma_k * sigma_k);
+    }
+    if (d_rows) {
+        RT_HIP(launch_denoise_rows(a, stream));
+        if (check_rows) {
+            uint32_t bad = 0;
+            RT_HIP(hipMemcpyAsync(&bad, d_ws + denoise_layout(p->width, p->height).bad_rows, sizeof bad, hipMemcpyDeviceToHost, stream));
+            RT_HIP(hipStreamSynchronize(stream));
+            RT_REQUIRE(bad == 0, RT_ERR_INVALID, w + ": row_ids is not a permutation of the image's rows");
+        }
+    }
+    RT_HIP(launch_denoise(a, p->n_iter, inv_c, stream));
+}
+
 void finish(rt_scene *sc, hipStream_t stream) {
     Workspace &w = workspace_for(sc, stream);
     RT_HIP(hipStreamSynchronize(stream));
@@ -1173,6 +1223,59 @@ int rt_features_device(rt_scene *scene, const rt_camera *cam, const rt_params *p
         }
         DeviceGuard guard(scene->device);
         run_features(scene, cam, params, params->row_ids, d_out_features, (hipStream_t)hip_stream, stats, true, "rt_features_device");
+        return RT_OK;
+    });
+}
+
+uint64_t rt_denoise_workspace_bytes(const rt_denoise_params *p) {
+    return denoise_params_fault(p) ? 0 : denoise_layout(p->width, p->height).bytes;
+}
+
+int rt_denoise_device(const double *d_rgb_sum, const rt_feature *d_features, const uint32_t *d_row_ids, const rt_denoise_params *p,
+                      double *d_out_rgb_sum, void *d_workspace, void *hip_stream) {
+    return guarded([&]() -> int {
+        const std::string w("rt_denoise_device");
+        check_denoise(d_rgb_sum, d_features, p, d_out_rgb_sum, w);
+        RT_REQUIRE(d_workspace, RT_ERR_INVALID, w + ": null workspace");
+        RT_REQUIRE(!(((uintptr_t)d_rgb_sum | (uintptr_t)d_features | (uintptr_t)d_out_rgb_sum | (uintptr_t)d_workspace) & 15u), RT_ERR_INVALID,
+                   w + ": the buffers and the workspace must be 16-byte aligned");
+        RT_REQUIRE(!((uintptr_t)d_row_ids & 3u), RT_ERR_INVALID, w + ": row_ids must be 4-byte aligned");
+        run_denoise(d_rgb_sum, d_features, d_row_ids, p, d_out_rgb_sum, (char *)d_workspace, (hipStream_t)hip_stream, true, w);
+        return RT_OK;
+    });
+}
+
+int rt_denoise(const double *rgb_sum, const rt_feature *features, const uint32_t *row_ids, const rt_denoise_params *p,
+               double *out_rgb_sum, double *ms) {
+    return guarded([&]() -> int {
+        const std::string w("rt_denoise");
+        check_denoise(rgb_sum, features, p, out_rgb_sum, w);
+        if (row_ids) {                                         // a permutation of [0, height)?
+            std::vector<char> seen(p->height, 0);
+            for (uint32_t i = 0; i < p->height; i++) {
+                RT_REQUIRE(row_ids[i] < p->height && !seen[row_ids[i]], RT_ERR_INVALID, w + ": row_ids is not a permutation of the image's rows");
+                seen[row_ids[i]] = 1;
+            }
+        }
+        const uint64_t n = (uint64_t)p->width * p->height;
+        DeviceBuf<double> d_sum(3 * n);                        // (filtered in place)
+        DeviceBuf<rt_feature> d_feat(n);
+        DeviceBuf<uint32_t> d_rows(row_ids ? p->height : 0);
+        DeviceBuf<char> d_ws(denoise_layout(p->width, p->height).bytes);
+        Event ev0{hipEventDefault}, ev1{hipEventDefault};
+        RT_HIP(hipMemcpy(d_sum, rgb_sum, 3 * n * sizeof(double), hipMemcpyHostToDevice));
+        RT_HIP(hipMemcpy(d_feat, features, n * sizeof(rt_feature), hipMemcpyHostToDevice));
+        if (row_ids) RT_HIP(hipMemcpy(d_rows, row_ids, p->height * sizeof(uint32_t), hipMemcpyHostToDevice));
+        RT_HIP(hipEventRecord(ev0, nullptr));
+        run_denoise(d_sum, d_feat, row_ids ? d_rows.p : nullptr, p, d_sum, d_ws, nullptr, false, w);
+        RT_HIP(hipEventRecord(ev1, nullptr));
+        RT_HIP(hipStreamSynchronize(nullptr));
+        RT_HIP(hipMemcpy(out_rgb_sum, d_sum, 3 * n * sizeof(double), hipMemcpyDeviceToHost));
+        if (ms) {
+            float t = 0.f;
+            RT_HIP(hipEventElapsedTime(&t, ev0, ev1));
+            *ms = (double)t;
+        }
         return RT_OK;
     });
 }

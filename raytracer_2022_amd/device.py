@@ -53,6 +53,52 @@ def radiance_params(spp=1, background=(0.0, 0.0, 0.0), t_min=0.001, max_depth=50
     return p
 
 
+def denoise_params(width, height, spp, n_iter=5, sigma_color=1.0, sigma_normal=0.3, sigma_depth=np.inf, sigma_albedo=0.3,
+                   albedo_floor=1e-3, demodulate=True):
+    """rt_denoise_params: the image, the divisor of the sums, the a-trous iterations and the edge-stopping sigmas (+inf
+    switches a term off); demodulate=False sets RT_DENOISE_NO_DEMODULATE."""
+    p = F.rt_denoise_params()
+    p.width, p.height, p.spp, p.n_iter = width, height, spp, n_iter
+    p.sigma_color, p.sigma_normal, p.sigma_depth, p.sigma_albedo = sigma_color, sigma_normal, sigma_depth, sigma_albedo
+    p.albedo_floor = albedo_floor
+    p.flags = 0 if demodulate else F.RT_DENOISE_NO_DEMODULATE
+    return p
+
+
+def denoise_workspace_bytes(params):
+    """rt_denoise_workspace_bytes: device bytes denoise_device needs for params' image (0: invalid params)."""
+    return int(F.lib().rt_denoise_workspace_bytes(C.byref(params)))
+
+
+def denoise(rgb_sum, features, params, row_ids=None, want_ms=False):
+    """rt_denoise with host buffers: a render's sums (height, width, 3) and its FEATURE_DTYPE records (height, width), both
+    in the order of `row_ids` (None: image order; else the frame's row list, a permutation of the image's rows) -> the
+    filtered sums, same shape and order [, device ms]."""
+    s = np.ascontiguousarray(rgb_sum, dtype=np.float64)
+    f = np.ascontiguousarray(features, dtype=F.FEATURE_DTYPE)
+    n = params.width * params.height
+    if s.size != 3 * n or f.size != n:
+        raise ValueError("rgb_sum and features must hold width * height pixels")
+    rows = None
+    if row_ids is not None:
+        rows = np.ascontiguousarray(row_ids, dtype=np.uint32)
+        if rows.size != params.height:
+            raise ValueError("row_ids must hold one entry per image row")
+    out = np.empty_like(s)
+    ms = C.c_double()
+    F.check(F.lib().rt_denoise(s.ctypes.data, f.ctypes.data, rows.ctypes.data if rows is not None else None, C.byref(params),
+                               out.ctypes.data, C.byref(ms)))
+    return (out, ms.value) if want_ms else out
+
+
+def denoise_device(d_rgb_sum_ptr, d_features_ptr, params, d_out_ptr, d_workspace_ptr, d_row_ids_ptr=None, stream_ptr=None):
+    """rt_denoise_device: device pointers in (sums, rt_feature records, room for the filtered sums — it may be the input —
+    and denoise_workspace_bytes(params) bytes of workspace, all 16-byte aligned; `height` row ids or None), enqueued on
+    `stream_ptr` (hipStream_t as int). With no row list the call does not synchronise."""
+    F.check(F.lib().rt_denoise_device(C.c_void_p(d_rgb_sum_ptr), C.c_void_p(d_features_ptr), C.c_void_p(d_row_ids_ptr or 0),
+                                      C.byref(params), C.c_void_p(d_out_ptr), C.c_void_p(d_workspace_ptr), C.c_void_p(stream_ptr or 0)))
+
+
 class DeviceScene:
     """rt_scene: the flattened scene copied into HBM on the current HIP device."""
 

@@ -1,0 +1,311 @@
+"""Edge-avoiding denoiser (rt_denoise / rt_denoise_device) against a numpy restatement of its definition, bit for bit.
+
+`restate` below is include/rt2022.h's definition once more: the 25 taps one after the other in the header's order, the
+pixels of a tap vectorised, a skipped tap through np.where. numpy's element-wise + - * / on float64 are the IEEE
+operations and nothing is fused, so the kernels (built with -ffp-contract=off) must give the same doubles. Every comparison
+is on the uint64 view, the NaN patterns first."""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+
+from raytracer_2022_amd import _ffi as F
+
+pytestmark = pytest.mark.gpu
+
+H5 = [1.0 / 16.0, 1.0 / 4.0, 3.0 / 8.0, 1.0 / 4.0, 1.0 / 16.0]
+
+
+@pytest.fixture(scope="module", autouse=True)
+def torch_first():
+    """Bring torch's HIP context up before the library's first call, as the other GPU test modules do."""
+    import torch
+    assert torch.cuda.is_available(), "gpu tests need a GPU: the HIP path has no fallback"
+    torch.zeros(1, device="cuda")
+
+
+def dist(p, q):
+    d0, d1, d2 = p[..., 0] - q[..., 0], p[..., 1] - q[..., 1], p[..., 2] - q[..., 2]
+    return (d0 * d0 + d1 * d1) + d2 * d2
+
+
+def restate(sums, feat, p, rows=None):
+    """The definition in numpy. sums (H, W, 3) and feat (H, W) FEATURE_DTYPE in buffer order -> filtered sums, buffer order."""
+    H, W = p.height, p.width
+    sums = np.asarray(sums, dtype=np.float64).reshape(H, W, 3)
+    feat = np.asarray(feat).reshape(H, W)
+    if rows is not None:                                   # buffer row i is image row rows[i]
+        inv = np.empty(H, dtype=np.int64)
+        inv[np.asarray(rows, dtype=np.int64)] = np.arange(H)
+        sums, feat = sums[inv], feat[inv]
+    one = np.float64(1.0)
+    with np.errstate(all="ignore"):
+        sp = np.float64(p.spp)
+        c = np.where(np.isnan(sums), np.float64(0.0), sums) / sp
+        a, n, z = feat["albedo"] / sp, feat["normal"] / sp, feat["depth"] / sp
+        floor = np.float64(p.albedo_floor)
+        m = np.ones_like(a) if p.flags & F.RT_DENOISE_NO_DEMODULATE else np.where(a > floor, a, floor)
+        e = c / m
+        inv_n = one / (np.float64(p.sigma_normal) * np.float64(p.sigma_normal))
+        inv_z = one / (np.float64(p.sigma_depth) * np.float64(p.sigma_depth))
+        inv_a = one / (np.float64(p.sigma_albedo) * np.float64(p.sigma_albedo))
+        ys, xs = np.meshgrid(np.arange(H, dtype=np.int64), np.arange(W, dtype=np.int64), indexing="ij")
+        for k in range(p.n_iter):
+            s = 1 << k
+            sigma_k = np.float64(p.sigma_color) * np.float64(2.0 ** -k)
+            inv_c = one / (sigma_k * sigma_k)
+            sw, sv = np.zeros((H, W)), np.zeros((H, W, 3))
+            for j in range(-2, 3):
+                for i in range(-2, 3):
+                    qx, qy = xs + i * s, ys + j * s
+                    ok = (qx >= 0) & (qx < W) & (qy >= 0) & (qy < H)
+                    qx, qy = np.clip(qx, 0, W - 1), np.clip(qy, 0, H - 1)
+                    dc, dn, da = dist(e, e[qy, qx]), dist(n, n[qy, qx]), dist(a, a[qy, qx])
+                    dz = z - z[qy, qx]
+                    den = (((one + dc * inv_c) * (one + dn * inv_n)) * (one + (dz * dz) * inv_z)) * (one + da * inv_a)
+                    w = np.float64(H5[j + 2] * H5[i + 2]) / den
+                    sw = np.where(ok, sw + w, sw)
+                    sv = np.where(ok[..., None], sv + w[..., None] * e[qy, qx], sv)
+            e = sv / sw[..., None]
+        out = (e * m) * sp
+    return out if rows is None else out[np.asarray(rows, dtype=np.int64)]
+
+
+def bits(a):
+    v = np.ascontiguousarray(a, dtype=np.float64)
+    return np.where(np.isnan(v), np.float64(0), v).view(np.uint64), np.isnan(v)
+
+
+def assert_same_bits(got, ref, what=""):
+    (gb, gn), (rb, rn) = bits(got), bits(ref)
+    assert gb.shape == rb.shape, what
+    assert np.array_equal(gn, rn), (what, "NaN pattern")
+    bad = np.argwhere(gb != rb)
+    assert len(bad) == 0, (what, "first differing doubles", bad[:5].tolist(), len(bad))
+
+
+def buffers(W, H, spp=4, seed=1, hostile=True, nan_albedo=True):
+    """Random sums and feature records; hostile: NaN radiance components, zero and NaN albedo, all-zero "miss" records, 1e30s."""
+    g = np.random.default_rng(seed)
+    sums = g.uniform(0.0, 2.0 * spp, (H, W, 3))
+    feat = np.zeros((H, W), dtype=F.FEATURE_DTYPE)
+    feat["albedo"] = g.uniform(0.0, 1.0 * spp, (H, W, 3))
+    nrm = g.normal(size=(H, W, 3))
+    feat["normal"] = nrm / np.linalg.norm(nrm, axis=-1, keepdims=True) * spp
+    feat["depth"] = g.uniform(1.0, 20.0, (H, W)) * spp
+    feat["hits"] = spp
+    # a few flat regions, so that some weights are large
+    feat["albedo"][: H // 2, : W // 2] = (0.5 * spp, 0.25 * spp, 0.125 * spp)
+    feat["normal"][: H // 2] = (0.0, 0.0, 1.0 * spp)
+    if hostile:
+        pick = lambda frac, shape: g.random(shape) < frac
+        sums[pick(0.03, (H, W, 3))] = np.nan
+        sums[pick(0.01, (H, W, 3))] = 1e30
+        sums[pick(0.01, (H, W, 3))] = -3.0
+        feat["albedo"][pick(0.03, (H, W))] = 0.0
+        feat["albedo"][pick(0.01, (H, W, 3))] = 1e30
+        feat["depth"][pick(0.01, (H, W))] = 1e30
+        if nan_albedo:
+            feat["albedo"][pick(0.004, (H, W, 3))] = np.nan
+        miss = pick(0.05, (H, W))
+        feat.view(np.float64).reshape(H, W, 8)[miss] = 0.0
+    return sums, feat
+
+
+def check(rt, sums, feat, p, rows=None, what=""):
+    got = rt.denoise(sums, feat, p, row_ids=rows)
+    ref = restate(sums, feat, p, rows)
+    assert got.shape == np.asarray(sums).shape
+    assert_same_bits(got, ref, what)
+    return got
+
+
+# ---- hostile buffers ----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n_iter, nan_albedo", [(5, True), (5, False), (1, True), (2, True)])
+def test_hostile_buffers(rt, n_iter, nan_albedo):
+    """67 x 35: no multiple of the 64 x 4 workgroup, several workgroups each way. A NaN guide spreads to every pixel whose
+    footprint reaches it — after five iterations that is the whole image, so the same buffers are also run without NaN
+    albedo (finite results everywhere NaN radiance does not matter) and at one and two iterations (NaN islands)."""
+    W, H = 67, 35
+    sums, feat = buffers(W, H, hostile=True, nan_albedo=nan_albedo)
+    got = check(rt, sums, feat, rt.denoise_params(W, H, 4, n_iter=n_iter))
+    if not nan_albedo:
+        assert np.isfinite(got).all()
+    if n_iter == 1 and nan_albedo:
+        assert 0 < np.isnan(got).sum() < got.size
+
+
+# ---- footprint larger than the image ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("W, H", [(1, 1), (1, 9), (9, 1), (5, 3)])
+def test_footprint_larger_than_the_image(rt, W, H):
+    sums, feat = buffers(W, H, seed=W * 16 + H, hostile=False)
+    got = check(rt, sums, feat, rt.denoise_params(W, H, 4, n_iter=4))
+    if (W, H) == (1, 1):                                   # the centre tap alone: e / 1 * m * sp, the input to rounding
+        assert np.allclose(got, sums, rtol=1e-14)
+    big = rt.denoise_params(W, H, 4, n_iter=F.RT_DENOISE_MAX_ITER)         # steps up to 2^15
+    check(rt, sums, feat, big, what="16 iterations")
+
+
+# ---- switches --------------------------------------------------------------------------------------------------------------
+INF = math.inf
+SWITCHES = {
+    "n_iter 0": dict(n_iter=0), "n_iter 1": dict(n_iter=1), "no demodulation": dict(demodulate=False),
+    "colour off": dict(sigma_color=INF), "normal off": dict(sigma_normal=INF), "depth off": dict(sigma_depth=INF),
+    "depth on": dict(sigma_depth=2.0), "depth alone off": dict(sigma_depth=INF, sigma_color=0.5, sigma_normal=0.2, sigma_albedo=0.2),
+    "albedo off": dict(sigma_albedo=INF), "all off": dict(sigma_color=INF, sigma_normal=INF, sigma_depth=INF, sigma_albedo=INF),
+    "tight": dict(sigma_color=0.3, sigma_normal=0.05, sigma_depth=0.1, sigma_albedo=0.01, albedo_floor=0.3),
+    "spp 1": dict(spp=1), "spp 7, 3 iterations": dict(spp=7, n_iter=3),
+}
+
+
+@pytest.mark.parametrize("name", list(SWITCHES))
+def test_switches(rt, name):
+    W, H = 70, 9
+    kw = dict(SWITCHES[name])
+    spp = kw.pop("spp", 4)
+    sums, feat = buffers(W, H, spp=spp, seed=5, hostile=True, nan_albedo=False)
+    p = rt.denoise_params(W, H, spp, **kw)
+    got = check(rt, sums, feat, p, what=name)
+    if name == "n_iter 0":                                 # (c / m) * m * sp: the input to rounding, NaN -> 0
+        assert np.allclose(got, np.where(np.isnan(sums), 0.0, sums), rtol=1e-14)
+    if name == "all off":                                  # the plain B3 spline: a convex combination of the demodulated inputs
+        clean, cfeat = buffers(W, H, seed=5, hostile=False)
+        flat = check(rt, clean, cfeat, rt.denoise_params(W, H, 4, demodulate=False, **kw))
+        assert flat.min() >= clean.min() - 1e-9 and flat.max() <= clean.max() + 1e-9
+
+
+# ---- row lists -------------------------------------------------------------------------------------------------------------
+def test_shuffled_rows_give_the_image_order_result_permuted(rt):
+    W, H = 67, 35
+    sums, feat = buffers(W, H, seed=9, hostile=True, nan_albedo=False)
+    p = rt.denoise_params(W, H, 4)
+    image_order = check(rt, sums, feat, p)
+    rows = rt.shuffled_rows(H, 2022)
+    assert sorted(rows.tolist()) == list(range(H)) and rows.tolist() != list(range(H))
+    inv = np.argsort(rows)                                 # buffers written in `rows` order: buffer row i is image row rows[i]
+    got = check(rt, sums[rows], feat[rows], p, rows=rows)
+    assert_same_bits(got[inv], image_order, "shuffled rows")
+    assert_same_bits(rt.denoise(sums[rows], feat[rows], rt.denoise_params(W, H, 4, n_iter=0), row_ids=rows)[inv],
+                     restate(sums, feat, rt.denoise_params(W, H, 4, n_iter=0)), "shuffled rows, no iteration")
+
+
+def torch_buffers(sums, feat, p, rt, fill=None):
+    import torch
+    d_sums = torch.from_numpy(np.ascontiguousarray(sums)).cuda()
+    d_feat = torch.from_numpy(np.ascontiguousarray(feat).view(np.float64).reshape(-1)).cuda()
+    d_out = torch.full((p.height, p.width, 3), 7.0, dtype=torch.float64, device="cuda")
+    n_ws = rt.denoise_workspace_bytes(p)
+    d_ws = torch.zeros(n_ws, dtype=torch.uint8, device="cuda") if fill is None else torch.full((n_ws,), fill, dtype=torch.uint8, device="cuda")
+    return d_sums, d_feat, d_out, d_ws
+
+
+def test_bad_row_lists_are_refused_with_the_output_untouched(rt):
+    import torch
+    W, H = 12, 10
+    sums, feat = buffers(W, H, hostile=False)
+    for n_iter in (0, 3):
+        p = rt.denoise_params(W, H, 4, n_iter=n_iter)
+        d_sums, d_feat, d_out, d_ws = torch_buffers(sums, feat, p, rt)
+        for fault in ("repeated", "out of range", "huge"):
+            rows = np.arange(H, dtype=np.uint32)[::-1].copy()
+            rows[3] = {"repeated": rows[7], "out of range": H, "huge": 0xFFFFFFFF}[fault]
+            out = np.full((H, W, 3), 7.0)
+            with pytest.raises(rt.RtError) as e:
+                rt.denoise(sums, feat, p, row_ids=rows)
+            assert e.value.code == F.RT_ERR_INVALID and "not a permutation" in str(e.value), fault
+            d_rows = torch.from_numpy(rows.view(np.int32)).cuda()
+            torch.cuda.synchronize()
+            with pytest.raises(rt.RtError) as e:
+                rt.denoise_device(d_sums.data_ptr(), d_feat.data_ptr(), p, d_out.data_ptr(), d_ws.data_ptr(), d_row_ids_ptr=d_rows.data_ptr())
+            assert e.value.code == F.RT_ERR_INVALID and "not a permutation" in str(e.value), fault
+            torch.cuda.synchronize()
+            assert np.array_equal(d_out.cpu().numpy(), out), (fault, "the output was written")
+        # and the good list on the same workspace afterwards
+        rows = np.arange(H, dtype=np.uint32)[::-1].copy()
+        d_rows = torch.from_numpy(rows.view(np.int32)).cuda()
+        torch.cuda.synchronize()
+        rt.denoise_device(d_sums.data_ptr(), d_feat.data_ptr(), p, d_out.data_ptr(), d_ws.data_ptr(), d_row_ids_ptr=d_rows.data_ptr())
+        torch.cuda.synchronize()
+        assert_same_bits(d_out.cpu().numpy(), restate(sums, feat, p, rows), "good rows after bad ones")
+
+
+# ---- aliasing and reuse ----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n_iter", [0, 1, 4])
+def test_aliasing_workspace_reuse_and_poisoned_workspace(rt, n_iter):
+    import torch
+    W, H = 67, 35
+    sums, feat = buffers(W, H, seed=3, hostile=True, nan_albedo=False)
+    rows = rt.shuffled_rows(H, 7)
+    p = rt.denoise_params(W, H, 4, n_iter=n_iter)
+    ref = restate(sums, feat, p, rows)
+    d_sums, d_feat, d_out, d_ws = torch_buffers(sums, feat, p, rt, fill=0xFF)     # a workspace of 0xFF bytes
+    d_rows = torch.from_numpy(rows.view(np.int32)).cuda()
+    torch.cuda.synchronize()
+    call = lambda out, ws, r=d_rows: rt.denoise_device(d_sums.data_ptr(), d_feat.data_ptr(), p, out.data_ptr(), ws.data_ptr(),
+                                                       d_row_ids_ptr=r.data_ptr() if r is not None else None)
+    call(d_out, d_ws)
+    torch.cuda.synchronize()
+    assert_same_bits(d_out.cpu().numpy(), ref, "poisoned workspace")
+    d_out.fill_(7.0)
+    call(d_out, d_ws)                                      # the same workspace again
+    torch.cuda.synchronize()
+    assert_same_bits(d_out.cpu().numpy(), ref, "workspace reused")
+    # ... and with no row list after a call with one (the inverse map of the last call is still in the workspace)
+    d_out.fill_(7.0)
+    call(d_out, d_ws, None)
+    torch.cuda.synchronize()
+    assert_same_bits(d_out.cpu().numpy(), restate(sums, feat, p), "workspace reused without rows")
+    call(d_sums, d_ws)                                     # in place: the output is the input
+    torch.cuda.synchronize()
+    assert_same_bits(d_sums.cpu().numpy(), ref, "output aliasing the input")
+
+
+# ---- torch buffers, a stream of the caller's, the tone map behind it ------------------------------------------------------
+def test_device_form_on_torch_buffers_then_tonemap_on_the_same_stream(rt):
+    import torch
+    W, H, spp = 130, 21, 4
+    sums, feat = buffers(W, H, spp=spp, seed=11, hostile=False)
+    sums[np.random.default_rng(2).random((H, W, 3)) < 0.05] = np.nan
+    p = rt.denoise_params(W, H, spp)
+    d_sums, d_feat, d_out, d_ws = torch_buffers(sums, feat, p, rt)
+    d_u8 = torch.zeros((H, W, 3), dtype=torch.uint8, device="cuda")
+    stream = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    with torch.cuda.stream(stream):
+        rt.denoise_device(d_sums.data_ptr(), d_feat.data_ptr(), p, d_out.data_ptr(), d_ws.data_ptr(), stream_ptr=stream.cuda_stream)
+        F.check(rt.lib().rt_tonemap_device(C.c_void_p(d_out.data_ptr()), W * H, spp, C.c_void_p(d_u8.data_ptr()), C.c_void_p(stream.cuda_stream)))
+    stream.synchronize()
+    ref = restate(sums, feat, p)
+    assert_same_bits(d_out.cpu().numpy(), ref, "device form")
+    assert np.array_equal(d_u8.cpu().numpy(), rt.write_color(ref, spp))
+    assert np.array_equal(d_sums.cpu().numpy().view(np.uint64), sums.view(np.uint64))      # the input is read only
+
+
+# ---- end to end ------------------------------------------------------------------------------------------------------------
+def display(sums, spp):
+    c = np.where(np.isnan(sums), 0.0, sums) / spp
+    return np.sqrt(np.clip(c, 0.0, 0.999))
+
+
+@pytest.mark.parametrize("name, W, H", [("cornell_box", 48, 48), ("final_scene", 48, 48), ("random_scene", 60, 40)])
+def test_render_features_denoise_end_to_end(rt, name, W, H):
+    """4 spp at seed 2022, rows shuffled, the issue's three views: the denoised sums are the restatement's bit for bit, and
+    with the default parameters the frame is closer to a 512 spp render (seed 7) than the noisy one: MSE of the display
+    value sqrt(clip(c, 0, 0.999)), ratio < 1 (the CPU oracle's renders gave 0.13, 0.46 and 0.62)."""
+    spp = 4
+    s = rt.HostScene(name, seed=2022)
+    cam, bg = s.default_view(W / H)
+    dev = rt.DeviceScene(s.desc)
+    rows = rt.shuffled_rows(H, 2022)
+    params = rt.make_params(W, H, spp, 50, bg, seed=2022)
+    noisy = dev.render(cam, params, rows)
+    feat = dev.features(cam, params, rows)
+    p = rt.denoise_params(W, H, spp)
+    got = check(rt, noisy, feat, p, rows=rows, what=name)
+    reference = dev.render(cam, rt.make_params(W, H, 512, 50, bg, seed=7), rows)
+    target = display(reference, 512)
+    mse_noisy = float(np.mean((display(noisy, spp) - target) ** 2))
+    mse_denoised = float(np.mean((display(got, spp) - target) ** 2))
+    print("%s %dx%d: noisy MSE %.5f, denoised MSE %.5f, ratio %.3f" % (name, W, H, mse_noisy, mse_denoised, mse_denoised / mse_noisy))
+    assert mse_denoised < mse_noisy

@@ -1,0 +1,140 @@
+"""Edge-avoiding denoiser (rt_denoise*): the parameter block's layout, the bindings, the workspace size and argument checking.
+No compute calls: runs without a GPU (every RT_ERR_INVALID case returns before any device call)."""
+import ctypes as C
+import math
+import os
+import re
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OFFSETS = {"width": 0, "height": 4, "spp": 8, "n_iter": 12, "sigma_color": 16, "sigma_normal": 24, "sigma_depth": 32,
+           "sigma_albedo": 40, "albedo_floor": 48, "flags": 56, "_pad": 60}
+
+
+def test_params_layout_header_bindings_and_library_agree(rt):
+    from raytracer_2022_amd import _ffi as F
+    assert C.sizeof(F.rt_denoise_params) == 64
+    out = (C.c_uint32 * 8)()
+    n = rt.lib().rtb_denoise_abi_sizes(out, 8)
+    assert n == len(F.DENOISE_ABI_STRUCTS) == 1
+    assert [out[i] for i in range(n)] == [C.sizeof(t) for t in F.DENOISE_ABI_STRUCTS] == [64]
+    assert rt.lib().rtb_denoise_abi_sizes(out, 0) == 1                       # (a size query writes nothing)
+    assert [f[0] for f in F.rt_denoise_params._fields_] == list(OFFSETS)
+    for name, off in OFFSETS.items():
+        assert getattr(F.rt_denoise_params, name).offset == off, name
+    # the header's struct: the same fields in the same order, u32s and doubles as the offsets above imply
+    text = open(os.path.join(ROOT, "include", "rt2022.h")).read()
+    m = re.search(r"typedef struct rt_denoise_params \{(.*?)\} rt_denoise_params;", text, flags=re.S)
+    assert m, "rt_denoise_params is not declared"
+    body = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
+    fields, off = [], 0
+    for ctype, names in re.findall(r"(uint32_t|double)\s+([\w\s,]+);", body):
+        size = 4 if ctype == "uint32_t" else 8
+        for name in [s.strip() for s in names.split(",")]:
+            off = (off + size - 1) // size * size
+            fields.append((name, off))
+            off += size
+    assert fields == list(OFFSETS.items()) and off == 64
+    assert "#define RT_DENOISE_MAX_ITER      16" in text and "#define RT_DENOISE_NO_DEMODULATE 0x1u" in text
+    assert F.RT_DENOISE_MAX_ITER == 16 and F.RT_DENOISE_NO_DEMODULATE == 1
+    assert re.search(r"uint64_t rt_denoise_workspace_bytes\(const rt_denoise_params \*p\);", text)
+    assert re.search(r"int rt_denoise_device\(const double \*d_rgb_sum, const rt_feature \*d_features, const uint32_t \*d_row_ids,\s*"
+                     r"const rt_denoise_params \*p, double \*d_out_rgb_sum, void \*d_workspace, void \*hip_stream\);", text)
+    assert re.search(r"int rt_denoise\(const double \*rgb_sum, const rt_feature \*features, const uint32_t \*row_ids,\s*"
+                     r"const rt_denoise_params \*p, double \*out_rgb_sum, double \*ms\);", text)
+    # the general lists stay as they were, the ABI version too
+    assert F.rt_denoise_params not in F.ABI_STRUCTS and rt.lib().rt_abi_version() == 3
+    # the Python constructor's defaults are the issue's
+    p = rt.denoise_params(7, 5, 4)
+    assert (p.width, p.height, p.spp, p.n_iter, p.flags) == (7, 5, 4, 5, 0)
+    assert (p.sigma_color, p.sigma_normal, p.sigma_albedo, p.albedo_floor) == (1.0, 0.3, 0.3, 1e-3) and p.sigma_depth == math.inf
+    assert rt.denoise_params(7, 5, 4, demodulate=False).flags == F.RT_DENOISE_NO_DEMODULATE
+
+
+def bad_params(rt):
+    """(what, params) for every way a parameter block can be invalid."""
+    from raytracer_2022_amd import _ffi as F
+    cases = []
+    for field in ("width", "height", "spp"):
+        p = rt.denoise_params(8, 6, 4)
+        setattr(p, field, 0)
+        cases.append((field + " = 0", p))
+    cases.append(("n_iter", rt.denoise_params(8, 6, 4, n_iter=F.RT_DENOISE_MAX_ITER + 1)))
+    for field in ("sigma_color", "sigma_normal", "sigma_depth", "sigma_albedo", "albedo_floor"):
+        for v in (0.0, -1.0, math.nan, -math.inf):
+            cases.append(("%s = %r" % (field, v), rt.denoise_params(8, 6, 4, **{field: v})))
+    cases.append(("infinite floor", rt.denoise_params(8, 6, 4, albedo_floor=math.inf)))
+    for bits in (0x2, 0x80000000, 0x3):
+        p = rt.denoise_params(8, 6, 4)
+        p.flags = bits
+        cases.append(("flags %#x" % bits, p))
+    cases.append(("too many pixels", rt.denoise_params(1 << 20, (1 << 16) + 1, 4)))
+    return cases
+
+
+def test_workspace_bytes(rt):
+    from raytracer_2022_amd import _ffi as F
+    sizes = [rt.denoise_workspace_bytes(rt.denoise_params(w, h, 4)) for w, h in ((1, 1), (5, 3), (67, 35), (800, 800), (1 << 16, 1 << 16))]
+    assert all(s > 0 and s % 16 == 0 for s in sizes) and sizes == sorted(set(sizes))
+    # room for ten doubles per pixel at least (the guides and one colour plane) and never absurdly more
+    assert 80 * 800 * 800 <= sizes[3] <= 160 * 800 * 800
+    # n_iter, the sigmas and the flags do not change it; +inf sigmas and n_iter 0 / 16 are valid
+    inf = math.inf
+    p = rt.denoise_params(67, 35, 1, n_iter=0, sigma_color=inf, sigma_normal=inf, sigma_depth=inf, sigma_albedo=inf, demodulate=False)
+    assert rt.denoise_workspace_bytes(p) == sizes[2]
+    assert rt.denoise_workspace_bytes(rt.denoise_params(67, 35, 4, n_iter=F.RT_DENOISE_MAX_ITER)) == sizes[2]
+    assert rt.lib().rt_denoise_workspace_bytes(None) == 0
+    for what, p in bad_params(rt):
+        assert rt.denoise_workspace_bytes(p) == 0, what
+
+
+def test_denoise_arguments_are_checked_before_the_device(rt):
+    """Every RT_ERR_INVALID case of the two entry points, each with a message — on a machine without a GPU too."""
+    from raytracer_2022_amd import _ffi as F
+    L = rt.lib()
+    W, H = 8, 6
+    sums = np.ones((H, W, 3))
+    feat = np.zeros((H, W), dtype=F.FEATURE_DTYPE)
+    out = np.zeros((H, W, 3))
+    good = rt.denoise_params(W, H, 4)
+    err = lambda: L.rt_last_error().decode()
+
+    def host(p, s=sums.ctypes.data, f=feat.ctypes.data, o=out.ctypes.data, rows=None):
+        return L.rt_denoise(s, f, rows, C.byref(p) if p is not None else None, o, None)
+
+    def device(p, s=4096, f=8192, o=16384, ws=32768, rows=None):
+        return L.rt_denoise_device(s, f, rows, C.byref(p) if p is not None else None, o, ws, None)
+
+    for what, p in bad_params(rt):
+        assert host(p) == F.RT_ERR_INVALID and err().startswith("rt_denoise: "), what
+        assert device(p) == F.RT_ERR_INVALID and err().startswith("rt_denoise_device: "), what
+    assert host(rt.denoise_params(W, H, 4, n_iter=17)) == F.RT_ERR_INVALID and "n_iter" in err()
+    assert host(rt.denoise_params(W, H, 4, sigma_depth=-2.0)) == F.RT_ERR_INVALID and "sigma" in err()
+    assert host(rt.denoise_params(W, H, 4, albedo_floor=math.inf)) == F.RT_ERR_INVALID and "albedo_floor" in err()
+    assert device(rt.denoise_params(W, 0, 4)) == F.RT_ERR_INVALID and "empty image" in err()
+    # null params, buffers, workspace
+    assert host(None) == F.RT_ERR_INVALID and "null params" in err()
+    assert device(None) == F.RT_ERR_INVALID and "null params" in err()
+    assert L.rt_denoise(None, None, None, None, None, None) == F.RT_ERR_INVALID
+    assert L.rt_denoise_device(None, None, None, None, None, None, None) == F.RT_ERR_INVALID
+    for kw in ({"s": None}, {"f": None}, {"o": None}):
+        assert host(good, **kw) == F.RT_ERR_INVALID and "null sums, features or output" in err(), kw
+        assert device(good, **kw) == F.RT_ERR_INVALID and "null sums, features or output" in err(), kw
+    assert device(good, ws=None) == F.RT_ERR_INVALID and "null workspace" in err()
+    # misalignment: every device pointer by 16, the rows by 4
+    for kw in ({"s": 4096 + 8}, {"f": 8192 + 8}, {"o": 16384 + 8}, {"ws": 32768 + 4}, {"s": 4096 + 1}):
+        assert device(good, **kw) == F.RT_ERR_INVALID and "16-byte aligned" in err(), kw
+    for off in (1, 2, 3):
+        assert device(good, rows=65536 + off) == F.RT_ERR_INVALID and "4-byte aligned" in err()
+    # host rows that are not a permutation of [0, height): a repeated id, an id >= height
+    for bad in ([0, 1, 2, 3, 4, 4], [0, 1, 2, 3, 4, 6], [5, 4, 3, 2, 1, 0xFFFFFFFF]):
+        rows = np.array(bad, dtype=np.uint32)
+        assert host(good, rows=rows.ctypes.data) == F.RT_ERR_INVALID and "not a permutation" in err(), bad
+    assert not out.any()                                                      # nothing was written
+    # the Python wrapper refuses buffers of the wrong size before the library sees them
+    import pytest
+    with pytest.raises(ValueError):
+        rt.denoise(sums[:-1], feat, good)
+    with pytest.raises(ValueError):
+        rt.denoise(sums, feat, good, row_ids=np.arange(H - 1))
