@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from raytracer_2022_amd import _ffi as F
+from trace_scenes import median_split_bvh as _median_split_bvh
 
 pytestmark = pytest.mark.gpu
 
@@ -378,20 +379,6 @@ def test_single_precision_slab_test_on_hostile_spheres(rt, O):
         v2 = dev.trace_variant()
         assert v2["nodes_in_lds"] == 0 and v2["f32_slabs"], (label, v2)
         assert np.array_equal(bits(dev.render(cam, p, rows)), bits(ref)), label
-
-
-def _median_split_bvh(b, leaves):
-    def build(items, axis=0):
-        if len(items) == 1:
-            r, lo, hi = items[0]
-            return b.node(lo, hi, r, r), lo, hi
-        items = sorted(items, key=lambda it: it[1][axis])
-        h = len(items) // 2
-        l, llo, lhi = build(items[:h], (axis + 1) % 3)
-        r, rlo, rhi = build(items[h:], (axis + 1) % 3)
-        lo = tuple(min(a, c_) for a, c_ in zip(llo, rlo)); hi = tuple(max(a, c_) for a, c_ in zip(lhi, rhi))
-        return b.node(lo, hi, l, r), lo, hi
-    return build(leaves)[0]
 
 
 def test_mesh_takes_the_single_precision_records(rt, O):

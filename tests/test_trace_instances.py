@@ -1,0 +1,201 @@
+"""Every traversal-kernel instance a scene can select (wf_trace: 58 instantiations, pt_wavefront.hip), run on a scene built
+to select it (tests/trace_scenes.py) and compared with the CPU oracle bit for bit — pixel sums and counters. Which instance
+runs is asserted first, from a restatement of choose_trace, so a case cannot quietly test a neighbour: this code base has met
+a compiler defect that broke one instance only (tools/hipcc_slp_miscompile.md).
+
+Per case: the timed kernel, the counting kernel, the probe instance (tuning bit 29) and the literal node step (bit 30); the
+megakernel on the shapes that select its two stack sizes; the query and feature kernels on the deep FEAT-7 shapes. Then the
+scene whose movers, media and lights outgrow the small LDS tables of the kernels, and pairs of scenes one node, one sphere or
+one stack entry either side of every threshold of the choice."""
+import numpy as np
+import pytest
+
+import trace_scenes as T
+from raytracer_2022_amd import _ffi as F
+from test_features import check_view
+from test_query import assert_prims_consistent, assert_records_equal, counters, oracle_hits
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module", autouse=True)
+def torch_first():
+    """Bring torch's HIP context up before the library's first call, as the other GPU test modules do."""
+    import torch
+    assert torch.cuda.is_available(), "gpu tests need a GPU: the HIP path has no fallback"
+    torch.zeros(1, device="cuda")
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+def same(a, ref):
+    return np.array_equal(np.isnan(a), np.isnan(ref)) and np.array_equal(bits(a), bits(ref))
+
+
+def assert_variant(dev, d, tuning=T.TUNING):
+    """The library's choice for a timed render == the restated one; → (the restated choice, the stack need read back)."""
+    need = dev.info()["stack_need"]
+    assert need == T.stack_need(d)
+    want = T.expected_variant(d, need, tuning)
+    got = dev.trace_variant()
+    assert got == {k: v for k, v in want.items() if k != "table"}, (want, got)
+    return want, need
+
+
+def device_scene(rt, d, tuning=T.TUNING, engine="wavefront"):
+    dev = rt.DeviceScene(d)
+    dev.set_engine(engine)
+    dev.set_tuning(tuning)
+    return dev
+
+
+# ---- 1. the matrix -------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def matrix_reference(O):
+    """The oracle's render of every matrix case, made once and never written to: case → (scene, pixel sums, counters)."""
+    cache = {}
+
+    def get(case):
+        if case not in cache:
+            feat, shape, sphere_only = case
+            scene = T.make_scene(feat, shape, 1, sphere_only)
+            d, cam, p, rows = scene
+            ref, st = O.render_cpu(d, cam, p, rows, n_threads=8, want_stats=True)
+            ref.setflags(write=False)
+            cache[case] = (scene, ref, st.as_dict())
+        return cache[case]
+    return get
+
+
+@pytest.mark.parametrize("case", T.matrix_cases(), ids=T.case_id)
+def test_instance_matches_the_oracle(rt, matrix_reference, case):
+    """The instance the case selects — asserted — for the timed render; then the counting instance of its stack size (FEAT 7),
+    the probe instance (per FEAT at 22 entries, FEAT 7 at 30 and 64) and the timed one again with the literal node step."""
+    feat, shape, sphere_only = case
+    (d, cam, p, rows), ref, counters_ref = matrix_reference(case)
+    base = T.TUNING | (T.NO_TABLE if shape == "small" else 0)
+    dev = device_scene(rt, d, base)
+    want, need = assert_variant(dev, d, base)
+    table = {"whole": "prims" if sphere_only else "whole", "small": "plain", "mid": "plain", "large": "plain",
+             # a mesh without boxes or media keeps its single-precision node records in the plain kernel: no partial table for it
+             "partial": "plain" if feat in (1, 3) else "partial"}[shape]
+    assert want["table"] == table
+    assert want["stack_entries"] == (16 if table != "plain" else {"mid": 30, "large": 64}.get(shape, 22))
+    assert want["nodes_in_lds"] == {"plain": 0, "partial": T.NODE_CACHE}.get(table, d.n_nodes)
+    assert want["f32_slabs"] == (sphere_only or (table == "plain" and feat in (1, 3))) and want["spheres_in_lds"] == (table == "prims")
+    assert same(dev.render(cam, p, rows), ref), "timed instance"
+    out, st = dev.render(cam, p, rows, want_stats=True)
+    assert st.as_dict() == counters_ref, "counting instance: the device paths took different branches than the oracle's"
+    assert same(out, ref), "counting instance"
+    dev.set_tuning(base | T.PROBE)
+    assert same(dev.render(cam, p, rows), ref), "probe instance"
+    assert dev.pass_timing()["passes"] > 0
+    dev.set_tuning(base | T.LITERAL_STEP)
+    assert same(dev.render(cam, p, rows), ref), "literal node step"
+
+
+MEGA_CASES = [c for c in T.matrix_cases() if c[1] in ("small", "large")]
+
+
+@pytest.mark.parametrize("case", MEGA_CASES, ids=T.case_id)
+def test_megakernel_matches_the_oracle(rt, matrix_reference, case):
+    """pt_megakernel at both its stack sizes (22 entries: `small`; 64: `large`), with and without counters."""
+    (d, cam, p, rows), ref, counters_ref = matrix_reference(case)
+    dev = rt.DeviceScene(d)
+    if T.mega_refuses(d):                                 # (a boundary that is more than one primitive under movers: no case here has one)
+        with pytest.raises(rt.RtError) as e:
+            dev.set_engine("mega")
+        assert e.value.code == F.RT_ERR_UNSUPPORTED
+        return
+    dev.set_engine("mega")
+    need = dev.info()["stack_need"]
+    assert (need > T.STACK_MID) == (case[1] == "large") and (need <= T.STACK_SMALL) == (case[1] == "small")
+    out, st = dev.render(cam, p, rows, want_stats=True)
+    assert st.as_dict() == counters_ref
+    assert same(out, ref)
+    assert same(dev.render(cam, p, rows), ref)
+
+
+@pytest.mark.parametrize("shape", ["small", "mid", "large"])
+def test_query_and_feature_kernels_on_deep_stacks(rt, O, matrix_reference, shape):
+    """rt_intersect and rt_features take their stack size from the same need: FEAT 7 at 22, 30 and 64 entries."""
+    (d, cam, p, rows), _, _ = matrix_reference((7, shape, False))
+    dev = rt.DeviceScene(d)
+    assert T.expected_variant(d, dev.info()["stack_need"], T.NO_TABLE)["stack_entries"] == {"small": 22, "mid": 30, "large": 64}[shape]
+    origins, dirs = T.pinhole_rays(cam, T.W, T.H)
+    g = np.random.default_rng(3)
+    rays = rt.query_rays(origins, dirs, time=g.random(len(origins)))
+    rays["rng_state"] = g.integers(0, 2**63, len(rays), dtype=np.uint64)
+    got, st = dev.intersect(rays, want_stats=True)
+    ref, st_ref = oracle_hits(O, d, rays)
+    assert_records_equal(got, ref, shape)
+    assert_prims_consistent(d, got)
+    assert counters(st) == counters(st_ref, ref)
+    assert_records_equal(dev.intersect(rays), ref, shape + ", plain instance")
+    assert len(set(F.ref_kind(int(r)) for r in got["prim"][got["hit"] == 1])) >= 5
+    pf = F.rt_params.from_buffer_copy(p)
+    pf.spp = 2
+    check_view(rt, O, d, cam, pf, rows[:12], dev=dev)
+
+
+# ---- 2. records behind the small LDS tables ------------------------------------------------------------------------------------
+@pytest.mark.parametrize("mid", [False, True], ids=["list-root", "mid-chain"])
+def test_movers_media_and_lights_beyond_the_lds_tables(rt, O, mid):
+    """16 mover records, 5 media, 12 lights: wf_trace keeps 8 and 2 of the first two in LDS, wf_shade 8 lights; the others come
+    from global memory through a second code path (xform_words, the medium arm, light_at). rt_scene_create uploads the three
+    pools in the order of the desc, so the records behind the tables are the last created — every one of them the first hit of
+    some camera ray (tests/test_trace_scenes.py). Whole table in LDS, the plain 22-entry kernel (which keeps the world ray
+    in LDS) and the megakernel; under a chain of nodes the 30-entry kernels, which fetch it again."""
+    d, cam, p, rows, _ = T.overflow_scene(mid=mid)
+    ref, st_ref = O.render_cpu(d, cam, p, rows, n_threads=8, want_stats=True)
+    for label, tuning, engine in (("default", T.TUNING, "wavefront"), ("no node table", T.TUNING | T.NO_TABLE, "wavefront"),
+                                  ("megakernel", T.TUNING, "mega")):
+        dev = device_scene(rt, d, tuning, engine)
+        if engine == "mega":                              # (no wf_trace instance runs: the variant reads all zero)
+            assert not any(dev.trace_variant().values())
+            assert (dev.info()["stack_need"] > T.STACK_SMALL) == mid
+        else:
+            want, need = assert_variant(dev, d, tuning)
+            assert want["stack_entries"] == (30 if mid else 22 if tuning & T.NO_TABLE else 16), label
+        assert same(dev.render(cam, p, rows), ref), label
+        out, st = dev.render(cam, p, rows, want_stats=True)
+        assert st.as_dict() == st_ref.as_dict(), label
+        assert same(out, ref), label
+
+
+# ---- 3. either side of every threshold of the choice ---------------------------------------------------------------------------
+def check_threshold(rt, O, scene, table, **facts):
+    d, cam, p, rows = scene
+    dev = rt.DeviceScene(d)
+    want, need = assert_variant(dev, d)
+    assert want["table"] == table
+    for k, v in facts.items():
+        assert want[k] == v, (k, want)
+    assert same(dev.render(cam, p, rows), O.render_cpu(d, cam, p, rows, n_threads=8))
+    return need
+
+
+@pytest.mark.parametrize("n_nodes,table", [(1739, "whole"), (1740, "whole"), (1741, "partial")])
+def test_node_table_fills_at_1740_nodes(rt, O, n_nodes, table):
+    """The LDS arrays of the table hold exactly 1740 records: the last scene that fits whole, and the first that does not."""
+    check_threshold(rt, O, T.node_count_scene(n_nodes), table, nodes_in_lds=min(n_nodes, 1740), f32_slabs=False)
+
+
+@pytest.mark.parametrize("kw,table", [(dict(n_spheres=256), "prims"), (dict(n_spheres=257), "whole"),
+                                      (dict(n_spheres=4, n_moving=512), "prims"), (dict(n_spheres=4, n_moving=513), "whole"),
+                                      (dict(n_nodes=600), "prims"), (dict(n_nodes=601), "whole")],
+                         ids=lambda v: "-".join("%s%d" % kv for kv in v.items()) if isinstance(v, dict) else v)
+def test_all_in_lds_instance_fills_at_its_pool_sizes(rt, O, kw, table):
+    """Sphere-only scenes: 256 Spheres, 512 MovingSpheres and 600 nodes fit the all-in-LDS instance; one more of any sends the
+    scene to the whole-table instance with single-precision records."""
+    d = T.sphere_count_scene(**kw)
+    check_threshold(rt, O, d, table, spheres_in_lds=table == "prims", f32_slabs=True, nodes_in_lds=d[0].n_nodes)
+
+
+@pytest.mark.parametrize("need,stack", [(16, 16), (17, 22), (22, 22), (23, 30), (30, 30), (31, 64), (64, 64)])
+def test_stack_size_follows_the_need(rt, O, need, stack):
+    """Chains that need exactly as many entries as a kernel has, and one more. (65 is refused: test_deep_stacks_select_the_larger_kernels.)"""
+    got = check_threshold(rt, O, T.stack_need_scene(need), "prims" if need <= 16 else "plain", stack_entries=stack, f32_slabs=True)
+    assert got == need
