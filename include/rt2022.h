@@ -616,6 +616,77 @@ int rt_denoise_device(const double *d_rgb_sum, const rt_feature *d_features, con
 int rt_denoise(const double *rgb_sum, const rt_feature *features, const uint32_t *row_ids,
                const rt_denoise_params *p, double *out_rgb_sum, double *ms);
 
+/* ---- variance-guided denoising from two half-sample renders ------------------------------------------------
+ * rt_denoise's colour term cannot tell noise from detail. rt_params.n_frames already renders frames that share scene and
+ * camera and differ only in their RNG key: two frames of `spp` samples each are two independent estimates A and B of one
+ * image, (A + B) / 2 is the frame and ((A - B) / 2)^2 an unbiased estimate of that frame's variance. This filter is
+ * rt_denoise's with the colour distance measured in units of that variance, which it propagates through the iterations.
+ * A caller produces the halves with ONE render and ONE feature call, both with n_frames = 2 and the row list
+ * rows ++ (rows + height): the two halves of each output buffer are A and B. The engine is not touched.
+ *
+ * p is rt_denoise's block: spp is the samples in EACH half; width, height, n_iter, sigma_normal / depth / albedo,
+ * albedo_floor and RT_DENOISE_NO_DEMODULATE mean what they mean there; sigma_color is in units of the estimated standard
+ * deviation and is NOT halved per iteration — the propagated variance shrinks instead.
+ *
+ * Definition: IEEE + - * / on doubles in the stated order, no contraction. Per pixel, with sp = (double)spp, sp2 = sp + sp
+ * and nan0(x) = x is NaN ? 0 : x:
+ *   cA_j = nan0(A_j) / sp;  cB_j = nan0(B_j) / sp;  c_j = (cA_j + cB_j) * 0.5
+ *   a_j = (FA.albedo_j + FB.albedo_j) / sp2;  n_j and z likewise from normal and depth (hits is unused)
+ *   m_j = rt_denoise's rule on a_j (floor; NaN albedo -> floor; RT_DENOISE_NO_DEMODULATE -> 1.0)
+ *   e0_j = c_j / m_j
+ *   h_j  = ((cA_j - cB_j) * 0.5) / m_j
+ *   v0   = (h_0*h_0 + h_1*h_1) + h_2*h_2
+ * On the host: inv_n, inv_z, inv_a as for rt_denoise; inv_c = 1.0 / (sigma_color * sigma_color); +inf gives 0 (term off).
+ * Taps run over j = -2 .. 2 (rows), then i = -2 .. 2, offsets i*step and j*step in 64 bits, taps outside the image
+ * skipped, hh = h[j+2] * h[i+2], dn / da / dz as for rt_denoise on the averaged guides.
+ * Variance prefilter, t = 0 .. var_iter-1, step 2^t (sw = sx = 0.0 before the taps):
+ *   g = ((1.0 + dn*inv_n) * (1.0 + (dz*dz)*inv_z)) * (1.0 + da*inv_a);  w = hh / g
+ *   sw = sw + w;  sx = sx + w * v_t(q);          v_{t+1}(p) = sx / sw
+ * u_0 = v_{var_iter}. Colour iteration k = 0 .. n_iter-1, step 2^k (sw = su = sv_c = 0.0 before the taps):
+ *   dc  = rt_denoise's squared distance on e_k(p), e_k(q)
+ *   r   = (dc * inv_c) / ((u_k(p) + u_k(q)) + var_floor)
+ *   den = (((1.0 + r) * (1.0 + dn*inv_n)) * (1.0 + (dz*dz)*inv_z)) * (1.0 + da*inv_a);  w = hh / den
+ *   sw = sw + w;  sv_c = sv_c + w * e_k,c(q);  su = su + (w*w) * u_k(q)
+ *   e_{k+1},c(p) = sv_c / sw;   u_{k+1}(p) = su / (sw*sw)
+ * Outputs: out_c = (e_{n_iter},c * m_c) * sp2 — sums of 2*spp samples, so rt_tonemap_device(.., 2*spp, ..) applies as it
+ * is; out_variance[p] = u_{n_iter}(p), the residual variance of the demodulated mean, one double per pixel in buffer order
+ * (with n_iter = 0 the prefiltered input variance): what an adaptive sampler ranks pixels by. Buffer contents are never
+ * validated; NaN and inf in guides propagate as IEEE carries them.
+ *
+ * Row order: rt_denoise's rules. NULL, or `height` entries that are a permutation of [0, height); one list serves both
+ * halves and both outputs. rt_denoise_dual checks it on the host, rt_denoise_dual_device with rt_denoise_device's kernel
+ * behind one synchronisation of hip_stream, before anything writes an output; with NULL rows it is a pure enqueue.
+ *
+ * Workspace: rt_denoise_dual_device allocates nothing; the caller gives rt_denoise_dual_workspace_bytes(p) bytes (the
+ * packed guides, the ping-pong planes of colour and variance, the row map), contents meaningless before and reusable
+ * after. d_out_rgb_sum may alias either sum input (every input is read before any output is written); d_out_variance
+ * (may be NULL: not wanted) must not overlap any other buffer. All device buffers and the workspace are 16-byte aligned,
+ * device rows 4-byte aligned.
+ *
+ * RT_ERR_INVALID with rt_last_error() set, before any device call: everything rt_denoise* refuses; a null q, sum_b or
+ * feat_b; var_iter > RT_DENOISE_MAX_VAR_ITER; a var_floor that is <= 0, NaN or infinite; q->flags != 0; a misaligned
+ * d_out_variance. */
+typedef struct rt_denoise_dual_params {   /* 16 B */
+    uint32_t var_iter;                /* 0 .. RT_DENOISE_MAX_VAR_ITER: prefilter passes over the variance estimate */
+    uint32_t flags;                   /* must be 0 */
+    double   var_floor;               /* > 0, finite: added to the variance sum under the colour distance */
+} rt_denoise_dual_params;
+#define RT_DENOISE_MAX_VAR_ITER 8
+
+/* Bytes of device workspace rt_denoise_dual_device needs for p's image; 0 on invalid params. */
+uint64_t rt_denoise_dual_workspace_bytes(const rt_denoise_params *p);
+/* Device buffers (per half width * height * 3 sums and width * height records; NULL or `height` row ids; width * height
+ * * 3 sums and, if wanted, width * height variances out), enqueued on hip_stream (NULL = default stream). */
+int rt_denoise_dual_device(const double *d_sum_a, const double *d_sum_b,
+                           const rt_feature *d_feat_a, const rt_feature *d_feat_b,
+                           const uint32_t *d_row_ids, const rt_denoise_params *p, const rt_denoise_dual_params *q,
+                           double *d_out_rgb_sum, double *d_out_variance, void *d_workspace, void *hip_stream);
+/* Host buffers; synchronous. out_variance and ms may be NULL. */
+int rt_denoise_dual(const double *sum_a, const double *sum_b,
+                    const rt_feature *feat_a, const rt_feature *feat_b,
+                    const uint32_t *row_ids, const rt_denoise_params *p, const rt_denoise_dual_params *q,
+                    double *out_rgb_sum, double *out_variance, double *ms);
+
 /* write_color (main.rs:280-299): NaN→0, sqrt(c/spp), clamp [0,0.999], *255.999, floor. */
 void rt_write_color(const double rgb_sum[3], int32_t spp, uint8_t out_rgb[3]);
 /* Device form over n_pixels sums → n_pixels*3 bytes, on hip_stream. */

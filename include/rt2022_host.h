@@ -66,6 +66,8 @@ int rtb_radiance_abi_sizes(uint32_t *out, uint32_t n);
 int rtb_features_abi_sizes(uint32_t *out, uint32_t n);
 /* The same for the rt_denoise* structure: {rt_denoise_params}; returns 1. */
 int rtb_denoise_abi_sizes(uint32_t *out, uint32_t n);
+/* The same for the rt_denoise_dual* structure: {rt_denoise_dual_params}; returns 1. */
+int rtb_denoise_dual_abi_sizes(uint32_t *out, uint32_t n);
 
 #ifdef __cplusplus
 }

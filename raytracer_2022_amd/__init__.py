@@ -9,11 +9,13 @@ from . import _ffi
 from ._ffi import RtError, lib, make_ref, ref_index, ref_kind  # noqa: F401
 from .host import (DescBuilder, HostScene, camera_new, fill_image, load_image, make_params, shuffled_rows,  # noqa: F401
                    write_color, write_jpeg)
-from .device import (DeviceScene, DeviceSceneSet, denoise, denoise_device, denoise_params, denoise_workspace_bytes,  # noqa: F401
-                     query_rays, radiance_params, radiance_rays)
+from .device import (DUAL_DEFAULTS, DeviceScene, DeviceSceneSet, denoise, denoise_device, denoise_dual, denoise_dual_device,  # noqa: F401
+                     denoise_dual_params, denoise_dual_workspace_bytes, denoise_params, denoise_workspace_bytes, query_rays,
+                     radiance_params, radiance_rays, two_frame_rows)
 from ._ffi import FEATURE_DTYPE, HIT_DTYPE, QUERY_RAY_DTYPE, RADIANCE_RAY_DTYPE  # noqa: F401
 
 __all__ = ["DescBuilder", "HostScene", "DeviceScene", "DeviceSceneSet", "camera_new", "fill_image", "make_params", "shuffled_rows",
            "write_color", "write_jpeg", "load_image", "RtError", "lib", "make_ref", "ref_kind", "ref_index", "query_rays",
            "QUERY_RAY_DTYPE", "HIT_DTYPE", "radiance_rays", "radiance_params", "RADIANCE_RAY_DTYPE", "FEATURE_DTYPE",
-           "denoise", "denoise_device", "denoise_params", "denoise_workspace_bytes"]
+           "denoise", "denoise_device", "denoise_params", "denoise_workspace_bytes", "denoise_dual", "denoise_dual_device",
+           "denoise_dual_params", "denoise_dual_workspace_bytes", "two_frame_rows", "DUAL_DEFAULTS"]

@@ -214,6 +214,15 @@ RT_DENOISE_MAX_PIXELS = 1 << 36
 # The rt_denoise* structure, in the order of rtb_denoise_abi_sizes.
 DENOISE_ABI_STRUCTS = [rt_denoise_params]
 
+
+class rt_denoise_dual_params(C.Structure):
+    _fields_ = [("var_iter", C.c_uint32), ("flags", C.c_uint32), ("var_floor", C.c_double)]
+
+
+RT_DENOISE_MAX_VAR_ITER = 8
+# The rt_denoise_dual* structure, in the order of rtb_denoise_dual_abi_sizes.
+DENOISE_DUAL_ABI_STRUCTS = [rt_denoise_dual_params]
+
 ABI_STRUCTS = [rt_bvh_node, rt_sphere, rt_moving_sphere, rt_rect, rt_box, rt_triangle, rt_ring, rt_medium, rt_xform,
                rt_list, rt_material, rt_texture, rt_image, rt_perlin, rt_scene_desc, rt_camera, rt_params, rt_stats,
                rt_query_ray, rt_hit]
@@ -227,9 +236,11 @@ ABI_SYMBOLS = [
     "rt_tonemap_device", "rt_last_error", "rt_abi_version", "rt_scene_set_create", "rt_scene_set_destroy", "rt_render_multi",
     "rt_intersect", "rt_intersect_device", "rt_radiance", "rt_radiance_device",
     "rt_features", "rt_features_device", "rt_denoise_workspace_bytes", "rt_denoise", "rt_denoise_device",
+    "rt_denoise_dual_workspace_bytes", "rt_denoise_dual", "rt_denoise_dual_device",
     "rtb_scene_build", "rtb_scene_free", "rtb_scene_desc", "rtb_scene_default_view", "rtb_camera_new",
     "rtb_shuffled_rows", "rtb_bvh_build", "rtb_fill_image", "rtb_write_ppm", "rtb_write_jpeg", "rtb_image_load",
     "rtb_last_error", "rtb_abi_sizes", "rtb_radiance_abi_sizes", "rtb_features_abi_sizes", "rtb_denoise_abi_sizes",
+    "rtb_denoise_dual_abi_sizes",
     "rt_debug_math_device", "rt_debug_rng_device", "rt_debug_scene_info", "rt_debug_trace_variant", "rt_debug_set_tuning", "rt_debug_set_engine", "rt_debug_census", "rt_debug_pass_timing", "rt_debug_traffic_probe", "rt_debug_valu_probe", "rt_debug_set_partial_ring", "rt_debug_f32_slabs",
 ]
 
@@ -271,6 +282,10 @@ def lib():
     L.rt_denoise_workspace_bytes.restype = u64
     L.rt_denoise.argtypes = [vp, vp, vp, P(rt_denoise_params), vp, P(dbl)]
     L.rt_denoise_device.argtypes = [vp, vp, vp, P(rt_denoise_params), vp, vp, vp]
+    L.rt_denoise_dual_workspace_bytes.argtypes = [P(rt_denoise_params)]
+    L.rt_denoise_dual_workspace_bytes.restype = u64
+    L.rt_denoise_dual.argtypes = [vp, vp, vp, vp, vp, P(rt_denoise_params), P(rt_denoise_dual_params), vp, vp, P(dbl)]
+    L.rt_denoise_dual_device.argtypes = [vp, vp, vp, vp, vp, P(rt_denoise_params), P(rt_denoise_dual_params), vp, vp, vp, vp]
     L.rtb_scene_build.argtypes = [C.c_char_p, u64, C.c_char_p, i32, P(vp)]
     L.rtb_scene_free.argtypes = [vp]
     L.rtb_scene_free.restype = None
@@ -289,6 +304,7 @@ def lib():
     L.rtb_radiance_abi_sizes.argtypes = [P(u32), u32]
     L.rtb_features_abi_sizes.argtypes = [P(u32), u32]
     L.rtb_denoise_abi_sizes.argtypes = [P(u32), u32]
+    L.rtb_denoise_dual_abi_sizes.argtypes = [P(u32), u32]
     L.rt_debug_math_device.argtypes = [C.c_int, P(dbl), P(dbl), P(dbl), u64]
     L.rt_debug_rng_device.argtypes = [u64, C.c_int, dbl, dbl, u64, P(u64), u64]
     L.rt_debug_scene_info.argtypes = [vp, P(u32), P(i32)]

@@ -286,6 +286,33 @@ hipError_t launch_denoise_rows(const DenoiseArgs &a, hipStream_t stream);
 // prepare + n_iter a-trous passes; inv_c[k] = 1 / sigma_k^2.
 hipError_t launch_denoise(const DenoiseArgs &a, uint32_t n_iter, const double *inv_c, hipStream_t stream);
 
+// ---- variance-guided denoiser over two half-sample renders (pt_denoise.hip, rt_denoise_dual*) ----
+// The dual filter's workspace (byte offsets, each a multiple of 16). A pixel's eleven doubles are five 16-byte pieces and
+// one 8-byte piece, each a plane of its own.
+struct DenoiseDualLayout {
+    uint64_t guides;                   // 3 planes of n_pixels double2: {n0, n1} {n2, z} {a0, a1}, image order
+    uint64_t a2;                       // 1 plane of n_pixels double: the albedo's third component
+    uint64_t colour[2];                // ping-pong, each 2 planes of n_pixels double2: {e0, e1} {e2, u}
+    uint64_t var[2];                   // ping-pong of the prefilter, each 1 plane of n_pixels double: v
+    uint64_t inv_rows;                 // height x uint32: image row -> buffer row
+    uint64_t bad_rows;                 // one uint32: bad or repeated row ids of the call's list
+    uint64_t bytes;
+};
+DenoiseDualLayout denoise_dual_layout(uint32_t width, uint32_t height);
+struct DenoiseDualArgs {
+    DenoiseArgs a;                     // half A's buffers; sp = (double)spp of ONE half; ws laid out by denoise_dual_layout
+    const double *sum_b;               // device: half B's sums, buffer order
+    const rt_feature *feat_b;          // device, 16-byte aligned, buffer order
+    double *out_var;                   // device: the residual variance, buffer order (null: not wanted)
+    double sp2;                        // sp + sp
+    double inv_c;                      // 1 / sigma_color^2, every iteration's
+    double var_floor;
+};
+// The row kernel on a.a.rows (not null), into the dual layout's map and count.
+hipError_t launch_denoise_dual_rows(const DenoiseDualArgs &a, hipStream_t stream);
+// dual prepare + var_iter prefilter passes + n_iter variance-aware a-trous passes.
+hipError_t launch_denoise_dual(const DenoiseDualArgs &a, uint32_t var_iter, uint32_t n_iter, hipStream_t stream);
+
 // Launchers (pt_kernel.hip). `stack_need` = entries the scene needs (host-computed).
 hipError_t launch_render(const SceneDev &scene, const RenderArgs &args, uint32_t stack_need, bool counters,
                          int n_blocks_hint, hipStream_t stream);

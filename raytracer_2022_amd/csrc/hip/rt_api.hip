@@ -836,6 +836,47 @@ void run_denoise(const double *d_sum, const rt_feature *d_feat, const uint32_t *
     RT_HIP(launch_denoise(a, p->n_iter, inv_c, stream));
 }
 
+// The arguments of rt_denoise_dual*: what rt_denoise* refuses, then the dual filter's own.
+void check_denoise_dual(const double *sum_a, const double *sum_b, const rt_feature *feat_a, const rt_feature *feat_b, const rt_denoise_params *p,
+                        const rt_denoise_dual_params *q, const double *out, const std::string &w) {
+    check_denoise(sum_a, feat_a, p, out, w);
+    RT_REQUIRE(q, RT_ERR_INVALID, w + ": null dual params");
+    RT_REQUIRE(sum_b && feat_b, RT_ERR_INVALID, w + ": null sums or features of the second half");
+    RT_REQUIRE(q->var_iter <= RT_DENOISE_MAX_VAR_ITER, RT_ERR_INVALID, w + ": var_iter > RT_DENOISE_MAX_VAR_ITER");
+    RT_REQUIRE(q->var_floor > 0.0 && !std::isinf(q->var_floor), RT_ERR_INVALID, w + ": var_floor is <= 0, NaN or infinite");
+    RT_REQUIRE(q->flags == 0, RT_ERR_INVALID, w + ": dual flags must be 0");
+}
+
+// Enqueue one dual denoise on `stream`, like run_denoise.
+void run_denoise_dual(const double *d_sum_a, const double *d_sum_b, const rt_feature *d_feat_a, const rt_feature *d_feat_b, const uint32_t *d_rows,
+                      const rt_denoise_params *p, const rt_denoise_dual_params *q, double *d_out, double *d_out_var, char *d_ws,
+                      hipStream_t stream, bool check_rows, const std::string &w) {
+    DenoiseDualArgs d{};
+    DenoiseArgs &a = d.a;
+    a.width = p->width; a.height = p->height;
+    a.sp = (double)p->spp;
+    a.inv_n = 1.0 / (p->sigma_normal * p->sigma_normal);
+    a.inv_z = 1.0 / (p->sigma_depth * p->sigma_depth);
+    a.inv_a = 1.0 / (p->sigma_albedo * p->sigma_albedo);
+    a.albedo_floor = p->albedo_floor;
+    a.demodulate = !(p->flags & RT_DENOISE_NO_DEMODULATE);
+    a.sum = d_sum_a; a.feat = d_feat_a; a.rows = d_rows; a.out = d_out; a.ws = d_ws;
+    d.sum_b = d_sum_b; d.feat_b = d_feat_b; d.out_var = d_out_var;
+    d.sp2 = a.sp + a.sp;
+    d.inv_c = 1.0 / (p->sigma_color * p->sigma_color);
+    d.var_floor = q->var_floor;
+    if (d_rows) {
+        RT_HIP(launch_denoise_dual_rows(d, stream));
+        if (check_rows) {
+            uint32_t bad = 0;
+            RT_HIP(hipMemcpyAsync(&bad, d_ws + denoise_dual_layout(p->width, p->height).bad_rows, sizeof bad, hipMemcpyDeviceToHost, stream));
+            RT_HIP(hipStreamSynchronize(stream));
+            RT_REQUIRE(bad == 0, RT_ERR_INVALID, w + ": row_ids is not a permutation of the image's rows");
+        }
+    }
+    RT_HIP(launch_denoise_dual(d, q->var_iter, p->n_iter, stream));
+}
+
 void finish(rt_scene *sc, hipStream_t stream) {
     Workspace &w = workspace_for(sc, stream);
     RT_HIP(hipStreamSynchronize(stream));
@@ -1271,6 +1312,66 @@ int rt_denoise(const double *rgb_sum, const rt_feature *features, const uint32_t
         RT_HIP(hipEventRecord(ev1, nullptr));
         RT_HIP(hipStreamSynchronize(nullptr));
         RT_HIP(hipMemcpy(out_rgb_sum, d_sum, 3 * n * sizeof(double), hipMemcpyDeviceToHost));
+        if (ms) {
+            float t = 0.f;
+            RT_HIP(hipEventElapsedTime(&t, ev0, ev1));
+            *ms = (double)t;
+        }
+        return RT_OK;
+    });
+}
+
+uint64_t rt_denoise_dual_workspace_bytes(const rt_denoise_params *p) {
+    return denoise_params_fault(p) ? 0 : denoise_dual_layout(p->width, p->height).bytes;
+}
+
+int rt_denoise_dual_device(const double *d_sum_a, const double *d_sum_b, const rt_feature *d_feat_a, const rt_feature *d_feat_b,
+                           const uint32_t *d_row_ids, const rt_denoise_params *p, const rt_denoise_dual_params *q, double *d_out_rgb_sum,
+                           double *d_out_variance, void *d_workspace, void *hip_stream) {
+    return guarded([&]() -> int {
+        const std::string w("rt_denoise_dual_device");
+        check_denoise_dual(d_sum_a, d_sum_b, d_feat_a, d_feat_b, p, q, d_out_rgb_sum, w);
+        RT_REQUIRE(d_workspace, RT_ERR_INVALID, w + ": null workspace");
+        RT_REQUIRE(!(((uintptr_t)d_sum_a | (uintptr_t)d_sum_b | (uintptr_t)d_feat_a | (uintptr_t)d_feat_b | (uintptr_t)d_out_rgb_sum |
+                      (uintptr_t)d_out_variance | (uintptr_t)d_workspace) & 15u),
+                   RT_ERR_INVALID, w + ": the buffers and the workspace must be 16-byte aligned");
+        RT_REQUIRE(!((uintptr_t)d_row_ids & 3u), RT_ERR_INVALID, w + ": row_ids must be 4-byte aligned");
+        run_denoise_dual(d_sum_a, d_sum_b, d_feat_a, d_feat_b, d_row_ids, p, q, d_out_rgb_sum, d_out_variance, (char *)d_workspace,
+                         (hipStream_t)hip_stream, true, w);
+        return RT_OK;
+    });
+}
+
+int rt_denoise_dual(const double *sum_a, const double *sum_b, const rt_feature *feat_a, const rt_feature *feat_b, const uint32_t *row_ids,
+                    const rt_denoise_params *p, const rt_denoise_dual_params *q, double *out_rgb_sum, double *out_variance, double *ms) {
+    return guarded([&]() -> int {
+        const std::string w("rt_denoise_dual");
+        check_denoise_dual(sum_a, sum_b, feat_a, feat_b, p, q, out_rgb_sum, w);
+        if (row_ids) {                                         // a permutation of [0, height)?
+            std::vector<char> seen(p->height, 0);
+            for (uint32_t i = 0; i < p->height; i++) {
+                RT_REQUIRE(row_ids[i] < p->height && !seen[row_ids[i]], RT_ERR_INVALID, w + ": row_ids is not a permutation of the image's rows");
+                seen[row_ids[i]] = 1;
+            }
+        }
+        const uint64_t n = (uint64_t)p->width * p->height;
+        DeviceBuf<double> d_a(3 * n), d_b(3 * n);              // (A is filtered in place)
+        DeviceBuf<rt_feature> d_fa(n), d_fb(n);
+        DeviceBuf<double> d_var(out_variance ? n : 0);
+        DeviceBuf<uint32_t> d_rows(row_ids ? p->height : 0);
+        DeviceBuf<char> d_ws(denoise_dual_layout(p->width, p->height).bytes);
+        Event ev0{hipEventDefault}, ev1{hipEventDefault};
+        RT_HIP(hipMemcpy(d_a, sum_a, 3 * n * sizeof(double), hipMemcpyHostToDevice));
+        RT_HIP(hipMemcpy(d_b, sum_b, 3 * n * sizeof(double), hipMemcpyHostToDevice));
+        RT_HIP(hipMemcpy(d_fa, feat_a, n * sizeof(rt_feature), hipMemcpyHostToDevice));
+        RT_HIP(hipMemcpy(d_fb, feat_b, n * sizeof(rt_feature), hipMemcpyHostToDevice));
+        if (row_ids) RT_HIP(hipMemcpy(d_rows, row_ids, p->height * sizeof(uint32_t), hipMemcpyHostToDevice));
+        RT_HIP(hipEventRecord(ev0, nullptr));
+        run_denoise_dual(d_a, d_b, d_fa, d_fb, row_ids ? d_rows.p : nullptr, p, q, d_a, out_variance ? d_var.p : nullptr, d_ws, nullptr, false, w);
+        RT_HIP(hipEventRecord(ev1, nullptr));
+        RT_HIP(hipStreamSynchronize(nullptr));
+        RT_HIP(hipMemcpy(out_rgb_sum, d_a, 3 * n * sizeof(double), hipMemcpyDeviceToHost));
+        if (out_variance) RT_HIP(hipMemcpy(out_variance, d_var, n * sizeof(double), hipMemcpyDeviceToHost));
         if (ms) {
             float t = 0.f;
             RT_HIP(hipEventElapsedTime(&t, ev0, ev1));

@@ -99,6 +99,69 @@ def denoise_device(d_rgb_sum_ptr, d_features_ptr, params, d_out_ptr, d_workspace
                                       C.byref(params), C.c_void_p(d_out_ptr), C.c_void_p(d_workspace_ptr), C.c_void_p(stream_ptr or 0)))
 
 
+# The tuned parameters of the dual filter: the point of tools/denoise_dual_grid.py's grid with the smallest sum of the three
+# views' MSE ratios (profiles/denoise_dual_grid.log). sigma_color goes into denoise_params, the others into denoise_dual_params.
+DUAL_DEFAULTS = {"sigma_color": 2.0, "var_iter": 1, "var_floor": 1e-6}
+
+
+def denoise_dual_params(var_iter=DUAL_DEFAULTS["var_iter"], var_floor=DUAL_DEFAULTS["var_floor"]):
+    """rt_denoise_dual_params: prefilter passes over the variance estimate and the floor under the colour distance. The
+    defaults, with sigma_color=DUAL_DEFAULTS["sigma_color"] in denoise_params, are the grid point of
+    tools/denoise_dual_grid.py with the smallest summed MSE ratio (profiles/denoise_dual_grid.log)."""
+    q = F.rt_denoise_dual_params()
+    q.var_iter, q.flags, q.var_floor = var_iter, 0, var_floor
+    return q
+
+
+def denoise_dual_workspace_bytes(params):
+    """rt_denoise_dual_workspace_bytes: device bytes denoise_dual_device needs for params' image (0: invalid params)."""
+    return int(F.lib().rt_denoise_dual_workspace_bytes(C.byref(params)))
+
+
+def two_frame_rows(row_ids, height):
+    """The row list of a two-frame render or feature call over one frame's list: rows ++ (rows + height). The two halves of
+    the call's output are the halves A and B of denoise_dual."""
+    rows = np.ascontiguousarray(row_ids, dtype=np.uint32)
+    return np.concatenate([rows, rows + np.uint32(height)])
+
+
+def denoise_dual(sum_a, sum_b, feat_a, feat_b, params, dual_params=None, row_ids=None, want_variance=False, want_ms=False):
+    """rt_denoise_dual with host buffers: two half-sample renders' sums (height, width, 3) and FEATURE_DTYPE records (height,
+    width) of params.spp samples each, in the order of `row_ids` (None: image order) -> the filtered sums of 2 * spp samples,
+    same shape and order [, the residual variance (height, width)] [, device ms]. params.sigma_color counts estimated
+    standard deviations: DUAL_DEFAULTS["sigma_color"] is the tuned value."""
+    n = params.width * params.height
+    s = [np.ascontiguousarray(x, dtype=np.float64) for x in (sum_a, sum_b)]
+    f = [np.ascontiguousarray(x, dtype=F.FEATURE_DTYPE) for x in (feat_a, feat_b)]
+    if any(x.size != 3 * n for x in s) or any(x.size != n for x in f):
+        raise ValueError("both halves' rgb_sum and features must hold width * height pixels")
+    rows = None
+    if row_ids is not None:
+        rows = np.ascontiguousarray(row_ids, dtype=np.uint32)
+        if rows.size != params.height:
+            raise ValueError("row_ids must hold one entry per image row")
+    q = dual_params if dual_params is not None else denoise_dual_params()
+    out = np.empty_like(s[0])
+    var = np.empty(s[0].shape[:-1] if s[0].ndim > 1 else (n,), dtype=np.float64) if want_variance else None
+    ms = C.c_double()
+    F.check(F.lib().rt_denoise_dual(s[0].ctypes.data, s[1].ctypes.data, f[0].ctypes.data, f[1].ctypes.data,
+                                    rows.ctypes.data if rows is not None else None, C.byref(params), C.byref(q), out.ctypes.data,
+                                    var.ctypes.data if var is not None else None, C.byref(ms)))
+    res = (out,) + ((var,) if want_variance else ()) + ((ms.value,) if want_ms else ())
+    return res[0] if len(res) == 1 else res
+
+
+def denoise_dual_device(d_sum_a_ptr, d_sum_b_ptr, d_feat_a_ptr, d_feat_b_ptr, params, dual_params, d_out_ptr, d_workspace_ptr,
+                        d_out_variance_ptr=None, d_row_ids_ptr=None, stream_ptr=None):
+    """rt_denoise_dual_device: device pointers in (each half's sums and rt_feature records, room for the filtered sums — it
+    may be either half's — and denoise_dual_workspace_bytes(params) bytes of workspace, optionally room for width * height
+    variances, all 16-byte aligned; `height` row ids or None), enqueued on `stream_ptr` (hipStream_t as int). With no row
+    list the call does not synchronise."""
+    F.check(F.lib().rt_denoise_dual_device(C.c_void_p(d_sum_a_ptr), C.c_void_p(d_sum_b_ptr), C.c_void_p(d_feat_a_ptr), C.c_void_p(d_feat_b_ptr),
+                                           C.c_void_p(d_row_ids_ptr or 0), C.byref(params), C.byref(dual_params), C.c_void_p(d_out_ptr),
+                                           C.c_void_p(d_out_variance_ptr or 0), C.c_void_p(d_workspace_ptr), C.c_void_p(stream_ptr or 0)))
+
+
 class DeviceScene:
     """rt_scene: the flattened scene copied into HBM on the current HIP device."""
 

@@ -1,0 +1,127 @@
+"""The variance-guided denoiser (rt_denoise_dual*) once more in numpy, and the CPU side of its evaluation. No GPU is needed:
+tests/test_denoise_dual.py compares the library with `restate_dual` bit for bit, tools/denoise_dual_grid.py chooses the
+Python defaults with it on the oracle's renders.
+
+`restate_dual` is include/rt2022.h's definition: the 25 taps one after the other in the header's order, the pixels of a tap
+vectorised, a skipped tap through np.where. numpy's element-wise + - * / on float64 are the IEEE operations and nothing is
+fused, so the kernels (built with -ffp-contract=off) must give the same doubles."""
+import numpy as np
+
+from raytracer_2022_amd import _ffi as F
+
+H5 = [1.0 / 16.0, 1.0 / 4.0, 3.0 / 8.0, 1.0 / 4.0, 1.0 / 16.0]
+# The views of the end-to-end tests and of the grid: (scene, width, height). The last one the grid never sees.
+GRID_VIEWS = [("cornell_box", 48, 48), ("final_scene", 48, 48), ("random_scene", 60, 40)]
+HELD_OUT_VIEW = ("cornell_smoke", 48, 48)
+HALF_SPP, SEED, REF_SPP, REF_SEED = 2, 2022, 512, 7
+
+
+def dist(p, q):
+    d0, d1, d2 = p[..., 0] - q[..., 0], p[..., 1] - q[..., 1], p[..., 2] - q[..., 2]
+    return (d0 * d0 + d1 * d1) + d2 * d2
+
+
+def restate_dual(sum_a, sum_b, feat_a, feat_b, p, q, rows=None):
+    """The definition in numpy. Sums (H, W, 3) and FEATURE_DTYPE records (H, W) of both halves in buffer order -> (filtered
+    sums (H, W, 3), residual variance (H, W)), buffer order."""
+    H, W = p.height, p.width
+    sa, sb = (np.asarray(s, dtype=np.float64).reshape(H, W, 3) for s in (sum_a, sum_b))
+    fa, fb = (np.asarray(f).reshape(H, W) for f in (feat_a, feat_b))
+    if rows is not None:                                   # buffer row i is image row rows[i]
+        inv = np.empty(H, dtype=np.int64)
+        inv[np.asarray(rows, dtype=np.int64)] = np.arange(H)
+        sa, sb, fa, fb = sa[inv], sb[inv], fa[inv], fb[inv]
+    one, half, zero = np.float64(1.0), np.float64(0.5), np.float64(0.0)
+    with np.errstate(all="ignore"):
+        sp = np.float64(p.spp)
+        sp2 = sp + sp
+        ca = np.where(np.isnan(sa), zero, sa) / sp
+        cb = np.where(np.isnan(sb), zero, sb) / sp
+        c = (ca + cb) * half
+        a = (fa["albedo"] + fb["albedo"]) / sp2
+        n = (fa["normal"] + fb["normal"]) / sp2
+        z = (fa["depth"] + fb["depth"]) / sp2
+        floor = np.float64(p.albedo_floor)
+        m = np.ones_like(a) if p.flags & F.RT_DENOISE_NO_DEMODULATE else np.where(a > floor, a, floor)
+        e = c / m
+        h = ((ca - cb) * half) / m
+        u = (h[..., 0] * h[..., 0] + h[..., 1] * h[..., 1]) + h[..., 2] * h[..., 2]
+        inv_n = one / (np.float64(p.sigma_normal) * np.float64(p.sigma_normal))
+        inv_z = one / (np.float64(p.sigma_depth) * np.float64(p.sigma_depth))
+        inv_a = one / (np.float64(p.sigma_albedo) * np.float64(p.sigma_albedo))
+        inv_c = one / (np.float64(p.sigma_color) * np.float64(p.sigma_color))
+        var_floor = np.float64(q.var_floor)
+        ys, xs = np.meshgrid(np.arange(H, dtype=np.int64), np.arange(W, dtype=np.int64), indexing="ij")
+
+        def taps(s):
+            for j in range(-2, 3):
+                for i in range(-2, 3):
+                    qx, qy = xs + i * s, ys + j * s
+                    ok = (qx >= 0) & (qx < W) & (qy >= 0) & (qy < H)
+                    qx, qy = np.clip(qx, 0, W - 1), np.clip(qy, 0, H - 1)
+                    dn, da = dist(n, n[qy, qx]), dist(a, a[qy, qx])
+                    dz = z - z[qy, qx]
+                    yield np.float64(H5[j + 2] * H5[i + 2]), ok, qy, qx, dn, da, dz
+
+        for t in range(q.var_iter):
+            sw, sx = np.zeros((H, W)), np.zeros((H, W))
+            for hh, ok, qy, qx, dn, da, dz in taps(1 << t):
+                g = ((one + dn * inv_n) * (one + (dz * dz) * inv_z)) * (one + da * inv_a)
+                w = hh / g
+                sw = np.where(ok, sw + w, sw)
+                sx = np.where(ok, sx + w * u[qy, qx], sx)
+            u = sx / sw
+        for k in range(p.n_iter):
+            sw, su, sv = np.zeros((H, W)), np.zeros((H, W)), np.zeros((H, W, 3))
+            for hh, ok, qy, qx, dn, da, dz in taps(1 << k):
+                dc = dist(e, e[qy, qx])
+                r = (dc * inv_c) / ((u + u[qy, qx]) + var_floor)
+                den = (((one + r) * (one + dn * inv_n)) * (one + (dz * dz) * inv_z)) * (one + da * inv_a)
+                w = hh / den
+                sw = np.where(ok, sw + w, sw)
+                sv = np.where(ok[..., None], sv + w[..., None] * e[qy, qx], sv)
+                su = np.where(ok, su + (w * w) * u[qy, qx], su)
+            e = sv / sw[..., None]
+            u = su / (sw * sw)
+        out = (e * m) * sp2
+    if rows is None:
+        return out, u
+    rows = np.asarray(rows, dtype=np.int64)
+    return out[rows], u[rows]
+
+
+def bits(a):
+    v = np.ascontiguousarray(a, dtype=np.float64)
+    return np.where(np.isnan(v), np.float64(0), v).view(np.uint64), np.isnan(v)
+
+
+def assert_same_bits(got, ref, what=""):
+    (gb, gn), (rb, rn) = bits(got), bits(ref)
+    assert gb.shape == rb.shape, what
+    assert np.array_equal(gn, rn), (what, "NaN pattern")
+    bad = np.argwhere(gb != rb)
+    assert len(bad) == 0, (what, "first differing doubles", bad[:5].tolist(), len(bad))
+
+
+def display(sums, spp):
+    c = np.where(np.isnan(sums), 0.0, sums) / spp
+    return np.sqrt(np.clip(c, 0.0, 0.999))
+
+
+def mse(sums, spp, target):
+    return float(np.mean((display(sums, spp) - target) ** 2))
+
+
+def add_features(fa, fb):
+    """FA + FB field by field: the records of the 2 * spp frame, as rt_denoise reads them."""
+    out = np.zeros(fa.shape, dtype=F.FEATURE_DTYPE)
+    out.view(np.float64)[...] = np.ascontiguousarray(fa).view(np.float64) + np.ascontiguousarray(fb).view(np.float64)
+    return out
+
+
+def dual_blocks(rt, W, H, spp, sigma_color=None, var_iter=None, var_floor=None, **kw):
+    """(rt_denoise_params, rt_denoise_dual_params) with the package's tuned values where none is given."""
+    d = rt.DUAL_DEFAULTS
+    p = rt.denoise_params(W, H, spp, sigma_color=d["sigma_color"] if sigma_color is None else sigma_color, **kw)
+    q = rt.denoise_dual_params(d["var_iter"] if var_iter is None else var_iter, d["var_floor"] if var_floor is None else var_floor)
+    return p, q

@@ -1,0 +1,315 @@
+"""Variance-guided denoiser (rt_denoise_dual / rt_denoise_dual_device) against the numpy restatement of its definition
+(tests/denoise_dual_ref.py), bit for bit: every comparison is on the uint64 view, the NaN patterns first. The shapes are
+those at which the kernels can go wrong: no multiple of the 64 x 4 workgroup, several workgroups each way, images smaller
+than the footprint."""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+
+from raytracer_2022_amd import _ffi as F
+
+import denoise_dual_ref as R
+from denoise_dual_ref import assert_same_bits, restate_dual
+from test_denoise import buffers, restate as restate_single
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module", autouse=True)
+def torch_first():
+    """Bring torch's HIP context up before the library's first call, as the other GPU test modules do."""
+    import torch
+    assert torch.cuda.is_available(), "gpu tests need a GPU: the HIP path has no fallback"
+    torch.zeros(1, device="cuda")
+
+
+def halves(W, H, spp=4, seed=1, hostile=True, nan_albedo=True):
+    """Two halves of random buffers. hostile: each half has NaN, 1e30 and negative sums, zero / NaN albedo and all-zero miss
+    records of its own, and the top-left quarter of A's are B's as well (faults in one half only and in both)."""
+    sa, fa = buffers(W, H, spp=spp, seed=seed, hostile=hostile, nan_albedo=nan_albedo)
+    sb, fb = buffers(W, H, spp=spp, seed=seed + 100, hostile=hostile, nan_albedo=nan_albedo)
+    if hostile:
+        odd = ~np.isfinite(sa) | (sa == 1e30) | (sa == -3.0)
+        odd[H // 2:], odd[:, W // 2:] = False, False
+        sb[odd] = sa[odd]
+        fb[: H // 4, : W // 4] = fa[: H // 4, : W // 4]
+    return sa, sb, fa, fb
+
+
+def check(rt, h, p, q, rows=None, what=""):
+    got, var = rt.denoise_dual(*h, p, q, row_ids=rows, want_variance=True)
+    ref, ref_var = restate_dual(*h, p, q, rows)
+    assert got.shape == np.asarray(h[0]).shape and var.shape == got.shape[:-1]
+    assert_same_bits(got, ref, what)
+    assert_same_bits(var, ref_var, (what, "variance"))
+    return got, var
+
+
+# ---- hostile buffers ----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n_iter", [5, 1, 2])
+@pytest.mark.parametrize("var_iter", [0, 1, 3])
+def test_hostile_buffers(rt, n_iter, var_iter):
+    """67 x 35. A NaN guide spreads to every pixel whose footprint reaches it, so one and two iterations leave NaN islands."""
+    W, H = 67, 35
+    h = halves(W, H)
+    p, q = R.dual_blocks(rt, W, H, 4, var_iter=var_iter, n_iter=n_iter)
+    got, var = check(rt, h, p, q)
+    if n_iter == 1 and var_iter == 0:
+        assert 0 < np.isnan(got).sum() < got.size and 0 < np.isnan(var).sum() < var.size
+
+
+def test_hostile_sums_alone_give_finite_results(rt):
+    """Without NaN albedo the NaN radiance (-> 0), the 1e30s and the negative sums stay finite through five iterations."""
+    W, H = 67, 35
+    h = halves(W, H, nan_albedo=False)
+    got, var = check(rt, h, *R.dual_blocks(rt, W, H, 4))
+    assert np.isfinite(got).all() and np.isfinite(var).all() and (var >= 0.0).all()
+
+
+# ---- footprint larger than the image ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("W, H", [(1, 1), (1, 9), (9, 1), (5, 3)])
+def test_footprint_larger_than_the_image(rt, W, H):
+    h = halves(W, H, seed=W * 16 + H, hostile=False)
+    p, q = R.dual_blocks(rt, W, H, 4, var_iter=F.RT_DENOISE_MAX_VAR_ITER, n_iter=F.RT_DENOISE_MAX_ITER)     # steps up to 2^15
+    got, var = check(rt, h, p, q)
+    if (W, H) == (1, 1):                                   # the centre tap alone
+        assert np.allclose(got, h[0] + h[1], rtol=1e-14)
+
+
+# ---- switches --------------------------------------------------------------------------------------------------------------
+INF = math.inf
+ALL_OFF = dict(sigma_color=INF, sigma_normal=INF, sigma_depth=INF, sigma_albedo=INF)
+SWITCHES = {
+    "colour off": dict(sigma_color=INF), "normal off": dict(sigma_normal=INF), "depth off": dict(sigma_depth=INF),
+    "depth on": dict(sigma_depth=2.0), "albedo off": dict(sigma_albedo=INF), "all off": dict(ALL_OFF),
+    "n_iter 0": dict(n_iter=0), "n_iter 0, no prefilter": dict(n_iter=0, var_iter=0), "n_iter 1": dict(n_iter=1),
+    "no prefilter": dict(var_iter=0), "no demodulation": dict(demodulate=False), "spp 1": dict(spp=1), "spp 7": dict(spp=7, n_iter=3),
+    "tight": dict(sigma_color=0.5, sigma_normal=0.05, sigma_depth=0.1, sigma_albedo=0.01, albedo_floor=0.3, var_floor=1e-2, var_iter=2),
+}
+
+
+@pytest.mark.parametrize("name", list(SWITCHES))
+def test_switches(rt, name):
+    W, H = 70, 9
+    kw = dict(SWITCHES[name])
+    spp = kw.pop("spp", 4)
+    h = halves(W, H, spp=spp, seed=5, hostile=True, nan_albedo=False)
+    p, q = R.dual_blocks(rt, W, H, spp, **kw)
+    got, var = check(rt, h, p, q, what=name)
+    if name.startswith("n_iter 0"):                        # (c / m) * m * sp2: A + B to rounding, NaN -> 0; the variance is u_0
+        nan0 = lambda s: np.where(np.isnan(s), 0.0, s)
+        assert np.allclose(got, nan0(h[0]) + nan0(h[1]), rtol=1e-13)
+        assert (var >= 0.0).all() and var.max() > 0.0
+        if q.var_iter == 0:                                # the raw estimate, whose mean over the colours needs no filter
+            m = np.maximum((h[2]["albedo"] + h[3]["albedo"]) / (2 * spp), p.albedo_floor)
+            assert np.allclose(var, ((((nan0(h[0]) - nan0(h[1])) / spp) * 0.5 / m) ** 2).sum(-1), rtol=1e-12)
+
+
+def test_all_sigmas_off_is_the_plain_spline_on_colour_and_variance(rt):
+    """Every term off, one iteration, clean buffers: w = hh, so e1 = sum(hh e0) / sum(hh) and u1 = sum(hh^2 u0) / sum(hh)^2 —
+    computed here tap by tap with python floats at pixels whose footprint lies inside the image (sum(hh) = 1)."""
+    W, H = 70, 9
+    h = halves(W, H, seed=5, hostile=False)
+    p0, q = R.dual_blocks(rt, W, H, 4, var_iter=0, n_iter=0, demodulate=False, **ALL_OFF)
+    p1, _ = R.dual_blocks(rt, W, H, 4, var_iter=0, n_iter=1, demodulate=False, **ALL_OFF)
+    e0, u0 = check(rt, h, p0, q)
+    e1, u1 = check(rt, h, p1, q)
+    for y, x in ((2, 2), (4, 33), (6, 67)):
+        ks = [(R.H5[j + 2] * R.H5[i + 2], y + j, x + i) for j in range(-2, 3) for i in range(-2, 3)]
+        assert math.isclose(u1[y, x], sum(k * k * u0[qy, qx] for k, qy, qx in ks), rel_tol=1e-12)
+        assert np.allclose(e1[y, x], sum(k * e0[qy, qx] for k, qy, qx in ks), rtol=1e-12)
+    assert (u1[2:-2, 2:-2] < u0.max()).all()                # a convex combination scaled by sum(hh^2) < 1
+
+
+def test_identical_halves_have_no_variance(rt):
+    """A == B bit for bit: v0 == 0 everywhere, every colour distance is divided by var_floor alone, the output is finite."""
+    W, H = 70, 9
+    sa, _, fa, _ = halves(W, H, seed=5, hostile=False)
+    sa[np.random.default_rng(3).random((H, W, 3)) < 0.05] = np.nan
+    h = (sa, sa.copy(), fa, fa.copy())
+    _, v0 = check(rt, h, *R.dual_blocks(rt, W, H, 4, var_iter=0, n_iter=0))
+    assert not v0.any()
+    got, var = check(rt, h, *R.dual_blocks(rt, W, H, 4))
+    assert np.isfinite(got).all() and not var.any()
+
+
+# ---- row lists -------------------------------------------------------------------------------------------------------------
+def test_shuffled_rows_give_the_image_order_result_permuted(rt):
+    W, H = 67, 35
+    h = halves(W, H, seed=9, hostile=True, nan_albedo=False)
+    p, q = R.dual_blocks(rt, W, H, 4)
+    image_order, image_var = check(rt, h, p, q)
+    rows = rt.shuffled_rows(H, 2022)
+    inv = np.argsort(rows)                                 # buffers written in `rows` order: buffer row i is image row rows[i]
+    got, var = check(rt, tuple(b[rows] for b in h), p, q, rows=rows)
+    assert_same_bits(got[inv], image_order, "shuffled rows")
+    assert_same_bits(var[inv], image_var, "shuffled rows, variance")
+    p0, q0 = R.dual_blocks(rt, W, H, 4, n_iter=0, var_iter=0)
+    got, var = check(rt, tuple(b[rows] for b in h), p0, q0, rows=rows)
+    assert_same_bits(var[inv], restate_dual(*h, p0, q0)[1], "shuffled rows, nothing but the prepare kernel")
+
+
+class Device:
+    """Both halves, the outputs and a workspace as torch buffers; call() is rt_denoise_dual_device on them."""
+
+    def __init__(self, rt, h, p, q, fill=0):
+        import torch
+        self.rt, self.p, self.q, self.torch = rt, p, q, torch
+        self.sa, self.sb = (torch.from_numpy(np.ascontiguousarray(s)).cuda() for s in h[:2])
+        self.fa, self.fb = (torch.from_numpy(np.ascontiguousarray(f).view(np.float64).reshape(-1)).cuda() for f in h[2:])
+        self.out = torch.full((p.height, p.width, 3), 7.0, dtype=torch.float64, device="cuda")
+        self.var = torch.full((p.height, p.width), 7.0, dtype=torch.float64, device="cuda")
+        self.ws = torch.full((rt.denoise_dual_workspace_bytes(p),), fill, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+
+    def call(self, out=None, var="given", rows=None, stream=None, p=None, q=None):
+        var = self.var if isinstance(var, str) else var
+        self.rt.denoise_dual_device(self.sa.data_ptr(), self.sb.data_ptr(), self.fa.data_ptr(), self.fb.data_ptr(), p or self.p, q or self.q,
+                                    (self.out if out is None else out).data_ptr(), self.ws.data_ptr(),
+                                    d_out_variance_ptr=var.data_ptr() if var is not None else None,
+                                    d_row_ids_ptr=rows.data_ptr() if rows is not None else None, stream_ptr=stream)
+
+    def results(self, out=None):
+        self.torch.cuda.synchronize()
+        return (self.out if out is None else out).cpu().numpy(), self.var.cpu().numpy()
+
+
+def test_bad_row_lists_are_refused_with_both_outputs_untouched(rt):
+    import torch
+    W, H = 12, 10
+    h = halves(W, H, hostile=False)
+    for n_iter, var_iter in ((0, 0), (0, 2), (3, 1)):
+        p, q = R.dual_blocks(rt, W, H, 4, n_iter=n_iter, var_iter=var_iter)
+        d = Device(rt, h, p, q)
+        for fault in ("repeated", "out of range", "huge"):
+            rows = np.arange(H, dtype=np.uint32)[::-1].copy()
+            rows[3] = {"repeated": rows[7], "out of range": H, "huge": 0xFFFFFFFF}[fault]
+            with pytest.raises(rt.RtError) as e:
+                rt.denoise_dual(*h, p, q, row_ids=rows)
+            assert e.value.code == F.RT_ERR_INVALID and "not a permutation" in str(e.value), fault
+            d_rows = torch.from_numpy(rows.view(np.int32)).cuda()
+            torch.cuda.synchronize()
+            with pytest.raises(rt.RtError) as e:
+                d.call(rows=d_rows)
+            assert e.value.code == F.RT_ERR_INVALID and "not a permutation" in str(e.value), fault
+            out, var = d.results()
+            assert (out == 7.0).all() and (var == 7.0).all(), (fault, "an output was written")
+        # and the good list on the same workspace afterwards
+        rows = np.arange(H, dtype=np.uint32)[::-1].copy()
+        d_rows = torch.from_numpy(rows.view(np.int32)).cuda()
+        torch.cuda.synchronize()
+        d.call(rows=d_rows)
+        out, var = d.results()
+        ref, ref_var = restate_dual(*h, p, q, rows)
+        assert_same_bits(out, ref, "good rows after bad ones")
+        assert_same_bits(var, ref_var, "good rows after bad ones, variance")
+
+
+# ---- workspace, aliasing, the optional variance ---------------------------------------------------------------------------
+@pytest.mark.parametrize("n_iter, var_iter", [(0, 0), (0, 2), (1, 0), (4, 1)])
+def test_aliasing_workspace_reuse_and_poisoned_workspace(rt, n_iter, var_iter):
+    import torch
+    W, H = 67, 35
+    h = halves(W, H, seed=3, hostile=True, nan_albedo=False)
+    rows = rt.shuffled_rows(H, 7)
+    p, q = R.dual_blocks(rt, W, H, 4, n_iter=n_iter, var_iter=var_iter)
+    ref, ref_var = restate_dual(*h, p, q, rows)
+    d = Device(rt, h, p, q, fill=0xFF)                     # a workspace of 0xFF bytes
+    d_rows = torch.from_numpy(rows.view(np.int32)).cuda()
+    torch.cuda.synchronize()
+
+    def same(what, out=None, r=(ref, ref_var)):
+        got, var = d.results(out)
+        assert_same_bits(got, r[0], what)
+        assert_same_bits(var, r[1], (what, "variance"))
+
+    d.call(rows=d_rows)
+    same("poisoned workspace")
+    d.out.fill_(7.0), d.var.fill_(7.0)
+    d.call(rows=d_rows)                                    # the same workspace again
+    same("workspace reused")
+    # ... with no row list after a call with one (the inverse map of the last call is still in the workspace)
+    d.out.fill_(7.0), d.var.fill_(7.0)
+    d.call()
+    same("workspace reused without rows", r=restate_dual(*h, p, q))
+    # ... without the variance: the same colour bits, the variance buffer untouched
+    d.out.fill_(7.0), d.var.fill_(7.0)
+    d.call(var=None, rows=d_rows)
+    got, var = d.results()
+    assert_same_bits(got, ref, "no variance output")
+    assert (var == 7.0).all()
+    # in place: the output is half B, then half A (B restored first)
+    d.call(out=d.sb, rows=d_rows)
+    same("output aliasing half B", out=d.sb)
+    d.sb.copy_(torch.from_numpy(np.ascontiguousarray(h[1])))
+    d.call(out=d.sa, rows=d_rows)
+    same("output aliasing half A", out=d.sa)
+
+
+# ---- torch buffers, a stream of the caller's, the tone map behind it ------------------------------------------------------
+def test_device_form_on_torch_buffers_then_tonemap_on_the_same_stream(rt):
+    import torch
+    W, H, spp = 130, 21, 4
+    h = halves(W, H, spp=spp, seed=11, hostile=False)
+    h[0][np.random.default_rng(2).random((H, W, 3)) < 0.05] = np.nan
+    p, q = R.dual_blocks(rt, W, H, spp)
+    d = Device(rt, h, p, q)
+    d_u8 = torch.zeros((H, W, 3), dtype=torch.uint8, device="cuda")
+    stream = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    with torch.cuda.stream(stream):
+        d.call(stream=stream.cuda_stream)
+        F.check(rt.lib().rt_tonemap_device(C.c_void_p(d.out.data_ptr()), W * H, 2 * spp, C.c_void_p(d_u8.data_ptr()), C.c_void_p(stream.cuda_stream)))
+    stream.synchronize()
+    ref, ref_var = restate_dual(*h, p, q)
+    out, var = d.results()
+    assert_same_bits(out, ref, "device form")
+    assert_same_bits(var, ref_var, "device form, variance")
+    assert np.array_equal(d_u8.cpu().numpy(), rt.write_color(ref, 2 * spp))
+    for dev, host in zip((d.sa, d.sb), h[:2]):             # the inputs are read only
+        assert np.array_equal(dev.cpu().numpy().view(np.uint64), host.view(np.uint64))
+
+
+# ---- end to end ------------------------------------------------------------------------------------------------------------
+# Views where the CPU evaluation (profiles/denoise_dual_grid.log) has mse_dual <= 0.95 * mse_single: there the dual filter must beat
+# rt_denoise on the device too. random_scene's 0.97 is inside the margin: both numbers are printed, nothing is asserted.
+BEATS_SINGLE = {"cornell_box", "final_scene", "cornell_smoke"}
+
+
+@pytest.mark.parametrize("name, W, H", R.GRID_VIEWS + [R.HELD_OUT_VIEW])
+def test_render_features_denoise_dual_end_to_end(rt, name, W, H):
+    """Two frames of 2 spp at seed 2022 from ONE render and ONE feature call (n_frames = 2, two_frame_rows of the shuffled
+    list), the default parameters: the result is the restatement's bit for bit and closer to a 512 spp render (seed 7) than
+    the noisy 4 spp frame A + B. MSE of the display value sqrt(clip(c, 0, 0.999)) on the CPU oracle's renders
+    (tools/denoise_dual_grid.py, the chosen point sigma_color 2, var_iter 1, var_floor 1e-6):
+
+        view            mse_noisy   mse_single  mse_dual    dual/noisy  dual/single
+        cornell_box     3.0346e-02  3.2984e-03  2.6829e-03  0.088       0.813
+        final_scene     4.4665e-02  2.0989e-02  1.3631e-02  0.305       0.649
+        random_scene    8.7606e-03  5.5353e-03  5.3776e-03  0.614       0.972   (no 5 % margin: printed only)
+        cornell_smoke   3.5304e-02  9.8554e-03  6.7149e-03  0.190       0.681   (never seen by the grid)
+
+    mse_single is rt_denoise at its defaults on A + B with features FA + FB and spp 4."""
+    half = R.HALF_SPP
+    s = rt.HostScene(name, seed=2022)
+    cam, bg = s.default_view(W / H)
+    dev = rt.DeviceScene(s.desc)
+    rows = rt.shuffled_rows(H, 2022)
+    params = rt.make_params(W, H, half, 50, bg, seed=R.SEED, n_frames=2)
+    sums = dev.render(cam, params, rt.two_frame_rows(rows, H))
+    feat = dev.features(cam, params, rt.two_frame_rows(rows, H))
+    h = (sums[:H], sums[H:], feat[:H], feat[H:])
+    got, _ = check(rt, h, *R.dual_blocks(rt, W, H, half), rows=rows, what=name)
+    noisy = h[0] + h[1]
+    single = rt.denoise(noisy, R.add_features(h[2], h[3]), rt.denoise_params(W, H, 2 * half), row_ids=rows)
+    assert_same_bits(single, restate_single(noisy, R.add_features(h[2], h[3]), rt.denoise_params(W, H, 2 * half), rows), "rt_denoise")
+    reference = dev.render(cam, rt.make_params(W, H, R.REF_SPP, 50, bg, seed=R.REF_SEED), rows)
+    target = R.display(reference, R.REF_SPP)
+    mse_noisy, mse_single, mse_dual = (R.mse(x, 2 * half, target) for x in (noisy, single, got))
+    print("%s %dx%d: MSE noisy %.6e, rt_denoise %.6e, dual %.6e; dual/noisy %.3f, dual/single %.3f"
+          % (name, W, H, mse_noisy, mse_single, mse_dual, mse_dual / mse_noisy, mse_dual / mse_single))
+    assert mse_dual < mse_noisy
+    if name in BEATS_SINGLE:
+        assert mse_dual < mse_single
