@@ -22,6 +22,20 @@ class rto_hit_record(C.Structure):
                 ("t", C.c_double), ("u", C.c_double), ("v", C.c_double), ("mat", C.c_uint32), ("rng_draws", C.c_uint32)]
 
 
+class rto_shade_census(C.Structure):
+    """rt_oracle.h: the shade census. Indices: ARMS, MIX, DIEL, END below; a trailing [2] is (no / back face, yes / front face)."""
+    _fields_ = [("scatter", C.c_uint64 * 2 * 5 * 5 * 5), ("emitted", C.c_uint64 * 2 * 4), ("light_draw", C.c_uint64 * 6),
+                ("mixture_choice", C.c_uint64 * 3), ("light_pdf", C.c_uint64 * 2 * 6), ("dielectric", C.c_uint64 * 2 * 3),
+                ("metal", C.c_uint64 * 2), ("path_end", C.c_uint64 * 2 * 2 * 4)]
+
+
+ARM_SPHERE, ARM_RECT_XY, ARM_RECT_XZ, ARM_RECT_YZ, ARM_FLIPPED, ARM_OTHER = range(6)
+TEX_NONE = 4
+MIX_LIGHT, MIX_COSINE, MIX_COSINE_ONLY = range(3)
+DIEL_CANNOT_REFRACT, DIEL_SCHLICK, DIEL_REFRACT = range(3)
+END_MISS, END_LIGHT_FRONT, END_LIGHT_BACK, END_DEPTH = range(4)
+
+
 LIBM_LIB_PATH = os.path.join(_HERE, "librt_oracle_libm.so")
 
 
@@ -107,6 +121,10 @@ def _bind(L):
     L.rto_uses_own_math.restype = C.c_int
     L.rto_path_math.argtypes = [C.c_int, dbl, dbl]
     L.rto_path_math.restype = dbl
+    L.rto_census_enable.argtypes = [C.c_int]
+    L.rto_census_enable.restype = None
+    L.rto_census_read.argtypes = [P(rto_shade_census)]
+    L.rto_census_read.restype = None
     return L
 
 
@@ -129,6 +147,19 @@ def render_cpu(desc, cam, params, row_ids, n_threads=1, want_stats=False, libm=F
     if rc < 0:
         raise RuntimeError("oracle error %d: %s" % (rc, L.rto_last_error().decode()))
     return (out, st) if want_stats else out
+
+
+def census_begin():
+    """Zero the shade census and switch it on: render_cpu and ray_color calls count into it until census_end()."""
+    lib().rto_census_enable(1)
+
+
+def census_end():
+    """Switch the shade census off → {field: uint64 array} of rto_shade_census (scatter[mat][leaf][top][front], ...)."""
+    lib().rto_census_enable(0)
+    c = rto_shade_census()
+    lib().rto_census_read(C.byref(c))
+    return {name: np.ctypeslib.as_array(getattr(c, name)).astype(np.uint64) for name, _ in rto_shade_census._fields_}
 
 
 def write_color(rgb_sum, spp):

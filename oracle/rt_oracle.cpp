@@ -21,7 +21,9 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <atomic>
 #include <chrono>
+#include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
@@ -90,7 +92,44 @@ struct Ctx {
     Rng *rng;
     rt_stats *st;           // never null
     bool in_light_pdf = false;
+    rto_shade_census *cen = nullptr;   // the shade census of the calling thread (null: off, the default)
+    bool tainted = false;              // census: some record of the path in flight has a pdf of 0 / NaN or a non-finite weight
 };
+
+// ---- shade census (rt_oracle.h): what ray_color did, counted apart from rt_stats -----------------------------------
+// Off by default: Ctx::cen stays null and every site below is one untaken branch. A call counts into a census of its own
+// (render_cpu: one per worker thread) and adds it to the process-wide one under a mutex when it is done.
+std::atomic<int> g_census_on{0};
+std::mutex g_census_mu;
+rto_shade_census g_census;
+
+void census_add(const rto_shade_census &c) {
+    static_assert(sizeof(rto_shade_census) % sizeof(uint64_t) == 0, "the census is an array of counters");
+    std::lock_guard<std::mutex> lock(g_census_mu);
+    const uint64_t *src = reinterpret_cast<const uint64_t *>(&c);
+    uint64_t *dst = reinterpret_cast<uint64_t *>(&g_census);
+    for (size_t i = 0; i < sizeof(rto_shade_census) / sizeof(uint64_t); i++) dst[i] += src[i];
+}
+// The arm of Hittable::pdf_value / random a light-list entry takes (light_pdf_value, light_random below).
+int light_arm(const rt_scene_desc &s, uint32_t ref) {
+    if (ref & RT_REF_FLIP) return RTO_ARM_FLIPPED;
+    uint32_t kind = RT_REF_KIND(ref);
+    if (kind == RT_KIND_SPHERE) return RTO_ARM_SPHERE;
+    if (kind == RT_KIND_RECT) {
+        uint32_t axis = s.rects[RT_REF_INDEX(ref)].axis;
+        return axis == RT_RECT_XY ? RTO_ARM_RECT_XY : axis == RT_RECT_XZ ? RTO_ARM_RECT_XZ : RTO_ARM_RECT_YZ;
+    }
+    return RTO_ARM_OTHER;
+}
+// One bounce record (weight, pdf) as the device's tape keeps it: does it taint the path?
+bool record_taints(Vec3 w, double pdf) {
+    return !(std::isfinite(w.x) && std::isfinite(w.y) && std::isfinite(w.z) && pdf == pdf && pdf != 0.0);
+}
+void census_path_end(Ctx &c, int cause, Color terminal) {
+    if (!c.cen) return;
+    bool zero = terminal.x == 0.0 && terminal.y == 0.0 && terminal.z == 0.0;
+    c.cen->path_end[cause][c.tainted ? 1 : 0][zero ? 1 : 0]++;
+}
 
 inline Vec3 v3(const double d[3]) { return Vec3(d[0], d[1], d[2]); }
 
@@ -427,6 +466,15 @@ Color texture_value(const rt_scene_desc &s, uint32_t tex, double u, double v, Po
     }
 }
 
+// Census only: the kind of the texture a chain of checkers ends in at p (the selection rule of texture_value above).
+uint32_t leaf_texture_kind(const rt_scene_desc &s, uint32_t tex, Point3 p) {
+    for (uint32_t guard = 0; guard <= s.n_textures && s.textures[tex].kind == RT_TEX_CHECKER; guard++) {
+        double sines = om::sin_(p.x * 10.0) * om::sin_(p.y * 10.0) * om::sin_(p.z * 10.0);
+        tex = sines < 0.0 ? s.textures[tex].a : s.textures[tex].b;
+    }
+    return s.textures[tex].kind;
+}
+
 // ---- samplers, basic/vec.rs:69-117, basic/pdf.rs:12-21 ------------------------
 // (Loops cut at RT_MAX_REJECT tries like the device code: unreachable, see rt_math.h.)
 Vec3 random_in_unit_sphere(Rng &rng) {
@@ -469,8 +517,9 @@ Vec3 random_cosine_direction(Rng &rng) {
 // ---- Hittable::pdf_value / random for light objects ----------------------------
 // Sphere: sphere.rs:75-90. Rects: aarect.rs:74-93,157-176,240-259. Everything
 // else (incl. any wrapper, FlipFace too): the trait defaults 0 / (1,0,0), mod.rs:62-67.
-double light_pdf_value(Ctx &c, uint32_t ref, Point3 o, Vec3 v) {
+double light_pdf_value_of(Ctx &c, uint32_t ref, Point3 o, Vec3 v, bool &was_hit) {
     const rt_scene_desc &s = *c.s;
+    was_hit = false;
     if (ref & RT_REF_FLIP) return 0.0;
     uint32_t kind = RT_REF_KIND(ref), idx = RT_REF_INDEX(ref);
     HitRecord rec;
@@ -478,6 +527,7 @@ double light_pdf_value(Ctx &c, uint32_t ref, Point3 o, Vec3 v) {
         const rt_sphere &q = s.spheres[idx];
         c.st->light_pdf_tests++;
         if (!sphere_hit_at(v3(q.center), q.radius, q.mat, Ray(o, v, 0.0), 0.001, rtm::INF, rec)) return 0.0;
+        was_hit = true;
         double cos_max = rtm::sqrt_(1.0 - q.radius * q.radius / (v3(q.center) - o).length_sqr());
         double solid_angle = 2.0 * rtm::PI * (1.0 - cos_max);
         return 1.0 / solid_angle;
@@ -486,6 +536,7 @@ double light_pdf_value(Ctx &c, uint32_t ref, Point3 o, Vec3 v) {
         const rt_rect &q = s.rects[idx];
         c.st->light_pdf_tests++;
         if (!rect_hit(q, Ray(o, v, 0.0), 0.001, rtm::INF, rec)) return 0.0;
+        was_hit = true;
         double area = (q.a1 - q.a0) * (q.b1 - q.b0);
         double dis_sqr = rec.t * rec.t * v.length_sqr();
         double cosv = rtm::fabs_(rtm::dot(v, rec.normal) / v.length());
@@ -493,8 +544,15 @@ double light_pdf_value(Ctx &c, uint32_t ref, Point3 o, Vec3 v) {
     }
     return 0.0;
 }
+double light_pdf_value(Ctx &c, uint32_t ref, Point3 o, Vec3 v) {
+    bool was_hit;
+    double pdf = light_pdf_value_of(c, ref, o, v, was_hit);
+    if (c.cen) c.cen->light_pdf[light_arm(*c.s, ref)][was_hit ? 1 : 0]++;
+    return pdf;
+}
 Vec3 light_random(Ctx &c, uint32_t ref, Point3 o) {
     const rt_scene_desc &s = *c.s;
+    if (c.cen) c.cen->light_draw[light_arm(s, ref)]++;
     if (ref & RT_REF_FLIP) return Vec3(1.0, 0.0, 0.0);
     uint32_t kind = RT_REF_KIND(ref), idx = RT_REF_INDEX(ref);
     if (kind == RT_KIND_SPHERE) {
@@ -561,6 +619,7 @@ bool scatter(Ctx &c, const rt_material &m, const Ray &r_in, const HitRecord &rec
             return true;
         case RT_MAT_METAL: {                                     // mod.rs:85-96
             Vec3 reflected = rtm::reflect(rtm::to_unit(r_in.dir), rec.normal);
+            if (c.cen) c.cen->metal[m.param > 0.0 ? 1 : 0]++;
             srec.has_specular = true;
             srec.specular_ray = Ray(rec.p, reflected + random_in_unit_sphere(*c.rng) * m.param, 0.0);
             srec.attenuation = v3(m.albedo);
@@ -574,6 +633,9 @@ bool scatter(Ctx &c, const rt_material &m, const Ray &r_in, const HitRecord &rec
             double sin_theta = rtm::sqrt_(1.0 - cos_theta * cos_theta);
             bool cannot_refract = refraction_ratio * sin_theta > 1.0;
             double random_double = c.rng->gen_range(0.0, 1.0);
+            if (c.cen)
+                c.cen->dielectric[cannot_refract ? RTO_DIEL_CANNOT_REFRACT : reflectance(cos_theta, refraction_ratio) > random_double ? RTO_DIEL_SCHLICK : RTO_DIEL_REFRACT]
+                                 [rec.front_face ? 1 : 0]++;
             Vec3 direction = (cannot_refract || reflectance(cos_theta, refraction_ratio) > random_double)
                                  ? rtm::reflect(unit_direction, rec.normal)
                                  : rtm::refract(unit_direction, rec.normal, refraction_ratio);
@@ -606,16 +668,30 @@ Color emitted(Ctx &c, const rt_material &m, const HitRecord &rec) {
 
 // ---- ray_color, main.rs:233-278 --------------------------------------------------
 Color ray_color(Ctx &c, const Ray &r, Color background, double t_min, int depth) {
-    if (depth <= 0) return Color(0.0, 0.0, 0.0);
+    if (depth <= 0) { census_path_end(c, RTO_END_DEPTH, Color(0.0, 0.0, 0.0)); return Color(0.0, 0.0, 0.0); }
     c.st->rays++;
     HitRecord rec;
-    if (!hit(c, c.s->root, r, t_min, rtm::F64_MAX, rec)) return background;
+    if (!hit(c, c.s->root, r, t_min, rtm::F64_MAX, rec)) { census_path_end(c, RTO_END_MISS, background); return background; }
     const rt_material &m = c.s->materials[rec.mat];
     Color emit = emitted(c, m, rec);
     ScatterRecord srec;
-    if (!scatter(c, m, r, rec, srec)) return emit;
-    if (srec.has_specular)
+    if (!scatter(c, m, r, rec, srec)) {
+        if (c.cen) {
+            c.cen->emitted[leaf_texture_kind(*c.s, m.tex, rec.p)][rec.front_face ? 1 : 0]++;
+            census_path_end(c, rec.front_face ? RTO_END_LIGHT_FRONT : RTO_END_LIGHT_BACK, emit);
+        }
+        return emit;
+    }
+    if (c.cen) {
+        bool textured = m.kind == RT_MAT_LAMBERTIAN || m.kind == RT_MAT_ISOTROPIC;
+        uint32_t top = textured ? c.s->textures[m.tex].kind : (uint32_t)RTO_TEX_NONE;
+        uint32_t leaf = textured ? leaf_texture_kind(*c.s, m.tex, rec.p) : (uint32_t)RTO_TEX_NONE;
+        c.cen->scatter[m.kind][leaf][top][rec.front_face ? 1 : 0]++;
+    }
+    if (srec.has_specular) {
+        if (c.cen && record_taints(srec.attenuation, 1.0)) c.tainted = true;
         return srec.attenuation * ray_color(c, srec.specular_ray, background, t_min, depth - 1);
+    }
     Vec3 dir;
     double pdf_val;
     if (c.s->n_lights == 0) {
@@ -623,14 +699,18 @@ Color ray_color(Ctx &c, const Ray &r, Color background, double t_min, int depth)
         // list; here the mixture degenerates to the cosine pdf alone.
         dir = srec.cos_uvw.local_vec(random_cosine_direction(*c.rng));
         pdf_val = cos_pdf_value(srec.cos_uvw, dir);
+        if (c.cen) c.cen->mixture_choice[RTO_MIX_COSINE_ONLY]++;
     } else {
         // MixturePdf(HittablePdf(lights, rec.p), cos): pdf.rs:94-104.
-        if (c.rng->gen_range(0.0, 1.0) < 0.5) dir = lights_random(c, rec.p);
+        bool light_half = c.rng->gen_range(0.0, 1.0) < 0.5;
+        if (c.cen) c.cen->mixture_choice[light_half ? RTO_MIX_LIGHT : RTO_MIX_COSINE]++;
+        if (light_half) dir = lights_random(c, rec.p);
         else dir = srec.cos_uvw.local_vec(random_cosine_direction(*c.rng));
         pdf_val = 0.5 * lights_pdf_value(c, rec.p, dir) + 0.5 * cos_pdf_value(srec.cos_uvw, dir);
     }
     Ray scattered(rec.p, dir, r.tm);
     double spdf = scattering_pdf(m, rec, scattered);
+    if (c.cen && record_taints(srec.attenuation * spdf, pdf_val)) c.tainted = true;
     return emit + ((srec.attenuation * spdf) * ray_color(c, scattered, background, t_min, depth - 1)) / pdf_val;
 }
 
@@ -647,7 +727,7 @@ Ray get_ray(const rt_camera &cam, double s, double t, Rng &rng) {
 
 // ---- one pixel: main.rs:141-152 ---------------------------------------------------
 void render_pixel(const rt_scene_desc &s, const rt_camera &cam, const rt_params &p, uint32_t g, uint32_t x,
-                  rt_stats &st, double out[3]) {
+                  rt_stats &st, rto_shade_census *cen, double out[3]) {
     uint32_t frame = g / p.height, y = g % p.height;
     uint64_t pixel = (uint64_t)y * p.width + x;
     Color background = v3(p.background);
@@ -659,6 +739,7 @@ void render_pixel(const rt_scene_desc &s, const rt_camera &cam, const rt_params 
         for (uint32_t smp = s0; smp < s1; smp++) {
             Rng rng(rtm::path_key(p.seed, frame, pixel, smp));
             Ctx c{&s, &rng, &st};
+            c.cen = cen;
             double rand_u = rng.gen_f64();
             double rand_v = rng.gen_f64();
             double u = ((double)x + rand_u) / (double)(p.width - 1);
@@ -707,6 +788,9 @@ int rt_render_cpu(const rt_scene_desc *scene, const rt_camera *cam, const rt_par
     if ((uint32_t)n_threads > params->n_rows && params->n_rows > 0) n_threads = (int)params->n_rows;
     std::vector<rt_stats> per(n_threads);
     for (auto &s : per) std::memset(&s, 0, sizeof s);
+    const bool census = g_census_on.load() != 0;
+    std::vector<rto_shade_census> per_census(census ? n_threads : 0);      // (one per worker, like the counters)
+    for (auto &c : per_census) std::memset(&c, 0, sizeof c);
     auto t0 = std::chrono::steady_clock::now();
     auto work = [&](int tid) {
         uint32_t section = params->n_rows / (uint32_t)n_threads;
@@ -714,7 +798,7 @@ int rt_render_cpu(const rt_scene_desc *scene, const rt_camera *cam, const rt_par
         uint32_t end = tid == n_threads - 1 ? params->n_rows : beg + section;
         for (uint32_t yi = beg; yi < end; yi++)
             for (uint32_t x = 0; x < params->width; x++)
-                render_pixel(*scene, *cam, *params, params->row_ids[yi], x, per[tid],
+                render_pixel(*scene, *cam, *params, params->row_ids[yi], x, per[tid], census ? &per_census[tid] : nullptr,
                              out_rgb_sum + ((size_t)yi * params->width + x) * 3);
     };
     if (n_threads == 1) work(0);
@@ -724,12 +808,25 @@ int rt_render_cpu(const rt_scene_desc *scene, const rt_camera *cam, const rt_par
         for (auto &t : pool) t.join();
     }
     auto t1 = std::chrono::steady_clock::now();
+    for (auto &c : per_census) census_add(c);
     if (stats) {
         std::memset(stats, 0, sizeof *stats);
         for (auto &s : per) add_stats(*stats, s);
         stats->ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
     }
     return RT_OK;
+}
+
+// The shade census: switched on (and zeroed) or off, and read, by entry points of its own. rt_render_cpu and rto_ray_color
+// count into it while it is on; nothing else about them changes.
+void rto_census_enable(int on) {
+    std::lock_guard<std::mutex> lock(g_census_mu);
+    if (on) std::memset(&g_census, 0, sizeof g_census);
+    g_census_on.store(on ? 1 : 0);
+}
+void rto_census_read(rto_shade_census *out) {
+    std::lock_guard<std::mutex> lock(g_census_mu);
+    if (out) *out = g_census;
 }
 
 // write_color, main.rs:280-299.
@@ -768,8 +865,11 @@ int rto_ray_color(const rt_scene_desc *scene, const double ray[7], const double 
     rt_stats local; std::memset(&local, 0, sizeof local);
     Rng rng(rng_state);
     Ctx c{scene, &rng, stats ? stats : &local};
+    rto_shade_census cen;
+    if (g_census_on.load()) { std::memset(&cen, 0, sizeof cen); c.cen = &cen; }
     Ray r(Vec3(ray[0], ray[1], ray[2]), Vec3(ray[3], ray[4], ray[5]), ray[6]);
     Color col = ray_color(c, r, v3(background), t_min, depth);
+    if (c.cen) census_add(cen);
     out_rgb[0] = col.x; out_rgb[1] = col.y; out_rgb[2] = col.z;
     (stats ? stats : &local)->rng_draws += rng.draws;
     return RT_OK;

@@ -19,6 +19,27 @@ typedef struct rto_hit_record {       /* HitRecord, hittable/mod.rs:18-26 */
 
 enum rto_math_op { RTO_SIN = 0, RTO_COS = 1, RTO_ACOS = 2, RTO_ATAN2 = 3, RTO_LOG = 4, RTO_SQRT = 5, RTO_DIV = 6 };
 
+/* The shade census: what rto_ray_color did on the paths of rt_render_cpu / rto_ray_color calls made while it was on.
+ * Off by default; rt_stats, results and every other counter are the same with it on or off. Indices are the enums of
+ * rt2022.h (rt_material_kind, rt_texture_kind) and the ones below; a [2] is [0] = no / back face, [1] = yes / front face. */
+enum rto_light_arm { RTO_ARM_SPHERE = 0, RTO_ARM_RECT_XY = 1, RTO_ARM_RECT_XZ = 2, RTO_ARM_RECT_YZ = 3, RTO_ARM_FLIPPED = 4, RTO_ARM_OTHER = 5 };
+enum rto_tex_none { RTO_TEX_NONE = 4 };                      /* the material reads no texture (Metal, Dielectric) */
+enum rto_mixture_choice { RTO_MIX_LIGHT = 0, RTO_MIX_COSINE = 1, RTO_MIX_COSINE_ONLY = 2 /* n_lights == 0: no choice is drawn */ };
+enum rto_dielectric_outcome { RTO_DIEL_CANNOT_REFRACT = 0, RTO_DIEL_SCHLICK = 1, RTO_DIEL_REFRACT = 2 };
+enum rto_path_end { RTO_END_MISS = 0, RTO_END_LIGHT_FRONT = 1, RTO_END_LIGHT_BACK = 2, RTO_END_DEPTH = 3 };
+typedef struct rto_shade_census {
+    uint64_t scatter[5][5][5][2];   /* Material::scatter -> Some: [material kind][leaf texture kind, checkers resolved][top texture kind][front_face] */
+    uint64_t emitted[4][2];         /* a DiffuseLight was hit: [leaf texture kind][front_face] */
+    uint64_t light_draw[6];         /* HittableList::random, by the arm of the entry drawn */
+    uint64_t mixture_choice[3];     /* MixturePdf::generate: light half, cosine half; cosine-only mode */
+    uint64_t light_pdf[6][2];       /* Hittable::pdf_value of one entry: [arm][the ray hit it] */
+    uint64_t dielectric[3][2];      /* [outcome][front_face] */
+    uint64_t metal[2];              /* fuzz == 0, fuzz > 0 */
+    uint64_t path_end[4][2][2];     /* [cause][tainted: a record with pdf 0 / NaN or a non-finite weight][terminal radiance == (0, 0, 0)] */
+} rto_shade_census;
+void rto_census_enable(int on);     /* on != 0: zero the census and start counting; 0: stop (the counts stay readable) */
+void rto_census_read(rto_shade_census *out);
+
 /* CPU twin of rt_render (main.rs:109-162 threading scheme with n_threads workers). */
 int rt_render_cpu(const rt_scene_desc *scene, const rt_camera *cam, const rt_params *params,
                   double *out_rgb_sum, rt_stats *stats, int n_threads);

@@ -417,8 +417,9 @@ RT_DEV double perlin_turb(const rt_perlin &pl, Vec3 p, int depth) {
     return rtm::fabs_(accum);
 }
 RT_DEV Vec3 texture_value(const SceneDev &s, uint32_t tex, double u, double v, Vec3 p) {
-    // CheckerTexture only selects one of its two children: resolve iteratively.
-    for (int lvl = 0; lvl < 8; lvl++) {
+    // CheckerTexture only selects one of its two children: resolve iteratively. (kCheckerDepth levels: rt_scene_create
+    // accepts no deeper chain, so the texture after the loop is never a checker.)
+    for (int lvl = 0; lvl < kCheckerDepth; lvl++) {
         const rt_texture &t = s.textures[tex];
         if (t.kind != RT_TEX_CHECKER) break;
         double sines = rtm::sin_(p.x * 10.0) * rtm::sin_(p.y * 10.0) * rtm::sin_(p.z * 10.0);
@@ -441,7 +442,7 @@ RT_DEV Vec3 texture_value(const SceneDev &s, uint32_t tex, double u, double v, V
         const uint8_t *px = s.image_data + im.offset + 3 * (j * im.width + i);
         return Vec3((double)px[0] * color_scale, (double)px[1] * color_scale, (double)px[2] * color_scale);
     }
-    return ld3(t.color);   // SolidColor (a Checker nested deeper than 8 falls back to its colour field)
+    return ld3(t.color);   // SolidColor
 }
 
 // ---- samplers, vec.rs:69-117, pdf.rs:12-21 ------------------------------------------

@@ -134,6 +134,8 @@ enum SlotKind : uint32_t {
 
 // `mat` of the device copies of the primitive pools = material index | slot kind of a hit on it << kMatKindShift.
 constexpr uint32_t kMatKindShift = 24, kMatIndexMask = (1u << kMatKindShift) - 1u;
+// CheckerTextures texture_value (pt_common.hpp) follows before the texture that answers: rt_scene_create refuses a deeper chain.
+constexpr int kCheckerDepth = 8;
 
 // A pool of path slots in HBM, one array of records per field; segment b (= shade workgroup b) owns
 // the slots [b*kSlotsPerBlock, (b+1)*kSlotsPerBlock) for the whole frame.

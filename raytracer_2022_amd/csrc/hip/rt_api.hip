@@ -42,11 +42,17 @@ int guarded(F &&f) {
 // ---- validation -------------------------------------------------------------------
 struct Validator {
     const rt_scene_desc &d;
-    std::vector<int32_t> node_need;      // memo: stack need of each node (-1 unknown, -2 on the DFS stack)
-    std::vector<int32_t> node_xdepth;
+    // What need() knows of a record that has children: the stack entries trace<> needs below it, the deepest nesting of
+    // movers below it, and whether a medium lies below it (media do not nest inside a medium's boundary).
+    struct Need {
+        int32_t need = kUnknown, xdepth = 0;
+        bool medium = false;
+    };
+    static constexpr int32_t kUnknown = -1, kOnStack = -2;       // Need::need of a record not yet walked / being walked
+    std::vector<Need> node_memo, xform_memo, list_memo, medium_memo;     // one walk per record, however many paths lead to it
     mutable bool general_boundaries = false;   // some medium boundary is more than a primitive under movers
-    bool in_boundary = false;                  // need(): inside a medium's boundary (media do not nest there)
-    explicit Validator(const rt_scene_desc &desc) : d(desc), node_need(desc.n_nodes, -1), node_xdepth(desc.n_nodes, 0) {}
+    explicit Validator(const rt_scene_desc &desc)
+        : d(desc), node_memo(desc.n_nodes), xform_memo(desc.n_xforms), list_memo(desc.n_lists), medium_memo(desc.n_media) {}
 
     uint32_t pool_size(uint32_t kind) const {
         switch (kind) {
@@ -140,8 +146,11 @@ struct Validator {
         }
         for (uint32_t i = 0; i < d.n_images; i++) {
             const rt_image &im = d.images[i];
-            RT_REQUIRE(im.offset + (uint64_t)im.width * im.height * 3 <= d.image_data_bytes, RT_ERR_INVALID, "image: data out of range");
+            // offset + 3 * width * height <= image_data_bytes, without a sum or a product that can wrap
+            const uint64_t pixels = (uint64_t)im.width * im.height;            // < 2^64: both are 32-bit
+            RT_REQUIRE(im.offset <= d.image_data_bytes && pixels <= (d.image_data_bytes - im.offset) / 3, RT_ERR_INVALID, "image: data out of range");
         }
+        check_checkers();
         for (uint32_t i = 0; i < d.n_perlins; i++)
             for (int k = 0; k < 256; k++) {
                 const rt_perlin &p = d.perlins[i];
@@ -149,60 +158,75 @@ struct Validator {
             }
     }
 
-    // Stack entries trace<> needs while processing `ref` (its own slot included), and
-    // the deepest nesting of movers below it. Cycles are rejected.
-    void need(uint32_t ref, int depth, int32_t &out_need, int32_t &out_xdepth) {
+    // Chains of CheckerTextures: texture_value (pt_common.hpp) follows at most kCheckerDepth checkers to the texture that
+    // answers, where the reference recurses to the leaf (texture/mod.rs:51-60). A deeper chain would render differently and
+    // a cyclic one has no leaf at all: both are refused. One walk per texture (depth[] memoises).
+    void check_checkers() const {
+        std::vector<int32_t> depth(d.n_textures, kUnknown);      // checkers on the longest chain from the texture to a leaf
+        std::vector<uint32_t> stack;
+        for (uint32_t t0 = 0; t0 < d.n_textures; t0++) {
+            if (depth[t0] != kUnknown) continue;
+            stack.push_back(t0);
+            while (!stack.empty()) {
+                const uint32_t t = stack.back();
+                if (d.textures[t].kind != RT_TEX_CHECKER) { depth[t] = 0; stack.pop_back(); continue; }
+                depth[t] = kOnStack;
+                const uint32_t kids[2] = {d.textures[t].a, d.textures[t].b};
+                bool pushed = false;
+                for (uint32_t k : kids) {
+                    RT_REQUIRE(depth[k] != kOnStack, RT_ERR_INVALID, "checker: cycle among checker children");      // (k == t too)
+                    if (depth[k] == kUnknown) { stack.push_back(k); pushed = true; break; }
+                }
+                if (pushed) continue;
+                depth[t] = 1 + std::max(depth[kids[0]], depth[kids[1]]);
+                stack.pop_back();
+            }
+        }
+        for (uint32_t t = 0; t < d.n_textures; t++)
+            RT_REQUIRE(depth[t] <= kCheckerDepth, RT_ERR_UNSUPPORTED,
+                       "checker: textures nested deeper than " + std::to_string(kCheckerDepth) + " checkers (kCheckerDepth)");
+    }
+
+    // Stack entries trace<> needs while processing `ref` (its own slot included), the deepest nesting of movers below it and
+    // whether a medium lies below it. Every node, mover, list and medium is walked once and remembered, so the walk is linear
+    // in the scene's records however many paths lead to a shared one; meeting a record that is still being walked is a cycle.
+    Need need(uint32_t ref, int depth) {
         RT_REQUIRE(depth < 4096, RT_ERR_UNSUPPORTED, "scene graph too deep");
         uint32_t kind = RT_REF_KIND(ref), idx = RT_REF_INDEX(ref);
+        Need *memo = kind == RT_KIND_NODE ? &node_memo[idx] : kind >= RT_KIND_TRANSLATE && kind <= RT_KIND_ZOOM ? &xform_memo[idx]
+                   : kind == RT_KIND_LIST ? &list_memo[idx] : kind == RT_KIND_MEDIUM ? &medium_memo[idx] : nullptr;
+        if (!memo) return Need{1, 0, false};                      // a primitive
+        if (kind == RT_KIND_NODE) RT_REQUIRE(!(ref & RT_REF_FLIP), RT_ERR_UNSUPPORTED, "FlipFace directly on a BvhNode ref: push the flip down to the leaves");
+        if (kind == RT_KIND_LIST) RT_REQUIRE(!(ref & RT_REF_FLIP), RT_ERR_UNSUPPORTED, "FlipFace directly on a HittableList ref: push the flip down to the items");
+        RT_REQUIRE(memo->need != kOnStack, RT_ERR_INVALID,
+                   kind == RT_KIND_NODE ? "cycle in the BVH" : "cycle in the scene graph (a list, mover or medium that contains itself)");
+        if (memo->need != kUnknown) return *memo;
+        memo->need = kOnStack;
+        Need out;
         if (kind == RT_KIND_NODE) {
-            RT_REQUIRE(!(ref & RT_REF_FLIP), RT_ERR_UNSUPPORTED, "FlipFace directly on a BvhNode ref: push the flip down to the leaves");
-            RT_REQUIRE(node_need[idx] != -2, RT_ERR_INVALID, "cycle in the BVH");
-            if (node_need[idx] >= 0) { out_need = node_need[idx]; out_xdepth = node_xdepth[idx]; return; }
-            node_need[idx] = -2;
-            int32_t nl, xl, nr, xr;
-            need(d.nodes[idx].left, depth + 1, nl, xl);
-            if (d.nodes[idx].right == d.nodes[idx].left) { nr = nl; xr = xl; }
-            else need(d.nodes[idx].right, depth + 1, nr, xr);
-            out_need = std::max(1 + nl, nr);
-            out_xdepth = std::max(xl, xr);
-            node_need[idx] = out_need;
-            node_xdepth[idx] = out_xdepth;
-            return;
-        }
-        if (kind >= RT_KIND_TRANSLATE && kind <= RT_KIND_ZOOM) {
-            int32_t nc, xc;
-            need(d.xforms[idx].child, depth + 1, nc, xc);
-            out_need = 1 + nc;
-            out_xdepth = 1 + xc;
-            return;
-        }
-        if (kind == RT_KIND_LIST) {
-            RT_REQUIRE(!(ref & RT_REF_FLIP), RT_ERR_UNSUPPORTED, "FlipFace directly on a HittableList ref: push the flip down to the items");
+            const Need l = need(d.nodes[idx].left, depth + 1);
+            const Need r = d.nodes[idx].right == d.nodes[idx].left ? l : need(d.nodes[idx].right, depth + 1);
+            out = Need{std::max(1 + l.need, r.need), std::max(l.xdepth, r.xdepth), l.medium || r.medium};
+        } else if (kind == RT_KIND_LIST) {
             const rt_list &l = d.lists[idx];
-            int32_t best = std::max<int32_t>(1, (int32_t)l.count), bx = 0;
+            out = Need{std::max<int32_t>(1, (int32_t)l.count), 0, false};
             for (uint32_t i = 0; i < l.count; i++) {
-                int32_t ni, xi;
-                need(d.list_items[l.first + i], depth + 1, ni, xi);
-                best = std::max(best, (int32_t)(l.count - 1 - i) + ni);
-                bx = std::max(bx, xi);
+                const Need it = need(d.list_items[l.first + i], depth + 1);
+                out.need = std::max(out.need, (int32_t)(l.count - 1 - i) + it.need);
+                out.xdepth = std::max(out.xdepth, it.xdepth);
+                out.medium = out.medium || it.medium;
             }
-            out_need = best;
-            out_xdepth = bx;
-            return;
-        }
-        if (kind == RT_KIND_MEDIUM) {
+        } else if (kind == RT_KIND_MEDIUM) {
             // the medium's own slot becomes the sub-query sentinel while its boundary is traversed
-            RT_REQUIRE(!in_boundary, RT_ERR_UNSUPPORTED, "a medium inside another medium's boundary");
-            in_boundary = true;
-            int32_t nb, xb;
-            need(d.media[idx].boundary, depth + 1, nb, xb);
-            in_boundary = false;
-            out_need = 1 + nb;
-            out_xdepth = xb;
-            return;
+            const Need b = need(d.media[idx].boundary, depth + 1);
+            RT_REQUIRE(!b.medium, RT_ERR_UNSUPPORTED, "a medium inside another medium's boundary");
+            out = Need{1 + b.need, b.xdepth, true};
+        } else {
+            const Need c = need(d.xforms[idx].child, depth + 1);
+            out = Need{1 + c.need, 1 + c.xdepth, c.medium};
         }
-        out_need = 1;
-        out_xdepth = 0;
+        *memo = out;
+        return out;
     }
 };
 
@@ -906,8 +930,8 @@ int rt_scene_create(const rt_scene_desc *desc, rt_scene **out) {
         Validator v(*desc);
         v.check_pools();
         v.check_ref(desc->root, "root");
-        int32_t need = 1, xdepth = 0;
-        v.need(desc->root, 0, need, xdepth);
+        const Validator::Need root = v.need(desc->root, 0);
+        const int32_t need = root.need, xdepth = root.xdepth;
         RT_REQUIRE(need <= kStackLarge, RT_ERR_UNSUPPORTED, "scene needs a deeper traversal stack than the kernel provides");
         RT_REQUIRE(xdepth <= RT_MAX_XFORM_DEPTH, RT_ERR_UNSUPPORTED, "movers nested deeper than RT_MAX_XFORM_DEPTH");
         int ndev = 0;

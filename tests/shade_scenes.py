@@ -1,0 +1,409 @@
+"""Scenes built to enter one arm of the shade pass each (wf_shade: pt_wavefront.hip; the megakernel's twin of it: pt_kernel.hip):
+every material with every texture, the arms of the light list, the outcomes of Dielectric and Metal, and the ways a path's tape is
+unwound. No GPU is needed to build or to check a scene: the oracle's shade census (oracle/rt_oracle.h) says which arms its paths
+entered (tests/test_shade_scenes.py); tests/test_shade_arms.py then runs every case on the device.
+
+The stage is a floor, three walls and a sky, every one plain grey Lambertian, so that bounces come back to the subject. A case is
+a Case below: `build()` gives (desc, cam, params, rows); `want` names the census cells the case is built to fill (each must hold
+MIN_EVENTS events on the oracle), `zero` the cells it must not reach. A cell is (field, index): the fields and indices of
+rto_shade_census, a slice standing for "all of them".
+"""
+import numpy as np
+
+import raytracer_2022_amd as rt
+from oracle import oracle_ffi as O
+from raytracer_2022_amd import _ffi as F
+
+W, H, SPP, MAX_DEPTH = 24, 16, 4, 8
+MIN_EVENTS = 20
+ALL = slice(None)
+LAMB, METAL, DIEL, LIGHT, ISO = (F.RT_MAT_LAMBERTIAN, F.RT_MAT_METAL, F.RT_MAT_DIELECTRIC, F.RT_MAT_DIFFUSE_LIGHT, F.RT_MAT_ISOTROPIC)
+SOLID, CHECKER, NOISE, IMAGE, NONE = F.RT_TEX_SOLID, F.RT_TEX_CHECKER, F.RT_TEX_NOISE, F.RT_TEX_IMAGE, O.TEX_NONE
+SKY = (0.55, 0.65, 0.85)
+CHECKER_DEPTH = 8                                           # pt_device.h: kCheckerDepth, the deepest chain rt_scene_create accepts
+
+
+class Case:
+    def __init__(self, name, build, want, zero=(), spp=SPP, note=""):
+        self.name, self._build, self.want, self.zero, self.spp, self.note = name, build, list(want), list(zero), spp, note
+
+    def build(self):
+        """(desc, cam, params, rows) [+ whatever the builder adds]; the desc keeps its builder alive."""
+        return self._build(self)
+
+    def __repr__(self):
+        return self.name
+
+
+# ---- the stage -----------------------------------------------------------------------------------------------------------
+def stage(b, walls=True):
+    """Floor, back wall, left and right wall: grey Lambertian rects → list of refs."""
+    grey = b.lambertian((0.5, 0.5, 0.5))
+    refs = [b.rect(F.RT_RECT_XZ, -4, 4, -4, 6, 0.0, grey)]
+    if walls:
+        refs += [b.rect(F.RT_RECT_XY, -4, 4, 0, 5, -4.0, grey), b.rect(F.RT_RECT_YZ, 0, 5, -4, 6, -4.0, grey),
+                 b.rect(F.RT_RECT_YZ, 0, 5, -4, 6, 4.0, grey)]
+    return refs
+
+
+def lamp(b, color=(7, 7, 6)):
+    """The ceiling lamp: an XZ rect facing down in the world, the plain rect in the light list (as scene.rs does) → its world ref."""
+    ref = b.rect(F.RT_RECT_XZ, -1.5, 1.5, -1.5, 1.5, 5.0, b.diffuse_light(color), flip=True)
+    b.light(F.make_ref(F.RT_KIND_RECT, F.ref_index(ref)))
+    return ref
+
+
+def finish(case, b, refs, lookfrom=(0.0, 2.0, 7.5), lookat=(0.0, 1.3, 0.0), vfov=30.0, background=SKY, depth=MAX_DEPTH, seed=5,
+           times=(0.0, 1.0)):
+    b.set_root(b.list(refs))
+    d = b.desc()
+    d._builder = b                                          # (the pools live in the builder)
+    cam = rt.camera_new(lookfrom, lookat, (0, 1, 0), vfov, W / H, 0.0, 10.0, times[0], times[1])
+    p = rt.make_params(W, H, case.spp, depth, background, seed=seed)
+    return d, cam, p, rt.shuffled_rows(H, seed)
+
+
+# ---- textures ------------------------------------------------------------------------------------------------------------
+IMG = ((np.arange(8 * 4 * 3, dtype=np.uint8).reshape(4, 8, 3) * 7) % 251)
+
+
+def _unit(g, n):
+    v = g.normal(size=(n, 3))
+    return v / np.linalg.norm(v, axis=1, keepdims=True)
+
+
+def perlin(b, seed=11):
+    g = np.random.default_rng(seed)
+    return b.perlin(_unit(g, 256), g.permutation(256), g.permutation(256), g.permutation(256))
+
+
+def nested_checker(b, depth, g):
+    """A texture `depth` checkers deep. A CheckerTexture selects by the point alone (texture/mod.rs:51-60), so a point follows
+    the odd child at every level or the even child at every level: of a nest of checkers exactly two leaves can ever answer, the
+    end of the all-odd chain and the end of the all-even chain. Both chains are `depth` checkers long here, and the sibling at
+    every level is a solid of a colour of its own — a wrong turn at any level, or a resolution that stops early, shows.
+    → (texture, the two leaf colours (odd, even))."""
+    leaves = []
+
+    def chain(odd):
+        color = tuple(g.uniform(0.1, 0.9, 3))
+        leaves.append(color)
+        tex = b.solid(color)
+        for _ in range(depth - 1):
+            decoy = b.solid(tuple(g.uniform(0.1, 0.9, 3)))
+            tex = b.checker(tex, decoy) if odd else b.checker(decoy, tex)
+        return tex
+    return b.checker(chain(True), chain(False)), leaves
+
+
+TEXTURES = ("solid", "checker", "checker-image-noise", "noise", "image", "nested8")
+# texture name → the (leaf, top) kinds a hit on it can resolve to
+TEX_CELLS = {"solid": [(SOLID, SOLID)], "checker": [(SOLID, CHECKER)], "checker-image-noise": [(IMAGE, CHECKER), (NOISE, CHECKER)],
+             "noise": [(NOISE, NOISE)], "image": [(IMAGE, IMAGE)], "nested8": [(SOLID, CHECKER)], "image-1x1": [(IMAGE, IMAGE)],
+             "image-empty": [(IMAGE, IMAGE)]}
+
+
+def make_texture(b, name):
+    if name == "solid":
+        return b.solid((0.8, 0.4, 0.3))
+    if name == "checker":
+        return b.checker(b.solid((0.2, 0.3, 0.1)), b.solid((0.9, 0.9, 0.9)))
+    if name == "checker-image-noise":
+        return b.checker(b.image(IMG), b.noise(perlin(b), 4.0))
+    if name == "noise":
+        return b.noise(perlin(b), 4.0)
+    if name == "image":
+        return b.image(IMG)
+    if name == "image-1x1":
+        return b.image(np.array([[[200, 90, 30]]], dtype=np.uint8))
+    if name == "image-empty":
+        return b.image(np.zeros((0, 0, 3), dtype=np.uint8))       # width * height == 0: the cyan fallback (texture/mod.rs:111-113)
+    assert name == "nested8"
+    return nested_checker(b, CHECKER_DEPTH, np.random.default_rng(8))[0]
+
+
+def others_zero(mat, cells):
+    """The census cells a material x texture case must not reach: no texture kind but the subject's and the stage's solid, in
+    scatter and in emitted; and no scatter of the subject's material on another texture."""
+    zero = []
+    allowed = set(cells) | {(SOLID, SOLID)}
+    for leaf in (SOLID, CHECKER, NOISE, IMAGE):
+        for top in (SOLID, CHECKER, NOISE, IMAGE):
+            if (leaf, top) not in allowed:
+                zero.append(("scatter", (ALL, leaf, top, ALL)))
+            elif (leaf, top) not in cells and mat == ISO:         # (the stage is Lambertian on a solid; nothing else is)
+                zero.append(("scatter", (mat, leaf, top, ALL)))
+        if mat != LIGHT and leaf != SOLID:
+            zero.append(("emitted", (leaf, ALL)))
+    if mat == LIGHT:
+        leaves = {c[0] for c in cells} | {SOLID}                 # (the ceiling lamp is a solid light)
+        zero += [("emitted", (leaf, ALL)) for leaf in (CHECKER, NOISE, IMAGE) if leaf not in leaves]
+    return zero
+
+
+def material_case(mat, tex_name, spp=SPP):
+    """The subject — a sphere that fills most of the view — of material `mat` with texture `tex_name`, lit by the ceiling lamp."""
+    cells = TEX_CELLS[tex_name]
+    if mat == LIGHT:
+        want = [("emitted", (leaf, 1)) for leaf, _ in cells]
+    else:
+        want = [("scatter", (mat, leaf, top, 1)) for leaf, top in cells]
+    want += [("mixture_choice", (O.MIX_LIGHT,)), ("mixture_choice", (O.MIX_COSINE,))]
+    zero = others_zero(mat, cells) + [("mixture_choice", (O.MIX_COSINE_ONLY,)), ("dielectric", (ALL, ALL)), ("metal", (ALL,))]
+
+    def build(case):
+        b = rt.DescBuilder()
+        refs = stage(b) + [lamp(b)]
+        tex = make_texture(b, tex_name)
+        if mat == ISO:                                      # a dense medium in a sphere boundary: most rays scatter inside it
+            refs.append(b.medium(b.sphere((0, 1.4, 0), 1.4, b.dielectric(1.5)), 2.5, b.isotropic(tex=tex)))
+        else:
+            refs.append(b.sphere((0, 1.4, 0), 1.4, b.lambertian(tex=tex) if mat == LAMB else b.diffuse_light(tex=tex)))
+        return finish(case, b, refs)
+    return Case("%s-%s" % ({LAMB: "lambertian", LIGHT: "light", ISO: "isotropic"}[mat], tex_name), build, want, zero, spp)
+
+
+def image_rect_case():
+    """An image texture on a rect: (u, v) from the rect's own arithmetic (aarect.rs:64-65), not from get_sphere_uv. The builder
+    also returns rays for rt_radiance that hit the rect exactly on its a1 / b1 edges: u == 1 or v == 1, where u * width == width
+    and the index clamp i >= width is taken (texture/mod.rs:121-126)."""
+    want = [("scatter", (LAMB, IMAGE, IMAGE, 1))]
+
+    def build(case):
+        b = rt.DescBuilder()
+        refs = stage(b) + [lamp(b)]
+        refs.append(b.rect(F.RT_RECT_XY, -2.0, 2.0, 0.25, 2.75, -1.0, b.lambertian(tex=b.image(IMG))))
+        edge = {"origins": [(2.0, 2.75, 3.0), (2.0, 1.0, 3.0), (0.5, 2.75, 3.0), (-2.0, 0.25, 3.0)], "direction": (0.0, 0.0, -1.0),
+                "uv": [(1.0, 1.0), (1.0, 0.3), (0.625, 1.0), (0.0, 0.0)]}
+        return finish(case, b, refs) + (edge,)
+    return Case("lambertian-image-rect", build, want, others_zero(LAMB, [(IMAGE, IMAGE)]))
+
+
+def panels_case():
+    """Checkers 1 to 8 deep, one panel each: the leaf that answers lies 1, 2, ... 8 checkers down, on the odd chain and on the
+    even chain — 16 leaves of colours of their own, every one the first hit of some camera ray."""
+    want = [("scatter", (LAMB, SOLID, CHECKER, 1))]
+
+    def build(case):
+        b = rt.DescBuilder()
+        refs = stage(b) + [lamp(b)]
+        g = np.random.default_rng(88)
+        leaves, mats = [], []
+        for k in range(CHECKER_DEPTH):
+            tex, lv = nested_checker(b, k + 1, g)
+            leaves += lv
+            mats.append(b.lambertian(tex=tex))
+            x0 = -3.6 + 0.9 * k
+            refs.append(b.rect(F.RT_RECT_XY, x0, x0 + 0.9, 0.2, 3.0, -1.0 + 0.01 * k, mats[-1]))
+        return finish(case, b, refs, lookfrom=(0.0, 1.6, 8.5), lookat=(0.0, 1.6, 0.0), vfov=46.0) + ({"leaves": leaves, "mats": mats},)
+    return Case("lambertian-nested-1-to-8", build, want, others_zero(LAMB, [(SOLID, CHECKER)]))
+
+
+# ---- light lists ---------------------------------------------------------------------------------------------------------
+ARMS = {"sphere": O.ARM_SPHERE, "xy": O.ARM_RECT_XY, "xz": O.ARM_RECT_XZ, "yz": O.ARM_RECT_YZ, "flipped": O.ARM_FLIPPED,
+        "box": O.ARM_OTHER, "mover": O.ARM_OTHER}
+
+
+def light_object(b, what, i=0):
+    """One emitter of the kind → (its ref in the world, its ref in the light list). `i` moves and tints it."""
+    em = b.diffuse_light((6 + i % 3, 5 + (i * 2) % 4, 4 + (i * 3) % 5))
+    o = 0.35 * i
+    if what == "xy":                                        # on the back wall, facing the camera
+        r = b.rect(F.RT_RECT_XY, -3.0 + o, -1.5 + o, 3.0, 4.5, -3.98 + 0.001 * i, em)
+        return r, r
+    if what == "xz":                                        # under the sky, facing down
+        r = b.rect(F.RT_RECT_XZ, -1.0 + o, 0.5 + o, -2.0, -0.5, 4.8 + 0.01 * i, em, flip=True)
+        return r, F.make_ref(F.RT_KIND_RECT, F.ref_index(r))
+    if what == "yz":                                        # on the left wall, facing right
+        r = b.rect(F.RT_RECT_YZ, 2.5, 4.0, -2.0 + o, -0.5 + o, -3.98 + 0.001 * i, em)
+        return r, r
+    if what == "sphere":
+        r = b.sphere((2.4, 3.6, 0.5), 0.45, em)
+        return r, r
+    if what == "flipped":                                   # FlipFace in the light list: pdf_value 0, random (1, 0, 0), hittable/mod.rs:62-67
+        r = b.rect(F.RT_RECT_XZ, 1.0, 2.5, 0.5, 2.0, 4.9, em, flip=True)
+        return r, r
+    if what == "box":                                       # any other object: the same trait defaults
+        r = b.box((-3.2, 0.0, 1.0), (-2.4, 0.8, 1.8), em)
+        return r, r
+    assert what == "mover"
+    r = b.translate(b.sphere((0.0, 0.0, 0.0), 0.4, em), (2.8, 0.4, 2.0))
+    return r, r
+
+
+def light_list_case(name, entries, repeat_first=False, spp=SPP):
+    """The stage and a Lambertian subject under the light list `entries` (kinds of light_object), every entry an emitter of the
+    scene. repeat_first: the first entry is listed once more at the end."""
+    n = len(entries) + (1 if repeat_first else 0)
+    arms = sorted({ARMS[e] for e in entries})
+    want = [("light_draw", (a,)) for a in arms]
+    want += [("light_pdf", (a, 1)) for a in arms if a not in (O.ARM_FLIPPED, O.ARM_OTHER)]
+    want += [("light_pdf", (a, 0)) for a in arms]
+    zero = [("light_draw", (a,)) for a in range(6) if a not in arms] + [("light_pdf", (a, ALL)) for a in range(6) if a not in arms]
+    zero += [("light_pdf", (a, 1)) for a in (O.ARM_FLIPPED, O.ARM_OTHER)]
+    if n:
+        want += [("mixture_choice", (O.MIX_LIGHT,)), ("mixture_choice", (O.MIX_COSINE,))]
+        zero += [("mixture_choice", (O.MIX_COSINE_ONLY,))]
+    else:
+        want += [("mixture_choice", (O.MIX_COSINE_ONLY,))]
+        zero += [("mixture_choice", (O.MIX_LIGHT,)), ("mixture_choice", (O.MIX_COSINE,))]
+
+    def build(case):
+        b = rt.DescBuilder()
+        refs = stage(b)
+        refs.append(b.sphere((0, 1.2, 0), 1.2, b.lambertian((0.7, 0.6, 0.5))))
+        listed = []
+        for i, e in enumerate(entries):
+            world, ref = light_object(b, e, i)
+            refs.append(world)
+            listed.append(ref)
+        if repeat_first:
+            listed.append(listed[0])
+        for ref in listed:
+            b.light(ref)
+        out = finish(case, b, refs, vfov=42.0)
+        assert out[0].n_lights == n
+        return out
+    return Case(name, build, want, zero, spp)
+
+
+EIGHT = ["xy", "xz", "yz", "xy", "xz", "yz", "xz", "yz"]      # the ninth of `lights-9` is the one sphere: only a fetch of entry 8 finds it
+
+
+# ---- dielectric and metal ---------------------------------------------------------------------------------------------------
+def specular_case(name, subject, want, zero=(), spp=SPP, **view):
+    def build(case):
+        b = rt.DescBuilder()
+        refs = stage(b) + [lamp(b)]
+        refs += subject(b)
+        return finish(case, b, refs, **view)
+    return Case(name, build, want, list(zero) + [("mixture_choice", (O.MIX_COSINE_ONLY,))], spp)
+
+
+def D(outcome, front):
+    return ("dielectric", (outcome, front))
+
+
+# ---- tape and unwinding -----------------------------------------------------------------------------------------------------
+def E(cause, tainted, zero):
+    return ("path_end", (cause, tainted, zero))
+
+
+def tape_case(name, background, depth, want, zero=(), spp=SPP):
+    """The floor under a FlipFace'd light-list entry (test_nan_pixels_survive_like_the_reference): the light half of the mixture
+    answers random = (1, 0, 0) and pdf_value = 0, along the floor, so cosine = 0, both pdfs 0 and the record is 0 / 0 — the path
+    is tainted. Along +x such a ray meets, by its z: the BACK of a light, a grey wall — or the floor again, in whose plane it
+    travels ((k - y) / 0, aarect.rs:135). The tilted triangle over the floor faces the camera and away from +x: a light-half
+    bounce from it is tainted too (cosine < 0), passes behind it above the wall and the light, and misses."""
+    def build(case):
+        b = rt.DescBuilder()
+        grey = b.lambertian((0.7, 0.7, 0.7))
+        refs = [b.rect(F.RT_RECT_XZ, -5, 5, -5, 5, 0.0, grey),
+                b.rect(F.RT_RECT_YZ, -0.5, 1.0, -5.0, -1.0, 5.0, b.diffuse_light((4, 4, 4))),      # front face to +x: seen from behind
+                b.rect(F.RT_RECT_YZ, -0.5, 1.0, -1.0, 2.0, 5.0, grey),
+                b.triangle((-3.0, 1.1, 1.0), (-1.0, 1.1, 3.0), (-2.6, 3.2, 1.6), grey)]
+        b.light(b.rect(F.RT_RECT_XZ, -1, 1, -1, 1, 3.0, b.diffuse_light((5, 5, 5)), flip=True))        # (in the light list only)
+        return finish(case, b, refs, lookfrom=(0, 3, 6), lookat=(0, 0, 0), vfov=40.0, background=background, depth=depth, seed=3)
+    return Case(name, build, want, list(zero) + [("light_pdf", (ALL, 1)), ("light_draw", (O.ARM_SPHERE,))], spp)
+
+
+def zero_light_case():
+    """A DiffuseLight of colour (0, 0, 0) behind the camera, in the light list: no camera ray sees it, every path that ends on
+    it does so after a bounce, from the front — a terminal radiance of exactly zero under an untainted tape."""
+    def build(case):
+        b = rt.DescBuilder()
+        refs = stage(b)
+        refs.append(b.sphere((0, 1.2, 0), 1.2, b.lambertian((0.7, 0.6, 0.5))))
+        dark = b.sphere((0.0, 3.0, 12.0), 2.5, b.diffuse_light((0, 0, 0)))
+        refs.append(dark)
+        b.light(dark)
+        return finish(case, b, refs)
+    return Case("tape-zero-light", build, [E(O.END_LIGHT_FRONT, 0, 1), ("light_pdf", (O.ARM_SPHERE, 1)), E(O.END_MISS, 0, 0)],
+                [E(O.END_LIGHT_FRONT, ALL, 0), E(ALL, 1, ALL)])
+
+
+def inf_light_case():
+    """A lamp with an infinite colour component: the terminal radiance is not finite, and a weight of 0 in that channel up the
+    tape makes 0 * inf."""
+    def build(case):
+        b = rt.DescBuilder()
+        refs = stage(b) + [lamp(b, (float("inf"), 3.0, 2.0))]
+        refs.append(b.sphere((0, 1.2, 0), 1.2, b.lambertian((0.7, 0.0, 0.5))))
+        return finish(case, b, refs)
+    return Case("tape-inf-light", build, [E(O.END_LIGHT_FRONT, 0, 0), E(O.END_MISS, 0, 0)], [E(O.END_LIGHT_FRONT, ALL, 1)])
+
+
+# ---- the table -------------------------------------------------------------------------------------------------------------
+def _glass_ball(ir):
+    return lambda b: [b.sphere((0, 1.4, 0), 1.4, b.dielectric(ir))]
+
+
+def _mirror_and_mover(b):
+    """A mirror on the back of the stage and a MovingSphere between it and the camera that crosses the view during the shutter:
+    the camera sees it where it is in [0.5, 1], the mirror — whose bounce carries time 0 (material/mod.rs:91) — at its start."""
+    mirror = b.rect(F.RT_RECT_XY, -3.5, 3.5, 0.2, 4.0, -3.0, b.metal((0.9, 0.9, 0.9), 0.0))
+    ball = b.moving_sphere((-2.5, 1.2, 0.0), (2.5, 1.2, 0.0), 0.0, 1.0, 0.8, b.lambertian((0.8, 0.3, 0.2)))
+    return [mirror, ball]
+
+
+def cases():
+    out = []
+    for mat in (LAMB, LIGHT, ISO):
+        for tex in TEXTURES:
+            if mat == LAMB and tex == "nested8":
+                out.append(panels_case())
+            out.append(material_case(mat, tex))
+    out += [image_rect_case(), material_case(LAMB, "image-1x1"), material_case(LAMB, "image-empty")]
+    out += [light_list_case("lights-0", []), light_list_case("lights-1-xy", ["xy"]), light_list_case("lights-1-xz", ["xz"]),
+            light_list_case("lights-1-yz", ["yz"]), light_list_case("lights-1-sphere", ["sphere"]),
+            light_list_case("lights-1-flipped", ["flipped"]), light_list_case("lights-2-box-mover", ["box", "mover"]),
+            light_list_case("lights-2-listed-twice", ["xz"], repeat_first=True),
+            light_list_case("lights-8", EIGHT), light_list_case("lights-9", EIGHT + ["sphere"])]
+    R, S, X = O.DIEL_REFRACT, O.DIEL_SCHLICK, O.DIEL_CANNOT_REFRACT
+    out += [
+        specular_case("glass-outside", _glass_ball(1.5), [D(R, 1), D(R, 0), D(S, 1), ("scatter", (DIEL, NONE, NONE, 1)),
+                                                         ("scatter", (DIEL, NONE, NONE, 0))],
+                      [D(X, 1), D(X, 0), ("metal", (ALL,))]),      # (a ray refracted into a ball meets its inside below the critical angle)
+        # the camera 0.75 radii off the centre of a ball, looking across it: past the critical angle (sin = 1 / 1.5) in the middle of
+        # the view, under it at the sides
+        specular_case("glass-camera-inside", lambda b: [b.sphere((1.2, 2.0, 7.5), 1.6, b.dielectric(1.5))], [D(R, 0), D(S, 0), D(X, 0)],
+                      [D(X, 1), ("metal", (ALL,))], vfov=80.0),
+        specular_case("glass-0.7-front-total-reflection", _glass_ball(0.7), [D(X, 1), D(R, 1), D(R, 0)], [D(X, 0), ("metal", (ALL,))]),
+        specular_case("glass-grazing", lambda b: [b.box((-3.5, 0.02, -3.5), (3.5, 0.3, 5.0), b.dielectric(1.5))], [D(S, 1), D(R, 1)],
+                      [D(X, 1), ("metal", (ALL,))], lookfrom=(0.0, 0.55, 7.5), lookat=(0.0, 0.3, 0.0)),
+        specular_case("metal-fuzz-0", lambda b: [b.sphere((0, 1.4, 0), 1.4, b.metal((0.8, 0.7, 0.6), 0.0))],
+                      [("metal", (0,)), ("scatter", (METAL, NONE, NONE, 1))], [("metal", (1,)), ("dielectric", (ALL, ALL))]),
+        specular_case("metal-fuzz-1", lambda b: [b.sphere((0, 1.4, 0), 1.4, b.metal((0.8, 0.7, 0.6), 1.0))],
+                      [("metal", (1,)), ("scatter", (METAL, NONE, NONE, 1))], [("metal", (0,)), ("dielectric", (ALL, ALL))]),
+        specular_case("metal-mirror-moving-sphere", _mirror_and_mover, [("metal", (0,))], [("metal", (1,)), ("dielectric", (ALL, ALL))],
+                      times=(0.5, 1.0), vfov=42.0),
+    ]
+    M, B, Dp = O.END_MISS, O.END_LIGHT_BACK, O.END_DEPTH
+    out += [
+        tape_case("tape-black-background", (0.0, 0.0, 0.0), 10, [E(M, 1, 1), E(M, 0, 1), E(B, 1, 1)], [E(M, ALL, 0)]),
+        tape_case("tape-sky-background", (0.2, 0.2, 0.2), 10, [E(M, 1, 0), E(M, 0, 0), E(B, 1, 1)], [E(M, ALL, 1)]),
+        tape_case("tape-depth-2", (0.0, 0.0, 0.0), 2, [E(Dp, 1, 1), E(Dp, 0, 1), E(M, 1, 1), E(B, 1, 1)], [E(ALL, ALL, 0)],
+                  spp=8),      # (at 4 samples depth / clean / zero holds 15 events)
+        zero_light_case(), inf_light_case(),
+    ]
+    assert len({c.name for c in out}) == len(out)
+    return out
+
+
+CASES = cases()
+BY_NAME = {c.name: c for c in CASES}
+
+
+def cell_count(census, cell):
+    """The events of a census (oracle_ffi.census_end) in a cell (field, index)."""
+    field, idx = cell
+    return int(np.sum(census[field][idx]))
+
+
+def pinhole_rays(cam, width, height):
+    """The ray through the middle of every pixel (origin, direction arrays): Camera::get_ray without the lens."""
+    px, py = np.meshgrid(np.arange(width), np.arange(height))
+    s, t = (px.ravel() + 0.5) / (width - 1), (py.ravel() + 0.5) / (height - 1)
+    o = np.array(cam.origin[:])
+    d = np.array(cam.lower_left_corner[:]) + s[:, None] * np.array(cam.horizontal[:]) + t[:, None] * np.array(cam.vertical[:]) - o
+    return np.broadcast_to(o, d.shape).copy(), d

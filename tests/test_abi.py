@@ -3,7 +3,9 @@ structures have the layout the bindings assume. No compute calls (runs without a
 import ctypes as C
 import os
 import re
+import time
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -90,6 +92,181 @@ def test_scene_validation_errors_are_reported_not_crashed(rt):
     d.abi_version = 99
     with pytest.raises(rt.RtError):
         rt.DeviceScene(d)
+
+
+def create_verdict(rt, d):
+    """(verdict of rt_scene_create's validation, its message, seconds). Validation comes before the first device call, so on
+    a machine without a GPU a scene that passed it stops at RT_ERR_DEVICE: that counts as accepted (RT_OK) here. Nothing is
+    ever rendered: an accepted scene is destroyed at once."""
+    from raytracer_2022_amd import _ffi as F
+    t0 = time.perf_counter()
+    try:
+        rt.DeviceScene(d).close()
+        code, msg = F.RT_OK, ""
+    except rt.RtError as e:
+        code, msg = (F.RT_OK, "") if e.code == F.RT_ERR_DEVICE else (e.code, str(e))
+    return code, msg, time.perf_counter() - t0
+
+
+def checker_chain_desc(rt, depth):
+    """A Lambertian sphere whose texture is `depth` checkers deep on both branches at every level, distinct solids below."""
+    b = rt.DescBuilder()
+    tex = b.solid((0.5, 0.5, 0.5))
+    for lvl in range(depth):
+        tex = b.checker(b.solid((0.1 * lvl, 0.2, 0.3)), tex) if lvl % 2 else b.checker(tex, b.solid((0.1 * lvl, 0.2, 0.3)))
+    b.set_root(b.sphere((0, 0, 0), 1.0, b.lambertian(tex=tex)))
+    return b
+
+
+def test_checker_chains_are_validated(rt):
+    """texture_value follows kCheckerDepth = 8 checkers where the reference recurses to the leaf (texture/mod.rs:51-60): a
+    chain of exactly 8 is accepted (tests/test_shade_arms.py renders one against the oracle), a deeper one is
+    RT_ERR_UNSUPPORTED with the limit in its message, and a cycle among checker children — which has no leaf — RT_ERR_INVALID."""
+    from raytracer_2022_amd import _ffi as F
+    assert create_verdict(rt, checker_chain_desc(rt, 8).desc())[0] == F.RT_OK
+    for depth in (9, 10, 40):
+        code, msg, _ = create_verdict(rt, checker_chain_desc(rt, depth).desc())
+        assert code == F.RT_ERR_UNSUPPORTED and "8" in msg and "checker" in msg, (depth, code, msg)
+    # a texture that no material uses is validated like any other
+    b = checker_chain_desc(rt, 2)
+    unused = b.solid((1, 1, 1))
+    for _ in range(9):
+        unused = b.checker(unused, unused)
+    assert create_verdict(rt, b.desc())[0] == F.RT_ERR_UNSUPPORTED
+    # a checker that is its own child; a cycle of two; a cycle reached through a sound checker
+    b = checker_chain_desc(rt, 1)
+    top = len(b.pools["textures"]) - 1
+    b.pools["textures"][top].a = top
+    code, msg, _ = create_verdict(rt, b.desc())
+    assert code == F.RT_ERR_INVALID and "cycle" in msg, (code, msg)
+    b = checker_chain_desc(rt, 2)
+    top = len(b.pools["textures"]) - 1
+    inner = b.pools["textures"][top].b
+    assert b.pools["textures"][inner].kind == F.RT_TEX_CHECKER
+    b.pools["textures"][inner].b = top
+    code, msg, _ = create_verdict(rt, b.desc())
+    assert code == F.RT_ERR_INVALID and "cycle" in msg, (code, msg)
+    b = checker_chain_desc(rt, 1)
+    s0 = b.solid((0, 0, 0))
+    x = b.checker(s0, s0)
+    y = b.checker(s0, x)
+    b.pools["textures"][x].b = y
+    b.checker(s0, y)                                               # (sound itself; its child lies on the cycle)
+    code, msg, _ = create_verdict(rt, b.desc())
+    assert code == F.RT_ERR_INVALID and "cycle" in msg, (code, msg)
+    # shared children are no cycle: 8 levels, every one holding the next one twice
+    b = rt.DescBuilder()
+    tex = b.solid((0.3, 0.3, 0.3))
+    for _ in range(8):
+        tex = b.checker(tex, tex)
+    b.set_root(b.sphere((0, 0, 0), 1.0, b.lambertian(tex=tex)))
+    assert create_verdict(rt, b.desc())[0] == F.RT_OK
+
+
+def test_scene_graph_cycles_are_refused_and_shared_records_walked_once(rt):
+    """Cycles through lists, movers and medium boundaries are RT_ERR_INVALID ("cycle"), found at once; a legal graph with
+    shared sub-lists — 40 lists, each holding the next one twice: 2^40 paths from the root — is walked once per record and
+    accepted. A second per call is generous: each scene is a few hundred records."""
+    from raytracer_2022_amd import _ffi as F
+
+    def own_list(b, n_items=2):
+        """A list of n_items spheres (to be overwritten by the caller) → (ref, index of its first item)."""
+        m = b.lambertian((0.5, 0.5, 0.5))
+        first = len(b.pools["list_items"])
+        return b.list([b.sphere((0, 0, i), 0.4, m) for i in range(n_items)]), first
+
+    # a list that holds itself twice
+    b = rt.DescBuilder()
+    me, first = own_list(b)
+    b.pools["list_items"][first] = C.c_uint32(me)
+    b.pools["list_items"][first + 1] = C.c_uint32(me)
+    b.set_root(me)
+    code, msg, dt = create_verdict(rt, b.desc())
+    assert code == F.RT_ERR_INVALID and "cycle" in msg and dt < 1.0, (code, msg, dt)
+    # ... and two lists that hold each other twice
+    b = rt.DescBuilder()
+    l0, f0 = own_list(b)
+    l1, f1 = own_list(b)
+    for f, other in ((f0, l1), (f1, l0)):
+        b.pools["list_items"][f] = C.c_uint32(other)
+        b.pools["list_items"][f + 1] = C.c_uint32(other)
+    b.set_root(l0)
+    code, msg, dt = create_verdict(rt, b.desc())
+    assert code == F.RT_ERR_INVALID and "cycle" in msg and dt < 1.0, (code, msg, dt)
+    # a mover that is its own child: a cycle, not "too deep"
+    b = rt.DescBuilder()
+    t = b.translate(b.sphere((0, 0, 0), 1.0, b.lambertian((0.5, 0.5, 0.5))), (1, 0, 0))
+    b.pools["xforms"][0].child = t
+    b.set_root(t)
+    code, msg, dt = create_verdict(rt, b.desc())
+    assert code == F.RT_ERR_INVALID and "cycle" in msg and dt < 1.0, (code, msg, dt)
+    # a medium whose boundary leads back to it, through a mover and through a list
+    for via in ("mover", "list"):
+        b = rt.DescBuilder()
+        shell = b.sphere((0, 0, 0), 1.0, b.dielectric(1.5))
+        if via == "mover":
+            inner = b.translate(shell, (0, 0, 0))
+        else:
+            inner, first = own_list(b)
+        fog = b.medium(inner, 0.5, b.isotropic((1, 1, 1)))
+        if via == "mover":
+            b.pools["xforms"][0].child = fog
+        else:
+            b.pools["list_items"][first + 1] = C.c_uint32(fog)
+        b.set_root(fog)
+        code, msg, dt = create_verdict(rt, b.desc())
+        assert code == F.RT_ERR_INVALID and "cycle" in msg and dt < 1.0, (via, code, msg, dt)
+    # a medium below a list that is shared with another medium's boundary is still "a medium inside a boundary"
+    b = rt.DescBuilder()
+    fog = b.medium(b.sphere((0, 0, 0), 1.0, b.dielectric(1.5)), 0.5, b.isotropic((1, 1, 1)))
+    shared = b.list([fog, b.sphere((3, 0, 0), 1.0, b.dielectric(1.5))])
+    b.set_root(b.list([shared, b.medium(shared, 0.5, b.isotropic((1, 1, 1)))]))          # (walked from the root first, then as a boundary)
+    code, msg, dt = create_verdict(rt, b.desc())
+    assert code == F.RT_ERR_UNSUPPORTED and "medium" in msg, (code, msg)
+    # the legal one: 40 lists, each holding the next twice; the last one holds a sphere twice
+    b = rt.DescBuilder()
+    sph = b.sphere((0, 0, 0), 1.0, b.lambertian((0.5, 0.5, 0.5)))
+    ref = b.list([sph, sph])
+    for _ in range(39):
+        ref = b.list([ref, ref])
+    b.set_root(ref)
+    d = b.desc()
+    assert d.n_lists == 40 and d.n_list_items == 80
+    code, msg, dt = create_verdict(rt, d)
+    assert code == F.RT_OK and dt < 1.0, (code, msg, dt)
+    # ... and the same sharing through movers' children, nodes and a medium's boundary
+    b = rt.DescBuilder()
+    sph = b.sphere((0, 0, 0), 1.0, b.dielectric(1.5))
+    ref = b.translate(sph, (0.1, 0, 0))
+    for i in range(30):
+        ref = b.list([ref, ref]) if i % 2 else b.node((-9, -9, -9), (9, 9, 9), ref, b.list([ref]))
+    b.set_root(b.list([b.medium(ref, 0.5, b.isotropic((1, 1, 1))), ref]))
+    code, msg, dt = create_verdict(rt, b.desc())
+    assert code == F.RT_OK and dt < 1.0, (code, msg, dt)
+
+
+def test_image_bounds_check_does_not_wrap(rt):
+    """offset + 3 * width * height is compared with image_data_bytes without a sum or product that can wrap: an offset of
+    2^64 - 8 with a 2 x 2 image sums to 4 modulo 2^64, and 0xFFFFFFFF x 0xFFFFFFFF x 3 exceeds 2^64."""
+    from raytracer_2022_amd import _ffi as F
+
+    def with_image(width, height, offset, data_bytes=12):
+        b = rt.DescBuilder()
+        tex = b.image(np.zeros((2, 2, 3), dtype=np.uint8))
+        assert len(b.image_data) == 12
+        b.image_data += bytes(data_bytes - 12)
+        im = b.pools["images"][0]
+        im.width, im.height, im.offset = width, height, offset
+        b.set_root(b.sphere((0, 0, 0), 1.0, b.lambertian(tex=tex)))
+        return b.desc()
+
+    assert create_verdict(rt, with_image(2, 2, 0))[0] == F.RT_OK
+    assert create_verdict(rt, with_image(2, 2, 4, data_bytes=16))[0] == F.RT_OK          # ends exactly at the end of the data
+    assert create_verdict(rt, with_image(0, 0, 12))[0] == F.RT_OK                        # an empty image at the very end
+    for width, height, offset in ((2, 2, 2**64 - 8), (0xFFFFFFFF, 0xFFFFFFFF, 0), (0xFFFFFFFF, 0xFFFFFFFF, 2**64 - 8),
+                                  (2, 2, 1), (2, 3, 0), (0, 0, 13), (0x80000000, 2, 0), (1, 1, 2**64 - 1)):
+        code, msg, _ = create_verdict(rt, with_image(width, height, offset))
+        assert code == F.RT_ERR_INVALID and "image" in msg, (width, height, hex(offset), code, msg)
 
 
 @pytest.mark.skipif(__import__("tests.conftest", fromlist=["has_gpu"]).has_gpu(), reason="needs a machine without a GPU")

@@ -1,0 +1,180 @@
+"""The scenes of tests/shade_scenes.py, checked on the oracle alone (no GPU) with its shade census on: every census cell a case
+is named for holds at least MIN_EVENTS = 20 events, the cells it must not reach hold none, and paths go on past the camera ray.
+So the device tests of tests/test_shade_arms.py cannot pass on an arm of the shade pass that no path enters.
+
+The cells (fields of rto_shade_census, oracle/rt_oracle.h) and the cases that fill them. 24 x 16 pixels, 4 samples, depth 8 unless
+said otherwise; [f] = front face, [b] = back face.
+
+  scatter[Lambertian][leaf][top][f]
+      solid / solid                lambertian-solid (and the grey stage of every case)
+      solid / checker              lambertian-checker, lambertian-nested8, lambertian-nested-1-to-8
+      image / checker, noise / checker   lambertian-checker-image-noise
+      noise / noise                lambertian-noise
+      image / image                lambertian-image (sphere: get_sphere_uv), lambertian-image-rect (the rect's own u, v),
+                                   lambertian-image-1x1, lambertian-image-empty (the cyan fallback)
+  emitted[leaf][f]                 light-solid, -checker (solid), -checker-image-noise (image and noise), -noise, -image, -nested8
+  scatter[Isotropic][leaf][top][f] isotropic-solid, -checker, -checker-image-noise (both leaves), -noise, -image, -nested8
+                                   (a medium's hit record is always a front face: constantmedium.rs:78)
+  scatter[Metal][none][none][f], metal[fuzz 0]      metal-fuzz-0, metal-mirror-moving-sphere (camera times in [0.5, 1])
+  scatter[Metal][none][none][f], metal[fuzz > 0]    metal-fuzz-1
+  scatter[Dielectric][none][none][f and b]          glass-outside
+  dielectric[refract][f], [refract][b], [Schlick][f]    glass-outside (cannot-refract stays 0 there, on both faces: a ray
+                                   refracted into a ball meets its inside below the critical angle)
+  dielectric[refract][b], [Schlick][b], [cannot refract][b]    glass-camera-inside
+  dielectric[cannot refract][f]    glass-0.7-front-total-reflection
+  dielectric[Schlick][f]           glass-grazing
+  mixture_choice[cosine only]      lights-0 (no light draw, no light pdf)
+  mixture_choice[light], [cosine]  every case with a light list
+  light_draw[arm], light_pdf[arm][hit], light_pdf[arm][miss]
+      rect XY, rect XZ, rect YZ, sphere     lights-1-xy, lights-1-xz, lights-1-yz, lights-1-sphere
+      flipped (pdf always a miss)  lights-1-flipped and the three tape-* cases
+      other (pdf always a miss)    lights-2-box-mover: a Box ref and a Translate ref
+      the light listed twice       lights-2-listed-twice
+      8 entries, 9 entries         lights-8 (no sphere), lights-9 (the ninth — the first behind the LDS table — is the only sphere)
+  path_end[cause][tainted][terminal radiance == 0]
+      miss / tainted / zero, miss / clean / zero, light back / tainted / zero           tape-black-background
+      miss / tainted / non-zero, miss / clean / non-zero                                tape-sky-background
+      depth / tainted / zero, depth / clean / zero, miss / tainted / zero, light back / tainted / zero    tape-depth-2 (depth 2;
+                                   8 samples: at 4 the cell depth / clean / zero holds 15 events)
+      light front / clean / zero   tape-zero-light (the light is behind the camera: every such end lies behind a bounce)
+      light front / clean / non-zero with an infinite component                          tape-inf-light
+
+Cells left out: none. Two things geometry forbids: a nest of checkers selects by the point alone, so a
+single texture 8 deep reaches two leaves, not 16; lambertian-nested-1-to-8 shows checkers 1, 2, ... 8 deep side by side instead
+and counts the 16 leaf colours of those. An exact hit on a rect's a1 / b1 edge (u == 1) cannot come from a camera with random
+pixel offsets: lambertian-image-rect carries rays for rt_radiance that do it, checked here with rto_hit.
+"""
+import numpy as np
+import pytest
+
+import shade_scenes as S
+from raytracer_2022_amd import _ffi as F
+
+IDS = [c.name for c in S.CASES]
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+def render_with_census(O, scene, n_threads=4):
+    d, cam, p, rows = scene[:4]
+    O.census_begin()
+    try:
+        ref, st = O.render_cpu(d, cam, p, rows, n_threads=n_threads, want_stats=True)
+    finally:
+        cen = O.census_end()
+    return ref, st, cen
+
+
+@pytest.mark.parametrize("case", S.CASES, ids=IDS)
+def test_case_enters_the_arms_it_is_named_for(O, case):
+    scene = case.build()
+    d, cam, p, rows = scene[:4]
+    ref, st, cen = render_with_census(O, scene)
+    for cell in case.want:
+        assert S.cell_count(cen, cell) >= S.MIN_EVENTS, (case.name, cell, S.cell_count(cen, cell))
+    for cell in case.zero:
+        assert S.cell_count(cen, cell) == 0, (case.name, cell, S.cell_count(cen, cell))
+    paths = S.W * S.H * case.spp
+    assert st.paths == paths and st.rays > paths
+    # the census agrees with the counters it stands beside
+    n_end = {k: int(cen["path_end"][k].sum()) for k in range(4)}
+    assert sum(n_end.values()) == paths
+    assert int(cen["scatter"].sum() + cen["emitted"].sum()) + n_end[O.END_MISS] == st.rays
+    assert int(cen["emitted"][:, 1].sum()) == n_end[O.END_LIGHT_FRONT] and int(cen["emitted"][:, 0].sum()) == n_end[O.END_LIGHT_BACK]
+    mix = cen["mixture_choice"]
+    assert int(cen["light_draw"].sum()) == int(mix[O.MIX_LIGHT])
+    assert int(cen["light_pdf"].sum()) == d.n_lights * int(mix[O.MIX_LIGHT] + mix[O.MIX_COSINE])
+    assert int(cen["light_pdf"][:O.ARM_FLIPPED].sum()) == st.light_pdf_tests
+    assert int(mix.sum()) == int(cen["scatter"][S.LAMB].sum())
+    assert int(cen["metal"].sum()) == int(cen["scatter"][S.METAL].sum()) and int(cen["dielectric"].sum()) == int(cen["scatter"][S.DIEL].sum())
+    # ... and changes nothing: the same render with the census off, the same bits and counters
+    plain, st0 = O.render_cpu(d, cam, p, rows, n_threads=1, want_stats=True)
+    assert np.array_equal(bits(plain), bits(ref)) and st0.as_dict() == st.as_dict()
+
+
+def test_census_is_off_by_default_and_safe_under_threads(O):
+    scene = S.BY_NAME["lights-9"].build()
+    d, cam, p, rows = scene[:4]
+    _, _, one = render_with_census(O, scene, n_threads=1)
+    _, _, eight = render_with_census(O, scene, n_threads=8)
+    for k in one:
+        assert np.array_equal(one[k], eight[k]), k
+    O.render_cpu(d, cam, p, rows, n_threads=4)                  # off: the counts stay what the last census_end() read
+    import ctypes as C
+    c = O.rto_shade_census()
+    O.lib().rto_census_read(C.byref(c))
+    for k in one:
+        assert np.array_equal(np.ctypeslib.as_array(getattr(c, k)), eight[k]), k
+    # rto_ray_color counts too while it is on: one path, one end
+    O.census_begin()
+    O.ray_color(d, cam.origin[:], (0.0, -0.2, -1.0), background=S.SKY, depth=S.MAX_DEPTH, rng_state=7)
+    assert int(O.census_end()["path_end"].sum()) == 1
+
+
+def first_hits(O, d, cam):
+    """rto_hit of the pinhole ray through every pixel → the records that hit."""
+    origins, dirs = S.pinhole_rays(cam, S.W, S.H)
+    recs = [O.hit(d, d.root, origins[i], dirs[i], tm=0.5, rng_state=i + 1) for i in range(len(origins))]
+    return [r for r in recs if r.hit]
+
+
+def test_nested_checkers_reach_both_leaves_at_every_depth(O):
+    """Checkers 1 to 8 deep: the two leaves of every panel — 16 colours — are among the albedos of the camera rays' first hits,
+    and no sibling colour is."""
+    d, cam, p, rows, extra = S.BY_NAME["lambertian-nested-1-to-8"].build()
+    seen = set()
+    for rec in first_hits(O, d, cam):
+        if rec.mat in extra["mats"]:
+            seen.add(tuple(O.texture_value(d, d.materials[rec.mat].tex, rec.u, rec.v, rec.p[:])))
+    assert len(extra["leaves"]) == 2 * S.CHECKER_DEPTH == 16 and len(set(extra["leaves"])) == 16
+    assert seen == set(extra["leaves"])
+    # the single sphere of the material x texture cases: 8 deep, its two leaves and nothing else
+    d, cam, p, rows = S.BY_NAME["lambertian-nested8"].build()
+    depth = lambda t: 0 if d.textures[t].kind != F.RT_TEX_CHECKER else 1 + max(depth(d.textures[t].a), depth(d.textures[t].b))
+    subject = d.spheres[d.n_spheres - 1].mat
+    assert depth(d.materials[subject].tex) == S.CHECKER_DEPTH
+    colours = {tuple(O.texture_value(d, d.materials[subject].tex, r.u, r.v, r.p[:])) for r in first_hits(O, d, cam) if r.mat == subject}
+    assert len(colours) == 2
+
+
+def test_edge_rays_hit_the_rect_at_u_or_v_of_exactly_one(O):
+    d, cam, p, rows, edge = S.BY_NAME["lambertian-image-rect"].build()
+    img = S.IMG
+    for o, (u, v) in zip(edge["origins"], edge["uv"]):
+        rec = O.hit(d, d.root, o, edge["direction"])
+        assert rec.hit and rec.u == u and rec.v == v, (o, rec.u, rec.v)
+        tex = d.materials[rec.mat].tex
+        assert d.textures[tex].kind == F.RT_TEX_IMAGE
+        i, j = min(int(u * img.shape[1]), img.shape[1] - 1), min(int(v * img.shape[0]), img.shape[0] - 1)      # the clamp, texture/mod.rs:121-126
+        assert np.array_equal(O.texture_value(d, tex, rec.u, rec.v, rec.p[:]), img[j, i] * (1.0 / 255.999))
+
+
+def test_small_and_empty_images(O):
+    d = S.BY_NAME["lambertian-image-1x1"].build()[0]
+    assert (d.images[0].width, d.images[0].height) == (1, 1)
+    tex = d.materials[d.spheres[d.n_spheres - 1].mat].tex
+    for u, v in ((0.0, 0.0), (0.5, 0.5), (1.0, 1.0)):
+        assert np.array_equal(O.texture_value(d, tex, u, v, (0, 0, 0)), np.array([200, 90, 30]) * (1.0 / 255.999))
+    d = S.BY_NAME["lambertian-image-empty"].build()[0]
+    assert d.images[0].width * d.images[0].height == 0 and d.image_data_bytes == 0
+    tex = d.materials[d.spheres[d.n_spheres - 1].mat].tex
+    assert np.array_equal(O.texture_value(d, tex, 0.3, 0.7, (0, 0, 0)), (0.0, 1.0, 1.0))
+
+
+def test_mirror_sees_the_moving_sphere_at_time_zero(O):
+    """Metal's scattered ray carries time 0 (material/mod.rs:91), whatever the camera ray's: with camera times in [0.5, 1] the
+    sphere is right of the middle when seen directly and at its start, on the left, in the mirror."""
+    d, cam, p, rows = S.BY_NAME["metal-mirror-moving-sphere"].build()
+    assert cam.time0 == 0.5 and cam.time1 == 1.0
+    ball = d.moving_spheres[0].mat
+    direct = O.hit(d, d.root, cam.origin[:], (1.6 - cam.origin[0], 1.2 - cam.origin[1], 0.0 - cam.origin[2]), tm=0.9)
+    assert direct.hit and direct.mat == ball                     # at 0.9 its centre is at x = 2
+    # a ray into the mirror at (-1.944, 1.378, -3) from the camera goes on to the sphere's place at time 0, x = -2.5
+    m = O.hit(d, d.root, cam.origin[:], (-1.944 - cam.origin[0], 1.378 - cam.origin[1], -3.0 - cam.origin[2]), tm=0.9)
+    assert m.hit and d.materials[m.mat].kind == F.RT_MAT_METAL
+    out = np.array([-1.944 - cam.origin[0], 1.378 - cam.origin[1], -(-3.0 - cam.origin[2])])
+    assert O.hit(d, d.root, m.p[:], out, tm=0.0).mat == ball and O.hit(d, d.root, m.p[:], out, tm=0.9).mat != ball
+    st = O.render_cpu(d, cam, p, rows, want_stats=True)[1]
+    assert st.prim_tests[F.RT_KIND_MOVING_SPHERE] > 0
