@@ -13,7 +13,8 @@ extern "C" {
 
 /* op: 0 sin, 1 cos, 2 acos, 3 atan2(a,b), 4 log, 5 sqrt, 6 a/b. Host buffers. */
 int rt_debug_math_device(int op, const double *a, const double *b, double *out, uint64_t n);
-/* n draws from Rng(state): mode 0 next_u64, 1 gen_f64 (bits), 2 gen_range(lo,hi) (bits), 3 gen_index(bound). */
+/* n draws from Rng(state): mode 0 next_u64, 1 gen_f64 (bits), 2 gen_range(lo,hi) (bits), 3 gen_index(bound);
+ * 4 / 5: the generator's state after each gen_range(lo,hi) / gen_index(bound) instead of the value. */
 int rt_debug_rng_device(uint64_t state, int mode, double lo, double hi, uint64_t bound, uint64_t *out, uint64_t n);
 /* Scheduler knobs of the engines. node_quorum is the tuning word, a bit field (the same list, with its accessors: namespace tune
  * in csrc/hip/pt_device.h):

@@ -290,7 +290,8 @@ __global__ void __launch_bounds__(256) math_probe_kernel(int op, const double *a
     }
     out[i] = r;
 }
-// RNG stream on the device: mode 0 = next_u64, 1 = gen_f64 bits, 2 = gen_range bits, 3 = gen_index.
+// RNG stream on the device: mode 0 = next_u64, 1 = gen_f64 bits, 2 = gen_range bits, 3 = gen_index; 4 / 5 = the generator's
+// state after each gen_range / gen_index instead of the value (how many words a redraw loop consumed).
 __global__ void rng_probe_kernel(uint64_t state, int mode, double lo, double hi, uint64_t bound, uint64_t *out, uint64_t n) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
     Rng r(state);
@@ -298,6 +299,8 @@ __global__ void rng_probe_kernel(uint64_t state, int mode, double lo, double hi,
         if (mode == 0) out[i] = r.next_u64();
         else if (mode == 1) out[i] = rtm::d2u(r.gen_f64());
         else if (mode == 2) out[i] = rtm::d2u(r.gen_range(lo, hi));
+        else if (mode == 4) { r.gen_range(lo, hi); out[i] = r.s; }
+        else if (mode == 5) { r.gen_index(bound); out[i] = r.s; }
         else out[i] = r.gen_index(bound);
     }
 }

@@ -461,13 +461,24 @@ struct Rng {
     // UniformFloat::sample_single: gen_range(low..high), 52 bits, redraw if res >= high.
     // (The redraw fires only when rounding lands on `high`; the loop is bounded so
     // that a NaN bound cannot hang a GPU wave — rand would have panicked instead.)
+    //
+    // The three range functions below are written as "first draw, then the redraw loop
+    // behind an unlikely branch", not as one loop over all RT_MAX_REJECT tries: the
+    // generator is counter based, so the device compiler turns a plain loop into a block
+    // that computes four draws side by side and then picks the first accepted one — on
+    // every call, although the redraw (almost) never fires. Same draws, same order, same
+    // cap; the redraws stay in the function (a call would force `s` through memory).
+    RT_HD double range_draw(double low, double scale) {
+        double value1_2 = u2d((next_u64() >> 12) | 0x3FF0000000000000ull);
+        double value0_1 = value1_2 - 1.0;
+        return value0_1 * scale + low;
+    }
     RT_HD double gen_range(double low, double high) {
         double scale = high - low;
-        double res = low;
-        for (int tries = 0; tries < RT_MAX_REJECT; tries++) {
-            double value1_2 = u2d((next_u64() >> 12) | 0x3FF0000000000000ull);
-            double value0_1 = value1_2 - 1.0;
-            res = value0_1 * scale + low;
+        double res = range_draw(low, scale);
+        if (__builtin_expect(res < high, 1)) return res;
+        for (int tries = 1; tries < RT_MAX_REJECT; tries++) {
+            res = range_draw(low, scale);
             if (res < high) return res;
         }
         return res;
@@ -475,27 +486,26 @@ struct Rng {
     // UniformInt<usize>::sample_single: gen_range(0..n), widening multiply + zone.
     RT_HD uint64_t gen_index(uint64_t n) {
         uint64_t zone = (n << __builtin_clzll(n)) - 1;
-        uint64_t hi = 0;
-        for (int tries = 0; tries < RT_MAX_REJECT; tries++) {
-            uint64_t v = next_u64();
-            uint64_t lo = v * n;
+        uint64_t v = next_u64();
+        uint64_t hi = mulhi64(v, n);
+        if (__builtin_expect(v * n <= zone, 1)) return hi;
+        for (int tries = 1; tries < RT_MAX_REJECT; tries++) {
+            v = next_u64();
             hi = mulhi64(v, n);
-            if (lo <= zone) return hi;
+            if (v * n <= zone) return hi;
         }
         return hi;
     }
     // UniformInt<u32>::sample_single: gen_range(0..n) on u32 (main.rs:97).
     RT_HD uint32_t gen_index_u32(uint32_t n) {
         uint32_t zone = (n << __builtin_clz(n)) - 1;
-        uint32_t hi = 0;
-        for (int tries = 0; tries < RT_MAX_REJECT; tries++) {
-            uint32_t v = next_u32();
-            uint64_t m = (uint64_t)v * n;
-            uint32_t lo = (uint32_t)m;
-            hi = (uint32_t)(m >> 32);
-            if (lo <= zone) return hi;
+        uint64_t m = (uint64_t)next_u32() * n;
+        if (__builtin_expect((uint32_t)m <= zone, 1)) return (uint32_t)(m >> 32);
+        for (int tries = 1; tries < RT_MAX_REJECT; tries++) {
+            m = (uint64_t)next_u32() * n;
+            if ((uint32_t)m <= zone) return (uint32_t)(m >> 32);
         }
-        return hi;
+        return (uint32_t)(m >> 32);
     }
 };
 
