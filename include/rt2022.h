@@ -687,6 +687,99 @@ int rt_denoise_dual(const double *sum_a, const double *sum_b,
                     const uint32_t *row_ids, const rt_denoise_params *p, const rt_denoise_dual_params *q,
                     double *out_rgb_sum, double *out_variance, double *ms);
 
+/* ---- per-pixel adaptive sampling: pixel-list renders and a sample planner -------------------------------------
+ * The consumer of rt_denoise_dual's variance: more samples where the frame needs them, none where it does not,
+ *   render -> features -> denoise_dual -> plan -> render_pixels -> merge -> ... -> resolve,
+ * all in HBM. The unit of extra work is one FRAME's worth of samples of one pixel: rt_params.n_frames already gives every
+ * (frame, pixel) an independent, reproducible set of `spp` samples, so "k more units for pixel b" is "pixel b of k frames
+ * nobody has rendered yet" — and a per-pixel sample count is a multiple of spp.
+ *
+ * rt_render_pixels*: a render of a LIST of (frame, pixel) ids instead of whole rows. An entry is
+ *   id = frame * (width * height) + py * width + px,     py counted upwards as in a render,
+ * and out_rgb_sum[3e .. 3e+3) of entry e is exactly what rt_render writes for column px of row id frame * height + py with
+ * the same rt_camera and rt_params (n_frames > frame), spp_chunk included: Rng(path_key(seed, frame, py * width + px, s)),
+ * the camera's draws, ray_color on the same generator, summed in the render's order — the oracle's rt_render_cpu bit for
+ * bit, NaN where it has NaN. Repeated ids are allowed and give equal sums; the order and the size of the list never change
+ * an entry's result. The work runs in the render's wavefront engine: the only difference is where a new path's px, py and
+ * frame come from.
+ *
+ * rt_params: used — width, height, spp, max_depth, background, t_min, seed, n_frames, spp_chunk, flags; IGNORED — n_rows,
+ * row_ids, progress_cb, progress_user.
+ *
+ * Arguments: n_entries == 0, spp == 0 and max_depth == 0 are RT_OK, as for rt_radiance (zeros are written where there is
+ * output, with no kernel of the engine). RT_ERR_INVALID with rt_last_error() set, before any engine kernel: a null scene,
+ * cam or params; a null id or output buffer with n_entries > 0; width, height or n_frames equal to 0, or height * n_frames
+ * above 2^32 - 1 (the matching row id must exist); cam->time0 >= cam->time1; a flag bit other than RT_FLAG_COUNTERS /
+ * RT_FLAG_KERNEL_TIMES; a device id buffer that is not 8-byte aligned or a device output that is not 16-byte aligned;
+ * n_entries > RT_RADIANCE_MAX_RAYS or n_entries * ceil(spp / chunk) > RT_RADIANCE_MAX_ITEMS; an id >= width * height *
+ * n_frames — host ids are checked on the host, device ids by a small counting kernel whose count is read behind the one
+ * synchronisation of hip_stream the engine makes anyway before its first pass (the output is untouched). A scene switched
+ * to the A/B megakernel engine is RT_ERR_UNSUPPORTED. There is no RT_FLAG_ASYNC and no rt_scene_set form.
+ *
+ * Workspace and stats: like rt_radiance*, the call runs in the render's per-(scene, stream) workspace — pool, planes (the
+ * ring of planes under the same rule) and tape; an RT_FLAG_ASYNC render in flight on that (scene, stream) is joined and
+ * finished first; renders after it keep their bits. rt_render_pixels_device returns once the call is complete.
+ * rt_render_pixels stages ids and sums through buffers the workspace keeps, on the default stream. rt_stats (may be NULL)
+ * means what it means for a render of those pixels: paths = n_entries * spp, and with RT_FLAG_COUNTERS the counters are
+ * the oracle's sums over the same samples, camera draws included. */
+int rt_render_pixels(rt_scene *scene, const rt_camera *cam, const rt_params *params, const uint64_t *pixel_ids, uint64_t n_entries,
+                     double *out_rgb_sum, rt_stats *stats);
+int rt_render_pixels_device(rt_scene *scene, const rt_camera *cam, const rt_params *params, const uint64_t *d_pixel_ids, uint64_t n_entries,
+                            double *d_out_rgb_sum, void *hip_stream, rt_stats *stats);
+
+/* The planner, the merge and the resolve: no rt_scene, nothing of a render's state. All are defined bit for bit: IEEE * / +
+ * on doubles in the stated order with no contraction, integers otherwise. Buffers are in BUFFER order: row r of a buffer is
+ * image row row_ids[r]; row_ids is NULL (the identity) or `height` entries that are a permutation of [0, height), under
+ * rt_denoise's rules and checked by its row kernel.
+ *
+ * Plan — an error map to a list of entries. Per buffer pixel b = r * width + x (n = width * height of them):
+ *   t = err[b] * scale
+ *   units[b] = !(t >= 1.0) ? 0 : (t >= (double)max_units ? max_units : (uint32_t)t)       NaN and negatives: 0; +inf: max_units
+ *   offsets[0 .. n] = the exclusive prefix sum of units in 64 bits; offsets[n] = total, also stored to *out_total
+ *   only if total <= capacity: for k < units[b]:
+ *       entries[offsets[b] + k] = (uint64_t)(first_frame + k) * (width * height) + row_ids[r] * width + x
+ *   otherwise no entry is written, units and offsets are still valid and the call is RT_OK: capacity == 0 with NULL entries
+ *   counts only, so a caller can lower scale or grow the buffer and call again.
+ * rt_adaptive_plan_device allocates nothing: the caller gives it rt_adaptive_workspace_bytes(p) bytes (the scan's tile
+ * totals, the row kernel's map and count). It synchronises hip_stream ONCE, reading the total and the bad-row count
+ * together; a bad row list is RT_ERR_INVALID with units, offsets and entries untouched. The prefix sum is a scan in three
+ * launches — tile totals, a scan of the totals, emit — in which no workgroup ever waits on another.
+ * RT_ERR_INVALID with rt_last_error() set, before any device call: a null params, error map, units, offsets or workspace,
+ * null entries with capacity > 0; width or height 0; width * height > RT_DENOISE_MAX_PIXELS; max_units == 0 or first_frame
+ * + max_units > 2^32 - 1; a scale that is <= 0, NaN or infinite; flags or _pad != 0; misalignment — 16 bytes for the error
+ * map and the workspace, 8 for offsets and entries, 4 for units and rows. rt_adaptive_plan (host buffers) checks the row
+ * list on the host and stages through device memory of its own on the current device's default stream.
+ *
+ * Merge — the sums rt_render_pixels* wrote for a plan's entries (E, three doubles per entry), into per-pixel accumulators.
+ * One lane per pixel b, for k = 0 .. units[b]-1 in order: acc_c = acc_c + E[(offsets[b] + k) * 3 + c]; then
+ * acc_n[b] = acc_n[b] + (double)((uint64_t)units[b] * spp). Pixels with 0 units are not written. A pure enqueue.
+ * Resolve — out_c = (acc_c / acc_n[b]) * (double)spp_out: sums "of spp_out samples", so rt_tonemap_device, rt_write_color
+ * and both denoisers apply as they are; acc_n == 0 gives NaN, which the tone map turns to 0. d_out may alias d_acc_sum. A
+ * pure enqueue. Both take buffers that are 8-byte aligned (units 4); n_pixels == 0 is RT_OK with no launch; a null buffer
+ * or n_pixels > RT_DENOISE_MAX_PIXELS is RT_ERR_INVALID.
+ *
+ * Two independent halves for rt_denoise_dual need nothing more: plan twice with first_frame = f and f + max_units (the
+ * units are the same), writing at d_entries and d_entries + total; render both lists in ONE rt_render_pixels_device; merge
+ * each half of the sums into its own accumulator. */
+typedef struct rt_adaptive_params {   /* 32 B */
+    uint32_t width, height;
+    uint32_t first_frame;             /* frame of a pixel's first new unit */
+    uint32_t max_units;               /* >= 1; first_frame + max_units <= 2^32 - 1 */
+    double   scale;                   /* > 0, finite */
+    uint32_t flags, _pad;             /* 0 */
+} rt_adaptive_params;
+
+/* Bytes of device workspace rt_adaptive_plan_device needs for p's image; 0 on invalid params. */
+uint64_t rt_adaptive_workspace_bytes(const rt_adaptive_params *p);
+int rt_adaptive_plan_device(const double *d_err, const uint32_t *d_row_ids, const rt_adaptive_params *p, uint32_t *d_units, uint64_t *d_offsets,
+                            uint64_t *d_entries, uint64_t capacity, void *d_workspace, void *hip_stream, uint64_t *out_total);
+/* Host buffers (entries may be NULL with capacity 0; out_total may be NULL); synchronous. */
+int rt_adaptive_plan(const double *err, const uint32_t *row_ids, const rt_adaptive_params *p, uint32_t *units, uint64_t *offsets,
+                     uint64_t *entries, uint64_t capacity, uint64_t *out_total);
+int rt_adaptive_merge_device(const double *d_entry_sums, const uint32_t *d_units, const uint64_t *d_offsets, uint64_t n_pixels, uint32_t spp,
+                             double *d_acc_sum, double *d_acc_n, void *hip_stream);
+int rt_adaptive_resolve_device(const double *d_acc_sum, const double *d_acc_n, uint64_t n_pixels, uint32_t spp_out, double *d_out, void *hip_stream);
+
 /* write_color (main.rs:280-299): NaN→0, sqrt(c/spp), clamp [0,0.999], *255.999, floor. */
 void rt_write_color(const double rgb_sum[3], int32_t spp, uint8_t out_rgb[3]);
 /* Device form over n_pixels sums → n_pixels*3 bytes, on hip_stream. */

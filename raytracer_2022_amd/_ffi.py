@@ -223,6 +223,14 @@ RT_DENOISE_MAX_VAR_ITER = 8
 # The rt_denoise_dual* structure, in the order of rtb_denoise_dual_abi_sizes.
 DENOISE_DUAL_ABI_STRUCTS = [rt_denoise_dual_params]
 
+class rt_adaptive_params(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("first_frame", C.c_uint32), ("max_units", C.c_uint32),
+                ("scale", C.c_double), ("flags", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+# The rt_adaptive_* structure, in the order of rtb_adaptive_abi_sizes.
+ADAPTIVE_ABI_STRUCTS = [rt_adaptive_params]
+
 ABI_STRUCTS = [rt_bvh_node, rt_sphere, rt_moving_sphere, rt_rect, rt_box, rt_triangle, rt_ring, rt_medium, rt_xform,
                rt_list, rt_material, rt_texture, rt_image, rt_perlin, rt_scene_desc, rt_camera, rt_params, rt_stats,
                rt_query_ray, rt_hit]
@@ -237,6 +245,8 @@ ABI_SYMBOLS = [
     "rt_intersect", "rt_intersect_device", "rt_radiance", "rt_radiance_device",
     "rt_features", "rt_features_device", "rt_denoise_workspace_bytes", "rt_denoise", "rt_denoise_device",
     "rt_denoise_dual_workspace_bytes", "rt_denoise_dual", "rt_denoise_dual_device",
+    "rt_render_pixels", "rt_render_pixels_device", "rt_adaptive_workspace_bytes", "rt_adaptive_plan", "rt_adaptive_plan_device",
+    "rt_adaptive_merge_device", "rt_adaptive_resolve_device", "rtb_adaptive_abi_sizes",
     "rtb_scene_build", "rtb_scene_free", "rtb_scene_desc", "rtb_scene_default_view", "rtb_camera_new",
     "rtb_shuffled_rows", "rtb_bvh_build", "rtb_fill_image", "rtb_write_ppm", "rtb_write_jpeg", "rtb_image_load",
     "rtb_last_error", "rtb_abi_sizes", "rtb_radiance_abi_sizes", "rtb_features_abi_sizes", "rtb_denoise_abi_sizes",
@@ -286,6 +296,15 @@ def lib():
     L.rt_denoise_dual_workspace_bytes.restype = u64
     L.rt_denoise_dual.argtypes = [vp, vp, vp, vp, vp, P(rt_denoise_params), P(rt_denoise_dual_params), vp, vp, P(dbl)]
     L.rt_denoise_dual_device.argtypes = [vp, vp, vp, vp, vp, P(rt_denoise_params), P(rt_denoise_dual_params), vp, vp, vp, vp]
+    L.rt_render_pixels.argtypes = [vp, P(rt_camera), P(rt_params), vp, u64, vp, P(rt_stats)]
+    L.rt_render_pixels_device.argtypes = [vp, P(rt_camera), P(rt_params), vp, u64, vp, vp, P(rt_stats)]
+    L.rt_adaptive_workspace_bytes.argtypes = [P(rt_adaptive_params)]
+    L.rt_adaptive_workspace_bytes.restype = u64
+    L.rt_adaptive_plan_device.argtypes = [vp, vp, P(rt_adaptive_params), vp, vp, vp, u64, vp, vp, P(u64)]
+    L.rt_adaptive_plan.argtypes = [vp, vp, P(rt_adaptive_params), vp, vp, vp, u64, P(u64)]
+    L.rt_adaptive_merge_device.argtypes = [vp, vp, vp, u64, u32, vp, vp, vp]
+    L.rt_adaptive_resolve_device.argtypes = [vp, vp, u64, u32, vp, vp]
+    L.rtb_adaptive_abi_sizes.argtypes = [P(u32), u32]
     L.rtb_scene_build.argtypes = [C.c_char_p, u64, C.c_char_p, i32, P(vp)]
     L.rtb_scene_free.argtypes = [vp]
     L.rtb_scene_free.restype = None

@@ -316,6 +316,11 @@ DenoiseLayout denoise_layout(uint32_t width, uint32_t height) {
     return l;
 }
 
+hipError_t launch_row_list_check(const uint32_t *rows, uint32_t height, uint32_t *inv, uint32_t *bad, hipStream_t stream) {
+    hipLaunchKernelGGL(dn_rows, dim3(1), dim3(1024), 0, stream, rows, height, inv, bad);
+    return hipGetLastError();
+}
+
 hipError_t launch_denoise_rows(const DenoiseArgs &a, hipStream_t stream) {
     const DenoiseLayout l = denoise_layout(a.width, a.height);
     hipLaunchKernelGGL(dn_rows, dim3(1), dim3(1024), 0, stream, a.rows, a.height, reinterpret_cast<uint32_t *>(a.ws + l.inv_rows),

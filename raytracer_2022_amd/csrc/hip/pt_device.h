@@ -110,6 +110,10 @@ struct RenderArgs {
     // rays (n_pixels = n_rays, width = 1, no row ids), one sample per work item, the path of sample s of ray i keyed
     // path_key(rays[i].rng_state, 0, 0, s); wf_shade's rays instances read them in its fresh-path sweep.
     const rt_radiance_ray *rays;
+    // rt_render_pixels* (device, null otherwise): a list of (frame, pixel) ids takes the place of the row list. The "pixels" are
+    // the entries (n_pixels = n_entries, no row ids); entry e renders id = frame * (width * height) + py * width + px with the
+    // render's own keying and camera draws — width, height and n_frames stay the image's. wf_shade's pixel instances decode it.
+    const uint64_t *pixel_ids;
 };
 
 // ---- wavefront engine (pt_wavefront.hip) -------------------------------------------
@@ -314,6 +318,36 @@ struct DenoiseDualArgs {
 hipError_t launch_denoise_dual_rows(const DenoiseDualArgs &a, hipStream_t stream);
 // dual prepare + var_iter prefilter passes + n_iter variance-aware a-trous passes.
 hipError_t launch_denoise_dual(const DenoiseDualArgs &a, uint32_t var_iter, uint32_t n_iter, hipStream_t stream);
+
+// The denoisers' row kernel (dn_rows) on a list of `height` ids: inv[image row] = buffer row, *bad = ids out of range or repeated.
+hipError_t launch_row_list_check(const uint32_t *rows, uint32_t height, uint32_t *inv, uint32_t *bad, hipStream_t stream);
+
+// ---- adaptive sampling: planner, merge, resolve (pt_adaptive.hip, rt_adaptive_*) -----------------------
+// The planner's workspace (byte offsets, each a multiple of 16).
+struct AdaptiveLayout {
+    uint64_t n_tiles;                  // workgroups of the scan (tiles of 1024 pixels)
+    uint64_t totals;                   // (n_tiles + 1) x uint64: the tiles' units, then their exclusive scan; the last word: the total
+    uint64_t bad_rows;                 // one uint32: bad or repeated row ids of the call's list
+    uint64_t inv_rows;                 // height x uint32: image row -> buffer row (the row kernel's by-product)
+    uint64_t bytes;
+};
+AdaptiveLayout adaptive_layout(uint32_t width, uint32_t height);
+struct AdaptivePlanArgs {
+    uint32_t width, height, first_frame, max_units;
+    double scale;
+    const double *err;                 // device, buffer order
+    const uint32_t *rows;              // device: buffer row -> image row (null: the identity)
+    uint32_t *units;                   // device: [n]
+    uint64_t *offsets;                 // device: [n + 1]
+    uint64_t *entries;                 // device: [capacity] (null with capacity 0)
+    uint64_t capacity;
+    char *ws;                          // the workspace, 16-byte aligned
+};
+// The row kernel (with rows) and the scan's three launches; the total is then at ws + totals + 8 * n_tiles, the bad-row count at ws + bad_rows.
+hipError_t launch_adaptive_plan(const AdaptivePlanArgs &p, hipStream_t stream);
+hipError_t launch_adaptive_merge(const double *sums, const uint32_t *units, const uint64_t *offsets, uint64_t n, uint32_t spp, double *acc,
+                                 double *acc_n, hipStream_t stream);
+hipError_t launch_adaptive_resolve(const double *acc, const double *acc_n, uint64_t n, uint32_t spp_out, double *out, hipStream_t stream);
 
 // Launchers (pt_kernel.hip). `stack_need` = entries the scene needs (host-computed).
 hipError_t launch_render(const SceneDev &scene, const RenderArgs &args, uint32_t stack_need, bool counters,

@@ -290,9 +290,13 @@ RT_DEV Vec3 texture_value_top(const SceneDev &s, uint32_t tex, uint32_t tex_kind
 
 // RING: the partial-sum ring of RenderArgs::ring is in use (a build of its own: the default instance carries none of its
 // bookkeeping — bounded claims, starved slots, the oldest item in flight).
-// RAYS: a new path's first ray is the caller's (RenderArgs::rays, rt_radiance*) instead of the camera's: "pixel" = ray index,
-// no row ids, no camera draws. Everything else — the first sweep, the unwinding, the planes and the ring — is the render's.
-template <bool STATS, bool RING = false, bool RAYS = false>
+// SRC: where a new path starts. kSrcRows: the camera's ray for a pixel of the render's row list. kSrcRays: the caller's ray
+// (RenderArgs::rays, rt_radiance*) instead of the camera's: "pixel" = ray index, no row ids, no camera draws. kSrcPixels: the
+// camera's ray for an entry of a list of (frame, pixel) ids (RenderArgs::pixel_ids, rt_render_pixels*): "pixel" = list entry,
+// no row ids; the camera's draws are the row source's, on the image's own width and height. Everything else — the first sweep,
+// the unwinding, the planes and the ring — is the render's in all three.
+constexpr int kSrcRows = 0, kSrcRays = 1, kSrcPixels = 2;
+template <bool STATS, bool RING = false, int SRC = kSrcRows>
 __global__ void __launch_bounds__(kBlock, kShadeWaves) wf_shade(const SceneDev s, const RenderArgs *__restrict__ ap, const WfPool pool, const uint32_t parity) {
     __shared__ uint32_t hist[SK_COUNT];
     __shared__ uint32_t cursor[SK_COUNT];
@@ -653,8 +657,18 @@ __global__ void __launch_bounds__(kBlock, kShadeWaves) wf_shade(const SceneDev s
                             smp = chunk_id * a.chunk;
                             smp_end = smp + a.chunk < a.spp ? smp + a.chunk : a.spp;
                             stt.item = (uint64_t)(RING ? chunk_id % a.ring : chunk_id) * a.n_pixels + pix_slot;     // (kept as the item's place in the partial sums: ring mode, plane = sample mod R)
-                            if constexpr (RAYS) {                       // (width 1: pix_slot is the ray; n_rays < 2^32, checked by the host)
+                            if constexpr (SRC == kSrcRays) {            // (width 1: pix_slot is the ray; n_rays < 2^32, checked by the host)
                                 stt.px = (uint32_t)pix_slot; stt.py = 0; stt.frame = 0;
+                            } else if constexpr (SRC == kSrcPixels) {   // id = frame * (width * height) + py * width + px, range-checked by the host
+                                const uint64_t id = a.pixel_ids[pix_slot];
+                                if ((uint64_t)a.width * ((uint64_t)a.height * a.n_frames) <= 0xFFFFFFFFull) {     // (every id fits 32 bits)
+                                    const uint32_t i32 = (uint32_t)id, np32 = a.width * a.height;
+                                    const uint32_t f32 = i32 / np32, r32 = i32 - f32 * np32, y32 = r32 / a.width;
+                                    stt.px = r32 - y32 * a.width; stt.py = y32; stt.frame = f32;
+                                } else {
+                                    const uint64_t np = (uint64_t)a.width * a.height, f = id / np, rem = id - f * np, y = rem / a.width;
+                                    stt.px = (uint32_t)(rem - y * a.width); stt.py = (uint32_t)y; stt.frame = (uint32_t)f;
+                                }
                             } else {
                                 uint32_t g = a.row_ids[yi];
                                 uint32_t frame = g / a.height;
@@ -672,7 +686,7 @@ __global__ void __launch_bounds__(kBlock, kShadeWaves) wf_shade(const SceneDev s
                 }
                 if (!have_item) break;                                // no work left: the slot goes idle
                 if (smp == smp_end) continue;                         // empty chunk (spp == 0): store zeros next turn
-                if constexpr (RAYS) {                                 // the caller's ray record, the engine's own layout: four 16-byte loads
+                if constexpr (SRC == kSrcRays) {                      // the caller's ray record, the engine's own layout: four 16-byte loads
                     const double2 *q = reinterpret_cast<const double2 *>(a.rays + stt.px);
                     const double2 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
                     r = Ray(Vec3(q0.x, q0.y, q1.x), Vec3(q1.y, q2.x, q2.y), q3.x);
@@ -1928,6 +1942,7 @@ struct WfLaunch {
     hipStream_t stream;
     bool ring = false;          // RenderArgs::ring in use: the shade pass's ring build
     bool rays = false;          // RenderArgs::rays in use: the shade pass's caller-ray build (rt_radiance*)
+    bool pixels = false;        // RenderArgs::pixel_ids in use: the shade pass's pixel-list build (rt_render_pixels*)
 };
 using TraceKernel = void (*)(SceneDev, WfPool, double, uint32_t, uint32_t, StatsDev *, uint32_t);
 // The all-in-LDS instance for sphere-only scenes (FEAT = 0): node table of kPrimNodes records and both sphere pools. (Named ahead of
@@ -1936,10 +1951,15 @@ constexpr TraceKernel kTraceAllInLds = wf_trace<kStackTiny, false, 0, false, kCa
 template <bool STATS>
 static void launch_shade(const WfLaunch &w, uint32_t parity) {
     if (w.rays) {
-        if (w.ring) hipLaunchKernelGGL((wf_shade<STATS, true, true>), dim3(w.blocks), dim3(kBlock), 0, w.stream, w.scene, w.d_args, w.pool, parity);
-        else hipLaunchKernelGGL((wf_shade<STATS, false, true>), dim3(w.blocks), dim3(kBlock), 0, w.stream, w.scene, w.d_args, w.pool, parity);
-    } else if (w.ring) hipLaunchKernelGGL((wf_shade<STATS, true>), dim3(w.blocks), dim3(kBlock), 0, w.stream, w.scene, w.d_args, w.pool, parity);
-    else hipLaunchKernelGGL((wf_shade<STATS, false>), dim3(w.blocks), dim3(kBlock), 0, w.stream, w.scene, w.d_args, w.pool, parity);
+        if (w.ring) hipLaunchKernelGGL((wf_shade<STATS, true, kSrcRays>), dim3(w.blocks), dim3(kBlock), 0, w.stream, w.scene, w.d_args, w.pool, parity);
+        else hipLaunchKernelGGL((wf_shade<STATS, false, kSrcRays>), dim3(w.blocks), dim3(kBlock), 0, w.stream, w.scene, w.d_args, w.pool, parity);
+    } else if (!w.pixels) {
+        if (w.ring) hipLaunchKernelGGL((wf_shade<STATS, true>), dim3(w.blocks), dim3(kBlock), 0, w.stream, w.scene, w.d_args, w.pool, parity);
+        else hipLaunchKernelGGL((wf_shade<STATS, false>), dim3(w.blocks), dim3(kBlock), 0, w.stream, w.scene, w.d_args, w.pool, parity);
+    } else {                    // (named last: the instances that were there keep their places in the code object)
+        if (w.ring) hipLaunchKernelGGL((wf_shade<STATS, true, kSrcPixels>), dim3(w.blocks), dim3(kBlock), 0, w.stream, w.scene, w.d_args, w.pool, parity);
+        else hipLaunchKernelGGL((wf_shade<STATS, false, kSrcPixels>), dim3(w.blocks), dim3(kBlock), 0, w.stream, w.scene, w.d_args, w.pool, parity);
+    }
 }
 static void launch_shade(const WfLaunch &w, bool stats, uint32_t parity) { stats ? launch_shade<true>(w, parity) : launch_shade<false>(w, parity); }
 // Ring mode: out[i] = (first plane of the frame ? 0 : out[i]) + partial[first mod R][i] + ... in sample order — pixel_color += ...,
@@ -2177,7 +2197,7 @@ hipError_t PassDriver::cut_groups() {
         v.next_chunk = pool.next_chunk + g;
         v.max_list = pool.max_list + 2 * g;
         grp[g].w = WfLaunch{*r.scene, v, r.d_args, args.t_min, args.tuning, args.vote_weights, args.stats, n_segs,
-                            G == 1 ? r.stream : gs.stream[g], ringed, args.rays != nullptr};
+                            G == 1 ? r.stream : gs.stream[g], ringed, args.rays != nullptr, args.pixel_ids != nullptr};
     }
     hipError_t e;
     if (G > 1) {                                // the groups start after what the caller's stream holds so far

@@ -329,6 +329,36 @@ struct RowCheck {
     }
 };
 
+// Ids of n device-resident (frame, pixel) entries that are >= limit.
+__global__ void __launch_bounds__(256) pixel_ids_bad_kernel(const uint64_t *ids, uint64_t n, uint64_t limit, uint32_t *out) {
+    uint32_t bad = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) bad += ids[i] >= limit ? 1u : 0u;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) bad += (uint32_t)__shfl_xor((int)bad, d);
+    if ((threadIdx.x & 63u) == 0 && bad) atomicAdd(out, bad);
+}
+// RowCheck's twin for the entry list of rt_render_pixels_device: how many ids are out of range, counted on the device into a
+// pinned word between begin() and the synchronisation the call makes anyway, looked at by end(). (An id out of range cannot
+// fault a kernel either: it only mis-keys a path.) The count saturates nowhere that matters: any nonzero word refuses the call.
+struct PixelCheck {
+    DeviceBuf<uint32_t> d_bad;
+    PinnedBuf<uint32_t> h_bad;
+    void begin(const uint64_t *d_ids, uint64_t n, uint64_t limit, hipStream_t stream) {      // n > 0
+        if (!h_bad) {
+            d_bad = DeviceBuf<uint32_t>(1);
+            h_bad = PinnedBuf<uint32_t>(1);
+        }
+        RT_HIP(hipMemsetAsync(d_bad, 0, sizeof(uint32_t), stream));
+        const uint64_t blocks = (n + 255u) / 256u;
+        hipLaunchKernelGGL(pixel_ids_bad_kernel, dim3((unsigned)(blocks > 256 ? 256 : blocks)), dim3(256), 0, stream, d_ids, n, limit, d_bad.p);
+        RT_HIP(hipGetLastError());
+        RT_HIP(hipMemcpyAsync(h_bad, d_bad, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    }
+    void end(const char *who) const {      // (after a synchronisation of the stream)
+        RT_REQUIRE(*h_bad.p == 0, RT_ERR_INVALID, std::string(who) + ": pixel id out of range (>= width * height * n_frames)");
+    }
+};
+
 // What one (scene, stream) keeps from render to render. Its members own their HIP resources; the ones every call needs —
 // work counter, counter block, two events — are created when it is constructed.
 struct Workspace {
@@ -354,6 +384,9 @@ struct Workspace {
     // rt_radiance (host buffers): the device copies of the caller's rays and of the sums, grown as needed
     DeviceBuf<rt_radiance_ray> rad_rays;
     DeviceBuf<double> rad_out;
+    // rt_render_pixels*: the check of device ids, and rt_render_pixels' device copy of the caller's list (its sums go through rad_out)
+    PixelCheck pixels;
+    DeviceBuf<uint64_t> pix_ids;
     // RT_FLAG_ASYNC: the host thread that drives the passes of the call in flight on this (scene, stream), and what it ended with
     // (read by rt_render_wait after the join).
     std::thread async_worker;
@@ -469,6 +502,13 @@ struct RaySource {
     const rt_radiance_ray *d_rays;
     uint64_t n_rays;
 };
+// Where the paths of an rt_render_pixels* call start: a list of (frame, pixel) ids (device) instead of the row list.
+struct PixelSource {
+    const uint64_t *d_ids;
+    uint64_t n_entries;
+    bool check;                       // the ids came from the caller's HBM: range-check them
+    const char *who;
+};
 static_assert(sizeof(rt_radiance_ray) == 64 && offsetof(rt_radiance_ray, time) == 48 && offsetof(rt_radiance_ray, rng_state) == 56,
               "rt_radiance_ray is the path slot's ray record {ox, oy, oz, dx, dy, dz, tm, rng}: wf_shade reads it in four 16-byte pieces");
 
@@ -538,12 +578,13 @@ PoolPlan plan_pool(uint64_t n_items, uint32_t n_cus, uint32_t max_depth, uint32_
 }
 
 // Enqueue one render on `stream`; row ids and output are device pointers. With `src` the call is an rt_radiance*: its
-// "pixels" are the rays of src (p: width 1, no rows, spp_chunk 1; cam unused).
+// "pixels" are the rays of src (p: width 1, no rows, spp_chunk 1; cam unused). With `pix` it is an rt_render_pixels*: its
+// "pixels" are the entries of pix (p: the image's own; n_rows and row_ids unused; wavefront engine only).
 void enqueue(rt_scene *sc, const rt_camera *cam, const rt_params *p, const uint32_t *d_rows, double *d_out,
              hipStream_t stream, rt_stats *stats, bool check_rows = false /* the row ids came from the caller's HBM: range-check them */,
-             const RaySource *src = nullptr) {
+             const RaySource *src = nullptr, const PixelSource *pix = nullptr) {
     Workspace &w = workspace_for(sc, stream);
-    if (p->n_rows == 0) check_rows = false;
+    if (p->n_rows == 0 || pix) check_rows = false;
     const uint64_t row_limit = (uint64_t)p->height * p->n_frames;
     RenderArgs a{};
     a.cam = *cam;
@@ -556,7 +597,7 @@ void enqueue(rt_scene *sc, const rt_camera *cam, const rt_params *p, const uint3
     std::memcpy(a.background, p->background, sizeof a.background);
     a.t_min = p->t_min;
     a.seed = p->seed;
-    a.n_pixels = src ? src->n_rays : (uint64_t)p->n_rows * p->width;
+    a.n_pixels = src ? src->n_rays : pix ? pix->n_entries : (uint64_t)p->n_rows * p->width;
     a.n_items = a.n_pixels * a.n_chunks;
     // The partial sums' byte counts below (24 B per work item) must not wrap: a wrapped size would allocate too little and the
     // shade pass would write past it. (rt_radiance*'s own limit, RT_RADIANCE_MAX_ITEMS, keeps its calls far below this.)
@@ -564,6 +605,7 @@ void enqueue(rt_scene *sc, const rt_camera *cam, const rt_params *p, const uint3
                RT_ERR_INVALID, "work items of the call overflow the partial sums' 64-bit byte counts");
     a.row_ids = d_rows;
     a.rays = src ? src->d_rays : nullptr;
+    a.pixel_ids = pix ? pix->d_ids : nullptr;
     bool counters = stats && (p->flags & RT_FLAG_COUNTERS);
     const bool want_kt = stats && (p->flags & RT_FLAG_KERNEL_TIMES) && sc->engine == 1;
     const RingPlan rp = sc->engine == 1 ? plan_ring(a.chunk, a.n_chunks, a.n_pixels, a.n_items, sc->partial_ring, sc->partial_ring_group, sc->ring_threshold_bytes)
@@ -613,14 +655,17 @@ void enqueue(rt_scene *sc, const rt_camera *cam, const rt_params *p, const uint3
         if (counters) RT_HIP(hipMemsetAsync(w.stats, 0, sizeof(StatsDev), stream));
         RT_HIP(hipMemcpyAsync(fx.d_args, &a, sizeof(RenderArgs), hipMemcpyHostToDevice, stream));
         if (check_rows) w.rows.begin(p->row_ids, p->n_rows, stream);
+        const bool check_pixels = pix && pix->check && pix->n_entries > 0;
+        if (check_pixels) w.pixels.begin(pix->d_ids, pix->n_entries, (uint64_t)p->width * row_limit, stream);
         RT_HIP(hipStreamSynchronize(stream));      // the three structs above live on this thread's stack
         if (check_rows) w.rows.end(row_limit, "rt_render_device");
+        if (check_pixels) w.pixels.end(pix->who);
         RT_HIP(hipEventRecord(w.ev0, stream));
         WfRender r;
         r.scene = &sc->dev; r.args = &a; r.d_args = fx.d_args; r.pool = &w.pool;
         r.stack_need = sc->stack_need; r.features = sc->features; r.counters = counters;
         r.gs = &fx.gs; r.stream = stream;
-        r.progress.cb = p->progress_cb; r.progress.user = p->progress_user;
+        r.progress.cb = pix ? nullptr : p->progress_cb; r.progress.user = p->progress_user;
         r.progress.total = a.n_pixels * p->spp; r.progress.per_item = a.chunk;
         r.ring.planes = a.ring; r.ring.out = d_out; r.ring.d_limit = fx.d_limit;
         // (watchdog of the ring's pass loop: a frame needs about items / slots pool fills of at most max_depth + 1 passes each)
@@ -808,6 +853,63 @@ void check_radiance(const rt_scene *scene, const void *rays, uint64_t n_rays, co
     RT_REQUIRE(p->spp == 0 || n_rays <= RT_RADIANCE_MAX_ITEMS / p->spp, RT_ERR_INVALID, w + ": n_rays * spp > RT_RADIANCE_MAX_ITEMS");
     RT_REQUIRE(scene, RT_ERR_INVALID, w + ": null scene");
     RT_REQUIRE(scene->engine == 1, RT_ERR_UNSUPPORTED, w + ": only the wavefront engine traces caller rays (rt_debug_set_engine)");
+}
+
+// The arguments of rt_render_pixels* (host side only, the scene last, like check_radiance). `device`: the buffers are
+// rt_render_pixels_device's — ids read as 8-byte words, sums written in 16-byte pieces.
+void check_render_pixels(const rt_scene *scene, const rt_camera *cam, const rt_params *p, const void *ids, uint64_t n_entries, const void *out,
+                         bool device, const char *who) {
+    const std::string w(who);
+    RT_REQUIRE(cam && p, RT_ERR_INVALID, w + ": null camera or params");
+    check_view(cam, p, w + ": ", "");
+    RT_REQUIRE(!(p->flags & ~(RT_FLAG_COUNTERS | RT_FLAG_KERNEL_TIMES)), RT_ERR_INVALID,
+               w + ": flag bits other than RT_FLAG_COUNTERS / RT_FLAG_KERNEL_TIMES");
+    RT_REQUIRE(n_entries == 0 || (ids && out), RT_ERR_INVALID, w + ": null id or output buffer");
+    RT_REQUIRE(!device || n_entries == 0 || !((uintptr_t)ids & 7u), RT_ERR_INVALID, w + ": the id buffer must be 8-byte aligned");
+    RT_REQUIRE(!device || n_entries == 0 || !((uintptr_t)out & 15u), RT_ERR_INVALID, w + ": the output buffer must be 16-byte aligned");
+    RT_REQUIRE(n_entries <= RT_RADIANCE_MAX_RAYS, RT_ERR_INVALID, w + ": n_entries > RT_RADIANCE_MAX_RAYS");
+    const uint32_t chunk = (p->spp_chunk == 0 || p->spp_chunk > p->spp) ? p->spp : p->spp_chunk;
+    const uint64_t n_chunks = p->spp == 0 ? 1 : ((uint64_t)p->spp + chunk - 1) / chunk;
+    // (a division, not a product: n_entries * n_chunks itself may not fit 64 bits)
+    RT_REQUIRE(n_entries <= RT_RADIANCE_MAX_ITEMS / n_chunks, RT_ERR_INVALID, w + ": n_entries * ceil(spp / spp_chunk) > RT_RADIANCE_MAX_ITEMS");
+    if (!device) {                                             // (device ids: the counting kernel, PixelCheck)
+        const uint64_t limit = (uint64_t)p->width * p->height * p->n_frames;
+        const uint64_t *host_ids = static_cast<const uint64_t *>(ids);
+        for (uint64_t i = 0; i < n_entries; i++)
+            RT_REQUIRE(host_ids[i] < limit, RT_ERR_INVALID, w + ": pixel id out of range (>= width * height * n_frames)");
+    }
+    RT_REQUIRE(scene, RT_ERR_INVALID, w + ": null scene");
+    RT_REQUIRE(scene->engine == 1, RT_ERR_UNSUPPORTED, w + ": only the wavefront engine renders pixel lists (rt_debug_set_engine)");
+}
+
+// What is wrong with the parameters of rt_adaptive_plan* (null: nothing) — rt_adaptive_workspace_bytes answers 0 to the same faults.
+const char *adaptive_params_fault(const rt_adaptive_params *p) {
+    if (!p) return "null params";
+    if (p->width == 0 || p->height == 0) return "empty image (width or height is 0)";
+    if ((uint64_t)p->width * p->height > RT_DENOISE_MAX_PIXELS) return "width * height > RT_DENOISE_MAX_PIXELS";
+    if (p->max_units == 0) return "max_units is 0";
+    if ((uint64_t)p->first_frame + p->max_units > 0xFFFFFFFFull) return "first_frame + max_units > 2^32 - 1";
+    if (!(p->scale > 0.0) || std::isinf(p->scale)) return "scale is <= 0, NaN or infinite";
+    if (p->flags != 0 || p->_pad != 0) return "flags must be 0";
+    return nullptr;
+}
+
+// One plan on `stream`: device buffers, the arguments checked. The kernels, then ONE synchronisation behind which the total
+// and the row kernel's count are read together.
+void run_adaptive_plan(const double *d_err, const uint32_t *d_rows, const rt_adaptive_params *p, uint32_t *d_units, uint64_t *d_offsets,
+                       uint64_t *d_entries, uint64_t capacity, char *d_ws, hipStream_t stream, uint64_t *out_total, const std::string &w) {
+    AdaptivePlanArgs a{};
+    a.width = p->width; a.height = p->height; a.first_frame = p->first_frame; a.max_units = p->max_units; a.scale = p->scale;
+    a.err = d_err; a.rows = d_rows; a.units = d_units; a.offsets = d_offsets; a.entries = d_entries; a.capacity = capacity; a.ws = d_ws;
+    const AdaptiveLayout l = adaptive_layout(p->width, p->height);
+    RT_HIP(launch_adaptive_plan(a, stream));
+    unsigned long long total = 0;
+    uint32_t bad = 0;
+    RT_HIP(hipMemcpyAsync(&total, d_ws + l.totals + l.n_tiles * sizeof(unsigned long long), sizeof total, hipMemcpyDeviceToHost, stream));
+    if (d_rows) RT_HIP(hipMemcpyAsync(&bad, d_ws + l.bad_rows, sizeof bad, hipMemcpyDeviceToHost, stream));
+    RT_HIP(hipStreamSynchronize(stream));
+    RT_REQUIRE(bad == 0, RT_ERR_INVALID, w + ": row_ids is not a permutation of the image's rows");
+    if (out_total) *out_total = total;
 }
 
 // What is wrong with the parameters of rt_denoise* (null: nothing) — rt_denoise_workspace_bytes answers 0 to the same faults.
@@ -1215,6 +1317,148 @@ int rt_radiance_device(rt_scene *scene, const rt_radiance_ray *d_rays, uint64_t 
         DeviceGuard guard(scene->device);
         finish_previous_async(scene, (hipStream_t)hip_stream, "rt_radiance_device");
         run_radiance(scene, d_rays, n_rays, p, d_out_rgb_sum, (hipStream_t)hip_stream, stats);
+        return RT_OK;
+    });
+}
+
+// One rt_render_pixels* call on `stream` (the scene's device is current, the arguments checked, finish_previous_async done;
+// host ids already range-checked, device ids checked here or by the enqueue): the passes, and stats.
+static void run_render_pixels(rt_scene *sc, const rt_camera *cam, const rt_params *params, const uint64_t *d_ids, uint64_t n_entries,
+                              double *d_out, hipStream_t stream, rt_stats *stats, bool check_ids, const char *who) {
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    uint32_t chunk = (params->spp_chunk == 0 || params->spp_chunk > params->spp) ? params->spp : params->spp_chunk;
+    if (chunk == 0) chunk = 1;
+    if (n_entries == 0) {
+        if (stats) stats->spp_chunk = chunk;
+        return;
+    }
+    if (params->spp == 0 || params->max_depth == 0) {           // no sample, or ray_color at depth 0: zeros, no pass
+        Workspace &w = workspace_for(sc, stream);
+        if (check_ids) w.pixels.begin(d_ids, n_entries, (uint64_t)params->width * params->height * params->n_frames, stream);
+        RT_HIP(hipStreamSynchronize(stream));
+        if (check_ids) w.pixels.end(who);
+        RT_HIP(hipMemsetAsync(d_out, 0, n_entries * 3 * sizeof(double), stream));
+        RT_HIP(hipStreamSynchronize(stream));
+        if (stats) { stats->paths = n_entries * params->spp; stats->spp_chunk = chunk; }
+        return;
+    }
+    rt_params p = *params;
+    p.n_rows = 0; p.row_ids = nullptr; p.progress_cb = nullptr; p.progress_user = nullptr;
+    const PixelSource pix{d_ids, n_entries, check_ids, who};
+    enqueue(sc, cam, &p, nullptr, d_out, stream, stats, false, nullptr, &pix);
+    finish(sc, stream);
+    if (stats) stats->paths = n_entries * params->spp;          // (the counter block's own count, also without RT_FLAG_COUNTERS)
+}
+
+int rt_render_pixels(rt_scene *scene, const rt_camera *cam, const rt_params *params, const uint64_t *pixel_ids, uint64_t n_entries,
+                     double *out_rgb_sum, rt_stats *stats) {
+    return guarded([&]() -> int {
+        const char *who = "rt_render_pixels";
+        check_render_pixels(scene, cam, params, pixel_ids, n_entries, out_rgb_sum, false, who);
+        DeviceGuard guard(scene->device);
+        finish_previous_async(scene, nullptr, who);             // (first: the staging buffers below belong to the workspace)
+        Workspace &w = workspace_for(scene, nullptr);
+        w.pix_ids.reserve(n_entries);
+        w.rad_out.reserve(n_entries * 3);
+        if (n_entries) {
+            RT_HIP(hipMemcpy(w.pix_ids, pixel_ids, n_entries * sizeof(uint64_t), hipMemcpyHostToDevice));
+            // Poison the output so an unwritten sum cannot pass for a result.
+            RT_HIP(hipMemset(w.rad_out, 0xFF, n_entries * 3 * sizeof(double)));
+        }
+        run_render_pixels(scene, cam, params, w.pix_ids, n_entries, w.rad_out, nullptr, stats, false, who);
+        if (n_entries) RT_HIP(hipMemcpy(out_rgb_sum, w.rad_out, n_entries * 3 * sizeof(double), hipMemcpyDeviceToHost));
+        return RT_OK;
+    });
+}
+
+int rt_render_pixels_device(rt_scene *scene, const rt_camera *cam, const rt_params *params, const uint64_t *d_pixel_ids, uint64_t n_entries,
+                            double *d_out_rgb_sum, void *hip_stream, rt_stats *stats) {
+    return guarded([&]() -> int {
+        const char *who = "rt_render_pixels_device";
+        check_render_pixels(scene, cam, params, d_pixel_ids, n_entries, d_out_rgb_sum, true, who);
+        DeviceGuard guard(scene->device);
+        finish_previous_async(scene, (hipStream_t)hip_stream, who);
+        run_render_pixels(scene, cam, params, d_pixel_ids, n_entries, d_out_rgb_sum, (hipStream_t)hip_stream, stats, true, who);
+        return RT_OK;
+    });
+}
+
+uint64_t rt_adaptive_workspace_bytes(const rt_adaptive_params *p) {
+    return adaptive_params_fault(p) ? 0 : adaptive_layout(p->width, p->height).bytes;
+}
+
+int rt_adaptive_plan_device(const double *d_err, const uint32_t *d_row_ids, const rt_adaptive_params *p, uint32_t *d_units, uint64_t *d_offsets,
+                            uint64_t *d_entries, uint64_t capacity, void *d_workspace, void *hip_stream, uint64_t *out_total) {
+    return guarded([&]() -> int {
+        const std::string w("rt_adaptive_plan_device");
+        const char *fault = adaptive_params_fault(p);
+        RT_REQUIRE(!fault, RT_ERR_INVALID, w + ": " + (fault ? fault : ""));
+        RT_REQUIRE(d_err && d_units && d_offsets, RT_ERR_INVALID, w + ": null error map, units or offsets");
+        RT_REQUIRE(d_entries || capacity == 0, RT_ERR_INVALID, w + ": null entries with a capacity");
+        RT_REQUIRE(d_workspace, RT_ERR_INVALID, w + ": null workspace");
+        RT_REQUIRE(!(((uintptr_t)d_err | (uintptr_t)d_workspace) & 15u), RT_ERR_INVALID, w + ": the error map and the workspace must be 16-byte aligned");
+        RT_REQUIRE(!(((uintptr_t)d_offsets | (uintptr_t)d_entries) & 7u), RT_ERR_INVALID, w + ": offsets and entries must be 8-byte aligned");
+        RT_REQUIRE(!(((uintptr_t)d_units | (uintptr_t)d_row_ids) & 3u), RT_ERR_INVALID, w + ": units and row_ids must be 4-byte aligned");
+        run_adaptive_plan(d_err, d_row_ids, p, d_units, d_offsets, d_entries, capacity, (char *)d_workspace, (hipStream_t)hip_stream, out_total, w);
+        return RT_OK;
+    });
+}
+
+int rt_adaptive_plan(const double *err, const uint32_t *row_ids, const rt_adaptive_params *p, uint32_t *units, uint64_t *offsets,
+                     uint64_t *entries, uint64_t capacity, uint64_t *out_total) {
+    return guarded([&]() -> int {
+        const std::string w("rt_adaptive_plan");
+        const char *fault = adaptive_params_fault(p);
+        RT_REQUIRE(!fault, RT_ERR_INVALID, w + ": " + (fault ? fault : ""));
+        RT_REQUIRE(err && units && offsets, RT_ERR_INVALID, w + ": null error map, units or offsets");
+        RT_REQUIRE(entries || capacity == 0, RT_ERR_INVALID, w + ": null entries with a capacity");
+        if (row_ids) {                                         // a permutation of [0, height)?
+            std::vector<char> seen(p->height, 0);
+            for (uint32_t i = 0; i < p->height; i++) {
+                RT_REQUIRE(row_ids[i] < p->height && !seen[row_ids[i]], RT_ERR_INVALID, w + ": row_ids is not a permutation of the image's rows");
+                seen[row_ids[i]] = 1;
+            }
+        }
+        const uint64_t n = (uint64_t)p->width * p->height;
+        DeviceBuf<double> d_err(n);
+        DeviceBuf<uint32_t> d_rows(row_ids ? p->height : 0), d_units(n);
+        DeviceBuf<uint64_t> d_offsets(n + 1), d_entries(capacity);
+        DeviceBuf<char> d_ws(adaptive_layout(p->width, p->height).bytes);
+        RT_HIP(hipMemcpy(d_err, err, n * sizeof(double), hipMemcpyHostToDevice));
+        if (row_ids) RT_HIP(hipMemcpy(d_rows, row_ids, p->height * sizeof(uint32_t), hipMemcpyHostToDevice));
+        uint64_t total = 0;
+        run_adaptive_plan(d_err, row_ids ? d_rows.p : nullptr, p, d_units, d_offsets, capacity ? d_entries.p : nullptr, capacity, d_ws, nullptr, &total, w);
+        RT_HIP(hipMemcpy(units, d_units, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        RT_HIP(hipMemcpy(offsets, d_offsets, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        if (total && total <= capacity) RT_HIP(hipMemcpy(entries, d_entries, total * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        if (out_total) *out_total = total;
+        return RT_OK;
+    });
+}
+
+int rt_adaptive_merge_device(const double *d_entry_sums, const uint32_t *d_units, const uint64_t *d_offsets, uint64_t n_pixels, uint32_t spp,
+                             double *d_acc_sum, double *d_acc_n, void *hip_stream) {
+    return guarded([&]() -> int {
+        const std::string w("rt_adaptive_merge_device");
+        RT_REQUIRE(n_pixels <= RT_DENOISE_MAX_PIXELS, RT_ERR_INVALID, w + ": n_pixels > RT_DENOISE_MAX_PIXELS");
+        if (n_pixels == 0) return RT_OK;
+        RT_REQUIRE(d_entry_sums && d_units && d_offsets && d_acc_sum && d_acc_n, RT_ERR_INVALID, w + ": null buffer");
+        RT_REQUIRE(!(((uintptr_t)d_entry_sums | (uintptr_t)d_offsets | (uintptr_t)d_acc_sum | (uintptr_t)d_acc_n) & 7u), RT_ERR_INVALID,
+                   w + ": sums, offsets and accumulators must be 8-byte aligned");
+        RT_REQUIRE(!((uintptr_t)d_units & 3u), RT_ERR_INVALID, w + ": units must be 4-byte aligned");
+        RT_HIP(launch_adaptive_merge(d_entry_sums, d_units, d_offsets, n_pixels, spp, d_acc_sum, d_acc_n, (hipStream_t)hip_stream));
+        return RT_OK;
+    });
+}
+
+int rt_adaptive_resolve_device(const double *d_acc_sum, const double *d_acc_n, uint64_t n_pixels, uint32_t spp_out, double *d_out, void *hip_stream) {
+    return guarded([&]() -> int {
+        const std::string w("rt_adaptive_resolve_device");
+        RT_REQUIRE(n_pixels <= RT_DENOISE_MAX_PIXELS, RT_ERR_INVALID, w + ": n_pixels > RT_DENOISE_MAX_PIXELS");
+        if (n_pixels == 0) return RT_OK;
+        RT_REQUIRE(d_acc_sum && d_acc_n && d_out, RT_ERR_INVALID, w + ": null buffer");
+        RT_REQUIRE(!(((uintptr_t)d_acc_sum | (uintptr_t)d_acc_n | (uintptr_t)d_out) & 7u), RT_ERR_INVALID, w + ": the buffers must be 8-byte aligned");
+        RT_HIP(launch_adaptive_resolve(d_acc_sum, d_acc_n, n_pixels, spp_out, d_out, (hipStream_t)hip_stream));
         return RT_OK;
     });
 }

@@ -215,6 +215,14 @@ int rtb_denoise_dual_abi_sizes(uint32_t *out, uint32_t n) {
     return (int)count;
 }
 
+// sizeof of the rt_adaptive_* structure: rt_adaptive_params (a list of its own, like the others).
+int rtb_adaptive_abi_sizes(uint32_t *out, uint32_t n) {
+    const uint32_t sizes[] = {sizeof(rt_adaptive_params)};
+    const uint32_t count = sizeof(sizes) / sizeof(sizes[0]);
+    for (uint32_t i = 0; i < n && i < count; i++) out[i] = sizes[i];
+    return (int)count;
+}
+
 int rtb_write_ppm(const char *path, const uint8_t *rgb8, uint32_t width, uint32_t height) {
     return guarded([&]() -> int {
         FILE *f = path ? std::fopen(path, "wb") : nullptr;

@@ -162,6 +162,224 @@ def denoise_dual_device(d_sum_a_ptr, d_sum_b_ptr, d_feat_a_ptr, d_feat_b_ptr, pa
                                            C.c_void_p(d_out_variance_ptr or 0), C.c_void_p(d_workspace_ptr), C.c_void_p(stream_ptr or 0)))
 
 
+def pixel_ids(frame, py, px, width, height):
+    """The entry ids of rt_render_pixels: frame * (width * height) + py * width + px as uint64, the arguments broadcast against
+    each other (py counts upwards, as in a render's row ids)."""
+    f, y, x = (np.asarray(v, dtype=np.uint64) for v in (frame, py, px))
+    return np.ascontiguousarray(f * np.uint64(width * height) + y * np.uint64(width) + x, dtype=np.uint64)
+
+
+def adaptive_params(width, height, scale, max_units, first_frame=0):
+    """rt_adaptive_params: the image, the frame of a pixel's first new unit, the cap on units per pixel and the factor that
+    turns an error into units (units = clamp(trunc(err * scale), 0, max_units))."""
+    p = F.rt_adaptive_params()
+    p.width, p.height, p.first_frame, p.max_units, p.scale, p.flags, p._pad = width, height, first_frame, max_units, scale, 0, 0
+    return p
+
+
+def adaptive_workspace_bytes(params):
+    """rt_adaptive_workspace_bytes: device bytes adaptive_plan_device needs for params' image (0: invalid params)."""
+    return int(F.lib().rt_adaptive_workspace_bytes(C.byref(params)))
+
+
+def plan_units(err, scale, max_units):
+    """The plan's own formula in numpy: units = !(t >= 1) ? 0 : (t >= max_units ? max_units : trunc(t)), t = err * scale."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        t = np.asarray(err, dtype=np.float64) * np.float64(scale)
+        ok = t >= 1.0                                             # (False for NaN)
+        capped = np.minimum(np.where(ok, t, 0.0), np.float64(max_units))
+    return np.where(ok, capped, 0.0).astype(np.uint32)
+
+
+def adaptive_scale(err, budget_units, max_units, steps=256):
+    """A scale for rt_adaptive_params: a bisection (numpy, on the plan's own formula) for the largest scale it finds whose
+    plan totals at most `budget_units`. Returns 0.0 when no positive scale it tries fits (a budget below one unit, or no
+    finite positive error): the caller then plans nothing. The total is monotone in the scale, so the bisection keeps
+    `lo` with total(lo) <= budget and `hi` with total(hi) > budget (or every pixel at max_units) and halves between them."""
+    e = np.asarray(err, dtype=np.float64).ravel()
+    total = lambda s: int(plan_units(e, s, max_units).sum(dtype=np.uint64))
+    pos = e[np.isfinite(e) & (e > 0.0)]
+    if budget_units <= 0 or pos.size == 0:
+        return 0.0
+    hi = float(max_units) / float(pos.min())                       # every positive finite pixel at max_units (unless it overflows)
+    if not np.isfinite(hi):
+        hi = np.finfo(np.float64).max
+    for _ in range(4):                                             # (the quotient may round to a hair below: min * hi < max_units)
+        if float(pos.min()) * hi >= float(max_units) or hi == np.finfo(np.float64).max:
+            break
+        hi = float(np.nextafter(hi, np.inf))
+    if total(hi) <= budget_units:
+        return hi
+    lo = 1.0 / float(pos.max()) * 0.5                              # below one unit everywhere (+inf errors aside)
+    if not (lo > 0.0) or total(lo) > budget_units:
+        return 0.0
+    for _ in range(steps):
+        mid = lo + (hi - lo) * 0.5
+        if not (lo < mid < hi):
+            break
+        if total(mid) <= budget_units:
+            lo = mid
+        else:
+            hi = mid
+    return lo
+
+
+def adaptive_plan(err, params, row_ids=None, capacity=None):
+    """rt_adaptive_plan with host buffers: the error map (height, width) in the order of `row_ids` (None: image order) ->
+    (units uint32 (height, width), offsets uint64 (n + 1), entries uint64 (total) or None, total). capacity=None sizes the
+    list by the plan's own formula; a capacity below the total gives entries None."""
+    e = np.ascontiguousarray(err, dtype=np.float64)
+    n = params.width * params.height
+    if e.size != n:
+        raise ValueError("err must hold width * height pixels")
+    rows = None
+    if row_ids is not None:
+        rows = np.ascontiguousarray(row_ids, dtype=np.uint32)
+        if rows.size != params.height:
+            raise ValueError("row_ids must hold one entry per image row")
+    if capacity is None:
+        capacity = int(plan_units(e, params.scale, params.max_units).sum(dtype=np.uint64))
+    units = np.zeros(e.shape, dtype=np.uint32)
+    offsets = np.zeros(n + 1, dtype=np.uint64)
+    entries = np.zeros(capacity, dtype=np.uint64)
+    total = C.c_uint64()
+    F.check(F.lib().rt_adaptive_plan(e.ctypes.data, rows.ctypes.data if rows is not None else None, C.byref(params), units.ctypes.data,
+                                     offsets.ctypes.data, entries.ctypes.data if capacity else None, capacity, C.byref(total)))
+    return units, offsets, (entries[:total.value] if total.value <= capacity else None), total.value
+
+
+def adaptive_plan_device(d_err_ptr, params, d_units_ptr, d_offsets_ptr, d_entries_ptr, capacity, d_workspace_ptr, d_row_ids_ptr=None,
+                         stream_ptr=None):
+    """rt_adaptive_plan_device: device pointers in (the error map and adaptive_workspace_bytes(params) bytes of workspace,
+    16-byte aligned; n units, n + 1 offsets, room for `capacity` entries — None with capacity 0 counts only), run on
+    `stream_ptr` (hipStream_t as int) -> the total. The call synchronises the stream once."""
+    total = C.c_uint64()
+    F.check(F.lib().rt_adaptive_plan_device(C.c_void_p(d_err_ptr), C.c_void_p(d_row_ids_ptr or 0), C.byref(params), C.c_void_p(d_units_ptr),
+                                            C.c_void_p(d_offsets_ptr), C.c_void_p(d_entries_ptr or 0), capacity, C.c_void_p(d_workspace_ptr),
+                                            C.c_void_p(stream_ptr or 0), C.byref(total)))
+    return total.value
+
+
+def adaptive_merge_device(d_entry_sums_ptr, d_units_ptr, d_offsets_ptr, n_pixels, spp, d_acc_sum_ptr, d_acc_n_ptr, stream_ptr=None):
+    """rt_adaptive_merge_device: adds every pixel's units of entry sums to its accumulator (3 doubles) and units * spp to its
+    sample count (1 double); a pure enqueue on `stream_ptr`."""
+    F.check(F.lib().rt_adaptive_merge_device(C.c_void_p(d_entry_sums_ptr), C.c_void_p(d_units_ptr), C.c_void_p(d_offsets_ptr), n_pixels, spp,
+                                             C.c_void_p(d_acc_sum_ptr), C.c_void_p(d_acc_n_ptr), C.c_void_p(stream_ptr or 0)))
+
+
+def adaptive_resolve_device(d_acc_sum_ptr, d_acc_n_ptr, n_pixels, spp_out, d_out_ptr, stream_ptr=None):
+    """rt_adaptive_resolve_device: out = (acc / acc_n) * spp_out, sums of spp_out samples (out may be acc); a pure enqueue."""
+    F.check(F.lib().rt_adaptive_resolve_device(C.c_void_p(d_acc_sum_ptr), C.c_void_p(d_acc_n_ptr), n_pixels, spp_out, C.c_void_p(d_out_ptr),
+                                               C.c_void_p(stream_ptr or 0)))
+
+
+# The error metric of render_adaptive: the dual filter's residual variance relative to the squared luminance of the filtered
+# demodulated mean, err = variance / (luma^2 + ADAPTIVE_LUMA_FLOOR). A documented default, not a tuned one.
+ADAPTIVE_LUMA_FLOOR = 0.01
+
+
+def render_adaptive(dev, cam, params, total_spp, rounds=2, max_units=4, denoise=None, dual=None, device="cuda", profile=False,
+                    want_state=False):
+    """Adaptive sampling on torch device buffers, image order, all stages in HBM:
+    an initial two-frame render (halves A and B, params.spp samples per pixel each) plus their features; then per round
+    denoise_dual (variance) -> err = variance / (luma^2 + 0.01) of the filtered demodulated mean -> adaptive_scale for the
+    round's share of the budget -> a plan for A and one for B (the same units, frames f.. and f + max_units..) -> ONE pixel
+    render of both lists -> two merges. The unit of extra work is params.spp samples of one half, so a unit costs 2 * spp
+    samples; the budget is total_spp * width * height samples, the initial frames included.
+    Returns (sums, counts, log): the resolved sums of A + B as a (height, width, 3) float64 tensor "of total_spp samples"
+    (rt_tonemap_device / denoisers apply with spp = total_spp), the samples each pixel really got as a (height, width)
+    float64 tensor, and a list of per-round dicts (budget_units, scale, total, pixels, samples).
+    profile=True adds the device ms of each round's plan calls, pixel render and merges to its dict (HIP events, a
+    synchronisation each). want_state=True returns a fourth value: {"acc", "acc_n", "feat"}, the halves' accumulators (2, H, W,
+    3), their sample counts (2, H, W) and the initial frames' rt_feature records (2, n, 8) — what a dual denoise of the result needs.
+    The result depends on params.seed and the arguments only: two calls give the same bits."""
+    import torch
+    W, H, spp = params.width, params.height, params.spp
+    n = W * H
+    if spp == 0 or total_spp < 2 * spp:
+        raise ValueError("total_spp must cover the two initial frames of params.spp samples each")
+    ptr = lambda t: t.data_ptr()
+    stream = torch.cuda.current_stream().cuda_stream
+    p = F.rt_params.from_buffer_copy(params)
+    p.n_frames = 2
+    p.progress_cb = None
+    p.flags = 0
+    rows = torch.from_numpy(two_frame_rows(np.arange(H, dtype=np.uint32), H).astype(np.int32)).to(device)
+    acc = torch.empty((2, H, W, 3), dtype=torch.float64, device=device)          # the halves' accumulators: A, B
+    feat = torch.empty((2, n, 8), dtype=torch.float64, device=device)            # rt_feature records
+    dev.render_device(cam, p, ptr(rows), 2 * H, ptr(acc), stream_ptr=stream)
+    dev.features_device(cam, p, ptr(rows), 2 * H, ptr(feat), stream_ptr=stream)
+    acc_n = torch.full((2, H, W), float(spp), dtype=torch.float64, device=device)
+    dn = denoise if denoise is not None else denoise_params(W, H, spp, sigma_color=DUAL_DEFAULTS["sigma_color"])
+    dn.spp = spp
+    dq = dual if dual is not None else denoise_dual_params()
+    ws = torch.empty(denoise_dual_workspace_bytes(dn), dtype=torch.uint8, device=device)
+    halves = torch.empty((2, H, W, 3), dtype=torch.float64, device=device)       # A and B as sums of spp samples
+    filt = torch.empty((H, W, 3), dtype=torch.float64, device=device)
+    var = torch.empty((H, W), dtype=torch.float64, device=device)
+    units = torch.empty(n, dtype=torch.int32, device=device)
+    offsets = torch.empty(n + 1, dtype=torch.int64, device=device)
+    ap0 = adaptive_params(W, H, 1.0, max_units)
+    aws = torch.empty(adaptive_workspace_bytes(ap0), dtype=torch.uint8, device=device)
+    alb = ((feat[0, :, 0:3] + feat[1, :, 0:3]) / float(spp + spp)).reshape(H, W, 3)
+    m = torch.where(alb > dn.albedo_floor, alb, torch.full_like(alb, dn.albedo_floor)) if not (dn.flags & F.RT_DENOISE_NO_DEMODULATE) \
+        else torch.ones_like(alb)
+    budget = (total_spp * n - 2 * spp * n) // (2 * spp)                           # units left
+
+    def timed(entry, key, call):
+        if not profile:
+            return call()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        r = call()
+        e1.record()
+        e1.synchronize()
+        entry[key] = entry.get(key, 0.0) + e0.elapsed_time(e1)
+        return r
+    frame, log = 2, []
+    for rnd in range(rounds):
+        share = budget // (rounds - rnd)
+        if share <= 0:
+            break
+        for h in range(2):
+            adaptive_resolve_device(ptr(acc[h]), ptr(acc_n[h]), n, spp, ptr(halves[h]), stream_ptr=stream)
+        denoise_dual_device(ptr(halves[0]), ptr(halves[1]), ptr(feat[0]), ptr(feat[1]), dn, dq, ptr(filt), ptr(ws),
+                            d_out_variance_ptr=ptr(var), stream_ptr=stream)
+        e = filt / (m * float(spp + spp))
+        luma = 0.2126 * e[..., 0] + 0.7152 * e[..., 1] + 0.0722 * e[..., 2]
+        err = (var / (luma * luma + ADAPTIVE_LUMA_FLOOR)).contiguous()
+        scale = adaptive_scale(err.cpu().numpy(), share, max_units)
+        entry = {"round": rnd, "budget_units": int(share), "scale": scale, "total": 0, "pixels": 0, "samples": 0}
+        log.append(entry)
+        if not scale > 0.0:
+            continue
+        ap = adaptive_params(W, H, scale, max_units, first_frame=frame)
+        total = timed(entry, "plan_ms", lambda: adaptive_plan_device(ptr(err), ap, ptr(units), ptr(offsets), None, 0, ptr(aws), stream_ptr=stream))
+        if total == 0:
+            continue
+        entries = torch.empty(2 * total, dtype=torch.int64, device=device)
+        sums = torch.empty((2 * total, 3), dtype=torch.float64, device=device)
+        timed(entry, "plan_ms", lambda: adaptive_plan_device(ptr(err), ap, ptr(units), ptr(offsets), ptr(entries), total, ptr(aws), stream_ptr=stream))
+        ap.first_frame = frame + max_units
+        timed(entry, "plan_ms", lambda: adaptive_plan_device(ptr(err), ap, ptr(units), ptr(offsets), ptr(entries[total:]), total, ptr(aws),
+                                                             stream_ptr=stream))
+        frame += 2 * max_units
+        p.n_frames = frame
+        timed(entry, "render_pixels_ms", lambda: dev.render_pixels_device(cam, p, ptr(entries), 2 * total, ptr(sums), stream_ptr=stream))
+        timed(entry, "merge_ms", lambda: [adaptive_merge_device(ptr(sums[h * total:]), ptr(units), ptr(offsets), n, spp, ptr(acc[h]), ptr(acc_n[h]),
+                                                                stream_ptr=stream) for h in range(2)])
+        budget -= total
+        entry.update(total=int(total), pixels=int((units > 0).sum().item()), samples=int(2 * total * spp))
+    counts = acc_n[0] + acc_n[1]
+    both = acc[0] + acc[1]
+    out = torch.empty((H, W, 3), dtype=torch.float64, device=device)
+    adaptive_resolve_device(ptr(both), ptr(counts), n, total_spp, ptr(out), stream_ptr=stream)
+    torch.cuda.current_stream().synchronize()
+    if want_state:
+        return out, counts, log, {"acc": acc, "acc_n": acc_n, "feat": feat}
+    return out, counts, log
+
+
 class DeviceScene:
     """rt_scene: the flattened scene copied into HBM on the current HIP device."""
 
@@ -275,6 +493,29 @@ class DeviceScene:
         An rt_stats is filled (its counters with RT_FLAG_COUNTERS in params.flags)."""
         F.check(F.lib().rt_radiance_device(self._h, C.c_void_p(d_rays_ptr), n, C.byref(params), C.c_void_p(d_out_ptr),
                                            C.c_void_p(stream_ptr or 0), C.byref(stats) if stats is not None else None))
+
+    def render_pixels(self, cam, params, ids, want_stats=False, kernel_times=False):
+        """rt_render_pixels with host buffers: the render's sums of a list of (frame, pixel) ids (uint64, see pixel_ids; params.n_frames
+        must exceed every frame) → (n, 3) float64 [, rt_stats with the counters]. n_rows, row_ids and progress_cb are ignored."""
+        e = np.ascontiguousarray(ids, dtype=np.uint64).ravel()
+        p = F.rt_params.from_buffer_copy(params)
+        p.n_rows, p.row_ids, p.progress_cb = 0, None, None
+        p.flags = (p.flags & (F.RT_FLAG_COUNTERS | F.RT_FLAG_KERNEL_TIMES)) | (F.RT_FLAG_COUNTERS if want_stats else 0) | \
+                  (F.RT_FLAG_KERNEL_TIMES if kernel_times else 0)
+        out = np.zeros((len(e), 3), dtype=np.float64)
+        st = F.rt_stats()
+        F.check(F.lib().rt_render_pixels(self._h, C.byref(cam), C.byref(p), e.ctypes.data if len(e) else None, len(e),
+                                         out.ctypes.data if len(e) else None, C.byref(st)))
+        return (out, st) if want_stats else out
+
+    def render_pixels_device(self, cam, params, d_ids_ptr, n_entries, d_out_ptr, stream_ptr=None, stats=None):
+        """rt_render_pixels_device: device pointers in (n_entries uint64 ids, 8-byte aligned; room for 3 * n_entries doubles,
+        16-byte aligned), run on `stream_ptr` (hipStream_t as int); returns when the sums are written. An rt_stats is filled
+        (its counters with RT_FLAG_COUNTERS in params.flags)."""
+        p = F.rt_params.from_buffer_copy(params)
+        p.n_rows, p.row_ids, p.progress_cb = 0, None, None
+        F.check(F.lib().rt_render_pixels_device(self._h, C.byref(cam), C.byref(p), C.c_void_p(d_ids_ptr), n_entries, C.c_void_p(d_out_ptr),
+                                                C.c_void_p(stream_ptr or 0), C.byref(stats) if stats is not None else None))
 
     def features(self, cam, params, row_ids, want_stats=False):
         """rt_features with host buffers: the first-hit guide buffers of the camera rays a render of (cam, params, row_ids)

@@ -1,0 +1,261 @@
+"""Pixel-list renders (rt_render_pixels / rt_render_pixels_device) against the CPU oracle's rt_render_cpu and against
+rt_render itself, entry by entry and bit for bit: entry id = frame * (width * height) + py * width + px is column px of row
+id frame * height + py of a render with the same camera and parameters, NaN where the oracle has NaN, and the summed
+counters where the list is whole rows."""
+import ctypes as C
+import json
+import os
+
+import numpy as np
+import pytest
+
+from raytracer_2022_amd import _ffi as F
+
+pytestmark = pytest.mark.gpu
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+INDEX = json.load(open(os.path.join(HERE, "golden", "golden_index.json")))
+COUNTERS = ("paths", "rays", "node_visits", "prim_tests", "light_pdf_tests", "rng_draws")
+
+
+@pytest.fixture(scope="module", autouse=True)
+def torch_first():
+    """Bring torch's HIP context up before the library's first call, as the other GPU test modules do."""
+    import torch
+    assert torch.cuda.is_available(), "gpu tests need a GPU: the HIP path has no fallback"
+    torch.zeros(1, device="cuda")
+
+
+def same_bits(a, b):
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return a.shape == b.shape and np.array_equal(np.isnan(a), np.isnan(b)) and \
+        np.array_equal(np.where(np.isnan(a), 0, a).view(np.uint64), np.where(np.isnan(b), 0, b).view(np.uint64))
+
+
+def counters(st):
+    d = st.as_dict()
+    return {k: d[k] for k in COUNTERS}
+
+
+def case(rt, name, n_frames=2, **over):
+    """(host scene, camera, params, device scene) of a golden case, with n_frames frames."""
+    c = INDEX[name]
+    s = rt.HostScene(c["scene"], seed=c["seed"], param=c["param"])
+    cam, bg = s.default_view(c["width"] / c["height"])
+    kw = dict(spp=c["spp"], max_depth=c["max_depth"], spp_chunk=c["spp_chunk"])
+    kw.update(over)
+    p = rt.make_params(c["width"], c["height"], kw["spp"], kw["max_depth"], bg, seed=c["seed"], n_frames=n_frames, spp_chunk=kw["spp_chunk"])
+    return s, cam, p, rt.DeviceScene(s.desc)
+
+
+def reference(O, s, cam, p, frames=(0, 1)):
+    """The oracle's render of every row of `frames` → {frame: (height, width, 3)}."""
+    rows = np.concatenate([np.arange(p.height, dtype=np.uint32) + np.uint32(f * p.height) for f in frames])
+    ref = O.render_cpu(s.desc, cam, p, rows, n_threads=4)
+    return {f: ref[i * p.height:(i + 1) * p.height] for i, f in enumerate(frames)}
+
+
+def random_list(rt, p, g, n, frames=(0, 1)):
+    """n entries over `frames` with repeats, shuffled → (ids, frame, py, px)."""
+    f = g.choice(np.asarray(frames, dtype=np.uint64), n)
+    py, px = g.integers(0, p.height, n), g.integers(0, p.width, n)
+    half = n // 2
+    if half:                                                       # repeats for certain: the second half echoes the first, then all is shuffled
+        f[half:2 * half], py[half:2 * half], px[half:2 * half] = f[:half], py[:half], px[:half]
+    perm = g.permutation(n)
+    f, py, px = f[perm], py[perm], px[perm]
+    return rt.pixel_ids(f, py, px, p.width, p.height), f, py, px
+
+
+def pick(ref, f, py, px):
+    return np.stack([ref[int(a)][int(b), int(c)] for a, b, c in zip(f, py, px)]) if len(f) else np.zeros((0, 3))
+
+
+@pytest.mark.parametrize("name", sorted(INDEX))
+def test_every_scene_builder_matches_the_oracle_and_the_render(rt, O, name):
+    s, cam, p, dev = case(rt, name)
+    g = np.random.default_rng(len(name))
+    ids, f, py, px = random_list(rt, p, g, 301)
+    assert len(np.unique(ids)) < len(ids)
+    rows = np.arange(2 * p.height, dtype=np.uint32)
+    for chunk in (0, 1, 2):
+        p.spp_chunk = chunk
+        ref = reference(O, s, cam, p)
+        want = pick(ref, f, py, px)
+        rendered = dev.render(cam, p, rows)
+        assert same_bits(rendered, np.concatenate([ref[0], ref[1]])), (name, chunk)
+        plain = dev.render_pixels(cam, p, ids)
+        counted, st = dev.render_pixels(cam, p, ids, want_stats=True)
+        assert same_bits(plain, want), (name, chunk, "plain")
+        assert same_bits(counted, want), (name, chunk, "counters")
+        assert st.paths == len(ids) * p.spp and st.spp_chunk == (chunk if 0 < chunk <= p.spp else p.spp), (name, chunk)
+        assert np.any(plain != 0)
+
+
+@pytest.mark.parametrize("name", ["cornell_smoke", "final_scene_chunked_2frames"])
+def test_whole_rows_have_the_oracles_counters(rt, O, name):
+    s, cam, p, dev = case(rt, name)
+    row_ids = np.array([p.height + 3, 1, 2 * p.height - 1], dtype=np.uint32)            # frame 1, frame 0, frame 1
+    ref, st_ref = O.render_cpu(s.desc, cam, p, row_ids, n_threads=1, want_stats=True)
+    f, py = row_ids // p.height, row_ids % p.height
+    ids = rt.pixel_ids(f[:, None], py[:, None], np.arange(p.width)[None, :], p.width, p.height).ravel()
+    got, st = dev.render_pixels(cam, p, ids, want_stats=True)
+    assert same_bits(got.reshape(ref.shape), ref)
+    assert counters(st) == counters(st_ref)
+    again, st_r = dev.render(cam, p, row_ids, want_stats=True)
+    assert same_bits(again, ref) and counters(st_r) == counters(st)
+    g = np.random.default_rng(5)
+    perm = g.permutation(len(ids))                                                       # the order of the list changes no counter
+    got_p, st_p = dev.render_pixels(cam, p, ids[perm], want_stats=True)
+    assert same_bits(got_p, got[perm]) and counters(st_p) == counters(st)
+
+
+def test_list_lengths_pool_of_one_segment_and_the_ring(rt, O):
+    s, cam, p, dev = case(rt, "cornell_box")
+    ref = reference(O, s, cam, p)
+    g = np.random.default_rng(9)
+    for n in (1, 63, 64, 65, 4097):
+        ids, f, py, px = random_list(rt, p, g, n)
+        assert same_bits(dev.render_pixels(cam, p, ids), pick(ref, f, py, px)), n
+    # one segment of 4096 slots for 3 * 4096 + 5 one-sample work items: every slot takes several items in turn
+    p1 = F.rt_params.from_buffer_copy(p)
+    p1.spp, p1.spp_chunk = 1, 1
+    ref1 = reference(O, s, cam, p1)
+    ids, f, py, px = random_list(rt, p1, g, 3 * 4096 + 5)
+    want = pick(ref1, f, py, px)
+    dev.set_engine("wavefront", max_pool_blocks=1)
+    got, st = dev.render_pixels(cam, p1, ids, want_stats=True)
+    assert st.pool_slots == 4096 and same_bits(got, want)
+    p.spp_chunk = 1                                                                      # 4 one-sample items per entry, one segment
+    ids4, f4, py4, px4 = random_list(rt, p, g, 4096 + 7)
+    ref_c1 = reference(O, s, cam, p)
+    want4 = pick(ref_c1, f4, py4, px4)
+    assert same_bits(dev.render_pixels(cam, p, ids4), want4)
+    dev.set_engine("wavefront", max_pool_blocks=0)
+    # the ring of planes forced to one and to two planes
+    full, st_full = dev.render_pixels(cam, p, ids4, want_stats=True)
+    assert same_bits(full, want4) and st_full.partial_bytes == len(ids4) * 4 * 24
+    for planes in (1, 2):
+        dev.set_partial_ring(planes)
+        ring, st_r = dev.render_pixels(cam, p, ids4, want_stats=True)
+        assert same_bits(ring, want4), planes
+        assert st_r.partial_bytes == planes * len(ids4) * 24 and counters(st_r) == counters(st_full), planes
+    dev.set_partial_ring(0)
+
+
+def test_ids_past_32_bits_take_the_64_bit_decode(rt, O):
+    """n_frames = 2^25 + 1 on the 16 x 12 case: the ids of frame 2^25 pass 2^32, its row ids still fit the oracle's 32 bits."""
+    big = 1 << 25
+    s, cam, p, dev = case(rt, "final_scene_chunked_2frames", n_frames=big + 1)
+    assert p.width * p.height * big > 1 << 32 and (big + 1) * p.height < 1 << 32
+    ref = reference(O, s, cam, p, frames=(0, 1, big))
+    g = np.random.default_rng(25)
+    ids, f, py, px = random_list(rt, p, g, 200, frames=(0, 1, big))
+    assert ids.max() > 1 << 32 and ids.min() < p.width * p.height
+    got, st = dev.render_pixels(cam, p, ids, want_stats=True)
+    assert same_bits(got, pick(ref, f, py, px))
+    assert same_bits(dev.render_pixels(cam, p, ids), got)
+    # the same frames 0 and 1 through the 32-bit decode
+    p2 = F.rt_params.from_buffer_copy(p)
+    p2.n_frames = 2
+    low = f < 2
+    assert same_bits(dev.render_pixels(cam, p2, ids[low]), got[low])
+
+
+def test_nan_pixels_come_out_like_the_oracles(rt, O):
+    b = rt.DescBuilder()
+    b.set_root(b.rect(F.RT_RECT_XZ, -5, 5, -5, 5, 0.0, b.lambertian((0.7, 0.7, 0.7))))
+    b.light(b.rect(F.RT_RECT_XZ, -1, 1, -1, 1, 3.0, b.diffuse_light((5, 5, 5)), flip=True))      # pdf 0: 0 / 0 samples
+    d = b.desc()
+    cam = rt.camera_new((0, 3, 6), (0, 0, 0), (0, 1, 0), 40.0, 1.0, 0.0, 10.0, 0.0, 1.0)
+    p = rt.make_params(24, 24, 8, 10, (0.2, 0.2, 0.2), seed=3)
+    ref = O.render_cpu(d, cam, p, np.arange(24, dtype=np.uint32), n_threads=4)
+    assert np.isnan(ref).any() and np.isfinite(ref).any()
+    ids = rt.pixel_ids(0, np.arange(24)[:, None], np.arange(24)[None, :], 24, 24).ravel()
+    got = rt.DeviceScene(d).render_pixels(cam, p, ids)
+    assert same_bits(got.reshape(ref.shape), ref)
+
+
+def test_zero_work_and_the_megakernel_engine(rt):
+    s, cam, p, dev = case(rt, "cornell_box")
+    ids = rt.pixel_ids(1, [0, 5], [3, 3], p.width, p.height)
+    out, st = dev.render_pixels(cam, p, ids[:0], want_stats=True)
+    assert out.shape == (0, 3) and st.paths == 0 and st.rays == 0
+    for kw in ({"spp": 0}, {"max_depth": 0}):
+        q = F.rt_params.from_buffer_copy(p)
+        for k, v in kw.items():
+            setattr(q, k, v)
+        out, st = dev.render_pixels(cam, q, ids, want_stats=True)
+        assert out.shape == (2, 3) and not np.any(out.view(np.uint64)), kw
+        assert st.paths == 2 * q.spp and st.rays == 0, kw
+    dev.set_engine("mega")
+    with pytest.raises(rt.RtError) as e:
+        dev.render_pixels(cam, p, ids)
+    assert e.value.code == F.RT_ERR_UNSUPPORTED and "wavefront" in str(e.value)
+    dev.set_engine("wavefront")
+    assert dev.render_pixels(cam, p, ids).shape == (2, 3)
+
+
+def test_device_form_streams_async_join_and_what_follows(rt, O):
+    import torch
+    c = INDEX["cornell_box"]
+    gold = np.load(os.path.join(HERE, "golden", "golden_cornell_box.npz"))
+    s, cam, p, dev = case(rt, "cornell_box")
+    p_gold = F.rt_params.from_buffer_copy(p)
+    p_gold.n_frames = c["n_frames"]
+    ref = reference(O, s, cam, p)
+    g = np.random.default_rng(4)
+    ids, f, py, px = random_list(rt, p, g, 777)
+    want = pick(ref, f, py, px)
+    n = len(ids)
+    L = rt.lib()
+    stream = torch.cuda.Stream()
+    d_ids = torch.from_numpy(ids.view(np.int64)).cuda()
+    d_out = torch.full((n, 3), 7.0, dtype=torch.float64, device="cuda")
+    torch.cuda.synchronize()
+    # ids out of range are refused by the counting kernel, the output untouched
+    limit = p.width * p.height * p.n_frames
+    for bad in (limit, (1 << 64) - 1):
+        e = ids.copy()
+        e[n // 2] = bad
+        d_bad = torch.from_numpy(e.view(np.int64)).cuda()
+        torch.cuda.synchronize()
+        rc = L.rt_render_pixels_device(dev._h, C.byref(cam), C.byref(p), C.c_void_p(d_bad.data_ptr()), n, C.c_void_p(d_out.data_ptr()),
+                                       C.c_void_p(stream.cuda_stream), None)
+        assert rc == F.RT_ERR_INVALID and "pixel id out of range" in L.rt_last_error().decode(), bad
+        torch.cuda.synchronize()
+        assert torch.all(d_out == 7.0), bad
+    # torch buffers on a stream of their own, with stats
+    st = F.rt_stats()
+    pc = F.rt_params.from_buffer_copy(p)
+    pc.flags = F.RT_FLAG_COUNTERS
+    dev.render_pixels_device(cam, pc, d_ids.data_ptr(), n, d_out.data_ptr(), stream.cuda_stream, st)
+    assert same_bits(d_out.cpu().numpy(), want) and st.paths == n * p.spp and st.rays >= st.paths
+    # the zero-work cases write zeros on the stream; a misaligned output is refused
+    q = F.rt_params.from_buffer_copy(p)
+    q.spp = 0
+    dev.render_pixels_device(cam, q, d_ids.data_ptr(), n, d_out.data_ptr(), stream.cuda_stream, None)
+    assert not torch.any(d_out.view(torch.int64))
+    rc = L.rt_render_pixels_device(dev._h, C.byref(cam), C.byref(p), C.c_void_p(d_ids.data_ptr()), 1, C.c_void_p(d_out.data_ptr() + 8),
+                                   C.c_void_p(stream.cuda_stream), None)
+    assert rc == F.RT_ERR_INVALID and "16-byte aligned" in L.rt_last_error().decode()
+    # an asynchronous render in flight on the stream is joined first, and keeps its result
+    big = rt.make_params(96, 64, 8, 50, tuple(p.background), seed=5, spp_chunk=1)
+    big_rows = rt.shuffled_rows(64, 5)
+    want_big = dev.render(cam, big, big_rows)
+    rays = rt.radiance_rays((278, 278, -800), np.array([[0.0, 0.0, 1.0], [0.1, 0.05, 1.0], [-0.2, 0.1, 1.0]]), rng_state=[3, 4, 5])
+    rad_before = dev.radiance(rays, spp=3)
+    d_rows = torch.from_numpy(big_rows.view(np.int32)).cuda()
+    d_big = torch.full((64, 96, 3), float("nan"), dtype=torch.float64, device="cuda")
+    d_out.fill_(float("nan"))
+    torch.cuda.synchronize()
+    big_st = F.rt_stats()
+    dev.render_device(cam, big, d_rows.data_ptr(), 64, d_big.data_ptr(), stream.cuda_stream, big_st, asynchronous=True)
+    dev.render_pixels_device(cam, p, d_ids.data_ptr(), n, d_out.data_ptr(), stream.cuda_stream, None)
+    assert same_bits(d_out.cpu().numpy(), want)
+    assert same_bits(d_big.cpu().numpy(), want_big) and big_st.passes > 0           # (its stats were filled by the join)
+    # what follows keeps its bits: the golden render, and a radiance call
+    rows = np.ascontiguousarray(gold["rows"], dtype=np.uint32)
+    assert np.array_equal(dev.render(cam, p_gold, rows).view(np.uint64), gold["rgb_sum"].view(np.uint64))
+    assert same_bits(dev.radiance(rays, spp=3), rad_before)
+    assert same_bits(dev.render_pixels(cam, p, ids), want)
