@@ -95,6 +95,7 @@ def _bind(L):
     L.rto_last_error.restype = C.c_char_p
     L.rto_hit.argtypes = [P(F.rt_scene_desc), u32, P(dbl), dbl, dbl, u64, P(rto_hit_record), P(F.rt_stats)]
     L.rto_ray_color.argtypes = [P(F.rt_scene_desc), P(dbl), P(dbl), dbl, C.c_int, u64, P(dbl), P(F.rt_stats)]
+    L.rto_radiance.argtypes = [P(F.rt_scene_desc), C.c_void_p, u64, u32, P(dbl), dbl, C.c_int, C.c_void_p, P(F.rt_stats), C.c_int]
     L.rto_get_ray.argtypes = [P(F.rt_camera), dbl, dbl, u64, P(dbl)]
     L.rto_texture_value.argtypes = [P(F.rt_scene_desc), u32, dbl, dbl, P(dbl), P(dbl)]
     L.rto_perlin_noise.argtypes = [P(F.rt_perlin), P(dbl)]
@@ -183,6 +184,19 @@ def ray_color(desc, orig, direction, tm=0.0, background=(0, 0, 0), t_min=0.001, 
     lib().rto_ray_color(C.byref(desc), ray, _d(background), t_min, depth, rng_state, out,
                         C.byref(stats) if stats is not None else None)
     return np.array(out[:])
+
+
+def radiance(desc, rays, spp=1, background=(0, 0, 0), t_min=0.001, depth=50, n_threads=1, want_stats=False):
+    """rto_radiance, the CPU twin of rt_radiance: `rays` an array of RADIANCE_RAY_DTYPE records → (n, 3) float64 sums over
+    spp samples, sample s of ray i drawing from path_key(rng_state_i, 0, 0, s) [, rt_stats with the summed counters]."""
+    r = np.ascontiguousarray(rays, dtype=F.RADIANCE_RAY_DTYPE)
+    out = np.zeros((len(r), 3), dtype=np.float64)
+    st = F.rt_stats()
+    rc = lib().rto_radiance(C.byref(desc), r.ctypes.data if len(r) else None, len(r), spp, _d(background), t_min, depth,
+                            out.ctypes.data if len(r) else None, C.byref(st), n_threads)
+    if rc < 0:
+        raise RuntimeError("oracle error %d: %s" % (rc, lib().rto_last_error().decode()))
+    return (out, st) if want_stats else out
 
 
 def texture_value(desc, tex, u, v, p):

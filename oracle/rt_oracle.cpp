@@ -875,6 +875,58 @@ int rto_ray_color(const rt_scene_desc *scene, const double ray[7], const double 
     return RT_OK;
 }
 
+// CPU twin of rt_radiance: sample s of ray i draws from path_key(rays[i].rng_state, 0, 0, s); the samples are summed
+// 0 + L_0 + L_1 + ... in order (main.rs:143,149), one ray_color call each. Workers take contiguous sections of the ray
+// list like rt_render_cpu's of the row list; a ray's sum does not depend on the section it falls in.
+int rto_radiance(const rt_scene_desc *scene, const rt_radiance_ray *rays, uint64_t n, uint32_t spp, const double background[3],
+                 double t_min, int depth, double *out_rgb_sum, rt_stats *stats, int n_threads) {
+    if (!scene || !background || ((!rays || !out_rgb_sum) && n)) { g_err = "null argument"; return RT_ERR_INVALID; }
+    if (scene->abi_version != RT2022_ABI_VERSION) { g_err = "abi_version mismatch"; return RT_ERR_INVALID; }
+    if (n_threads < 1) n_threads = 1;
+    if ((uint64_t)n_threads > n && n > 0) n_threads = (int)n;
+    std::vector<rt_stats> per(n_threads);
+    for (auto &s : per) std::memset(&s, 0, sizeof s);
+    const bool census = g_census_on.load() != 0;
+    std::vector<rto_shade_census> per_census(census ? n_threads : 0);
+    for (auto &c : per_census) std::memset(&c, 0, sizeof c);
+    const Color bg = v3(background);
+    auto t0 = std::chrono::steady_clock::now();
+    auto work = [&](int tid) {
+        uint64_t section = n / (uint64_t)n_threads;
+        uint64_t beg = (uint64_t)tid * section;
+        uint64_t end = tid == n_threads - 1 ? n : beg + section;
+        rt_stats &st = per[tid];
+        for (uint64_t i = beg; i < end; i++) {
+            const rt_radiance_ray &q = rays[i];
+            Ray r(v3(q.origin), v3(q.direction), q.time);
+            Color acc(0.0, 0.0, 0.0);
+            for (uint32_t smp = 0; smp < spp; smp++) {
+                Rng rng(rtm::path_key(q.rng_state, 0, 0, smp));
+                Ctx c{scene, &rng, &st};
+                if (census) c.cen = &per_census[tid];
+                st.paths++;
+                acc += ray_color(c, r, bg, t_min, depth);
+                st.rng_draws += rng.draws;
+            }
+            out_rgb_sum[3 * i + 0] = acc.x; out_rgb_sum[3 * i + 1] = acc.y; out_rgb_sum[3 * i + 2] = acc.z;
+        }
+    };
+    if (n_threads == 1) work(0);
+    else {
+        std::vector<std::thread> pool;
+        for (int t = 0; t < n_threads; t++) pool.emplace_back(work, t);
+        for (auto &t : pool) t.join();
+    }
+    auto t1 = std::chrono::steady_clock::now();
+    for (auto &c : per_census) census_add(c);
+    if (stats) {
+        std::memset(stats, 0, sizeof *stats);
+        for (auto &s : per) add_stats(*stats, s);
+        stats->ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    }
+    return RT_OK;
+}
+
 int rto_get_ray(const rt_camera *cam, double s, double t, uint64_t rng_state, double out_ray[7]) {
     Rng rng(rng_state);
     Ray r = get_ray(*cam, s, t, rng);

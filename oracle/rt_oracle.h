@@ -50,6 +50,11 @@ int rto_hit(const rt_scene_desc *scene, uint32_t ref, const double ray[7], doubl
             uint64_t rng_state, rto_hit_record *out, rt_stats *stats);
 int rto_ray_color(const rt_scene_desc *scene, const double ray[7], const double background[3], double t_min,
                   int depth, uint64_t rng_state, double out_rgb[3], rt_stats *stats);
+/* CPU twin of rt_radiance: out_rgb_sum[3 i ..] = 0 + L_0 + L_1 + ... over spp samples of ray i, sample s drawing from
+ * path_key(rays[i].rng_state, 0, 0, s), each L one ray_color call; n_threads workers over contiguous sections of the rays.
+ * stats (may be NULL): paths = n * spp and the summed counters of the calls. */
+int rto_radiance(const rt_scene_desc *scene, const rt_radiance_ray *rays, uint64_t n, uint32_t spp, const double background[3],
+                 double t_min, int depth, double *out_rgb_sum, rt_stats *stats, int n_threads);
 int rto_get_ray(const rt_camera *cam, double s, double t, uint64_t rng_state, double out_ray[7]);
 int rto_texture_value(const rt_scene_desc *scene, uint32_t tex, double u, double v, const double p[3], double out_rgb[3]);
 double rto_perlin_noise(const rt_perlin *pl, const double p[3]);
