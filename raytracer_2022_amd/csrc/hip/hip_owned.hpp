@@ -1,25 +1,20 @@
 // hip_owned.hpp — the four HIP resources the library holds, each owned by a small move-only struct: a device allocation,
 // a pinned host allocation, an event, a stream. Creation throws Fail (RT_HIP); destructors ignore HIP errors. An empty
 // owner (default-constructed, moved from) holds null and makes no HIP call when it dies. They are destroyed with the
-// device they were created on current: rt_api.hip's entry points see to that (DeviceGuard).
+// device they were created on current: the entry points (hip/rt_*.hip) see to that (DeviceGuard, rt_internal.hpp).
 #ifndef RT2022_HIP_OWNED_HPP
 #define RT2022_HIP_OWNED_HPP
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <string>
 #include <utility>
 
 #include "../../../include/rt2022.h"
+#include "../host/rt_error.hpp"
 
 namespace rt2022 {
 
-struct Fail {
-    int code;
-    std::string msg;
-};
-#define RT_REQUIRE(cond, code, msg) do { if (!(cond)) throw Fail{code, msg}; } while (0)
 #define RT_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) throw Fail{RT_ERR_DEVICE, std::string(#expr ": ") + hipGetErrorString(e_)}; } while (0)
 
 template <class T>

@@ -1,5 +1,5 @@
 // pt_device.h — device-side views of the flattened scene and the launch interface
-// between rt_api.hip (C ABI, validation, HBM residency) and pt_kernel.hip (kernels).
+// between the entry points (hip/rt_*.hip: C ABI, HBM residency) and the kernels (pt_*.hip).
 #ifndef RT2022_PT_DEVICE_H
 #define RT2022_PT_DEVICE_H
 
@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../../include/rt2022.h"
+#include "../host/rt_constants.hpp"
 #include "hip_owned.hpp"
 
 namespace rt2022 {
@@ -136,14 +137,9 @@ enum SlotKind : uint32_t {
     SK_COUNT = 12
 };
 
-// `mat` of the device copies of the primitive pools = material index | slot kind of a hit on it << kMatKindShift.
-constexpr uint32_t kMatKindShift = 24, kMatIndexMask = (1u << kMatKindShift) - 1u;
-// CheckerTextures texture_value (pt_common.hpp) follows before the texture that answers: rt_scene_create refuses a deeper chain.
-constexpr int kCheckerDepth = 8;
 
 // A pool of path slots in HBM, one array of records per field; segment b (= shade workgroup b) owns
-// the slots [b*kSlotsPerBlock, (b+1)*kSlotsPerBlock) for the whole frame.
-constexpr int kSlotsPerBlock = 4096;     // (a multiple of 256, at most 32768: list entries are u16)
+// the slots [b*kSlotsPerBlock, (b+1)*kSlotsPerBlock) for the whole frame (kSlotsPerBlock: rt_constants.hpp).
 constexpr uint64_t kRecBytes = 128, kRecDoubles = kRecBytes / 8, kRecWords = kRecBytes / 4;      // the slot record
 struct WfPool {
     uint32_t n_slots;
@@ -218,10 +214,9 @@ constexpr uint32_t kDefault = 18u | kRetiredDefault | ((uint32_t)(8 * 4096 / kSl
 static_assert(kDefault == 0x00282112u, "the default tuning word");
 } // namespace tune
 
-// Traversal-stack capacities the megakernel is instantiated for.
+// Traversal-stack capacities the megakernel is instantiated for (the largest, kStackLarge: rt_constants.hpp).
 constexpr int kStackSmall = 22;   // 22 KiB of LDS per workgroup; the lean kernels run four workgroups per CU (VGPR-bound)
 constexpr int kStackMid = 30;     // million-triangle meshes need ~26 entries; built for four workgroups per CU
-constexpr int kStackLarge = 64;
 constexpr int kBlock = 256;
 // Vote weights of the traversal schedulers, four bits per operation label from the lowest nibble up: node, sphere, rect,
 // box, medium, misc, ctx, done (publish + refill). The wave runs the label with the largest lanes x weight.
@@ -234,10 +229,6 @@ constexpr int kNodeCache = 1740;
 // The all-in-LDS instance for small sphere-only scenes: 600 node records (33 600 B), 256 Sphere records (36 B each) and
 // 512 MovingSphere records (80 B each) beside the 64 KiB of stacks.
 constexpr int kPrimNodes = 600, kPrimSpheres = 256, kPrimMoving = 512;
-// Four traversal workgroups per CU = 4 waves per SIMD = a budget of 128 VGPRs: the kernel then needs 116 and spills
-// nothing. Five (96 VGPRs, 27 spilled, 84 B of scratch per lane) measured 3 % slower in the same run, three 8-9 %
-// slower (profiles/r2_ab_occupancy.log): the kernel is bound by instruction issue far more than by latency.
-constexpr int kTraceBlocksPerCU = 4;   // resident traversal workgroups per CU the lean kernels are built for
 
 // ---- closest-hit queries (pt_query.hip, rt_intersect*) ------------------------------
 struct QueryArgs {
@@ -352,10 +343,6 @@ hipError_t launch_adaptive_resolve(const double *acc, const double *acc_n, uint6
 // Launchers (pt_kernel.hip). `stack_need` = entries the scene needs (host-computed).
 hipError_t launch_render(const SceneDev &scene, const RenderArgs &args, uint32_t stack_need, bool counters,
                          int n_blocks_hint, hipStream_t stream);
-// Arms of the traversal kernel a scene can reach (template FEAT of wf_trace).
-constexpr unsigned kFeatMisc = 1;      // triangles, rings
-constexpr unsigned kFeatMovers = 2;    // Translate / RotateY / Zoom, HittableList objects
-constexpr unsigned kFeatVolumes = 4;   // Boxes, ConstantMedium
 
 // Streams the wavefront engine runs its groups of segments on, with their events and pinned words: all created when
 // one is constructed (the caller keeps it from render to render).

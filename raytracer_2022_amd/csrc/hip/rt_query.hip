@@ -1,0 +1,186 @@
+// rt_query.hip — the closest-hit calls on a device scene: ray queries (rt_intersect*) and first-hit feature buffers (rt_features*).
+#include "rt_internal.hpp"
+
+using namespace rt2022;
+
+namespace {
+
+// The scratch of `stream` in sc->qs or sc->fs.
+QueryScratch &scratch_for(rt_scene *sc, std::map<hipStream_t, std::unique_ptr<QueryScratch>> &of, hipStream_t stream) {
+    std::lock_guard<std::mutex> lock(sc->qmu);
+    std::unique_ptr<QueryScratch> &q = of[stream];
+    if (!q) q.reset(new QueryScratch());                   // (stored once it is complete, or not at all)
+    return *q;
+}
+
+// One closest-hit call on `stream`, q locked: the counters reset, `launch()` — the kernel, on q.counter and, with `counters`,
+// q.stats — and with stats the wait for it and what read_stats makes of it.
+template <class Launch>
+void run_counted(QueryScratch &q, bool counters, hipStream_t stream, rt_stats *stats, Launch launch) {
+    RT_HIP(hipMemsetAsync(q.counter, 0, sizeof(unsigned long long), stream));
+    if (counters) RT_HIP(hipMemsetAsync(q.stats, 0, sizeof(StatsDev), stream));
+    if (stats) RT_HIP(hipEventRecord(q.ev0, stream));
+    RT_HIP(launch());
+    if (!stats) return;
+    RT_HIP(hipEventRecord(q.ev1, stream));
+    RT_HIP(hipStreamSynchronize(stream));
+    StatsDev h;
+    *stats = read_stats(q.ev0, q.ev1, counters ? q.stats.p : nullptr, h);
+}
+
+void check_query(const rt_scene *scene, const void *rays, uint64_t n_rays, uint32_t flags, const void *hits, const char *who) {
+    RT_REQUIRE(scene, RT_ERR_INVALID, std::string(who) + ": null scene");
+    RT_REQUIRE(n_rays == 0 || (rays && hits), RT_ERR_INVALID, std::string(who) + ": null ray or hit buffer");
+    RT_REQUIRE(!(flags & ~(RT_FLAG_COUNTERS | RT_FLAG_ANY_HIT)), RT_ERR_INVALID, std::string(who) + ": unknown flag bits");
+    RT_REQUIRE(!(flags & RT_FLAG_ANY_HIT) || scene->dev.n_media == 0, RT_ERR_UNSUPPORTED,
+               std::string(who) + ": RT_FLAG_ANY_HIT on a scene with a ConstantMedium (its verdict depends on the closest hit so far)");
+}
+
+// Enqueue one query on `stream` (the scene's device is current); with stats, wait for it and fill them.
+void run_query(rt_scene *sc, const rt_query_ray *d_rays, uint64_t n_rays, uint32_t flags, rt_hit *d_hits, hipStream_t stream,
+               rt_stats *stats) {
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (n_rays == 0) return;
+    QueryScratch &q = scratch_for(sc, sc->qs, stream);
+    std::lock_guard<std::mutex> lock(q.mu);
+    const bool counters = stats && (flags & RT_FLAG_COUNTERS);
+    const QueryArgs a{d_rays, d_hits, n_rays, q.counter, counters ? q.stats.p : nullptr};
+    run_counted(q, counters, stream, stats, [&] { return launch_query(sc->dev, a, sc->stack_need, counters, (flags & RT_FLAG_ANY_HIT) != 0, stream); });
+    if (stats) stats->rays = n_rays;               // (a query counts no paths, rays or light tests of its own)
+}
+
+// The arguments of rt_features* (host side only; the scene comes last so that a bad argument is reported as such whatever
+// the scene). `device`: rows and output are rt_features_device's — the rows are range-checked on the device later.
+void check_features(const rt_scene *scene, const rt_camera *cam, const rt_params *p, const void *out, bool device, const char *who) {
+    const std::string w(who);
+    RT_REQUIRE(p, RT_ERR_INVALID, w + ": null params");
+    RT_REQUIRE(cam, RT_ERR_INVALID, w + ": null camera");
+    RT_REQUIRE(!(p->flags & ~RT_FLAG_COUNTERS), RT_ERR_INVALID, w + ": flag bits other than RT_FLAG_COUNTERS");
+    check_view(cam, p, w + ": ", " (width, height or n_frames is 0)");
+    const bool need_rows = p->n_rows > 0 && p->spp > 0;
+    RT_REQUIRE(p->n_rows == 0 || out, RT_ERR_INVALID, w + ": null output");
+    RT_REQUIRE(!need_rows || p->row_ids, RT_ERR_INVALID, w + ": null row_ids");
+    RT_REQUIRE((uint64_t)p->n_rows * p->width <= (1ull << 40), RT_ERR_INVALID, w + ": n_rows * width too large");
+    if (device) {
+        RT_REQUIRE(p->n_rows == 0 || !((uintptr_t)out & 15u), RT_ERR_INVALID, w + ": the output must be 16-byte aligned");
+        RT_REQUIRE(!need_rows || !((uintptr_t)p->row_ids & 3u), RT_ERR_INVALID, w + ": row_ids must be 4-byte aligned");
+    } else if (need_rows) {
+        for (uint32_t i = 0; i < p->n_rows; i++)
+            RT_REQUIRE(p->row_ids[i] < (uint64_t)p->height * p->n_frames, RT_ERR_INVALID, w + ": row id out of range");
+    }
+    RT_REQUIRE(scene, RT_ERR_INVALID, w + ": null scene");
+}
+
+// Enqueue one feature call on `stream` (the scene's device is current, the arguments checked); with stats, wait for it and
+// fill them. `check_rows`: the row ids came from the caller's HBM — range-check them first (one synchronisation of the stream).
+void run_features(rt_scene *sc, const rt_camera *cam, const rt_params *p, const uint32_t *d_rows, rt_feature *d_out,
+                  hipStream_t stream, rt_stats *stats, bool check_rows, const char *who) {
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    const uint64_t n_pixels = (uint64_t)p->n_rows * p->width;
+    if (n_pixels == 0) return;
+    if (p->spp == 0) {                                     // no sample: zeros, no kernel
+        RT_HIP(hipMemsetAsync(d_out, 0, n_pixels * sizeof(rt_feature), stream));
+        if (stats) RT_HIP(hipStreamSynchronize(stream));
+        return;
+    }
+    QueryScratch &q = scratch_for(sc, sc->fs, stream);
+    std::lock_guard<std::mutex> lock(q.mu);
+    if (check_rows) {
+        q.rows.begin(d_rows, p->n_rows, (uint64_t)p->height * p->n_frames, stream);
+        RT_HIP(hipStreamSynchronize(stream));
+        q.rows.end(who, ": row id out of range");
+    }
+    const bool counters = stats && (p->flags & RT_FLAG_COUNTERS);
+    FeatureArgs a{};
+    a.cam = *cam;
+    a.width = p->width; a.height = p->height; a.spp = p->spp; a.n_rows = p->n_rows;
+    std::memcpy(a.background, p->background, sizeof a.background);
+    a.t_min = p->t_min;
+    a.seed = p->seed;
+    a.n_pixels = n_pixels;
+    a.row_ids = d_rows;
+    a.out = d_out;
+    a.counter = q.counter;
+    a.stats = counters ? q.stats.p : nullptr;
+    run_counted(q, counters, stream, stats, [&] { return launch_features(sc->dev, a, sc->stack_need, counters, stream); });
+    if (stats) stats->paths = stats->rays = n_pixels * p->spp;     // (one camera path, one world.hit per sample; the kernel counts neither)
+}
+
+} // namespace
+
+extern "C" {
+
+int rt_intersect(rt_scene *scene, const rt_query_ray *rays, uint64_t n_rays, uint32_t flags, rt_hit *out_hits, rt_stats *stats) {
+    return guarded([&]() -> int {
+        check_query(scene, rays, n_rays, flags, out_hits, "rt_intersect");
+        if (n_rays == 0) {
+            if (stats) std::memset(stats, 0, sizeof *stats);
+            return RT_OK;
+        }
+        RT_REQUIRE(n_rays <= (1ull << 40), RT_ERR_INVALID, "rt_intersect: n_rays too large");
+        DeviceGuard guard(scene->device);
+        DeviceBuf<rt_query_ray> d_rays(n_rays);                // (after the guard: freed with the scene's device current)
+        DeviceBuf<rt_hit> d_hits(n_rays);
+        RT_HIP(hipMemcpy(d_rays, rays, n_rays * sizeof(rt_query_ray), hipMemcpyHostToDevice));
+        run_query(scene, d_rays, n_rays, flags, d_hits, nullptr, stats);
+        RT_HIP(hipMemcpy(out_hits, d_hits, n_rays * sizeof(rt_hit), hipMemcpyDeviceToHost));
+        return RT_OK;
+    });
+}
+
+int rt_intersect_device(rt_scene *scene, const rt_query_ray *d_rays, uint64_t n_rays, uint32_t flags, rt_hit *d_out_hits,
+                        void *hip_stream, rt_stats *stats) {
+    return guarded([&]() -> int {
+        check_query(scene, d_rays, n_rays, flags, d_out_hits, "rt_intersect_device");
+        RT_REQUIRE(n_rays == 0 || !(((uintptr_t)d_rays | (uintptr_t)d_out_hits) & 15u), RT_ERR_INVALID,
+                   "rt_intersect_device: ray and hit buffers must be 16-byte aligned");
+        if (n_rays == 0) {
+            if (stats) std::memset(stats, 0, sizeof *stats);
+            return RT_OK;
+        }
+        DeviceGuard guard(scene->device);
+        run_query(scene, d_rays, n_rays, flags, d_out_hits, (hipStream_t)hip_stream, stats);
+        return RT_OK;
+    });
+}
+
+int rt_features(rt_scene *scene, const rt_camera *cam, const rt_params *params, rt_feature *out_features, rt_stats *stats) {
+    return guarded([&]() -> int {
+        check_features(scene, cam, params, out_features, false, "rt_features");
+        const uint64_t n_pixels = (uint64_t)params->n_rows * params->width;
+        if (n_pixels == 0) {
+            if (stats) std::memset(stats, 0, sizeof *stats);
+            return RT_OK;
+        }
+        if (params->spp == 0) {                                // zeros, and nothing for the device to do
+            if (stats) std::memset(stats, 0, sizeof *stats);
+            std::memset(out_features, 0, n_pixels * sizeof(rt_feature));
+            return RT_OK;
+        }
+        DeviceGuard guard(scene->device);
+        DeviceBuf<uint32_t> d_rows(params->n_rows);            // (after the guard: freed with the scene's device current)
+        DeviceBuf<rt_feature> d_out(n_pixels);
+        RT_HIP(hipMemcpy(d_rows, params->row_ids, params->n_rows * sizeof(uint32_t), hipMemcpyHostToDevice));
+        // Poison the output so an unwritten record cannot pass for a result.
+        RT_HIP(hipMemset(d_out, 0xFF, n_pixels * sizeof(rt_feature)));
+        run_features(scene, cam, params, d_rows, d_out, nullptr, stats, false, "rt_features");
+        RT_HIP(hipMemcpy(out_features, d_out, n_pixels * sizeof(rt_feature), hipMemcpyDeviceToHost));
+        return RT_OK;
+    });
+}
+
+int rt_features_device(rt_scene *scene, const rt_camera *cam, const rt_params *params, rt_feature *d_out_features, void *hip_stream,
+                       rt_stats *stats) {
+    return guarded([&]() -> int {
+        check_features(scene, cam, params, d_out_features, true, "rt_features_device");
+        if ((uint64_t)params->n_rows * params->width == 0) {
+            if (stats) std::memset(stats, 0, sizeof *stats);
+            return RT_OK;
+        }
+        DeviceGuard guard(scene->device);
+        run_features(scene, cam, params, params->row_ids, d_out_features, (hipStream_t)hip_stream, stats, true, "rt_features_device");
+        return RT_OK;
+    });
+}
+
+} // extern "C"

@@ -1,0 +1,248 @@
+// scene_check.cpp — validation of a scene description (the host half of rt_scene_create): pure host arithmetic, no HIP.
+#include "scene_check.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <string>
+
+#include "rt_constants.hpp"
+#include "rt_error.hpp"
+
+namespace rt2022 {
+namespace {
+
+// ---- validation -------------------------------------------------------------------
+struct Validator {
+    const rt_scene_desc &d;
+    // What need() knows of a record that has children: the stack entries trace<> needs below it, the deepest nesting of
+    // movers below it, and whether a medium lies below it (media do not nest inside a medium's boundary).
+    struct Need {
+        int32_t need = kUnknown, xdepth = 0;
+        bool medium = false;
+    };
+    static constexpr int32_t kUnknown = -1, kOnStack = -2;       // Need::need of a record not yet walked / being walked
+    std::vector<Need> node_memo, xform_memo, list_memo, medium_memo;     // one walk per record, however many paths lead to it
+    mutable bool general_boundaries = false;   // some medium boundary is more than a primitive under movers
+    explicit Validator(const rt_scene_desc &desc)
+        : d(desc), node_memo(desc.n_nodes), xform_memo(desc.n_xforms), list_memo(desc.n_lists), medium_memo(desc.n_media) {}
+
+    uint32_t pool_size(uint32_t kind) const {
+        switch (kind) {
+            case RT_KIND_NODE: return d.n_nodes;
+            case RT_KIND_SPHERE: return d.n_spheres;
+            case RT_KIND_MOVING_SPHERE: return d.n_moving_spheres;
+            case RT_KIND_RECT: return d.n_rects;
+            case RT_KIND_BOX: return d.n_boxes;
+            case RT_KIND_TRIANGLE: return d.n_triangles;
+            case RT_KIND_RING: return d.n_rings;
+            case RT_KIND_MEDIUM: return d.n_media;
+            case RT_KIND_TRANSLATE: case RT_KIND_ROTATE_Y: case RT_KIND_ZOOM: return d.n_xforms;
+            case RT_KIND_LIST: return d.n_lists;
+            default: return 0;
+        }
+    }
+    void check_ref(uint32_t ref, const char *where) const {
+        uint32_t kind = RT_REF_KIND(ref), idx = RT_REF_INDEX(ref);
+        RT_REQUIRE(kind < RT_KIND_COUNT, RT_ERR_INVALID, std::string(where) + ": ref with unknown kind");
+        RT_REQUIRE(idx < pool_size(kind), RT_ERR_INVALID, std::string(where) + ": ref index out of range");
+        if (kind >= RT_KIND_TRANSLATE && kind <= RT_KIND_ZOOM)
+            RT_REQUIRE(d.xforms[idx].kind == kind, RT_ERR_INVALID, std::string(where) + ": mover ref kind does not match its record");
+    }
+    // Node boxes as the reference builds them (min / max of real coordinates): finite and ordered.
+    bool boxes_plain() const {
+        for (uint32_t i = 0; i < d.n_nodes; i++)
+            for (int a = 0; a < 3; a++) {
+                double lo = d.nodes[i].bmin[a], hi = d.nodes[i].bmax[a];
+                if (!(std::isfinite(lo) && std::isfinite(hi) && lo <= hi)) return false;
+            }
+        return true;
+    }
+    void check_mat(uint32_t mat, const char *where) const {
+        RT_REQUIRE(mat < d.n_materials, RT_ERR_INVALID, std::string(where) + ": material index out of range");
+    }
+
+    void check_pools() const {
+#define RT_NONNULL(n, p) RT_REQUIRE(d.n == 0 || d.p != nullptr, RT_ERR_INVALID, #p " is null but " #n " > 0")
+        RT_NONNULL(n_nodes, nodes); RT_NONNULL(n_spheres, spheres); RT_NONNULL(n_moving_spheres, moving_spheres);
+        RT_NONNULL(n_rects, rects); RT_NONNULL(n_boxes, boxes); RT_NONNULL(n_triangles, triangles); RT_NONNULL(n_rings, rings);
+        RT_NONNULL(n_media, media); RT_NONNULL(n_xforms, xforms); RT_NONNULL(n_lists, lists); RT_NONNULL(n_list_items, list_items);
+        RT_NONNULL(n_lights, lights); RT_NONNULL(n_materials, materials); RT_NONNULL(n_textures, textures);
+        RT_NONNULL(n_images, images); RT_NONNULL(image_data_bytes, image_data); RT_NONNULL(n_perlins, perlins);
+#undef RT_NONNULL
+        for (uint32_t i = 0; i < d.n_nodes; i++) { check_ref(d.nodes[i].left, "node.left"); check_ref(d.nodes[i].right, "node.right"); }
+        for (uint32_t i = 0; i < d.n_spheres; i++) check_mat(d.spheres[i].mat, "sphere");
+        for (uint32_t i = 0; i < d.n_moving_spheres; i++) check_mat(d.moving_spheres[i].mat, "moving_sphere");
+        for (uint32_t i = 0; i < d.n_rects; i++) { check_mat(d.rects[i].mat, "rect"); RT_REQUIRE(d.rects[i].axis <= RT_RECT_YZ, RT_ERR_INVALID, "rect: bad axis"); }
+        for (uint32_t i = 0; i < d.n_boxes; i++) check_mat(d.boxes[i].mat, "box");
+        for (uint32_t i = 0; i < d.n_triangles; i++) check_mat(d.triangles[i].mat, "triangle");
+        for (uint32_t i = 0; i < d.n_rings; i++) check_mat(d.rings[i].mat, "ring");
+        for (uint32_t i = 0; i < d.n_media; i++) {
+            check_mat(d.media[i].mat, "medium");
+            RT_REQUIRE(d.materials[d.media[i].mat].kind == RT_MAT_ISOTROPIC, RT_ERR_INVALID, "medium: phase function must be Isotropic");
+            check_ref(d.media[i].boundary, "medium.boundary");
+            // A boundary that is one primitive under movers is what the megakernel engine accepts;
+            // anything else (a box of boxes, a BVH, a list) takes the wavefront engine.
+            uint32_t ref = d.media[i].boundary;
+            int lvl = 0;
+            bool simple = true;
+            while (RT_REF_KIND(ref) >= RT_KIND_TRANSLATE && RT_REF_KIND(ref) <= RT_KIND_ZOOM) {
+                if (++lvl > RT_MAX_XFORM_DEPTH) { simple = false; break; }
+                ref = d.xforms[RT_REF_INDEX(ref)].child;
+                check_ref(ref, "medium.boundary chain");
+            }
+            uint32_t k = RT_REF_KIND(ref);
+            if (!(k >= RT_KIND_SPHERE && k <= RT_KIND_RING)) simple = false;
+            if (!simple) general_boundaries = true;
+        }
+        for (uint32_t i = 0; i < d.n_xforms; i++) {
+            uint32_t k = d.xforms[i].kind;
+            RT_REQUIRE(k >= RT_KIND_TRANSLATE && k <= RT_KIND_ZOOM, RT_ERR_INVALID, "xform: bad kind");
+            check_ref(d.xforms[i].child, "xform.child");
+        }
+        for (uint32_t i = 0; i < d.n_lists; i++)
+            RT_REQUIRE((uint64_t)d.lists[i].first + d.lists[i].count <= d.n_list_items, RT_ERR_INVALID, "list: items out of range");
+        for (uint32_t i = 0; i < d.n_list_items; i++) check_ref(d.list_items[i], "list item");
+        for (uint32_t i = 0; i < d.n_lights; i++) check_ref(d.lights[i], "light");
+        for (uint32_t i = 0; i < d.n_materials; i++) {
+            const rt_material &m = d.materials[i];
+            RT_REQUIRE(m.kind <= RT_MAT_ISOTROPIC, RT_ERR_INVALID, "material: bad kind");
+            if (m.kind == RT_MAT_LAMBERTIAN || m.kind == RT_MAT_DIFFUSE_LIGHT || m.kind == RT_MAT_ISOTROPIC)
+                RT_REQUIRE(m.tex < d.n_textures, RT_ERR_INVALID, "material: texture index out of range");
+        }
+        for (uint32_t i = 0; i < d.n_textures; i++) {
+            const rt_texture &t = d.textures[i];
+            RT_REQUIRE(t.kind <= RT_TEX_IMAGE, RT_ERR_INVALID, "texture: bad kind");
+            if (t.kind == RT_TEX_CHECKER) RT_REQUIRE(t.a < d.n_textures && t.b < d.n_textures, RT_ERR_INVALID, "checker: child out of range");
+            if (t.kind == RT_TEX_NOISE) RT_REQUIRE(t.a < d.n_perlins, RT_ERR_INVALID, "noise: perlin index out of range");
+            if (t.kind == RT_TEX_IMAGE) RT_REQUIRE(t.a < d.n_images, RT_ERR_INVALID, "image texture: image index out of range");
+        }
+        for (uint32_t i = 0; i < d.n_images; i++) {
+            const rt_image &im = d.images[i];
+            // offset + 3 * width * height <= image_data_bytes, without a sum or a product that can wrap
+            const uint64_t pixels = (uint64_t)im.width * im.height;            // < 2^64: both are 32-bit
+            RT_REQUIRE(im.offset <= d.image_data_bytes && pixels <= (d.image_data_bytes - im.offset) / 3, RT_ERR_INVALID, "image: data out of range");
+        }
+        check_checkers();
+        for (uint32_t i = 0; i < d.n_perlins; i++)
+            for (int k = 0; k < 256; k++) {
+                const rt_perlin &p = d.perlins[i];
+                RT_REQUIRE((uint32_t)p.perm_x[k] < 256 && (uint32_t)p.perm_y[k] < 256 && (uint32_t)p.perm_z[k] < 256, RT_ERR_INVALID, "perlin: permutation entry out of range");
+            }
+    }
+
+    // Chains of CheckerTextures: texture_value (pt_common.hpp) follows at most kCheckerDepth checkers to the texture that
+    // answers, where the reference recurses to the leaf (texture/mod.rs:51-60). A deeper chain would render differently and
+    // a cyclic one has no leaf at all: both are refused. One walk per texture (depth[] memoises).
+    void check_checkers() const {
+        std::vector<int32_t> depth(d.n_textures, kUnknown);      // checkers on the longest chain from the texture to a leaf
+        std::vector<uint32_t> stack;
+        for (uint32_t t0 = 0; t0 < d.n_textures; t0++) {
+            if (depth[t0] != kUnknown) continue;
+            stack.push_back(t0);
+            while (!stack.empty()) {
+                const uint32_t t = stack.back();
+                if (d.textures[t].kind != RT_TEX_CHECKER) { depth[t] = 0; stack.pop_back(); continue; }
+                depth[t] = kOnStack;
+                const uint32_t kids[2] = {d.textures[t].a, d.textures[t].b};
+                bool pushed = false;
+                for (uint32_t k : kids) {
+                    RT_REQUIRE(depth[k] != kOnStack, RT_ERR_INVALID, "checker: cycle among checker children");      // (k == t too)
+                    if (depth[k] == kUnknown) { stack.push_back(k); pushed = true; break; }
+                }
+                if (pushed) continue;
+                depth[t] = 1 + std::max(depth[kids[0]], depth[kids[1]]);
+                stack.pop_back();
+            }
+        }
+        for (uint32_t t = 0; t < d.n_textures; t++)
+            RT_REQUIRE(depth[t] <= kCheckerDepth, RT_ERR_UNSUPPORTED,
+                       "checker: textures nested deeper than " + std::to_string(kCheckerDepth) + " checkers (kCheckerDepth)");
+    }
+
+    // Stack entries trace<> needs while processing `ref` (its own slot included), the deepest nesting of movers below it and
+    // whether a medium lies below it. Every node, mover, list and medium is walked once and remembered, so the walk is linear
+    // in the scene's records however many paths lead to a shared one; meeting a record that is still being walked is a cycle.
+    Need need(uint32_t ref, int depth) {
+        RT_REQUIRE(depth < 4096, RT_ERR_UNSUPPORTED, "scene graph too deep");
+        uint32_t kind = RT_REF_KIND(ref), idx = RT_REF_INDEX(ref);
+        Need *memo = kind == RT_KIND_NODE ? &node_memo[idx] : kind >= RT_KIND_TRANSLATE && kind <= RT_KIND_ZOOM ? &xform_memo[idx]
+                   : kind == RT_KIND_LIST ? &list_memo[idx] : kind == RT_KIND_MEDIUM ? &medium_memo[idx] : nullptr;
+        if (!memo) return Need{1, 0, false};                      // a primitive
+        if (kind == RT_KIND_NODE) RT_REQUIRE(!(ref & RT_REF_FLIP), RT_ERR_UNSUPPORTED, "FlipFace directly on a BvhNode ref: push the flip down to the leaves");
+        if (kind == RT_KIND_LIST) RT_REQUIRE(!(ref & RT_REF_FLIP), RT_ERR_UNSUPPORTED, "FlipFace directly on a HittableList ref: push the flip down to the items");
+        RT_REQUIRE(memo->need != kOnStack, RT_ERR_INVALID,
+                   kind == RT_KIND_NODE ? "cycle in the BVH" : "cycle in the scene graph (a list, mover or medium that contains itself)");
+        if (memo->need != kUnknown) return *memo;
+        memo->need = kOnStack;
+        Need out;
+        if (kind == RT_KIND_NODE) {
+            const Need l = need(d.nodes[idx].left, depth + 1);
+            const Need r = d.nodes[idx].right == d.nodes[idx].left ? l : need(d.nodes[idx].right, depth + 1);
+            out = Need{std::max(1 + l.need, r.need), std::max(l.xdepth, r.xdepth), l.medium || r.medium};
+        } else if (kind == RT_KIND_LIST) {
+            const rt_list &l = d.lists[idx];
+            out = Need{std::max<int32_t>(1, (int32_t)l.count), 0, false};
+            for (uint32_t i = 0; i < l.count; i++) {
+                const Need it = need(d.list_items[l.first + i], depth + 1);
+                out.need = std::max(out.need, (int32_t)(l.count - 1 - i) + it.need);
+                out.xdepth = std::max(out.xdepth, it.xdepth);
+                out.medium = out.medium || it.medium;
+            }
+        } else if (kind == RT_KIND_MEDIUM) {
+            // the medium's own slot becomes the sub-query sentinel while its boundary is traversed
+            const Need b = need(d.media[idx].boundary, depth + 1);
+            RT_REQUIRE(!b.medium, RT_ERR_UNSUPPORTED, "a medium inside another medium's boundary");
+            out = Need{1 + b.need, b.xdepth, true};
+        } else {
+            const Need c = need(d.xforms[idx].child, depth + 1);
+            out = Need{1 + c.need, 1 + c.xdepth, c.medium};
+        }
+        *memo = out;
+        return out;
+    }
+};
+
+} // namespace
+
+SceneFacts check_scene(const rt_scene_desc &d) {
+    Validator v(d);
+    v.check_pools();
+    v.check_ref(d.root, "root");
+    const Validator::Need root = v.need(d.root, 0);
+    RT_REQUIRE(root.need <= kStackLarge, RT_ERR_UNSUPPORTED, "scene needs a deeper traversal stack than the kernel provides");
+    RT_REQUIRE(root.xdepth <= RT_MAX_XFORM_DEPTH, RT_ERR_UNSUPPORTED, "movers nested deeper than RT_MAX_XFORM_DEPTH");
+    const unsigned features = ((d.n_triangles || d.n_rings) ? kFeatMisc : 0u) | ((d.n_xforms || d.n_lists) ? kFeatMovers : 0u) |
+                              ((d.n_boxes || d.n_media) ? kFeatVolumes : 0u);
+    return SceneFacts{(uint32_t)root.need, root.xdepth, v.general_boundaries, v.boxes_plain(), features};
+}
+
+// New index of every BVH node in the device copy: breadth-first from the root, through movers, lists and medium
+// boundaries. The traversal kernels keep the FIRST records of the node table in LDS (pt_wavefront.hip); numbered this
+// way those are the top levels of the BVHs — the nodes every ray goes through. (The flattener emits children before
+// parents; the order of the records means nothing to the results.)
+std::vector<uint32_t> breadth_first_nodes(const rt_scene_desc &d) {
+    std::vector<uint32_t> new_of(d.n_nodes, 0xFFFFFFFFu), queue;
+    std::vector<char> seen_x(d.n_xforms, 0), seen_l(d.n_lists, 0), seen_m(d.n_media, 0);
+    uint32_t next = 0;
+    queue.push_back(d.root);
+    for (size_t h = 0; h < queue.size(); h++) {
+        const uint32_t ref = queue[h], kind = RT_REF_KIND(ref), idx = RT_REF_INDEX(ref);
+        if (kind == RT_KIND_NODE) {
+            if (new_of[idx] != 0xFFFFFFFFu) continue;
+            new_of[idx] = next++;
+            queue.push_back(d.nodes[idx].left);
+            if (d.nodes[idx].right != d.nodes[idx].left) queue.push_back(d.nodes[idx].right);
+        } else if (kind >= RT_KIND_TRANSLATE && kind <= RT_KIND_ZOOM) {
+            if (!seen_x[idx]) { seen_x[idx] = 1; queue.push_back(d.xforms[idx].child); }
+        } else if (kind == RT_KIND_LIST) {
+            if (!seen_l[idx]) { seen_l[idx] = 1; for (uint32_t i = 0; i < d.lists[idx].count; i++) queue.push_back(d.list_items[d.lists[idx].first + i]); }
+        } else if (kind == RT_KIND_MEDIUM) {
+            if (!seen_m[idx]) { seen_m[idx] = 1; queue.push_back(d.media[idx].boundary); }
+        }
+    }
+    for (uint32_t i = 0; i < d.n_nodes; i++)
+        if (new_of[i] == 0xFFFFFFFFu) new_of[i] = next++;            // (unreachable nodes keep a place behind the others)
+    return new_of;
+}
+
+} // namespace rt2022

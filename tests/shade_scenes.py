@@ -20,7 +20,7 @@ ALL = slice(None)
 LAMB, METAL, DIEL, LIGHT, ISO = (F.RT_MAT_LAMBERTIAN, F.RT_MAT_METAL, F.RT_MAT_DIELECTRIC, F.RT_MAT_DIFFUSE_LIGHT, F.RT_MAT_ISOTROPIC)
 SOLID, CHECKER, NOISE, IMAGE, NONE = F.RT_TEX_SOLID, F.RT_TEX_CHECKER, F.RT_TEX_NOISE, F.RT_TEX_IMAGE, O.TEX_NONE
 SKY = (0.55, 0.65, 0.85)
-CHECKER_DEPTH = 8                                           # pt_device.h: kCheckerDepth, the deepest chain rt_scene_create accepts
+CHECKER_DEPTH = 8                                           # csrc/host/rt_constants.hpp: kCheckerDepth, the deepest chain rt_scene_create accepts
 
 
 class Case:

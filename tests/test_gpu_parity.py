@@ -813,6 +813,45 @@ def test_a_rejected_row_id_leaves_the_stream_working(rt, call):
     assert np.array_equal(bits(d_out.cpu().numpy()), bits(host))
 
 
+@pytest.mark.parametrize("form", ["rows", "pixels"])
+def test_device_id_check_reaches_every_entry_of_a_long_list(rt, form):
+    """The device-side id check on a list longer than its grid: 65 536 + 65 entries are one grid-stride round of its 256
+    blocks of 256 threads, then a tail of one full wave and one lane. A single bad id — one past the limit — is found as the
+    last entry (the tail's lone lane) and as the first, and the list without it is accepted."""
+    import torch
+    W, H, n = 2, 8, 65536 + 65
+    s = rt.HostScene("two_spheres")
+    cam, bg = s.default_view(W / H)
+    dev = rt.DeviceScene(s.desc)
+    p = rt.make_params(W, H, 1, 1, bg)
+    stream = torch.cuda.Stream()
+    if form == "rows":
+        limit, dtype, message = H, np.uint32, "row id out of range"
+        d_out = torch.zeros((n, W, 3), dtype=torch.float64, device="cuda")
+        run = lambda d_ids: dev.render_device(cam, p, d_ids.data_ptr(), n, d_out.data_ptr(), stream.cuda_stream)
+    else:
+        limit, dtype, message = W * H, np.uint64, "pixel id out of range"
+        d_out = torch.zeros((n, 3), dtype=torch.float64, device="cuda")
+        run = lambda d_ids: dev.render_pixels_device(cam, p, d_ids.data_ptr(), n, d_out.data_ptr(), stream.cuda_stream, None)
+    good = (np.arange(n) % limit).astype(dtype)
+    signed = np.int32 if form == "rows" else np.int64
+    for where in (n - 1, 0):
+        ids = good.copy()
+        ids[where] = limit
+        d_ids = torch.from_numpy(ids.view(signed)).cuda()
+        torch.cuda.synchronize()
+        with pytest.raises(rt.RtError) as e:
+            run(d_ids)
+        assert e.value.code == F.RT_ERR_INVALID and message in str(e.value), where
+    d_ids = torch.from_numpy(good.view(signed)).cuda()
+    torch.cuda.synchronize()
+    run(d_ids)
+    if form == "rows":
+        dev.wait(stream.cuda_stream)
+    stream.synchronize()
+    assert torch.isfinite(d_out).all()
+
+
 @pytest.mark.parametrize("scene,W,H,param,assets", [
     ("random_scene", 1200, 800, 0, False),        # BASELINE config 2
     ("cornell_box", 600, 600, 0, False),          # BASELINE config 4

@@ -83,7 +83,7 @@ def feature_word(d):
 
 
 def stack_need(d):
-    """Validator::need (rt_api.hip): the stack entries a traversal of the scene needs."""
+    """Validator::need (csrc/host/scene_check.cpp): the stack entries a traversal of the scene needs."""
     memo = {}
 
     def need(ref):

@@ -50,7 +50,8 @@ def main():
     only = [a[7:] for a in sys.argv[1:] if a.startswith("--only=")]       # e.g. --only=pt_wavefront.hip
     rows = []
     with tempfile.TemporaryDirectory() as tmp:
-        for src in ("pt_wavefront.hip", "pt_kernel.hip", "pt_query.hip", "pt_features.hip", "pt_denoise.hip", "pt_adaptive.hip", "rt_api.hip"):
+        for src in ("pt_wavefront.hip", "pt_kernel.hip", "pt_query.hip", "pt_features.hip", "pt_denoise.hip", "pt_adaptive.hip",
+                    "rt_scene.hip", "rt_render.hip", "rt_query.hip", "rt_post.hip", "rt_debug.hip"):
             if only and src not in only:
                 continue
             p = subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + extra + ["-c", os.path.join(CSRC, "hip", src), "-o", os.path.join(tmp, src + ".o")],
