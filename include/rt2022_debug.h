@@ -20,7 +20,9 @@ int rt_debug_rng_device(uint64_t state, int mode, double lo, double hi, uint64_t
  * in csrc/hip/pt_device.h):
  *   0-7   lanes that must want a BVH-node step before the wave takes the node fast path without a
  *         vote (1..64);
- *   8-15  accepted and ignored (two sphere tests per turn and a tail factor of 2 are built in);
+ *   8-14  accepted and ignored (two sphere tests per turn and a tail factor of 2 are built in);
+ *   15    the timed wavefront traversal visits every node's children in the reference's order, left then right, instead of
+ *         the nearer one first where the scene allows that (rt_debug_trace_variant says whether it does; A/B runs, parity tests);
  *   16-19 pool size of the wavefront engine: segments of 4096 path slots per resident traversal
  *         workgroup (1..8, default 8);
  *   20-23 s: every segment's ray list is ordered longest-first by (expected node steps) >> s, 0 = slot order;
@@ -71,7 +73,10 @@ int rt_debug_scene_info(const rt_scene *scene, uint32_t *stack_need, int32_t *gr
  * entries per lane, how many of the scene's node records the workgroup keeps in LDS (0: the plain kernels, every
  * node fetched through L1 / L2), and in *spheres_in_lds two flags: bit 0 — its Sphere / MovingSphere pools are there too (small
  * sphere-only scenes); bit 1 — it tests node boxes in single precision, with the double-precision test wherever the two could
- * differ (sphere scenes: 44-byte records in LDS, or 32-byte records from HBM / L2 and a partial LDS table). */
+ * differ (sphere scenes: 44-byte records in LDS, or 32-byte records from HBM / L2 and a partial LDS table);
+ * bit 2 — it visits the nearer child of a BVH node first where the result cannot change (off under tuning bit 15
+ * and for a scene whose nodes or primitives are shared between paths); bit 3 — the counting instance (RT_FLAG_COUNTERS) does:
+ * never, its node and primitive counts are those of the reference's order. */
 int rt_debug_trace_variant(const rt_scene *scene, uint32_t *workgroup_threads, uint32_t *stack_entries, uint32_t *nodes_in_lds,
                            uint32_t *spheres_in_lds);
 /* The single-precision slab test of the traversal kernel for sphere-only scenes: out[3] = which instances

@@ -68,6 +68,16 @@ struct SceneDev {
     uint32_t n_xforms, n_media;        // records in `xforms`, `media_dev`
     uint32_t n_spheres, n_moving_spheres;
     uint32_t n_rects;                  // (0 with FEAT 0: every primitive is a sphere — the scenes that take the single-precision slab test)
+    // Child order of the timed wavefront traversal (host/scene_check.hpp: child_order; wf_trace). A node ref
+    // READ BY THOSE KERNELS carries its node's order in bits 24..26 (0: the reference's order): the last two words of a node
+    // record — {push ref, left} so tagged, beside the plain {left, right} every other kernel reads — nodes32, and these copies
+    // of the root ref, the list items and the mover records. node_index_mask takes the index out of such a ref (24 bits, or
+    // all 27 where nothing is tagged). prim_rank: the tie rule's table (null: no rule), ranks of kind k's pool from word [k] on.
+    const uint32_t *list_items_ord;
+    const rt_xform *xforms_ord;
+    const uint32_t *prim_rank;
+    uint32_t root_ord;
+    uint32_t node_index_mask;
 };
 
 // Counter block in HBM (same order as rt_stats' integer fields).
@@ -183,8 +193,10 @@ struct WfPool {
 // speed only, never results. This is the one description of its fields; every reader goes through these accessors.
 //   0-7    quorum: lanes that must want a BVH-node step before the wave takes the node fast path without a vote (1..64; the
 //          one field the megakernel and nothing else of the word reads)
-//   8-15   accepted and ignored: extra sphere tests per turn (8-11) and the tail factor (12-15) went with the build switches
+//   8-14   accepted and ignored: extra sphere tests per turn (8-11) and the tail factor (12-14) went with the build switches
 //          that read them (two sphere tests per turn and a tail factor of 2 are built in); callers still pass 1 and 2 here
+//   15     kRefOrder: the timed wavefront traversal visits a node's children in the reference's order, left then right, whatever
+//          the node's order bits say (A/B runs, bit-parity tests)
 //   16-19  segments: pool size of the wavefront engine, segments of kSlotsPerBlock path slots per resident traversal workgroup (1..8)
 //   20-23  class_shift s: every segment's ray list is ordered longest-first by (expected node steps) >> s, 0 = slot order
 //   24-27  groups the pool is cut into, each alternating its passes on a stream of its own (1..kMaxGroups; 0: the library's choice)
@@ -195,6 +207,8 @@ struct WfPool {
 //          (for_kernels), whatever the caller passed
 namespace tune {
 constexpr uint32_t kSegmentsShift = 16, kClassShift = 20, kGroupsShift = 24;
+constexpr uint32_t kRefOrder = 1u << 15;
+constexpr bool ref_order(uint32_t word) { return (word & kRefOrder) != 0; }
 constexpr uint32_t kNoNodeTable = 1u << 28, kPassTiming = 1u << 29, kLiteralStep = 1u << 30, kBoxesPlain = 1u << 31;
 constexpr uint32_t quorum(uint32_t word) { return word & 0xFFu; }
 constexpr uint32_t segments(uint32_t word) { return (word >> kSegmentsShift) & 0xFu; }

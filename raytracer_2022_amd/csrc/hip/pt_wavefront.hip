@@ -865,6 +865,9 @@ struct TLane {
     //   kHasRay    the lane carries a ray
     //   kSubFound  the medium sub-query in progress has found a boundary hit
     //   kNeed64    the single-precision slab test could not decide the node step at hand: the voted node arm takes it in double precision
+    //   bits 25-30 (kOrderMask) the ray's side of the child order: bit 31 - k is set where a node of order k has its right child
+    //              nearer to this ray (k = 1 + 2 * axis + sense, host/scene_check.hpp) — flags << k then has it in the sign bit,
+    //              and a node of order 0 never does (bit 31 stays clear); set wherever inv is (t_flags)
     uint32_t flags;
 };
 
@@ -875,14 +878,31 @@ struct TStack {
     RT_DEV uint32_t pop(TLane &L) { if (L.sp > 0) { L.sp--; return col[L.sp * WG]; } return REF_EMPTY; }
 };
 
-constexpr uint32_t kPlain = 1u, kHasRay = 2u, kSubFound = 4u, kNeed64 = 8u;
+constexpr uint32_t kPlain = 1u, kHasRay = 2u, kSubFound = 4u, kNeed64 = 8u, kOrderMask = 0x7E000000u;
 RT_DEV void t_flag(TLane &L, uint32_t bit, bool on) { L.flags = on ? (L.flags | bit) : (L.flags & ~bit); asm volatile("" : "+v"(L.flags)); }
 RT_DEV bool t_finite(double x) { return (rtm::d2u(x) & 0x7FF0000000000000ull) != 0x7FF0000000000000ull; }
 // The fast node step applies (see there): every 1/d finite and non-zero, origin finite, boxes plain.
-RT_DEV void t_flags(TLane &L, bool boxes_plain) {
+// ... and the order bits (`order`: kOrderMask where the instance orders children and the tuning word lets it, else 0). Any choice is a valid one — the
+// closest hit does not depend on the order of the visits inside a subtree without media, ties go by rank (t_accept) — so a
+// zero or NaN component simply counts as pointing up its axis.
+RT_DEV void t_flags(TLane &L, bool boxes_plain, uint32_t order) {
     const bool plain = boxes_plain && t_finite(L.inv.x) && t_finite(L.inv.y) && t_finite(L.inv.z) && L.inv.x != 0.0 && L.inv.y != 0.0 &&
               L.inv.z != 0.0 && t_finite(L.cur.o.x) && t_finite(L.cur.o.y) && t_finite(L.cur.o.z);
+    uint32_t m = 0;
+    if (order) {                                                  // (kOrderMask or 0: one scalar register, known 0 where nothing is ordered)
+#pragma unroll
+        for (int i = 0; i < 3; i++) m |= (L.inv[i] < 0.0 ? 0x40000000u : 0x20000000u) >> (2 * i);
+    }
+    L.flags = (L.flags & ~kOrderMask) | (m & order);
     t_flag(L, kPlain, plain);
+}
+// A node's children as a kernel takes them from the last 16 bytes of its record {left, right, push ref, left}: the last two
+// words carry the order bits of the nodes they name (rt_scene_create) — the ordering kernels read those; the others the plain
+// left child, and the plain push ref: the right child, or "nothing" where the record's push ref says so.
+template <bool TAGGED>
+RT_DEV void t_children(const u32x4 rw, uint32_t &left, uint32_t &push) {
+    if (TAGGED) { left = rw.w; push = rw.z; }
+    else { left = rw.x; push = rw.z == REF_EMPTY ? REF_EMPTY : rw.y; }
 }
 // For a plain ray the slab test's min(t0, t1) / max(t0, t1) per axis IS the choice of bmin or bmax by the sign of 1/d (the
 // products are ordered by it: see the fast path) — made here once per direction instead of twice per axis and node step.
@@ -949,15 +969,24 @@ RT_DEV void t_slabs32g(TLane &L) {
     }
     L.e_ray = ok ? __builtin_fmaf(e, kF32RayBound, 2e-8f) : __builtin_inff();
 }
-RT_DEV void t_set_cur(TLane &L, const XRay &c, bool boxes_plain) {
+RT_DEV void t_set_cur(TLane &L, const XRay &c, bool boxes_plain, uint32_t order) {
     L.cur = c;
     L.inv = Vec3(1.0 / c.d.x, 1.0 / c.d.y, 1.0 / c.d.z);
     L.a_len = c.d.length_sqr();
-    t_flags(L, boxes_plain);
+    t_flags(L, boxes_plain, order);
 }
 RT_DEV double t_hi(const TLane &L) { return L.med_ref ? L.sub_closest : L.closest; }
-RT_DEV void t_accept(TLane &L, double t, uint32_t face, uint32_t mat_word) {
+// ORDER (the kernels that may visit a node's right child first): the reference accepts t == t_max, so among candidates of exactly
+// equal t the one it visits LAST wins. Visited in another order, the same one wins when a tie between two different primitives
+// goes to the higher rank in the reference's depth-first order (SceneDev::prim_rank; read here only, in a branch next to never taken).
+template <bool ORDER>
+RT_DEV void t_accept(const SceneDev &s, TLane &L, double t, uint32_t face, uint32_t mat_word) {
     if (L.med_ref) { L.sub_closest = t; t_flag(L, kSubFound, true); return; }
+    if (ORDER && t == L.closest && L.win_leaf != REF_EMPTY && ((L.win_leaf ^ L.top) << 1) != 0u && s.prim_rank) {
+        const uint32_t mine = s.prim_rank[s.prim_rank[RT_REF_KIND(L.top) & 7u] + RT_REF_INDEX(L.top)];
+        const uint32_t theirs = s.prim_rank[s.prim_rank[RT_REF_KIND(L.win_leaf) & 7u] + RT_REF_INDEX(L.win_leaf)];
+        if (mine < theirs) return;
+    }
     L.closest = t;
     L.win_leaf = L.top; L.win_face = face; L.win_chain = L.ctx; L.win_mat = mat_word;
 }
@@ -1115,6 +1144,10 @@ constexpr bool f32_lds(unsigned feat, bool cache, bool partial, bool prims, bool
 constexpr bool f32_hbm(unsigned feat, bool cache, bool prims, bool spheres, bool stats, bool probe) {
     return ((feat == 0 && spheres) || ((feat & kFeatMisc) && !(feat & kFeatVolumes))) && !prims && !stats && !probe && !cache;
 }
+// Which wf_trace instances may visit a node's nearer child first (kOrder): the timed ones. The counting instances
+// keep the reference's order — their node_visits and prim_tests are the oracle's, which follow it. Not the FEAT 7 ones either: they
+// are at 128 VGPRs with spills as it is, and the step's extra scalar registers cost them one more spilled VGPR (kernel_resources).
+constexpr bool trace_orders(bool stats, unsigned feat) { return !stats && (feat & 7u) != 7u; }
 // FEAT: which arms the scene can reach (kFeat* bits); the others are compiled out, which is
 // worth 20-60 VGPRs — the difference between 3 and 4-5 resident waves per SIMD.
 // SPHERES: every primitive of the scene is a sphere (sphere_only) — the scenes whose node boxes are tested in single precision
@@ -1138,6 +1171,13 @@ __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, W
     constexpr bool kF32 = f32_lds(FEAT, CACHE > 0, PARTIAL, PRIMS, SPHERES);
     constexpr bool kF32G = f32_hbm(FEAT, CACHE > 0, PRIMS, SPHERES, STATS, PROBE);
     constexpr bool kStashInv = !(kF32G && (FEAT & kFeatMovers));
+    // (kTagged: the instance reads the node refs that carry order bits — every timed one, so that a scene's upload need not know
+    // which of them will run it; kOrder: it acts on them)
+    constexpr bool kTagged = !STATS;
+    constexpr bool kOrder = trace_orders(STATS, FEAT);
+    const uint32_t order_on = kOrder && !tune::ref_order(tuning) ? kOrderMask : 0u;
+    // (a table that holds every node has at most kNodeCache of them: the mask is a literal there, no scalar register)
+    const uint32_t node_mask = !kTagged ? RT_REF_INDEX_MASK : (CACHE > 0 && !PARTIAL) ? 0x00FFFFFFu : s.node_index_mask;
     __shared__ f64x2 nc_box[CACHE > 0 && !kF32 && !kF32G ? 3 * CACHE : 1];
     __shared__ u32x2 nc_ref[CACHE > 0 && !kF32 && !kF32G ? CACHE : 1];
     __shared__ uint32_t nc32[kF32 ? kNode32Words * CACHE : 1];
@@ -1156,13 +1196,18 @@ __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, W
     const unsigned lane = tid & 63u;
     Counters<STATS> cnt;
     TStack<STACK, WG> st{stack_lds + tid};
+    // (the copies of the mover records and the list items whose node refs carry the order bits: SceneDev)
+    const rt_xform *const xforms = kTagged ? s.xforms_ord : s.xforms;
+    const uint32_t *const list_items = kTagged ? s.list_items_ord : s.list_items;
     const uint32_t n_cached = CACHE > 0 ? (s.n_nodes < (uint32_t)CACHE ? s.n_nodes : (uint32_t)CACHE) : 0u;
     if (CACHE > 0) {
         for (uint32_t i = tid; i < n_cached; i += (uint32_t)WG) {
             const f64x2 *np = reinterpret_cast<const f64x2 *>(s.nodes + i);
             f64x2 b0 = np[0], b1 = np[1], b2 = np[2];
-            const u32x4 rw = reinterpret_cast<const u32x4 *>(np)[3];          // {left, right, push ref, -}: see rt_scene_create
-            const u32x2 rr = {rw.x, rw.z};
+            const u32x4 rw = reinterpret_cast<const u32x4 *>(np)[3];          // {left, right, push ref, left}: see rt_scene_create, t_children
+            uint32_t c_left, c_push;
+            t_children<kTagged>(rw, c_left, c_push);
+            const u32x2 rr = {c_left, c_push};
             if (kF32) {
                 const float lo[3] = {(float)b0.x, (float)b0.y, (float)b1.x}, hi[3] = {(float)b1.y, (float)b2.x, (float)b2.y};
                 uint32_t *rec = nc32 + kNode32Words * i;
@@ -1187,14 +1232,14 @@ __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, W
         }
     }
     if (kLdsXforms || kLdsMedia || CACHE > 0) {
-        if (tid < 2 * kLdsXforms && tid < 2 * s.n_xforms) xf_lds[tid] = reinterpret_cast<const u32x4 *>(s.xforms)[tid];
+        if (tid < 2 * kLdsXforms && tid < 2 * s.n_xforms) xf_lds[tid] = reinterpret_cast<const u32x4 *>(xforms)[tid];
         if (tid >= 64 && tid < 64 + 4 * kLdsMedia && tid < 64 + 4 * s.n_media) md_lds[tid - 64] = reinterpret_cast<const f64x2 *>(s.media_dev)[tid - 64];
         __syncthreads();
     }
     // A mover's record {kind, child | p[0] | p[1], p[2]} from wherever it lives.
     auto xform_words = [&](uint32_t idx, u32x4 &x0, f64x2 &x1) {
         if (kLdsXforms && idx < kLdsXforms) { x0 = xf_lds[2 * idx]; x1 = reinterpret_cast<const f64x2 *>(xf_lds)[2 * idx + 1]; }
-        else { const u32x4 *xp = reinterpret_cast<const u32x4 *>(s.xforms + idx); x0 = xp[0]; x1 = reinterpret_cast<const f64x2 *>(xp)[1]; }
+        else { const u32x4 *xp = reinterpret_cast<const u32x4 *>(xforms + idx); x0 = xp[0]; x1 = reinterpret_cast<const f64x2 *>(xp)[1]; }
     };
     // ray_at_level of pt_common.hpp with the movers' records taken through xform_words.
     auto ray_at = [&](const Chain &ch, uint32_t level, XRay r) {
@@ -1311,7 +1356,7 @@ __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, W
                 //
                 // Straight-line on purpose: the node's 64 bytes and the stack entry below the top are
                 // requested together, before the arithmetic — no load waits for the outcome of the test.
-                const uint32_t nidx = RT_REF_INDEX(L.top);
+                const uint32_t nidx = L.top & node_mask;             // (kTagged: bits 24..26 of a node ref are its order)
                 const int below_sp = L.sp > 0 ? L.sp - 1 : 0;
                 double bmin[3], bmax[3];
                 uint32_t left, right, below;
@@ -1444,7 +1489,7 @@ __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, W
                     asm volatile("" : "+v"(q3), "+v"(below));         // (q3 as ONE 16-byte load — left and the push ref are not neighbours in it — and the stack read beside the fetches)
                     bmin[0] = rtm::u2d(((uint64_t)q0.y << 32) | q0.x); bmin[1] = rtm::u2d(((uint64_t)q0.w << 32) | q0.z); bmin[2] = rtm::u2d(((uint64_t)q1.y << 32) | q1.x);
                     bmax[0] = rtm::u2d(((uint64_t)q1.w << 32) | q1.z); bmax[1] = rtm::u2d(((uint64_t)q2.y << 32) | q2.x); bmax[2] = rtm::u2d(((uint64_t)q2.w << 32) | q2.z);
-                    left = q3.x; right = q3.z;                    // (the push ref: `right`, or "nothing" for a span-1 twin — rt_scene_create)
+                    t_children<kTagged>(q3, left, right);          // (the push ref: `right`, or "nothing" for a span-1 twin — rt_scene_create)
                 }
                 double tmn, tmx;
 #pragma unroll
@@ -1476,6 +1521,17 @@ __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, W
                 } else {
                 cnt.node();
                 L.steps++;
+                if (kOrder) {
+                    // The nearer child first: the node's order k is the top byte of its ref, the lane's flags hold "the
+                    // right child is nearer" for order k in bit 31 - k — one shift by that byte puts it into the sign bit.
+                    uint32_t sh;
+                    asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_3 src1_sel:DWORD" : "=v"(sh) : "v"(L.top), "v"(L.flags));
+                    // ... and the lanes that have it set exchange their two refs in ONE vector instruction, under a mask of their own
+                    // (two selects otherwise; the mask is scalar work, beside the vector pipes this loop is bound by).
+                    const unsigned long long swap = wballot((int32_t)sh < 0);
+                    unsigned long long saved;
+                    asm volatile("s_and_saveexec_b64 %2, %3\n\tv_swap_b32 %0, %1\n\ts_mov_b64 exec, %2" : "+v"(left), "+v"(right), "=&s"(saved) : "s"(swap));
+                }
                 const bool twin = right == ref_empty;
                 const bool push = hit && !twin && L.sp < STACK;
                 if (push) st.col[L.sp * WG] = right;
@@ -1521,7 +1577,7 @@ __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, W
             for (int rep = 0; rep < kNodeReps && L.op == OP_NODE; rep++) {
             cnt.node();
             L.steps++;
-            const uint32_t nidx = RT_REF_INDEX(L.top);
+            const uint32_t nidx = L.top & node_mask;
             f64x2 n0, n1, n2;
             u32x4 n3;
             bool decided = false, miss = false;
@@ -1555,7 +1611,10 @@ __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, W
             } else {
                 const f64x2 *np = reinterpret_cast<const f64x2 *>(s.nodes + nidx);
                 n0 = np[0]; n1 = np[1]; n2 = np[2];
-                n3 = reinterpret_cast<const u32x4 *>(np)[3];
+                const u32x4 rw = reinterpret_cast<const u32x4 *>(np)[3];
+                uint32_t c_left, c_push;
+                t_children<kTagged>(rw, c_left, c_push);
+                n3 = (u32x4){c_left, 0u, c_push, 0u};
             }
             t_pin(n0); t_pin(n1); t_pin(n2); t_pin(n3);
             const double bmin[3] = {n0.x, n0.y, n1.x}, bmax[3] = {n1.y, n2.x, n2.y};
@@ -1574,7 +1633,8 @@ __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, W
             }
             if (kF32 || kF32G) L.flags &= ~kNeed64;
             if (!miss) {
-                const uint32_t left = n3.x, push_ref = n3.z;           // (push ref: see the fast path)
+                uint32_t left = n3.x, push_ref = n3.z;                 // (push ref: see the fast path)
+                if (kOrder && (int32_t)(L.flags << (L.top >> 24)) < 0) { left = n3.z; push_ref = n3.x; }      // (the nearer child first: see the fast path)
                 if (push_ref == REF_EMPTY) cnt.prim(RT_REF_KIND(left));
                 else st.push(L, push_ref);
                 L.top = left;
@@ -1615,7 +1675,7 @@ __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, W
                 }
                 double t;
                 bool h = sphere_t(center, radius, L.cur, L.a_len, L.t_lo, t_hi(L), t);
-                if (h) t_accept(L, t, 0, mat_word);
+                if (h) t_accept<kOrder>(s, L, t, 0, mat_word);
                 T_NEXT();
             }
         } else if (best == OP_RECT) {
@@ -1625,7 +1685,7 @@ __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, W
             t_pin(q0); t_pin(q1); t_pin(q2);
             const uint64_t am = rtm::d2u(q2.y);
             double t;
-            if (rect_t((uint32_t)am, q0.x, q0.y, q1.x, q1.y, q2.x, L.cur, L.t_lo, t_hi(L), t)) t_accept(L, t, 0, (uint32_t)(am >> 32));
+            if (rect_t((uint32_t)am, q0.x, q0.y, q1.x, q1.y, q2.x, L.cur, L.t_lo, t_hi(L), t)) t_accept<kOrder>(s, L, t, 0, (uint32_t)(am >> 32));
             T_NEXT();
         } else if ((FEAT & kFeatVolumes) && best == OP_BOX) {
             // (like the spheres: the leaves of a box BVH come in pairs, a lane whose next entry is a box again takes it in the same turn)
@@ -1640,7 +1700,7 @@ __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, W
             double t;
             uint32_t face = 0;
             bool h = t_box(b0.x, b0.y, b1.x, b1.y, b2.x, b2.y, L.cur, L.t_lo, t_hi(L), t, face);
-            if (h) t_accept(L, t, face, mat_word);
+            if (h) t_accept<kOrder>(s, L, t, face, mat_word);
             T_NEXT();
             }
         } else if ((FEAT & kFeatVolumes) && best == OP_MEDIUM) {      // ConstantMedium::hit, constantmedium.rs:49-83
@@ -1682,7 +1742,7 @@ __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, W
                         double distance_inside_boundary = (t2 - t1) * ray_length;
                         double rnd = L.rng.gen_f64();
                         double hit_distance = m.neg_inv_density * (rtm::log_(rnd) / rtm::log_(rtm::E_));
-                        if (!(hit_distance > distance_inside_boundary)) t_accept(L, t1 + hit_distance / ray_length, 0, mat_word);   // (L.top is the medium)
+                        if (!(hit_distance > distance_inside_boundary)) t_accept<kOrder>(s, L, t1 + hit_distance / ray_length, 0, mat_word);   // (L.top is the medium)
                     }
                 }
                 T_NEXT();
@@ -1705,7 +1765,7 @@ __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, W
                         double hit_distance = m.neg_inv_density * (rtm::log_(rnd) / rtm::log_(rtm::E_));
                         if (!(hit_distance > distance_inside_boundary)) {
                             L.top = mref;                             // the medium itself is the winning leaf
-                            t_accept(L, t1 + hit_distance / ray_length, 0, m.mat);
+                            t_accept<kOrder>(s, L, t1 + hit_distance / ray_length, 0, m.mat);
                         }
                     }
                 }
@@ -1732,7 +1792,7 @@ __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, W
                 mat_word = s.rings[idx].mat;
                 h = ring_t(s.rings[idx], L.cur, L.t_lo, t_hi(L), t);
             }
-            if (h) t_accept(L, t, 0, mat_word);
+            if (h) t_accept<kOrder>(s, L, t, 0, mat_word);
             T_NEXT();
             }
         } else if ((FEAT & kFeatMovers) && best == OP_CTX) {                                  // movers in / out, HittableList expansion
@@ -1770,7 +1830,7 @@ __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, W
                     L.stash_level = 0xFFFFFFFFu;
                     L.a_len = L.cur.d.length_sqr();
                 }
-                t_flags(L, boxes_plain);
+                t_flags(L, boxes_plain, order_on);
                 if (kSlabs) t_slabs(L, table_at); if (kF32) t_slabs32(L, table_at); if (kF32G) t_slabs32g(L);
                 T_SETTLE();
             } else {
@@ -1778,7 +1838,7 @@ __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, W
                 if (kind == RT_KIND_LIST) {
                     cnt.prim(kind);
                     const rt_list &l = s.lists[idx];
-                    for (uint32_t i = l.count; i > 0; i--) st.push(L, s.list_items[l.first + i - 1]);
+                    for (uint32_t i = l.count; i > 0; i--) st.push(L, list_items[l.first + i - 1]);
                     T_NEXT();
                 } else if (L.ctx.n < RT_MAX_XFORM_DEPTH) {
                     // Entering a mover — and, in the same turn, the movers its child is wrapped in directly.
@@ -1808,7 +1868,7 @@ __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, W
                         kind = RT_REF_KIND(L.top); idx = RT_REF_INDEX(L.top);
                         if (!(kind >= RT_KIND_TRANSLATE && kind <= RT_KIND_ZOOM && L.ctx.n < RT_MAX_XFORM_DEPTH)) break;
                     }
-                    t_flags(L, boxes_plain);
+                    t_flags(L, boxes_plain, order_on);
                     if (kSlabs) t_slabs(L, table_at); if (kF32) t_slabs32(L, table_at); if (kF32G) t_slabs32g(L);
                     T_SETTLE();
                 } else {
@@ -1870,7 +1930,7 @@ __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, W
                 Ray wr = pv.load_ray(L.slot, rs);
                 L.tm = wr.tm;
                 L.rng = Rng(rs);
-                t_set_cur(L, XRay{wr.orig, wr.dir}, boxes_plain);
+                t_set_cur(L, XRay{wr.orig, wr.dir}, boxes_plain, order_on);
                 if (kSlabs) t_slabs(L, table_at); if (kF32) t_slabs32(L, table_at); if (kF32G) t_slabs32g(L);
                 if (FEAT & kFeatMovers) L.stash_level = 0xFFFFFFFFu;
                 if (kStash) {                                         // what leaving a mover goes back to (OP_CTX)
@@ -1883,7 +1943,7 @@ __global__ void __launch_bounds__(WG, trace_waves_per_simd(STACK, STATS, FEAT, W
                 L.win_leaf = REF_EMPTY; L.win_face = 0;
                 L.ctx.n = 0;
                 L.sp = 0;
-                L.top = s.root;
+                L.top = kTagged ? s.root_ord : s.root;
                 T_SETTLE();
                 t_flag(L, kHasRay, true);
             } else {
@@ -2353,7 +2413,10 @@ void trace_variant(const SceneDev &scene, uint32_t stack_need, uint32_t tuning, 
     out[0] = (uint32_t)(table ? kCacheBlock : kBlock);
     out[1] = (uint32_t)c.stack;
     out[2] = !table ? 0u : scene.n_nodes < (uint32_t)kNodeCache ? scene.n_nodes : (uint32_t)kNodeCache;
-    out[3] = (c.table == kTablePrims ? 1u : 0u) | (f32 ? 2u : 0u);
+    // (bit 2: the timed instance visits the nearer child first — it is built to, the tuning word lets it, and the scene has an order
+    // to go by; bit 3: the counting instance does — never)
+    const bool orders = trace_orders(c.stats, c.feat) && !tune::ref_order(tuning) && scene.prim_rank != nullptr;
+    out[3] = (c.table == kTablePrims ? 1u : 0u) | (f32 ? 2u : 0u) | (orders ? 4u : 0u) | (trace_orders(true, 7u) ? 8u : 0u);
 }
 
 // Diagnostic builds: what the section clocks of the traversal / shade kernels added up to over the render.

@@ -7,6 +7,9 @@
 
 using namespace rt2022;
 
+static_assert(kStackTiers[0] == kStackTiny && kStackTiers[1] == kStackSmall && kStackTiers[2] == kStackMid && kStackTiers[3] == kStackLarge,
+              "child_order (host/scene_check.cpp) bounds the ordered traversal's stack need by the capacities wf_trace is built with");
+
 namespace {
 
 template <class T>
@@ -49,6 +52,11 @@ int rt_scene_create(const rt_scene_desc *desc, rt_scene **out) {
         auto node_ref = [&](uint32_t ref) {
             return RT_REF_KIND(ref) == RT_KIND_NODE ? (ref & ~RT_REF_INDEX_MASK) | new_of[RT_REF_INDEX(ref)] : ref;
         };
+        // ... and, where the timed wavefront traversal reads them, carry the node's child order in bits 24..26 (child_order).
+        const ChildOrder ord = child_order(*desc);
+        auto node_ref_ord = [&](uint32_t ref) {
+            return RT_REF_KIND(ref) == RT_KIND_NODE ? node_ref(ref) | ((uint32_t)ord.order[RT_REF_INDEX(ref)] << kOrderShift) : ref;
+        };
         {
             std::vector<rt_bvh_node> nodes(desc->n_nodes);
             for (uint32_t i = 0; i < desc->n_nodes; i++) {
@@ -59,7 +67,9 @@ int rt_scene_create(const rt_scene_desc *desc, rt_scene **out) {
                 // node holding the same plain primitive twice (bvh/mod.rs:44-47), whose second test finds the first one's hit again
                 // (counted, not repeated). Media, movers, lists and nodes are really visited twice: they draw from the RNG or recurse.
                 const uint32_t lk = RT_REF_KIND(q.left);
-                q._pad[0] = (q.left == q.right && lk >= RT_KIND_SPHERE && lk <= RT_KIND_RING) ? (14u << RT_REF_KIND_SHIFT) : q.right;
+                // (Both last words are the timed wavefront kernels': the push ref and the left child again, node refs with their order bits.)
+                q._pad[0] = (q.left == q.right && lk >= RT_KIND_SPHERE && lk <= RT_KIND_RING) ? (14u << RT_REF_KIND_SHIFT) : node_ref_ord(desc->nodes[i].right);
+                q._pad[1] = node_ref_ord(desc->nodes[i].left);
                 nodes[new_of[i]] = q;
             }
             s.nodes = upload(nodes.data(), nodes.size(), sc->owned);
@@ -71,7 +81,7 @@ int rt_scene_create(const rt_scene_desc *desc, rt_scene **out) {
                     std::memcpy(&n32[8 * i + 2 * ax], &lo, 4);
                     std::memcpy(&n32[8 * i + 2 * ax + 1], &hi, 4);
                 }
-                n32[8 * i + 6] = q.left; n32[8 * i + 7] = q._pad[0];
+                n32[8 * i + 6] = q._pad[1]; n32[8 * i + 7] = q._pad[0];
             }
             s.nodes32 = upload(n32.data(), n32.size(), sc->owned);
         }
@@ -126,7 +136,14 @@ int rt_scene_create(const rt_scene_desc *desc, rt_scene **out) {
             std::vector<uint32_t> items(desc->list_items, desc->list_items + desc->n_list_items);
             for (uint32_t &r : items) r = node_ref(r);
             s.list_items = upload(items.data(), items.size(), sc->owned);
+            for (uint32_t i = 0; i < desc->n_xforms; i++) xforms[i].child = node_ref_ord(desc->xforms[i].child);
+            s.xforms_ord = upload(xforms.data(), xforms.size(), sc->owned);
+            for (uint32_t i = 0; i < desc->n_list_items; i++) items[i] = node_ref_ord(desc->list_items[i]);
+            s.list_items_ord = upload(items.data(), items.size(), sc->owned);
         }
+        s.root_ord = node_ref_ord(desc->root);
+        s.node_index_mask = ord.usable ? (1u << kOrderShift) - 1u : RT_REF_INDEX_MASK;
+        s.prim_rank = ord.usable ? upload(ord.rank.data(), ord.rank.size(), sc->owned) : nullptr;
         s.lists = upload(desc->lists, desc->n_lists, sc->owned);
         s.lights = upload(desc->lights, desc->n_lights, sc->owned);
         s.materials = upload(desc->materials, desc->n_materials, sc->owned);

@@ -245,4 +245,187 @@ std::vector<uint32_t> breadth_first_nodes(const rt_scene_desc &d) {
     return new_of;
 }
 
+// ---- child order of the timed wavefront traversal -----------------------------------------------------------------------
+namespace {
+
+struct OrderWalk {
+    const rt_scene_desc &d;
+    ChildOrder &out;
+    std::vector<int8_t> node_medium, xform_medium, list_medium;      // -1: not walked yet
+    std::vector<char> node_seen;
+    uint32_t next_rank = 0;
+    bool shared = false;
+    static constexpr uint32_t kNoRank = 0xFFFFFFFFu;
+    OrderWalk(const rt_scene_desc &desc, ChildOrder &o)
+        : d(desc), out(o), node_medium(desc.n_nodes, -1), xform_medium(desc.n_xforms, -1), list_medium(desc.n_lists, -1), node_seen(desc.n_nodes, 0) {}
+
+    static bool is_prim(uint32_t kind) { return kind >= RT_KIND_SPHERE && kind <= RT_KIND_RING; }
+
+    // (a) a ConstantMedium below `ref` — through nodes, lists and movers; a medium's own boundary counts as holding one.
+    bool holds_medium(uint32_t ref) {
+        const uint32_t kind = RT_REF_KIND(ref), idx = RT_REF_INDEX(ref);
+        if (kind == RT_KIND_MEDIUM) return true;
+        if (is_prim(kind)) return false;
+        int8_t &memo = kind == RT_KIND_NODE ? node_medium[idx] : kind == RT_KIND_LIST ? list_medium[idx] : xform_medium[idx];
+        if (memo >= 0) return memo != 0;
+        bool m = false;
+        if (kind == RT_KIND_NODE) {
+            m = holds_medium(d.nodes[idx].left);
+            m = holds_medium(d.nodes[idx].right) || m;
+        } else if (kind == RT_KIND_LIST) {
+            for (uint32_t i = 0; i < d.lists[idx].count; i++) m = holds_medium(d.list_items[d.lists[idx].first + i]) || m;
+        } else {
+            m = holds_medium(d.xforms[idx].child);
+        }
+        memo = m ? 1 : 0;
+        return m;
+    }
+
+    // Every node of a medium's boundary counts as holding one: the boundary queries are the medium's own.
+    void mark_boundary(uint32_t ref) {
+        const uint32_t kind = RT_REF_KIND(ref), idx = RT_REF_INDEX(ref);
+        if (kind == RT_KIND_NODE) {
+            if (out.medium[idx] == 2) return;
+            out.medium[idx] = 2;                                  // (2 while marking: a shared subtree is walked once)
+            mark_boundary(d.nodes[idx].left);
+            mark_boundary(d.nodes[idx].right);
+        } else if (kind == RT_KIND_LIST) {
+            for (uint32_t i = 0; i < d.lists[idx].count; i++) mark_boundary(d.list_items[d.lists[idx].first + i]);
+        } else if (kind >= RT_KIND_TRANSLATE && kind <= RT_KIND_ZOOM) {
+            mark_boundary(d.xforms[idx].child);
+        }
+    }
+
+    // Ranks: the reference's depth-first order of what the main query can accept — left before right, a list's items in turn.
+    // A medium is one such candidate; its boundary answers the medium's own two queries and is not walked (the final scene's
+    // subsurface ball is a world object and a boundary at once).
+    uint32_t &rank_of(uint32_t kind, uint32_t idx) { return out.rank[out.rank[kind] + idx]; }
+    void rank_walk(uint32_t ref) {
+        const uint32_t kind = RT_REF_KIND(ref), idx = RT_REF_INDEX(ref);
+        if (is_prim(kind) || kind == RT_KIND_MEDIUM) {
+            if (rank_of(kind, idx) != kNoRank) shared = true;
+            else rank_of(kind, idx) = next_rank++;
+        } else if (kind == RT_KIND_NODE) {
+            if (node_seen[idx]) { shared = true; return; }
+            node_seen[idx] = 1;
+            rank_walk(d.nodes[idx].left);
+            if (d.nodes[idx].right != d.nodes[idx].left) rank_walk(d.nodes[idx].right);       // (a span-1 twin: one primitive, one rank)
+        } else if (kind == RT_KIND_LIST) {
+            for (uint32_t i = 0; i < d.lists[idx].count; i++) rank_walk(d.list_items[d.lists[idx].first + i]);
+        } else {
+            rank_walk(d.xforms[idx].child);
+        }
+    }
+
+    // min + max of the child's box per axis — twice its centre: a node's record, or the reference's own bounding_box of the
+    // primitive (sphere.rs:68-73,167-177, aarect.rs:40-45,123-128,206-211, boxes.rs:77-79, triangle.rs:79-92, ring.rs:55-62).
+    bool centre2(uint32_t ref, double c[3]) const {
+        const uint32_t kind = RT_REF_KIND(ref), idx = RT_REF_INDEX(ref);
+        if (ref & RT_REF_FLIP) return false;
+        switch (kind) {
+            case RT_KIND_NODE:
+                for (int a = 0; a < 3; a++) c[a] = d.nodes[idx].bmin[a] + d.nodes[idx].bmax[a];
+                return true;
+            case RT_KIND_SPHERE: {
+                const rt_sphere &s = d.spheres[idx];
+                for (int a = 0; a < 3; a++) c[a] = (s.center[a] - s.radius) + (s.center[a] + s.radius);
+                return true;
+            }
+            case RT_KIND_MOVING_SPHERE: {                         // the union of its boxes at time0 and time1: center0's and center1's
+                const rt_moving_sphere &s = d.moving_spheres[idx];
+                for (int a = 0; a < 3; a++)
+                    c[a] = (std::min(s.center0[a], s.center1[a]) - s.radius) + (std::max(s.center0[a], s.center1[a]) + s.radius);
+                return true;
+            }
+            case RT_KIND_RECT: {
+                const rt_rect &r = d.rects[idx];
+                const int ia = r.axis == RT_RECT_YZ ? 1 : 0, ib = r.axis == RT_RECT_XY ? 1 : 2, ik = 3 - ia - ib;
+                c[ia] = r.a0 + r.a1; c[ib] = r.b0 + r.b1; c[ik] = (r.k - 0.0001) + (r.k + 0.0001);
+                return true;
+            }
+            case RT_KIND_BOX:
+                for (int a = 0; a < 3; a++) c[a] = d.boxes[idx].p0[a] + d.boxes[idx].p1[a];
+                return true;
+            case RT_KIND_TRIANGLE: {
+                const rt_triangle &t = d.triangles[idx];
+                for (int a = 0; a < 3; a++) c[a] = std::min(t.a[a], std::min(t.b[a], t.c[a])) + std::max(t.a[a], std::max(t.b[a], t.c[a]));
+                return true;
+            }
+            case RT_KIND_RING:                                    // a ring lies round the origin of its frame
+                c[0] = c[1] = c[2] = 0.0;
+                return true;
+            default: return false;                                // a mover, a list, a medium: keep
+        }
+    }
+    // Stack entries a traversal of `ref` needs (Validator::need's count): reference order everywhere, or — `ordered` — with
+    // either child first at the nodes that have an order: the child visited second waits on the stack, so 1 + the larger need.
+    std::vector<int32_t> need_memo[2];
+    int32_t need(uint32_t ref, bool ordered) {
+        const uint32_t kind = RT_REF_KIND(ref), idx = RT_REF_INDEX(ref);
+        if (is_prim(kind)) return 1;
+        if (kind == RT_KIND_MEDIUM) return 1 + need(d.media[idx].boundary, ordered);
+        if (kind >= RT_KIND_TRANSLATE && kind <= RT_KIND_ZOOM) return 1 + need(d.xforms[idx].child, ordered);
+        if (kind == RT_KIND_LIST) {
+            const rt_list &l = d.lists[idx];
+            int32_t n = std::max<int32_t>(1, (int32_t)l.count);
+            for (uint32_t i = 0; i < l.count; i++) n = std::max(n, (int32_t)(l.count - 1 - i) + need(d.list_items[l.first + i], ordered));
+            return n;
+        }
+        std::vector<int32_t> &memo = need_memo[ordered ? 1 : 0];
+        if (memo.empty()) memo.assign(d.n_nodes, -1);
+        if (memo[idx] >= 0) return memo[idx];
+        const int32_t l = need(d.nodes[idx].left, ordered);
+        const int32_t r = d.nodes[idx].right == d.nodes[idx].left ? l : need(d.nodes[idx].right, ordered);
+        return memo[idx] = (ordered && out.order[idx]) ? 1 + std::max(l, r) : std::max(1 + l, r);
+    }
+    uint8_t order_of(uint32_t i) const {
+        const rt_bvh_node &n = d.nodes[i];
+        if (out.medium[i] || n.left == n.right) return 0;
+        double cl[3], cr[3];
+        if (!centre2(n.left, cl) || !centre2(n.right, cr)) return 0;
+        int axis = -1;
+        double best = 0.0;
+        for (int a = 0; a < 3; a++) {
+            const double diff = cr[a] - cl[a];
+            if (!std::isfinite(diff)) return 0;
+            if (std::fabs(diff) > best) { best = std::fabs(diff); axis = a; }
+        }
+        if (axis < 0) return 0;                                   // equal centres on every axis
+        return (uint8_t)(1 + 2 * axis + (cr[axis] - cl[axis] > 0.0 ? 0 : 1));
+    }
+};
+
+} // namespace
+
+ChildOrder child_order(const rt_scene_desc &d) {
+    ChildOrder out;
+    out.order.assign(d.n_nodes, 0);
+    out.medium.assign(d.n_nodes, 0);
+    const uint64_t pools[8] = {0, d.n_spheres, d.n_moving_spheres, d.n_rects, d.n_boxes, d.n_triangles, d.n_rings, d.n_media};
+    uint64_t at = 8;
+    out.rank.assign(8, 0);
+    for (int k = 0; k < 8; k++) { out.rank[k] = (uint32_t)at; at += pools[k]; }
+    out.rank.resize(at, OrderWalk::kNoRank);
+    OrderWalk w(d, out);
+    for (uint32_t i = 0; i < d.n_nodes; i++) out.medium[i] = w.holds_medium(RT_MAKE_REF(RT_KIND_NODE, i)) ? 1 : 0;
+    for (uint32_t i = 0; i < d.n_media; i++) w.mark_boundary(d.media[i].boundary);
+    for (uint32_t i = 0; i < d.n_nodes; i++) out.medium[i] = out.medium[i] ? 1 : 0;
+    w.rank_walk(d.root);
+    out.usable = !w.shared && d.n_nodes <= (1u << kOrderShift) && at < (1ull << 32);
+    if (out.usable) {
+        for (uint32_t i = 0; i < d.n_nodes; i++) out.order[i] = w.order_of(i);
+        // The traversal stack is sized for the reference's order (check_scene: stack_need → the kernels' capacity, kStackTiers).
+        // With the right child first the LEFT one waits on the stack: where that can outgrow the capacity the scene's kernels
+        // have, only the nodes whose right subtree needs no more than their left keep their order — swapped, such a node needs
+        // max(1 + r, l) <= 1 + l, what it needs in the reference's order, so by induction the whole scene does.
+        const int32_t ref_need = w.need(d.root, false);
+        int32_t capacity = ref_need;
+        for (int t = 3; t >= 0; t--) if (ref_need <= kStackTiers[t]) capacity = kStackTiers[t];
+        if (w.need(d.root, true) > capacity)
+            for (uint32_t i = 0; i < d.n_nodes; i++)
+                if (out.order[i] && w.need(d.nodes[i].right, false) > w.need(d.nodes[i].left, false)) out.order[i] = 0;
+    }
+    return out;
+}
+
 } // namespace rt2022

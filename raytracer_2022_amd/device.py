@@ -399,6 +399,13 @@ class DeviceScene:
         return {"workgroup_threads": wg.value, "stack_entries": st.value, "nodes_in_lds": nc.value, "spheres_in_lds": bool(sp.value & 1),
                 "f32_slabs": bool(sp.value & 2)}
 
+    def child_order(self):
+        """Whether the scene's traversal visits the nearer child of a BVH node first (bits 2 and 3 of rt_debug_trace_variant's last
+        word): {"timed": the timed instance does, "counting": the counting instance does — never}."""
+        sp = C.c_uint32()
+        F.check(F.lib().rt_debug_trace_variant(self._h, None, None, None, C.byref(sp)))
+        return {"timed": bool(sp.value & 4), "counting": bool(sp.value & 8)}
+
     def set_tuning(self, node_quorum=18 | (1 << 8) | (2 << 12) | (8 << 16) | (2 << 20) | (1 << 24), vote_weights=0):
         F.check(F.lib().rt_debug_set_tuning(self._h, node_quorum, vote_weights))
 
