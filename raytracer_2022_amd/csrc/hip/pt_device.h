@@ -235,7 +235,7 @@ constexpr int kBlock = 256;
 // Vote weights of the traversal schedulers, four bits per operation label from the lowest nibble up: node, sphere, rect,
 // box, medium, misc, ctx, done (publish + refill). The wave runs the label with the largest lanes x weight.
 constexpr uint32_t kWfVoteWeights = 0x24444442u;      // wavefront engine: node and refill yield to the arms (the megakernel votes by plain counts)
-// Node-cache variant of the traversal kernel (pt_wavefront.hip): one workgroup of 1024 threads per CU, stacks of 16
+// Node-cache variant of the traversal kernel (pt_wavefront_trace.hip): one workgroup of 1024 threads per CU, stacks of 16
 // entries (64 KiB), and the first kNodeCache node records in the remaining LDS (56 bytes each: 97 440 B).
 constexpr int kCacheBlock = 1024;
 constexpr int kStackTiny = 16;

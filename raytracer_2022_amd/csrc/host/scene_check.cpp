@@ -217,7 +217,7 @@ SceneFacts check_scene(const rt_scene_desc &d) {
 }
 
 // New index of every BVH node in the device copy: breadth-first from the root, through movers, lists and medium
-// boundaries. The traversal kernels keep the FIRST records of the node table in LDS (pt_wavefront.hip); numbered this
+// boundaries. The traversal kernels keep the FIRST records of the node table in LDS (pt_wavefront_trace.hip); numbered this
 // way those are the top levels of the BVHs — the nodes every ray goes through. (The flattener emits children before
 // parents; the order of the records means nothing to the results.)
 std::vector<uint32_t> breadth_first_nodes(const rt_scene_desc &d) {

@@ -1,4 +1,4 @@
-"""Scenes built to enter one arm of the shade pass each (wf_shade: pt_wavefront.hip; the megakernel's twin of it: pt_kernel.hip):
+"""Scenes built to enter one arm of the shade pass each (wf_shade: pt_wavefront_shade.hip; the megakernel's twin of it: pt_kernel.hip):
 every material with every texture, the arms of the light list, the outcomes of Dielectric and Metal, and the ways a path's tape is
 unwound. No GPU is needed to build or to check a scene: the oracle's shade census (oracle/rt_oracle.h) says which arms its paths
 entered (tests/test_shade_scenes.py); tests/test_shade_arms.py then runs every case on the device.

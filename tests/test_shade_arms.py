@@ -1,4 +1,4 @@
-"""Every arm of the shade pass (wf_shade, pt_wavefront.hip; the megakernel's twin, pt_kernel.hip) on a scene built to enter it
+"""Every arm of the shade pass (wf_shade, pt_wavefront_shade.hip; the megakernel's twin, pt_kernel.hip) on a scene built to enter it
 (tests/shade_scenes.py), compared with the CPU oracle bit for bit — pixel sums with their NaN patterns, counters, u8 pixels. That
 the oracle's paths enter the arm a case is named for is asserted without a GPU, from its shade census
 (tests/test_shade_scenes.py); equal counters then say the device's paths took the same turns.

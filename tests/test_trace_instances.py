@@ -1,4 +1,4 @@
-"""Every traversal-kernel instance a scene can select (wf_trace: 58 instantiations, pt_wavefront.hip), run on a scene built
+"""Every traversal-kernel instance a scene can select (wf_trace: 58 instantiations, pt_wavefront_trace.hip), run on a scene built
 to select it (tests/trace_scenes.py) and compared with the CPU oracle bit for bit — pixel sums and counters. Which instance
 runs is asserted first, from a restatement of choose_trace, so a case cannot quietly test a neighbour: this code base has met
 a compiler defect that broke one instance only (tools/hipcc_slp_miscompile.md).

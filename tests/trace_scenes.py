@@ -1,4 +1,4 @@
-"""Scenes built to select one traversal-kernel instance each (wf_trace: pt_wavefront.hip, choose_trace), and the Python
+"""Scenes built to select one traversal-kernel instance each (wf_trace: pt_wavefront_trace.hip, choose_trace), and the Python
 restatements the tests compare the library's choice with. No GPU is needed to build or to check a scene: the oracle alone
 says which object kinds its rays reach (tests/test_trace_scenes.py); tests/test_trace_instances.py then runs every case on the
 device.
@@ -122,7 +122,7 @@ def mega_refuses(d):
 
 
 def expected_variant(d, need, tuning=TUNING):
-    """choose_trace and trace_variant (pt_wavefront.hip) for a timed render under the tuning word: what
+    """choose_trace and trace_variant (pt_wavefront_trace.hip) for a timed render under the tuning word: what
     DeviceScene.trace_variant() must report, and `table` — plain, whole, partial or prims — for the reader."""
     feat = feature_word(d)
     spheres = feat == 0 and d.n_rects == 0

@@ -3,7 +3,7 @@
 
     python3 tools/isa_draws.py > profiles/<tag>_isa_draws.txt
 
-Compiles pt_wavefront.hip, pt_kernel.hip and pt_features.hip to assembly with the library's flags (device side only) and lists,
+Compiles pt_wavefront_shade.hip, pt_kernel.hip and pt_features.hip to assembly with the library's flags (device side only) and lists,
 for every instance of wf_shade, pt_megakernel and pt_features, the basic blocks that hold draws of the counter-based
 generator (rt_math.h: draw i = mix64(s + i * gamma)) with their instruction counts. A draw is recognised by the mixer's middle
 step, the 64-bit `z ^ (z >> 27)` (one per mix64; the shift amount occurs nowhere else in these kernels); beside it the block's
@@ -27,7 +27,7 @@ import tempfile
 
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIP = os.path.join(HERE, "raytracer_2022_amd", "csrc", "hip")
-SOURCES = ["pt_wavefront.hip", "pt_kernel.hip", "pt_features.hip"]
+SOURCES = ["pt_wavefront_shade.hip", "pt_kernel.hip", "pt_features.hip"]
 FLAGS = ["-O3", "-std=c++17", "-ffp-contract=off", "-fno-math-errno", "--offload-arch=gfx950", "-fno-slp-vectorize", "-mllvm", "-disable-machine-licm",
          "--cuda-device-only", "-S"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -3,7 +3,7 @@
 
     python3 tools/isa_mix.py > profiles/rN_node_step_isa_mix.txt
 
-Compiles raytracer_2022_amd/csrc/hip/pt_wavefront.hip to assembly with the library's flags (device side only), finds in each
+Compiles raytracer_2022_amd/csrc/hip/pt_wavefront_trace.hip to assembly with the library's flags (device side only), finds in each
 listed wf_trace instance the innermost loop that holds the node step (the loop with the node record's LDS / global loads),
 and counts its instructions per turn = per node step of every lane that is in it:
   f64 VALU   v_*_f64 (one SIMD issue slot = a quad-cycle each)        32-bit VALU   every other v_* (two can share a slot)
@@ -19,15 +19,15 @@ import sys
 import tempfile
 
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(HERE, "raytracer_2022_amd", "csrc", "hip", "pt_wavefront.hip")
+SRC = os.path.join(HERE, "raytracer_2022_amd", "csrc", "hip", "pt_wavefront_trace.hip")
 FLAGS = ["-O3", "-std=c++17", "-ffp-contract=off", "-fno-math-errno", "--offload-arch=gfx950", "-fno-slp-vectorize", "-mllvm", "-disable-machine-licm",
          "--cuda-device-only", "-S"]
 KERNELS = [
-    ("headline (book-2 final scene): wf_trace<16,false,6,false,1024,1740,false,false>, node table in LDS", "ILi16ELb0ELj6ELb0ELi1024ELi1740ELb0ELb0EEE"),
-    ("C2 (random spheres): wf_trace<16,false,0,false,1024,600,false,true>, node table and sphere pools in LDS", "ILi16ELb0ELj0ELb0ELi1024ELi600ELb0ELb1EEE"),
-    ("C4 (Cornell box): wf_trace<16,false,0,...,1740,false,false>", "ILi16ELb0ELj0ELb0ELi1024ELi1740ELb0ELb0EEE"),
-    ("C5 (wwscene, 1.7 M nodes): wf_trace<30,false,3,false,256,0,false,false>, nodes from L1 / L2", "ILi30ELb0ELj3ELb0ELi256ELi0ELb0ELb0EEE"),
-    ("s1e6 (1 M spheres): wf_trace<22,false,0,false,256,0,false,false>, nodes from L2 / HBM", "ILi22ELb0ELj0ELb0ELi256ELi0ELb0ELb0EEE"),
+    ("headline (book-2 final scene): wf_trace<16,false,6,false,kTableWhole>, node table in LDS", "ILi16ELb0ELj6ELb0ELNS_10TraceTableE1ELb0EEE"),
+    ("C2 (random spheres): wf_trace<16,false,0,false,kTablePrims>, node table and sphere pools in LDS", "ILi16ELb0ELj0ELb0ELNS_10TraceTableE3ELb0EEE"),
+    ("C4 (Cornell box): wf_trace<16,false,0,false,kTableWhole>", "ILi16ELb0ELj0ELb0ELNS_10TraceTableE1ELb0EEE"),
+    ("C5 (wwscene, 1.7 M nodes): wf_trace<30,false,3,false,kTablePlain>, nodes from L1 / L2", "ILi30ELb0ELj3ELb0ELNS_10TraceTableE0ELb0EEE"),
+    ("s1e6 (1 M spheres): wf_trace<22,false,0,false,kTablePlain>, nodes from L2 / HBM", "ILi22ELb0ELj0ELb0ELNS_10TraceTableE0ELb0EEE"),
 ]
 
 
@@ -89,7 +89,7 @@ def main():
             sys.stderr.write(p.stderr[-2000:])
             sys.exit(1)
         text = open(out).read().split("\n")
-    print("# tools/isa_mix.py: instructions per turn of the node fast path (= per node step), from hipcc's gfx950 assembly of pt_wavefront.hip")
+    print("# tools/isa_mix.py: instructions per turn of the node fast path (= per node step), from hipcc's gfx950 assembly of pt_wavefront_trace.hip")
     print("# flags: %s" % " ".join(FLAGS[:-2]))
     for label, key in KERNELS:
         start = next((i for i, l in enumerate(text) if l.startswith("_ZN6rt20228wf_trace" + key) and l.rstrip().endswith(":") or (l.startswith("_ZN6rt20228wf_trace" + key) and ": " in l)), None)

@@ -47,10 +47,10 @@ def short(name):
 
 def main():
     extra = [a for a in sys.argv[1:] if not a.startswith("--only=")]
-    only = [a[7:] for a in sys.argv[1:] if a.startswith("--only=")]       # e.g. --only=pt_wavefront.hip
+    only = [a[7:] for a in sys.argv[1:] if a.startswith("--only=")]       # e.g. --only=pt_wavefront_trace.hip
     rows = []
     with tempfile.TemporaryDirectory() as tmp:
-        for src in ("pt_wavefront.hip", "pt_kernel.hip", "pt_query.hip", "pt_features.hip", "pt_denoise.hip", "pt_adaptive.hip",
+        for src in ("pt_wavefront.hip", "pt_wavefront_shade.hip", "pt_wavefront_trace.hip", "pt_kernel.hip", "pt_query.hip", "pt_features.hip", "pt_denoise.hip", "pt_adaptive.hip",
                     "rt_scene.hip", "rt_render.hip", "rt_query.hip", "rt_post.hip", "rt_debug.hip"):
             if only and src not in only:
                 continue
@@ -77,7 +77,7 @@ def main():
         r["name"] = short(n)
     rows.sort(key=lambda r: (r["file"], r["name"]))
     print("# hipcc -Rpass-analysis=kernel-resource-usage, flags: %s" % " ".join(FLAGS[:-1] + extra))
-    print("# wf_trace<STACK, STATS, FEAT, PROBE, WG, CACHE, PARTIAL, PRIMS>: FEAT bits 1 = triangles/rings, 2 = movers/lists, 4 = boxes/media")
+    print("# wf_trace<STACK, STATS, FEAT, PROBE, TABLE, SPHERES>: FEAT bits 1 = triangles/rings, 2 = movers/lists, 4 = boxes/media; TABLE 0 = plain, 1 = whole node table in LDS, 2 = its first records, 3 = all in LDS")
     print("%-78s %5s %5s %10s %10s %8s %7s %5s" % ("kernel", "VGPR", "SGPR", "sgpr_spill", "vgpr_spill", "scratch", "LDS", "waves"))
     for r in rows:
         print("%-78s %5d %5d %10d %10d %8d %7d %5d" % (r["name"][:78], r.get("VGPRs", -1), r.get("SGPRs", -1), r.get("sgpr_spill", -1),
