@@ -545,6 +545,35 @@ int rt_features(rt_scene *scene, const rt_camera *cam, const rt_params *params,
 int rt_features_device(rt_scene *scene, const rt_camera *cam, const rt_params *params,
                        rt_feature *d_out_features, void *hip_stream, rt_stats *stats);
 
+/* The pixel-list form: the feature records of a LIST of (frame, pixel) ids instead of whole rows — rt_render_pixels' ids,
+ *   id = frame * (width * height) + py * width + px.
+ * Record e of the output is exactly the record rt_features writes for column px of row id frame * height + py with the same
+ * rt_camera and rt_params (n_frames > frame): the same composition summed over spp samples in sample order, bit for bit,
+ * NaN where the oracle has NaN. Repeated ids are allowed and give equal records; the order and the length of the list
+ * never change an entry's record. The kernel is rt_features' own with another source of work items: one lane works one
+ * ENTRY through all its samples, and decodes the id by two 32-bit divisions where width * height * n_frames fits 32 bits,
+ * by 64-bit ones otherwise.
+ *
+ * rt_params: used — width, height, spp, background, t_min, seed, n_frames, flags; IGNORED — n_rows, row_ids, max_depth,
+ * spp_chunk, progress_cb / progress_user.
+ *
+ * Arguments: n_entries == 0 is RT_OK; spp == 0 is RT_OK and writes zeros with no feature kernel. RT_ERR_INVALID with
+ * rt_last_error() set, before any feature kernel: a null scene, cam or params; null ids or output with n_entries > 0;
+ * width, height or n_frames equal to 0 (or height * n_frames above 2^32 - 1: the matching row id must exist);
+ * cam->time0 >= cam->time1; a flag bit other than RT_FLAG_COUNTERS; device ids that are not 8-byte aligned or a device
+ * output that is not 16-byte aligned; n_entries > 2^40; an id >= width * height * n_frames — host ids are checked on the
+ * host, device ids by the counting kernel rt_render_pixels_device uses, behind one synchronisation of hip_stream BEFORE
+ * the feature kernel is enqueued: a refused call leaves the output untouched.
+ *
+ * rt_stats (may be NULL): paths = rays = n_entries * spp; with RT_FLAG_COUNTERS node_visits, prim_tests[] and rng_draws
+ * are the oracle's sums as for rt_features; ms is the device time; everything else is 0. Scratch and independence are
+ * rt_features*' own: the same per-(scene, stream) scratch, neither engine, no pool. No RT_FLAG_ASYNC, no rt_scene_set
+ * form. With stats == NULL the device form returns after the enqueue, apart from the id check's synchronisation. */
+int rt_features_pixels(rt_scene *scene, const rt_camera *cam, const rt_params *params, const uint64_t *pixel_ids, uint64_t n_entries,
+                       rt_feature *out_features, rt_stats *stats);
+int rt_features_pixels_device(rt_scene *scene, const rt_camera *cam, const rt_params *params, const uint64_t *d_pixel_ids, uint64_t n_entries,
+                              rt_feature *d_out_features, void *hip_stream, rt_stats *stats);
+
 /* ---- edge-avoiding denoiser over the feature buffers ----------------------------------------------------
  * The consumer of rt_features*: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) on albedo-demodulated
  * radiance, guided by the frame's first-hit albedo, normal and depth — the step between a render and its tone map,
@@ -758,6 +787,16 @@ int rt_render_pixels_device(rt_scene *scene, const rt_camera *cam, const rt_para
  * pure enqueue. Both take buffers that are 8-byte aligned (units 4); n_pixels == 0 is RT_OK with no launch; a null buffer
  * or n_pixels > RT_DENOISE_MAX_PIXELS is RT_ERR_INVALID.
  *
+ * Feature records go through the same accumulators, so that an adaptive frame's guides come from every sample it took:
+ * rt_adaptive_merge_features_device — E the records rt_features_pixels* wrote for a plan's entries; one lane per pixel b,
+ * for k = 0 .. units[b]-1 in order, each of the record's eight doubles f: acc_f = acc_f + E[offsets[b] + k].f. Pixels with
+ * 0 units are not written. It touches no sample count: the radiance merge's acc_n counts both.
+ * rt_adaptive_resolve_features_device — out_f = (acc_f / acc_n[b]) * (double)spp_out on all eight fields: records "of
+ * spp_out samples", which both denoisers take as they are (they divide albedo, normal and depth by the sample count and
+ * ignore hits, so every field is linear). acc_n == 0 gives NaN; d_out may alias d_acc. Both are pure enqueues; records are
+ * 16-byte aligned and moved as four 16-byte pieces, units 4-byte, offsets and acc_n 8-byte aligned; n_pixels == 0 is RT_OK
+ * with no launch; a null buffer, a misaligned buffer or n_pixels > RT_DENOISE_MAX_PIXELS is RT_ERR_INVALID.
+ *
  * Two independent halves for rt_denoise_dual need nothing more: plan twice with first_frame = f and f + max_units (the
  * units are the same), writing at d_entries and d_entries + total; render both lists in ONE rt_render_pixels_device; merge
  * each half of the sums into its own accumulator. */
@@ -779,6 +818,10 @@ int rt_adaptive_plan(const double *err, const uint32_t *row_ids, const rt_adapti
 int rt_adaptive_merge_device(const double *d_entry_sums, const uint32_t *d_units, const uint64_t *d_offsets, uint64_t n_pixels, uint32_t spp,
                              double *d_acc_sum, double *d_acc_n, void *hip_stream);
 int rt_adaptive_resolve_device(const double *d_acc_sum, const double *d_acc_n, uint64_t n_pixels, uint32_t spp_out, double *d_out, void *hip_stream);
+int rt_adaptive_merge_features_device(const rt_feature *d_entry_features, const uint32_t *d_units, const uint64_t *d_offsets,
+                                      uint64_t n_pixels, rt_feature *d_acc, void *hip_stream);
+int rt_adaptive_resolve_features_device(const rt_feature *d_acc, const double *d_acc_n, uint64_t n_pixels, uint32_t spp_out,
+                                        rt_feature *d_out, void *hip_stream);
 
 /* write_color (main.rs:280-299): NaN→0, sqrt(c/spp), clamp [0,0.999], *255.999, floor. */
 void rt_write_color(const double rgb_sum[3], int32_t spp, uint8_t out_rgb[3]);

@@ -12,6 +12,7 @@ from .host import (DescBuilder, HostScene, camera_new, fill_image, load_image, m
 from .device import (DUAL_DEFAULTS, DeviceScene, DeviceSceneSet, denoise, denoise_device, denoise_dual, denoise_dual_device,  # noqa: F401
                      denoise_dual_params, denoise_dual_workspace_bytes, denoise_params, denoise_workspace_bytes, query_rays,
                      radiance_params, radiance_rays, two_frame_rows)
+from .device import adaptive_merge_features_device, adaptive_resolve_features_device  # noqa: F401
 from .device import (ADAPTIVE_LUMA_FLOOR, adaptive_merge_device, adaptive_params, adaptive_plan, adaptive_plan_device,  # noqa: F401
                      adaptive_resolve_device, adaptive_scale, adaptive_workspace_bytes, pixel_ids, plan_units, render_adaptive)
 from ._ffi import FEATURE_DTYPE, HIT_DTYPE, QUERY_RAY_DTYPE, RADIANCE_RAY_DTYPE  # noqa: F401
@@ -22,4 +23,5 @@ __all__ = ["DescBuilder", "HostScene", "DeviceScene", "DeviceSceneSet", "camera_
            "denoise", "denoise_device", "denoise_params", "denoise_workspace_bytes", "denoise_dual", "denoise_dual_device",
            "denoise_dual_params", "denoise_dual_workspace_bytes", "two_frame_rows", "DUAL_DEFAULTS",
            "pixel_ids", "adaptive_params", "adaptive_workspace_bytes", "adaptive_plan", "adaptive_plan_device", "adaptive_merge_device",
-           "adaptive_resolve_device", "adaptive_scale", "plan_units", "render_adaptive", "ADAPTIVE_LUMA_FLOOR"]
+           "adaptive_resolve_device", "adaptive_scale", "plan_units", "render_adaptive", "ADAPTIVE_LUMA_FLOOR",
+           "adaptive_merge_features_device", "adaptive_resolve_features_device"]

@@ -17,6 +17,8 @@
 // progress, which nothing on a shared device guarantees.)
 //   ad_merge    a lane per pixel: the pixel's units of entry sums, added to its accumulator in entry order
 //   ad_resolve  a lane per pixel: accumulator -> sums of spp_out samples
+//   ad_merge_features / ad_resolve_features  the same two for rt_feature records: eight doubles a pixel, moved as four
+//               16-byte pieces, every field linear (the sample count is the radiance merge's acc_n)
 #include "pt_device.h"
 
 namespace rt2022 {
@@ -151,6 +153,38 @@ __global__ void __launch_bounds__(kAdBlock) ad_resolve(const double *acc, const 
     out[3 * b] = (c0 / d) * spp_out; out[3 * b + 1] = (c1 / d) * spp_out; out[3 * b + 2] = (c2 / d) * spp_out;
 }
 
+// A pixel's units of entry records, added field by field to its accumulated record in entry order.
+__global__ void __launch_bounds__(kAdBlock) ad_merge_features(const double2 *entries, const uint32_t *units, const uint64_t *offsets, uint64_t n,
+                                                              double2 *acc) {
+    const uint64_t b = (uint64_t)blockIdx.x * kAdBlock + threadIdx.x;
+    if (b >= n) return;
+    const uint32_t u = units[b];
+    if (!u) return;
+    const double2 *e = entries + offsets[b] * 4;
+    double2 *c = acc + b * 4;
+    double2 c0 = c[0], c1 = c[1], c2 = c[2], c3 = c[3];
+    for (uint32_t k = 0; k < u; k++) {
+        const double2 e0 = e[4 * k], e1 = e[4 * k + 1], e2 = e[4 * k + 2], e3 = e[4 * k + 3];
+        c0 = make_double2(c0.x + e0.x, c0.y + e0.y);
+        c1 = make_double2(c1.x + e1.x, c1.y + e1.y);
+        c2 = make_double2(c2.x + e2.x, c2.y + e2.y);
+        c3 = make_double2(c3.x + e3.x, c3.y + e3.y);
+    }
+    c[0] = c0; c[1] = c1; c[2] = c2; c[3] = c3;
+}
+
+// Accumulated record -> sums of spp_out samples: (acc / acc_n) * spp_out on all eight fields.
+__global__ void __launch_bounds__(kAdBlock) ad_resolve_features(const double2 *acc, const double *acc_n, uint64_t n, double spp_out, double2 *out) {
+    const uint64_t b = (uint64_t)blockIdx.x * kAdBlock + threadIdx.x;
+    if (b >= n) return;
+    const double d = acc_n[b];
+    const double2 c0 = acc[4 * b], c1 = acc[4 * b + 1], c2 = acc[4 * b + 2], c3 = acc[4 * b + 3];       // (out may be acc)
+    out[4 * b] = make_double2((c0.x / d) * spp_out, (c0.y / d) * spp_out);
+    out[4 * b + 1] = make_double2((c1.x / d) * spp_out, (c1.y / d) * spp_out);
+    out[4 * b + 2] = make_double2((c2.x / d) * spp_out, (c2.y / d) * spp_out);
+    out[4 * b + 3] = make_double2((c3.x / d) * spp_out, (c3.y / d) * spp_out);
+}
+
 } // namespace
 
 AdaptiveLayout adaptive_layout(uint32_t width, uint32_t height) {
@@ -192,6 +226,20 @@ hipError_t launch_adaptive_merge(const double *sums, const uint32_t *units, cons
 
 hipError_t launch_adaptive_resolve(const double *acc, const double *acc_n, uint64_t n, uint32_t spp_out, double *out, hipStream_t stream) {
     hipLaunchKernelGGL(ad_resolve, dim3((unsigned)((n + kAdBlock - 1) / kAdBlock)), dim3(kAdBlock), 0, stream, acc, acc_n, n, (double)spp_out, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_adaptive_merge_features(const rt_feature *entries, const uint32_t *units, const uint64_t *offsets, uint64_t n, rt_feature *acc,
+                                          hipStream_t stream) {
+    hipLaunchKernelGGL(ad_merge_features, dim3((unsigned)((n + kAdBlock - 1) / kAdBlock)), dim3(kAdBlock), 0, stream,
+                       reinterpret_cast<const double2 *>(entries), units, offsets, n, reinterpret_cast<double2 *>(acc));
+    return hipGetLastError();
+}
+
+hipError_t launch_adaptive_resolve_features(const rt_feature *acc, const double *acc_n, uint64_t n, uint32_t spp_out, rt_feature *out,
+                                            hipStream_t stream) {
+    hipLaunchKernelGGL(ad_resolve_features, dim3((unsigned)((n + kAdBlock - 1) / kAdBlock)), dim3(kAdBlock), 0, stream,
+                       reinterpret_cast<const double2 *>(acc), acc_n, n, (double)spp_out, reinterpret_cast<double2 *>(out));
     return hipGetLastError();
 }
 

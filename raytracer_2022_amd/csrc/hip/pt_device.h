@@ -258,17 +258,26 @@ hipError_t launch_query(const SceneDev &scene, const QueryArgs &args, uint32_t s
 // ---- first-hit feature buffers (pt_features.hip, rt_features*) ----------------------
 struct FeatureArgs {
     rt_camera cam;
-    uint32_t width, height, spp, n_rows;
+    uint32_t width, height, spp;
+    union {
+        uint32_t n_rows;
+        uint32_t ids32;                // pixel source: width * height * n_frames fits 32 bits, the ids are decoded by 32-bit divisions
+    };
     double background[3];
     double t_min;
     uint64_t seed;
-    uint64_t n_pixels;                 // n_rows * width
-    const uint32_t *row_ids;           // device
-    rt_feature *out;                   // device, 16-byte aligned: n_pixels records in row_ids order
+    uint64_t n_pixels;                 // n_rows * width; pixel source: the entries of the list
+    union {                            // device (a union, and ids32 one above: the row instances' kernel arguments keep their layout)
+        const uint32_t *row_ids;
+        const uint64_t *pixel_ids;     // pixel source: n_pixels ids, frame * (width * height) + py * width + px, each < width * height * n_frames
+    };
+    rt_feature *out;                   // device, 16-byte aligned: n_pixels records in row_ids order (in list order)
     unsigned long long *counter;       // pixels handed out so far (zeroed before launch)
     StatsDev *stats;                   // counter instances only
 };
 hipError_t launch_features(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, hipStream_t stream);
+// The pixel source (rt_features_pixels*): args.pixel_ids and args.ids32 in place of row_ids and n_rows.
+hipError_t launch_features_pixels(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, hipStream_t stream);
 
 // ---- edge-avoiding denoiser (pt_denoise.hip, rt_denoise*) ----------------------------
 // Where the pieces of the caller's workspace lie (byte offsets, each a multiple of 16) — the one place that knows.
@@ -353,6 +362,11 @@ hipError_t launch_adaptive_plan(const AdaptivePlanArgs &p, hipStream_t stream);
 hipError_t launch_adaptive_merge(const double *sums, const uint32_t *units, const uint64_t *offsets, uint64_t n, uint32_t spp, double *acc,
                                  double *acc_n, hipStream_t stream);
 hipError_t launch_adaptive_resolve(const double *acc, const double *acc_n, uint64_t n, uint32_t spp_out, double *out, hipStream_t stream);
+// The same two for rt_feature records (16-byte aligned): all eight fields are linear; the sample count is the radiance merge's.
+hipError_t launch_adaptive_merge_features(const rt_feature *entries, const uint32_t *units, const uint64_t *offsets, uint64_t n, rt_feature *acc,
+                                          hipStream_t stream);
+hipError_t launch_adaptive_resolve_features(const rt_feature *acc, const double *acc_n, uint64_t n, uint32_t spp_out, rt_feature *out,
+                                            hipStream_t stream);
 
 // Launchers (pt_kernel.hip). `stack_need` = entries the scene needs (host-computed).
 hipError_t launch_render(const SceneDev &scene, const RenderArgs &args, uint32_t stack_need, bool counters,

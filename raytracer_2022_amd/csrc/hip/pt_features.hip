@@ -15,6 +15,10 @@
 //   - the scheduler loop, written out here as in every kernel (pt_traverse.hpp says why) — and with it the LDS node
 //     prefix and the lane's state before the loop, pt_query's line for line: through trav_cache_nodes / trav_lane_clear
 //     the 1024-thread instance spills differently, and nobody has measured that.
+// Two sources of work items (SRC, the way wf_shade has one): the rows of a render's row list (rt_features*), or a list of
+// (frame, pixel) ids, rt_render_pixels' (rt_features_pixels*). With a list the work item is ONE ENTRY, the lane's record is
+// out + entry, and f_camera decodes pixel_ids[entry] into frame, py and px where the row source reads row_ids[row]; all else
+// — traversal, f_albedo, the record's four pieces, the claim, the scheduler loop — is the same code.
 // One lane per pixel means a few-pixel x huge-spp job balances poorly; the intended use is a whole frame at modest spp.
 // All arithmetic is f64 through rt_math.h with -ffp-contract=off, so every sum is the CPU oracle's composition bit for bit.
 #include "pt_traverse.hpp"
@@ -25,15 +29,37 @@ namespace {
 
 constexpr uint32_t kFHasPixel = 1u;    // lane flag: the lane carries a pixel (a sample of it is in flight)
 
+constexpr int kFeatRows = 0, kFeatPixels = 1;      // SRC: a row list, a list of (frame, pixel) ids
+
 struct FLane : TravLane {
-    uint32_t row, px;      // the pixel: entry of the row list, column
+    uint32_t row, px;      // the pixel: entry of the row list, column (kFeatPixels: the low and the high word of the entry's index)
     uint32_t smp;          // the sample in flight
 };
 
 // The camera ray of (row, px, sample) and the RNG behind it, as wf_shade's fresh-path code aims it (main.rs:144-149).
+template <int SRC>
 RT_DEV Ray f_camera(const FeatureArgs &a, uint32_t row, uint32_t px, uint32_t smp, Rng &rng) {
-    const uint32_t g = a.row_ids[row];
-    const uint32_t frame = g / a.height, py = g - frame * a.height;
+    uint32_t frame, py;
+    if constexpr (SRC == kFeatPixels) {
+        // id = frame * (width * height) + py * width + px. Two 32-bit divisions where every id of the view fits 32 bits (a
+        // uniform test on kernel arguments: the host checked the ids against width * height * n_frames), else 64-bit ones.
+        const uint64_t id = a.pixel_ids[(uint64_t)row | ((uint64_t)px << 32)];
+        if (a.ids32) {
+            const uint32_t i = (uint32_t)id, ip = a.width * a.height;
+            frame = i / ip;
+            const uint32_t rem = i - frame * ip;
+            py = rem / a.width;
+            px = rem - py * a.width;
+        } else {
+            const uint64_t ip = (uint64_t)a.width * a.height, f = id / ip, rem = id - f * ip, y = rem / a.width;
+            frame = (uint32_t)f;
+            py = (uint32_t)y;
+            px = (uint32_t)(rem - y * a.width);
+        }
+    } else {
+        const uint32_t g = a.row_ids[row];
+        frame = g / a.height; py = g - frame * a.height;
+    }
     rng = Rng(rtm::path_key(a.seed, frame, (uint64_t)py * a.width + px, smp));
     const double rand_u = rng.gen_f64();
     const double rand_v = rng.gen_f64();
@@ -41,9 +67,10 @@ RT_DEV Ray f_camera(const FeatureArgs &a, uint32_t row, uint32_t px, uint32_t sm
     const double v = ((double)py + rand_v) / (double)(a.height - 1);
     return get_ray(a.cam, u, v, rng);
 }
+template <int SRC>
 RT_DEV Ray f_world(const FeatureArgs &a, const FLane &L) {
     Rng unused;
-    return f_camera(a, L.row, L.px, L.smp, unused);
+    return f_camera<SRC>(a, L.row, L.px, L.smp, unused);
 }
 
 // scatter's attenuation where the material scatters, emitted where it does not (material/mod.rs).
@@ -57,16 +84,19 @@ RT_DEV Vec3 f_albedo(const SceneDev &s, const HitRec &rec) {
 }
 
 // The finished sample's features, added into the lane's own record: {a.x, a.y} {a.z, n.x} {n.y, n.z} {depth, hits}.
+template <int SRC>
 RT_DEV void f_accumulate(const SceneDev &s, const FeatureArgs &a, const FLane &L) {
     Vec3 alb = ld3(a.background), n(0.0, 0.0, 0.0);
     double depth = 0.0, hits = 0.0;
     if (L.flags & kFound) {
         HitRec rec;
-        winner_record(s, f_world(a, L), L.win, rec, true);
+        winner_record(s, f_world<SRC>(a, L), L.win, rec, true);
         alb = f_albedo(s, rec);
         n = rec.normal; depth = rec.t; hits = 1.0;
     }
-    double2 *o = reinterpret_cast<double2 *>(a.out + ((uint64_t)L.row * a.width + L.px));
+    double2 *o;
+    if constexpr (SRC == kFeatPixels) o = reinterpret_cast<double2 *>(a.out + ((uint64_t)L.row | ((uint64_t)L.px << 32)));
+    else o = reinterpret_cast<double2 *>(a.out + ((uint64_t)L.row * a.width + L.px));
     double2 s0 = make_double2(0.0, 0.0), s1 = s0, s2 = s0, s3 = s0;
     if (L.smp > 0) { s0 = o[0]; s1 = o[1]; s2 = o[2]; s3 = o[3]; }
     o[0] = make_double2(s0.x + alb.x, s0.y + alb.y);
@@ -76,21 +106,22 @@ RT_DEV void f_accumulate(const SceneDev &s, const FeatureArgs &a, const FLane &L
 }
 
 // Aim sample L.smp of the lane's pixel and start its traversal at the root (`have` false: nothing left, the lane idles).
+template <int SRC>
 RT_DEV void f_aim(const SceneDev &s, const FeatureArgs &a, FLane &L, bool have) {
     Rng rng;
     Ray r(Vec3(0.0, 0.0, 0.0), Vec3(0.0, 0.0, 0.0), 0.0);
-    if (have) r = f_camera(a, L.row, L.px, L.smp, rng);
+    if (have) r = f_camera<SRC>(a, L.row, L.px, L.smp, rng);
     trav_begin(s, L, have, XRay{r.orig, r.dir}, r.tm, a.t_min, rtm::F64_MAX, rng);   // (rng's draws so far are the camera's: the hit's come on top)
     if (have) L.flags = kFHasPixel;
 }
 
 // Done: add the finished sample into the pixel's record, then aim the pixel's next sample — or take the next pixel (one
 // atomic per wave for every lane that refills).
-template <bool STATS>
+template <int SRC, bool STATS>
 RT_DEV void f_done(const SceneDev &s, const FeatureArgs &a, FLane &L, unsigned lane, Counters<STATS> &cnt) {
     bool refill = true;
     if (L.flags & kFHasPixel) {
-        f_accumulate(s, a, L);
+        f_accumulate<SRC>(s, a, L);
         cnt.draws(L.rng.draws);
         L.smp++;
         refill = L.smp >= a.spp;
@@ -101,11 +132,16 @@ RT_DEV void f_done(const SceneDev &s, const FeatureArgs &a, FLane &L, unsigned l
         const unsigned long long i = wave_claim(a.counter, m, lane);
         have = i < a.n_pixels;
         const unsigned long long ii = have ? i : 0ull;
-        L.row = (uint32_t)(ii / a.width);
-        L.px = (uint32_t)(ii - (unsigned long long)L.row * a.width);
+        if constexpr (SRC == kFeatPixels) {
+            L.row = (uint32_t)ii;
+            L.px = (uint32_t)(ii >> 32);
+        } else {
+            L.row = (uint32_t)(ii / a.width);
+            L.px = (uint32_t)(ii - (unsigned long long)L.row * a.width);
+        }
         L.smp = 0;
     }
-    f_aim(s, a, L, have);
+    f_aim<SRC>(s, a, L, have);
 }
 
 } // namespace
@@ -115,8 +151,9 @@ RT_DEV void f_done(const SceneDev &s, const FeatureArgs &a, FLane &L, unsigned l
 // instances take 3 (168 VGPRs) where pt_query takes 4 — measured at 4 / 3 / 2 on the 800x800 default views at 4 spp: C5's
 // mesh 169 / 333 / 291 Mrays/s, 1e5 spheres 143 / 299 / 278 (profiles/features_ab_occupancy.log).
 constexpr int feat_waves(int stack, int wg) { return wg > 256 ? 4 : stack > 32 ? 2 : 3; }
-// STACK: traversal stack entries; WG: threads per workgroup; CACHE: node records kept in LDS (0: none); STATS: counter instance.
-template <int STACK, int WG, int CACHE, bool STATS>
+// STACK: traversal stack entries; WG: threads per workgroup; CACHE: node records kept in LDS (0: none); STATS: counter instance;
+// SRC: kFeatRows or kFeatPixels (last, and defaulted: the row instances keep their names).
+template <int STACK, int WG, int CACHE, bool STATS, int SRC = kFeatRows>
 __global__ void __launch_bounds__(WG, feat_waves(STACK, WG)) pt_features(const SceneDev s, const FeatureArgs a) {
     __shared__ uint32_t stack_lds[STACK * WG];
     __shared__ double node_lds[CACHE > 0 ? CACHE * kTravNodeDoubles : 1];
@@ -144,7 +181,7 @@ __global__ void __launch_bounds__(WG, feat_waves(STACK, WG)) pt_features(const S
     L.win.t = 0.0; L.win.leaf = 0; L.win.face = 0; L.win.chain = L.ctx;
     L.row = 0; L.px = 0; L.smp = 0; L.sp = 0; L.top = REF_EMPTY; L.op = OP_SHADE; L.flags = 0;
 
-    const auto world = [&] { const Ray w = f_world(a, L); return XRay{w.orig, w.dir}; };
+    const auto world = [&] { const Ray w = f_world<SRC>(a, L); return XRay{w.orig, w.dir}; };
     for (;;) {
         // Fast path: keep stepping nodes while enough lanes want to.
         for (;;) {
@@ -169,7 +206,7 @@ __global__ void __launch_bounds__(WG, feat_waves(STACK, WG)) pt_features(const S
                 case OP_MEDIUM: trav_medium<false>(s, L, st, cnt); break;
                 case OP_MISC: trav_misc<false>(s, L, st, cnt); break;
                 case OP_CTX: trav_ctx<false>(s, L, st, cnt, world); break;
-                default: f_done<STATS>(s, a, L, lane, cnt); break;
+                default: f_done<SRC, STATS>(s, a, L, lane, cnt); break;
             }
         }
     }
@@ -182,6 +219,17 @@ hipError_t launch_features(const SceneDev &scene, const FeatureArgs &args, uint3
         using S = decltype(shape);
         void (*const kernel)(SceneDev, FeatureArgs) =
             counters ? pt_features<S::stack, S::wg, S::cache, true> : pt_features<S::stack, S::wg, S::cache, false>;
+        return launch_persistent(kernel, S::wg, args.n_pixels, scene, args, stream);
+    });
+}
+
+// (behind the row instances: those keep their places in the code object)
+hipError_t launch_features_pixels(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, hipStream_t stream) {
+    if (args.n_pixels == 0 || args.spp == 0) return hipSuccess;
+    return trav_dispatch(stack_need, [&](auto shape) {
+        using S = decltype(shape);
+        void (*const kernel)(SceneDev, FeatureArgs) = counters ? pt_features<S::stack, S::wg, S::cache, true, kFeatPixels>
+                                                               : pt_features<S::stack, S::wg, S::cache, false, kFeatPixels>;
         return launch_persistent(kernel, S::wg, args.n_pixels, scene, args, stream);
     });
 }

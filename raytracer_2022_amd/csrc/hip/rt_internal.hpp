@@ -133,6 +133,7 @@ struct QueryScratch {
     DeviceBuf<StatsDev> stats{1};
     Event ev0{hipEventDefault}, ev1{hipEventDefault};
     IdCheck<uint32_t> rows;           // rt_features_device's row ids
+    IdCheck<uint64_t> pixels;         // rt_features_pixels_device's ids
 };
 
 } // namespace rt2022

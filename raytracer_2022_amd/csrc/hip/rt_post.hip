@@ -230,6 +230,35 @@ int rt_adaptive_resolve_device(const double *d_acc_sum, const double *d_acc_n, u
     });
 }
 
+int rt_adaptive_merge_features_device(const rt_feature *d_entry_features, const uint32_t *d_units, const uint64_t *d_offsets, uint64_t n_pixels,
+                                      rt_feature *d_acc, void *hip_stream) {
+    return guarded([&]() -> int {
+        const std::string w("rt_adaptive_merge_features_device");
+        RT_REQUIRE(n_pixels <= RT_DENOISE_MAX_PIXELS, RT_ERR_INVALID, w + ": n_pixels > RT_DENOISE_MAX_PIXELS");
+        if (n_pixels == 0) return RT_OK;
+        RT_REQUIRE(d_entry_features && d_units && d_offsets && d_acc, RT_ERR_INVALID, w + ": null buffer");
+        RT_REQUIRE(!(((uintptr_t)d_entry_features | (uintptr_t)d_acc) & 15u), RT_ERR_INVALID, w + ": the records must be 16-byte aligned");
+        RT_REQUIRE(!((uintptr_t)d_offsets & 7u), RT_ERR_INVALID, w + ": offsets must be 8-byte aligned");
+        RT_REQUIRE(!((uintptr_t)d_units & 3u), RT_ERR_INVALID, w + ": units must be 4-byte aligned");
+        RT_HIP(launch_adaptive_merge_features(d_entry_features, d_units, d_offsets, n_pixels, d_acc, (hipStream_t)hip_stream));
+        return RT_OK;
+    });
+}
+
+int rt_adaptive_resolve_features_device(const rt_feature *d_acc, const double *d_acc_n, uint64_t n_pixels, uint32_t spp_out, rt_feature *d_out,
+                                        void *hip_stream) {
+    return guarded([&]() -> int {
+        const std::string w("rt_adaptive_resolve_features_device");
+        RT_REQUIRE(n_pixels <= RT_DENOISE_MAX_PIXELS, RT_ERR_INVALID, w + ": n_pixels > RT_DENOISE_MAX_PIXELS");
+        if (n_pixels == 0) return RT_OK;
+        RT_REQUIRE(d_acc && d_acc_n && d_out, RT_ERR_INVALID, w + ": null buffer");
+        RT_REQUIRE(!(((uintptr_t)d_acc | (uintptr_t)d_out) & 15u), RT_ERR_INVALID, w + ": the records must be 16-byte aligned");
+        RT_REQUIRE(!((uintptr_t)d_acc_n & 7u), RT_ERR_INVALID, w + ": the sample counts must be 8-byte aligned");
+        RT_HIP(launch_adaptive_resolve_features(d_acc, d_acc_n, n_pixels, spp_out, d_out, (hipStream_t)hip_stream));
+        return RT_OK;
+    });
+}
+
 uint64_t rt_denoise_workspace_bytes(const rt_denoise_params *p) {
     return denoise_params_fault(p) ? 0 : denoise_layout(p->width, p->height).bytes;
 }

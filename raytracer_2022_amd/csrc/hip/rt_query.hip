@@ -1,4 +1,5 @@
-// rt_query.hip — the closest-hit calls on a device scene: ray queries (rt_intersect*) and first-hit feature buffers (rt_features*).
+// rt_query.hip — the closest-hit calls on a device scene: ray queries (rt_intersect*) and first-hit feature buffers (rt_features*,
+// rt_features_pixels*).
 #include "rt_internal.hpp"
 
 using namespace rt2022;
@@ -106,6 +107,64 @@ void run_features(rt_scene *sc, const rt_camera *cam, const rt_params *p, const 
     if (stats) stats->paths = stats->rays = n_pixels * p->spp;     // (one camera path, one world.hit per sample; the kernel counts neither)
 }
 
+// The arguments of rt_features_pixels* (host side only, the scene last, like check_features). `device`: ids and output are
+// rt_features_pixels_device's — the ids are range-checked on the device later.
+void check_features_pixels(const rt_scene *scene, const rt_camera *cam, const rt_params *p, const uint64_t *ids, uint64_t n_entries,
+                           const void *out, bool device, const char *who) {
+    const std::string w(who);
+    RT_REQUIRE(p, RT_ERR_INVALID, w + ": null params");
+    RT_REQUIRE(cam, RT_ERR_INVALID, w + ": null camera");
+    RT_REQUIRE(!(p->flags & ~RT_FLAG_COUNTERS), RT_ERR_INVALID, w + ": flag bits other than RT_FLAG_COUNTERS");
+    check_view(cam, p, w + ": ", " (width, height or n_frames is 0)");
+    RT_REQUIRE(n_entries == 0 || (ids && out), RT_ERR_INVALID, w + ": null id or output buffer");
+    RT_REQUIRE(n_entries <= (1ull << 40), RT_ERR_INVALID, w + ": n_entries too large");
+    if (device) {
+        RT_REQUIRE(n_entries == 0 || !((uintptr_t)ids & 7u), RT_ERR_INVALID, w + ": the id buffer must be 8-byte aligned");
+        RT_REQUIRE(n_entries == 0 || !((uintptr_t)out & 15u), RT_ERR_INVALID, w + ": the output must be 16-byte aligned");
+    } else {
+        const uint64_t limit = (uint64_t)p->width * p->height * p->n_frames;      // (check_view: height * n_frames fits 32 bits)
+        for (uint64_t i = 0; i < n_entries; i++)
+            RT_REQUIRE(ids[i] < limit, RT_ERR_INVALID, w + ": pixel id out of range (>= width * height * n_frames)");
+    }
+    RT_REQUIRE(scene, RT_ERR_INVALID, w + ": null scene");
+}
+
+// Enqueue one pixel-list feature call on `stream`, like run_features (n_entries > 0). `check_ids`: the ids came from the caller's
+// HBM — range-check them first (one synchronisation of the stream), whatever becomes of the list: a refused call has enqueued
+// nothing that writes the output.
+void run_features_pixels(rt_scene *sc, const rt_camera *cam, const rt_params *p, const uint64_t *d_ids, uint64_t n_entries, rt_feature *d_out,
+                         hipStream_t stream, rt_stats *stats, bool check_ids, const char *who) {
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    const uint64_t limit = (uint64_t)p->width * p->height * p->n_frames;
+    QueryScratch &q = scratch_for(sc, sc->fs, stream);
+    std::lock_guard<std::mutex> lock(q.mu);
+    if (check_ids) {
+        q.pixels.begin(d_ids, n_entries, limit, stream);
+        RT_HIP(hipStreamSynchronize(stream));
+        q.pixels.end(who, ": pixel id out of range (>= width * height * n_frames)");
+    }
+    if (p->spp == 0) {                                     // no sample: zeros, no kernel
+        RT_HIP(hipMemsetAsync(d_out, 0, n_entries * sizeof(rt_feature), stream));
+        if (stats) RT_HIP(hipStreamSynchronize(stream));
+        return;
+    }
+    const bool counters = stats && (p->flags & RT_FLAG_COUNTERS);
+    FeatureArgs a{};
+    a.cam = *cam;
+    a.width = p->width; a.height = p->height; a.spp = p->spp;
+    a.ids32 = limit <= 0xFFFFFFFFull ? 1u : 0u;
+    std::memcpy(a.background, p->background, sizeof a.background);
+    a.t_min = p->t_min;
+    a.seed = p->seed;
+    a.n_pixels = n_entries;
+    a.out = d_out;
+    a.counter = q.counter;
+    a.stats = counters ? q.stats.p : nullptr;
+    a.pixel_ids = d_ids;
+    run_counted(q, counters, stream, stats, [&] { return launch_features_pixels(sc->dev, a, sc->stack_need, counters, stream); });
+    if (stats) stats->paths = stats->rays = n_entries * p->spp;    // (as run_features)
+}
+
 } // namespace
 
 extern "C" {
@@ -179,6 +238,44 @@ int rt_features_device(rt_scene *scene, const rt_camera *cam, const rt_params *p
         }
         DeviceGuard guard(scene->device);
         run_features(scene, cam, params, params->row_ids, d_out_features, (hipStream_t)hip_stream, stats, true, "rt_features_device");
+        return RT_OK;
+    });
+}
+
+int rt_features_pixels(rt_scene *scene, const rt_camera *cam, const rt_params *params, const uint64_t *pixel_ids, uint64_t n_entries,
+                       rt_feature *out_features, rt_stats *stats) {
+    return guarded([&]() -> int {
+        check_features_pixels(scene, cam, params, pixel_ids, n_entries, out_features, false, "rt_features_pixels");
+        // (These early returns, here and in the device form, never read *scene: the checks above only compare the pointer with
+        // null. tests/test_features_pixels_abi.py calls them with a handle that is no scene; keep it that way.)
+        if (n_entries == 0 || params->spp == 0) {              // nothing, or zeros: nothing for the device to do
+            if (stats) std::memset(stats, 0, sizeof *stats);
+            if (n_entries) std::memset(out_features, 0, n_entries * sizeof(rt_feature));
+            return RT_OK;
+        }
+        DeviceGuard guard(scene->device);
+        DeviceBuf<uint64_t> d_ids(n_entries);                  // (after the guard: freed with the scene's device current)
+        DeviceBuf<rt_feature> d_out(n_entries);
+        RT_HIP(hipMemcpy(d_ids, pixel_ids, n_entries * sizeof(uint64_t), hipMemcpyHostToDevice));
+        // Poison the output so an unwritten record cannot pass for a result.
+        RT_HIP(hipMemset(d_out, 0xFF, n_entries * sizeof(rt_feature)));
+        run_features_pixels(scene, cam, params, d_ids, n_entries, d_out, nullptr, stats, false, "rt_features_pixels");
+        RT_HIP(hipMemcpy(out_features, d_out, n_entries * sizeof(rt_feature), hipMemcpyDeviceToHost));
+        return RT_OK;
+    });
+}
+
+int rt_features_pixels_device(rt_scene *scene, const rt_camera *cam, const rt_params *params, const uint64_t *d_pixel_ids, uint64_t n_entries,
+                              rt_feature *d_out_features, void *hip_stream, rt_stats *stats) {
+    return guarded([&]() -> int {
+        check_features_pixels(scene, cam, params, d_pixel_ids, n_entries, d_out_features, true, "rt_features_pixels_device");
+        if (n_entries == 0) {
+            if (stats) std::memset(stats, 0, sizeof *stats);
+            return RT_OK;
+        }
+        DeviceGuard guard(scene->device);
+        run_features_pixels(scene, cam, params, d_pixel_ids, n_entries, d_out_features, (hipStream_t)hip_stream, stats, true,
+                            "rt_features_pixels_device");
         return RT_OK;
     });
 }

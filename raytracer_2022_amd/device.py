@@ -273,13 +273,27 @@ def adaptive_resolve_device(d_acc_sum_ptr, d_acc_n_ptr, n_pixels, spp_out, d_out
                                                C.c_void_p(stream_ptr or 0)))
 
 
+def adaptive_merge_features_device(d_entry_features_ptr, d_units_ptr, d_offsets_ptr, n_pixels, d_acc_ptr, stream_ptr=None):
+    """rt_adaptive_merge_features_device: adds every pixel's units of entry rt_feature records (features_pixels_device's, 16-byte
+    aligned) to its accumulated record, field by field in entry order; the sample count is adaptive_merge_device's. A pure enqueue."""
+    F.check(F.lib().rt_adaptive_merge_features_device(C.c_void_p(d_entry_features_ptr), C.c_void_p(d_units_ptr), C.c_void_p(d_offsets_ptr),
+                                                      n_pixels, C.c_void_p(d_acc_ptr), C.c_void_p(stream_ptr or 0)))
+
+
+def adaptive_resolve_features_device(d_acc_ptr, d_acc_n_ptr, n_pixels, spp_out, d_out_ptr, stream_ptr=None):
+    """rt_adaptive_resolve_features_device: out = (acc / acc_n) * spp_out on all eight fields of every record, records "of
+    spp_out samples" for the denoisers (out may be acc); a pure enqueue."""
+    F.check(F.lib().rt_adaptive_resolve_features_device(C.c_void_p(d_acc_ptr), C.c_void_p(d_acc_n_ptr), n_pixels, spp_out,
+                                                        C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr or 0)))
+
+
 # The error metric of render_adaptive: the dual filter's residual variance relative to the squared luminance of the filtered
 # demodulated mean, err = variance / (luma^2 + ADAPTIVE_LUMA_FLOOR). A documented default, not a tuned one.
 ADAPTIVE_LUMA_FLOOR = 0.01
 
 
 def render_adaptive(dev, cam, params, total_spp, rounds=2, max_units=4, denoise=None, dual=None, device="cuda", profile=False,
-                    want_state=False):
+                    want_state=False, guides="initial"):
     """Adaptive sampling on torch device buffers, image order, all stages in HBM:
     an initial two-frame render (halves A and B, params.spp samples per pixel each) plus their features; then per round
     denoise_dual (variance) -> err = variance / (luma^2 + 0.01) of the filtered demodulated mean -> adaptive_scale for the
@@ -292,12 +306,20 @@ def render_adaptive(dev, cam, params, total_spp, rounds=2, max_units=4, denoise=
     profile=True adds the device ms of each round's plan calls, pixel render and merges to its dict (HIP events, a
     synchronisation each). want_state=True returns a fourth value: {"acc", "acc_n", "feat"}, the halves' accumulators (2, H, W,
     3), their sample counts (2, H, W) and the initial frames' rt_feature records (2, n, 8) — what a dual denoise of the result needs.
+    guides="initial" filters and ranks every round under the initial frames' records. guides="all" carries the records through the
+    accumulators too: each round also makes ONE features_pixels_device call over the pixel render's entries and two feature merges
+    into a (2, n, 8) accumulator that starts as the initial frames' records; at the top of each round the halves' guides are
+    resolved to sums of spp samples, and those feed the dual denoise and the metric's demodulation. The state then gains
+    "feat_acc", the accumulated records (their sample counts are "acc_n"); "feat" stays the initial frames' records.
     The result depends on params.seed and the arguments only: two calls give the same bits."""
     import torch
     W, H, spp = params.width, params.height, params.spp
     n = W * H
     if spp == 0 or total_spp < 2 * spp:
         raise ValueError("total_spp must cover the two initial frames of params.spp samples each")
+    if guides not in ("initial", "all"):
+        raise ValueError('guides must be "initial" or "all"')
+    all_guides = guides == "all"
     ptr = lambda t: t.data_ptr()
     stream = torch.cuda.current_stream().cuda_stream
     p = F.rt_params.from_buffer_copy(params)
@@ -321,9 +343,14 @@ def render_adaptive(dev, cam, params, total_spp, rounds=2, max_units=4, denoise=
     offsets = torch.empty(n + 1, dtype=torch.int64, device=device)
     ap0 = adaptive_params(W, H, 1.0, max_units)
     aws = torch.empty(adaptive_workspace_bytes(ap0), dtype=torch.uint8, device=device)
-    alb = ((feat[0, :, 0:3] + feat[1, :, 0:3]) / float(spp + spp)).reshape(H, W, 3)
-    m = torch.where(alb > dn.albedo_floor, alb, torch.full_like(alb, dn.albedo_floor)) if not (dn.flags & F.RT_DENOISE_NO_DEMODULATE) \
-        else torch.ones_like(alb)
+
+    def demodulator(g):                                                           # of two halves' records, sums of spp samples each
+        alb = ((g[0, :, 0:3] + g[1, :, 0:3]) / float(spp + spp)).reshape(H, W, 3)
+        return torch.where(alb > dn.albedo_floor, alb, torch.full_like(alb, dn.albedo_floor)) if not (dn.flags & F.RT_DENOISE_NO_DEMODULATE) \
+            else torch.ones_like(alb)
+    m = demodulator(feat)
+    feat_acc = feat.clone() if all_guides else None                               # the halves' accumulated records
+    guide = torch.empty_like(feat) if all_guides else feat                        # ... resolved to sums of spp samples
     budget = (total_spp * n - 2 * spp * n) // (2 * spp)                           # units left
 
     def timed(entry, key, call):
@@ -343,7 +370,11 @@ def render_adaptive(dev, cam, params, total_spp, rounds=2, max_units=4, denoise=
             break
         for h in range(2):
             adaptive_resolve_device(ptr(acc[h]), ptr(acc_n[h]), n, spp, ptr(halves[h]), stream_ptr=stream)
-        denoise_dual_device(ptr(halves[0]), ptr(halves[1]), ptr(feat[0]), ptr(feat[1]), dn, dq, ptr(filt), ptr(ws),
+        if all_guides:
+            for h in range(2):
+                adaptive_resolve_features_device(ptr(feat_acc[h]), ptr(acc_n[h]), n, spp, ptr(guide[h]), stream_ptr=stream)
+            m = demodulator(guide)
+        denoise_dual_device(ptr(halves[0]), ptr(halves[1]), ptr(guide[0]), ptr(guide[1]), dn, dq, ptr(filt), ptr(ws),
                             d_out_variance_ptr=ptr(var), stream_ptr=stream)
         e = filt / (m * float(spp + spp))
         luma = 0.2126 * e[..., 0] + 0.7152 * e[..., 1] + 0.0722 * e[..., 2]
@@ -366,6 +397,11 @@ def render_adaptive(dev, cam, params, total_spp, rounds=2, max_units=4, denoise=
         frame += 2 * max_units
         p.n_frames = frame
         timed(entry, "render_pixels_ms", lambda: dev.render_pixels_device(cam, p, ptr(entries), 2 * total, ptr(sums), stream_ptr=stream))
+        if all_guides:
+            efeat = torch.empty((2 * total, 8), dtype=torch.float64, device=device)
+            timed(entry, "features_pixels_ms", lambda: dev.features_pixels_device(cam, p, ptr(entries), 2 * total, ptr(efeat), stream_ptr=stream))
+            timed(entry, "merge_features_ms", lambda: [adaptive_merge_features_device(ptr(efeat[h * total:]), ptr(units), ptr(offsets), n,
+                                                                                      ptr(feat_acc[h]), stream_ptr=stream) for h in range(2)])
         timed(entry, "merge_ms", lambda: [adaptive_merge_device(ptr(sums[h * total:]), ptr(units), ptr(offsets), n, spp, ptr(acc[h]), ptr(acc_n[h]),
                                                                 stream_ptr=stream) for h in range(2)])
         budget -= total
@@ -376,7 +412,10 @@ def render_adaptive(dev, cam, params, total_spp, rounds=2, max_units=4, denoise=
     adaptive_resolve_device(ptr(both), ptr(counts), n, total_spp, ptr(out), stream_ptr=stream)
     torch.cuda.current_stream().synchronize()
     if want_state:
-        return out, counts, log, {"acc": acc, "acc_n": acc_n, "feat": feat}
+        state = {"acc": acc, "acc_n": acc_n, "feat": feat}
+        if all_guides:
+            state["feat_acc"] = feat_acc
+        return out, counts, log, state
     return out, counts, log
 
 
@@ -550,6 +589,31 @@ class DeviceScene:
         p.flags = F.RT_FLAG_COUNTERS if stats is not None else 0
         F.check(F.lib().rt_features_device(self._h, C.byref(cam), C.byref(p), C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr or 0),
                                            C.byref(stats) if stats is not None else None))
+
+    def features_pixels(self, cam, params, ids, want_stats=False):
+        """rt_features_pixels with host buffers: the feature records of a list of (frame, pixel) ids (uint64, see pixel_ids;
+        params.n_frames must exceed every frame) → (n,) array of FEATURE_DTYPE records, each the record features() gives that
+        pixel of that frame [, rt_stats]. n_rows, row_ids, max_depth, spp_chunk and progress_cb are ignored."""
+        e = np.ascontiguousarray(ids, dtype=np.uint64).ravel()
+        p = F.rt_params.from_buffer_copy(params)
+        p.n_rows, p.row_ids, p.progress_cb = 0, None, None
+        p.flags = F.RT_FLAG_COUNTERS if want_stats else 0
+        out = np.zeros(len(e), dtype=F.FEATURE_DTYPE)
+        st = F.rt_stats()
+        F.check(F.lib().rt_features_pixels(self._h, C.byref(cam), C.byref(p), e.ctypes.data if len(e) else None, len(e),
+                                           out.ctypes.data if len(e) else None, C.byref(st)))
+        return (out, st) if want_stats else out
+
+    def features_pixels_device(self, cam, params, d_ids_ptr, n_entries, d_out_ptr, stream_ptr=None, stats=None):
+        """rt_features_pixels_device: device pointers in (n_entries uint64 ids, 8-byte aligned; room for n_entries rt_feature
+        records, 16-byte aligned), enqueued on `stream_ptr` (hipStream_t as int) behind the range check of the ids (one
+        synchronisation of the stream). stats=None returns once the kernel is enqueued; an rt_stats makes the call
+        synchronise the stream and fill it, counters included."""
+        p = F.rt_params.from_buffer_copy(params)
+        p.n_rows, p.row_ids, p.progress_cb = 0, None, None
+        p.flags = F.RT_FLAG_COUNTERS if stats is not None else 0
+        F.check(F.lib().rt_features_pixels_device(self._h, C.byref(cam), C.byref(p), C.c_void_p(d_ids_ptr), n_entries, C.c_void_p(d_out_ptr),
+                                                  C.c_void_p(stream_ptr or 0), C.byref(stats) if stats is not None else None))
 
     def close(self):
         if self._h:
