@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+from query_scenes import composite_boundary_scene, every_kind_scene      # noqa: F401 (other test modules import them from here)
 from raytracer_2022_amd import _ffi as F
 
 pytestmark = pytest.mark.gpu
@@ -142,42 +143,6 @@ def check_scene(rt, O, desc, cam, n, seed, dev=None):
     assert st.paths == 0 and st.passes == 0 and st.pool_slots == 0 and st.partial_bytes == 0 and st.ms > 0
     assert np.array_equal(dev.intersect(rays).view(np.uint8), got.view(np.uint8))          # the plain kernel instance
     return got, rays
-
-
-def every_kind_scene(rt, with_medium=True):
-    """The hand-built scene of tests/test_gpu_parity.py: one of each hittable kind under a HittableList root."""
-    b = rt.DescBuilder()
-    lam = b.lambertian((0.6, 0.5, 0.4))
-    img = (np.arange(8 * 4 * 3, dtype=np.uint8).reshape(4, 8, 3) * 7) % 251
-    refs = [
-        b.sphere((0, -100, 0), 100.0, b.lambertian(tex=b.checker(b.solid((0.2, 0.3, 0.1)), b.solid((0.9, 0.9, 0.9))))),
-        b.sphere((0, 1, 0), 1.0, b.lambertian(tex=b.image(img))),
-        b.moving_sphere((2.5, 0.5, 0), (2.5, 1.0, 0), 0, 1, 0.5, b.metal((0.8, 0.7, 0.6), 0.3)),
-        b.sphere((-2.5, 1, 0), 1.0, b.dielectric(1.5)),
-        b.triangle((-1, 0.01, 2), (1, 0.01, 2), (0, 1.5, 2.5), lam),
-        b.translate(b.ring(1.5, 0.3, lam), (0, 0.5, -3)),
-        b.translate(b.rotate_y(b.zoom(b.box((-0.5, 0, -0.5), (0.5, 1, 0.5), lam), 1.5), 0.5, 0.8660254037844386), (4.5, 0, 2)),
-        b.list([b.rect(F.RT_RECT_XZ, -1, 1, -1, 1, 6.0, b.diffuse_light((8, 8, 8)), flip=True),
-                b.rect(F.RT_RECT_XY, -6, 6, 0, 4, -6.0, lam)]),
-    ]
-    if with_medium:
-        refs.append(b.medium(b.sphere((-4, 1, 2), 1.0, b.dielectric(1.5)), 0.8, b.isotropic((0.3, 0.3, 0.9))))
-    refs.append(b.sphere((5, 6, -2), 0.7, b.diffuse_light((20, 18, 15))))
-    b.set_root(b.list(refs))
-    cam = rt.camera_new((9, 4, 9), (0, 1, 0), (0, 1, 0), 35.0, 56 / 40, 0.0, 12.0, 0.0, 1.0)
-    return b, b.desc(), cam
-
-
-def composite_boundary_scene(rt):
-    """A medium whose boundary is a BVH of a box and a sphere: its two boundary queries are traversals of their own."""
-    b = rt.DescBuilder()
-    glass = b.dielectric(1.5)
-    shell = b.node((-3, -3, -8), (3, 3, -2), b.box((-2, -1, -7), (0.5, 1, -4), glass), b.sphere((1.0, 0, -5), 1.5, glass))
-    fog = b.medium(shell, 0.9, b.isotropic((0.8, 0.5, 0.3)))
-    floor_ = b.rect(F.RT_RECT_XZ, -20, 20, -20, 20, -1.5, b.lambertian((0.5, 0.5, 0.5)))
-    b.set_root(b.list([fog, floor_]))
-    cam = rt.camera_new((0, 1, 4), (0, 0, -5), (0, 1, 0), 45.0, 48 / 36, 0.0, 9.0, 0.0, 1.0)
-    return b.desc(), cam
 
 
 @pytest.mark.parametrize("name", BUILDERS)

@@ -28,7 +28,8 @@ STACK_TINY, STACK_SMALL, STACK_MID, STACK_LARGE = 16, 22, 30, 64
 NODE_CACHE, PRIM_NODES, PRIM_SPHERES, PRIM_MOVING = 1740, 600, 256, 512
 MID_NEED, LARGE_NEED = 27, 48                                                # stack needs the `mid` / `large` chains are cut to
 EPS = 1e-4
-WORLD = ((-60.0, -60.0, -60.0), (60.0, 60.0, 60.0))                          # the box of every chain link: the camera is inside it
+WORLD = ((-250.0, -250.0, -250.0), (250.0, 250.0, 250.0))                    # the box of every chain link: it holds every object (the
+                                                                             # ground spheres reach y = -200.5) and the camera
 
 # kinds each feature bit promises / the base scene holds (indices of rt_stats.prim_tests)
 BASE_KINDS = (F.RT_KIND_SPHERE, F.RT_KIND_MOVING_SPHERE, F.RT_KIND_RECT)
