@@ -716,6 +716,104 @@ int rt_denoise_dual(const double *sum_a, const double *sum_b,
                     const uint32_t *row_ids, const rt_denoise_params *p, const rt_denoise_dual_params *q,
                     double *out_rgb_sum, double *out_variance, double *ms);
 
+/* ---- temporal accumulation with reprojection for moving-camera frames ------------------------------------
+ * A caller who renders a camera path reuses the earlier frames' samples: each pixel's first-hit point is found from the
+ * frame's own feature record, projected into the previous camera, and the previous frame's accumulated radiance is
+ * gathered there by bilinear taps that pass a depth and a normal test. It sits between the feature call and the denoiser,
+ *   rt_render_device -> rt_features_device -> rt_temporal_device -> rt_denoise*_device -> rt_tonemap_device,
+ * all in HBM on one stream, needs no rt_scene and changes nothing of a render. The scene is taken to be static: the camera
+ * moves, objects do not. The mean first-hit point of a pixel comes from F.depth / F.hits alone: get_ray's direction is
+ * lower_left + s*horizontal + t*vertical - origin - offset, so a hit at ray parameter z lies at origin + z*(G - origin) +
+ * (1 - z)*offset with G the point of the focus plane, and the lens offset averages to zero over a pixel's samples.
+ *
+ * State: one rt_temporal_pixel per pixel in IMAGE order (index y * width + x, y the image row of a row id, whatever the
+ * order of the sums): the accumulated demodulated mean radiance e, the history length n, and this frame's mean first-hit
+ * depth and normal, which the NEXT frame's taps are tested against. The caller keeps two states and swaps them.
+ *
+ * Definition: IEEE + - * / on doubles in the stated order, no contraction; floor() is exact. Per pixel p = (x, y), with
+ * sp = (double)spp, S the pixel's sums, F its rt_feature record (both sums of `spp` samples) and nan0(v) = v is NaN ? 0 : v:
+ *   c_j = nan0(S_j) / sp;  a_j = F.albedo_j / sp
+ *   m_j = a_j > albedo_floor ? a_j : albedo_floor  (rt_denoise's rule; RT_TEMPORAL_NO_DEMODULATE: m_j = 1.0);  e_j = c_j / m_j
+ *   covered = F.hits > 0;  zb = covered ? F.depth / F.hits : 0;  nb_j = covered ? F.normal_j / F.hits : 0
+ * Restart: e_out = e, n_out = 1. A pixel restarts with no d_prev, when it is not covered, and wherever stated below.
+ * Otherwise, with cross(u, v) = (u1*v2 - u2*v1, u2*v0 - u0*v2, u0*v1 - u1*v0) and dot(u, v) = (u0*v0 + u1*v1) + u2*v2,
+ * o / llc / hor / ver the current camera's origin, lower_left_corner, horizontal, vertical and o' / llc' / hor' / ver' the
+ * previous camera's:
+ *   sc = ((double)x + 0.5) / (double)(width - 1);  tc = ((double)y + 0.5) / (double)(height - 1)
+ *   G_k = (llc_k + sc*hor_k) + tc*ver_k;   P_k = o_k + zb*(G_k - o_k)                    the mean first-hit point
+ *   D_k = P_k - o'_k;  r_k = o'_k - llc'_k;  c_k = -D_k                                   solve s'*hor' + t'*ver' + lam*c = r
+ *   bc = cross(ver', c);  rc = cross(r, c);  br = cross(ver', r);  det = dot(hor', bc)
+ *   s' = dot(r, bc) / det;  t' = dot(hor', rc) / det;  lam = dot(hor', br) / det
+ *   fx = s' * (double)(width - 1) - 0.5;  fy = t' * (double)(height - 1) - 0.5;  ze = 1.0 / lam
+ * ze is the ray parameter at which the previous camera's ray through (fx, fy) reaches P: what its depth records hold.
+ * History exists only if lam > 0, fx and fy are finite, -1 <= fx < (double)width and -1 <= fy < (double)height; otherwise
+ * the pixel restarts (every pixel of an image one pixel wide or high does: sc or tc is infinite). Only then are fx and fy
+ * converted to integers: x0 = floor(fx), wx = fx - x0, y0 = floor(fy), wy = fy - y0. The taps q_0 .. q_3 are (x0, y0),
+ * (x0+1, y0), (x0, y0+1), (x0+1, y0+1) with bw_0 = (1.0 - wx)*(1.0 - wy), bw_1 = wx*(1.0 - wy), bw_2 = (1.0 - wx)*wy,
+ * bw_3 = wx*wy. A tap q counts if it is inside the image, prev(q).depth > 0, |prev(q).depth - ze| <= tol_depth * ze and
+ * d <= tol_normal with d = (d0*d0 + d1*d1) + d2*d2, d_k = nb_k - prev(q).normal_k; a tolerance of +inf skips its test (a
+ * NaN then passes it). Over the counting taps in tap order, from sw = sn = se_j = 0.0:
+ *   sw = sw + bw;  se_j = se_j + bw * prev(q).e_j;  sn = sn + bw * prev(q).n
+ * If sw >= w_min:  eh_j = se_j / sw;  nh = sn / sw;  t = nh + 1.0;  n_out = t < n_max ? t : n_max;
+ *                  e_out_j = eh_j + (e_j - eh_j) / n_out;       otherwise the pixel restarts.
+ * Outputs: state_out(p) = {e_out, n_out, zb, nb}; out_j = (e_out_j * m_j) * sp at the pixel's place in the sums' order —
+ * sums of `spp` samples again, so rt_tonemap_device, rt_denoise*, rt_write_color apply as they are. Buffer contents are
+ * never validated: NaN and inf propagate as IEEE carries them. n_max = 1 makes e_out = eh + (e - eh), which is e to rounding: no history is kept.
+ *
+ * Two halves for rt_denoise_dual need nothing more: call once per half, each with that half's own sums, features and
+ * states, so that A and B stay independent estimates; then rt_denoise_dual_device on the two outputs with the current
+ * frame's features.
+ *
+ * Row order: d_rgb_sum, d_features and d_out_rgb_sum are in row_ids order under rt_denoise's rules — NULL, or `height`
+ * entries that are a permutation of [0, height), checked on the host by rt_temporal and by rt_denoise_device's row kernel
+ * behind one synchronisation of hip_stream by rt_temporal_device, before anything writes an output: a refused list leaves
+ * both outputs untouched. With NULL rows rt_temporal_device is a pure enqueue. Both states are always in image order.
+ *
+ * Buffers: d_prev == NULL means the first frame (prev_cam may then be NULL too). d_out_rgb_sum may alias d_rgb_sum.
+ * d_state_out must not overlap d_prev — the kernel gathers from d_prev — which is checked on the address ranges. The
+ * workspace (rt_temporal_workspace_bytes(p) bytes: the inverse row map, height x uint32 rounded up to 16 bytes, and 16
+ * bytes for its bad-id count) means nothing before the call and may be reused. All buffers and the workspace are 16-byte
+ * aligned, device rows 4-byte aligned. rt_temporal stages host buffers through device memory of its own on the current
+ * device's default stream and reports the device time of the kernel in *ms.
+ *
+ * RT_ERR_INVALID with rt_last_error() set, before any device call: a null params, cam, sums, features, output, state or
+ * workspace; width, height or spp equal to 0; width * height > RT_DENOISE_MAX_PIXELS; a tolerance that is <= 0 or NaN;
+ * n_max < 1, NaN or infinite; w_min outside (0, 1]; a floor that is <= 0, NaN or infinite; a flag bit other than
+ * RT_TEMPORAL_NO_DEMODULATE; a misaligned pointer; d_prev without prev_cam; overlapping states.
+ *
+ * Limits: static scenes only. A ConstantMedium's first hit has a drawn depth and the normal (1, 0, 0): pixels seen through
+ * a medium mostly fail the depth test and restart. Edge pixels whose samples straddle two surfaces have a mean depth on
+ * neither and restart. Neither state can be given as a strip of rows; there is no rt_scene_set form. */
+typedef struct rt_temporal_pixel {    /* 64 B: four 16-byte pieces */
+    double   e[3];                    /* accumulated demodulated mean radiance */
+    double   n;                       /* history length, >= 1 (a double: bilinear taps mix lengths) */
+    double   depth;                   /* this frame's mean first-hit depth F.depth / F.hits; 0 = not covered */
+    double   normal[3];               /* F.normal / F.hits; 0 when not covered */
+} rt_temporal_pixel;
+
+typedef struct rt_temporal_params {   /* 64 B */
+    uint32_t width, height, spp, flags;   /* flags: RT_TEMPORAL_NO_DEMODULATE */
+    double   tol_depth, tol_normal;   /* > 0; +inf = test off */
+    double   n_max;                   /* >= 1, finite: cap of the history length */
+    double   w_min;                   /* in (0, 1]: least valid bilinear weight that still counts as history */
+    double   albedo_floor;            /* > 0, finite: rt_denoise's rule */
+    double   _pad;
+} rt_temporal_params;
+#define RT_TEMPORAL_NO_DEMODULATE 0x1u               /* accumulate the radiance itself: m = 1 */
+
+/* Bytes of device workspace rt_temporal_device needs for p's image; 0 on invalid params. */
+uint64_t rt_temporal_workspace_bytes(const rt_temporal_params *p);
+/* Device buffers (width * height * 3 sums in and out, width * height feature records, NULL or `height` row ids, width *
+ * height state records in — or NULL — and out), enqueued on hip_stream (NULL = default stream). */
+int rt_temporal_device(const double *d_rgb_sum, const rt_feature *d_features, const uint32_t *d_row_ids,
+                       const rt_camera *cam, const rt_temporal_pixel *d_prev, const rt_camera *prev_cam,
+                       const rt_temporal_params *p, rt_temporal_pixel *d_state_out, double *d_out_rgb_sum,
+                       void *d_workspace, void *hip_stream);
+/* Host buffers; synchronous. prev, prev_cam and ms may be NULL. */
+int rt_temporal(const double *rgb_sum, const rt_feature *features, const uint32_t *row_ids,
+                const rt_camera *cam, const rt_temporal_pixel *prev, const rt_camera *prev_cam,
+                const rt_temporal_params *p, rt_temporal_pixel *state_out, double *out_rgb_sum, double *ms);
+
 /* ---- per-pixel adaptive sampling: pixel-list renders and a sample planner -------------------------------------
  * The consumer of rt_denoise_dual's variance: more samples where the frame needs them, none where it does not,
  *   render -> features -> denoise_dual -> plan -> render_pixels -> merge -> ... -> resolve,

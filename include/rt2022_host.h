@@ -70,6 +70,8 @@ int rtb_denoise_abi_sizes(uint32_t *out, uint32_t n);
 int rtb_denoise_dual_abi_sizes(uint32_t *out, uint32_t n);
 /* The same for the rt_adaptive_* structure: {rt_adaptive_params}; returns 1. */
 int rtb_adaptive_abi_sizes(uint32_t *out, uint32_t n);
+/* The same for the rt_temporal* structures: {rt_temporal_pixel, rt_temporal_params}; returns 2. */
+int rtb_temporal_abi_sizes(uint32_t *out, uint32_t n);
 
 #ifdef __cplusplus
 }

@@ -15,7 +15,8 @@ from .device import (DUAL_DEFAULTS, DeviceScene, DeviceSceneSet, denoise, denois
 from .device import adaptive_merge_features_device, adaptive_resolve_features_device  # noqa: F401
 from .device import (ADAPTIVE_LUMA_FLOOR, adaptive_merge_device, adaptive_params, adaptive_plan, adaptive_plan_device,  # noqa: F401
                      adaptive_resolve_device, adaptive_scale, adaptive_workspace_bytes, pixel_ids, plan_units, render_adaptive)
-from ._ffi import FEATURE_DTYPE, HIT_DTYPE, QUERY_RAY_DTYPE, RADIANCE_RAY_DTYPE  # noqa: F401
+from .device import TEMPORAL_DEFAULTS, temporal, temporal_device, temporal_params, temporal_workspace_bytes  # noqa: F401
+from ._ffi import FEATURE_DTYPE, HIT_DTYPE, QUERY_RAY_DTYPE, RADIANCE_RAY_DTYPE, TEMPORAL_PIXEL_DTYPE  # noqa: F401
 
 __all__ = ["DescBuilder", "HostScene", "DeviceScene", "DeviceSceneSet", "camera_new", "fill_image", "make_params", "shuffled_rows",
            "write_color", "write_jpeg", "load_image", "RtError", "lib", "make_ref", "ref_kind", "ref_index", "query_rays",
@@ -24,4 +25,5 @@ __all__ = ["DescBuilder", "HostScene", "DeviceScene", "DeviceSceneSet", "camera_
            "denoise_dual_params", "denoise_dual_workspace_bytes", "two_frame_rows", "DUAL_DEFAULTS",
            "pixel_ids", "adaptive_params", "adaptive_workspace_bytes", "adaptive_plan", "adaptive_plan_device", "adaptive_merge_device",
            "adaptive_resolve_device", "adaptive_scale", "plan_units", "render_adaptive", "ADAPTIVE_LUMA_FLOOR",
-           "adaptive_merge_features_device", "adaptive_resolve_features_device"]
+           "adaptive_merge_features_device", "adaptive_resolve_features_device",
+           "temporal", "temporal_device", "temporal_params", "temporal_workspace_bytes", "TEMPORAL_DEFAULTS", "TEMPORAL_PIXEL_DTYPE"]

@@ -223,6 +223,23 @@ RT_DENOISE_MAX_VAR_ITER = 8
 # The rt_denoise_dual* structure, in the order of rtb_denoise_dual_abi_sizes.
 DENOISE_DUAL_ABI_STRUCTS = [rt_denoise_dual_params]
 
+
+class rt_temporal_pixel(C.Structure):
+    _fields_ = [("e", d3), ("n", C.c_double), ("depth", C.c_double), ("normal", d3)]
+
+
+class rt_temporal_params(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("spp", C.c_uint32), ("flags", C.c_uint32),
+                ("tol_depth", C.c_double), ("tol_normal", C.c_double), ("n_max", C.c_double), ("w_min", C.c_double),
+                ("albedo_floor", C.c_double), ("_pad", C.c_double)]
+
+
+RT_TEMPORAL_NO_DEMODULATE = 0x1
+# numpy twin of rt_temporal_pixel (arrays of it are the states of rt_temporal as they are)
+TEMPORAL_PIXEL_DTYPE = np.dtype([("e", "<f8", (3,)), ("n", "<f8"), ("depth", "<f8"), ("normal", "<f8", (3,))])
+# The rt_temporal* structures, in the order of rtb_temporal_abi_sizes.
+TEMPORAL_ABI_STRUCTS = [rt_temporal_pixel, rt_temporal_params]
+
 class rt_adaptive_params(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("first_frame", C.c_uint32), ("max_units", C.c_uint32),
                 ("scale", C.c_double), ("flags", C.c_uint32), ("_pad", C.c_uint32)]
@@ -252,6 +269,7 @@ ABI_SYMBOLS = [
     "rtb_shuffled_rows", "rtb_bvh_build", "rtb_fill_image", "rtb_write_ppm", "rtb_write_jpeg", "rtb_image_load",
     "rtb_last_error", "rtb_abi_sizes", "rtb_radiance_abi_sizes", "rtb_features_abi_sizes", "rtb_denoise_abi_sizes",
     "rtb_denoise_dual_abi_sizes",
+    "rt_temporal_workspace_bytes", "rt_temporal", "rt_temporal_device", "rtb_temporal_abi_sizes",
     "rt_debug_math_device", "rt_debug_rng_device", "rt_debug_scene_info", "rt_debug_trace_variant", "rt_debug_set_tuning", "rt_debug_set_engine", "rt_debug_census", "rt_debug_pass_timing", "rt_debug_traffic_probe", "rt_debug_valu_probe", "rt_debug_set_partial_ring", "rt_debug_f32_slabs",
 ]
 
@@ -297,6 +315,11 @@ def lib():
     L.rt_denoise_dual_workspace_bytes.restype = u64
     L.rt_denoise_dual.argtypes = [vp, vp, vp, vp, vp, P(rt_denoise_params), P(rt_denoise_dual_params), vp, vp, P(dbl)]
     L.rt_denoise_dual_device.argtypes = [vp, vp, vp, vp, vp, P(rt_denoise_params), P(rt_denoise_dual_params), vp, vp, vp, vp]
+    L.rt_temporal_workspace_bytes.argtypes = [P(rt_temporal_params)]
+    L.rt_temporal_workspace_bytes.restype = u64
+    L.rt_temporal.argtypes = [vp, vp, vp, P(rt_camera), vp, P(rt_camera), P(rt_temporal_params), vp, vp, P(dbl)]
+    L.rt_temporal_device.argtypes = [vp, vp, vp, P(rt_camera), vp, P(rt_camera), P(rt_temporal_params), vp, vp, vp, vp]
+    L.rtb_temporal_abi_sizes.argtypes = [P(u32), u32]
     L.rt_render_pixels.argtypes = [vp, P(rt_camera), P(rt_params), vp, u64, vp, P(rt_stats)]
     L.rt_render_pixels_device.argtypes = [vp, P(rt_camera), P(rt_params), vp, u64, vp, vp, P(rt_stats)]
     L.rt_adaptive_workspace_bytes.argtypes = [P(rt_adaptive_params)]

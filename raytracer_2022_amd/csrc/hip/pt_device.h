@@ -336,6 +336,26 @@ hipError_t launch_denoise_dual(const DenoiseDualArgs &a, uint32_t var_iter, uint
 // The denoisers' row kernel (dn_rows) on a list of `height` ids: inv[image row] = buffer row, *bad = ids out of range or repeated.
 hipError_t launch_row_list_check(const uint32_t *rows, uint32_t height, uint32_t *inv, uint32_t *bad, hipStream_t stream);
 
+// ---- temporal accumulation with reprojection (pt_temporal.hip, rt_temporal*) ------------------------------
+// One kernel, one lane per pixel; the workspace holds nothing but the row kernel's map (host/temporal_check.hpp).
+struct TemporalArgs {
+    uint32_t width, height;
+    double sp;                         // (double)spp
+    double wm1, hm1;                   // (double)(width - 1), (double)(height - 1)
+    double wd, hd;                     // (double)width, (double)height
+    double tol_depth, tol_normal, n_max, w_min, albedo_floor;
+    bool demodulate, depth_test, normal_test;      // (a tolerance of +inf switches its test off)
+    double o[3], llc[3], hor[3], ver[3];           // the current camera
+    double po[3], pr[3], phor[3], pver[3];         // the previous camera: origin, origin - lower_left_corner, horizontal, vertical
+    const double *sum;                 // device: the render's sums, buffer order
+    const rt_feature *feat;            // device, 16-byte aligned, buffer order
+    const uint32_t *inv;               // device: image row -> buffer row (null: the identity)
+    const rt_temporal_pixel *prev;     // device, image order (null: the first frame)
+    rt_temporal_pixel *state;          // device, image order; never overlaps prev
+    double *out;                       // device: the accumulated sums, buffer order (may be `sum`)
+};
+hipError_t launch_temporal(const TemporalArgs &a, hipStream_t stream);
+
 // ---- adaptive sampling: planner, merge, resolve (pt_adaptive.hip, rt_adaptive_*) -----------------------
 // The planner's workspace (byte offsets, each a multiple of 16).
 struct AdaptiveLayout {

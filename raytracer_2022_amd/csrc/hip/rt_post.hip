@@ -1,7 +1,8 @@
-// rt_post.hip — what works on a render's buffers and takes no scene: the denoisers (rt_denoise*, rt_denoise_dual*) and the
-// adaptive-sampling planner, merge and resolve (rt_adaptive_*).
+// rt_post.hip — what works on a render's buffers and takes no scene: the denoisers (rt_denoise*, rt_denoise_dual*), the
+// temporal accumulation (rt_temporal*) and the adaptive-sampling planner, merge and resolve (rt_adaptive_*).
 #include <cmath>
 
+#include "../host/temporal_check.hpp"
 #include "rt_internal.hpp"
 
 using namespace rt2022;
@@ -150,6 +151,45 @@ void run_denoise_dual(const double *d_sum_a, const double *d_sum_b, const rt_fea
         if (check_rows) read_bad_rows(d_ws + denoise_dual_layout(p->width, p->height).bad_rows, stream, w);
     }
     RT_HIP(launch_denoise_dual(d, q->var_iter, p->n_iter, stream));
+}
+
+// The arguments of rt_temporal* (host/temporal_check.hpp has the rules): the parameters, then the buffers.
+void check_temporal(const double *sum, const rt_feature *feat, const uint32_t *rows, const rt_camera *cam, const rt_temporal_pixel *prev,
+                    const rt_camera *prev_cam, const rt_temporal_params *p, const rt_temporal_pixel *state_out, const double *out,
+                    const void *workspace, bool device, const std::string &w) {
+    const char *fault = temporal_params_fault(p);
+    if (!fault) fault = temporal_buffers_fault(sum, feat, rows, cam, prev, prev_cam, p, state_out, out, workspace, device);
+    RT_REQUIRE(!fault, RT_ERR_INVALID, w + ": " + (fault ? fault : ""));
+}
+
+// Enqueue one temporal accumulation on `stream`, like run_denoise: device buffers, the arguments checked.
+void run_temporal(const double *d_sum, const rt_feature *d_feat, const uint32_t *d_rows, const rt_camera *cam, const rt_temporal_pixel *d_prev,
+                  const rt_camera *prev_cam, const rt_temporal_params *p, rt_temporal_pixel *d_state, double *d_out, char *d_ws,
+                  hipStream_t stream, bool check_rows, const std::string &w) {
+    TemporalArgs a{};
+    a.width = p->width; a.height = p->height;
+    a.sp = (double)p->spp;
+    a.wm1 = (double)(p->width - 1u); a.hm1 = (double)(p->height - 1u);
+    a.wd = (double)p->width; a.hd = (double)p->height;
+    a.tol_depth = p->tol_depth; a.tol_normal = p->tol_normal; a.n_max = p->n_max; a.w_min = p->w_min; a.albedo_floor = p->albedo_floor;
+    a.demodulate = !(p->flags & RT_TEMPORAL_NO_DEMODULATE);
+    a.depth_test = !std::isinf(p->tol_depth); a.normal_test = !std::isinf(p->tol_normal);
+    for (int k = 0; k < 3; k++) {
+        a.o[k] = cam->origin[k]; a.llc[k] = cam->lower_left_corner[k]; a.hor[k] = cam->horizontal[k]; a.ver[k] = cam->vertical[k];
+        if (d_prev) {
+            a.po[k] = prev_cam->origin[k]; a.pr[k] = prev_cam->origin[k] - prev_cam->lower_left_corner[k];
+            a.phor[k] = prev_cam->horizontal[k]; a.pver[k] = prev_cam->vertical[k];
+        }
+    }
+    a.sum = d_sum; a.feat = d_feat; a.prev = d_prev; a.state = d_state; a.out = d_out;
+    if (d_rows) {
+        const TemporalLayout l = temporal_layout(p->height);
+        uint32_t *const inv = reinterpret_cast<uint32_t *>(d_ws + l.inv_rows);
+        RT_HIP(launch_row_list_check(d_rows, p->height, inv, reinterpret_cast<uint32_t *>(d_ws + l.bad_rows), stream));
+        if (check_rows) read_bad_rows(d_ws + l.bad_rows, stream, w);
+        a.inv = inv;
+    }
+    RT_HIP(launch_temporal(a, stream));
 }
 
 } // namespace
@@ -341,6 +381,47 @@ int rt_denoise_dual(const double *sum_a, const double *sum_b, const rt_feature *
         timer.run([&] { run_denoise_dual(d_a, d_b, d_fa, d_fb, row_ids ? d_rows.p : nullptr, p, q, d_a, out_variance ? d_var.p : nullptr, d_ws, nullptr, false, w); });
         RT_HIP(hipMemcpy(out_rgb_sum, d_a, 3 * n * sizeof(double), hipMemcpyDeviceToHost));
         if (out_variance) RT_HIP(hipMemcpy(out_variance, d_var, n * sizeof(double), hipMemcpyDeviceToHost));
+        timer.report(ms);
+        return RT_OK;
+    });
+}
+
+uint64_t rt_temporal_workspace_bytes(const rt_temporal_params *p) {
+    return temporal_params_fault(p) ? 0 : temporal_layout(p->height).bytes;
+}
+
+int rt_temporal_device(const double *d_rgb_sum, const rt_feature *d_features, const uint32_t *d_row_ids, const rt_camera *cam,
+                       const rt_temporal_pixel *d_prev, const rt_camera *prev_cam, const rt_temporal_params *p, rt_temporal_pixel *d_state_out,
+                       double *d_out_rgb_sum, void *d_workspace, void *hip_stream) {
+    return guarded([&]() -> int {
+        const std::string w("rt_temporal_device");
+        check_temporal(d_rgb_sum, d_features, d_row_ids, cam, d_prev, prev_cam, p, d_state_out, d_out_rgb_sum, d_workspace, true, w);
+        run_temporal(d_rgb_sum, d_features, d_row_ids, cam, d_prev, prev_cam, p, d_state_out, d_out_rgb_sum, (char *)d_workspace,
+                     (hipStream_t)hip_stream, true, w);
+        return RT_OK;
+    });
+}
+
+int rt_temporal(const double *rgb_sum, const rt_feature *features, const uint32_t *row_ids, const rt_camera *cam, const rt_temporal_pixel *prev,
+                const rt_camera *prev_cam, const rt_temporal_params *p, rt_temporal_pixel *state_out, double *out_rgb_sum, double *ms) {
+    return guarded([&]() -> int {
+        const std::string w("rt_temporal");
+        check_temporal(rgb_sum, features, row_ids, cam, prev, prev_cam, p, state_out, out_rgb_sum, nullptr, false, w);
+        check_row_permutation(row_ids, p->height, w);
+        const uint64_t n = (uint64_t)p->width * p->height;
+        DeviceBuf<double> d_sum(3 * n);                        // (accumulated in place)
+        DeviceBuf<rt_feature> d_feat(n);
+        DeviceBuf<rt_temporal_pixel> d_prev(prev ? n : 0), d_state(n);
+        DeviceBuf<uint32_t> d_rows(row_ids ? p->height : 0);
+        DeviceBuf<char> d_ws(temporal_layout(p->height).bytes);
+        NullStreamTimer timer;
+        RT_HIP(hipMemcpy(d_sum, rgb_sum, 3 * n * sizeof(double), hipMemcpyHostToDevice));
+        RT_HIP(hipMemcpy(d_feat, features, n * sizeof(rt_feature), hipMemcpyHostToDevice));
+        if (prev) RT_HIP(hipMemcpy(d_prev, prev, n * sizeof(rt_temporal_pixel), hipMemcpyHostToDevice));
+        if (row_ids) RT_HIP(hipMemcpy(d_rows, row_ids, p->height * sizeof(uint32_t), hipMemcpyHostToDevice));
+        timer.run([&] { run_temporal(d_sum, d_feat, row_ids ? d_rows.p : nullptr, cam, prev ? d_prev.p : nullptr, prev_cam, p, d_state, d_sum, d_ws, nullptr, false, w); });
+        RT_HIP(hipMemcpy(out_rgb_sum, d_sum, 3 * n * sizeof(double), hipMemcpyDeviceToHost));
+        RT_HIP(hipMemcpy(state_out, d_state, n * sizeof(rt_temporal_pixel), hipMemcpyDeviceToHost));
         timer.report(ms);
         return RT_OK;
     });

@@ -223,6 +223,14 @@ int rtb_adaptive_abi_sizes(uint32_t *out, uint32_t n) {
     return (int)count;
 }
 
+// sizeof of the rt_temporal* structures: rt_temporal_pixel, rt_temporal_params (a list of its own, like the others).
+int rtb_temporal_abi_sizes(uint32_t *out, uint32_t n) {
+    const uint32_t sizes[] = {sizeof(rt_temporal_pixel), sizeof(rt_temporal_params)};
+    const uint32_t count = sizeof(sizes) / sizeof(sizes[0]);
+    for (uint32_t i = 0; i < n && i < count; i++) out[i] = sizes[i];
+    return (int)count;
+}
+
 int rtb_write_ppm(const char *path, const uint8_t *rgb8, uint32_t width, uint32_t height) {
     return guarded([&]() -> int {
         FILE *f = path ? std::fopen(path, "wb") : nullptr;

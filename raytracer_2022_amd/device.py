@@ -162,6 +162,70 @@ def denoise_dual_device(d_sum_a_ptr, d_sum_b_ptr, d_feat_a_ptr, d_feat_b_ptr, pa
                                            C.c_void_p(d_out_variance_ptr or 0), C.c_void_p(d_workspace_ptr), C.c_void_p(stream_ptr or 0)))
 
 
+# The tuned parameters of the temporal accumulation: the point of tools/temporal_grid.py's grid with the smallest sum of the
+# three camera paths' MSE ratios accumulated / last frame (profiles/temporal_grid.log). The paths have 8 frames, so the grid
+# cannot tell n_max 8 from 32: the first of the two stands.
+TEMPORAL_DEFAULTS = {"tol_depth": 0.2, "tol_normal": 0.3, "n_max": 8.0, "w_min": 0.25}
+
+
+def temporal_params(width, height, spp, tol_depth=TEMPORAL_DEFAULTS["tol_depth"], tol_normal=TEMPORAL_DEFAULTS["tol_normal"],
+                    n_max=TEMPORAL_DEFAULTS["n_max"], w_min=TEMPORAL_DEFAULTS["w_min"], albedo_floor=1e-3, demodulate=True):
+    """rt_temporal_params: the image, the divisor of the sums, the relative depth and squared normal tolerances of a history tap
+    (+inf switches a test off), the cap of the history length and the least bilinear weight that still counts as history;
+    demodulate=False sets RT_TEMPORAL_NO_DEMODULATE."""
+    p = F.rt_temporal_params()
+    p.width, p.height, p.spp = width, height, spp
+    p.flags = 0 if demodulate else F.RT_TEMPORAL_NO_DEMODULATE
+    p.tol_depth, p.tol_normal, p.n_max, p.w_min, p.albedo_floor = tol_depth, tol_normal, n_max, w_min, albedo_floor
+    return p
+
+
+def temporal_workspace_bytes(params):
+    """rt_temporal_workspace_bytes: device bytes temporal_device needs for params' image (0: invalid params)."""
+    return int(F.lib().rt_temporal_workspace_bytes(C.byref(params)))
+
+
+def temporal(sums, features, cam, params, prev=None, prev_cam=None, row_ids=None, want_ms=False):
+    """rt_temporal with host buffers: a frame's sums (height, width, 3) and FEATURE_DTYPE records (height, width) in the order
+    of `row_ids` (None: image order), its camera, and the previous frame's state (TEMPORAL_PIXEL_DTYPE, (height, width), image
+    order; None: the first frame) with that frame's camera -> (the accumulated sums, same shape and order, the new state in
+    image order) [, device ms]."""
+    s = np.ascontiguousarray(sums, dtype=np.float64)
+    f = np.ascontiguousarray(features, dtype=F.FEATURE_DTYPE)
+    n = params.width * params.height
+    if s.size != 3 * n or f.size != n:
+        raise ValueError("sums and features must hold width * height pixels")
+    pv = None
+    if prev is not None:
+        pv = np.ascontiguousarray(prev, dtype=F.TEMPORAL_PIXEL_DTYPE)
+        if pv.size != n:
+            raise ValueError("prev must hold width * height pixels")
+    rows = None
+    if row_ids is not None:
+        rows = np.ascontiguousarray(row_ids, dtype=np.uint32)
+        if rows.size != params.height:
+            raise ValueError("row_ids must hold one entry per image row")
+    out = np.empty_like(s)
+    state = np.empty((params.height, params.width), dtype=F.TEMPORAL_PIXEL_DTYPE)
+    ms = C.c_double()
+    F.check(F.lib().rt_temporal(s.ctypes.data, f.ctypes.data, rows.ctypes.data if rows is not None else None, C.byref(cam),
+                                pv.ctypes.data if pv is not None else None, C.byref(prev_cam) if prev_cam is not None else None,
+                                C.byref(params), state.ctypes.data, out.ctypes.data, C.byref(ms)))
+    return (out, state, ms.value) if want_ms else (out, state)
+
+
+def temporal_device(d_sums_ptr, d_features_ptr, cam, params, d_state_out_ptr, d_out_ptr, d_workspace_ptr, d_prev_ptr=None, prev_cam=None,
+                    d_row_ids_ptr=None, stream_ptr=None):
+    """rt_temporal_device: device pointers in (sums, rt_feature records, room for the new state and for the accumulated sums —
+    these may be the input sums — temporal_workspace_bytes(params) bytes of workspace, the previous state or None, all 16-byte
+    aligned; `height` row ids or None), enqueued on `stream_ptr` (hipStream_t as int). The two states must not overlap. With
+    no row list the call does not synchronise."""
+    F.check(F.lib().rt_temporal_device(C.c_void_p(d_sums_ptr), C.c_void_p(d_features_ptr), C.c_void_p(d_row_ids_ptr or 0), C.byref(cam),
+                                       C.c_void_p(d_prev_ptr or 0), C.byref(prev_cam) if prev_cam is not None else None, C.byref(params),
+                                       C.c_void_p(d_state_out_ptr), C.c_void_p(d_out_ptr), C.c_void_p(d_workspace_ptr),
+                                       C.c_void_p(stream_ptr or 0)))
+
+
 def pixel_ids(frame, py, px, width, height):
     """The entry ids of rt_render_pixels: frame * (width * height) + py * width + px as uint64, the arguments broadcast against
     each other (py counts upwards, as in a render's row ids)."""

@@ -1,0 +1,137 @@
+"""Synthetic frames for the temporal accumulation's tests (no scene, no GPU): random and hostile buffers with a plausible
+geometry, the cameras they are seen from, and the analytic cases — a fronto-parallel plane under a sideways camera move,
+a disocclusion edge, a camera that stands still — whose results are known in closed form. tests/test_temporal_ref.py runs
+them through the numpy restatement, tests/test_temporal.py through the library."""
+import math
+
+import numpy as np
+
+from raytracer_2022_amd import _ffi as F
+
+import temporal_ref as R
+
+Z_MID = 5.0                                                # depth parameter the random frames scatter around
+
+
+def camera(rt, W, H, lookfrom=(0.0, 0.0, 0.0), lookat=(0.0, 0.0, -1.0)):
+    """vfov 90, focus 1, no lens, aspect (W - 1) / (H - 1): neighbouring pixel centres are |horizontal| / (W - 1) apart on the
+    focus plane and a depth parameter is a distance along -w. A width or height of one takes aspect 1."""
+    aspect = (W - 1) / (H - 1) if W > 1 and H > 1 else 1.0
+    return rt.camera_new(lookfrom, lookat, (0.0, 1.0, 0.0), 90.0, aspect, 0.0, 1.0, 0.0, 1.0)
+
+
+def pixel_shift(cam, W, z, pixels):
+    """The sideways move (along u) that shifts what lies at depth parameter z by `pixels` columns."""
+    hor = R.vec(cam.horizontal)
+    return R.vec(cam.u) * (math.sqrt(float(hor @ hor)) * z * pixels / (W - 1 if W > 1 else 1))
+
+
+def cameras(rt, W, H):
+    """name -> (current camera, previous camera) of the bit-for-bit tests."""
+    base = camera(rt, W, H)
+    moved = R.shifted_camera(base, pixel_shift(base, W, Z_MID, 2.3) + R.vec(base.v) * 0.4 + R.vec(base.w) * 0.15)
+    return {"moved": (moved, base), "identical": (base, base),
+            "previous camera facing away": (base, camera(rt, W, H, lookat=(0.0, 0.0, 1.0))),
+            "every tap outside": (R.shifted_camera(base, pixel_shift(base, W, Z_MID, 3 * W + 7)), base)}
+
+
+def frame(W, H, spp=4, seed=1, hostile=True):
+    """Sums (H, W, 3) and FEATURE_DTYPE records (H, W) of one frame: depths around Z_MID (the left half flat), normals mostly
+    facing the camera, some pixels with fewer hits than samples. hostile: NaN, 1e30 and negative sums, zero / NaN / huge
+    albedo, huge depths, NaN hits and all-zero miss records."""
+    g = np.random.default_rng(seed)
+    pick = lambda frac, shape: g.random(shape) < frac
+    sums = g.uniform(0.0, 2.0 * spp, (H, W, 3))
+    feat = np.zeros((H, W), dtype=F.FEATURE_DTYPE)
+    hits = np.full((H, W), float(spp))
+    if spp > 1:
+        part = pick(0.15, (H, W))
+        hits[part] = g.integers(1, spp, (H, W)).astype(np.float64)[part]
+    z = g.uniform(Z_MID - 2.0, Z_MID + 2.0, (H, W))
+    z[:, : W // 2] = Z_MID
+    nrm = g.normal(size=(H, W, 3))
+    nrm /= np.linalg.norm(nrm, axis=-1, keepdims=True)
+    nrm[~pick(0.3, (H, W))] = (0.0, 0.0, 1.0)
+    feat["albedo"] = g.uniform(0.0, 1.0 * spp, (H, W, 3))
+    feat["normal"] = nrm * hits[..., None]
+    feat["depth"] = z * hits
+    feat["hits"] = hits
+    if hostile:
+        sums[pick(0.03, (H, W, 3))] = np.nan
+        sums[pick(0.01, (H, W, 3))] = 1e30
+        sums[pick(0.01, (H, W, 3))] = -3.0
+        feat["albedo"][pick(0.03, (H, W))] = 0.0
+        feat["albedo"][pick(0.01, (H, W, 3))] = 1e30
+        feat["albedo"][pick(0.01, (H, W, 3))] = np.nan
+        feat["depth"][pick(0.01, (H, W))] = 1e30
+        feat["hits"][pick(0.01, (H, W))] = np.nan
+        feat.view(np.float64).reshape(H, W, 8)[pick(0.05, (H, W))] = 0.0
+    return sums, feat
+
+
+def poisoned(state, seed=1):
+    """A copy of a state with NaN, inf and zero depths, NaN radiance, an infinite and a NaN history length and NaN normals."""
+    g = np.random.default_rng(seed)
+    s = state.copy()
+    H, W = s.shape
+    pick = lambda frac, shape=(H, W): g.random(shape) < frac
+    s["depth"][pick(0.04)] = np.nan
+    s["depth"][pick(0.04)] = np.inf
+    s["depth"][pick(0.04)] = 0.0
+    s["depth"][pick(0.02)] = -1.0
+    s["e"][pick(0.03, (H, W, 3))] = np.nan
+    s["e"][pick(0.01, (H, W, 3))] = np.inf
+    s["n"][pick(0.02)] = np.inf
+    s["n"][pick(0.02)] = np.nan
+    s["normal"][pick(0.02, (H, W, 3))] = np.nan
+    return s
+
+
+def plane_frame(W, H, spp, z_of_column, seed):
+    """A frame that sees fronto-parallel planes: column x lies at depth parameter z_of_column[x], every sample hits, the
+    normal faces the camera; random sums and albedo."""
+    g = np.random.default_rng(seed)
+    sums = g.uniform(0.5, 2.0 * spp, (H, W, 3))
+    feat = np.zeros((H, W), dtype=F.FEATURE_DTYPE)
+    feat["albedo"] = g.uniform(0.2 * spp, 1.0 * spp, (H, W, 3))
+    feat["normal"] = (0.0, 0.0, 1.0 * spp)
+    feat["depth"] = np.asarray(z_of_column, dtype=np.float64)[None, :] * spp
+    feat["hits"] = spp
+    return sums, feat
+
+
+def plane_shift_case(rt, W=37, H=19, spp=4, Z=7.0):
+    """One plane at depth Z; the camera moves along +x so that the plane shifts by 3 columns. -> (params, previous frame,
+    previous camera, current frame, current camera). Expected: the history of (x, y) is the previous (x + 3, y) for
+    x + 3 <= W - 2; the last 3 columns restart."""
+    prev_cam = camera(rt, W, H)
+    cam = R.shifted_camera(prev_cam, pixel_shift(prev_cam, W, Z, 3))
+    p = rt.temporal_params(W, H, spp)
+    return p, plane_frame(W, H, spp, np.full(W, Z), 21), prev_cam, plane_frame(W, H, spp, np.full(W, Z), 22), cam
+
+
+def disocclusion_case(rt, W=38, H=19, spp=4, Z=7.0):
+    """Previous frame: a near plane (Z) on the columns < W / 2, a far one (2 Z) on the rest. The camera moves for a 6-column
+    near shift, so the far plane shifts 3 and the near plane covers the columns < W / 2 - 6 now. Expected: exactly the far
+    columns [W / 2 - 6, W / 2 - 3) and the last 3 columns restart; every other pixel has n == previous n + 1."""
+    assert W % 2 == 0
+    prev_cam = camera(rt, W, H)
+    cam = R.shifted_camera(prev_cam, pixel_shift(prev_cam, W, Z, 6))
+    x = np.arange(W)
+    p = rt.temporal_params(W, H, spp)
+    prev = plane_frame(W, H, spp, np.where(x < W // 2, Z, 2 * Z), 31)
+    cur = plane_frame(W, H, spp, np.where(x < W // 2 - 6, Z, 2 * Z), 32)
+    restart = ((x >= W // 2 - 6) & (x < W // 2 - 3)) | (x >= W - 3)
+    return p, prev, prev_cam, cur, cam, restart
+
+
+def check_plane_shift(state, prev_state, cur_e, W):
+    """The current state of the plane-shift case against its closed form: n == 2 and e == h + (e_cur - h) / 2 with h the
+    previous e three columns to the right, within 1e-9 of max |e|, for x + 3 <= W - 2; the last 3 columns restarted."""
+    scale = max(np.abs(prev_state["e"]).max(), np.abs(cur_e).max())
+    h = prev_state["e"][:, 3: W - 1]
+    want = h + (cur_e[:, : W - 4] - h) / 2.0
+    assert np.abs(state["e"][:, : W - 4] - want).max() <= 1e-9 * scale
+    assert (state["n"][:, : W - 4] == 2.0).all()
+    assert (state["n"][:, W - 3:] == 1.0).all()
+    assert np.array_equal(state["e"][:, W - 3:], cur_e[:, W - 3:])
