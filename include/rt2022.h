@@ -410,6 +410,7 @@ typedef struct rt_hit {               /* 96 B */
 
 #define RT_REF_NONE     0xFFFFFFFFu
 #define RT_FLAG_ANY_HIT 0x8u          /* rt_intersect*: stop at the first accepted candidate (see above) */
+#define RT_FLAG_SURFACES 0x10u        /* rt_features* / rt_features_pixels* only: look through every ConstantMedium (see there) */
 
 /* Host buffers; synchronous. stats may be NULL. */
 int rt_intersect(rt_scene *scene, const rt_query_ray *rays, uint64_t n_rays, uint32_t flags,
@@ -503,6 +504,19 @@ int rt_radiance_device(rt_scene *scene, const rt_radiance_ray *d_rays, uint64_t 
  *   depth      rec.t                                                                            0
  *   hits       1                                                                                0
  *
+ * RT_FLAG_SURFACES (a flag bit older callers never set: the ABI version stays 3; all four feature calls take it): the
+ * records of the first SURFACE behind every participating medium. The sample is the one above with one change:
+ * ConstantMedium::hit returns None at once — it does not query its boundary and draws no word. Everything else stays:
+ * world.hit's order, the winner's record, the albedo rule, the sums and their order. Fog in front of nothing gives the miss
+ * record (background, zeros, hits 0); an object that is both in the world and some medium's boundary is still hit through
+ * its own reference; a scene whose root is a medium gives miss records only. On a scene without a medium the flag changes
+ * nothing, counters included. With RT_FLAG_COUNTERS rt_stats counts what this definition does: prim_tests[RT_KIND_MEDIUM]
+ * is 0, no boundary is tested, and rng_draws is the camera's words only (2 + what rto_get_ray returns). The CPU oracle
+ * gives the same records on a copy of the scene whose media all have neg_inv_density = -inf (hit_distance is then +inf
+ * and a medium never answers) as long as every distance_inside_boundary is finite. What it is for: rt_temporal* and the
+ * denoisers read these records, and a medium's drawn depth and (1, 0, 0) normal are noise to them. Participating media are
+ * then reprojected and filtered by the surface behind them — wrong for dense smoke with parallax of its own.
+ *
  * Each field of a pixel's record is 0 + f_0 + f_1 + ... + f_{spp-1}, added in sample order and NOT divided by spp, like a
  * render's sums (rt_tonemap_device / rt_write_color do not apply): hits / spp is coverage, depth / hits the mean depth over
  * the hits. Records come in row_ids order, n_rows * width of them. Every sum is the CPU oracle's composition rto_path_key
@@ -515,7 +529,7 @@ int rt_radiance_device(rt_scene *scene, const rt_radiance_ray *d_rays, uint64_t 
  *
  * Arguments: spp == 0 or n_rows == 0 is RT_OK (zeros or nothing written, no kernel). RT_ERR_INVALID with rt_last_error()
  * set, before any kernel: a null scene, cam or params; null rows or output with work to do; a flag bit other than
- * RT_FLAG_COUNTERS; a device output that is not 16-byte aligned or device rows that are not 4-byte aligned; width, height
+ * RT_FLAG_COUNTERS / RT_FLAG_SURFACES; a device output that is not 16-byte aligned or device rows that are not 4-byte aligned; width, height
  * or n_frames equal to 0 (or cam->time0 >= cam->time1, as for a render); a row id >= height * n_frames (device rows are
  * checked by the small reduction kernel rt_render_device uses, behind one synchronisation of hip_stream before the
  * feature kernel is enqueued).
@@ -554,13 +568,13 @@ int rt_features_device(rt_scene *scene, const rt_camera *cam, const rt_params *p
  * ENTRY through all its samples, and decodes the id by two 32-bit divisions where width * height * n_frames fits 32 bits,
  * by 64-bit ones otherwise.
  *
- * rt_params: used — width, height, spp, background, t_min, seed, n_frames, flags; IGNORED — n_rows, row_ids, max_depth,
+ * rt_params: used — width, height, spp, background, t_min, seed, n_frames, flags (RT_FLAG_SURFACES as for rt_features); IGNORED — n_rows, row_ids, max_depth,
  * spp_chunk, progress_cb / progress_user.
  *
  * Arguments: n_entries == 0 is RT_OK; spp == 0 is RT_OK and writes zeros with no feature kernel. RT_ERR_INVALID with
  * rt_last_error() set, before any feature kernel: a null scene, cam or params; null ids or output with n_entries > 0;
  * width, height or n_frames equal to 0 (or height * n_frames above 2^32 - 1: the matching row id must exist);
- * cam->time0 >= cam->time1; a flag bit other than RT_FLAG_COUNTERS; device ids that are not 8-byte aligned or a device
+ * cam->time0 >= cam->time1; a flag bit other than RT_FLAG_COUNTERS / RT_FLAG_SURFACES; device ids that are not 8-byte aligned or a device
  * output that is not 16-byte aligned; n_entries > 2^40; an id >= width * height * n_frames — host ids are checked on the
  * host, device ids by the counting kernel rt_render_pixels_device uses, behind one synchronisation of hip_stream BEFORE
  * the feature kernel is enqueued: a refused call leaves the output untouched.
@@ -735,7 +749,7 @@ int rt_denoise_dual(const double *sum_a, const double *sum_b,
  *   c_j = nan0(S_j) / sp;  a_j = F.albedo_j / sp
  *   m_j = a_j > albedo_floor ? a_j : albedo_floor  (rt_denoise's rule; RT_TEMPORAL_NO_DEMODULATE: m_j = 1.0);  e_j = c_j / m_j
  *   covered = F.hits > 0;  zb = covered ? F.depth / F.hits : 0;  nb_j = covered ? F.normal_j / F.hits : 0
- * Restart: e_out = e, n_out = 1. A pixel restarts with no d_prev, when it is not covered, and wherever stated below.
+ * Restart: e_out = e, n_out = 1. A pixel restarts with no d_prev, when it is not covered (but see RT_TEMPORAL_FAR_MISSES below), and wherever stated below.
  * Otherwise, with cross(u, v) = (u1*v2 - u2*v1, u2*v0 - u0*v2, u0*v1 - u1*v0) and dot(u, v) = (u0*v0 + u1*v1) + u2*v2,
  * o / llc / hor / ver the current camera's origin, lower_left_corner, horizontal, vertical and o' / llc' / hor' / ver' the
  * previous camera's:
@@ -760,6 +774,18 @@ int rt_denoise_dual(const double *sum_a, const double *sum_b,
  * sums of `spp` samples again, so rt_tonemap_device, rt_denoise*, rt_write_color apply as they are. Buffer contents are
  * never validated: NaN and inf propagate as IEEE carries them. n_max = 1 makes e_out = eh + (e - eh), which is e to rounding: no history is kept.
  *
+ * RT_TEMPORAL_FAR_MISSES (a flag bit older callers never set: the ABI version stays 3): history for pixels that miss. It
+ * applies when d_prev is given and the pixel is not covered (F.hits > 0 is false); covered pixels are untouched. Then
+ *   D_k = G_k - o_k  with G from sc, tc as above: the pixel centre's direction, a point at infinity
+ *   c_k = -D_k;  r_k = o'_k - llc'_k
+ *   bc, rc, br, det, s', t', lam, fx, fy by the same expressions in the same order; no ze is formed.
+ * History exists only if lam > 0 and the same range tests hold; only then are fx and fy converted to integers, and the taps
+ * and their weights are the same four. A tap q counts if it is inside the image and prev(q).depth == 0.0 — an uncovered
+ * pixel of the previous state (a NaN depth does not count); there is no depth test and no normal test. The sums, the w_min
+ * rule, n_out and e_out are as above; state_out(p) = {e_out, n_out, 0, 0}. A covered pixel's taps need depth > 0, so the
+ * two kinds never mix. An image one pixel wide or high still restarts everywhere. Sky, a black backdrop and — with
+ * RT_FLAG_SURFACES records — fog in front of nothing then keep their history under a turning camera.
+ *
  * Two halves for rt_denoise_dual need nothing more: call once per half, each with that half's own sums, features and
  * states, so that A and B stay independent estimates; then rt_denoise_dual_device on the two outputs with the current
  * frame's features.
@@ -779,10 +805,12 @@ int rt_denoise_dual(const double *sum_a, const double *sum_b,
  * RT_ERR_INVALID with rt_last_error() set, before any device call: a null params, cam, sums, features, output, state or
  * workspace; width, height or spp equal to 0; width * height > RT_DENOISE_MAX_PIXELS; a tolerance that is <= 0 or NaN;
  * n_max < 1, NaN or infinite; w_min outside (0, 1]; a floor that is <= 0, NaN or infinite; a flag bit other than
- * RT_TEMPORAL_NO_DEMODULATE; a misaligned pointer; d_prev without prev_cam; overlapping states.
+ * RT_TEMPORAL_NO_DEMODULATE / RT_TEMPORAL_FAR_MISSES; a misaligned pointer; d_prev without prev_cam; overlapping states.
  *
- * Limits: static scenes only. A ConstantMedium's first hit has a drawn depth and the normal (1, 0, 0): pixels seen through
- * a medium mostly fail the depth test and restart. Edge pixels whose samples straddle two surfaces have a mean depth on
+ * Limits: static scenes only. Under first-hit records a ConstantMedium's hit has a drawn depth and the normal (1, 0, 0):
+ * pixels seen through a medium mostly fail the depth test and restart. RT_FLAG_SURFACES records reproject a medium by the
+ * surface behind it instead, which is wrong for dense smoke with parallax of its own. Without RT_TEMPORAL_FAR_MISSES a pixel
+ * that is not covered never takes history. Edge pixels whose samples straddle two surfaces have a mean depth on
  * neither and restart. Neither state can be given as a strip of rows; there is no rt_scene_set form. */
 typedef struct rt_temporal_pixel {    /* 64 B: four 16-byte pieces */
     double   e[3];                    /* accumulated demodulated mean radiance */
@@ -792,7 +820,7 @@ typedef struct rt_temporal_pixel {    /* 64 B: four 16-byte pieces */
 } rt_temporal_pixel;
 
 typedef struct rt_temporal_params {   /* 64 B */
-    uint32_t width, height, spp, flags;   /* flags: RT_TEMPORAL_NO_DEMODULATE */
+    uint32_t width, height, spp, flags;   /* flags: RT_TEMPORAL_NO_DEMODULATE | RT_TEMPORAL_FAR_MISSES */
     double   tol_depth, tol_normal;   /* > 0; +inf = test off */
     double   n_max;                   /* >= 1, finite: cap of the history length */
     double   w_min;                   /* in (0, 1]: least valid bilinear weight that still counts as history */
@@ -800,6 +828,7 @@ typedef struct rt_temporal_params {   /* 64 B */
     double   _pad;
 } rt_temporal_params;
 #define RT_TEMPORAL_NO_DEMODULATE 0x1u               /* accumulate the radiance itself: m = 1 */
+#define RT_TEMPORAL_FAR_MISSES 0x4u                  /* uncovered pixels reproject as points at infinity (see above); 0x2 is not a flag */
 
 /* Bytes of device workspace rt_temporal_device needs for p's image; 0 on invalid params. */
 uint64_t rt_temporal_workspace_bytes(const rt_temporal_params *p);

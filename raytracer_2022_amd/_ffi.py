@@ -26,6 +26,7 @@ RT_FLAG_COUNTERS = 0x1
 RT_FLAG_KERNEL_TIMES = 0x2
 RT_FLAG_ASYNC = 0x4
 RT_FLAG_ANY_HIT = 0x8
+RT_FLAG_SURFACES = 0x10
 RT_REF_NONE = 0xFFFFFFFF
 RT_OK, RT_ERR_INVALID, RT_ERR_UNSUPPORTED, RT_ERR_DEVICE, RT_ERR_NOMEM = 0, -1, -2, -3, -4
 
@@ -235,6 +236,7 @@ class rt_temporal_params(C.Structure):
 
 
 RT_TEMPORAL_NO_DEMODULATE = 0x1
+RT_TEMPORAL_FAR_MISSES = 0x4
 # numpy twin of rt_temporal_pixel (arrays of it are the states of rt_temporal as they are)
 TEMPORAL_PIXEL_DTYPE = np.dtype([("e", "<f8", (3,)), ("n", "<f8"), ("depth", "<f8"), ("normal", "<f8", (3,))])
 # The rt_temporal* structures, in the order of rtb_temporal_abi_sizes.

@@ -275,9 +275,11 @@ struct FeatureArgs {
     unsigned long long *counter;       // pixels handed out so far (zeroed before launch)
     StatsDev *stats;                   // counter instances only
 };
-hipError_t launch_features(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, hipStream_t stream);
+// `surfaces`: RT_FLAG_SURFACES, the instances that pop a medium leaf instead of entering it.
+hipError_t launch_features(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, bool surfaces, hipStream_t stream);
 // The pixel source (rt_features_pixels*): args.pixel_ids and args.ids32 in place of row_ids and n_rows.
-hipError_t launch_features_pixels(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, hipStream_t stream);
+hipError_t launch_features_pixels(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, bool surfaces,
+                                  hipStream_t stream);
 
 // ---- edge-avoiding denoiser (pt_denoise.hip, rt_denoise*) ----------------------------
 // Where the pieces of the caller's workspace lie (byte offsets, each a multiple of 16) — the one place that knows.
@@ -345,6 +347,7 @@ struct TemporalArgs {
     double wd, hd;                     // (double)width, (double)height
     double tol_depth, tol_normal, n_max, w_min, albedo_floor;
     bool demodulate, depth_test, normal_test;      // (a tolerance of +inf switches its test off)
+    bool far_misses;                   // RT_TEMPORAL_FAR_MISSES: uncovered pixels reproject as points at infinity
     double o[3], llc[3], hor[3], ver[3];           // the current camera
     double po[3], pr[3], phor[3], pver[3];         // the previous camera: origin, origin - lower_left_corner, horizontal, vertical
     const double *sum;                 // device: the render's sums, buffer order

@@ -19,6 +19,11 @@
 // (frame, pixel) ids, rt_render_pixels' (rt_features_pixels*). With a list the work item is ONE ENTRY, the lane's record is
 // out + entry, and f_camera decodes pixel_ids[entry] into frame, py and px where the row source reads row_ids[row]; all else
 // — traversal, f_albedo, the record's four pieces, the claim, the scheduler loop — is the same code.
+// RT_FLAG_SURFACES (SURF, instances of their own): a ConstantMedium answers None at once — its leaf is popped where the
+// medium arm would enter trav_medium, so no boundary is queried, no word drawn and nothing counted; an object that is also
+// some medium's boundary is still reached through its own reference. Instances and not a uniform switch in FeatureArgs: with
+// the switch five of the sixteen unflagged instances spilled more (up to +8 bytes of scratch per lane); as instances, those
+// are compiled from the code they had and keep every register (profiles/features_surfaces_kernel_resources.txt).
 // One lane per pixel means a few-pixel x huge-spp job balances poorly; the intended use is a whole frame at modest spp.
 // All arithmetic is f64 through rt_math.h with -ffp-contract=off, so every sum is the CPU oracle's composition bit for bit.
 #include "pt_traverse.hpp"
@@ -152,8 +157,8 @@ RT_DEV void f_done(const SceneDev &s, const FeatureArgs &a, FLane &L, unsigned l
 // mesh 169 / 333 / 291 Mrays/s, 1e5 spheres 143 / 299 / 278 (profiles/features_ab_occupancy.log).
 constexpr int feat_waves(int stack, int wg) { return wg > 256 ? 4 : stack > 32 ? 2 : 3; }
 // STACK: traversal stack entries; WG: threads per workgroup; CACHE: node records kept in LDS (0: none); STATS: counter instance;
-// SRC: kFeatRows or kFeatPixels (last, and defaulted: the row instances keep their names).
-template <int STACK, int WG, int CACHE, bool STATS, int SRC = kFeatRows>
+// SRC: kFeatRows or kFeatPixels; SURF: RT_FLAG_SURFACES (both defaulted: the earlier instances keep their names).
+template <int STACK, int WG, int CACHE, bool STATS, int SRC = kFeatRows, bool SURF = false>
 __global__ void __launch_bounds__(WG, feat_waves(STACK, WG)) pt_features(const SceneDev s, const FeatureArgs a) {
     __shared__ uint32_t stack_lds[STACK * WG];
     __shared__ double node_lds[CACHE > 0 ? CACHE * kTravNodeDoubles : 1];
@@ -203,7 +208,10 @@ __global__ void __launch_bounds__(WG, feat_waves(STACK, WG)) pt_features(const S
                 case OP_SPHERE: trav_sphere<false>(s, L, st, cnt); break;
                 case OP_RECT: trav_rect<false>(s, L, st, cnt); break;
                 case OP_BOX: trav_box<false>(s, L, st, cnt); break;
-                case OP_MEDIUM: trav_medium<false>(s, L, st, cnt); break;
+                case OP_MEDIUM:                            // (SURF: the leaf is popped; no sentinel is ever pushed then)
+                    if constexpr (SURF) trav_next<false>(L, st);
+                    else trav_medium<false>(s, L, st, cnt);
+                    break;
                 case OP_MISC: trav_misc<false>(s, L, st, cnt); break;
                 case OP_CTX: trav_ctx<false>(s, L, st, cnt, world); break;
                 default: f_done<SRC, STATS>(s, a, L, lane, cnt); break;
@@ -213,25 +221,30 @@ __global__ void __launch_bounds__(WG, feat_waves(STACK, WG)) pt_features(const S
     if (STATS) cnt.flush_wave(a.stats);
 }
 
-hipError_t launch_features(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, hipStream_t stream) {
+namespace {
+
+// The instance of a call: by the scene's stack need, then counters and RT_FLAG_SURFACES.
+template <int SRC>
+hipError_t launch_features_src(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, bool surfaces, hipStream_t stream) {
     if (args.n_pixels == 0 || args.spp == 0) return hipSuccess;
     return trav_dispatch(stack_need, [&](auto shape) {
         using S = decltype(shape);
         void (*const kernel)(SceneDev, FeatureArgs) =
-            counters ? pt_features<S::stack, S::wg, S::cache, true> : pt_features<S::stack, S::wg, S::cache, false>;
+            surfaces ? (counters ? pt_features<S::stack, S::wg, S::cache, true, SRC, true> : pt_features<S::stack, S::wg, S::cache, false, SRC, true>)
+                     : (counters ? pt_features<S::stack, S::wg, S::cache, true, SRC> : pt_features<S::stack, S::wg, S::cache, false, SRC>);
         return launch_persistent(kernel, S::wg, args.n_pixels, scene, args, stream);
     });
 }
 
-// (behind the row instances: those keep their places in the code object)
-hipError_t launch_features_pixels(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, hipStream_t stream) {
-    if (args.n_pixels == 0 || args.spp == 0) return hipSuccess;
-    return trav_dispatch(stack_need, [&](auto shape) {
-        using S = decltype(shape);
-        void (*const kernel)(SceneDev, FeatureArgs) = counters ? pt_features<S::stack, S::wg, S::cache, true, kFeatPixels>
-                                                               : pt_features<S::stack, S::wg, S::cache, false, kFeatPixels>;
-        return launch_persistent(kernel, S::wg, args.n_pixels, scene, args, stream);
-    });
+} // namespace
+
+hipError_t launch_features(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, bool surfaces, hipStream_t stream) {
+    return launch_features_src<kFeatRows>(scene, args, stack_need, counters, surfaces, stream);
+}
+
+hipError_t launch_features_pixels(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, bool surfaces,
+                                  hipStream_t stream) {
+    return launch_features_src<kFeatPixels>(scene, args, stack_need, counters, surfaces, stream);
 }
 
 } // namespace rt2022

@@ -8,7 +8,8 @@
 // lane reads two 128-byte spans of d_prev as 16-byte pieces. It writes its own state record (four 16-byte pieces, image
 // order) and its three sums (buffer order). Nothing is staged: no LDS, and no workspace but the row kernel's map (dn_rows of
 // pt_denoise.hip, through launch_row_list_check). fx / fy become integers only after the range test, so a tap's address is
-// computed from numbers in [-1, width] x [-1, height] and is used only when it lies inside the image.
+// computed from numbers in [-1, width] x [-1, height] and is used only when it lies inside the image. A far miss
+// (RT_TEMPORAL_FAR_MISSES) takes the same path with another right-hand side and another tap rule: the same four taps.
 #include "pt_device.h"
 
 namespace rt2022 {
@@ -50,14 +51,20 @@ __global__ void __launch_bounds__(kTpBlock) tp_accumulate(const TemporalArgs a) 
     const double nb[3] = {covered ? f1.y / hits : 0.0, covered ? f2.x / hits : 0.0, covered ? f2.y / hits : 0.0};
 
     double eo[3] = {e[0], e[1], e[2]}, no = 1.0;           // the restart
-    if (a.prev && covered) {
+    // RT_TEMPORAL_FAR_MISSES (a.far_misses, uniform): an uncovered pixel is a point at infinity — the pixel centre's
+    // direction in place of P - o', no ze, and its taps are the previous state's uncovered pixels (depth == 0.0), untested.
+    if (a.prev && (covered || a.far_misses)) {
         const double sc = ((double)x + 0.5) / a.wm1, tc = ((double)y + 0.5) / a.hm1;
         double c[3];
 #pragma unroll
         for (int k = 0; k < 3; k++) {
             const double g = (a.llc[k] + sc * a.hor[k]) + tc * a.ver[k];
-            const double p = a.o[k] + zb * (g - a.o[k]);
-            c[k] = -(p - a.po[k]);
+            if (covered) {
+                const double p = a.o[k] + zb * (g - a.o[k]);
+                c[k] = -(p - a.po[k]);
+            } else {
+                c[k] = -(g - a.o[k]);
+            }
         }
         double bc[3], rc[3], br[3];
         tp_cross(a.pver, c, bc);
@@ -68,7 +75,7 @@ __global__ void __launch_bounds__(kTpBlock) tp_accumulate(const TemporalArgs a) 
         const double fx = s1 * a.wm1 - 0.5, fy = t1 * a.hm1 - 0.5;
         // (the range test refuses NaN and both infinities: only then are fx and fy turned into integers)
         if (lam > 0.0 && fx >= -1.0 && fx < a.wd && fy >= -1.0 && fy < a.hd) {
-            const double ze = 1.0 / lam;
+            const double ze = covered ? 1.0 / lam : 0.0;
             const double xf = floor(fx), yf = floor(fy);
             const double wx = fx - xf, wy = fy - yf;
             const int64_t x0 = (int64_t)xf, y0 = (int64_t)yf;
@@ -81,12 +88,12 @@ __global__ void __launch_bounds__(kTpBlock) tp_accumulate(const TemporalArgs a) 
                 const double2 *q = reinterpret_cast<const double2 *>(a.prev + ((uint64_t)qy * a.width + (uint64_t)qx));
                 const double2 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];       // {e0, e1} {e2, n} {depth, n0} {n1, n2}
                 const double pd = q2.x;
-                if (!(pd > 0.0)) continue;
-                if (a.depth_test) {
+                if (!(covered ? pd > 0.0 : pd == 0.0)) continue;
+                if (covered && a.depth_test) {
                     const double dd = pd - ze;
                     if (!((dd < 0.0 ? -dd : dd) <= a.tol_depth * ze)) continue;
                 }
-                if (a.normal_test) {
+                if (covered && a.normal_test) {
                     const double d0 = nb[0] - q2.y, d1 = nb[1] - q3.x, d2 = nb[2] - q3.y;
                     if (!((d0 * d0 + d1 * d1) + d2 * d2 <= a.tol_normal)) continue;
                 }

@@ -174,6 +174,7 @@ void run_temporal(const double *d_sum, const rt_feature *d_feat, const uint32_t 
     a.tol_depth = p->tol_depth; a.tol_normal = p->tol_normal; a.n_max = p->n_max; a.w_min = p->w_min; a.albedo_floor = p->albedo_floor;
     a.demodulate = !(p->flags & RT_TEMPORAL_NO_DEMODULATE);
     a.depth_test = !std::isinf(p->tol_depth); a.normal_test = !std::isinf(p->tol_normal);
+    a.far_misses = (p->flags & RT_TEMPORAL_FAR_MISSES) != 0;
     for (int k = 0; k < 3; k++) {
         a.o[k] = cam->origin[k]; a.llc[k] = cam->lower_left_corner[k]; a.hor[k] = cam->horizontal[k]; a.ver[k] = cam->vertical[k];
         if (d_prev) {

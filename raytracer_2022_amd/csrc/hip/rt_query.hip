@@ -56,7 +56,7 @@ void check_features(const rt_scene *scene, const rt_camera *cam, const rt_params
     const std::string w(who);
     RT_REQUIRE(p, RT_ERR_INVALID, w + ": null params");
     RT_REQUIRE(cam, RT_ERR_INVALID, w + ": null camera");
-    RT_REQUIRE(!(p->flags & ~RT_FLAG_COUNTERS), RT_ERR_INVALID, w + ": flag bits other than RT_FLAG_COUNTERS");
+    RT_REQUIRE(!(p->flags & ~(RT_FLAG_COUNTERS | RT_FLAG_SURFACES)), RT_ERR_INVALID, w + ": flag bits other than RT_FLAG_COUNTERS | RT_FLAG_SURFACES");
     check_view(cam, p, w + ": ", " (width, height or n_frames is 0)");
     const bool need_rows = p->n_rows > 0 && p->spp > 0;
     RT_REQUIRE(p->n_rows == 0 || out, RT_ERR_INVALID, w + ": null output");
@@ -103,7 +103,8 @@ void run_features(rt_scene *sc, const rt_camera *cam, const rt_params *p, const 
     a.out = d_out;
     a.counter = q.counter;
     a.stats = counters ? q.stats.p : nullptr;
-    run_counted(q, counters, stream, stats, [&] { return launch_features(sc->dev, a, sc->stack_need, counters, stream); });
+    const bool surfaces = (p->flags & RT_FLAG_SURFACES) != 0;
+    run_counted(q, counters, stream, stats, [&] { return launch_features(sc->dev, a, sc->stack_need, counters, surfaces, stream); });
     if (stats) stats->paths = stats->rays = n_pixels * p->spp;     // (one camera path, one world.hit per sample; the kernel counts neither)
 }
 
@@ -114,7 +115,7 @@ void check_features_pixels(const rt_scene *scene, const rt_camera *cam, const rt
     const std::string w(who);
     RT_REQUIRE(p, RT_ERR_INVALID, w + ": null params");
     RT_REQUIRE(cam, RT_ERR_INVALID, w + ": null camera");
-    RT_REQUIRE(!(p->flags & ~RT_FLAG_COUNTERS), RT_ERR_INVALID, w + ": flag bits other than RT_FLAG_COUNTERS");
+    RT_REQUIRE(!(p->flags & ~(RT_FLAG_COUNTERS | RT_FLAG_SURFACES)), RT_ERR_INVALID, w + ": flag bits other than RT_FLAG_COUNTERS | RT_FLAG_SURFACES");
     check_view(cam, p, w + ": ", " (width, height or n_frames is 0)");
     RT_REQUIRE(n_entries == 0 || (ids && out), RT_ERR_INVALID, w + ": null id or output buffer");
     RT_REQUIRE(n_entries <= (1ull << 40), RT_ERR_INVALID, w + ": n_entries too large");
@@ -160,8 +161,9 @@ void run_features_pixels(rt_scene *sc, const rt_camera *cam, const rt_params *p,
     a.out = d_out;
     a.counter = q.counter;
     a.stats = counters ? q.stats.p : nullptr;
+    const bool surfaces = (p->flags & RT_FLAG_SURFACES) != 0;
     a.pixel_ids = d_ids;
-    run_counted(q, counters, stream, stats, [&] { return launch_features_pixels(sc->dev, a, sc->stack_need, counters, stream); });
+    run_counted(q, counters, stream, stats, [&] { return launch_features_pixels(sc->dev, a, sc->stack_need, counters, surfaces, stream); });
     if (stats) stats->paths = stats->rays = n_entries * p->spp;    // (as run_features)
 }
 

@@ -19,7 +19,7 @@ inline const char *temporal_params_fault(const rt_temporal_params *p) {
     if (!(p->n_max >= 1.0) || std::isinf(p->n_max)) return "n_max is < 1, NaN or infinite";
     if (!(p->w_min > 0.0) || !(p->w_min <= 1.0)) return "w_min is outside (0, 1]";
     if (!(p->albedo_floor > 0.0) || std::isinf(p->albedo_floor)) return "albedo_floor is <= 0, NaN or infinite";
-    if (p->flags & ~RT_TEMPORAL_NO_DEMODULATE) return "flag bits other than RT_TEMPORAL_NO_DEMODULATE";
+    if (p->flags & ~(RT_TEMPORAL_NO_DEMODULATE | RT_TEMPORAL_FAR_MISSES)) return "flag bits other than RT_TEMPORAL_NO_DEMODULATE | RT_TEMPORAL_FAR_MISSES";
     return nullptr;
 }
 

@@ -1,0 +1,388 @@
+"""RT_FLAG_SURFACES on the four feature calls: the records of the first surface behind every ConstantMedium, against the
+oracle's composition on the looked-through copy of the scene (tests/surface_ref.py) bit for bit, with the counters the
+definition implies; the flag on scenes without media (nothing changes, on every kernel shape); the pixel-list and the device
+forms; what still refuses the bit; render_adaptive(surfaces=True). Every test here needs the flag: the parent refuses it."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from raytracer_2022_amd import _ffi as F
+
+import surface_ref as S
+import trace_scenes as TS
+from query_scenes import composite_boundary_scene
+from test_features import assert_same_bits, every_kind_scene
+from test_features_pixels import all_rows, oracle_ids, shuffled_ids_with_repeats
+
+pytestmark = pytest.mark.gpu
+
+W0, H0, SPP0 = 48, 32, 3
+MEDIA_FREE = ["cornell_box", "earth", "random_scene", "simple_light", "two_perlin_spheres", "two_spheres", "wwscene"]
+
+
+@pytest.fixture(scope="module", autouse=True)
+def torch_first():
+    """Bring torch's HIP context up before the library's first call, as the other GPU test modules do."""
+    import torch
+    assert torch.cuda.is_available(), "gpu tests need a GPU: the HIP path has no fallback"
+    torch.zeros(1, device="cuda")
+
+
+# ---- scenes ---------------------------------------------------------------------------------------------------------------
+def under_movers_scene(rt):
+    """A medium UNDER Translate + RotateY (the movers hold the medium, not its boundary), in front of a textured wall."""
+    b = rt.DescBuilder()
+    glass = b.dielectric(1.5)
+    fog = b.medium(b.box((-0.8, 0.0, -0.8), (0.8, 1.6, 0.8), glass), 2.0, b.isotropic((0.9, 0.9, 0.9)))
+    moved = b.translate(b.rotate_y(fog, 0.5, 0.8660254037844386), (0.6, 0.1, -1.0))
+    wall = b.rect(F.RT_RECT_XY, -6, 6, -2, 5, -4.0, b.lambertian(tex=b.checker(b.solid((0.2, 0.3, 0.1)), b.solid((0.9, 0.9, 0.9)))))
+    ball = b.translate(b.sphere((0.0, 0.0, 0.0), 0.5, b.metal((0.8, 0.6, 0.2), 0.0)), (0.5, 0.8, -2.6))      # behind the fog
+    b.set_root(b.list([moved, wall, ball]))
+    cam = rt.camera_new((0, 1.0, 5), (0.3, 0.8, -1), (0, 1, 0), 40.0, W0 / H0, 0.0, 6.0, 0.0, 1.0)
+    return b, b.desc(), cam, (0.3, 0.4, 0.6)
+
+
+def list_boundary_scene(rt):
+    """A medium whose boundary is a HittableList of two spheres and a box; one of the spheres is in the world as well, under its
+    own reference: it is still hit."""
+    b = rt.DescBuilder()
+    glass = b.dielectric(1.5)
+    shared = b.sphere((-0.9, 0.3, -3.0), 0.9, glass)
+    shell = b.list([shared, b.sphere((0.9, 0.3, -3.0), 0.9, glass), b.box((-0.4, -0.6, -3.5), (0.4, 1.4, -2.5), glass)])
+    fog = b.medium(shell, 1.2, b.isotropic((0.4, 0.8, 0.5)))
+    floor_ = b.rect(F.RT_RECT_XZ, -20, 20, -20, 20, -0.6, b.lambertian((0.5, 0.5, 0.5)))
+    back = b.sphere((0.0, 0.5, -7.0), 1.5, b.lambertian((0.8, 0.2, 0.2)))
+    b.set_root(b.list([fog, floor_, shared, back]))
+    cam = rt.camera_new((0, 1, 3), (0, 0.3, -3), (0, 1, 0), 45.0, W0 / H0, 0.0, 6.0, 0.0, 1.0)
+    return b, b.desc(), cam, (0.6, 0.7, 0.9)
+
+
+def medium_root_scene(rt):
+    """The root IS a medium: under the flag nothing is ever hit."""
+    b = rt.DescBuilder()
+    b.set_root(b.medium(b.sphere((0, 0, -3), 2.0, b.dielectric(1.5)), 3.0, b.isotropic((0.9, 0.9, 0.9))))
+    cam = rt.camera_new((0, 0, 3), (0, 0, -3), (0, 1, 0), 50.0, W0 / H0, 0.0, 6.0, 0.0, 1.0)
+    return b, b.desc(), cam, (0.125, 0.25, 0.5)
+
+
+def case(rt, which):
+    """-> (what keeps the pools alive, desc, cam, background)"""
+    if which in ("cornell_smoke", "final_scene"):
+        s = rt.HostScene(which, seed=2022)
+        cam, bg = s.default_view(W0 / H0)
+        return s, s.desc, cam, bg
+    if which in ("every kind", "lens and shutter"):
+        b, d, _ = every_kind_scene(rt)
+        aperture = 0.4 if which == "lens and shutter" else 0.0     # (time0 < time1: the shutter's word is drawn either way)
+        return b, d, rt.camera_new((0, 1.8, 10), (0, 1.6, 0), (0, 1, 0), 40.0, W0 / H0, aperture, 10.0, 0.0, 1.0), (0.25, 0.5, 0.75)
+    if which == "bvh boundary":
+        d, cam = composite_boundary_scene(rt)
+        return d, d, cam, (0.5, 0.7, 1.0)
+    return {"under movers": under_movers_scene, "list boundary": list_boundary_scene, "medium root": medium_root_scene}[which](rt)
+
+
+CASES = ["cornell_smoke", "final_scene", "every kind", "under movers", "bvh boundary", "list boundary", "medium root", "lens and shutter"]
+
+
+def boundary_contents(d):
+    """(the kinds reachable from any medium's boundary, whether a BVH node is among them)."""
+    kinds, todo, seen = set(), [d.media[i].boundary for i in range(d.n_media)], set()
+    while todo:
+        r = int(todo.pop()) & ~F.RT_REF_FLIP & 0xFFFFFFFF
+        if r in seen:
+            continue
+        seen.add(r)
+        k, i = F.ref_kind(r), F.ref_index(r)
+        kinds.add(k)
+        if k == F.RT_KIND_NODE:
+            todo += [d.nodes[i].left, d.nodes[i].right]
+        elif k == F.RT_KIND_LIST:
+            todo += [d.list_items[d.lists[i].first + j] for j in range(d.lists[i].count)]
+        elif k in (F.RT_KIND_TRANSLATE, F.RT_KIND_ROTATE_Y, F.RT_KIND_ZOOM):
+            todo.append(d.xforms[i].child)
+        elif k == F.RT_KIND_MEDIUM:
+            todo.append(d.media[i].boundary)
+    return kinds, F.RT_KIND_NODE in kinds
+
+
+def check_counters(st, st_copy, words, n_samples, d):
+    """The counters of a flagged call against the copy's: what the definition does, and no more than the copy does."""
+    assert st.paths == st.rays == n_samples
+    assert st.rng_draws == words                            # the cameras' words only
+    got, ref = list(st.prim_tests), list(st_copy.prim_tests)
+    assert got[F.RT_KIND_MEDIUM] == 0
+    kinds, nodes_below = boundary_contents(d)
+    for k in range(len(got)):
+        assert got[k] <= ref[k], (F.KIND_NAMES[k] if k < len(F.KIND_NAMES) else k, got[k], ref[k])
+        if k != F.RT_KIND_MEDIUM and k not in kinds:
+            assert got[k] == ref[k], (F.KIND_NAMES[k] if k < len(F.KIND_NAMES) else k, got[k], ref[k])
+    assert st.node_visits <= st_copy.node_visits
+    if not nodes_below:
+        assert st.node_visits == st_copy.node_visits
+    assert st.light_pdf_tests == 0 and st.passes == 0 and st.pool_slots == 0 and st.partial_bytes == 0 and st.spp_chunk == 0
+    assert st.trace_ms == 0 and st.shade_ms == 0 and st.ms > 0
+
+
+# ---- 1. against the oracle on the looked-through copy -----------------------------------------------------------------------
+@pytest.mark.parametrize("which", CASES)
+def test_flagged_rows_match_the_oracle_on_the_copy(rt, O, which):
+    keep, d, cam, bg = case(rt, which)
+    p = rt.make_params(W0, H0, SPP0, 50, bg, seed=2022)
+    rows = rt.shuffled_rows(H0, 2022)
+    dev = rt.DeviceScene(d)
+    ref, st_copy, seen, words = S.oracle_surface_features(O, d, cam, p, rows)
+    got, st = dev.features(cam, p, rows, want_stats=True, surfaces=True)             # the counter instance
+    assert got.shape == (H0, W0) and got.dtype == F.FEATURE_DTYPE
+    assert_same_bits(got.reshape(-1), ref, which)
+    check_counters(st, st_copy, words, W0 * H0 * SPP0, d)
+    assert_same_bits(dev.features(cam, p, rows, surfaces=True).reshape(-1), ref, "plain instance")
+    assert d.n_media > 0 and not any(k[0] == F.RT_MAT_ISOTROPIC for k in seen.kinds)
+    plain = dev.features(cam, p, rows)
+    differ = np.any(plain.view(np.uint64).reshape(-1, 8) != got.view(np.uint64).reshape(-1, 8), axis=1).sum()
+    assert differ > 0, "the view never looked at a medium"
+    if which == "medium root":
+        miss = np.zeros(1, dtype=F.FEATURE_DTYPE)
+        miss["albedo"] = tuple((0.0 + c + c) + c for c in bg)               # 0 + bg + bg + bg, in sample order (SPP0 == 3)
+        assert (got.view(np.uint64).reshape(-1, 8) == miss.view(np.uint64)).all() and (plain["hits"] > 0).any()
+        assert st.node_visits == 0 and sum(st.prim_tests) == 0
+    if which == "lens and shutter":
+        assert words > 5 * W0 * H0 * SPP0                    # two jitter words, at least two lens words, the shutter's
+    if which == "list boundary":
+        shared = [m for m in seen.mats if d.materials[m].kind == F.RT_MAT_DIELECTRIC]
+        assert shared, "the sphere that is also a boundary was never hit through its own reference"
+    dev.close()
+
+
+@pytest.mark.parametrize("shape", ["whole", "mid", "large"])
+def test_flagged_kernel_shapes_match_the_oracle(rt, O, shape):
+    """The LDS-prefix instance and the 30- and 64-entry ones on scenes with a medium whose boundary lies under two movers. (The
+    22-entry instance is the 30-entry one's code with another stack size; its media-free case is below.)"""
+    d, cam, p0, rows = TS.make_scene(7, shape, 1)
+    dev = rt.DeviceScene(d)
+    p = F.rt_params.from_buffer_copy(p0)
+    p.spp = 2
+    rows = rows[:12]
+    ref, st_copy, seen, words = S.oracle_surface_features(O, d, cam, p, rows)
+    got, st = dev.features(cam, p, rows, want_stats=True, surfaces=True)
+    assert_same_bits(got.reshape(-1), ref, shape)
+    check_counters(st, st_copy, words, len(rows) * p.width * p.spp, d)
+    assert_same_bits(dev.features(cam, p, rows, surfaces=True).reshape(-1), ref, "plain instance")
+    need = dev.info()["stack_need"]
+    assert {"whole": need <= TS.STACK_TINY, "mid": TS.STACK_SMALL < need <= TS.STACK_MID, "large": need > TS.STACK_MID}[shape]
+    dev.close()
+
+
+# ---- 2. nothing changes without media -----------------------------------------------------------------------------------------
+def same_stats(a, b):
+    da, db = a.as_dict(), b.as_dict()
+    for k in ("ms", "trace_ms", "shade_ms"):
+        da.pop(k, None), db.pop(k, None)
+    return da == db
+
+
+def flag_changes_nothing(dev, cam, p, rows, what):
+    plain, st0 = dev.features(cam, p, rows, want_stats=True)
+    got, st1 = dev.features(cam, p, rows, want_stats=True, surfaces=True)
+    assert_same_bits(got, plain, what)
+    assert same_stats(st0, st1), (what, st0.as_dict(), st1.as_dict())
+    assert_same_bits(dev.features(cam, p, rows, surfaces=True), plain, (what, "plain instance"))
+    return plain
+
+
+@pytest.mark.parametrize("name", MEDIA_FREE)
+def test_flag_changes_nothing_on_media_free_builders(rt, name):
+    s = rt.HostScene(name, seed=2022)
+    assert s.desc.n_media == 0
+    cam, bg = s.default_view(W0 / H0)
+    dev = rt.DeviceScene(s.desc)
+    got = flag_changes_nothing(dev, cam, rt.make_params(W0, H0, SPP0, 50, bg, seed=2022), rt.shuffled_rows(H0, 2022), name)
+    assert got["hits"].sum() > 100
+    for W, H in ((1, 8), (8, 1), (1, 1)):                   # the NaN pattern of images one pixel wide or high
+        one = flag_changes_nothing(dev, cam, rt.make_params(W, H, SPP0, 50, (0.1, 0.2, 0.3), seed=2), np.arange(H, dtype=np.uint32), (name, W, H))
+        if name == "cornell_box":
+            assert np.isnan(one.view(np.float64)).any() or (one["hits"] == 0).any()
+    dev.close()
+
+
+@pytest.mark.parametrize("need, entries", [(10, 16), (20, 22), (27, 30), (48, 64)])
+def test_flag_changes_nothing_on_every_kernel_shape(rt, need, entries):
+    """One media-free scene per trav_dispatch shape: the LDS-prefix instance and the three deep-stack ones."""
+    d, cam, p, rows = TS.stack_need_scene(need)
+    dev = rt.DeviceScene(d)
+    got_need = dev.info()["stack_need"]
+    assert [e for e in (TS.STACK_TINY, TS.STACK_SMALL, TS.STACK_MID, TS.STACK_LARGE) if got_need <= e][0] == entries
+    flag_changes_nothing(dev, cam, p, rows, need)
+    ids = shuffled_ids_with_repeats(p.width * p.height, seed=need)[:500]
+    a, st0 = dev.features_pixels(cam, p, ids, want_stats=True)
+    b, st1 = dev.features_pixels(cam, p, ids, want_stats=True, surfaces=True)
+    assert_same_bits(a, b, "pixel list")
+    assert same_stats(st0, st1)
+    assert_same_bits(dev.features_pixels(cam, p, ids, surfaces=True), a, "pixel list, plain instance")
+    dev.close()
+
+
+# ---- 3. the pixel-list form ------------------------------------------------------------------------------------------------
+def test_flagged_pixel_lists_entry_by_entry(rt, O):
+    W = H = 16
+    s = rt.HostScene("cornell_smoke", seed=2022)
+    cam, bg = s.default_view(1.0)
+    dev = rt.DeviceScene(s.desc)
+    p = rt.make_params(W, H, SPP0, 50, bg, seed=6, n_frames=2)
+    whole = dev.features(cam, p, all_rows(H, 2), surfaces=True).reshape(-1)
+    assert np.any(whole.view(np.uint64) != dev.features(cam, p, all_rows(H, 2)).reshape(-1).view(np.uint64))
+    ids = shuffled_ids_with_repeats(2 * W * H, seed=4)
+    got, st = dev.features_pixels(cam, p, ids, want_stats=True, surfaces=True)
+    assert_same_bits(got, whole[ids], "counter instance")
+    assert_same_bits(dev.features_pixels(cam, p, ids, surfaces=True), whole[ids], "plain instance")
+    with S.media_looked_through(s.desc):
+        ref, st_copy, seen = oracle_ids(O, s.desc, cam, p, ids[:300])
+    assert_same_bits(got[:300], ref, "the oracle on the copy")
+    got300, st300 = dev.features_pixels(cam, p, ids[:300], want_stats=True, surfaces=True)
+    check_counters(st300, st_copy, S.camera_words(seen), 300 * SPP0, s.desc)
+    g = np.random.default_rng(9)
+    for n in (1, 63, 64, 65):
+        some = g.integers(0, 2 * W * H, n).astype(np.uint64)
+        some[n // 2] = some[0]                              # a repeat
+        out = dev.features_pixels(cam, p, some, surfaces=True)
+        assert_same_bits(out, whole[some], "length %d" % n)
+        perm = g.permutation(n)
+        assert_same_bits(dev.features_pixels(cam, p, some[perm], surfaces=True), out[perm], "permutation of length %d" % n)
+    # one entry more than the persistent grid has lanes
+    p1 = rt.make_params(W, H, 1, 50, bg, seed=6, n_frames=2)
+    whole1 = dev.features(cam, p1, all_rows(H, 2), surfaces=True).reshape(-1)
+    n = dev.info()["grid_blocks"] * 1024 + 1
+    assert 1024 < n < (1 << 24)
+    many = (np.arange(n, dtype=np.uint64) * np.uint64(5)) % np.uint64(2 * W * H)
+    got, st = dev.features_pixels(cam, p1, many, want_stats=True, surfaces=True)
+    assert st.paths == st.rays == n and st.prim_tests[F.RT_KIND_MEDIUM] == 0
+    assert_same_bits(got, whole1[many], "past the grid's lanes")
+    dev.close()
+
+
+# ---- 4. the device forms ---------------------------------------------------------------------------------------------------
+def test_flagged_device_forms_on_a_stream(rt):
+    import torch
+    W, H = 40, 24
+    s = rt.HostScene("final_scene", seed=2022)
+    cam, bg = s.default_view(W / H)
+    p = rt.make_params(W, H, SPP0, 50, bg, seed=8, n_frames=2)
+    rows = rt.shuffled_rows(H, 3)
+    dev = rt.DeviceScene(s.desc)
+    host = dev.features(cam, p, rows, surfaces=True)
+    assert np.any(host.view(np.uint64) != dev.features(cam, p, rows).view(np.uint64))
+    stream = torch.cuda.Stream()
+    d_rows = torch.from_numpy(rows.view(np.int32)).cuda()
+    d_out = torch.full((H * W * 8 + 2,), float("nan"), dtype=torch.float64, device="cuda")
+    torch.cuda.synchronize()
+    dev.features_device(cam, p, d_rows.data_ptr(), H, d_out.data_ptr(), stream.cuda_stream, surfaces=True)
+    stream.synchronize()
+    out = d_out.cpu().numpy()
+    assert_same_bits(out[: H * W * 8].view(F.FEATURE_DTYPE), host.reshape(-1))
+    assert np.isnan(out[H * W * 8:]).all()
+    st = F.rt_stats()
+    d_out.fill_(float("nan"))
+    torch.cuda.synchronize()
+    dev.features_device(cam, p, d_rows.data_ptr(), H, d_out.data_ptr(), stream.cuda_stream, stats=st, surfaces=True)
+    assert_same_bits(d_out.cpu().numpy()[: H * W * 8].view(F.FEATURE_DTYPE), host.reshape(-1))
+    assert st.paths == st.rays == W * H * SPP0 and st.prim_tests[F.RT_KIND_MEDIUM] == 0 and st.node_visits > st.rays
+    # the pixel list
+    ids = shuffled_ids_with_repeats(2 * W * H, seed=2)[:777]
+    want = dev.features_pixels(cam, p, ids, surfaces=True)
+    d_ids = torch.from_numpy(ids.view(np.int64)).cuda()
+    poison = np.random.default_rng(6).integers(1, 1 << 62, 777 * 8).astype(np.int64)
+    d_pix = torch.from_numpy(poison).cuda()
+    bad = ids.copy()
+    bad[400] = 2 * W * H
+    d_bad = torch.from_numpy(bad.view(np.int64)).cuda()
+    torch.cuda.synchronize()
+    with pytest.raises(rt.RtError) as e:                    # a refused id leaves the output untouched
+        dev.features_pixels_device(cam, p, d_bad.data_ptr(), 777, d_pix.data_ptr(), stream.cuda_stream, surfaces=True)
+    assert e.value.code == F.RT_ERR_INVALID and "pixel id out of range" in str(e.value)
+    torch.cuda.synchronize()
+    assert np.array_equal(d_pix.cpu().numpy(), poison)
+    dev.features_pixels_device(cam, p, d_ids.data_ptr(), 777, d_pix.data_ptr(), stream.cuda_stream, surfaces=True)
+    stream.synchronize()
+    assert_same_bits(d_pix.cpu().numpy().view(np.float64).view(F.FEATURE_DTYPE), want)
+    st = F.rt_stats()
+    dev.features_pixels_device(cam, p, d_ids.data_ptr(), 777, d_pix.data_ptr(), stream.cuda_stream, stats=st, surfaces=True)
+    assert_same_bits(d_pix.cpu().numpy().view(np.float64).view(F.FEATURE_DTYPE), want)
+    assert st.paths == st.rays == 777 * SPP0 and st.prim_tests[F.RT_KIND_MEDIUM] == 0
+    dev.close()
+
+
+# ---- 5. what still refuses the bit -------------------------------------------------------------------------------------------
+def test_refusals(rt):
+    import torch
+    L = rt.lib()
+    err = lambda: L.rt_last_error().decode()
+    s = rt.HostScene("cornell_box", seed=2022)
+    cam, bg = s.default_view(1.0)
+    dev = rt.DeviceScene(s.desc)
+    W = H = 8
+    # rt_radiance
+    rays = rt.radiance_rays(np.zeros((4, 3)), np.tile([0.0, 0.0, 1.0], (4, 1)))
+    out3 = np.zeros((4, 3))
+    for flags in (F.RT_FLAG_SURFACES, F.RT_FLAG_SURFACES | F.RT_FLAG_COUNTERS):
+        rp = rt.radiance_params(1, bg, flags=flags)
+        assert L.rt_radiance(dev._h, rays.ctypes.data, 4, C.byref(rp), out3.ctypes.data, None) == F.RT_ERR_INVALID and "flag bits" in err()
+    # rt_render_pixels
+    ids = np.arange(4, dtype=np.uint64)
+    p = rt.make_params(W, H, 1, 5, bg, seed=1, flags=F.RT_FLAG_SURFACES)
+    p.n_rows, p.row_ids = 0, None
+    assert L.rt_render_pixels(dev._h, C.byref(cam), C.byref(p), ids.ctypes.data, 4, out3.ctypes.data, None) == F.RT_ERR_INVALID
+    assert "flag bits" in err()
+    # rt_intersect
+    q = rt.query_rays(np.zeros((4, 3)), np.tile([0.0, 0.0, 1.0], (4, 1)))
+    hits = np.zeros(4, dtype=F.HIT_DTYPE)
+    assert L.rt_intersect(dev._h, q.ctypes.data, 4, F.RT_FLAG_SURFACES, hits.ctypes.data, None) == F.RT_ERR_INVALID and "flag bits" in err()
+    # the feature calls: the bit with another one
+    rows = np.arange(H, dtype=np.uint32)
+    feat = np.zeros(W * H, dtype=F.FEATURE_DTYPE)
+    d_rows = torch.arange(H, dtype=torch.int32, device="cuda")
+    d_ids = torch.arange(4, dtype=torch.int64, device="cuda")
+    d_out = torch.full((W * H * 8,), 7.0, dtype=torch.float64, device="cuda")
+    torch.cuda.synchronize()
+    for bad in (F.RT_FLAG_SURFACES | F.RT_FLAG_KERNEL_TIMES, F.RT_FLAG_SURFACES | F.RT_FLAG_ANY_HIT, F.RT_FLAG_SURFACES | 0x20):
+        pf = rt.make_params(W, H, 1, 5, bg, seed=1, flags=bad)
+        pf.n_rows, pf.row_ids = H, rows.ctypes.data
+        assert L.rt_features(dev._h, C.byref(cam), C.byref(pf), feat.ctypes.data, None) == F.RT_ERR_INVALID and "flag bits" in err()
+        assert L.rt_features_pixels(dev._h, C.byref(cam), C.byref(pf), ids.ctypes.data, 4, feat.ctypes.data, None) == F.RT_ERR_INVALID
+        assert "flag bits" in err()
+        pf.row_ids = d_rows.data_ptr()
+        assert L.rt_features_device(dev._h, C.byref(cam), C.byref(pf), C.c_void_p(d_out.data_ptr()), None, None) == F.RT_ERR_INVALID
+        assert "flag bits" in err()
+        assert L.rt_features_pixels_device(dev._h, C.byref(cam), C.byref(pf), C.c_void_p(d_ids.data_ptr()), 4, C.c_void_p(d_out.data_ptr()),
+                                           None, None) == F.RT_ERR_INVALID and "flag bits" in err()
+    torch.cuda.synchronize()
+    assert bool((d_out == 7.0).all())
+    # and the accepted pair
+    got, st = dev.features(cam, rt.make_params(W, H, 1, 5, bg, seed=1), rows, want_stats=True, surfaces=True)
+    assert st.paths == W * H and st.node_visits > 0
+    dev.close()
+
+
+# ---- 6. render_adaptive ----------------------------------------------------------------------------------------------------
+def test_render_adaptive_with_surface_guides(rt):
+    W = H = 24
+    n = W * H
+    spp, total_spp, max_units = 4, 32, 4
+    s = rt.HostScene("cornell_smoke", seed=2022)
+    cam, bg = s.default_view(1.0)
+    dev = rt.DeviceScene(s.desc)
+    p = rt.make_params(W, H, spp, 50, bg, seed=2022)
+    run = lambda **kw: rt.render_adaptive(dev, cam, p, total_spp, rounds=2, max_units=max_units, want_state=True, guides="all", **kw)
+    eq = lambda a, b: np.array_equal(a.cpu().numpy().view(np.uint64), b.cpu().numpy().view(np.uint64))
+    out, counts, log, state = run(surfaces=True)
+    out2, counts2, log2, state2 = run(surfaces=True)
+    assert eq(out, out2) and eq(counts, counts2) and log == log2 and eq(state["feat_acc"], state2["feat_acc"]) and eq(state["feat"], state2["feat"])
+    p2 = rt.make_params(W, H, spp, 50, bg, seed=2022, n_frames=2)
+    want = dev.features(cam, p2, all_rows(H, 2), surfaces=True).view(np.float64).reshape(2, n, 8)
+    assert_same_bits(state["feat"].cpu().numpy(), want, "the initial records are the flagged rt_features'")
+    plain = run()
+    assert not eq(plain[3]["feat"], state["feat"])          # the smoke is in the view
+    assert_same_bits(plain[3]["feat"].cpu().numpy(), dev.features(cam, p2, all_rows(H, 2)).view(np.float64).reshape(2, n, 8))
+    # every record the rounds added is a flagged one too: no record anywhere holds a medium's hit
+    acc = state["feat_acc"].cpu().numpy()
+    assert sum(r["total"] for r in log) > 0 and np.all(acc[..., 7] >= want[..., 7])
+    dev.close()

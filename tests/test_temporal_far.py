@@ -1,0 +1,205 @@
+"""rt_temporal / rt_temporal_device with RT_TEMPORAL_FAR_MISSES against its numpy restatement (tests/temporal_far_ref.py), bit
+for bit, and the whole chain render -> flagged features -> far-miss temporal on cornell_smoke against the oracle pipeline.
+Every test here sets the flag: the parent refuses it."""
+import math
+
+import numpy as np
+import pytest
+
+from raytracer_2022_amd import _ffi as F
+
+import surface_ref as S
+import temporal_cases as T
+import temporal_far_ref as FR
+import temporal_ref as R
+from temporal_ref import assert_same_bits
+from test_surfaces_ref import far_cameras, more_misses
+from test_temporal import Device
+
+pytestmark = pytest.mark.gpu
+
+SIZES = [(7, 5), (64, 4), (65, 5), (1, 6)]                  # below one workgroup, exactly one, one column and one row past it, one pixel wide
+FLAGS = [dict(far_misses=True), dict(far_misses=True, demodulate=False)]
+
+
+@pytest.fixture(scope="module", autouse=True)
+def torch_first():
+    """Bring torch's HIP context up before the library's first call, as the other GPU test modules do."""
+    import torch
+    assert torch.cuda.is_available(), "gpu tests need a GPU: the HIP path has no fallback"
+    torch.zeros(1, device="cuda")
+
+
+def check(rt, s, f, cam, p, prev=None, prev_cam=None, rows=None, what=""):
+    got, state = rt.temporal(s, f, cam, p, prev=prev, prev_cam=prev_cam, row_ids=rows)
+    ref, ref_state = FR.restate(s, f, cam, p, prev, prev_cam, rows)
+    assert_same_bits(got, ref, what)
+    assert_same_bits(state, ref_state, (what, "state"))
+    return got, state
+
+
+def hostile_history(state, seed):
+    s = T.poisoned(state, seed)
+    H, W = s.shape
+    s["depth"][np.random.default_rng(seed + 1).random((H, W)) < 0.05] = -np.inf
+    s["depth"][np.random.default_rng(seed + 2).random((H, W)) < 0.05] = -0.0       # -0.0 == 0.0: an uncovered pixel
+    return s
+
+
+@pytest.mark.parametrize("flags", FLAGS, ids=["far", "far, no demodulation"])
+@pytest.mark.parametrize("cams", ["moved", "identical", "previous camera facing away", "panned", "tilted and moved"])
+@pytest.mark.parametrize("W, H", SIZES)
+def test_hostile_frames_chained(rt, W, H, cams, flags):
+    """Four frames on top of each other, the cameras alternating, many misses in every frame, the third frame's history
+    poisoned (NaN, +-inf, zero, -0.0 and negative depths)."""
+    cam, prev_cam = far_cameras(rt, W, H)[cams]
+    p = rt.temporal_params(W, H, 4, **flags)
+    state, far_taken = None, 0
+    for k in range(4):
+        s, f = T.frame(W, H, seed=W * 16 + H + k)
+        f = more_misses(f, 100 + k)
+        now, before = (cam, prev_cam) if k % 2 else (prev_cam, cam)
+        if k == 2:
+            state = hostile_history(state, W + H)
+        _, state = check(rt, s, f, now, p, state, before if k else None, what=(cams, "frame", k))
+        miss = ~(f["hits"] > 0)
+        assert (state["depth"][miss] == 0.0).all() and (state["normal"][miss] == 0.0).all()
+        far_taken += int((state["n"][miss] > 1.0).sum()) if k else 0
+    if cams in ("moved", "identical", "panned") and W * H > 30:
+        assert far_taken > 0, "no uncovered pixel ever took its history"
+    if W == 1:
+        assert far_taken == 0                                # sc is infinite: every pixel restarts
+
+
+@pytest.mark.parametrize("kw", [dict(tol_depth=math.inf, tol_normal=math.inf), dict(n_max=1.0), dict(w_min=1.0),
+                                dict(tol_depth=0.02, tol_normal=0.05, n_max=2.5, w_min=0.6, albedo_floor=0.3)],
+                         ids=["both tests off", "n_max 1", "w_min 1", "tight"])
+def test_switches_with_the_flag(rt, kw):
+    W, H = 65, 5
+    cam, prev_cam = far_cameras(rt, W, H)["panned"]
+    p = rt.temporal_params(W, H, 4, far_misses=True, **kw)
+    (s0, f0), (s1, f1) = T.frame(W, H, seed=1), T.frame(W, H, seed=2)
+    f0, f1 = more_misses(f0, 3), more_misses(f1, 4)
+    _, st0 = check(rt, s0, f0, prev_cam, p)
+    _, st1 = check(rt, s1, f1, cam, p, st0, prev_cam, what=kw)
+    check(rt, s1, f1, cam, p, hostile_history(st0, 5), prev_cam, what=(kw, "poisoned"))
+    assert (st1["n"] >= 1.0).all() and st1["n"].max() <= p.n_max
+
+
+def test_covered_pixels_are_what_they_were(rt):
+    """The flag leaves every covered pixel's output as it is without it, bit for bit."""
+    W, H = 65, 5
+    cam, prev_cam = far_cameras(rt, W, H)["tilted and moved"]
+    (s0, f0), (s1, f1) = T.frame(W, H, seed=7), T.frame(W, H, seed=8)
+    f0, f1 = more_misses(f0, 1), more_misses(f1, 2)
+    far, plain = rt.temporal_params(W, H, 4, far_misses=True), rt.temporal_params(W, H, 4)
+    _, st0 = rt.temporal(s0, f0, prev_cam, plain)
+    out_f, st_f = rt.temporal(s1, f1, cam, far, prev=st0, prev_cam=prev_cam)
+    out_p, st_p = rt.temporal(s1, f1, cam, plain, prev=st0, prev_cam=prev_cam)
+    covered = f1["hits"] > 0
+    assert_same_bits(out_f[covered], out_p[covered]), assert_same_bits(st_f[covered], st_p[covered])
+    assert ((st_f["n"] > 1.0) & ~covered).any() and not ((st_p["n"] > 1.0) & ~covered).any()
+
+
+def test_row_lists_and_the_device_form(rt):
+    import torch
+    W, H = 65, 5
+    cam, prev_cam = far_cameras(rt, W, H)["panned"]
+    p = rt.temporal_params(W, H, 4, far_misses=True)
+    (s0, f0), (s1, f1) = T.frame(W, H, seed=11, hostile=False), T.frame(W, H, seed=12)
+    f0, f1 = more_misses(f0, 5), more_misses(f1, 6)
+    _, st0 = FR.restate(s0, f0, prev_cam, p)
+    image_order, image_state = check(rt, s1, f1, cam, p, st0, prev_cam)
+    rows = np.array([3, 0, 4, 1, 2], dtype=np.uint32)
+    got, state = check(rt, s1[rows], f1[rows], cam, p, st0, prev_cam, rows=rows, what="row list")
+    assert_same_bits(got[np.argsort(rows)], image_order), assert_same_bits(state, image_state)
+    # the device form on a stream of the caller's, with the row list
+    stream = torch.cuda.Stream()
+    d = Device(rt, s1[rows], f1[rows], p, st0, fill=0xFF)
+    d_rows = torch.from_numpy(rows.view(np.int32)).cuda()
+    torch.cuda.synchronize()
+    d.call(cam, prev_cam, rows=d_rows, stream=stream.cuda_stream)
+    stream.synchronize()
+    out, st = d.results()
+    assert_same_bits(out, got, "device form"), assert_same_bits(st, image_state, "device form, state")
+    # a refused row list leaves both outputs untouched
+    d.out.fill_(7.0), d.state.fill_(7.0)
+    for fault, v in (("repeated", rows[1]), ("out of range", H)):
+        bad = rows.copy()
+        bad[3] = v
+        with pytest.raises(rt.RtError) as e:
+            rt.temporal(s1[rows], f1[rows], cam, p, prev=st0, prev_cam=prev_cam, row_ids=bad)
+        assert e.value.code == F.RT_ERR_INVALID and "not a permutation" in str(e.value), fault
+        d_bad = torch.from_numpy(bad.view(np.int32)).cuda()
+        torch.cuda.synchronize()
+        with pytest.raises(rt.RtError) as e:
+            d.call(cam, prev_cam, rows=d_bad, stream=stream.cuda_stream)
+        assert e.value.code == F.RT_ERR_INVALID and "not a permutation" in str(e.value), fault
+        torch.cuda.synchronize()
+        assert (d.out == 7.0).all() and (d.state == 7.0).all(), (fault, "an output was written")
+    d.call(cam, prev_cam, stream=stream.cuda_stream)        # and without rows on the same workspace: the buffers in image order
+    stream.synchronize()
+    assert_same_bits(d.results()[1], FR.restate(s1[rows], f1[rows], cam, p, st0, prev_cam)[1], "no rows after rows")
+
+
+def test_accepted_flag_masks(rt):
+    W, H = 7, 5
+    cam = T.camera(rt, W, H)
+    s, f = T.frame(W, H, seed=1, hostile=False)
+    for bits in (0, 1, 4, 5):
+        p = rt.temporal_params(W, H, 4)
+        p.flags = bits
+        assert rt.temporal_workspace_bytes(p) > 0
+        check(rt, s, f, cam, p, what=bits)
+    for bits in (2, 3, 6, 8, 0x80000004):
+        p = rt.temporal_params(W, H, 4)
+        p.flags = bits
+        assert rt.temporal_workspace_bytes(p) == 0
+        with pytest.raises(rt.RtError) as e:
+            rt.temporal(s, f, cam, p)
+        assert e.value.code == F.RT_ERR_INVALID and "flag" in str(e.value)
+
+
+# ---- end to end ----------------------------------------------------------------------------------------------------------------
+def test_render_surface_features_far_temporal_end_to_end(rt, O):
+    """cornell_smoke, the last 4 cameras of its path at 48 x 48 x 4 spp: render_device -> features_device(surfaces) ->
+    temporal_device(far misses) on one stream with torch buffers, against the oracle's renders, its features on the
+    looked-through copy and the restatement, bit for bit."""
+    import torch
+    name, step = R.HELD_OUT
+    K, W, H, spp = 4, R.PATH_W, R.PATH_H, R.PATH_SPP
+    rows = rt.shuffled_rows(H, 2022)
+    s = rt.HostScene(name, seed=2022)
+    cam0, bg = s.default_view(W / H)
+    cams = R.camera_path(cam0, step, K)
+    sums, feats = [], []
+    for k, c in enumerate(cams):
+        params = R.frame_params(rt, W, H, spp, bg, k)
+        sums.append(O.render_cpu(s.desc, c, params, rows, n_threads=4))
+        feats.append(S.oracle_surface_features(O, s.desc, c, params, rows)[0].reshape(H, W))
+    p = rt.temporal_params(W, H, spp, far_misses=True)
+    ref_out, ref_state, restarts = FR.accumulate(sums, feats, cams, p, rows)
+    plain_restarts = R.accumulate(sums, feats, cams, rt.temporal_params(W, H, spp), rows)[2]
+    print("restart share per frame: far misses %s, without %s" % (" ".join("%.2f" % r for r in restarts), " ".join("%.2f" % r for r in plain_restarts)))
+    assert all(a < b for a, b in zip(restarts, plain_restarts))
+    dev = rt.DeviceScene(s.desc)
+    stream = torch.cuda.Stream()
+    d_rows = torch.from_numpy(rows.view(np.int32)).cuda()
+    d_sum = torch.zeros((H, W, 3), dtype=torch.float64, device="cuda")
+    d_feat = torch.zeros(W * H * 8, dtype=torch.float64, device="cuda")
+    d_state = [torch.zeros(W * H * 8, dtype=torch.float64, device="cuda") for _ in range(2)]
+    d_ws = torch.zeros(rt.temporal_workspace_bytes(p), dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    for k in range(K):
+        params = R.frame_params(rt, W, H, spp, bg, k)
+        dev.render_device(cams[k], params, d_rows.data_ptr(), H, d_sum.data_ptr(), stream.cuda_stream)
+        dev.features_device(cams[k], params, d_rows.data_ptr(), H, d_feat.data_ptr(), stream.cuda_stream, surfaces=True)
+        rt.temporal_device(d_sum.data_ptr(), d_feat.data_ptr(), cams[k], p, d_state[k & 1].data_ptr(), d_sum.data_ptr(), d_ws.data_ptr(),
+                           d_prev_ptr=d_state[~k & 1].data_ptr() if k else None, prev_cam=cams[k - 1] if k else None,
+                           d_row_ids_ptr=d_rows.data_ptr(), stream_ptr=stream.cuda_stream)
+    stream.synchronize()
+    assert_same_bits(d_sum.cpu().numpy(), ref_out, name)
+    state = d_state[(K - 1) & 1].cpu().numpy().view(F.TEMPORAL_PIXEL_DTYPE).reshape(H, W)
+    assert_same_bits(state, ref_state, (name, "state"))
+    assert ((state["depth"] == 0.0) & (state["n"] > 1.5)).sum() > 0, "no pixel that misses kept its history"
+    dev.close()

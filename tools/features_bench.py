@@ -8,6 +8,11 @@ Per scene and spp, one JSON line: the 800x800 default view, primary rays (= widt
 call (HIP events around `steps` calls after `warmup`) and Mrays/s; the same for rt_intersect_device on the camera rays of
 the view at --query-spp, generated once on the host with the render's own keying (so they are the rays the feature call
 aims: the hits are compared as a by-product); and ms of rt_render_device (depth 50, spp_chunk 1) for the same view and spp.
+
+    python3 tools/features_bench.py --surfaces [--scenes final_scene,cornell_smoke,c2] [--spp 4,16] [--no-render]
+
+times the RT_FLAG_SURFACES call beside the plain one on the same view: three windows of each, alternating (plain, flagged, plain,
+...), reported as "features_ms_windows" / "surfaces_ms_windows"; the spread of the plain windows is what a difference is read against.
 """
 import argparse
 import ctypes as C
@@ -29,6 +34,7 @@ SCENES = {                       # label: (builder, param, assets)
     "c2": ("random_scene", 0, False),
     "c5": ("wwscene", 3, True),
     "s1e5": ("random_scene", 158, False),
+    "cornell_smoke": ("cornell_smoke", 0, False),
 }
 W = H = 800
 M64 = np.uint64(0xFFFFFFFFFFFFFFFF)
@@ -83,13 +89,14 @@ def timed(torch, stream, call, steps, warmup):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--scenes", default=",".join(SCENES))
+    ap.add_argument("--scenes", default="final_scene,c2,c5,s1e5")
     ap.add_argument("--spp", default="4,16")
     ap.add_argument("--query-spp", type=int, default=4)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--seed", type=int, default=2022)
     ap.add_argument("--no-render", action="store_true")
+    ap.add_argument("--surfaces", action="store_true", help="time the RT_FLAG_SURFACES call beside the plain one")
     a = ap.parse_args()
     import torch
     torch.zeros(1, device="cuda")
@@ -125,6 +132,15 @@ def main():
         for spp in [int(x) for x in a.spp.split(",")]:
             p = rt.make_params(W, H, spp, 50, bg, seed=a.seed, spp_chunk=1)
             f_ms = timed(torch, stream, lambda: dev.features_device(cam, p, d_rows.data_ptr(), H, d_feat.data_ptr(), stream.cuda_stream), a.steps, a.warmup)
+            extra = {}
+            if a.surfaces:
+                call = lambda flag: timed(torch, stream, lambda: dev.features_device(cam, p, d_rows.data_ptr(), H, d_feat.data_ptr(), stream.cuda_stream,
+                                                                                     surfaces=flag), a.steps, a.warmup)
+                windows = [(call(False), call(True)) for _ in range(3)]
+                plain_ms, surf_ms = [w[0] for w in windows], [w[1] for w in windows]
+                extra = {"features_ms_windows": [round(x, 3) for x in plain_ms], "surfaces_ms_windows": [round(x, 3) for x in surf_ms],
+                         "surfaces_over_plain": round(min(surf_ms) / min(plain_ms), 3),
+                         "plain_spread": round(max(plain_ms) / min(plain_ms) - 1.0, 3), "media": s.desc.n_media}
             r_ms = float("nan")
             if not a.no_render:
                 st = F.rt_stats()
@@ -137,7 +153,7 @@ def main():
                     ms.append(st.ms)
                 r_ms = float(np.median(ms))
             n = W * H * spp
-            print(json.dumps({"scene": label, "builder": name, "param": param, "spp": spp, "primary_rays": n,
+            print(json.dumps({**extra, "scene": label, "builder": name, "param": param, "spp": spp, "primary_rays": n,
                               "features_ms": round(f_ms, 3), "features_mrays_per_s": round(n / f_ms / 1e3, 1),
                               "query_spp": a.query_spp, "query_ms": round(q_ms, 3), "query_mrays_per_s": round(q_rate, 1),
                               "features_vs_query": round(n / f_ms / 1e3 / q_rate, 3), "render_ms": round(r_ms, 3),

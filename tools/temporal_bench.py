@@ -14,6 +14,9 @@ Then, per scene of --path-scenes, one JSON line for an 8-camera path at --mse-si
 scaled to the same shift in pixels per frame), each frame two halves of spp / 2 samples from ONE two-frame render and feature
 call: the display-value MSE against a --ref-spp render at the last camera of the last frame A + B, of the accumulation of the
 whole frames, of rt_denoise_dual on the last frame's halves and of rt_denoise_dual on the two accumulated halves.
+
+--surfaces: the timed calls take RT_FLAG_SURFACES records and RT_TEMPORAL_FAR_MISSES, and every path (default then: final_scene,
+cornell_smoke) is run twice, without and with the two flags ("surfaces": false / true in its line).
 """
 import argparse
 import json
@@ -66,13 +69,13 @@ def timing(a, torch):
     # the frame before, from the camera one step to the left, and its state
     dev.render_device(prev_cam, p, d_rows.data_ptr(), H, d_rgb0.data_ptr(), sp, st)
     dev.wait(sp)
-    dev.features_device(prev_cam, p, d_rows.data_ptr(), H, d_feat0.data_ptr(), sp)
-    tp = rt.temporal_params(W, H, a.spp)
+    dev.features_device(prev_cam, p, d_rows.data_ptr(), H, d_feat0.data_ptr(), sp, surfaces=a.surfaces)
+    tp = rt.temporal_params(W, H, a.spp, far_misses=a.surfaces)
     d_tws = torch.empty(rt.temporal_workspace_bytes(tp), dtype=torch.uint8, device="cuda")
     rt.temporal_device(d_rgb0.data_ptr(), d_feat0.data_ptr(), prev_cam, tp, d_state[0].data_ptr(), d_out.data_ptr(), d_tws.data_ptr(),
                        d_row_ids_ptr=d_rows.data_ptr(), stream_ptr=sp)
     # this frame
-    f_ms = timed(torch, stream, lambda: dev.features_device(cam, p, d_rows.data_ptr(), H, d_feat.data_ptr(), sp), a.steps, a.warmup)
+    f_ms = timed(torch, stream, lambda: dev.features_device(cam, p, d_rows.data_ptr(), H, d_feat.data_ptr(), sp, surfaces=a.surfaces), a.steps, a.warmup)
     ms = []
     for _ in range(4):
         dev.render_device(cam, p, d_rows.data_ptr(), H, d_rgb.data_ptr(), sp, st)
@@ -97,7 +100,7 @@ def timing(a, torch):
     rows_ms = timed(torch, stream, lambda: temporal(d_rows.data_ptr()), a.steps, a.warmup)
     stream.synchronize()
     state = d_state[1].cpu().numpy().view(F.TEMPORAL_PIXEL_DTYPE)
-    print(json.dumps({"scene": a.scene, "size": "%dx%d" % (W, H), "spp": a.spp, "render_ms": round(r_ms, 3), "features_ms": round(f_ms, 3),
+    print(json.dumps({"scene": a.scene, "surfaces": a.surfaces, "size": "%dx%d" % (W, H), "spp": a.spp, "render_ms": round(r_ms, 3), "features_ms": round(f_ms, 3),
                       "denoise_ms": [round(x, 4) for x in s_ms], "denoise_dual_ms": [round(x, 4) for x in d_ms],
                       "temporal_ms": [round(x, 4) for x in t_ms], "temporal_ms_first_frame": round(first_ms, 4),
                       "temporal_ms_with_row_list": round(rows_ms, 4), "temporal_vs_denoise": round(min(t_ms) / min(s_ms), 3),
@@ -108,7 +111,7 @@ def timing(a, torch):
     dev.close()
 
 
-def path_mse(a, name):
+def path_mse(a, name, surfaces=False):
     S, K, half = a.mse_size, R.PATH_K, a.spp // 2
     s = rt.HostScene(name, seed=2022, assets_dir=ASSETS if os.path.isdir(ASSETS) else None)
     dev = rt.DeviceScene(s.desc)
@@ -117,11 +120,11 @@ def path_mse(a, name):
     rows = np.arange(S, dtype=np.uint32)
     rows2 = rt.two_frame_rows(rows, S)
     target = R.display(dev.render(cam, rt.make_params(S, S, a.ref_spp, 50, bg, seed=7, spp_chunk=1), rows), a.ref_spp)
-    tp_full, tp_half = rt.temporal_params(S, S, 2 * half), rt.temporal_params(S, S, half)
+    tp_full, tp_half = rt.temporal_params(S, S, 2 * half, far_misses=surfaces), rt.temporal_params(S, S, half, far_misses=surfaces)
     full = st_a = st_b = acc = acc_a = acc_b = None
     for k in range(K):
         p2 = rt.make_params(S, S, half, 50, bg, seed=a.seed + k, n_frames=2, spp_chunk=1)
-        sums, feat = dev.render(cams[k], p2, rows2), dev.features(cams[k], p2, rows2)
+        sums, feat = dev.render(cams[k], p2, rows2), dev.features(cams[k], p2, rows2, surfaces=surfaces)
         sa, sb, fa, fb = sums[:S], sums[S:], feat[:S], feat[S:]
         before = cams[k - 1] if k else None
         acc, full = rt.temporal(sa + sb, add_features(fa, fb), cams[k], tp_full, prev=full, prev_cam=before)
@@ -132,7 +135,7 @@ def path_mse(a, name):
     dual_acc = rt.denoise_dual(acc_a, acc_b, fa, fb, dd)
     m = lambda img: R.mse(img, 2 * half, target)
     m_last, m_acc, m_dual, m_dual_acc = m(sa + sb), m(acc), m(dual_last), m(dual_acc)
-    print(json.dumps({"path": name, "size": "%dx%d" % (S, S), "cameras": K, "spp": "2 x %d" % half, "ref_spp": a.ref_spp,
+    print(json.dumps({"path": name, "surfaces": surfaces, "size": "%dx%d" % (S, S), "cameras": K, "spp": "2 x %d" % half, "ref_spp": a.ref_spp,
                       "mse_last_frame": round(m_last, 6), "mse_accumulated": round(m_acc, 6), "accumulated_over_last": round(m_acc / m_last, 3),
                       "mse_dual_last_frame": round(m_dual, 6), "mse_dual_accumulated_halves": round(m_dual_acc, 6),
                       "dual_accumulated_over_dual_last": round(m_dual_acc / m_dual, 3),
@@ -150,13 +153,18 @@ def main():
     ap.add_argument("--seed", type=int, default=2022)
     ap.add_argument("--mse-size", type=int, default=200)
     ap.add_argument("--ref-spp", type=int, default=512)
-    ap.add_argument("--path-scenes", default="cornell_box,final_scene")
+    ap.add_argument("--path-scenes", default=None)
+    ap.add_argument("--surfaces", action="store_true", help="RT_FLAG_SURFACES records and RT_TEMPORAL_FAR_MISSES (see above)")
     a = ap.parse_args()
+    if a.path_scenes is None:
+        a.path_scenes = "final_scene,cornell_smoke" if a.surfaces else "cornell_box,final_scene"
     import torch
     torch.zeros(1, device="cuda")
     timing(a, torch)
     for name in [x for x in a.path_scenes.split(",") if x]:
         path_mse(a, name)
+        if a.surfaces:
+            path_mse(a, name, surfaces=True)
 
 
 if __name__ == "__main__":

@@ -13,6 +13,13 @@ with its aperture, final_scene — of 8 cameras on a line at 48 x 48, 4 spp per 
 as a ratio to the MSE of the last frame alone. The grid point with the smallest sum of the three ratios is the package's
 TEMPORAL_DEFAULTS; the same numbers at that point for one path the grid never saw close the log, with the fraction of pixels
 that restart per frame (with both tests off for comparison: what the geometry alone loses).
+
+    python3 tools/temporal_grid.py --media > profiles/temporal_media_grid.log
+
+prints another table instead, at TEMPORAL_DEFAULTS and with both tests off, for cornell_smoke, final_scene, cornell_box and
+random_scene: the ratio and the restart share under (1) first-hit records, (2) RT_FLAG_SURFACES records — the oracle's
+composition on a copy of the scene whose media never answer (tests/surface_ref.py) — and (3) surface records with
+RT_TEMPORAL_FAR_MISSES (tests/temporal_far_ref.py's restatement).
 """
 import itertools
 import math
@@ -26,6 +33,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import raytracer_2022_amd as rt  # noqa: E402
 from oracle import oracle_ffi as O  # noqa: E402
 import temporal_ref as R  # noqa: E402
+import surface_ref as S  # noqa: E402
+import temporal_far_ref as FR  # noqa: E402
 
 TOL_DEPTH, TOL_NORMAL, N_MAX, W_MIN = (0.02, 0.05, 0.1, 0.2), (0.05, 0.1, 0.3), (8.0, 32.0), 0.25
 THREADS = min(8, os.cpu_count() or 1)
@@ -76,5 +85,31 @@ def main():
                  off[2], " ".join("%.2f" % x for x in off[3])), flush=True)
 
 
+def media_table():
+    import numpy as np
+    W, H, spp = R.PATH_W, R.PATH_H, R.PATH_SPP
+    print("# tools/temporal_grid.py --media: CPU oracle renders (%d cameras, %dx%d, %d spp, seed %d + frame; target %d spp, seed %d), numpy restatement"
+          % (R.PATH_K, W, H, spp, R.SEED, R.REF_SPP, R.REF_SEED))
+    print("# per cell: mse_accumulated / mse_last, then the restarted share of frames 1 .. 7; columns: first-hit records | surface records"
+          " (RT_FLAG_SURFACES) | surface records and RT_TEMPORAL_FAR_MISSES")
+    steps = dict(R.PATH_STEP, **{R.HELD_OUT[0]: R.HELD_OUT[1]})
+    rows = np.arange(H, dtype=np.uint32)
+    for name in ("cornell_smoke", "final_scene", "cornell_box", "random_scene"):
+        s, bg, cams, sums, feats = R.oracle_path(rt, O, name, steps[name], threads=THREADS)
+        surf = [S.oracle_surface_features(O, s.desc, c, R.frame_params(rt, W, H, spp, bg, k), rows)[0].reshape(H, W) for k, c in enumerate(cams)]
+        same = all(np.array_equal(a.view(np.uint64), b.view(np.uint64)) for a, b in zip(feats, surf))
+        depths = np.concatenate([f["depth"].ravel() for f in surf])
+        target = R.oracle_target(rt, O, s, bg, cams[-1], threads=THREADS)
+        last = R.mse(sums[-1], spp, target)
+        print("path %-13s step %-5g media %d  mse_last %.6e  surface records %s, every depth finite: %s"
+              % (name, steps[name], s.desc.n_media, last, "bit-equal to first-hit records" if same else "differ", bool(np.isfinite(depths).all())), flush=True)
+        for label, kw in (("defaults ", {}), ("tests off", {"tol_depth": math.inf, "tol_normal": math.inf})):
+            cells = []
+            for records, far in ((feats, False), (surf, False), (surf, True)):
+                out, _, restarts = FR.accumulate(sums, records, cams, rt.temporal_params(W, H, spp, far_misses=far, **kw))
+                cells.append("%.4f  restarts %s" % (R.mse(out, spp, target) / last, " ".join("%.2f" % x for x in restarts)))
+            print("  %s  %s" % (label, "  |  ".join(cells)), flush=True)
+
+
 if __name__ == "__main__":
-    main()
+    media_table() if "--media" in sys.argv[1:] else main()
