@@ -76,11 +76,15 @@ def ref_index(ref):
 class LeafPath:
     """One way from the root to a leaf: `movers` [(kind, (p0, p1, p2))] outermost first, `flip` the parity of the FlipFace bits
     on the way (the leaf's own included), `leaf` the leaf's ref as its parent holds it, `nodes` [(node index, movers above it)]
-    for every NODE on the way, `medium` the index into Scene.media of the medium whose boundary this is, or None."""
-    __slots__ = ("movers", "flip", "leaf", "nodes", "medium")
+    for every NODE on the way, `medium` the index into Scene.media of the medium whose boundary this is, or None. `flips` is
+    the same parity level by level, len(movers) + 1 entries, outermost first: flips[j] is the parity of the bits on the refs
+    from below mover j - 1 down to mover j's own ref (the leaf's own for the last entry) — a mover's set_face_normal
+    recomputes the flag, so a record needs to know on which side of each mover a bit sits (tests/brute_records.py)."""
+    __slots__ = ("movers", "flip", "leaf", "nodes", "medium", "flips")
 
-    def __init__(self, movers, flip, leaf, nodes, medium):
+    def __init__(self, movers, flip, leaf, nodes, medium, flips=None):
         self.movers, self.flip, self.leaf, self.nodes, self.medium = movers, flip, leaf, nodes, medium
+        self.flips = (flip,) if flips is None else flips
 
     @property
     def zoomed(self):
@@ -108,33 +112,34 @@ class Scene:
             self.pools[name] = np.frombuffer(raw, dtype=dt)
         self.root = int(desc.root)
         self.paths, self.media = [], []
-        stack = [(self.root, (), False, (), None)]
+        stack = [(self.root, (), False, (), None, (), False)]
         while stack:                                             # (explicit: node chains run to 64 links and more)
-            ref, movers, flip, nodes, medium = stack.pop()
+            ref, movers, flip, nodes, medium, flips, seg = stack.pop()
             kind, idx = ref_kind(ref), ref_index(ref)
             flip = flip != bool(ref & FLIP)
+            seg = seg != bool(ref & FLIP)
             if kind == K_NODE:
                 n = self.pools["nodes"][idx]
                 below = nodes + ((idx, len(movers)),)
                 if n["right"] != n["left"]:                      # (a span-1 node holds one object twice: one path)
-                    stack.append((int(n["right"]), movers, flip, below, medium))
-                stack.append((int(n["left"]), movers, flip, below, medium))
+                    stack.append((int(n["right"]), movers, flip, below, medium, flips, seg))
+                stack.append((int(n["left"]), movers, flip, below, medium, flips, seg))
             elif kind == K_LIST:
                 l = self.pools["lists"][idx]
                 for r in self.pools["list_items"][int(l["first"]):int(l["first"]) + int(l["count"])][::-1]:
-                    stack.append((int(r), movers, flip, nodes, medium))
+                    stack.append((int(r), movers, flip, nodes, medium, flips, seg))
             elif K_TRANSLATE <= kind <= K_ZOOM:
                 x = self.pools["xforms"][idx]
                 assert int(x["kind"]) == kind
-                stack.append((int(x["child"]), movers + ((kind, tuple(float(v) for v in x["p"])),), flip, nodes, medium))
+                stack.append((int(x["child"]), movers + ((kind, tuple(float(v) for v in x["p"])),), flip, nodes, medium, flips + (seg,), False))
             elif kind == K_MEDIUM:
                 assert medium is None, "a medium inside a medium's boundary"
                 m = self.pools["media"][idx]
                 self.media.append(Medium(ref, idx, int(m["mat"]), nodes, len(movers)))
-                stack.append((int(m["boundary"]), movers, False, nodes, len(self.media) - 1))
+                stack.append((int(m["boundary"]), movers, False, nodes, len(self.media) - 1, (False,) * len(movers), False))
             else:
                 assert K_SPHERE <= kind <= K_RING, kind
-                p = LeafPath(movers, flip, ref, nodes, medium)
+                p = LeafPath(movers, flip, ref, nodes, medium, flips + (seg,))
                 (self.paths if medium is None else self.media[medium].boundary).append(p)
 
 

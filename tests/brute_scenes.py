@@ -7,7 +7,7 @@ import os
 import raytracer_2022_amd as rt
 
 import trace_scenes as T
-from query_scenes import composite_boundary_scene, every_kind_scene
+from query_scenes import composite_boundary_scene, every_kind_scene, mover_records_scene
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ASSETS_SMALL = os.path.join(HERE, "fixtures", "assets_small")
@@ -73,6 +73,48 @@ def oracle_results(O, desc, rays, ref=None):
                     rng_state=int(r["rng_state"]))
         hit[i], t[i], draws[i], front[i] = rec.hit, rec.t, rec.rng_draws, rec.front_face
     return hit, t, draws, front
+
+
+RECORD_FIELDS = ("hit", "t", "u", "v", "p", "normal", "front_face", "mat", "rng_draws")
+
+
+def oracle_records(O, desc, rays, ref=None):
+    """The whole rto_hit_record of every ray → {field: array}, the fields an rt_hit has (tests/brute_records.py: compare)."""
+    import numpy as np
+    n = len(rays)
+    got = {k: np.zeros(n, np.uint32) for k in ("hit", "front_face", "mat", "rng_draws")}
+    got.update({k: np.zeros(n) for k in ("t", "u", "v")}, p=np.zeros((n, 3)), normal=np.zeros((n, 3)))
+    ref = desc.root if ref is None else ref
+    for i, r in enumerate(rays):
+        rec = O.hit(desc, ref, r["origin"], r["direction"], tm=float(r["time"]), t_min=float(r["t_min"]), t_max=float(r["t_max"]),
+                    rng_state=int(r["rng_state"]))
+        for k in ("hit", "front_face", "mat", "rng_draws", "t", "u", "v"):
+            got[k][i] = getattr(rec, k)
+        got["p"][i], got["normal"][i] = rec.p[:], rec.normal[:]
+    return got
+
+
+def oracle_albedo(O, desc, got):
+    """The feature header's albedo of every record by the oracle's own composition (tests/test_features.py: oracle_sample):
+    rto_texture_value at the oracle's own u, v, p → (n, 3); zeros on a miss."""
+    import numpy as np
+    from raytracer_2022_amd import _ffi as F
+    out = np.zeros((len(got["hit"]), 3))
+    for i in np.flatnonzero(got["hit"]):
+        m = desc.materials[int(got["mat"][i])]
+        if m.kind == F.RT_MAT_METAL:
+            out[i] = m.albedo[:]
+        elif m.kind == F.RT_MAT_DIELECTRIC:
+            out[i] = 1.0
+        elif not (m.kind == F.RT_MAT_DIFFUSE_LIGHT and not got["front_face"][i]):
+            out[i] = O.texture_value(desc, m.tex, got["u"][i], got["v"][i], got["p"][i])
+    return out
+
+
+def mover_records():
+    b, d, cam = mover_records_scene(rt)
+    d._builder = b
+    return d, cam
 
 
 N_RAYS = 2000                                            # per scene: four families of 500

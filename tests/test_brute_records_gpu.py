@@ -1,0 +1,284 @@
+"""The device against the BVH-free record reference of tests/brute_records.py directly, not through the oracle:
+  rt_intersect          the whole rt_hit — p, normal, front_face, u, v, mat — of every compared ray;
+  rt_radiance           textures through the shade pass: on an emissive copy of a scene, depth 1, the radiance IS the texture
+                        value at the first hit's record (front face), black (back face) or the background (miss) — which also
+                        pins the winner and its face under movers, where tests/test_brute_hits_gpu.py accepts "colour or black";
+  rt_features*          albedo, normal, depth and hits of a frame, summed in sample order from the reference's records.
+tests/test_brute_hits_gpu.py holds hit / miss, t and prim; the classes and tolerances here are brute_records' (its docstring)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import brute_hits as B
+import brute_records as BR
+import brute_scenes as S
+import trace_scenes as T
+from raytracer_2022_amd import _ffi as F
+
+pytestmark = pytest.mark.gpu
+
+REF_ORDER = 1 << 15                                      # rt2022_debug.h: tuning bit 15, the reference's child order
+BACKGROUND = (0.25, 0.5, 0.75)
+NEW_CLASS_SHARE = 0.03
+GOLDEN, MASK64 = 0x9E3779B97F4A7C15, (1 << 64) - 1
+F64_MAX = float(np.finfo(np.float64).max)
+W, H, SPP = 48, 32, 2
+
+
+@pytest.fixture(scope="module", autouse=True)
+def torch_first():
+    """Bring torch's HIP context up before the library's first call, as the other GPU test modules do."""
+    import torch
+    assert torch.cuda.is_available(), "gpu tests need a GPU: the HIP path has no fallback"
+    torch.zeros(1, device="cuda")
+
+
+def scene_of(name):
+    if name == "stack-20":
+        return T.stack_need_scene(20)[:2]
+    if name == "mover_records":
+        return S.mover_records()
+    return S.make(name)
+
+
+def record_view(name, cam):
+    """final_scene's own view is 700 and more away from its cluster of spheres of radius 10: disc / half_b^2 = (r / distance)^2 is
+    under brute_hits' margin for nearly every such hit, and where every window is open to +inf (renders, features) they pass 3 %
+    of the camera rays. This view looks past the cluster at the textured spheres; the scene is the builder's."""
+    if name != "final_scene":
+        return cam
+    return S.rt.camera_new((150.0, 278.0, -500.0), (420.0, 200.0, 150.0), (0, 1, 0), 40.0, 1.0, 0.0, 10.0, float(cam.time0), float(cam.time1))
+
+
+def capped(classes, n, what):
+    """The rays (or pixels) the new classes leave out are at most 3 %: asserted from the reference alone."""
+    out = np.zeros(n, bool)
+    for v in classes.values():
+        out |= v
+    assert out.sum() <= NEW_CLASS_SHARE * n, (what, {k: int(v.sum()) for k, v in classes.items()})
+    return out
+
+
+# ---- rt_intersect: the whole rt_hit ---------------------------------------------------------------------------------------------
+INTERSECT_CASES = ["trace-feat7-whole", "trace-feat7-partial", "stack-20", "trace-feat7-mid", "trace-feat7-large", "trace-overflow",
+                   "every_kind", "cornell_smoke", "final_scene", "wwscene", "cornell_box", "earth", "two_perlin_spheres", "mover_records"]
+
+
+@pytest.mark.parametrize("name", INTERSECT_CASES)
+def test_intersect_records_against_brute_force(rt, name):
+    d, cam = scene_of(name)
+    sc = B.Scene(d)
+    dev = rt.DeviceScene(d)
+    compared = t_compared_hits = 0
+    worst = {f: 0.0 for f in BR.FIELDS}
+    floors = np.zeros(3, int)                                     # from the reference alone: under a mover, back behind a RotateY, flip below a mover
+    for family, rays in S.families(B, sc, cam, 300 + len(name)).items():
+        ans = B.solve(sc, rays["origin"], rays["direction"], rays["time"], rays["t_min"], rays["t_max"])
+        assert B.classify(sc, ans)[3].sum() <= S.AMBIGUOUS_SHARE * len(rays), (name, family)
+        R = BR.records(sc, rays, ans)
+        capped(BR.new_classes(sc, ans, R), len(rays), (name, family))                      # (before the device is called)
+        c1, c2, c3, amb = B.classify(sc, ans)
+        held = ans.hit & ~(c1 | c2 | c3 | amb | ans.tie) & ~R.face_ambiguous
+        floors += [(held & R.moved).sum(), (held & R.rotated & ~R.front).sum(), (held & R.flip_below).sum()]
+        q = np.ascontiguousarray(rays, dtype=F.QUERY_RAY_DTYPE)
+        got = dev.intersect(q)                                                           # the plain instance
+        counted, st = dev.intersect(q, want_stats=True)                                  # the counter instance
+        assert np.array_equal(got.view(np.uint8), counted.view(np.uint8)) and st.rays == len(q)
+        ta_t, _ = B.compare(sc, rays, got["hit"], got["t"], got["rng_draws"], got["prim"], ans=ans)
+        assert not ta_t.failures, (name, family, ta_t.failures[:5])
+        ta = BR.compare(sc, rays, ans, R, {k: got[k] for k in S.RECORD_FIELDS})
+        print(ta.line(name, family, "hip"))
+        assert not ta.failures, (name, family, ta.failures[:5])
+        assert ta.worst_ratio <= 1.0, (name, family, ta.worst)
+        t_compared_hits += int((~(c1 | c2 | c3 | amb | ans.tie) & (got["hit"] == 1)).sum())
+        compared += ta.compared + ta.media
+        worst = {f: max(worst[f], ta.worst[f]) for f in worst}
+    print("%-22s records held %d of the %d hits the t check holds; worst error / tolerance %s" % (
+        name, compared, t_compared_hits, " ".join("%s %.2e" % (f, worst[f]) for f in ("p", "normal", "u", "v"))))
+    assert compared >= 0.9 * t_compared_hits and compared >= 100
+    if name == "mover_records":
+        print("mover_records: %d winners under a mover, %d with front_face 0 behind a RotateY, %d with a flip below a mover" % tuple(floors))
+        assert floors[0] >= 500 and floors[1] >= 100 and floors[2] >= 100
+
+
+# ---- rt_radiance: textures through the shade pass ----------------------------------------------------------------------------------
+def own_colour(i):
+    return (2.0 + i, 0.5, 0.25)
+
+
+def emissive_copy(d):
+    """The desc's geometry with every surface a light that shows its own texture: a Lambertian, Isotropic or DiffuseLight
+    material becomes a DiffuseLight on its texture, a Metal or Dielectric a DiffuseLight on a new solid of the colour
+    own_colour(material index). ray_color at depth 1 then returns the texture value at the hit's (u, v, p) on a front face,
+    black on a back face and the background on a miss. n_lights = 0 (nothing is sampled at depth 1). A ConstantMedium's own
+    material must stay Isotropic; its neg_inv_density becomes -inf, so that hit_distance is +inf and the medium never answers
+    (it still draws): every ray's result is then decided by the solids alone, which is what the reference knows."""
+    out = F.rt_scene_desc.from_buffer_copy(d)
+    medium_mats = {d.media[i].mat for i in range(d.n_media)}
+    mats = [F.rt_material.from_buffer_copy(d.materials[i]) for i in range(d.n_materials)]
+    texs = [F.rt_texture.from_buffer_copy(d.textures[i]) for i in range(d.n_textures)]
+    for i, m in enumerate(mats):
+        if i in medium_mats:
+            continue
+        if m.kind in (F.RT_MAT_METAL, F.RT_MAT_DIELECTRIC):
+            texs.append(F.rt_texture(kind=F.RT_TEX_SOLID, color=F.d3(*own_colour(i))))
+            m.tex = len(texs) - 1
+        m.kind = F.RT_MAT_DIFFUSE_LIGHT
+    m_arr, t_arr = (F.rt_material * len(mats))(*mats), (F.rt_texture * len(texs))(*texs)
+    out.n_materials, out.materials = len(mats), C.cast(m_arr, C.POINTER(F.rt_material))
+    out.n_textures, out.textures = len(texs), C.cast(t_arr, C.POINTER(F.rt_texture))
+    media = (F.rt_medium * max(1, d.n_media))(*[F.rt_medium(boundary=d.media[i].boundary, mat=d.media[i].mat, neg_inv_density=-np.inf)
+                                                for i in range(d.n_media)])
+    out.media = C.cast(media, C.POINTER(F.rt_medium))
+    out.n_lights = 0
+    out._keep = [d, m_arr, t_arr, media]
+    return out
+
+
+TEXTURE_FLOORS = {"every_kind": {BR.TEX_CHECKER: 100, BR.TEX_IMAGE: 25}, "final_scene": {BR.TEX_SOLID: 100}, "earth": {BR.TEX_IMAGE: 100},
+                  "two_perlin_spheres": {BR.TEX_NOISE: 100}, "mover_records": {BR.TEX_CHECKER: 100, BR.TEX_NOISE: 100, BR.TEX_IMAGE: 100}}
+
+
+@pytest.mark.parametrize("name", list(TEXTURE_FLOORS))
+def test_textures_through_the_shade_pass(rt, name):
+    """rt_radiance at depth 1, spp 1 on the emissive copy, with the nearer child first and with the reference's child order.
+    Per ray that brute_hits compares (no tie) and no texture class leaves out: the background on a miss; on a hit black where
+    the reference says back face, texture_value_ref at the reference's record where it says front face — within the value's
+    tolerance for a p in error by tol_p — and either of the two only where the face is ambiguous."""
+    d0, cam = scene_of(name)
+    cam = record_view(name, cam)
+    d = emissive_copy(d0)
+    sc, sh = B.Scene(d), BR.Shading(d)
+    fams = S.families(B, sc, cam, 600 + len(name))
+    left_out, check = [], []
+    rays = np.concatenate(list(fams.values()))
+    rays["t_min"], rays["t_max"] = 0.001, np.inf
+    ans = B.solve(sc, rays["origin"], rays["direction"], rays["time"], 0.001, np.inf)
+    R = BR.records(sc, rays, ans)
+    want = BR.albedo_ref(sh, R.mat, np.ones(len(rays), bool), R.u, R.v, R.p)              # (every material is a light: the texture, front or not)
+    c1, c2, c3, amb = B.classify(sc, ans)
+    family = np.concatenate([np.full(len(r), i) for i, r in enumerate(fams.values())])
+    classes = BR.new_classes(sc, ans, R, want)
+    classes.pop("face")                                                                  # (not left out: "either" is asserted)
+    for i, fam in enumerate(fams):
+        assert amb[family == i].sum() <= S.AMBIGUOUS_SHARE * (family == i).sum(), (name, fam, int(amb[family == i].sum()))
+        capped({k: v[family == i] for k, v in classes.items()}, int((family == i).sum()), (name, fam))
+    skip = np.zeros(len(rays), bool)
+    for k, v in classes.items():
+        skip |= v & ~((k in ("pole", "uv-degenerate")) & (want.kind != BR.TEX_IMAGE))        # (u, v matter to an image alone)
+    check = ~(c1 | c2 | c3 | amb | ans.tie) & ~skip
+    assert check.sum() >= 0.9 * (~(c1 | c2 | c3 | amb | ans.tie)).sum()
+    front = check & ans.hit & R.front & ~R.face_ambiguous
+    print(name, "front-face rays by texture kind asked:", {k: int((front & (want.top == k)).sum()) for k in range(4)})
+    for kind, floor in TEXTURE_FLOORS[name].items():
+        assert (front & (want.top == kind)).sum() >= floor, (name, kind, int((front & (want.top == kind)).sum()))
+    value = np.where(ans.hit[:, None], np.asarray(want.value, dtype=np.float64), np.array(BACKGROUND)[None])
+    tol = np.where(ans.hit, want.tolerance(R.tol_p), 0.0)
+    rr = rt.radiance_rays(rays["origin"], rays["direction"], time=rays["time"], rng_state=rays["rng_state"])
+    dev = rt.DeviceScene(d)
+    for word in (T.TUNING, T.TUNING | REF_ORDER):
+        dev.set_tuning(word)
+        out = dev.radiance(rr, spp=1, background=BACKGROUND, t_min=0.001, max_depth=1)
+        ratio = BR._ratio(np.abs(B.LD(1) * out - np.where(ans.hit[:, None], want.value, B.LD(1) * np.array(BACKGROUND)[None])).max(1), tol)
+        same, black = ratio <= 1, (out == 0).all(1)
+        must_value = ~ans.hit | (R.front & ~R.face_ambiguous)
+        must_black = ans.hit & ~R.front & ~R.face_ambiguous
+        ok = np.where(must_value, same, np.where(must_black, black, same | black))
+        bad = np.flatnonzero(check & ~ok)
+        print("%-20s %-9s rays %5d compared %5d: value %5d (worst error / tolerance %.2e), black %5d, either %3d, background %5d" % (
+            name, "ref-order" if word & REF_ORDER else "ordered", len(rays), check.sum(), (check & must_value & ans.hit).sum(),
+            ratio[check & must_value & ans.hit & same].max(initial=0.0), (check & must_black).sum(), (check & ~must_value & ~must_black).sum(),
+            (check & ~ans.hit).sum()))
+        assert len(bad) == 0, (name, word, [(int(i), out[i].tolist(), value[i].tolist(), float(ans.t[i]), bool(R.front[i]), hex(int(ans.leaf[i])),
+                                             int(want.kind[i]), float(ratio[i])) for i in bad[:5]])
+
+
+# ---- rt_features and rt_features_pixels -----------------------------------------------------------------------------------------------
+def camera_rays(O, cam, p, frame=0):
+    """The camera rays of a frame by the oracle's composition rto_path_key -> rto_rng_f64 -> rto_get_ray (the first half of
+    tests/test_features.py: oracle_sample; camera code is not under test here) → rays (H, W, SPP) with the window and the
+    rng_state world.hit gets."""
+    L = O.lib()
+    rays = np.zeros((p.height, p.width, p.spp), dtype=B.RAY_DTYPE)
+    uv, ray = (C.c_double * 2)(), (C.c_double * 7)()
+    for py in range(p.height):
+        for px in range(p.width):
+            for s in range(p.spp):
+                key = L.rto_path_key(p.seed, frame, py * p.width + px, s)
+                L.rto_rng_f64(key, uv, 2)
+                u = float((np.float64(px) + np.float64(uv[0])) / np.float64(p.width - 1))
+                v = float((np.float64(py) + np.float64(uv[1])) / np.float64(p.height - 1))
+                draws = L.rto_get_ray(C.byref(cam), u, v, (key + 2 * GOLDEN) & MASK64, ray)
+                r = rays[py, px, s]
+                r["origin"], r["direction"], r["time"] = ray[0:3], ray[3:6], ray[6]
+                r["t_min"], r["t_max"], r["rng_state"] = p.t_min, F64_MAX, (key + (2 + draws) * GOLDEN) & MASK64
+    return rays
+
+
+def reference_features(sc, sh, rays, background):
+    """→ (want (H, W, 8) longdouble: albedo, normal, depth, hits summed in sample order; tol (H, W, 8); keep (H, W): no sample
+    of the pixel is left out), from the reference alone."""
+    shape = rays.shape
+    flat = rays.reshape(-1)
+    ans = B.solve(sc, flat["origin"], flat["direction"], flat["time"], flat["t_min"], flat["t_max"])
+    R = BR.records(sc, flat, ans)
+    alb = BR.albedo_ref(sh, R.mat, R.front, R.u, R.v, R.p)
+    c1, c2, c3, amb = B.classify(sc, ans)
+    light = np.array([int(sh.pools["materials"][int(m)]["kind"]) == BR.MAT_DIFFUSE_LIGHT for m in R.mat]) & ans.hit
+    reads_uv = ans.hit & (alb.kind == BR.TEX_IMAGE)
+    out = (c1 | c2 | c3 | amb | ans.tie | (ans.hit & R.face_ambiguous) | (ans.hit & alb.edge) | (reads_uv & (R.pole | R.uv_degenerate | (alb.seam & R.sphere))))
+    f = np.zeros((len(flat), 8), dtype=B.LD)
+    tol = np.zeros((len(flat), 8))
+    hit = ans.hit
+    f[:, 0:3] = np.where(hit[:, None], alb.value, B.LD(1) * np.array(background)[None])
+    f[:, 3:6] = np.where(hit[:, None], R.normal, 0)
+    f[:, 6] = np.where(hit, ans.t, 0)
+    f[:, 7] = hit
+    tol[:, 0:3] = np.where(hit, alb.tolerance(R.tol_p), 0.0)[:, None]
+    tol[:, 3:6] = np.where(hit, R.tol_n, 0.0)[:, None]
+    tol[:, 6] = np.where(hit, B.tolerance(ans, flat["direction"]), 0.0)
+    f, tol = f.reshape(shape + (8,)), tol.reshape(shape + (8,))
+    want = np.zeros(shape[:2] + (8,), dtype=B.LD)
+    for s in range(shape[2]):                                    # 0 + f_0 + f_1 + ..., each add within one f64 rounding
+        want = want + f[:, :, s]
+    tol = tol.sum(2) + shape[2] * 2.0 ** -52 * np.asarray(np.abs(want), dtype=np.float64)
+    return want, tol, ~out.reshape(shape).any(2), (light, hit)
+
+
+FEATURE_CASES = [("final_scene", True), ("cornell_smoke", True), ("every_kind", True), ("cornell_box", False), ("earth", False),
+                 ("two_perlin_spheres", False), ("mover_records", False)]
+
+
+def check_features(got, want, tol, keep, what):
+    flat = np.concatenate([got["albedo"], got["normal"], got["depth"][..., None], got["hits"][..., None]], axis=-1)
+    ratio = BR._ratio(np.abs(B.LD(1) * flat - want), tol)
+    bad = np.argwhere(keep[..., None] & (ratio > 1))
+    worst = [float(ratio[..., sl][keep].max()) for sl in (slice(0, 3), slice(3, 6), slice(6, 7), slice(7, 8))]
+    print("%-28s pixels %5d compared %5d; worst error / tolerance albedo %.2e normal %.2e depth %.2e hits %.2e" % ((what, keep.size, keep.sum()) + tuple(worst)))
+    assert len(bad) == 0, (what, [(tuple(int(x) for x in i), float(flat[tuple(i)]), float(want[tuple(i)]), float(tol[tuple(i)])) for i in bad[:5]])
+
+
+@pytest.mark.parametrize("name,surfaces", FEATURE_CASES, ids=[c[0] for c in FEATURE_CASES])
+def test_features_against_reference_records(rt, O, name, surfaces):
+    """rt_features of a 48 x 32 frame at spp 2 against records summed from the reference. With RT_FLAG_SURFACES a medium never
+    answers, so the reference's solids are the whole answer; without it the scenes have no medium. mover_records also runs
+    the pixel-list form on 200 shuffled ids."""
+    d, cam = scene_of(name)
+    cam = record_view(name, cam)
+    sc, sh = B.Scene(d), BR.Shading(d)
+    assert surfaces or not sc.media
+    p = rt.make_params(W, H, SPP, background=BACKGROUND, seed=77)
+    rays = camera_rays(O, cam, p)
+    want, tol, keep, _ = reference_features(sc, sh, rays, BACKGROUND)
+    assert (~keep).sum() <= NEW_CLASS_SHARE * keep.size, (name, int((~keep).sum()))            # (before the device is called)
+    assert want[..., 7][keep].sum() >= 0.2 * SPP * keep.sum(), "the view sees too little of the scene"
+    dev = rt.DeviceScene(d)
+    got = dev.features(cam, p, np.arange(H, dtype=np.uint32), surfaces=surfaces)
+    check_features(got, want, tol, keep, name + (" surfaces" if surfaces else ""))
+    if name == "mover_records":
+        ids = np.random.default_rng(11).permutation(W * H)[:200]
+        py, px = ids // W, ids % W
+        listed = dev.features_pixels(cam, p, rt.pixel_ids(0, py, px, W, H), surfaces=surfaces)
+        check_features(listed, want[py, px], tol[py, px], keep[py, px], name + " pixel list")
+        assert np.array_equal(listed.view(np.uint8), np.ascontiguousarray(got[py, px]).view(np.uint8))
