@@ -411,6 +411,9 @@ typedef struct rt_hit {               /* 96 B */
 #define RT_REF_NONE     0xFFFFFFFFu
 #define RT_FLAG_ANY_HIT 0x8u          /* rt_intersect*: stop at the first accepted candidate (see above) */
 #define RT_FLAG_SURFACES 0x10u        /* rt_features* / rt_features_pixels* only: look through every ConstantMedium (see there) */
+#define RT_FLAG_SPECULAR 0x40u        /* rt_features* / rt_features_pixels* only: follow the sample's path through glass and mirrors
+                                         (see there); 0x20 is not a flag */
+#define RT_FEATURE_SPECULAR_BOUNCES 8 /* RT_FLAG_SPECULAR: specular vertices a sample follows at the most */
 
 /* Host buffers; synchronous. stats may be NULL. */
 int rt_intersect(rt_scene *scene, const rt_query_ray *rays, uint64_t n_rays, uint32_t flags,
@@ -517,6 +520,35 @@ int rt_radiance_device(rt_scene *scene, const rt_radiance_ray *d_rays, uint64_t 
  * denoisers read these records, and a medium's drawn depth and (1, 0, 0) normal are noise to them. Participating media are
  * then reprojected and filtered by the surface behind them — wrong for dense smoke with parallax of its own.
  *
+ * RT_FLAG_SPECULAR (a flag bit older callers never set: the ABI version stays 3; all four feature calls take it, alone, with
+ * RT_FLAG_COUNTERS, with RT_FLAG_SURFACES or with both; every other call refuses it): the records of the first NON-SPECULAR
+ * vertex of the sample's own path, behind glass and mirrors. The sample is aimed as above (rng, two jitter draws, r_0 =
+ * get_ray(...)). Then, for k = 0, 1, ...: rec_k = world.hit(r_k, t_min, f64::MAX) on the root with the same rng continuing.
+ *   - A miss at k = 0 is the miss record above (background, zeros, hits 0). A miss at k > 0 ends the chain with the
+ *     terminal colour c = background and the normal rec_{k-1}.normal.
+ *   - A hit is FOLLOWED iff k < RT_FEATURE_SPECULAR_BOUNCES and its material is DIELECTRIC, or METAL with param == 0.0.
+ *     Then a_k is Material::scatter's attenuation — (1, 1, 1) for a Dielectric, the albedo for a Metal — and r_{k+1} is
+ *     scatter's specular ray with rng continuing (material/mod.rs:85-147): a Dielectric draws its one gen_range word and
+ *     keeps r_k.tm; a Metal draws random_in_unit_sphere although it is multiplied by a fuzz of 0, and its ray has tm = 0.0.
+ *   - Any other hit is the terminal vertex j: Lambertian, Isotropic, DiffuseLight, Metal with fuzz > 0, and whatever is
+ *     hit at k == RT_FEATURE_SPECULAR_BOUNCES. Its colour c is the albedo rule above on rec_j, the normal is rec_j.normal.
+ * The record: albedo = a_0 * (a_1 * ( ... * (a_{j-1} * c))), component-wise and innermost first — ray_color's own order,
+ * attenuation * ray_color(...), which matters for the bits once two metals are in a chain (a Dielectric's factor is exactly
+ * 1); normal as said; depth = rec_0.t and hits = 1, the primary-visibility values as without the flag, so coverage and the
+ * silhouette of the specular object stay what they were. Sums per pixel are 0 + f_0 + f_1 + ... in sample order as above; NaN
+ * where IEEE gives NaN. On a scene with no Dielectric and no fuzz-0 Metal the flag changes nothing, counters included. With
+ * RT_FLAG_SURFACES as well a ConstantMedium answers None on EVERY segment (the oracle's reference is then the same
+ * composition on the looked-through copy). The guides describe the path prefix the pixel's radiance came from, each sample's
+ * reflect / refract choice at a Dielectric included: on a scene that holds only specular surfaces, lights and background the
+ * flagged albedo of a sample whose chain ends within the cap IS ray_color of that sample, bit for bit. rt_stats under the
+ * flag: paths = n * spp; rays is the number of world.hit calls, counted on the device and filled only with
+ * RT_FLAG_COUNTERS (0 without); with counters node_visits and prim_tests[] sum over all segments and rng_draws is the
+ * camera's words plus every hit's plus every followed vertex's scatter words. What it is for: the denoisers (rt_denoise*,
+ * rt_denoise_dual*, render_adaptive's guides) — demodulation then divides by the albedo the radiance actually carries, and
+ * the edge-stopping terms see edges inside a reflection or a refraction. What it is NOT for: rt_temporal*. A mirror image
+ * does not reproject by the mirror's depth, and the normals now change with each sample's reflect / refract choice: the
+ * accumulation stays better served by first-hit or RT_FLAG_SURFACES records.
+ *
  * Each field of a pixel's record is 0 + f_0 + f_1 + ... + f_{spp-1}, added in sample order and NOT divided by spp, like a
  * render's sums (rt_tonemap_device / rt_write_color do not apply): hits / spp is coverage, depth / hits the mean depth over
  * the hits. Records come in row_ids order, n_rows * width of them. Every sum is the CPU oracle's composition rto_path_key
@@ -529,14 +561,14 @@ int rt_radiance_device(rt_scene *scene, const rt_radiance_ray *d_rays, uint64_t 
  *
  * Arguments: spp == 0 or n_rows == 0 is RT_OK (zeros or nothing written, no kernel). RT_ERR_INVALID with rt_last_error()
  * set, before any kernel: a null scene, cam or params; null rows or output with work to do; a flag bit other than
- * RT_FLAG_COUNTERS / RT_FLAG_SURFACES; a device output that is not 16-byte aligned or device rows that are not 4-byte aligned; width, height
+ * RT_FLAG_COUNTERS / RT_FLAG_SURFACES / RT_FLAG_SPECULAR; a device output that is not 16-byte aligned or device rows that are not 4-byte aligned; width, height
  * or n_frames equal to 0 (or cam->time0 >= cam->time1, as for a render); a row id >= height * n_frames (device rows are
  * checked by the small reduction kernel rt_render_device uses, behind one synchronisation of hip_stream before the
  * feature kernel is enqueued).
  *
  * rt_stats (may be NULL): paths = rays = n_rows * width * spp; with RT_FLAG_COUNTERS node_visits and prim_tests[] are the
  * sums of rto_hit's counters and rng_draws the camera's words (2 + what rto_get_ray returns) plus the hit's; ms is the
- * device time of the call; everything else is 0.
+ * device time of the call; everything else is 0. (RT_FLAG_SPECULAR: see there — rays counts every segment.)
  *
  * Independence: a call owns its scratch per (scene, stream) — a work counter, a counter block, two events — and uses
  * neither engine, so it works whichever is selected, never touches a render's pool, tape or pending stats, and may run on
@@ -568,13 +600,13 @@ int rt_features_device(rt_scene *scene, const rt_camera *cam, const rt_params *p
  * ENTRY through all its samples, and decodes the id by two 32-bit divisions where width * height * n_frames fits 32 bits,
  * by 64-bit ones otherwise.
  *
- * rt_params: used — width, height, spp, background, t_min, seed, n_frames, flags (RT_FLAG_SURFACES as for rt_features); IGNORED — n_rows, row_ids, max_depth,
+ * rt_params: used — width, height, spp, background, t_min, seed, n_frames, flags (RT_FLAG_SURFACES and RT_FLAG_SPECULAR as for rt_features); IGNORED — n_rows, row_ids, max_depth,
  * spp_chunk, progress_cb / progress_user.
  *
  * Arguments: n_entries == 0 is RT_OK; spp == 0 is RT_OK and writes zeros with no feature kernel. RT_ERR_INVALID with
  * rt_last_error() set, before any feature kernel: a null scene, cam or params; null ids or output with n_entries > 0;
  * width, height or n_frames equal to 0 (or height * n_frames above 2^32 - 1: the matching row id must exist);
- * cam->time0 >= cam->time1; a flag bit other than RT_FLAG_COUNTERS / RT_FLAG_SURFACES; device ids that are not 8-byte aligned or a device
+ * cam->time0 >= cam->time1; a flag bit other than RT_FLAG_COUNTERS / RT_FLAG_SURFACES / RT_FLAG_SPECULAR; device ids that are not 8-byte aligned or a device
  * output that is not 16-byte aligned; n_entries > 2^40; an id >= width * height * n_frames — host ids are checked on the
  * host, device ids by the counting kernel rt_render_pixels_device uses, behind one synchronisation of hip_stream BEFORE
  * the feature kernel is enqueued: a refused call leaves the output untouched.

@@ -27,6 +27,8 @@ RT_FLAG_KERNEL_TIMES = 0x2
 RT_FLAG_ASYNC = 0x4
 RT_FLAG_ANY_HIT = 0x8
 RT_FLAG_SURFACES = 0x10
+RT_FLAG_SPECULAR = 0x40
+RT_FEATURE_SPECULAR_BOUNCES = 8
 RT_REF_NONE = 0xFFFFFFFF
 RT_OK, RT_ERR_INVALID, RT_ERR_UNSUPPORTED, RT_ERR_DEVICE, RT_ERR_NOMEM = 0, -1, -2, -3, -4
 

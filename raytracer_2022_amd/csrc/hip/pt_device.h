@@ -275,11 +275,16 @@ struct FeatureArgs {
     unsigned long long *counter;       // pixels handed out so far (zeroed before launch)
     StatsDev *stats;                   // counter instances only
 };
-// `surfaces`: RT_FLAG_SURFACES, the instances that pop a medium leaf instead of entering it.
-hipError_t launch_features(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, bool surfaces, hipStream_t stream);
+// `surfaces`: RT_FLAG_SURFACES, the instances that pop a medium leaf instead of entering it. `specular`: RT_FLAG_SPECULAR, the
+// instances of pt_features_specular.hip that follow a sample through glass and mirrors (with counters they count their rays).
+hipError_t launch_features(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, bool surfaces, bool specular,
+                           hipStream_t stream);
 // The pixel source (rt_features_pixels*): args.pixel_ids and args.ids32 in place of row_ids and n_rows.
-hipError_t launch_features_pixels(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, bool surfaces,
+hipError_t launch_features_pixels(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, bool surfaces, bool specular,
                                   hipStream_t stream);
+// The RT_FLAG_SPECULAR instances (pt_features_specular.hip); `pixels`: the pixel source.
+hipError_t launch_features_specular(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, bool surfaces, bool pixels,
+                                    hipStream_t stream);
 
 // ---- edge-avoiding denoiser (pt_denoise.hip, rt_denoise*) ----------------------------
 // Where the pieces of the caller's workspace lie (byte offsets, each a multiple of 16) — the one place that knows.

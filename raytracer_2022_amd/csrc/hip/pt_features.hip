@@ -24,68 +24,21 @@
 // some medium's boundary is still reached through its own reference. Instances and not a uniform switch in FeatureArgs: with
 // the switch five of the sixteen unflagged instances spilled more (up to +8 bytes of scratch per lane); as instances, those
 // are compiled from the code they had and keep every register (profiles/features_surfaces_kernel_resources.txt).
+// RT_FLAG_SPECULAR: a kernel of its own, pt_features_specular.hip, around the same pieces (pt_features.hpp); nothing of it is
+// compiled into the instances here.
 // One lane per pixel means a few-pixel x huge-spp job balances poorly; the intended use is a whole frame at modest spp.
 // All arithmetic is f64 through rt_math.h with -ffp-contract=off, so every sum is the CPU oracle's composition bit for bit.
-#include "pt_traverse.hpp"
+#include "pt_features.hpp"
 
 namespace rt2022 {
 
 namespace {
 
-constexpr uint32_t kFHasPixel = 1u;    // lane flag: the lane carries a pixel (a sample of it is in flight)
-
-constexpr int kFeatRows = 0, kFeatPixels = 1;      // SRC: a row list, a list of (frame, pixel) ids
-
-struct FLane : TravLane {
-    uint32_t row, px;      // the pixel: entry of the row list, column (kFeatPixels: the low and the high word of the entry's index)
-    uint32_t smp;          // the sample in flight
-};
-
-// The camera ray of (row, px, sample) and the RNG behind it, as wf_shade's fresh-path code aims it (main.rs:144-149).
-template <int SRC>
-RT_DEV Ray f_camera(const FeatureArgs &a, uint32_t row, uint32_t px, uint32_t smp, Rng &rng) {
-    uint32_t frame, py;
-    if constexpr (SRC == kFeatPixels) {
-        // id = frame * (width * height) + py * width + px. Two 32-bit divisions where every id of the view fits 32 bits (a
-        // uniform test on kernel arguments: the host checked the ids against width * height * n_frames), else 64-bit ones.
-        const uint64_t id = a.pixel_ids[(uint64_t)row | ((uint64_t)px << 32)];
-        if (a.ids32) {
-            const uint32_t i = (uint32_t)id, ip = a.width * a.height;
-            frame = i / ip;
-            const uint32_t rem = i - frame * ip;
-            py = rem / a.width;
-            px = rem - py * a.width;
-        } else {
-            const uint64_t ip = (uint64_t)a.width * a.height, f = id / ip, rem = id - f * ip, y = rem / a.width;
-            frame = (uint32_t)f;
-            py = (uint32_t)y;
-            px = (uint32_t)(rem - y * a.width);
-        }
-    } else {
-        const uint32_t g = a.row_ids[row];
-        frame = g / a.height; py = g - frame * a.height;
-    }
-    rng = Rng(rtm::path_key(a.seed, frame, (uint64_t)py * a.width + px, smp));
-    const double rand_u = rng.gen_f64();
-    const double rand_v = rng.gen_f64();
-    const double u = ((double)px + rand_u) / (double)(a.width - 1);
-    const double v = ((double)py + rand_v) / (double)(a.height - 1);
-    return get_ray(a.cam, u, v, rng);
-}
+// (FLane, f_camera, f_albedo, f_add and f_take: pt_features.hpp, shared with the RT_FLAG_SPECULAR kernel)
 template <int SRC>
 RT_DEV Ray f_world(const FeatureArgs &a, const FLane &L) {
     Rng unused;
     return f_camera<SRC>(a, L.row, L.px, L.smp, unused);
-}
-
-// scatter's attenuation where the material scatters, emitted where it does not (material/mod.rs).
-RT_DEV Vec3 f_albedo(const SceneDev &s, const HitRec &rec) {
-    const rt_material &m = s.materials[rec.mat & kMatIndexMask];
-    const uint32_t kind = m.kind;
-    if (kind == RT_MAT_METAL) return ld3(m.albedo);
-    if (kind == RT_MAT_DIELECTRIC) return Vec3(1.0, 1.0, 1.0);
-    if (kind == RT_MAT_DIFFUSE_LIGHT && !rec.front_face) return Vec3(0.0, 0.0, 0.0);
-    return texture_value(s, m.tex, rec.u, rec.v, rec.p);
 }
 
 // The finished sample's features, added into the lane's own record: {a.x, a.y} {a.z, n.x} {n.y, n.z} {depth, hits}.
@@ -99,15 +52,7 @@ RT_DEV void f_accumulate(const SceneDev &s, const FeatureArgs &a, const FLane &L
         alb = f_albedo(s, rec);
         n = rec.normal; depth = rec.t; hits = 1.0;
     }
-    double2 *o;
-    if constexpr (SRC == kFeatPixels) o = reinterpret_cast<double2 *>(a.out + ((uint64_t)L.row | ((uint64_t)L.px << 32)));
-    else o = reinterpret_cast<double2 *>(a.out + ((uint64_t)L.row * a.width + L.px));
-    double2 s0 = make_double2(0.0, 0.0), s1 = s0, s2 = s0, s3 = s0;
-    if (L.smp > 0) { s0 = o[0]; s1 = o[1]; s2 = o[2]; s3 = o[3]; }
-    o[0] = make_double2(s0.x + alb.x, s0.y + alb.y);
-    o[1] = make_double2(s1.x + alb.z, s1.y + n.x);
-    o[2] = make_double2(s2.x + n.y, s2.y + n.z);
-    o[3] = make_double2(s3.x + depth, s3.y + hits);
+    f_add<SRC>(a, L, alb, n, depth, hits);
 }
 
 // Aim sample L.smp of the lane's pixel and start its traversal at the root (`have` false: nothing left, the lane idles).
@@ -135,16 +80,7 @@ RT_DEV void f_done(const SceneDev &s, const FeatureArgs &a, FLane &L, unsigned l
     bool have = true;
     if (refill) {
         const unsigned long long i = wave_claim(a.counter, m, lane);
-        have = i < a.n_pixels;
-        const unsigned long long ii = have ? i : 0ull;
-        if constexpr (SRC == kFeatPixels) {
-            L.row = (uint32_t)ii;
-            L.px = (uint32_t)(ii >> 32);
-        } else {
-            L.row = (uint32_t)(ii / a.width);
-            L.px = (uint32_t)(ii - (unsigned long long)L.row * a.width);
-        }
-        L.smp = 0;
+        have = f_take<SRC>(a, L, i);
     }
     f_aim<SRC>(s, a, L, have);
 }
@@ -238,12 +174,15 @@ hipError_t launch_features_src(const SceneDev &scene, const FeatureArgs &args, u
 
 } // namespace
 
-hipError_t launch_features(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, bool surfaces, hipStream_t stream) {
+hipError_t launch_features(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, bool surfaces, bool specular,
+                           hipStream_t stream) {
+    if (specular) return launch_features_specular(scene, args, stack_need, counters, surfaces, false, stream);
     return launch_features_src<kFeatRows>(scene, args, stack_need, counters, surfaces, stream);
 }
 
-hipError_t launch_features_pixels(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, bool surfaces,
+hipError_t launch_features_pixels(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, bool surfaces, bool specular,
                                   hipStream_t stream) {
+    if (specular) return launch_features_specular(scene, args, stack_need, counters, surfaces, true, stream);
     return launch_features_src<kFeatPixels>(scene, args, stack_need, counters, surfaces, stream);
 }
 

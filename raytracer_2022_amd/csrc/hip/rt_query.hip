@@ -1,5 +1,5 @@
-// rt_query.hip — the closest-hit calls on a device scene: ray queries (rt_intersect*) and first-hit feature buffers (rt_features*,
-// rt_features_pixels*).
+// rt_query.hip — the closest-hit calls on a device scene: ray queries (rt_intersect*) and feature buffers (rt_features*,
+// rt_features_pixels*: first-hit records, and with RT_FLAG_SPECULAR the records behind glass and mirrors).
 #include "rt_internal.hpp"
 
 using namespace rt2022;
@@ -50,13 +50,25 @@ void run_query(rt_scene *sc, const rt_query_ray *d_rays, uint64_t n_rays, uint32
     if (stats) stats->rays = n_rays;               // (a query counts no paths, rays or light tests of its own)
 }
 
+// The flag bits the four feature calls take.
+constexpr uint32_t kFeatureFlags = RT_FLAG_COUNTERS | RT_FLAG_SURFACES | RT_FLAG_SPECULAR;
+
+// paths and rays of a feature call of n samples. First-hit records: one camera path, one world.hit per sample; the kernel counts
+// neither. RT_FLAG_SPECULAR: a sample has a segment per vertex it follows — rays is what the counter instance counted (read_stats
+// put it there), 0 without counters.
+void fill_feature_paths(rt_stats *stats, uint64_t n_samples, bool specular) {
+    if (!stats) return;
+    stats->paths = n_samples;
+    if (!specular) stats->rays = n_samples;
+}
+
 // The arguments of rt_features* (host side only; the scene comes last so that a bad argument is reported as such whatever
 // the scene). `device`: rows and output are rt_features_device's — the rows are range-checked on the device later.
 void check_features(const rt_scene *scene, const rt_camera *cam, const rt_params *p, const void *out, bool device, const char *who) {
     const std::string w(who);
     RT_REQUIRE(p, RT_ERR_INVALID, w + ": null params");
     RT_REQUIRE(cam, RT_ERR_INVALID, w + ": null camera");
-    RT_REQUIRE(!(p->flags & ~(RT_FLAG_COUNTERS | RT_FLAG_SURFACES)), RT_ERR_INVALID, w + ": flag bits other than RT_FLAG_COUNTERS | RT_FLAG_SURFACES");
+    RT_REQUIRE(!(p->flags & ~kFeatureFlags), RT_ERR_INVALID, w + ": flag bits other than RT_FLAG_COUNTERS | RT_FLAG_SURFACES | RT_FLAG_SPECULAR");
     check_view(cam, p, w + ": ", " (width, height or n_frames is 0)");
     const bool need_rows = p->n_rows > 0 && p->spp > 0;
     RT_REQUIRE(p->n_rows == 0 || out, RT_ERR_INVALID, w + ": null output");
@@ -103,9 +115,9 @@ void run_features(rt_scene *sc, const rt_camera *cam, const rt_params *p, const 
     a.out = d_out;
     a.counter = q.counter;
     a.stats = counters ? q.stats.p : nullptr;
-    const bool surfaces = (p->flags & RT_FLAG_SURFACES) != 0;
-    run_counted(q, counters, stream, stats, [&] { return launch_features(sc->dev, a, sc->stack_need, counters, surfaces, stream); });
-    if (stats) stats->paths = stats->rays = n_pixels * p->spp;     // (one camera path, one world.hit per sample; the kernel counts neither)
+    const bool surfaces = (p->flags & RT_FLAG_SURFACES) != 0, specular = (p->flags & RT_FLAG_SPECULAR) != 0;
+    run_counted(q, counters, stream, stats, [&] { return launch_features(sc->dev, a, sc->stack_need, counters, surfaces, specular, stream); });
+    fill_feature_paths(stats, n_pixels * p->spp, specular);
 }
 
 // The arguments of rt_features_pixels* (host side only, the scene last, like check_features). `device`: ids and output are
@@ -115,7 +127,7 @@ void check_features_pixels(const rt_scene *scene, const rt_camera *cam, const rt
     const std::string w(who);
     RT_REQUIRE(p, RT_ERR_INVALID, w + ": null params");
     RT_REQUIRE(cam, RT_ERR_INVALID, w + ": null camera");
-    RT_REQUIRE(!(p->flags & ~(RT_FLAG_COUNTERS | RT_FLAG_SURFACES)), RT_ERR_INVALID, w + ": flag bits other than RT_FLAG_COUNTERS | RT_FLAG_SURFACES");
+    RT_REQUIRE(!(p->flags & ~kFeatureFlags), RT_ERR_INVALID, w + ": flag bits other than RT_FLAG_COUNTERS | RT_FLAG_SURFACES | RT_FLAG_SPECULAR");
     check_view(cam, p, w + ": ", " (width, height or n_frames is 0)");
     RT_REQUIRE(n_entries == 0 || (ids && out), RT_ERR_INVALID, w + ": null id or output buffer");
     RT_REQUIRE(n_entries <= (1ull << 40), RT_ERR_INVALID, w + ": n_entries too large");
@@ -161,10 +173,10 @@ void run_features_pixels(rt_scene *sc, const rt_camera *cam, const rt_params *p,
     a.out = d_out;
     a.counter = q.counter;
     a.stats = counters ? q.stats.p : nullptr;
-    const bool surfaces = (p->flags & RT_FLAG_SURFACES) != 0;
+    const bool surfaces = (p->flags & RT_FLAG_SURFACES) != 0, specular = (p->flags & RT_FLAG_SPECULAR) != 0;
     a.pixel_ids = d_ids;
-    run_counted(q, counters, stream, stats, [&] { return launch_features_pixels(sc->dev, a, sc->stack_need, counters, surfaces, stream); });
-    if (stats) stats->paths = stats->rays = n_entries * p->spp;    // (as run_features)
+    run_counted(q, counters, stream, stats, [&] { return launch_features_pixels(sc->dev, a, sc->stack_need, counters, surfaces, specular, stream); });
+    fill_feature_paths(stats, n_entries * p->spp, specular);
 }
 
 } // namespace

@@ -18,6 +18,7 @@ Workspace &workspace_for(rt_scene *sc, hipStream_t stream) {
 
 void check_params(const rt_scene *scene, const rt_camera *cam, const rt_params *p) {
     RT_REQUIRE(scene && cam && p, RT_ERR_INVALID, "null argument");
+    RT_REQUIRE(!(p->flags & RT_FLAG_SPECULAR), RT_ERR_INVALID, "flag bits: RT_FLAG_SPECULAR is for rt_features* / rt_features_pixels* only");
     check_view(cam, p, "", "");
     RT_REQUIRE(p->n_rows == 0 || p->row_ids, RT_ERR_INVALID, "row_ids is null");
 }

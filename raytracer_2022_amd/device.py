@@ -359,7 +359,7 @@ ADAPTIVE_LUMA_FLOOR = 0.01
 
 
 def render_adaptive(dev, cam, params, total_spp, rounds=2, max_units=4, denoise=None, dual=None, device="cuda", profile=False,
-                    want_state=False, guides="initial", surfaces=False):
+                    want_state=False, guides="initial", surfaces=False, specular=False):
     """Adaptive sampling on torch device buffers, image order, all stages in HBM:
     an initial two-frame render (halves A and B, params.spp samples per pixel each) plus their features; then per round
     denoise_dual (variance) -> err = variance / (luma^2 + 0.01) of the filtered demodulated mean -> adaptive_scale for the
@@ -378,6 +378,7 @@ def render_adaptive(dev, cam, params, total_spp, rounds=2, max_units=4, denoise=
     resolved to sums of spp samples, and those feed the dual denoise and the metric's demodulation. The state then gains
     "feat_acc", the accumulated records (their sample counts are "acc_n"); "feat" stays the initial frames' records.
     surfaces=True passes RT_FLAG_SURFACES to every feature call made here: the guides are those of the surfaces behind media.
+    specular=True passes RT_FLAG_SPECULAR likewise: the guides follow each sample through glass and mirrors.
     The result depends on params.seed and the arguments only: two calls give the same bits."""
     import torch
     W, H, spp = params.width, params.height, params.spp
@@ -397,7 +398,7 @@ def render_adaptive(dev, cam, params, total_spp, rounds=2, max_units=4, denoise=
     acc = torch.empty((2, H, W, 3), dtype=torch.float64, device=device)          # the halves' accumulators: A, B
     feat = torch.empty((2, n, 8), dtype=torch.float64, device=device)            # rt_feature records
     dev.render_device(cam, p, ptr(rows), 2 * H, ptr(acc), stream_ptr=stream)
-    dev.features_device(cam, p, ptr(rows), 2 * H, ptr(feat), stream_ptr=stream, surfaces=surfaces)
+    dev.features_device(cam, p, ptr(rows), 2 * H, ptr(feat), stream_ptr=stream, surfaces=surfaces, specular=specular)
     acc_n = torch.full((2, H, W), float(spp), dtype=torch.float64, device=device)
     dn = denoise if denoise is not None else denoise_params(W, H, spp, sigma_color=DUAL_DEFAULTS["sigma_color"])
     dn.spp = spp
@@ -467,7 +468,7 @@ def render_adaptive(dev, cam, params, total_spp, rounds=2, max_units=4, denoise=
         if all_guides:
             efeat = torch.empty((2 * total, 8), dtype=torch.float64, device=device)
             timed(entry, "features_pixels_ms", lambda: dev.features_pixels_device(cam, p, ptr(entries), 2 * total, ptr(efeat), stream_ptr=stream,
-                                                                                          surfaces=surfaces))
+                                                                                          surfaces=surfaces, specular=specular))
             timed(entry, "merge_features_ms", lambda: [adaptive_merge_features_device(ptr(efeat[h * total:]), ptr(units), ptr(offsets), n,
                                                                                       ptr(feat_acc[h]), stream_ptr=stream) for h in range(2)])
         timed(entry, "merge_ms", lambda: [adaptive_merge_device(ptr(sums[h * total:]), ptr(units), ptr(offsets), n, spp, ptr(acc[h]), ptr(acc_n[h]),
@@ -631,24 +632,27 @@ class DeviceScene:
         F.check(F.lib().rt_render_pixels_device(self._h, C.byref(cam), C.byref(p), C.c_void_p(d_ids_ptr), n_entries, C.c_void_p(d_out_ptr),
                                                 C.c_void_p(stream_ptr or 0), C.byref(stats) if stats is not None else None))
 
-    def features(self, cam, params, row_ids, want_stats=False, surfaces=False):
+    def features(self, cam, params, row_ids, want_stats=False, surfaces=False, specular=False):
         """rt_features with host buffers: the first-hit guide buffers of the camera rays a render of (cam, params, row_ids)
         shoots → array of FEATURE_DTYPE records of shape (n_rows, width) — fields albedo (3), normal (3), depth, hits: sums
         over the spp samples, not divided by spp [, rt_stats]. params.max_depth, spp_chunk and progress_cb are ignored.
         surfaces=True sets RT_FLAG_SURFACES (here and in the three forms below): a ConstantMedium is looked through, the
-        records are those of the first SURFACE behind it."""
+        records are those of the first SURFACE behind it. specular=True sets RT_FLAG_SPECULAR (likewise): the sample's own path is
+        followed through glass and fuzz-0 mirrors (at most RT_FEATURE_SPECULAR_BOUNCES vertices), albedo and normal are those of
+        the first non-specular vertex with the followed metals' albedos multiplied on, depth and hits stay the first hit's; rt_stats.rays
+        then counts every segment (with counters; 0 without). For the denoisers, not for the temporal accumulation."""
         rows = np.ascontiguousarray(row_ids, dtype=np.uint32)
         p = F.rt_params.from_buffer_copy(params)
         p.n_rows = len(rows)
         p.row_ids = rows.ctypes.data
         p.progress_cb = None
-        p.flags = (F.RT_FLAG_COUNTERS if want_stats else 0) | (F.RT_FLAG_SURFACES if surfaces else 0)
+        p.flags = (F.RT_FLAG_COUNTERS if want_stats else 0) | (F.RT_FLAG_SURFACES if surfaces else 0) | (F.RT_FLAG_SPECULAR if specular else 0)
         out = np.zeros((len(rows), p.width), dtype=F.FEATURE_DTYPE)
         st = F.rt_stats()
         F.check(F.lib().rt_features(self._h, C.byref(cam), C.byref(p), out.ctypes.data if out.size else None, C.byref(st)))
         return (out, st) if want_stats else out
 
-    def features_device(self, cam, params, d_row_ids_ptr, n_rows, d_out_ptr, stream_ptr=None, stats=None, surfaces=False):
+    def features_device(self, cam, params, d_row_ids_ptr, n_rows, d_out_ptr, stream_ptr=None, stats=None, surfaces=False, specular=False):
         """rt_features_device: device pointers in (n_rows row ids, room for n_rows * width rt_feature records, 16-byte
         aligned), enqueued on `stream_ptr` (hipStream_t as int). stats=None returns once the kernel is enqueued; an rt_stats
         makes the call synchronise the stream and fill it, counters included."""
@@ -656,32 +660,32 @@ class DeviceScene:
         p.n_rows = n_rows
         p.row_ids = d_row_ids_ptr
         p.progress_cb = None
-        p.flags = (F.RT_FLAG_COUNTERS if stats is not None else 0) | (F.RT_FLAG_SURFACES if surfaces else 0)
+        p.flags = (F.RT_FLAG_COUNTERS if stats is not None else 0) | (F.RT_FLAG_SURFACES if surfaces else 0) | (F.RT_FLAG_SPECULAR if specular else 0)
         F.check(F.lib().rt_features_device(self._h, C.byref(cam), C.byref(p), C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr or 0),
                                            C.byref(stats) if stats is not None else None))
 
-    def features_pixels(self, cam, params, ids, want_stats=False, surfaces=False):
+    def features_pixels(self, cam, params, ids, want_stats=False, surfaces=False, specular=False):
         """rt_features_pixels with host buffers: the feature records of a list of (frame, pixel) ids (uint64, see pixel_ids;
         params.n_frames must exceed every frame) → (n,) array of FEATURE_DTYPE records, each the record features() gives that
         pixel of that frame [, rt_stats]. n_rows, row_ids, max_depth, spp_chunk and progress_cb are ignored."""
         e = np.ascontiguousarray(ids, dtype=np.uint64).ravel()
         p = F.rt_params.from_buffer_copy(params)
         p.n_rows, p.row_ids, p.progress_cb = 0, None, None
-        p.flags = (F.RT_FLAG_COUNTERS if want_stats else 0) | (F.RT_FLAG_SURFACES if surfaces else 0)
+        p.flags = (F.RT_FLAG_COUNTERS if want_stats else 0) | (F.RT_FLAG_SURFACES if surfaces else 0) | (F.RT_FLAG_SPECULAR if specular else 0)
         out = np.zeros(len(e), dtype=F.FEATURE_DTYPE)
         st = F.rt_stats()
         F.check(F.lib().rt_features_pixels(self._h, C.byref(cam), C.byref(p), e.ctypes.data if len(e) else None, len(e),
                                            out.ctypes.data if len(e) else None, C.byref(st)))
         return (out, st) if want_stats else out
 
-    def features_pixels_device(self, cam, params, d_ids_ptr, n_entries, d_out_ptr, stream_ptr=None, stats=None, surfaces=False):
+    def features_pixels_device(self, cam, params, d_ids_ptr, n_entries, d_out_ptr, stream_ptr=None, stats=None, surfaces=False, specular=False):
         """rt_features_pixels_device: device pointers in (n_entries uint64 ids, 8-byte aligned; room for n_entries rt_feature
         records, 16-byte aligned), enqueued on `stream_ptr` (hipStream_t as int) behind the range check of the ids (one
         synchronisation of the stream). stats=None returns once the kernel is enqueued; an rt_stats makes the call
         synchronise the stream and fill it, counters included."""
         p = F.rt_params.from_buffer_copy(params)
         p.n_rows, p.row_ids, p.progress_cb = 0, None, None
-        p.flags = (F.RT_FLAG_COUNTERS if stats is not None else 0) | (F.RT_FLAG_SURFACES if surfaces else 0)
+        p.flags = (F.RT_FLAG_COUNTERS if stats is not None else 0) | (F.RT_FLAG_SURFACES if surfaces else 0) | (F.RT_FLAG_SPECULAR if specular else 0)
         F.check(F.lib().rt_features_pixels_device(self._h, C.byref(cam), C.byref(p), C.c_void_p(d_ids_ptr), n_entries, C.c_void_p(d_out_ptr),
                                                   C.c_void_p(stream_ptr or 0), C.byref(stats) if stats is not None else None))
 

@@ -1,0 +1,498 @@
+"""RT_FLAG_SPECULAR on the four feature calls: the records behind glass and mirrors against the restatement by oracle calls
+(tests/specular_ref.py) bit for bit, with the counters the definition implies; the identity that ties them to both render
+engines (on a scene of specular surfaces only the flagged albedo IS the render's radiance); every kernel shape; the stored
+world-frame ray under movers and an open shutter; media, with and without RT_FLAG_SURFACES; scenes the flag must not change;
+one-pixel-wide images, refused id lists, streams beside an asynchronous render, render_adaptive(specular=True). Every
+comparison is on the uint64 view with the NaN pattern. Every test here needs the flag: the parent refuses it."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from raytracer_2022_amd import _ffi as F
+
+import specular_ref as SP
+import trace_scenes as TS
+from test_features import assert_same_bits, oracle_features
+from test_features_pixels import all_rows, shuffled_ids_with_repeats
+from test_surfaces import boundary_contents, same_stats
+
+pytestmark = pytest.mark.gpu
+
+W0, H0, SPP0 = 32, 24, 2
+UNFOLLOWED = ["cornell_box", "cornell_smoke", "earth", "simple_light", "two_perlin_spheres", "two_spheres"]
+
+
+@pytest.fixture(scope="module", autouse=True)
+def torch_first():
+    """Bring torch's HIP context up before the library's first call, as the other GPU test modules do."""
+    import torch
+    assert torch.cuda.is_available(), "gpu tests need a GPU: the HIP path has no fallback"
+    torch.zeros(1, device="cuda")
+
+
+@pytest.fixture(scope="module")
+def hall(rt, O):
+    """The mirror hall, two frames of it by the restatement (computed once, never changed), and its device scene."""
+    b, d, cam, p = SP.mirror_hall(rt)
+    p2 = F.rt_params.from_buffer_copy(p)
+    p2.n_frames = 2
+    ref, st, info = SP.oracle_specular_features(O, d, cam, p2, all_rows(SP.HALL_H, 2))
+    dev = rt.DeviceScene(d)
+    yield b, d, cam, p2, ref, st, info, dev
+    dev.close()
+
+
+def check_counters(st, st_ref, info, n_samples, d=None, surfaces=False):
+    """rt_stats of a flagged counter call against the restatement's: paths, the device's ray count, the words, and the traversal
+    counters — summed over all segments; with RT_FLAG_SURFACES the copy still tests its media's boundaries, so those kinds bound."""
+    assert st.paths == n_samples and st.rays == info.segments and st.rng_draws == info.words, (st.as_dict(), info.segments, info.words)
+    got, ref = list(st.prim_tests), list(st_ref.prim_tests)
+    if not surfaces:
+        assert got == ref and st.node_visits == st_ref.node_visits
+    else:
+        kinds, nodes_below = boundary_contents(d)
+        assert got[F.RT_KIND_MEDIUM] == 0
+        for k in range(len(got)):
+            assert got[k] <= ref[k]
+            if k != F.RT_KIND_MEDIUM and k not in kinds:
+                assert got[k] == ref[k], (k, got[k], ref[k])
+        assert st.node_visits <= st_ref.node_visits and (nodes_below or st.node_visits == st_ref.node_visits)
+    assert st.light_pdf_tests == 0 and st.passes == 0 and st.pool_slots == 0 and st.partial_bytes == 0 and st.spp_chunk == 0
+    assert st.trace_ms == 0 and st.shade_ms == 0 and st.ms > 0
+
+
+def check_against_restatement(rt, O, d, cam, p, rows, what, surfaces=False, dev=None):
+    """The row form with counters and on the plain instance against the restatement -> (records, Info, the device scene)."""
+    dev = dev or rt.DeviceScene(d)
+    ref, st_ref, info = SP.oracle_specular_features(O, d, cam, p, rows, surfaces)
+    got, st = dev.features(cam, p, rows, want_stats=True, surfaces=surfaces, specular=True)
+    assert got.shape == (len(rows), p.width) and got.dtype == F.FEATURE_DTYPE
+    assert_same_bits(got.reshape(-1), ref, what)
+    check_counters(st, st_ref, info, len(rows) * p.width * p.spp, d, surfaces)
+    plain = dev.features(cam, p, rows, surfaces=surfaces, specular=True)
+    assert_same_bits(plain.reshape(-1), ref, (what, "plain instance"))
+    return got, info, dev
+
+
+# ---- 1. the mirror hall, all four calls --------------------------------------------------------------------------------------
+def test_mirror_hall_rows(rt, O, hall):
+    b, d, cam, p2, ref, st_ref, info, dev = hall
+    H, W = SP.HALL_H, SP.HALL_W
+    lengths = np.bincount(info.lengths.reshape(-1), minlength=SP.BOUNCES + 1)
+    assert (lengths >= 20).all() and info.capped.any()
+    rows = rt.shuffled_rows(2 * H, 11)
+    order = (rows[:, None].astype(np.int64) * W + np.arange(W)).reshape(-1)
+    got, st = dev.features(cam, p2, rows, want_stats=True, specular=True)
+    assert_same_bits(got.reshape(-1), ref[order], "counter instance")
+    check_counters(st, st_ref, info, 2 * W * H * p2.spp)
+    assert st.rays > st.paths
+    plain, st0 = dev.features(cam, p2, rows, specular=True), F.rt_stats()
+    assert_same_bits(plain.reshape(-1), ref[order], "plain instance")
+    # without RT_FLAG_COUNTERS rays is 0: nobody counted
+    pp = F.rt_params.from_buffer_copy(p2)
+    pp.n_rows, pp.row_ids, pp.flags = len(rows), rows.ctypes.data, F.RT_FLAG_SPECULAR
+    out = np.zeros(len(rows) * W, dtype=F.FEATURE_DTYPE)
+    F.check(rt.lib().rt_features(dev._h, C.byref(cam), C.byref(pp), out.ctypes.data, C.byref(st0)))
+    assert_same_bits(out, ref[order], "without counters")
+    assert st0.paths == 2 * W * H * p2.spp and st0.rays == 0 and st0.node_visits == 0 and st0.rng_draws == 0 and st0.ms > 0
+    # unflagged calls on the hall still give first-hit records
+    first, _, _ = oracle_features(O, d, cam, p2, all_rows(H, 2))
+    unflagged, st1 = dev.features(cam, p2, all_rows(H, 2), want_stats=True)
+    assert_same_bits(unflagged.reshape(-1), first, "unflagged")
+    assert st1.rays == st1.paths == 2 * W * H * p2.spp
+    assert_same_bits(got["depth"].reshape(-1), first["depth"][order], "depth is primary visibility")
+    assert_same_bits(got["hits"].reshape(-1), first["hits"][order], "hits")
+
+
+def test_mirror_hall_pixel_lists_and_device_forms(rt, O, hall):
+    import torch
+    b, d, cam, p2, ref, st_ref, info, dev = hall
+    H, W = SP.HALL_H, SP.HALL_W
+    n_ids = 2 * W * H
+    ids = shuffled_ids_with_repeats(n_ids, seed=4)
+    got, st = dev.features_pixels(cam, p2, ids, want_stats=True, specular=True)
+    assert_same_bits(got, ref[ids], "counter instance")
+    assert_same_bits(dev.features_pixels(cam, p2, ids, specular=True), ref[ids], "plain instance")
+    some = ids[:200]
+    ref200, st200, info200 = SP.oracle_specular_ids(O, d, cam, p2, some)
+    assert_same_bits(ref200, ref[some], "the id form of the restatement")
+    got200, stg = dev.features_pixels(cam, p2, some, want_stats=True, specular=True)
+    check_counters(stg, st200, info200, 200 * p2.spp)
+    g = np.random.default_rng(9)
+    for n in (1, 63, 64, 65):
+        lst = g.integers(0, n_ids, n).astype(np.uint64)
+        lst[n // 2] = lst[0]                                # a repeat
+        assert_same_bits(dev.features_pixels(cam, p2, lst, specular=True), ref[lst], "length %d" % n)
+    # one entry more than the persistent grid has lanes, at spp 1
+    p1 = F.rt_params.from_buffer_copy(p2)
+    p1.spp = 1
+    whole1 = dev.features(cam, p1, all_rows(H, 2), specular=True).reshape(-1)
+    ref1, _, info1 = SP.oracle_specular_features(O, d, cam, p1, all_rows(H, 2))
+    assert_same_bits(whole1, ref1, "spp 1")
+    n = dev.info()["grid_blocks"] * 1024 + 1
+    assert 1024 < n < (1 << 24)
+    many = (np.arange(n, dtype=np.uint64) * np.uint64(5)) % np.uint64(n_ids)
+    big, stb = dev.features_pixels(cam, p1, many, want_stats=True, specular=True)
+    assert_same_bits(big, whole1[many], "past the grid's lanes")
+    assert stb.paths == n and stb.rays == int((info1.lengths.reshape(-1)[many] + 1).sum())
+    # the device forms on a caller's stream
+    stream = torch.cuda.Stream()
+    rows = rt.shuffled_rows(2 * H, 5)
+    order = (rows[:, None].astype(np.int64) * W + np.arange(W)).reshape(-1)
+    d_rows = torch.from_numpy(rows.view(np.int32)).cuda()
+    d_out = torch.full((n_ids * 8 + 2,), float("nan"), dtype=torch.float64, device="cuda")
+    torch.cuda.synchronize()
+    dev.features_device(cam, p2, d_rows.data_ptr(), 2 * H, d_out.data_ptr(), stream.cuda_stream, specular=True)
+    stream.synchronize()
+    out = d_out.cpu().numpy()
+    assert_same_bits(out[: n_ids * 8].view(F.FEATURE_DTYPE), ref[order], "rt_features_device")
+    assert np.isnan(out[n_ids * 8:]).all()
+    std = F.rt_stats()
+    dev.features_device(cam, p2, d_rows.data_ptr(), 2 * H, d_out.data_ptr(), stream.cuda_stream, stats=std, specular=True)
+    assert_same_bits(d_out.cpu().numpy()[: n_ids * 8].view(F.FEATURE_DTYPE), ref[order], "rt_features_device with stats")
+    check_counters(std, st_ref, info, n_ids * p2.spp)
+    d_ids = torch.from_numpy(ids.view(np.int64)).cuda()
+    d_pix = torch.full((ids.size * 8,), float("nan"), dtype=torch.float64, device="cuda")
+    torch.cuda.synchronize()
+    dev.features_pixels_device(cam, p2, d_ids.data_ptr(), ids.size, d_pix.data_ptr(), stream.cuda_stream, specular=True)
+    stream.synchronize()
+    assert_same_bits(d_pix.cpu().numpy().view(F.FEATURE_DTYPE), ref[ids], "rt_features_pixels_device")
+    stp = F.rt_stats()
+    dev.features_pixels_device(cam, p2, d_ids.data_ptr(), ids.size, d_pix.data_ptr(), stream.cuda_stream, stats=stp, specular=True)
+    assert_same_bits(d_pix.cpu().numpy().view(F.FEATURE_DTYPE), ref[ids], "rt_features_pixels_device with stats")
+    assert stp.paths == ids.size * p2.spp and stp.rays == st.rays and stp.rng_draws == st.rng_draws
+
+
+# ---- 2. the render identity, on both engines -----------------------------------------------------------------------------------
+def test_flagged_albedo_is_the_renders_radiance(rt, O, hall):
+    b, d, cam, p2, ref, st_ref, info, dev0 = hall
+    H, W = SP.HALL_H, SP.HALL_W
+    p = rt.make_params(W, H, SP.HALL_SPP, 9, SP.HALL_BACKGROUND, seed=SP.HALL_SEED, spp_chunk=1)
+    rows = np.arange(H, dtype=np.uint32)
+    keep = ~info.capped[: W * H].any(axis=1)                # pixels of frame 0 with no cap-ended sample
+    print("pixels left out:", int((~keep).sum()), "of", W * H)
+    assert (~keep).sum() <= 16 and (~keep).sum() * 10 <= W * H
+    dev = rt.DeviceScene(d)
+    alb = dev.features(cam, p, rows, specular=True)["albedo"].reshape(-1, 3)
+    assert_same_bits(alb, ref["albedo"][: W * H], "the flagged albedo")
+    for engine in ("wavefront", "mega"):
+        if engine == "mega":
+            dev.set_engine("mega")
+        sums = dev.render(cam, p, rows).reshape(-1, 3)
+        assert_same_bits(sums[keep], alb[keep], "rt_render, %s engine, max_depth 9" % engine)
+        assert np.any(sums[~keep] != alb[~keep])            # a cap-ended sample's radiance is 0, its albedo is not
+    dev.close()
+    # rt_radiance on the camera rays of one row: the chain from (r_0, path_key(rng_state, 0, 0, 0)) is ray_color of that ray
+    row = H // 2
+    samples = [r for r in info.samples[row * W * SP.HALL_SPP:(row + 1) * W * SP.HALL_SPP]]
+    rays0 = np.array([r.ray0 for r in samples])
+    states = np.arange(100, 100 + len(samples), dtype=np.uint64)
+    st, chains = F.rt_stats(), []
+    for r, state in zip(samples, states):
+        chains.append(SP.chain_from(O, d, p, r.ray0, O.lib().rto_path_key(int(state), 0, 0, 0), 0, st))
+    ok = np.array([not c.capped for c in chains])
+    assert ok.sum() >= 0.9 * len(chains) and len({c.length for c in chains if not c.capped}) >= 4      # (at most 1 ray in 10 is left out)
+    rad = dev0.radiance(rt.radiance_rays(rays0[:, :3], rays0[:, 3:6], time=rays0[:, 6], rng_state=states), spp=1,
+                        background=SP.HALL_BACKGROUND, max_depth=9)
+    assert_same_bits(rad[ok], np.array([c.f[:3] for c in chains])[ok], "rt_radiance, max_depth 9")
+
+
+# ---- 3. one scene per shape of trav_dispatch -----------------------------------------------------------------------------------
+@pytest.mark.parametrize("need", [16, 17, 22, 23, 30, 31, 64])
+def test_every_kernel_shape(rt, O, need):
+    """The hall's list under chain links: 16 and 17 and 22 take the 22-entry instance (a tiny-stack scene is dispatched there under the
+    flag), 23 and 30 the 30-entry one, 31 and 64 the 64-entry one."""
+    b = rt.DescBuilder()
+    hall_list = b.list(SP.mirror_hall_refs(rt, b))
+    far = b.lambertian((0.2, 0.9, 0.4))
+    b.set_root(TS.chain(b, hall_list, need - 7, lambda i: b.sphere((-3.0 + 0.4 * i, 2.2, -5.0), 0.15, far)))
+    d = b.desc()
+    assert TS.stack_need(d) == need
+    cam = SP.mirror_hall_camera(rt)
+    p = rt.make_params(SP.HALL_W, SP.HALL_H, 2, 9, SP.HALL_BACKGROUND, seed=need)
+    rows = rt.shuffled_rows(SP.HALL_H, need)
+    got, info, dev = check_against_restatement(rt, O, d, cam, p, rows, need)
+    assert dev.info()["stack_need"] == need
+    assert info.lengths.max() == SP.BOUNCES and (info.lengths > 0).sum() > 100
+    ids = shuffled_ids_with_repeats(SP.HALL_W * SP.HALL_H, seed=need)[:300]
+    ref, st_ref, info_i = SP.oracle_specular_ids(O, d, cam, p, ids)
+    out, st = dev.features_pixels(cam, p, ids, want_stats=True, specular=True)
+    assert_same_bits(out, ref, "pixel list")
+    check_counters(st, st_ref, info_i, 300 * p.spp)
+    assert_same_bits(dev.features_pixels(cam, p, ids, specular=True), ref, "pixel list, plain instance")
+    dev.close()
+
+
+# ---- 4. the stored world-frame ray -----------------------------------------------------------------------------------------------
+def textures(rt, b):
+    g = np.random.default_rng(11)
+    vec = g.normal(size=(256, 3))
+    vec /= np.linalg.norm(vec, axis=1, keepdims=True)
+    pl = b.perlin(vec, g.permutation(256), g.permutation(256), g.permutation(256))
+    img = (np.arange(8 * 4 * 3, dtype=np.uint8).reshape(4, 8, 3) * 7) % 251
+    return [b.solid((0.7, 0.3, 0.2)), b.checker(b.solid((0.2, 0.3, 0.1)), b.solid((0.9, 0.9, 0.9))), b.noise(pl, 4.0), b.image(img)]
+
+
+def four_deep(b, ref, offset):
+    """`ref` under translate(rotate_y(translate(rotate_y(.)))): RT_MAX_XFORM_DEPTH movers."""
+    s, c = 0.5, 0.8660254037844386
+    return b.translate(b.rotate_y(b.translate(b.rotate_y(ref, s, c), (0.2, 0.0, -0.1)), -s, c), offset)
+
+
+def movers_scene(rt):
+    """A glass sphere and a mirror sphere, each four movers deep, over a checkered floor: every segment behind them leaves
+    movers with the stored ray, and the winner's record is rebuilt from it."""
+    b = rt.DescBuilder()
+    floor_ = b.rect(F.RT_RECT_XZ, -20, 20, -20, 20, -1.0, b.lambertian(tex=b.checker(b.solid((0.2, 0.3, 0.1)), b.solid((0.9, 0.9, 0.9)))))
+    glass = four_deep(b, b.sphere((0.0, 0.0, 0.0), 1.0, b.dielectric(1.5)), (-1.3, 0.0, 0.0))
+    mirror = four_deep(b, b.sphere((0.0, 0.0, 0.0), 1.0, b.metal((0.9, 0.8, 0.7), 0.0)), (1.3, 0.0, -0.5))
+    box_ = four_deep(b, b.box((-0.4, -0.4, -0.4), (0.4, 0.4, 0.4), b.metal((0.6, 0.9, 0.9), 0.0)), (0.0, 1.6, 0.5))
+    b.set_root(b.list([floor_, glass, mirror, box_]))
+    cam = rt.camera_new((0, 1.0, 6), (0, 0.2, 0), (0, 1, 0), 40.0, W0 / H0, 0.05, 6.0, 0.0, 1.0)
+    return b, b.desc(), cam, (0.5, 0.7, 1.0)
+
+
+def shutter_scene(rt):
+    """A moving sphere seen in a mirror with an open shutter: a Metal's outgoing tm is 0, so the reflection shows it at time 0
+    while the direct view shows it at the camera ray's time."""
+    b = rt.DescBuilder()
+    mover = b.lambertian((0.8, 0.2, 0.2))
+    ball = b.moving_sphere((-1.0, 0.0, 0.0), (1.5, 0.8, 0.0), 0.0, 1.0, 0.5, mover)
+    mirror = b.rect(F.RT_RECT_XY, -4, 4, -2, 3, -2.0, b.metal((0.9, 0.9, 0.9), 0.0))
+    floor_ = b.rect(F.RT_RECT_XZ, -6, 6, -6, 6, -0.6, b.lambertian((0.4, 0.5, 0.4)))
+    b.set_root(b.list([ball, mirror, floor_]))
+    cam = rt.camera_new((0, 1.0, 5), (0, 0.3, -2), (0, 1, 0), 50.0, W0 / H0, 0.0, 5.0, 0.0, 1.0)
+    return b, b.desc(), cam, (0.1, 0.1, 0.2), mover
+
+
+def behind_glass_scene(rt):
+    """Behind a glass slab and in a mirror: a Lambertian of every texture kind, a light seen from behind, a fuzz-0.3 metal."""
+    b = rt.DescBuilder()
+    refs = [b.box((-4.0, -1.0, 1.0), (4.0, 3.0, 1.3), b.dielectric(1.5))]
+    for i, t in enumerate(textures(rt, b)):
+        refs.append(b.sphere(((i - 1.5) * 1.3, 0.0, -0.5), 0.55, b.lambertian(tex=t)))
+    refs.append(b.rect(F.RT_RECT_XY, -1.5, 1.5, 1.0, 2.2, -1.0, b.diffuse_light((5, 4, 3)), flip=True))     # its back towards the camera
+    refs.append(b.rect(F.RT_RECT_XY, -3.5, -2.0, 1.0, 2.2, -1.0, b.diffuse_light((3, 4, 5))))
+    refs.append(b.sphere((2.6, 1.6, -0.6), 0.5, b.metal((0.8, 0.7, 0.6), 0.3)))
+    refs.append(b.rect(F.RT_RECT_XY, -6, 6, -2, 5, -3.0, b.metal((0.95, 0.95, 0.95), 0.0)))                 # the mirror behind it all
+    refs.append(b.rect(F.RT_RECT_XZ, -20, 20, -20, 20, -1.0, b.lambertian(tex=b.checker(b.solid((0.1, 0.1, 0.1)), b.image(
+        (np.arange(6 * 3 * 3, dtype=np.uint8).reshape(3, 6, 3) * 5) % 253)))))
+    b.set_root(b.list(refs))
+    cam = rt.camera_new((0, 1.0, 7), (0, 0.8, 0), (0, 1, 0), 45.0, W0 / H0, 0.0, 7.0, 0.0, 1.0)
+    return b, b.desc(), cam, (0.3, 0.4, 0.6)
+
+
+def test_stored_ray_under_movers(rt, O):
+    b, d, cam, bg = movers_scene(rt)
+    assert d.n_xforms == 12
+    p = rt.make_params(W0, H0, SPP0, 50, bg, seed=31)
+    got, info, dev = check_against_restatement(rt, O, d, cam, p, rt.shuffled_rows(H0, 3), "movers")
+    kinds = {(k > 0, kind) for k, kind, front, tex in info.seen}
+    assert (True, F.RT_MAT_LAMBERTIAN) in kinds and (True, F.RT_MAT_DIELECTRIC) in kinds and (True, F.RT_MAT_METAL) in kinds
+    assert (info.lengths >= 2).sum() > 50                    # in and out of the glass
+    dev.close()
+
+
+def test_reflection_of_a_moving_sphere_is_at_time_zero(rt, O):
+    b, d, cam, bg, mover = shutter_scene(rt)
+    p = rt.make_params(W0, H0, SPP0, 50, bg, seed=32)
+    got, info, dev = check_against_restatement(rt, O, d, cam, p, rt.shuffled_rows(H0, 4), "shutter")
+    assert (0, F.RT_MAT_LAMBERTIAN, True, F.RT_TEX_SOLID) in info.seen and (1, F.RT_MAT_LAMBERTIAN, True, F.RT_TEX_SOLID) in info.seen
+    # the same view with the ball frozen where it is at time 0: every reflected record stays, the direct view changes
+    d.moving_spheres[0].center1[:] = d.moving_spheres[0].center0[:]
+    frozen, info_f = SP.oracle_specular_features(O, d, cam, p, rt.shuffled_rows(H0, 4))[::2]
+    mirrored = (info.lengths.min(axis=1) > 0) & (info_f.lengths.min(axis=1) > 0)
+    assert mirrored.sum() > 50
+    assert_same_bits(got.reshape(-1)[mirrored]["albedo"], frozen[mirrored]["albedo"], "the reflection is time 0's")
+    assert np.any(got.reshape(-1)[~mirrored].view(np.uint64) != frozen[~mirrored].view(np.uint64))
+    dev.close()
+
+
+def test_every_terminal_vertex_behind_glass(rt, O):
+    b, d, cam, bg = behind_glass_scene(rt)
+    p = rt.make_params(W0, H0, SPP0, 50, bg, seed=33)
+    got, info, dev = check_against_restatement(rt, O, d, cam, p, rt.shuffled_rows(H0, 5), "behind glass")
+    behind = {(kind, front) for k, kind, front, tex in info.seen if k > 0}
+    assert {(F.RT_MAT_LAMBERTIAN, True), (F.RT_MAT_DIFFUSE_LIGHT, True), (F.RT_MAT_DIFFUSE_LIGHT, False), (F.RT_MAT_METAL, True)} <= behind
+    tex_kinds = {tex for k, kind, front, tex in info.seen if k > 0 and kind == F.RT_MAT_LAMBERTIAN}
+    assert tex_kinds == {F.RT_TEX_SOLID, F.RT_TEX_CHECKER, F.RT_TEX_NOISE, F.RT_TEX_IMAGE}
+    fuzzy = [r for r in info.samples if r.length > 0 and r.end_mat >= 0 and d.materials[r.end_mat].kind == F.RT_MAT_METAL and not r.capped]
+    assert len(fuzzy) > 10 and all(d.materials[r.end_mat].param == 0.3 for r in fuzzy)
+    first = dev.features(cam, p, rt.shuffled_rows(H0, 5))
+    changed = np.any(first.view(np.uint64).reshape(-1, 8) != got.view(np.uint64).reshape(-1, 8), axis=1)
+    assert changed.sum() > W0 * H0 // 4
+    dev.close()
+
+
+# ---- 5. media --------------------------------------------------------------------------------------------------------------------
+def media_scene(rt):
+    """A thin medium in front of a mirror and one inside a glass ball: the media's words, the Dielectric's and the Metal's
+    sampler's interleave on one stream, as the render's do."""
+    b = rt.DescBuilder()
+    glass = b.dielectric(1.5)
+    mist = b.medium(b.box((-3.0, -1.0, -1.2), (0.5, 2.5, -0.6), glass), 0.6, b.isotropic((0.9, 0.9, 0.9)))
+    mirror = b.rect(F.RT_RECT_XY, -4, 1, -1, 3, -2.0, b.metal((0.9, 0.85, 0.8), 0.0))
+    ball = b.sphere((2.0, 0.3, 0.0), 1.2, glass)
+    inner = b.medium(b.sphere((2.0, 0.3, 0.0), 0.9, glass), 0.8, b.isotropic((0.2, 0.4, 0.9)))
+    floor_ = b.rect(F.RT_RECT_XZ, -20, 20, -20, 20, -1.0, b.lambertian(tex=b.checker(b.solid((0.2, 0.3, 0.1)), b.solid((0.9, 0.9, 0.9)))))
+    b.set_root(b.list([mist, mirror, ball, inner, floor_]))
+    cam = rt.camera_new((0.3, 1.0, 6), (0.3, 0.4, 0), (0, 1, 0), 45.0, W0 / H0, 0.0, 6.0, 0.0, 1.0)
+    return b, b.desc(), cam, (0.5, 0.6, 0.8)
+
+
+@pytest.mark.parametrize("surfaces", [False, True])
+def test_media_in_front_of_a_mirror_and_inside_glass(rt, O, surfaces):
+    b, d, cam, bg = media_scene(rt)
+    p = rt.make_params(W0, H0, SPP0, 50, bg, seed=41)
+    rows = rt.shuffled_rows(H0, 6)
+    got, info, dev = check_against_restatement(rt, O, d, cam, p, rows, "media", surfaces=surfaces)
+    iso_behind = any(kind == F.RT_MAT_ISOTROPIC and k > 0 for k, kind, front, tex in info.seen)
+    iso_first = any(kind == F.RT_MAT_ISOTROPIC and k == 0 for k, kind, front, tex in info.seen)
+    assert (iso_behind, iso_first) == ((False, False) if surfaces else (True, True))
+    other = dev.features(cam, p, rows, surfaces=not surfaces, specular=True)
+    assert np.any(other.view(np.uint64) != got.view(np.uint64))
+    dev.close()
+
+
+@pytest.mark.parametrize("name", ["final_scene", "random_scene"])
+def test_builders_under_both_combinations(rt, O, name):
+    W, H, spp = 48, 32, 2
+    s = rt.HostScene(name, seed=2022)
+    cam, bg = s.default_view(W / H)
+    p = rt.make_params(W, H, spp, 50, bg, seed=2022)
+    rows = rt.shuffled_rows(H, 2022)
+    dev = rt.DeviceScene(s.desc)
+    got, info, _ = check_against_restatement(rt, O, s.desc, cam, p, rows, name, dev=dev)
+    assert (info.lengths > 0).sum() >= (100 if name == "random_scene" else 30)
+    both, info_b, _ = check_against_restatement(rt, O, s.desc, cam, p, rows, (name, "with surfaces"), surfaces=True, dev=dev)
+    if s.desc.n_media:
+        assert np.any(both.view(np.uint64) != got.view(np.uint64))
+    else:
+        assert_same_bits(both, got, "no media: RT_FLAG_SURFACES changes nothing")
+    dev.close()
+
+
+# ---- 6. scenes that must not change -----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", UNFOLLOWED)
+def test_flag_changes_nothing_without_followed_materials(rt, name):
+    s = rt.HostScene(name, seed=2022)
+    d = s.desc
+    assert not any(SP.followed(d.materials[i]) for i in range(d.n_materials))
+    W, H, spp = 48, 32, 3
+    cam, bg = s.default_view(W / H)
+    p = rt.make_params(W, H, spp, 50, bg, seed=2022)
+    rows = rt.shuffled_rows(H, 2022)
+    dev = rt.DeviceScene(d)
+    for surfaces in (False, True):
+        plain, st0 = dev.features(cam, p, rows, want_stats=True, surfaces=surfaces)
+        got, st1 = dev.features(cam, p, rows, want_stats=True, surfaces=surfaces, specular=True)
+        assert_same_bits(got, plain, (name, surfaces))
+        assert same_stats(st0, st1), (name, st0.as_dict(), st1.as_dict())
+        assert_same_bits(dev.features(cam, p, rows, surfaces=surfaces, specular=True), plain, (name, surfaces, "plain instance"))
+    ids = shuffled_ids_with_repeats(W * H, seed=7)[:400]
+    a, sa = dev.features_pixels(cam, p, ids, want_stats=True)
+    c, sc = dev.features_pixels(cam, p, ids, want_stats=True, specular=True)
+    assert_same_bits(c, a, "pixel list")
+    assert same_stats(sa, sc) and plain["hits"].sum() > 100
+    dev.close()
+
+
+def test_flag_changes_nothing_on_a_wwscene_pixel(rt):
+    """wwscene holds glass among its small spheres: the pixel tests/test_specular_ref.py checks, whose samples meet none."""
+    W, H = 12, 8
+    s = rt.HostScene("wwscene", seed=2022)
+    cam, bg = s.default_view(W / H)
+    p = rt.make_params(W, H, 2, 50, bg, seed=2022)
+    dev = rt.DeviceScene(s.desc)
+    ids = np.array([(H // 2) * W + W // 2], dtype=np.uint64)
+    a, sa = dev.features_pixels(cam, p, ids, want_stats=True)
+    c, sc = dev.features_pixels(cam, p, ids, want_stats=True, specular=True)
+    assert_same_bits(c, a, "wwscene")
+    assert same_stats(sa, sc) and a["hits"][0] > 0
+    dev.close()
+
+
+# ---- 7. hostile and plumbing --------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("W, H", [(1, 8), (8, 1), (1, 1)])
+def test_one_pixel_wide_images(rt, O, hall, W, H):
+    b, d, cam, p2, ref, st_ref, info, dev = hall
+    p = rt.make_params(W, H, 3, 9, (0.1, 0.2, 0.3), seed=2)
+    rows = np.arange(H, dtype=np.uint32)
+    want, st_w, info_w = SP.oracle_specular_features(O, d, cam, p, rows)
+    got, st = dev.features(cam, p, rows, want_stats=True, specular=True)
+    assert_same_bits(got.reshape(-1), want, (W, H))
+    check_counters(st, st_w, info_w, W * H * 3)
+    assert_same_bits(dev.features_pixels(cam, p, np.arange(W * H, dtype=np.uint64), specular=True), want, "pixel list")
+    assert np.isnan(want.view(np.float64)).any() or (want["hits"] == 0).any()
+
+
+def test_a_refused_id_list_leaves_the_output_untouched(rt, hall):
+    import torch
+    b, d, cam, p2, ref, st_ref, info, dev = hall
+    n_ids = 2 * SP.HALL_W * SP.HALL_H
+    ids = shuffled_ids_with_repeats(n_ids, seed=2)[:333]
+    bad = ids.copy()
+    bad[200] = n_ids
+    poison = np.random.default_rng(6).integers(1, 1 << 62, 333 * 8).astype(np.int64)
+    d_pix = torch.from_numpy(poison).cuda()
+    d_bad = torch.from_numpy(bad.view(np.int64)).cuda()
+    stream = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    with pytest.raises(rt.RtError) as e:
+        dev.features_pixels_device(cam, p2, d_bad.data_ptr(), 333, d_pix.data_ptr(), stream.cuda_stream, specular=True)
+    assert e.value.code == F.RT_ERR_INVALID and "pixel id out of range" in str(e.value)
+    torch.cuda.synchronize()
+    assert np.array_equal(d_pix.cpu().numpy(), poison)
+    d_ids = torch.from_numpy(ids.view(np.int64)).cuda()
+    dev.features_pixels_device(cam, p2, d_ids.data_ptr(), 333, d_pix.data_ptr(), stream.cuda_stream, specular=True)
+    stream.synchronize()
+    assert_same_bits(d_pix.cpu().numpy().view(np.float64).view(F.FEATURE_DTYPE), ref[ids], "the next valid call")
+
+
+def test_beside_an_asynchronous_render(rt, hall):
+    import torch
+    b, d, cam, p2, ref, st_ref, info, dev = hall
+    H, W = SP.HALL_H, SP.HALL_W
+    p = F.rt_params.from_buffer_copy(p2)
+    p.spp_chunk = 1
+    rows = rt.shuffled_rows(2 * H, 3)
+    order = (rows[:, None].astype(np.int64) * W + np.arange(W)).reshape(-1)
+    ref_render = dev.render(cam, p, rows)
+    a_stream, b_stream = torch.cuda.Stream(), torch.cuda.Stream()
+    d_rows = torch.from_numpy(rows.view(np.int32)).cuda()
+    image = torch.full((2 * H, W, 3), float("nan"), dtype=torch.float64, device="cuda")
+    feats = [torch.full((2 * H * W * 8,), float("nan"), dtype=torch.float64, device="cuda") for _ in range(3)]
+    torch.cuda.synchronize()
+    dev.render_device(cam, p, d_rows.data_ptr(), 2 * H, image.data_ptr(), a_stream.cuda_stream, None, asynchronous=True)
+    for f_ in feats:
+        dev.features_device(cam, p, d_rows.data_ptr(), 2 * H, f_.data_ptr(), b_stream.cuda_stream, specular=True)
+    b_stream.synchronize()
+    dev.wait(a_stream.cuda_stream)
+    assert np.array_equal(image.cpu().numpy().view(np.uint64), ref_render.view(np.uint64))       # the render's bits stay its own
+    for f_ in feats:
+        assert_same_bits(f_.cpu().numpy().view(F.FEATURE_DTYPE), ref[order], "beside a render")
+    assert np.array_equal(dev.render(cam, p, rows).view(np.uint64), ref_render.view(np.uint64))
+
+
+def test_render_adaptive_with_specular_guides(rt):
+    W = H = 24
+    n = W * H
+    spp, total_spp, max_units = 4, 32, 4
+    s = rt.HostScene("random_scene", seed=2022)
+    cam, bg = s.default_view(1.0)
+    dev = rt.DeviceScene(s.desc)
+    p = rt.make_params(W, H, spp, 50, bg, seed=2022)
+    run = lambda **kw: rt.render_adaptive(dev, cam, p, total_spp, rounds=2, max_units=max_units, want_state=True, guides="all", **kw)
+    eq = lambda a, b: np.array_equal(a.cpu().numpy().view(np.uint64), b.cpu().numpy().view(np.uint64))
+    out, counts, log, state = run(specular=True)
+    out2, counts2, log2, state2 = run(specular=True)
+    assert eq(out, out2) and eq(counts, counts2) and log == log2 and eq(state["feat_acc"], state2["feat_acc"]) and eq(state["feat"], state2["feat"])
+    p2 = rt.make_params(W, H, spp, 50, bg, seed=2022, n_frames=2)
+    want = dev.features(cam, p2, all_rows(H, 2), specular=True).view(np.float64).reshape(2, n, 8)
+    assert_same_bits(state["feat"].cpu().numpy(), want, "the initial records are the flagged rt_features'")
+    plain = run()
+    assert not eq(plain[3]["feat"], state["feat"])          # glass and mirrors are in the view
+    acc = state["feat_acc"].cpu().numpy()
+    assert sum(r["total"] for r in log) > 0 and np.all(acc[..., 7] >= want[..., 7])
+    dev.close()

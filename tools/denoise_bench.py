@@ -15,6 +15,10 @@ frame A + B, of rt_denoise's result and of the dual filter's.
 
 --surfaces: every feature call takes RT_FLAG_SURFACES (the guides are those of the surfaces behind participating media); the
 lines say "surfaces": true. Run once without and once with it to compare the MSE after the filter.
+
+--specular: every feature call takes RT_FLAG_SPECULAR (the guides follow each sample through glass and mirrors); the lines say
+"specular": true. Run once without and once with it (same seeds, same --ref-spp target) to compare the MSE of both filters under
+first-hit and under specular guides.
 """
 import argparse
 import json
@@ -60,7 +64,7 @@ def dual(a, torch, dev, cam, bg, rows, stream, spp, target, st):
     d_feat2 = torch.empty(2 * n * 8, dtype=torch.float64, device="cuda")
     d_out, d_var = torch.empty(n * 3, dtype=torch.float64, device="cuda"), torch.empty(n, dtype=torch.float64, device="cuda")
     p2 = rt.make_params(W, H, half, 50, bg, seed=a.seed, n_frames=2, spp_chunk=1)
-    f_ms = timed(torch, stream, lambda: dev.features_device(cam, p2, d_rows2.data_ptr(), 2 * H, d_feat2.data_ptr(), sp, surfaces=a.surfaces), a.steps, a.warmup)
+    f_ms = timed(torch, stream, lambda: dev.features_device(cam, p2, d_rows2.data_ptr(), 2 * H, d_feat2.data_ptr(), sp, surfaces=a.surfaces, specular=a.specular), a.steps, a.warmup)
     dev.render_device(cam, p2, d_rows2.data_ptr(), 2 * H, d_rgb2.data_ptr(), sp, st)       # (the pool may grow here)
     dev.wait(sp)
     ms = []
@@ -91,7 +95,7 @@ def dual(a, torch, dev, cam, bg, rows, stream, spp, target, st):
     noisy = d_sum.cpu().numpy().reshape(H, W, 3)
     mse = lambda img: float(np.mean((display(img, 2 * half) - target) ** 2))
     m_noisy, m_single, m_dual = mse(noisy), mse(den_single), mse(den_dual)
-    print(json.dumps({"dual": True, "scene": a.scene, "surfaces": a.surfaces, "spp": "2 x %d" % half, "n_iter": a.n_iter, "var_iter": q.var_iter,
+    print(json.dumps({"dual": True, "scene": a.scene, "surfaces": a.surfaces, "specular": a.specular, "spp": "2 x %d" % half, "n_iter": a.n_iter, "var_iter": q.var_iter,
                       "sigma_color": pd.sigma_color, "var_floor": q.var_floor, "render_2_frames_ms": round(r_ms, 3),
                       "features_2_frames_ms": round(f_ms, 3), "denoise_ms": [round(x, 4) for x in s_ms],
                       "denoise_dual_ms": [round(x, 4) for x in d_ms], "denoise_dual_ms_without_variance_out": round(novar_ms, 4),
@@ -113,6 +117,7 @@ def main():
     ap.add_argument("--seed", type=int, default=2022)
     ap.add_argument("--dual", action="store_true", help="also the variance-guided filter on two half-sample frames")
     ap.add_argument("--surfaces", action="store_true", help="RT_FLAG_SURFACES on every feature call")
+    ap.add_argument("--specular", action="store_true", help="RT_FLAG_SPECULAR on every feature call")
     a = ap.parse_args()
     import torch
     torch.zeros(1, device="cuda")
@@ -142,7 +147,7 @@ def main():
     target = display(d_rgb.cpu().numpy().reshape(H, W, 3), a.ref_spp)
     for spp in [int(x) for x in a.spp.split(",")]:
         p = rt.make_params(W, H, spp, 50, bg, seed=a.seed, spp_chunk=1)
-        f_ms = timed(torch, stream, lambda: dev.features_device(cam, p, d_rows.data_ptr(), H, d_feat.data_ptr(), sp, surfaces=a.surfaces), a.steps, a.warmup)
+        f_ms = timed(torch, stream, lambda: dev.features_device(cam, p, d_rows.data_ptr(), H, d_feat.data_ptr(), sp, surfaces=a.surfaces, specular=a.specular), a.steps, a.warmup)
         r_ms = render(p, 3)
         dp = rt.denoise_params(W, H, spp, n_iter=a.n_iter)
         d_ws = torch.empty(rt.denoise_workspace_bytes(dp), dtype=torch.uint8, device="cuda")
@@ -152,7 +157,7 @@ def main():
         noisy = d_rgb.cpu().numpy().reshape(H, W, 3)
         den = d_out.cpu().numpy().reshape(H, W, 3)
         mse = lambda img: float(np.mean((display(img, spp) - target) ** 2))
-        print(json.dumps({"scene": a.scene, "surfaces": a.surfaces, "spp": spp, "n_iter": a.n_iter, "render_ms": round(r_ms, 3), "features_ms": round(f_ms, 3),
+        print(json.dumps({"scene": a.scene, "surfaces": a.surfaces, "specular": a.specular, "spp": spp, "n_iter": a.n_iter, "render_ms": round(r_ms, 3), "features_ms": round(f_ms, 3),
                           "denoise_ms": [round(x, 4) for x in ms], "denoise_ms_with_row_list": round(rows_ms, 4),
                           "denoise_vs_render": round(min(ms) / r_ms, 5),
                           "workspace_mb": round(d_ws.numel() / 1e6, 1), "ref_spp": a.ref_spp, "mse_noisy": round(mse(noisy), 6),

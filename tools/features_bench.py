@@ -13,6 +13,12 @@ aims: the hits are compared as a by-product); and ms of rt_render_device (depth 
 
 times the RT_FLAG_SURFACES call beside the plain one on the same view: three windows of each, alternating (plain, flagged, plain,
 ...), reported as "features_ms_windows" / "surfaces_ms_windows"; the spread of the plain windows is what a difference is read against.
+
+    python3 tools/features_bench.py --specular [--scenes final_scene,c2] [--spp 4] [--no-render]
+
+does the same for the RT_FLAG_SPECULAR call ("specular_ms_windows", "specular_over_plain"), and adds what a counter call of each
+reports: "segments_per_sample" (rt_stats.rays / paths under the flag: the world.hit calls a sample makes) and the node visits of both,
+so the time ratio can be read against the extra traversal work the flag asks for.
 """
 import argparse
 import ctypes as C
@@ -97,6 +103,7 @@ def main():
     ap.add_argument("--seed", type=int, default=2022)
     ap.add_argument("--no-render", action="store_true")
     ap.add_argument("--surfaces", action="store_true", help="time the RT_FLAG_SURFACES call beside the plain one")
+    ap.add_argument("--specular", action="store_true", help="time the RT_FLAG_SPECULAR call beside the plain one")
     a = ap.parse_args()
     import torch
     torch.zeros(1, device="cuda")
@@ -141,6 +148,19 @@ def main():
                 extra = {"features_ms_windows": [round(x, 3) for x in plain_ms], "surfaces_ms_windows": [round(x, 3) for x in surf_ms],
                          "surfaces_over_plain": round(min(surf_ms) / min(plain_ms), 3),
                          "plain_spread": round(max(plain_ms) / min(plain_ms) - 1.0, 3), "media": s.desc.n_media}
+            if a.specular:
+                call = lambda flag: timed(torch, stream, lambda: dev.features_device(cam, p, d_rows.data_ptr(), H, d_feat.data_ptr(), stream.cuda_stream,
+                                                                                     specular=flag), a.steps, a.warmup)
+                windows = [(call(False), call(True)) for _ in range(3)]
+                plain_ms, spec_ms = [w[0] for w in windows], [w[1] for w in windows]
+                st0, st1 = F.rt_stats(), F.rt_stats()
+                dev.features_device(cam, p, d_rows.data_ptr(), H, d_feat.data_ptr(), stream.cuda_stream, stats=st0)
+                dev.features_device(cam, p, d_rows.data_ptr(), H, d_feat.data_ptr(), stream.cuda_stream, stats=st1, specular=True)
+                extra.update({"features_ms_windows": [round(x, 3) for x in plain_ms], "specular_ms_windows": [round(x, 3) for x in spec_ms],
+                              "specular_over_plain": round(min(spec_ms) / min(plain_ms), 3),
+                              "plain_spread": round(max(plain_ms) / min(plain_ms) - 1.0, 3),
+                              "segments_per_sample": round(st1.rays / st1.paths, 4), "node_visits_plain": st0.node_visits,
+                              "node_visits_specular": st1.node_visits})
             r_ms = float("nan")
             if not a.no_render:
                 st = F.rt_stats()
