@@ -982,6 +982,50 @@ int rt_adaptive_merge_features_device(const rt_feature *d_entry_features, const 
 int rt_adaptive_resolve_features_device(const rt_feature *d_acc, const double *d_acc_n, uint64_t n_pixels, uint32_t spp_out,
                                         rt_feature *d_out, void *hip_stream);
 
+/* ---- a BVH over caller geometry, built on the device -------------------------------------------------------
+ * Everything above needs only a valid rt_scene_desc; this makes its rt_bvh_node records from the caller's own leaves — a
+ * mesh, a million spheres — instead of the nine scene builders' (rt2022_host.h). A linear BVH: Morton order of the leaf
+ * boxes' centres, Karras' radix tree over the sorted keys, one bottom-up pass. The definition is exact (f64, no contraction),
+ * so the records are defined bit for bit (tests/bvh_ref.py restates them in numpy); DESIGN.md §4.15 has the reasoning.
+ *
+ * Input: n_leaves refs and boxes6[i] = {min[3], max[3]} of leaf i (rtb_ref_boxes computes them for the refs of a description).
+ * A ref goes into the tree exactly as given, flip bit included; a ref of kind RT_KIND_NODE is allowed (a subtree as a leaf).
+ * Output: max(1, n_leaves - 1) records; record j is the ref RT_MAKE_REF(RT_KIND_NODE, node_base + j) and the root is record
+ * 0, so the result can be appended to a pool that already holds node_base nodes. _pad is 0.
+ *
+ *   1. Scene box: lo[a] = min_i bmin_i[a], hi[a] = max_i bmax_i[a] (a two-stage reduction).
+ *   2. Key of leaf i, per axis: c = 0.5 * (bmin + bmax); e = hi - lo; q = e > 0 ? (c - lo) / e : 0;
+ *      k = (uint32) min(q * 2097152.0, 2097151.0) — 21 bits. The 63-bit Morton key has bit b of k_x at 3b + 2, of k_y at
+ *      3b + 1, of k_z at 3b.
+ *   3. Order: by (key, i) — a stable radix sort of (key, index) pairs.
+ *   4. Tree: Karras' radix tree over the n distinct 95-bit keys (key << 32) | i in that order. The range [a, b] of sorted
+ *      positions splits at g, the last position whose key shares more than the range's common prefix with key a; the children
+ *      are [a, g] and [g + 1, b]. A child of one position is that leaf's ref; otherwise the left child is internal node g and
+ *      the right one internal node g + 1. The root, [0, n - 1], is node 0. Built in parallel, one thread per internal node.
+ *   5. Bottom-up: a node's box is the component-wise min and max of its children's (exact, order-free). Stack need: a leaf
+ *      needs 1, a node with children needing l and r needs max(1 + l, r) — what rt_scene_create counts (a leaf that is itself a
+ *      subtree, a mover, a list or a medium counts as 1 here). If need(left) > need(right) the children are swapped before the
+ *      node's need is computed, which gives need(root) <= 1 + floor(log2 n): a need of k takes at least 2^(k-1) leaves. So a
+ *      million primitive leaves stay on the 22-entry stack however deep the radix tree is (clustered geometry makes it deep).
+ *      Record j stays node j whichever way its children are ordered.
+ *   6. n_leaves == 1: one record with left == right == the leaf and the leaf's box (the reference's span-1 node; its need is 2).
+ *
+ * RT_ERR_INVALID with rt_last_error() set and the output untouched: a null pointer; n_leaves == 0; node_base + max(1, n - 1)
+ * > 2^27; (device form) a workspace that is null, not 16-byte aligned or smaller than rt_bvh_workspace_bytes(n_leaves), node
+ * or box buffers that are not 16-byte aligned, refs that are not 4-byte aligned — all before any device call; and any box
+ * with a non-finite coordinate, a coordinate beyond 1e300 in magnitude or min > max — counted on the device by the reduction
+ * of step 1, before anything but workspace is written. Without a device rt_bvh_build then returns RT_ERR_DEVICE.
+ *
+ * rt_bvh_build_device is ordered on hip_stream (NULL = default stream) on the current device. It synchronises that stream
+ * once, to read the count of refused boxes, and makes no other host round trip. It allocates nothing: the caller gives it
+ * rt_bvh_workspace_bytes(n_leaves) bytes of 16-byte aligned device memory, whose contents before the call mean nothing and
+ * which the next build on the stream may reuse (a larger workspace serves a smaller build). rt_bvh_build stages host
+ * buffers through device memory of its own on the default stream. Out of scope: no SAH, no refit, no treelet optimisation. */
+uint64_t rt_bvh_workspace_bytes(uint32_t n_leaves);
+int rt_bvh_build_device(const uint32_t *d_leaf_refs, const double *d_boxes6, uint32_t n_leaves, uint32_t node_base,
+                        rt_bvh_node *d_out_nodes, void *d_workspace, uint64_t workspace_bytes, void *hip_stream);
+int rt_bvh_build(const uint32_t *leaf_refs, const double *boxes6, uint32_t n_leaves, uint32_t node_base, rt_bvh_node *out_nodes);
+
 /* write_color (main.rs:280-299): NaN→0, sqrt(c/spp), clamp [0,0.999], *255.999, floor. */
 void rt_write_color(const double rgb_sum[3], int32_t spp, uint8_t out_rgb[3]);
 /* Device form over n_pixels sums → n_pixels*3 bytes, on hip_stream. */

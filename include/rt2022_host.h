@@ -44,6 +44,15 @@ int rtb_shuffled_rows(uint32_t image_height, uint64_t seed, uint32_t *out_rows);
 int rtb_bvh_build(const uint32_t *leaf_refs, const double *boxes6, uint32_t n, uint64_t seed,
                   rt_bvh_node *out_nodes, uint32_t max_nodes);
 
+/* The reference's bounding_box(time0, time1) of `n` refs of a description, out_boxes6[i] = {min[3], max[3]}: the leaf boxes
+ * rt_bvh_build* wants (rt2022.h). The rules are the host layer's own, restated on the records: the sphere; the moving sphere
+ * over both times; a rect's +-0.0001 padding; the box; the triangle, which has no padding; the ring; a medium, which is its
+ * boundary's box; Translate and Zoom of the child's box; RotateY's eight corners of the child's box over (0, 1) whatever
+ * interval is asked for (RotateY::new, mod.rs:188-228); a list, the union of its items; a node, its stored box. The flip bit
+ * of a ref changes nothing. RT_ERR_INVALID: a null argument, a ref of an unknown kind or out of its pool, a ref without a
+ * box — an empty list is one — and nesting deeper than 64. */
+int rtb_ref_boxes(const rt_scene_desc *desc, const uint32_t *refs, uint32_t n, double time0, double time1, double *out_boxes6);
+
 /* Image output (main.rs:191-201): place the row sums (row_ids order) at
  * (x, H-1-y) of an RGB8 image through write_color. rgb8 = width*height*3 bytes. */
 int rtb_fill_image(const double *rgb_sum, const uint32_t *row_ids, uint32_t n_rows, uint32_t width,

@@ -17,6 +17,9 @@ from .device import (ADAPTIVE_LUMA_FLOOR, adaptive_merge_device, adaptive_params
                      adaptive_resolve_device, adaptive_scale, adaptive_workspace_bytes, pixel_ids, plan_units, render_adaptive)
 from .device import TEMPORAL_DEFAULTS, temporal, temporal_device, temporal_params, temporal_workspace_bytes  # noqa: F401
 from ._ffi import FEATURE_DTYPE, HIT_DTYPE, QUERY_RAY_DTYPE, RADIANCE_RAY_DTYPE, TEMPORAL_PIXEL_DTYPE  # noqa: F401
+from ._ffi import BVH_NODE_DTYPE  # noqa: F401
+from .host import rebuild_bvh, ref_boxes, tree_leaves  # noqa: F401
+from .device import bvh_build, bvh_build_device, bvh_workspace_bytes  # noqa: F401
 
 __all__ = ["DescBuilder", "HostScene", "DeviceScene", "DeviceSceneSet", "camera_new", "fill_image", "make_params", "shuffled_rows",
            "write_color", "write_jpeg", "load_image", "RtError", "lib", "make_ref", "ref_kind", "ref_index", "query_rays",
@@ -26,4 +29,5 @@ __all__ = ["DescBuilder", "HostScene", "DeviceScene", "DeviceSceneSet", "camera_
            "pixel_ids", "adaptive_params", "adaptive_workspace_bytes", "adaptive_plan", "adaptive_plan_device", "adaptive_merge_device",
            "adaptive_resolve_device", "adaptive_scale", "plan_units", "render_adaptive", "ADAPTIVE_LUMA_FLOOR",
            "adaptive_merge_features_device", "adaptive_resolve_features_device",
-           "temporal", "temporal_device", "temporal_params", "temporal_workspace_bytes", "TEMPORAL_DEFAULTS", "TEMPORAL_PIXEL_DTYPE"]
+           "temporal", "temporal_device", "temporal_params", "temporal_workspace_bytes", "TEMPORAL_DEFAULTS", "TEMPORAL_PIXEL_DTYPE",
+           "ref_boxes", "rebuild_bvh", "tree_leaves", "bvh_build", "bvh_build_device", "bvh_workspace_bytes", "BVH_NODE_DTYPE"]

@@ -252,6 +252,12 @@ class rt_adaptive_params(C.Structure):
 # The rt_adaptive_* structure, in the order of rtb_adaptive_abi_sizes.
 ADAPTIVE_ABI_STRUCTS = [rt_adaptive_params]
 
+# numpy twins of rt_bvh_node, rt_sphere and rt_triangle (arrays of them go to and from rt_bvh_build and the bulk adders as they are)
+BVH_NODE_DTYPE = np.dtype([("bmin", "<f8", (3,)), ("bmax", "<f8", (3,)), ("left", "<u4"), ("right", "<u4"), ("_pad", "<u4", (2,))])
+SPHERE_DTYPE = np.dtype([("center", "<f8", (3,)), ("radius", "<f8"), ("mat", "<u4"), ("_pad", "<u4")])
+TRIANGLE_DTYPE = np.dtype([("a", "<f8", (3,)), ("b", "<f8", (3,)), ("c", "<f8", (3,)), ("mat", "<u4"), ("_pad", "<u4")])
+RT_BVH_MAX_NODES = 1 << 27
+
 ABI_STRUCTS = [rt_bvh_node, rt_sphere, rt_moving_sphere, rt_rect, rt_box, rt_triangle, rt_ring, rt_medium, rt_xform,
                rt_list, rt_material, rt_texture, rt_image, rt_perlin, rt_scene_desc, rt_camera, rt_params, rt_stats,
                rt_query_ray, rt_hit]
@@ -274,6 +280,7 @@ ABI_SYMBOLS = [
     "rtb_last_error", "rtb_abi_sizes", "rtb_radiance_abi_sizes", "rtb_features_abi_sizes", "rtb_denoise_abi_sizes",
     "rtb_denoise_dual_abi_sizes",
     "rt_temporal_workspace_bytes", "rt_temporal", "rt_temporal_device", "rtb_temporal_abi_sizes",
+    "rt_bvh_workspace_bytes", "rt_bvh_build_device", "rt_bvh_build", "rtb_ref_boxes",
     "rt_debug_math_device", "rt_debug_rng_device", "rt_debug_scene_info", "rt_debug_trace_variant", "rt_debug_set_tuning", "rt_debug_set_engine", "rt_debug_census", "rt_debug_pass_timing", "rt_debug_traffic_probe", "rt_debug_valu_probe", "rt_debug_set_partial_ring", "rt_debug_f32_slabs",
 ]
 
@@ -324,6 +331,11 @@ def lib():
     L.rt_temporal.argtypes = [vp, vp, vp, P(rt_camera), vp, P(rt_camera), P(rt_temporal_params), vp, vp, P(dbl)]
     L.rt_temporal_device.argtypes = [vp, vp, vp, P(rt_camera), vp, P(rt_camera), P(rt_temporal_params), vp, vp, vp, vp]
     L.rtb_temporal_abi_sizes.argtypes = [P(u32), u32]
+    L.rt_bvh_workspace_bytes.argtypes = [u32]
+    L.rt_bvh_workspace_bytes.restype = u64
+    L.rt_bvh_build_device.argtypes = [vp, vp, u32, u32, vp, vp, u64, vp]
+    L.rt_bvh_build.argtypes = [vp, vp, u32, u32, vp]
+    L.rtb_ref_boxes.argtypes = [P(rt_scene_desc), vp, u32, dbl, dbl, vp]
     L.rt_render_pixels.argtypes = [vp, P(rt_camera), P(rt_params), vp, u64, vp, P(rt_stats)]
     L.rt_render_pixels_device.argtypes = [vp, P(rt_camera), P(rt_params), vp, u64, vp, vp, P(rt_stats)]
     L.rt_adaptive_workspace_bytes.argtypes = [P(rt_adaptive_params)]

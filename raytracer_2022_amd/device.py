@@ -488,6 +488,31 @@ def render_adaptive(dev, cam, params, total_spp, rounds=2, max_units=4, denoise=
     return out, counts, log
 
 
+def bvh_workspace_bytes(n_leaves):
+    """rt_bvh_workspace_bytes: device bytes bvh_build_device needs for a build over n_leaves leaves."""
+    return int(F.lib().rt_bvh_workspace_bytes(n_leaves))
+
+
+def bvh_build(refs, boxes6, node_base=0):
+    """rt_bvh_build with host buffers: n leaf refs and their (n, 6) {min, max} boxes → the max(1, n - 1) records of the linear
+    BVH built on the device (BVH_NODE_DTYPE), record j being the node ref node_base + j and record 0 the root."""
+    r = np.ascontiguousarray(refs, dtype=np.uint32)
+    b = np.ascontiguousarray(boxes6, dtype=np.float64)
+    if b.size != 6 * r.size:
+        raise ValueError("boxes6 must hold six coordinates per ref")
+    out = np.zeros(max(1, r.size - 1), dtype=F.BVH_NODE_DTYPE)
+    F.check(F.lib().rt_bvh_build(r.ctypes.data, b.ctypes.data, r.size, node_base, out.ctypes.data))
+    return out
+
+
+def bvh_build_device(d_refs_ptr, d_boxes_ptr, n_leaves, d_out_ptr, d_workspace_ptr, workspace_bytes, node_base=0, stream_ptr=None):
+    """rt_bvh_build_device: device pointers in (n uint32 refs, n x 6 doubles, room for max(1, n - 1) rt_bvh_node records,
+    bvh_workspace_bytes(n) bytes of workspace; nodes, boxes and workspace 16-byte aligned), ordered on `stream_ptr`
+    (hipStream_t as int), which it synchronises once. With torch: tensor.data_ptr() and torch.cuda.current_stream().cuda_stream."""
+    F.check(F.lib().rt_bvh_build_device(C.c_void_p(d_refs_ptr), C.c_void_p(d_boxes_ptr), n_leaves, node_base, C.c_void_p(d_out_ptr),
+                                        C.c_void_p(d_workspace_ptr), workspace_bytes, C.c_void_p(stream_ptr or 0)))
+
+
 class DeviceScene:
     """rt_scene: the flattened scene copied into HBM on the current HIP device."""
 

@@ -110,8 +110,10 @@ class HostScene:
 
 
 class DescBuilder:
-    """Assembles a flattened rt_scene_desc by hand (pool by pool). Used for small
-    known-answer scenes; real scenes come from HostScene."""
+    """Assembles a flattened rt_scene_desc by hand (pool by pool): small known-answer
+    scenes record by record, and a caller's own geometry through add_spheres /
+    add_triangles and bvh(), which builds the tree on the device. The reference's
+    nine scenes come from HostScene."""
 
     POOLS = [("nodes", F.rt_bvh_node), ("spheres", F.rt_sphere), ("moving_spheres", F.rt_moving_sphere),
              ("rects", F.rt_rect), ("boxes", F.rt_box), ("triangles", F.rt_triangle), ("rings", F.rt_ring),
@@ -223,6 +225,49 @@ class DescBuilder:
         self.pools["list_items"] += [C.c_uint32(r) for r in refs]
         return self._add("lists", F.RT_KIND_LIST, F.rt_list(first=first, count=len(refs)))
 
+    # -- bulk geometry and the device BVH builder (rt_bvh_build, include/rt2022.h)
+    def _add_bulk(self, pool, kind, ctype, records):
+        """The records of a numpy array whose dtype is the twin of `ctype`, appended to `pool` → their refs (uint32 array)."""
+        first = len(self.pools[pool])
+        if first + len(records) > F.RT_REF_INDEX_MASK + 1:
+            raise ValueError("pool '%s' would outgrow a ref's index field" % pool)
+        if len(records):
+            self.pools[pool] += list((ctype * len(records)).from_buffer_copy(records.tobytes()))
+        return (np.uint32(kind << F.RT_REF_KIND_SHIFT) | np.arange(first, first + len(records), dtype=np.uint32)).astype(np.uint32)
+
+    def add_triangles(self, vertices, mat):
+        """(n, 3, 3) vertices — triangle, corner, xyz — of material `mat` → n refs. The records are triangle()'s."""
+        v = np.ascontiguousarray(vertices, dtype=np.float64)
+        if v.ndim != 3 or v.shape[1:] != (3, 3):
+            raise ValueError("vertices must have the shape (n, 3, 3)")
+        rec = np.zeros(len(v), dtype=F.TRIANGLE_DTYPE)
+        rec["a"], rec["b"], rec["c"], rec["mat"] = v[:, 0], v[:, 1], v[:, 2], mat
+        return self._add_bulk("triangles", F.RT_KIND_TRIANGLE, F.rt_triangle, rec)
+
+    def add_spheres(self, centers, radii, mat):
+        """(n, 3) centres and (n,) radii of material `mat` → n refs. The records are sphere()'s."""
+        c = np.ascontiguousarray(centers, dtype=np.float64)
+        r = np.ascontiguousarray(radii, dtype=np.float64)
+        if c.ndim != 2 or c.shape[1] != 3 or r.shape != (len(c),):
+            raise ValueError("centers must have the shape (n, 3) and radii the shape (n,)")
+        rec = np.zeros(len(c), dtype=F.SPHERE_DTYPE)
+        rec["center"], rec["radius"], rec["mat"] = c, r, mat
+        return self._add_bulk("spheres", F.RT_KIND_SPHERE, F.rt_sphere, rec)
+
+    def bvh(self, refs, boxes6=None, time0=0.0, time1=1.0, build=None):
+        """A BVH over `refs` built on the device (rt_bvh_build), appended to the node pool → the root's ref. boxes6: (n, 6)
+        {min, max} per ref; None: the reference's bounding_box(time0, time1) of each ref over this builder's pools.
+        build(refs, boxes6, node_base) → nodes: the builder to use instead of the device's (tests/bvh_ref.py)."""
+        if build is None:
+            from .device import bvh_build as build
+        refs = np.ascontiguousarray(refs, dtype=np.uint32)
+        if boxes6 is None:
+            boxes6 = ref_boxes(self.desc(), refs, time0, time1)
+        base = len(self.pools["nodes"])
+        nodes = np.ascontiguousarray(build(refs, boxes6, base), dtype=F.BVH_NODE_DTYPE)
+        self.pools["nodes"] += list((F.rt_bvh_node * len(nodes)).from_buffer_copy(nodes.tobytes()))
+        return F.make_ref(F.RT_KIND_NODE, base)
+
     def light(self, ref):
         self.pools["lights"].append(C.c_uint32(ref))
 
@@ -244,3 +289,60 @@ class DescBuilder:
         d.image_data_bytes = len(self.image_data)
         d.image_data = C.cast(data, C.POINTER(C.c_uint8))
         return d
+
+
+def ref_boxes(desc, refs, time0=0.0, time1=1.0):
+    """rtb_ref_boxes: the reference's bounding_box(time0, time1) of each ref of `desc` → (n, 6) {min, max}."""
+    refs = np.ascontiguousarray(refs, dtype=np.uint32)
+    out = np.zeros((len(refs), 6), dtype=np.float64)
+    F.check(F.lib().rtb_ref_boxes(C.byref(desc), refs.ctypes.data, len(refs), time0, time1, out.ctypes.data))
+    return out
+
+
+def desc_nodes(desc):
+    """The node pool of a description as a BVH_NODE_DTYPE array (a copy)."""
+    if not desc.n_nodes:
+        return np.zeros(0, dtype=F.BVH_NODE_DTYPE)
+    return np.frombuffer(C.string_at(desc.nodes, desc.n_nodes * C.sizeof(F.rt_bvh_node)), dtype=F.BVH_NODE_DTYPE).copy()
+
+
+def tree_leaves(desc):
+    """The leaves of the root tree of a description whose root is a NODE ref: the non-node refs reached through nodes only,
+    left before right; a span-1 node's leaf counts once → uint32 array."""
+    if F.ref_kind(desc.root) != F.RT_KIND_NODE:
+        raise ValueError("the description's root is not a NODE ref")
+    nodes = desc_nodes(desc)
+    left, right = nodes["left"].tolist(), nodes["right"].tolist()
+    leaves, seen, stack = [], set(), [desc.root]
+    while stack:
+        ref = stack.pop()
+        if F.ref_kind(ref) != F.RT_KIND_NODE:
+            leaves.append(ref)
+            continue
+        i = F.ref_index(ref)
+        if i in seen:
+            continue
+        seen.add(i)
+        if right[i] != left[i]:
+            stack.append(right[i])
+        stack.append(left[i])
+    return np.array(leaves, dtype=np.uint32)
+
+
+def rebuild_bvh(desc, time0=0.0, time1=1.0, build=None):
+    """A copy of `desc` (root: a NODE ref) whose root tree is rebuilt by rt_bvh_build over the same leaves, boxed by
+    ref_boxes over (time0, time1). The new nodes are appended to the pool and `root` points at the first of them; the
+    replaced nodes stay in the pool, unreachable (which is legal). build(refs, boxes6, node_base) → nodes: the builder to
+    use instead of the device's (tests/bvh_ref.py)."""
+    if build is None:
+        from .device import bvh_build as build
+    refs = tree_leaves(desc)
+    boxes = ref_boxes(desc, refs, time0, time1)
+    new = np.ascontiguousarray(build(refs, boxes, desc.n_nodes), dtype=F.BVH_NODE_DTYPE)
+    both = np.concatenate([desc_nodes(desc), new])
+    arr = (F.rt_bvh_node * len(both)).from_buffer_copy(both.tobytes())
+    out = F.rt_scene_desc.from_buffer_copy(desc)
+    out.n_nodes, out.nodes = len(both), C.cast(arr, C.POINTER(F.rt_bvh_node))
+    out.root = F.make_ref(F.RT_KIND_NODE, desc.n_nodes)
+    out._keep = [desc, arr]                    # the other pools are the original's
+    return out
