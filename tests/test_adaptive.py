@@ -7,6 +7,7 @@ import pytest
 
 import adaptive_ref as R
 from raytracer_2022_amd import _ffi as F
+from test_denoise import LONG_HEIGHTS, LONG_W, long_row_lists
 
 pytestmark = pytest.mark.gpu
 
@@ -76,6 +77,123 @@ def test_plan_matches_the_restatement(rt, w, h):
     # frames at the top of the range, and ids that pass 2^32
     top = rt.adaptive_params(w, h, 1.0, max_units, first_frame=0xFFFFFFFF - max_units)
     check_plan(rt.adaptive_plan(e.reshape(h, w), top), R.plan(e, w, h, 1.0, max_units, 0xFFFFFFFF - max_units), "top frames")
+
+
+# ---- more than one block of tiles: the carry loop of ad_offsets ----------------------------------------------------------
+# ad_offsets scans the tile totals kAdBlock = 256 at a time with a running carry; a tile is 1024 pixels, so the loop takes a
+# second trip above 256 * 1024 = 262 144 pixels. 512 x 512 is exactly 256 tiles (one trip, full), 513 x 512 is 257 tiles (a
+# second trip of one partly empty tile), 1031 x 509 is 513 tiles (a third trip of one).
+TRIP_PIXELS = 256 * 1024
+BIG_SIZES = [(512, 512), (513, 512), (1031, 509)]
+BIG_MAPS = ["hostile", "random", "one hot pixel in the last place", "units in tiles from 256 on only", "either side of the trip"]
+
+
+def big_map(name, w, h, max_units, g):
+    n = w * h
+    if name in ("hostile", "random", "one hot pixel in the last place"):
+        return error_maps(w, h, max_units, g)[name]
+    e = np.zeros(n)
+    if name == "units in tiles from 256 on only":            # (no such tile at 512 x 512: the map is empty there, and so is the plan)
+        e[TRIP_PIXELS:] = g.random(n - TRIP_PIXELS) * (max_units + 1.5)
+    else:                                                    # the last pixel of tile 255 and, where there is one, the first of tile 256
+        e[TRIP_PIXELS - 1] = 2.5
+        e[TRIP_PIXELS:TRIP_PIXELS + 1] = 3.5
+    return e
+
+
+@pytest.mark.parametrize("name", BIG_MAPS)
+@pytest.mark.parametrize("w,h", BIG_SIZES)
+def test_plan_beyond_one_block_of_tiles(rt, w, h, name):
+    """ad_offsets' carry loop (pt_adaptive.hip): its second trip starts at 262 145 pixels, its third at 524 289. Units,
+    offsets, entries and total against adaptive_ref.plan."""
+    max_units, scale, first = 5, 0.73, 7
+    e = big_map(name, w, h, max_units, np.random.default_rng(w * 1000 + h))
+    want = R.plan(e, w, h, scale, max_units, first)
+    first_trip = int(want[1][TRIP_PIXELS])                   # the units of the first 256 tiles, and those of the tiles behind them
+    later = want[3] - first_trip
+    assert (later > 0) == (w * h > TRIP_PIXELS)
+    if name == "either side of the trip":
+        assert (first_trip, later) == (1, 2 if w * h > TRIP_PIXELS else 0)
+    elif name in ("hostile", "random"):
+        assert first_trip > 0
+    else:
+        assert first_trip == (1 if w * h == TRIP_PIXELS and name == "one hot pixel in the last place" else 0)
+    check_plan(rt.adaptive_plan(e.reshape(h, w), rt.adaptive_params(w, h, scale, max_units, first_frame=first)), want, (w, h, name))
+
+
+def test_plan_beyond_one_block_of_tiles_rows_and_capacities(rt):
+    """513 x 512, 257 tiles: ad_offsets' second trip (it starts at 262 145 pixels) under a shuffled row list and with
+    capacities total - 1, total and 0 (ad_emit reads the grand total from behind the last tile offset: the carry after the
+    second trip)."""
+    w, h, max_units = 513, 512, 5
+    g = np.random.default_rng(513512)
+    e = big_map("random", w, h, max_units, g)
+    p = rt.adaptive_params(w, h, 1.0, max_units, first_frame=3)
+    rows = g.permutation(h).astype(np.uint32)
+    want = R.plan(e, w, h, 1.0, max_units, 3, row_ids=rows)
+    total = want[3]
+    assert total > w * h
+    check_plan(rt.adaptive_plan(e.reshape(h, w), p, row_ids=rows), want, "rows")
+    check_plan(rt.adaptive_plan(e.reshape(h, w), p, row_ids=rows, capacity=total), want, "exact")
+    short = (want[0], want[1], None, total)                  # (what adaptive_ref.plan returns for a capacity below the total)
+    check_plan(rt.adaptive_plan(e.reshape(h, w), p, row_ids=rows, capacity=total - 1), short, "one short")
+    check_plan(rt.adaptive_plan(e.reshape(h, w), p, row_ids=rows, capacity=0), short, "capacity 0")
+
+
+@pytest.mark.parametrize("w,h,max_units", [(65, 3, 0xFFFFFFFF - 7), (513, 512, 1 << 31)])
+def test_totals_beyond_32_bits(rt, w, h, max_units):
+    """Every pixel at the cap, counted only (capacity 0). 65 x 3: one tile whose thread sums, wave sums and total pass 2^32
+    (total = 195 * (2^32 - 8) = 837 518 621 160). 513 x 512: every tile total is 2^41, and ad_offsets' carry and its second
+    trip (from 262 145 pixels on) run on 64-bit sums."""
+    first = 7
+    e = np.full(w * h, 1e300)
+    want = R.plan(e, w, h, 1.0, max_units, first, capacity=0)
+    assert want[3] == w * h * max_units > (1 << 32) and want[2] is None
+    if (w, h) == (65, 3):
+        assert want[3] == 837_518_621_160
+    check_plan(rt.adaptive_plan(e.reshape(h, w), rt.adaptive_params(w, h, 1.0, max_units, first_frame=first), capacity=0), want, (w, h))
+
+
+@pytest.mark.parametrize("h", LONG_HEIGHTS)
+def test_row_lists_longer_than_the_row_kernels_block(rt, h):
+    """dn_rows' stride loop (pt_denoise.hip, one workgroup of 1024 threads): a thread's second trip starts at 1025 rows. Both
+    forms of the planner against adaptive_ref.plan under a shuffled list; the device form refuses a repeat across trips, a
+    repeat inside one thread and an id out of range on the last trip with nothing written, and takes the good list on the
+    same workspace afterwards."""
+    import torch
+    w, max_units = LONG_W, 5
+    n = w * h
+    rows, bad = long_row_lists(h, h + 4)
+    e = error_maps(w, h, max_units, np.random.default_rng(h))["hostile"]
+    p = rt.adaptive_params(w, h, 1.0, max_units, first_frame=2)
+    want = R.plan(e, w, h, 1.0, max_units, 2, row_ids=rows)
+    total = want[3]
+    assert total > 0
+    check_plan(rt.adaptive_plan(e.reshape(h, w), p, row_ids=rows), want, "host form")
+    cu = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    d_err = cu(e)
+    d_units = torch.full((n,), -1, dtype=torch.int32, device="cuda")
+    d_offsets = torch.full((n + 1,), -1, dtype=torch.int64, device="cuda")
+    d_entries = torch.full((total,), -1, dtype=torch.int64, device="cuda")
+    d_ws = torch.full((rt.adaptive_workspace_bytes(p),), 0xFF, dtype=torch.uint8, device="cuda")
+    sp = torch.cuda.current_stream().cuda_stream
+    for fault, lst in bad.items():
+        d_bad = cu(lst.view(np.int32))
+        torch.cuda.synchronize()
+        got = C.c_uint64(123)
+        rc = rt.lib().rt_adaptive_plan_device(C.c_void_p(d_err.data_ptr()), C.c_void_p(d_bad.data_ptr()), C.byref(p), C.c_void_p(d_units.data_ptr()),
+                                              C.c_void_p(d_offsets.data_ptr()), C.c_void_p(d_entries.data_ptr()), total, C.c_void_p(d_ws.data_ptr()),
+                                              C.c_void_p(sp), C.byref(got))
+        assert rc == F.RT_ERR_INVALID and "not a permutation" in rt.lib().rt_last_error().decode(), fault
+        torch.cuda.synchronize()
+        assert torch.all(d_units == -1) and torch.all(d_offsets == -1) and torch.all(d_entries == -1) and got.value == 123, fault
+    d_rows = cu(rows.view(np.int32))
+    torch.cuda.synchronize()
+    assert rt.adaptive_plan_device(d_err.data_ptr(), p, d_units.data_ptr(), d_offsets.data_ptr(), d_entries.data_ptr(), total, d_ws.data_ptr(),
+                                   d_rows.data_ptr(), sp) == total
+    torch.cuda.synchronize()
+    check_plan((d_units.cpu().numpy().view(np.uint32), d_offsets.cpu().numpy().view(np.uint64), d_entries.cpu().numpy().view(np.uint64), total),
+               want, "good rows after bad ones")
 
 
 def test_device_form_merge_resolve_and_the_two_half_recipe(rt):

@@ -1,0 +1,318 @@
+"""The persistent kernels past their first trip: calls with more work items than the grid has lanes, every record against the
+CPU oracle bit for bit.
+
+The bound. launch_persistent (pt_traverse.hpp) and the megakernel's launcher start at most as many workgroups as the device
+holds at once, and a CU holds at most 32 waves of 64 lanes, whatever the instance's occupancy. So no grid has more than
+L = multi_processor_count * 2048 lanes (the CU count is read from torch). A lane takes one item at a time, so a call with
+more than 2 L items makes some lane take a third one, by pigeonhole — and most lanes a second. Below L items every lane
+claims one item on its first pass through the done arm and its next wave_claim finds nothing: the arm's "write the record,
+take the next item" never runs. Every test here makes calls of n > 2 L items; the second trip of each kernel starts at
+n = (its grid's lanes) + 1 <= L + 1.
+
+A million records against the oracle. A base batch of M = 4099 distinct items (or, in the row forms, the 512 pixels of a
+64 x 8 image) has its reference computed in full, by the compositions of oracle calls the other modules use. The big call
+is K independent random permutations of the base, concatenated, K = ceil((2 L + 1) / M): n = K M > 2 L, a lane's successive
+items differ, a wave mixes kinds. EVERY record of the big call must equal the reference record of its base item, and the
+call's counters K times the base's reference counters. What the base batch shows (hits and misses, both faces, media draws)
+is asserted on the reference, not on the device's output."""
+import types
+
+import numpy as np
+import pytest
+
+from raytracer_2022_amd import _ffi as F
+
+import specular_ref as SP
+import surface_ref as S
+import trace_scenes as TS
+from test_features import assert_same_bits
+from test_features_pixels import check_counters as check_first_hit_counters, oracle_ids
+from test_query import (assert_prims_consistent, assert_records_equal, bounce_rays, camera_rays, counters, every_kind_scene, mixed_rays,
+                        oracle_hits, randomise_windows)
+from test_render_pixels import counters as render_counters, same_bits
+from test_specular import check_counters as check_specular_counters
+from test_surfaces import check_counters as check_surface_counters
+
+pytestmark = pytest.mark.gpu
+
+M = 4099                                                   # the base batch: distinct work items, a prime
+
+
+@pytest.fixture(scope="module", autouse=True)
+def torch_first():
+    """Bring torch's HIP context up before the library's first call, as the other GPU test modules do."""
+    import torch
+    assert torch.cuda.is_available(), "gpu tests need a GPU: the HIP path has no fallback"
+    torch.zeros(1, device="cuda")
+
+
+@pytest.fixture(scope="module")
+def lanes():
+    """L: no persistent grid of this device has more lanes (32 waves of 64 a CU)."""
+    import torch
+    return torch.cuda.get_device_properties(0).multi_processor_count * 2048
+
+
+def copies(lanes, m):
+    """K: the number of permutations of an m-item base whose concatenation passes 2 L items."""
+    return (2 * lanes + 1 + m - 1) // m
+
+
+def tiled(m, k, seed):
+    """k independent random permutations of range(m), concatenated."""
+    g = np.random.default_rng(seed)
+    return np.concatenate([g.permutation(m) for _ in range(k)])
+
+
+def times(st, k):
+    """The traversal counters of k copies of the work `st` counted (node_visits and prim_tests; the callers scale the rest)."""
+    out = F.rt_stats()
+    out.node_visits = k * st.node_visits
+    for i, v in enumerate(st.prim_tests):
+        out.prim_tests[i] = k * v
+    return out
+
+
+# ---- 1. rt_intersect -----------------------------------------------------------------------------------------------------------
+# One scene per shape trav_dispatch selects — stack needs 16 (kStackTiny, the node table in LDS), 22 (kStackSmall), 30 (kStackMid)
+# and 64 (kStackLarge), each the deepest its instance holds — and the two scenes with media and every object kind.
+QUERY_SCENES = ["need 16", "need 22", "need 30", "need 64", "final_scene", "every_kind"]
+
+
+def query_scene(rt, which):
+    """-> (what keeps the pools alive, desc, cam, the stack need the scene was built for or None)"""
+    if which.startswith("need"):
+        need = int(which.split()[1])
+        d, cam, _, _ = TS.stack_need_scene(need)
+        return d, d, cam, need
+    if which == "every_kind":
+        b, d, cam = every_kind_scene(rt)
+        return b, d, cam, None
+    s = rt.HostScene(which, seed=2022)
+    return s, s.desc, s.default_view(1.5)[0], None
+
+
+def base_rays(rt, O, d, cam, seed):
+    """M rays of test_query.check_scene's mixture — camera rays, random rays through the scene's bounds, one bounce from the
+    hits of both (the oracle's hits here) — with random windows, times and RNG states, in random order."""
+    first, g = mixed_rays(rt, d, cam, 3 * 1600, seed)
+    h0, _ = oracle_hits(O, d, first)
+    rays = np.concatenate([first, bounce_rays(rt, h0, g, 1600)])
+    if len(rays) < M:
+        rays = np.concatenate([rays, camera_rays(rt, cam, M - len(rays), g)])
+    rays = randomise_windows(rays, g)
+    return np.ascontiguousarray(rays[g.permutation(len(rays))[:M]])
+
+
+@pytest.mark.parametrize("which", QUERY_SCENES)
+def test_queries_beyond_one_grid(rt, O, lanes, which):
+    """pt_query's q_refill, "write the record, take the next ray": runs from the grid's lanes + 1 rays on (at most L + 1).
+    n > 2 L rays on the counting and on the plain instance; on the tiny-stack scene also under RT_FLAG_ANY_HIT."""
+    keep, d, cam, need = query_scene(rt, which)
+    dev = rt.DeviceScene(d)
+    assert need is None or dev.info()["stack_need"] == need
+    base = base_rays(rt, O, d, cam, seed=len(which))
+    ref, st_ref = oracle_hits(O, d, base)
+    h = ref["hit"] == 1
+    assert h.sum() > 100 and (~h).sum() > 0
+    assert set(ref["front_face"][h].tolist()) == {0, 1}
+    assert d.n_media == 0 or ref["rng_draws"].sum() > 0
+    small = dev.intersect(base)
+    assert_records_equal(small, ref, "the base batch")
+    assert_prims_consistent(d, small)
+    k = copies(lanes, M)
+    idx = tiled(M, k, seed=k)
+    n = k * M
+    assert n > 2 * lanes
+    rays = base[idx]
+    got, st = dev.intersect(rays, want_stats=True)
+    assert_records_equal(got, ref[idx], which)
+    assert np.array_equal(got["prim"], small["prim"][idx])
+    nodes, prims, draws = counters(st_ref, ref)
+    assert st.rays == n and counters(st) == (k * nodes, [k * x for x in prims], k * draws)
+    assert np.array_equal(dev.intersect(rays).view(np.uint8), got.view(np.uint8))          # the plain instance, prim included
+    if which == "need 16":
+        assert np.array_equal(dev.intersect(rays, any_hit=True)["hit"], ref["hit"][idx])
+    dev.close()
+
+
+# ---- 2. rt_features_pixels ------------------------------------------------------------------------------------------------------
+PIX_W, PIX_H, PIX_SPP = 64, 48, 3                          # two frames: 6144 ids, M of them taken
+FLAGS = {"first hit": (False, False), "surfaces": (True, False), "specular": (False, True), "surfaces and specular": (True, True)}
+
+
+def pixel_scene(rt, which):
+    """final_scene (glass, metal, fog and a subsurface medium), or test_specular's mirror hall at this module's size: only
+    specular surfaces, chains of every length. -> (what keeps the pools alive, desc, cam, params)"""
+    if which == "mirror hall":
+        b = rt.DescBuilder()
+        b.set_root(b.list(SP.mirror_hall_refs(rt, b)))
+        return b, b.desc(), SP.mirror_hall_camera(rt, PIX_W, PIX_H), rt.make_params(PIX_W, PIX_H, PIX_SPP, 9, SP.HALL_BACKGROUND, seed=7, n_frames=2)
+    s = rt.HostScene(which, seed=2022)
+    cam, bg = s.default_view(PIX_W / PIX_H)
+    return s, s.desc, cam, rt.make_params(PIX_W, PIX_H, PIX_SPP, 50, bg, seed=2022, n_frames=2)
+
+
+class Reference:
+    """The reference of one flag combination on a list of ids: the records, what the samples met, and check(st, k): the
+    counters of a call that holds every id k times."""
+
+    def __init__(self, O, d, cam, p, ids, surfaces, specular):
+        n = len(ids) * p.spp
+        if specular:
+            self.records, st, info = SP.oracle_specular_ids(O, d, cam, p, ids, surfaces)
+            self.fronts = {front for _, _, front, _ in info.seen}
+            self.words, self.followed = info.words, int((info.lengths > 0).sum())
+            self.check = lambda got, k: check_specular_counters(got, times(st, k), types.SimpleNamespace(segments=k * info.segments, words=k * info.words),
+                                                                k * n, d, surfaces)
+        elif surfaces:
+            ip = p.width * p.height
+            rows = np.array([(int(i) // ip) * p.height + (int(i) % ip) // p.width for i in ids], dtype=np.uint32)
+            pixels = [(e, (int(i) % ip) % p.width) for e, i in enumerate(ids)]
+            self.records, st, seen, words = S.oracle_surface_features(O, d, cam, p, rows, pixels)
+            self.fronts, self.words = {kind[2] for kind in seen.kinds}, words
+            self.check = lambda got, k: check_surface_counters(got, times(st, k), k * words, k * n, d)
+        else:
+            self.records, st, seen = oracle_ids(O, d, cam, p, ids)
+            self.fronts, self.words, self.medium_words = {kind[2] for kind in seen.kinds}, seen.draws, seen.medium_draws
+            self.check = lambda got, k: check_first_hit_counters(got, times(st, k), types.SimpleNamespace(draws=k * seen.draws), k * len(ids), p.spp)
+
+
+@pytest.fixture(scope="module")
+def pixel_cases(rt, O):
+    """which -> (scene, desc, cam, params, device scene, the M base ids, reference(flags)): built on first use, computed once
+    and never changed."""
+    made = {}
+
+    def get(which):
+        if which not in made:
+            keep, d, cam, p = pixel_scene(rt, which)
+            ids = np.random.default_rng(len(which)).permutation(2 * PIX_W * PIX_H)[:M].astype(np.uint64)
+            assert len(np.unique(ids)) == M and ids.max() >= PIX_W * PIX_H
+            refs = {}
+
+            def reference(name):
+                if name not in refs:
+                    refs[name] = Reference(O, d, cam, p, ids, *FLAGS[name])
+                return refs[name]
+            made[which] = (keep, d, cam, p, rt.DeviceScene(d), ids, reference)
+        return made[which]
+    yield get
+    for case in made.values():
+        case[4].close()
+
+
+@pytest.mark.parametrize("with_counters", [True, False], ids=["counters", "plain"])
+@pytest.mark.parametrize("flags", list(FLAGS))
+@pytest.mark.parametrize("which", ["final_scene", "mirror hall"])
+def test_pixel_lists_beyond_one_grid(rt, pixel_cases, lanes, which, flags, with_counters):
+    """pt_features' f_done and pt_features_specular's s_done, "take the next pixel" through f_take (L.smp = 0, the split of
+    the entry index into L.row | L.px << 32) and f_add's first-sample branch on a lane that has already written another
+    entry: from the grid's lanes + 1 entries on (at most L + 1). n > 2 L entries, spp 3, ids of both frames."""
+    keep, d, cam, p, dev, ids, reference = pixel_cases(which)
+    surfaces, specular = FLAGS[flags]
+    ref = reference(flags)
+    hits = ref.records["hits"]
+    assert hits.sum() > 100 and (hits < PIX_SPP).any() and ref.words > 0
+    first = reference("first hit")
+    if which == "final_scene":
+        assert first.medium_words > 0 and reference("specular").fronts == {True, False} and reference("specular").followed > 30
+        assert reference("surfaces").records.tobytes() != first.records.tobytes()
+    else:
+        assert reference("specular").fronts == {True, False} and reference("specular").followed > 1000
+    k = copies(lanes, M)
+    idx = tiled(M, k, seed=k + len(flags))
+    assert k * M > 2 * lanes
+    if with_counters:
+        got, st = dev.features_pixels(cam, p, ids[idx], want_stats=True, surfaces=surfaces, specular=specular)
+        ref.check(st, k)
+    else:
+        got = dev.features_pixels(cam, p, ids[idx], surfaces=surfaces, specular=specular)
+    assert_same_bits(got, ref.records[idx], (which, flags))
+
+
+# ---- 3. rt_features in row form, 4. the renders on the megakernel -----------------------------------------------------------------
+ROW_W, ROW_H = 64, 8
+
+
+def long_row_list(lanes, n_rows, seed):
+    """More than 2 L / ROW_W rows: whole permutations of the image's n_rows row ids -> (the list, how often it holds each row)."""
+    k = copies(lanes, ROW_W * n_rows)
+    rows = tiled(n_rows, k, seed).astype(np.uint32)
+    assert rows.size * ROW_W > 2 * lanes and rows.size >= (2 * lanes + 1 + ROW_W - 1) // ROW_W
+    return rows, k
+
+
+@pytest.fixture(scope="module")
+def row_case(rt):
+    s = rt.HostScene("final_scene", seed=2022)
+    cam, bg = s.default_view(ROW_W / ROW_H)
+    dev = rt.DeviceScene(s.desc)
+    yield s, cam, bg, dev
+    dev.close()
+
+
+@pytest.mark.parametrize("flags", ["surfaces", "specular", "surfaces and specular"])
+def test_feature_rows_beyond_one_grid(rt, O, row_case, lanes, flags):
+    """The row form of the same two kernels under the flags (flag 0 is test_headline_frame's): f_take's division of the claim
+    into (row entry, column) and f_add's first-sample branch on a lane's later pixels, from the grid's lanes + 1 pixels on (at
+    most L + 1). A 64 x 8 image under a list of more than 2 L / 64 rows; the reference is its 512 pixels."""
+    s, cam, bg, dev = row_case
+    surfaces, specular = FLAGS[flags]
+    p = rt.make_params(ROW_W, ROW_H, 3, 50, bg, seed=2022)
+    image = np.arange(ROW_H, dtype=np.uint32)
+    n = ROW_W * ROW_H * p.spp
+    if specular:
+        ref, st_ref, info = SP.oracle_specular_features(O, s.desc, cam, p, image, surfaces)
+        check = lambda st, k: check_specular_counters(st, times(st_ref, k), types.SimpleNamespace(segments=k * info.segments, words=k * info.words),
+                                                      k * n, s.desc, surfaces)
+        assert (info.lengths > 0).sum() > 0
+    else:
+        ref, st_ref, seen, words = S.oracle_surface_features(O, s.desc, cam, p, image)
+        check = lambda st, k: check_surface_counters(st, times(st_ref, k), k * words, k * n, s.desc)
+    assert ref["hits"].sum() > 100
+    rows, k = long_row_list(lanes, ROW_H, seed=len(flags))
+    want = ref.reshape(ROW_H, ROW_W)[rows].reshape(-1)
+    got, st = dev.features(cam, p, rows, want_stats=True, surfaces=surfaces, specular=specular)
+    assert_same_bits(got.reshape(-1), want, (flags, "counter instance"))
+    check(st, k)
+    assert_same_bits(dev.features(cam, p, rows, surfaces=surfaces, specular=specular).reshape(-1), want, (flags, "plain instance"))
+
+
+@pytest.mark.parametrize("spp_chunk", [0, 1])
+def test_megakernel_renders_beyond_one_grid(rt, O, row_case, lanes, spp_chunk):
+    """pt_megakernel's claim loop (pt_kernel.hip): a lane that has finished a work item — (row entry, column, chunk of samples)
+    — claims the next; its grid is at most L lanes, so that runs from L + 1 items on at the latest. rt_render on the long row
+    list, spp 2, against the oracle's render of the distinct rows: sums and K times its counters; the wavefront engine, once,
+    gives the same bits. Then rt_render_pixels on a long id list of two frames, held to the oracle in the same way — on the
+    wavefront engine, the only one that takes pixel lists (rt_render_pixels refuses the megakernel engine)."""
+    s, cam, bg, _ = row_case
+    p = rt.make_params(ROW_W, ROW_H, 2, 50, bg, seed=2022, spp_chunk=spp_chunk, n_frames=2)
+    dev = rt.DeviceScene(s.desc)
+    both = np.arange(2 * ROW_H, dtype=np.uint32)
+    ref, st_ref = O.render_cpu(s.desc, cam, p, both, n_threads=4, want_stats=True)
+    ref0, st_ref0 = O.render_cpu(s.desc, cam, p, both[:ROW_H], n_threads=4, want_stats=True)
+    assert same_bits(ref0, ref[:ROW_H]) and np.any(ref0 != 0)
+    scaled = lambda st, k: {key: [k * x for x in v] if isinstance(v, list) else k * v for key, v in render_counters(st).items()}
+    rows, k = long_row_list(lanes, ROW_H, seed=3 + spp_chunk)
+    want = ref0[rows]
+    wavefront = dev.render(cam, p, rows)
+    assert same_bits(wavefront, want), "wavefront engine"
+    dev.set_engine("mega")
+    got, st = dev.render(cam, p, rows, want_stats=True)
+    assert same_bits(got, want), "rt_render, counters"
+    assert render_counters(st) == scaled(st_ref0, k)
+    assert same_bits(dev.render(cam, p, rows), want), "rt_render, plain"
+    # a long id list: whole permutations of the two frames' 1024 ids. The megakernel engine refuses pixel lists (only the
+    # wavefront engine renders them), so this half runs on the wavefront engine, whose pool slots take item after item.
+    dev.set_engine("wavefront")
+    n_ids = 2 * ROW_W * ROW_H
+    k = copies(lanes, n_ids)
+    ids = tiled(n_ids, k, seed=5 + spp_chunk).astype(np.uint64)
+    assert ids.size > 2 * lanes
+    want = ref.reshape(-1, 3)[ids]
+    got, st = dev.render_pixels(cam, p, ids, want_stats=True)
+    assert same_bits(got, want), "rt_render_pixels, counters"
+    assert render_counters(st) == scaled(st_ref, k)
+    assert same_bits(dev.render_pixels(cam, p, ids), want), "rt_render_pixels, plain"
+    dev.close()

@@ -110,6 +110,30 @@ def test_bad_boxes_are_refused_with_the_output_untouched(rt, workspace, what, n)
     assert np.all(raw == FILL)
 
 
+def test_box_reduction_beyond_one_grid(rt):
+    """bvh_box_partial's grid-stride loop (pt_bvh.hip): its grid is capped at kBvhReduceBlocks = 1024 blocks of 256, so a thread
+    takes a second box from n = 262 145 on. n = 262 144 + 257: the last box, which only a second trip reads, is moved out to
+    +-1000 — the scene box, and with it every Morton key and the whole tree, depends on it. Then the same set with a NaN in
+    that box: refused, the output untouched."""
+    import torch
+    n = 1024 * 256 + 257
+    refs, boxes = K.random_boxes(n, 77)
+    boxes[n - 1, :3], boxes[n - 1, 3:] = -1000.0, 1000.0
+    ws = torch.empty(rt.bvh_workspace_bytes(n), dtype=torch.uint8, device="cuda")
+    assert ws.data_ptr() % 16 == 0
+    want = R.build(refs, boxes, node_base=BASE)
+    assert want["bmin"][0].tolist() == [-1000.0] * 3 and want["bmax"][0].tolist() == [1000.0] * 3       # (the root's box is the scene's)
+    rc, raw = device_form(rt, refs, boxes, BASE, ws)
+    assert rc == F.RT_OK, F.lib().rt_last_error()
+    n_bytes = len(want) * 64
+    assert raw[:n_bytes].tobytes() == want.tobytes(), "device form"
+    assert np.all(raw[n_bytes:] == FILL), "wrote past the records"
+    boxes[n - 1, 4] = np.nan
+    rc, raw = device_form(rt, refs, boxes, BASE, ws)
+    assert rc == F.RT_ERR_INVALID and b"leaf box" in F.lib().rt_last_error()
+    assert np.all(raw == FILL)
+
+
 def test_limit_coordinates_are_accepted(rt, workspace):
     refs, boxes = K.random_boxes(65, 10)
     boxes[7, :3], boxes[7, 3:] = -1e300, 1e300

@@ -230,6 +230,57 @@ def test_bad_row_lists_are_refused_with_the_output_untouched(rt):
         assert_same_bits(d_out.cpu().numpy(), restate(sums, feat, p, rows), "good rows after bad ones")
 
 
+# ---- row lists longer than the row kernel's block ---------------------------------------------------------------------------
+# dn_rows is ONE workgroup of 1024 threads striding over the list: thread t takes entries t, t + 1024, t + 2048, ... So a
+# thread's second trip starts at a height of 1025 (one entry on it) and 2500 rows give every thread two or three entries.
+LONG_W, LONG_HEIGHTS, ROW_BLOCK = 3, (1025, 2500), 1024
+
+
+def long_row_lists(H, seed):
+    """A shuffled list of H > 1024 rows and the lists dn_rows must refuse -> (rows, {fault: list}). A fault whose entries the
+    height does not hold is left out (1025 rows have no entry 1500 or 7 + 1024)."""
+    rows = np.random.default_rng(seed).permutation(H).astype(np.uint32)
+    assert H > ROW_BLOCK and rows.tolist() != list(range(H))
+    bad = {}
+    if H > 1500:                                           # a repeat across trips: entry 5 on a first trip, 1500 on thread 476's second
+        bad["repeat across trips"] = rows.copy()
+        bad["repeat across trips"][5] = rows[1500]
+    if H > 7 + ROW_BLOCK:                                  # a repeat inside one thread: entries 7 and 7 + 1024 are both thread 7's
+        bad["repeat inside one thread"] = rows.copy()
+        bad["repeat inside one thread"][7] = rows[7 + ROW_BLOCK]
+    bad["out of range on the last trip"] = rows.copy()
+    bad["out of range on the last trip"][H - 1] = H
+    return rows, bad
+
+
+@pytest.mark.parametrize("H", LONG_HEIGHTS)
+def test_row_lists_longer_than_the_row_kernels_block(rt, H):
+    """dn_rows' stride loop (pt_denoise.hip): a thread's second trip starts at 1025 rows. The host and the device form against
+    the restatement; the device form refuses a repeat across trips, a repeat inside one thread and an id out of range on the
+    last trip with the output untouched, and takes the good list on the same workspace afterwards."""
+    import torch
+    W = LONG_W
+    rows, bad = long_row_lists(H, H)
+    sums, feat = buffers(W, H, seed=H, hostile=True, nan_albedo=False)
+    p = rt.denoise_params(W, H, 4, n_iter=2)
+    ref = restate(sums, feat, p, rows)
+    assert_same_bits(rt.denoise(sums, feat, p, row_ids=rows), ref, "host form")
+    d_sums, d_feat, d_out, d_ws = torch_buffers(sums, feat, p, rt, fill=0xFF)
+    for fault, lst in bad.items():
+        d_rows = torch.from_numpy(lst.view(np.int32)).cuda()
+        torch.cuda.synchronize()
+        with pytest.raises(rt.RtError) as e:
+            rt.denoise_device(d_sums.data_ptr(), d_feat.data_ptr(), p, d_out.data_ptr(), d_ws.data_ptr(), d_row_ids_ptr=d_rows.data_ptr())
+        assert e.value.code == F.RT_ERR_INVALID and "not a permutation" in str(e.value), fault
+        torch.cuda.synchronize()
+        assert (d_out == 7.0).all(), (fault, "the output was written")
+    d_rows = torch.from_numpy(rows.view(np.int32)).cuda()
+    torch.cuda.synchronize()
+    rt.denoise_device(d_sums.data_ptr(), d_feat.data_ptr(), p, d_out.data_ptr(), d_ws.data_ptr(), d_row_ids_ptr=d_rows.data_ptr())
+    torch.cuda.synchronize()
+    assert_same_bits(d_out.cpu().numpy(), ref, "good rows after bad ones")
+
+
 # ---- aliasing and reuse ----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n_iter", [0, 1, 4])
 def test_aliasing_workspace_reuse_and_poisoned_workspace(rt, n_iter):

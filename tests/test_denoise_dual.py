@@ -12,7 +12,7 @@ from raytracer_2022_amd import _ffi as F
 
 import denoise_dual_ref as R
 from denoise_dual_ref import assert_same_bits, restate_dual
-from test_denoise import buffers, restate as restate_single
+from test_denoise import LONG_HEIGHTS, LONG_W, buffers, long_row_lists, restate as restate_single
 
 pytestmark = pytest.mark.gpu
 
@@ -205,6 +205,37 @@ def test_bad_row_lists_are_refused_with_both_outputs_untouched(rt):
         ref, ref_var = restate_dual(*h, p, q, rows)
         assert_same_bits(out, ref, "good rows after bad ones")
         assert_same_bits(var, ref_var, "good rows after bad ones, variance")
+
+
+@pytest.mark.parametrize("H", LONG_HEIGHTS)
+def test_row_lists_longer_than_the_row_kernels_block(rt, H):
+    """dn_rows' stride loop (pt_denoise.hip, one workgroup of 1024 threads): a thread's second trip starts at 1025 rows. Both
+    forms against the restatement; the device form refuses a repeat across trips, a repeat inside one thread and an id out of
+    range on the last trip with both outputs untouched, and takes the good list on the same workspace afterwards."""
+    import torch
+    W = LONG_W
+    rows, bad = long_row_lists(H, H + 1)
+    h = halves(W, H, seed=H, hostile=True, nan_albedo=False)
+    p, q = R.dual_blocks(rt, W, H, 4, n_iter=2, var_iter=1)
+    ref, ref_var = restate_dual(*h, p, q, rows)
+    got, var = rt.denoise_dual(*h, p, q, row_ids=rows, want_variance=True)
+    assert_same_bits(got, ref, "host form")
+    assert_same_bits(var, ref_var, "host form, variance")
+    d = Device(rt, h, p, q, fill=0xFF)
+    for fault, lst in bad.items():
+        d_rows = torch.from_numpy(lst.view(np.int32)).cuda()
+        torch.cuda.synchronize()
+        with pytest.raises(rt.RtError) as e:
+            d.call(rows=d_rows)
+        assert e.value.code == F.RT_ERR_INVALID and "not a permutation" in str(e.value), fault
+        out, v = d.results()
+        assert (out == 7.0).all() and (v == 7.0).all(), (fault, "an output was written")
+    d_rows = torch.from_numpy(rows.view(np.int32)).cuda()
+    torch.cuda.synchronize()
+    d.call(rows=d_rows)
+    out, v = d.results()
+    assert_same_bits(out, ref, "good rows after bad ones")
+    assert_same_bits(v, ref_var, "good rows after bad ones, variance")
 
 
 # ---- workspace, aliasing, the optional variance ---------------------------------------------------------------------------

@@ -599,6 +599,49 @@ def test_device_buffers_and_tonemap(rt, O):
     assert st.ms > 0
 
 
+def tonemap_edge_values(spp):
+    """The doubles at which write_color can go wrong: the specials, and the three doubles around every spp * (k / 255.999)^2
+    (where sqrt(c / spp) * 255.999 crosses the integer k) and around spp * 0.999^2 (where the clamp sets in); one 0.5 pads
+    the list to whole pixels."""
+    v = [np.nan, np.inf, -np.inf, -0.0, 0.0, 5e-324, -3.0, 1e300]
+    for t in [np.float64(spp) * (np.float64(k) / np.float64(255.999)) ** 2 for k in range(256)] + [np.float64(spp) * np.float64(0.999) ** 2]:
+        v += [np.nextafter(t, -np.inf), t, np.nextafter(t, np.inf)]
+    v.append(0.5)
+    assert len(v) % 3 == 0
+    return np.array(v, dtype=np.float64)
+
+
+@pytest.mark.parametrize("spp", [1, 7])
+def test_tonemap_beyond_one_grid_at_its_edges(rt, O, spp):
+    """tonemap_kernel's grid-stride loop (pt_kernel.hip): its grid is capped at 2048 blocks of 256, so a thread takes a second
+    value from 524 289 values on. 175 000 pixels are 525 000 values: the edge values stand at the head of the buffer (first
+    trip) and on the whole pixels of its last 712 values (second trip) — these hold 711 of the 780 edge values, so the call is
+    made twice, with the first 711 and with the last 711 of them there. Random values fill the rest (a block of 8192 pixels,
+    repeated: the host references take microseconds a pixel). Every byte against O.write_color and rt.write_color."""
+    import torch
+    n_pixels, trip = 175_000, 2048 * 256
+    edges = tonemap_edge_values(spp)
+    tail_pixels = (3 * n_pixels - trip) // 3
+    assert 3 * (n_pixels - tail_pixels) >= trip and 2 * 3 * tail_pixels >= edges.size > 3 * tail_pixels > 0
+    block = np.random.default_rng(spp).uniform(0.0, 1.2 * spp, (8192, 3))
+    n_mid = n_pixels - edges.size // 3 - tail_pixels
+    mid = np.resize(np.arange(8192), n_mid)
+    d_u8 = torch.full((n_pixels, 3), 0xAB, dtype=torch.uint8, device="cuda")
+    stream = torch.cuda.current_stream().cuda_stream
+    for tail in (edges[: 3 * tail_pixels], edges[-3 * tail_pixels:]):
+        parts = [edges.reshape(-1, 3), block, tail.reshape(-1, 3)]
+        sums = np.concatenate([parts[0], block[mid], parts[2]])
+        assert sums.shape == (n_pixels, 3)
+        d_sums = torch.from_numpy(sums).cuda()
+        F.check(rt.lib().rt_tonemap_device(C.c_void_p(d_sums.data_ptr()), n_pixels, spp, C.c_void_p(d_u8.data_ptr()), C.c_void_p(stream)))
+        torch.cuda.synchronize()
+        got = d_u8.cpu().numpy()
+        for name, write_color in (("oracle", O.write_color), ("host", rt.write_color)):
+            head, blk, end = (write_color(x, spp) for x in parts)
+            assert np.array_equal(got, np.concatenate([head, blk[mid], end])), name
+        assert len(np.unique(got[: edges.size // 3])) == 256                      # (every byte value is among the edges' results)
+
+
 def test_asynchronous_calls_on_two_streams(rt, O):
     """RT_FLAG_ASYNC: rt_render_device returns at once and a host thread of the library drives the passes; two frames in flight
     on two streams of ONE scene (each with its own pool), a third queued behind the first, all equal to the oracle bit for bit;

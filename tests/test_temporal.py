@@ -14,6 +14,7 @@ import denoise_dual_ref as D
 import temporal_cases as T
 import temporal_ref as R
 from temporal_ref import assert_same_bits
+from test_denoise import LONG_HEIGHTS, LONG_W, long_row_lists
 
 pytestmark = pytest.mark.gpu
 
@@ -182,6 +183,42 @@ def test_bad_row_lists_are_refused_with_both_outputs_untouched(rt):
     d.call(cam, prev_cam, rows=d_rows)
     out, state = d.results()
     ref, ref_state = R.restate(s1, f1, cam, p, st0, prev_cam, rows)
+    assert_same_bits(out, ref, "good rows after bad ones")
+    assert_same_bits(state, ref_state, "good rows after bad ones, state")
+
+
+@pytest.mark.parametrize("H", LONG_HEIGHTS)
+def test_row_lists_longer_than_the_row_kernels_block(rt, H):
+    """dn_rows' stride loop (pt_denoise.hip, one workgroup of 1024 threads): a thread's second trip starts at 1025 rows. One
+    chained pair of frames, each in a shuffled order of its own, against the restatement; the device form refuses a repeat
+    across trips, a repeat inside one thread and an id out of range on the last trip with both outputs untouched, and takes
+    the good list on the same workspace afterwards."""
+    import torch
+    W = LONG_W
+    rows, bad = long_row_lists(H, H + 2)
+    rows0 = np.random.default_rng(H + 3).permutation(H).astype(np.uint32)
+    cam, prev_cam = T.cameras(rt, W, H)["moved"]
+    p = rt.temporal_params(W, H, 4)
+    s0, f0 = T.frame(W, H, seed=H, hostile=False)
+    s1, f1 = T.frame(W, H, seed=H + 1, hostile=True)
+    _, st0 = check(rt, s0[rows0], f0[rows0], prev_cam, p, rows=rows0, what="first frame")
+    s1, f1 = s1[rows], f1[rows]
+    _, st1 = check(rt, s1, f1, cam, p, st0, prev_cam, rows=rows, what="second frame")
+    assert (st1["n"] > 1.0).any(), "no pixel took its history"
+    ref, ref_state = R.restate(s1, f1, cam, p, st0, prev_cam, rows)
+    d = Device(rt, s1, f1, p, st0, fill=0xFF)
+    for fault, lst in bad.items():
+        d_rows = torch.from_numpy(lst.view(np.int32)).cuda()
+        torch.cuda.synchronize()
+        with pytest.raises(rt.RtError) as e:
+            d.call(cam, prev_cam, rows=d_rows)
+        assert e.value.code == F.RT_ERR_INVALID and "not a permutation" in str(e.value), fault
+        torch.cuda.synchronize()
+        assert (d.out == 7.0).all() and (d.state == 7.0).all(), (fault, "an output was written")
+    d_rows = torch.from_numpy(rows.view(np.int32)).cuda()
+    torch.cuda.synchronize()
+    d.call(cam, prev_cam, rows=d_rows)
+    out, state = d.results()
     assert_same_bits(out, ref, "good rows after bad ones")
     assert_same_bits(state, ref_state, "good rows after bad ones, state")
 
