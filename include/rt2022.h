@@ -1026,6 +1026,72 @@ int rt_bvh_build_device(const uint32_t *d_leaf_refs, const double *d_boxes6, uin
                         rt_bvh_node *d_out_nodes, void *d_workspace, uint64_t workspace_bytes, void *hip_stream);
 int rt_bvh_build(const uint32_t *leaf_refs, const double *boxes6, uint32_t n_leaves, uint32_t node_base, rt_bvh_node *out_nodes);
 
+/* ---- a coherence order for a batch of rays, and queries worked in a given order ---------------------------------
+ * rt_intersect* works its rays in the caller's order, and a wave of 64 neighbouring rays that start far apart or point
+ * apart walks the tree with most lanes idle. rt_ray_order* computes, on the device and without a scene, an order that puts
+ * rays of like origin and direction next to each other; rt_intersect_ordered* does rt_intersect's work in a given order.
+ * DESIGN.md §4.16 has the reasoning and what it buys; tests/ray_order_ref.py restates the definition in numpy.
+ *
+ * order[w] is the index of the ray to work on w-th: the permutation that sorts (key, index) ascending (a stable radix sort
+ * of (key, index) pairs, indices going in ascending). Only origin[3] at byte 0 and direction[3] at byte 24 of each record
+ * are read, ray_stride bytes apart: 80 for rt_query_ray, 64 for rt_radiance_ray. All arithmetic is f64, no contraction:
+ *
+ *   Straggler: a ray with an origin or direction component that is not finite, an origin component beyond 1e300 in
+ *     magnitude, or all three direction components zero. Its key is 1 << 63: stragglers come last, in index order. They are
+ *     not refused (hostile rays are valid input to rt_intersect).
+ *   Origin box: lo, hi = component-wise min and max of the non-stragglers' origins (a two-stage reduction).
+ *   Origin word O, 3 * origin_bits bits. Per axis: e = hi - lo; q = e > 0 ? (o - lo) / e : 0;
+ *     k = (uint32) min(q * 2^origin_bits, 2^origin_bits - 1). Morton-interleaved: bit b of k_x at 3b + 2, of k_y at 3b + 1,
+ *     of k_z at 3b. origin_bits == 0 gives O = 0.
+ *   Direction word D, 3 + 2 * dir_bits bits. a = the first axis of largest |d|; m = |d_a|; s = d_a < 0; face = 2a + s.
+ *     For j = (a + 1) % 3, then (a + 2) % 3: r = d_j / m; k = (uint32) min((r + 1.0) * (0.5 * 2^dir_bits), 2^dir_bits - 1).
+ *     uv has bit b of the first k at 2b + 1 and of the second at 2b. D = face << (2 * dir_bits) | uv.
+ *   Key: RT_ORDER_ORIGIN_FIRST     O << (3 + 2 * dir_bits) | D
+ *        RT_ORDER_DIRECTION_FIRST  D << (3 * origin_bits) | O
+ *        RT_ORDER_FACE_ORIGIN_UV   face << (3 * origin_bits + 2 * dir_bits) | O << (2 * dir_bits) | uv
+ *     — at most 63 bits, so none reaches bit 63.
+ *
+ * rt_ray_order_device is a pure enqueue on hip_stream (NULL = default stream) on the current device, with no host
+ * synchronisation: nothing is refused on the device. It allocates nothing: the caller gives it
+ * rt_ray_order_workspace_bytes(n_rays) bytes of 16-byte aligned device memory, whose contents before the call mean nothing and
+ * which the next call on the stream may reuse (a larger workspace serves a smaller call). rt_ray_order stages host buffers
+ * through device memory of its own on the default stream. n_rays == 0 is RT_OK with no launch.
+ * RT_ERR_INVALID with rt_last_error() set and nothing written, before any device call: a null pointer with n_rays > 0;
+ * n_rays >= 2^32; origin_bits > 16, dir_bits > 6, an unknown layout; a ray_stride that is not a multiple of 16 or is below
+ * 48; (device form) a workspace that is null, not 16-byte aligned or too short, rays that are not 16-byte aligned, an order
+ * buffer that is not 4-byte aligned. */
+#define RT_ORDER_ORIGIN_FIRST    0u
+#define RT_ORDER_DIRECTION_FIRST 1u
+#define RT_ORDER_FACE_ORIGIN_UV  2u
+typedef struct rt_ray_order_params {  /* 16 B */
+    uint32_t origin_bits;             /* per axis, 0..16 */
+    uint32_t dir_bits;                /* per face axis, 0..6 */
+    uint32_t layout;                  /* RT_ORDER_* */
+    uint32_t ray_stride;              /* bytes from one ray record to the next: a multiple of 16, >= 48 */
+} rt_ray_order_params;
+uint64_t rt_ray_order_workspace_bytes(uint64_t n_rays);
+int rt_ray_order_device(const void *d_rays, uint64_t n_rays, const rt_ray_order_params *p, uint32_t *d_order,
+                        void *d_workspace, uint64_t workspace_bytes, void *hip_stream);
+int rt_ray_order(const void *rays, uint64_t n_rays, const rt_ray_order_params *p, uint32_t *order);
+
+/* rt_intersect's work in a given order: work item w is ray order[w], and its record goes to out_hits[order[w]] — the
+ * record rt_intersect_device writes for that ray, every byte of it. The rays are gathered into the workspace in working
+ * order, the query kernel runs on the gathered buffer as it does on a caller's, and the records are scattered back.
+ * Any order list is safe: an entry >= n_rays is never used as an address (its work item is an inert ray whose record goes
+ * nowhere); the record of a ray that no entry names stays untouched; a ray named twice is computed twice and gets the same
+ * record both times.
+ * rt_stats as for rt_intersect_device, except that rays counts the entries < n_rays and ms covers the gather, the query
+ * and the scatter; the sums of the counters do not depend on the order (an inert ray may add node visits of its own).
+ * rt_intersect_ordered_device: rt_intersect_device's arguments, refusals and synchronisation (none without stats), and
+ * rt_ray_order_device's for n_rays, the order buffer and the workspace, of rt_intersect_ordered_workspace_bytes(n_rays)
+ * bytes. rt_intersect_ordered: host buffers; order == NULL computes the order of the rays with p (then p must not be NULL,
+ * and its ray_stride must be 80; with an order, p is ignored). */
+uint64_t rt_intersect_ordered_workspace_bytes(uint64_t n_rays);
+int rt_intersect_ordered_device(rt_scene *scene, const rt_query_ray *d_rays, const uint32_t *d_order, uint64_t n_rays, uint32_t flags,
+                                rt_hit *d_out_hits, void *d_workspace, uint64_t workspace_bytes, void *hip_stream, rt_stats *stats);
+int rt_intersect_ordered(rt_scene *scene, const rt_query_ray *rays, const uint32_t *order, const rt_ray_order_params *p,
+                         uint64_t n_rays, uint32_t flags, rt_hit *out_hits, rt_stats *stats);
+
 /* write_color (main.rs:280-299): NaN→0, sqrt(c/spp), clamp [0,0.999], *255.999, floor. */
 void rt_write_color(const double rgb_sum[3], int32_t spp, uint8_t out_rgb[3]);
 /* Device form over n_pixels sums → n_pixels*3 bytes, on hip_stream. */

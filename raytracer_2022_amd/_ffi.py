@@ -258,6 +258,13 @@ SPHERE_DTYPE = np.dtype([("center", "<f8", (3,)), ("radius", "<f8"), ("mat", "<u
 TRIANGLE_DTYPE = np.dtype([("a", "<f8", (3,)), ("b", "<f8", (3,)), ("c", "<f8", (3,)), ("mat", "<u4"), ("_pad", "<u4")])
 RT_BVH_MAX_NODES = 1 << 27
 
+
+class rt_ray_order_params(C.Structure):
+    _fields_ = [("origin_bits", C.c_uint32), ("dir_bits", C.c_uint32), ("layout", C.c_uint32), ("ray_stride", C.c_uint32)]
+
+
+RT_ORDER_ORIGIN_FIRST, RT_ORDER_DIRECTION_FIRST, RT_ORDER_FACE_ORIGIN_UV = 0, 1, 2
+
 ABI_STRUCTS = [rt_bvh_node, rt_sphere, rt_moving_sphere, rt_rect, rt_box, rt_triangle, rt_ring, rt_medium, rt_xform,
                rt_list, rt_material, rt_texture, rt_image, rt_perlin, rt_scene_desc, rt_camera, rt_params, rt_stats,
                rt_query_ray, rt_hit]
@@ -281,6 +288,8 @@ ABI_SYMBOLS = [
     "rtb_denoise_dual_abi_sizes",
     "rt_temporal_workspace_bytes", "rt_temporal", "rt_temporal_device", "rtb_temporal_abi_sizes",
     "rt_bvh_workspace_bytes", "rt_bvh_build_device", "rt_bvh_build", "rtb_ref_boxes",
+    "rt_ray_order_workspace_bytes", "rt_ray_order_device", "rt_ray_order",
+    "rt_intersect_ordered_workspace_bytes", "rt_intersect_ordered_device", "rt_intersect_ordered",
     "rt_debug_math_device", "rt_debug_rng_device", "rt_debug_scene_info", "rt_debug_trace_variant", "rt_debug_set_tuning", "rt_debug_set_engine", "rt_debug_census", "rt_debug_pass_timing", "rt_debug_traffic_probe", "rt_debug_valu_probe", "rt_debug_set_partial_ring", "rt_debug_f32_slabs",
 ]
 
@@ -336,6 +345,14 @@ def lib():
     L.rt_bvh_build_device.argtypes = [vp, vp, u32, u32, vp, vp, u64, vp]
     L.rt_bvh_build.argtypes = [vp, vp, u32, u32, vp]
     L.rtb_ref_boxes.argtypes = [P(rt_scene_desc), vp, u32, dbl, dbl, vp]
+    L.rt_ray_order_workspace_bytes.argtypes = [u64]
+    L.rt_ray_order_workspace_bytes.restype = u64
+    L.rt_ray_order_device.argtypes = [vp, u64, P(rt_ray_order_params), vp, vp, u64, vp]
+    L.rt_ray_order.argtypes = [vp, u64, P(rt_ray_order_params), vp]
+    L.rt_intersect_ordered_workspace_bytes.argtypes = [u64]
+    L.rt_intersect_ordered_workspace_bytes.restype = u64
+    L.rt_intersect_ordered_device.argtypes = [vp, vp, vp, u64, u32, vp, vp, u64, vp, P(rt_stats)]
+    L.rt_intersect_ordered.argtypes = [vp, vp, vp, P(rt_ray_order_params), u64, u32, vp, P(rt_stats)]
     L.rt_render_pixels.argtypes = [vp, P(rt_camera), P(rt_params), vp, u64, vp, P(rt_stats)]
     L.rt_render_pixels_device.argtypes = [vp, P(rt_camera), P(rt_params), vp, u64, vp, vp, P(rt_stats)]
     L.rt_adaptive_workspace_bytes.argtypes = [P(rt_adaptive_params)]

@@ -1,5 +1,7 @@
-// rt_query.hip — the closest-hit calls on a device scene: ray queries (rt_intersect*) and feature buffers (rt_features*,
+// rt_query.hip — the closest-hit calls on a device scene: ray queries (rt_intersect*, and rt_intersect_ordered*: the same
+// launch between a gather and a scatter of pt_order.hip) and feature buffers (rt_features*,
 // rt_features_pixels*: first-hit records, and with RT_FLAG_SPECULAR the records behind glass and mirrors).
+#include "pt_order.hpp"
 #include "rt_internal.hpp"
 
 using namespace rt2022;
@@ -29,12 +31,22 @@ void run_counted(QueryScratch &q, bool counters, hipStream_t stream, rt_stats *s
     *stats = read_stats(q.ev0, q.ev1, counters ? q.stats.p : nullptr, h);
 }
 
-void check_query(const rt_scene *scene, const void *rays, uint64_t n_rays, uint32_t flags, const void *hits, const char *who) {
+// The arguments of a query: what can be said without looking into the scene ...
+void check_query_args(const rt_scene *scene, const void *rays, uint64_t n_rays, uint32_t flags, const void *hits, const char *who) {
     RT_REQUIRE(scene, RT_ERR_INVALID, std::string(who) + ": null scene");
     RT_REQUIRE(n_rays == 0 || (rays && hits), RT_ERR_INVALID, std::string(who) + ": null ray or hit buffer");
     RT_REQUIRE(!(flags & ~(RT_FLAG_COUNTERS | RT_FLAG_ANY_HIT)), RT_ERR_INVALID, std::string(who) + ": unknown flag bits");
+}
+
+// ... and what the scene has to say to the flags.
+void check_query_scene(const rt_scene *scene, uint32_t flags, const char *who) {
     RT_REQUIRE(!(flags & RT_FLAG_ANY_HIT) || scene->dev.n_media == 0, RT_ERR_UNSUPPORTED,
                std::string(who) + ": RT_FLAG_ANY_HIT on a scene with a ConstantMedium (its verdict depends on the closest hit so far)");
+}
+
+void check_query(const rt_scene *scene, const void *rays, uint64_t n_rays, uint32_t flags, const void *hits, const char *who) {
+    check_query_args(scene, rays, n_rays, flags, hits, who);
+    check_query_scene(scene, flags, who);
 }
 
 // Enqueue one query on `stream` (the scene's device is current); with stats, wait for it and fill them.
@@ -48,6 +60,44 @@ void run_query(rt_scene *sc, const rt_query_ray *d_rays, uint64_t n_rays, uint32
     const QueryArgs a{d_rays, d_hits, n_rays, q.counter, counters ? q.stats.p : nullptr};
     run_counted(q, counters, stream, stats, [&] { return launch_query(sc->dev, a, sc->stack_need, counters, (flags & RT_FLAG_ANY_HIT) != 0, stream); });
     if (stats) stats->rays = n_rays;               // (a query counts no paths, rays or light tests of its own)
+}
+
+// The arguments of rt_intersect_ordered_device (host side only; the scene is looked into last, so that a bad argument is
+// reported as such whatever the scene).
+void check_ordered(const rt_scene *scene, const void *d_rays, const void *d_order, uint64_t n_rays, uint32_t flags, const void *d_hits,
+                   const void *ws, uint64_t ws_bytes, const char *who) {
+    check_query_args(scene, d_rays, n_rays, flags, d_hits, who);
+    RT_REQUIRE(n_rays < kOrderMaxRays, RT_ERR_INVALID, std::string(who) + ": n_rays must be below 2^32 (an order entry is 32 bits)");
+    const char *fault = n_rays ? order_buffers_fault(d_rays, d_order, d_hits, true, ws, ws_bytes, ordered_layout(n_rays).bytes) : nullptr;
+    RT_REQUIRE(!fault, RT_ERR_INVALID, std::string(who) + ": " + (fault ? fault : ""));
+    check_query_scene(scene, flags, who);
+}
+
+// run_query in the order of d_order (n_rays > 0): the rays gathered into the workspace, the query kernel on the gathered
+// buffer, the records scattered back — all three between the call's two events.
+void run_query_ordered(rt_scene *sc, const rt_query_ray *d_rays, const uint32_t *d_order, uint64_t n_rays, uint32_t flags, rt_hit *d_hits,
+                       char *ws, hipStream_t stream, rt_stats *stats) {
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    const OrderedLayout l = ordered_layout(n_rays);
+    rt_query_ray *g_rays = reinterpret_cast<rt_query_ray *>(ws + l.rays);
+    rt_hit *g_hits = reinterpret_cast<rt_hit *>(ws + l.hits);
+    unsigned long long *d_valid = stats ? reinterpret_cast<unsigned long long *>(ws + l.valid) : nullptr;
+    QueryScratch &q = scratch_for(sc, sc->qs, stream);
+    std::lock_guard<std::mutex> lock(q.mu);
+    const bool counters = stats && (flags & RT_FLAG_COUNTERS);
+    const QueryArgs a{g_rays, g_hits, n_rays, q.counter, counters ? q.stats.p : nullptr};
+    if (d_valid) RT_HIP(hipMemsetAsync(d_valid, 0, sizeof *d_valid, stream));
+    run_counted(q, counters, stream, stats, [&] {
+        hipError_t e = launch_order_gather(d_rays, d_order, n_rays, g_rays, d_valid, stream);
+        if (e == hipSuccess) e = launch_query(sc->dev, a, sc->stack_need, counters, (flags & RT_FLAG_ANY_HIT) != 0, stream);
+        if (e == hipSuccess) e = launch_order_scatter(g_hits, d_order, n_rays, d_hits, stream);
+        return e;
+    });
+    if (stats) {                                   // (run_counted has synchronised the stream)
+        unsigned long long valid = 0;
+        RT_HIP(hipMemcpy(&valid, d_valid, sizeof valid, hipMemcpyDeviceToHost));
+        stats->rays = valid;
+    }
 }
 
 // The flag bits the four feature calls take.
@@ -213,6 +263,61 @@ int rt_intersect_device(rt_scene *scene, const rt_query_ray *d_rays, uint64_t n_
         }
         DeviceGuard guard(scene->device);
         run_query(scene, d_rays, n_rays, flags, d_out_hits, (hipStream_t)hip_stream, stats);
+        return RT_OK;
+    });
+}
+
+uint64_t rt_intersect_ordered_workspace_bytes(uint64_t n_rays) {
+    return ordered_layout(n_rays).bytes;
+}
+
+int rt_intersect_ordered_device(rt_scene *scene, const rt_query_ray *d_rays, const uint32_t *d_order, uint64_t n_rays, uint32_t flags,
+                                rt_hit *d_out_hits, void *d_workspace, uint64_t workspace_bytes, void *hip_stream, rt_stats *stats) {
+    return guarded([&]() -> int {
+        check_ordered(scene, d_rays, d_order, n_rays, flags, d_out_hits, d_workspace, workspace_bytes, "rt_intersect_ordered_device");
+        if (n_rays == 0) {
+            if (stats) std::memset(stats, 0, sizeof *stats);
+            return RT_OK;
+        }
+        DeviceGuard guard(scene->device);
+        run_query_ordered(scene, d_rays, d_order, n_rays, flags, d_out_hits, (char *)d_workspace, (hipStream_t)hip_stream, stats);
+        return RT_OK;
+    });
+}
+
+int rt_intersect_ordered(rt_scene *scene, const rt_query_ray *rays, const uint32_t *order, const rt_ray_order_params *p, uint64_t n_rays,
+                         uint32_t flags, rt_hit *out_hits, rt_stats *stats) {
+    return guarded([&]() -> int {
+        const std::string w("rt_intersect_ordered");
+        check_query_args(scene, rays, n_rays, flags, out_hits, w.c_str());
+        RT_REQUIRE(n_rays < kOrderMaxRays, RT_ERR_INVALID, w + ": n_rays must be below 2^32 (an order entry is 32 bits)");
+        if (!order) {
+            const char *fault = order_params_fault(n_rays, p);
+            if (!fault && p->ray_stride != sizeof(rt_query_ray)) fault = "ray_stride must be 80 (rt_query_ray)";
+            RT_REQUIRE(!fault, RT_ERR_INVALID, w + ": " + (fault ? fault : ""));
+        }
+        check_query_scene(scene, flags, w.c_str());
+        if (n_rays == 0) {
+            if (stats) std::memset(stats, 0, sizeof *stats);
+            return RT_OK;
+        }
+        DeviceGuard guard(scene->device);
+        DeviceBuf<rt_query_ray> d_rays(n_rays);                // (after the guard: freed with the scene's device current)
+        DeviceBuf<rt_hit> d_hits(n_rays);
+        DeviceBuf<uint32_t> d_order(n_rays);
+        DeviceBuf<char> d_ws(ordered_layout(n_rays).bytes);
+        RT_HIP(hipMemcpy(d_rays, rays, n_rays * sizeof(rt_query_ray), hipMemcpyHostToDevice));
+        // (the caller's records go up first: the record of a ray that no entry names comes back as it was)
+        RT_HIP(hipMemcpy(d_hits, out_hits, n_rays * sizeof(rt_hit), hipMemcpyHostToDevice));
+        if (order) {
+            RT_HIP(hipMemcpy(d_order, order, n_rays * sizeof(uint32_t), hipMemcpyHostToDevice));
+        } else {
+            DeviceBuf<char> d_order_ws(order_layout(n_rays).bytes);
+            launch_ray_order(OrderArgs{(const char *)d_rays.p, n_rays, *p, d_order, d_order_ws}, nullptr);
+            RT_HIP(hipStreamSynchronize(nullptr));             // (the ordering's workspace dies here)
+        }
+        run_query_ordered(scene, d_rays, d_order, n_rays, flags, d_hits, d_ws, nullptr, stats);
+        RT_HIP(hipMemcpy(out_hits, d_hits, n_rays * sizeof(rt_hit), hipMemcpyDeviceToHost));
         return RT_OK;
     });
 }

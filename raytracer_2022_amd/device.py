@@ -513,6 +513,58 @@ def bvh_build_device(d_refs_ptr, d_boxes_ptr, n_leaves, d_out_ptr, d_workspace_p
                                         C.c_void_p(d_workspace_ptr), workspace_bytes, C.c_void_p(stream_ptr or 0)))
 
 
+# The parameters of the ray ordering: the cell of tools/query_bench.py --order-grid with the smallest summed time, ordering plus
+# ordered query, over the bounce rays of its four scenes (profiles/ray_order.log, the "grid_best" line). Hardly a cell of that grid beats
+# the unordered call on those rays (none by more than 3 %), so what wins is the cheapest sort: no origin word, the face and 2 bits a face axis (with no
+# origin word ORIGIN_FIRST and DIRECTION_FIRST are one order). A shuffled batch of coherent rays wants a fine key instead —
+# ray_order_params(16, 6) — see DESIGN.md §4.16.
+RAY_ORDER_DEFAULTS = {"origin_bits": 0, "dir_bits": 2, "layout": F.RT_ORDER_ORIGIN_FIRST}
+
+
+def ray_order_params(origin_bits=RAY_ORDER_DEFAULTS["origin_bits"], dir_bits=RAY_ORDER_DEFAULTS["dir_bits"],
+                     layout=RAY_ORDER_DEFAULTS["layout"], stride=80):
+    """rt_ray_order_params: bits per origin axis (0..16) and per face axis of the direction (0..6), the layout of the key
+    (F.RT_ORDER_ORIGIN_FIRST, RT_ORDER_DIRECTION_FIRST, RT_ORDER_FACE_ORIGIN_UV) and the bytes from one ray record to the next
+    (80: QUERY_RAY_DTYPE, 64: RADIANCE_RAY_DTYPE). The defaults are RAY_ORDER_DEFAULTS."""
+    p = F.rt_ray_order_params()
+    p.origin_bits, p.dir_bits, p.layout, p.ray_stride = origin_bits, dir_bits, layout, stride
+    return p
+
+
+def ray_order_workspace_bytes(n_rays):
+    """rt_ray_order_workspace_bytes: device bytes ray_order_device needs for n_rays rays."""
+    return int(F.lib().rt_ray_order_workspace_bytes(n_rays))
+
+
+def intersect_ordered_workspace_bytes(n_rays):
+    """rt_intersect_ordered_workspace_bytes: device bytes DeviceScene.intersect_ordered_device needs for n_rays rays."""
+    return int(F.lib().rt_intersect_ordered_workspace_bytes(n_rays))
+
+
+def ray_order(rays, params=None, stride=None):
+    """rt_ray_order with host buffers: the coherence order of an array of ray records (QUERY_RAY_DTYPE, RADIANCE_RAY_DTYPE or any
+    record that starts with origin[3], direction[3]) → uint32 (n,): order[w] is the index of the ray to work on w-th.
+    params=None takes RAY_ORDER_DEFAULTS; the stride is `stride`, else params', else the records' item size."""
+    r = np.ascontiguousarray(rays)
+    step = stride if stride is not None else params.ray_stride if params is not None else r.dtype.itemsize
+    p = ray_order_params(stride=step) if params is None else F.rt_ray_order_params.from_buffer_copy(params)
+    p.ray_stride = step
+    if step <= 0 or r.nbytes % step:
+        raise ValueError("the rays must hold whole records of `stride` bytes")
+    n = r.nbytes // step
+    order = np.zeros(n, dtype=np.uint32)
+    F.check(F.lib().rt_ray_order(r.ctypes.data if n else None, n, C.byref(p), order.ctypes.data if n else None))
+    return order
+
+
+def ray_order_device(d_rays_ptr, n_rays, params, d_order_ptr, d_workspace_ptr, workspace_bytes, stream_ptr=None):
+    """rt_ray_order_device: device pointers in (n_rays records params.ray_stride bytes apart and ray_order_workspace_bytes(n_rays)
+    bytes of workspace, 16-byte aligned; room for n_rays uint32 entries), a pure enqueue on `stream_ptr` (hipStream_t as int):
+    no host synchronisation. With torch: tensor.data_ptr() and torch.cuda.current_stream().cuda_stream."""
+    F.check(F.lib().rt_ray_order_device(C.c_void_p(d_rays_ptr), n_rays, C.byref(params), C.c_void_p(d_order_ptr), C.c_void_p(d_workspace_ptr),
+                                        workspace_bytes, C.c_void_p(stream_ptr or 0)))
+
+
 class DeviceScene:
     """rt_scene: the flattened scene copied into HBM on the current HIP device."""
 
@@ -594,16 +646,47 @@ class DeviceScene:
     def wait(self, stream_ptr=None):
         F.check(F.lib().rt_render_wait(self._h, C.c_void_p(stream_ptr or 0)))
 
-    def intersect(self, rays, any_hit=False, want_stats=False):
+    def intersect(self, rays, any_hit=False, want_stats=False, order=None, order_params=None):
         """rt_intersect: closest hit (or, any_hit=True, the first accepted) of every ray of `rays` (QUERY_RAY_DTYPE, see
-        query_rays) → array of HIT_DTYPE records [, rt_stats with the counters]."""
+        query_rays) → array of HIT_DTYPE records [, rt_stats with the counters].
+        order=None works the rays in the order given. order="auto" (rt_intersect_ordered) computes a coherence order first, with
+        `order_params` (ray_order_params; None: RAY_ORDER_DEFAULTS): the same records, sooner for a shuffled batch of coherent rays
+        on a heavy scene under a fine key such as ray_order_params(16, 6), later for rays that are coherent as they come and for
+        bounce rays — so it is off by default. An index array is an order of
+        the caller's: entry w names the ray worked on w-th; a ray that no entry names keeps a zeroed record."""
         r = np.ascontiguousarray(rays, dtype=F.QUERY_RAY_DTYPE)
         out = np.zeros(len(r), dtype=F.HIT_DTYPE)
         flags = (F.RT_FLAG_ANY_HIT if any_hit else 0) | (F.RT_FLAG_COUNTERS if want_stats else 0)
         st = F.rt_stats()
-        F.check(F.lib().rt_intersect(self._h, r.ctypes.data if len(r) else None, len(r), flags, out.ctypes.data if len(r) else None,
-                                     C.byref(st)))
+        p_rays, p_out = (r.ctypes.data, out.ctypes.data) if len(r) else (None, None)
+        if order is None:
+            F.check(F.lib().rt_intersect(self._h, p_rays, len(r), flags, p_out, C.byref(st)))
+        elif isinstance(order, str):
+            if order != "auto":
+                raise ValueError('order must be None, "auto" or an index array')
+            p = order_params if order_params is not None else ray_order_params()
+            F.check(F.lib().rt_intersect_ordered(self._h, p_rays, None, C.byref(p), len(r), flags, p_out, C.byref(st)))
+        else:
+            o = np.ascontiguousarray(order, dtype=np.uint32)
+            if o.shape != (len(r),):
+                raise ValueError("an order holds one entry per ray")
+            # (the parameters are ignored beside an order; they only keep an empty batch, whose order is no pointer, valid)
+            F.check(F.lib().rt_intersect_ordered(self._h, p_rays, o.ctypes.data if len(r) else None, C.byref(ray_order_params()), len(r), flags,
+                                                 p_out, C.byref(st)))
         return (out, st) if want_stats else out
+
+    def intersect_ordered_device(self, d_rays_ptr, d_order_ptr, n, d_hits_ptr, d_workspace_ptr, workspace_bytes, stream_ptr=None,
+                                 any_hit=False, stats=None):
+        """rt_intersect_ordered_device: intersect_device's work in the order of n uint32 entries at `d_order_ptr` (ray_order_device's,
+        or any list: an entry >= n does nothing, a ray that no entry names keeps its record), through
+        intersect_ordered_workspace_bytes(n) bytes of 16-byte aligned workspace. stats=None returns after the enqueue; an rt_stats
+        makes the call synchronise the stream and fill it: rays counts the entries < n, ms covers gather, query and scatter."""
+        flags = F.RT_FLAG_ANY_HIT if any_hit else 0
+        if stats is not None:
+            flags |= F.RT_FLAG_COUNTERS
+        F.check(F.lib().rt_intersect_ordered_device(self._h, C.c_void_p(d_rays_ptr), C.c_void_p(d_order_ptr), n, flags, C.c_void_p(d_hits_ptr),
+                                                    C.c_void_p(d_workspace_ptr), workspace_bytes, C.c_void_p(stream_ptr or 0),
+                                                    C.byref(stats) if stats is not None else None))
 
     def intersect_device(self, d_rays_ptr, n, d_hits_ptr, stream_ptr=None, any_hit=False, stats=None):
         """rt_intersect_device: device pointers in (n rt_query_ray records, room for n rt_hit), enqueued on `stream_ptr`
