@@ -95,7 +95,7 @@ def oracle_records(O, desc, rays, ref=None):
 
 
 def oracle_albedo(O, desc, got):
-    """The feature header's albedo of every record by the oracle's own composition (tests/test_features.py: oracle_sample):
+    """The feature header's albedo of every record by the oracle's own composition (tests/features_ref.py: oracle_sample):
     rto_texture_value at the oracle's own u, v, p → (n, 3); zeros on a miss."""
     import numpy as np
     from raytracer_2022_amd import _ffi as F

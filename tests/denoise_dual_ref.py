@@ -9,16 +9,12 @@ import numpy as np
 
 from raytracer_2022_amd import _ffi as F
 
-H5 = [1.0 / 16.0, 1.0 / 4.0, 3.0 / 8.0, 1.0 / 4.0, 1.0 / 16.0]
+from denoise_ref import H5, dist, display
+
 # The views of the end-to-end tests and of the grid: (scene, width, height). The last one the grid never sees.
 GRID_VIEWS = [("cornell_box", 48, 48), ("final_scene", 48, 48), ("random_scene", 60, 40)]
 HELD_OUT_VIEW = ("cornell_smoke", 48, 48)
 HALF_SPP, SEED, REF_SPP, REF_SEED = 2, 2022, 512, 7
-
-
-def dist(p, q):
-    d0, d1, d2 = p[..., 0] - q[..., 0], p[..., 1] - q[..., 1], p[..., 2] - q[..., 2]
-    return (d0 * d0 + d1 * d1) + d2 * d2
 
 
 def restate_dual(sum_a, sum_b, feat_a, feat_b, p, q, rows=None):
@@ -88,24 +84,6 @@ def restate_dual(sum_a, sum_b, feat_a, feat_b, p, q, rows=None):
         return out, u
     rows = np.asarray(rows, dtype=np.int64)
     return out[rows], u[rows]
-
-
-def bits(a):
-    v = np.ascontiguousarray(a, dtype=np.float64)
-    return np.where(np.isnan(v), np.float64(0), v).view(np.uint64), np.isnan(v)
-
-
-def assert_same_bits(got, ref, what=""):
-    (gb, gn), (rb, rn) = bits(got), bits(ref)
-    assert gb.shape == rb.shape, what
-    assert np.array_equal(gn, rn), (what, "NaN pattern")
-    bad = np.argwhere(gb != rb)
-    assert len(bad) == 0, (what, "first differing doubles", bad[:5].tolist(), len(bad))
-
-
-def display(sums, spp):
-    c = np.where(np.isnan(sums), 0.0, sums) / spp
-    return np.sqrt(np.clip(c, 0.0, 0.999))
 
 
 def mse(sums, spp, target):

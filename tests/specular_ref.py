@@ -15,6 +15,7 @@ import numpy as np
 from raytracer_2022_amd import _ffi as F
 
 import surface_ref as S
+from surface_ref import boundary_contents
 
 GOLDEN = 0x9E3779B97F4A7C15
 MASK64 = (1 << 64) - 1
@@ -168,6 +169,25 @@ def oracle_specular_ids(O, desc, cam, params, ids, surfaces=False):
     per = params.width * params.height
     pixels = [(int(i) // per, (int(i) % per) // params.width, (int(i) % per) % params.width) for i in ids]
     return specular_pixels(O, desc, cam, params, pixels, surfaces)
+
+
+def check_specular_counters(st, st_ref, info, n_samples, d=None, surfaces=False):
+    """rt_stats of a flagged counter call against the restatement's: paths, the device's ray count, the words, and the traversal
+    counters — summed over all segments; with RT_FLAG_SURFACES the copy still tests its media's boundaries, so those kinds bound."""
+    assert st.paths == n_samples and st.rays == info.segments and st.rng_draws == info.words, (st.as_dict(), info.segments, info.words)
+    got, ref = list(st.prim_tests), list(st_ref.prim_tests)
+    if not surfaces:
+        assert got == ref and st.node_visits == st_ref.node_visits
+    else:
+        kinds, nodes_below = boundary_contents(d)
+        assert got[F.RT_KIND_MEDIUM] == 0
+        for k in range(len(got)):
+            assert got[k] <= ref[k]
+            if k != F.RT_KIND_MEDIUM and k not in kinds:
+                assert got[k] == ref[k], (k, got[k], ref[k])
+        assert st.node_visits <= st_ref.node_visits and (nodes_below or st.node_visits == st_ref.node_visits)
+    assert st.light_pdf_tests == 0 and st.passes == 0 and st.pool_slots == 0 and st.partial_bytes == 0 and st.spp_chunk == 0
+    assert st.trace_ms == 0 and st.shade_ms == 0 and st.ms > 0
 
 
 # ---- the "mirror hall": the smallest scene that reaches every chain length -----------------------------------------------------

@@ -135,3 +135,31 @@ def check_plane_shift(state, prev_state, cur_e, W):
     assert (state["n"][:, : W - 4] == 2.0).all()
     assert (state["n"][:, W - 3:] == 1.0).all()
     assert np.array_equal(state["e"][:, W - 3:], cur_e[:, W - 3:])
+
+
+# ---- the device form on torch buffers (the one thing here that needs a GPU) ---------------------------------------------------
+class Device:
+    """A frame's sums and records, two states, an output and a workspace as torch buffers; call() is rt_temporal_device."""
+
+    def __init__(self, rt, s, f, p, prev=None, fill=0):
+        import torch
+        self.rt, self.p, self.torch = rt, p, torch
+        n = p.width * p.height
+        self.sums = torch.from_numpy(np.ascontiguousarray(s)).cuda()
+        self.feat = torch.from_numpy(np.ascontiguousarray(f).view(np.float64).reshape(-1)).cuda()
+        self.prev = torch.from_numpy(np.ascontiguousarray(prev).view(np.float64).reshape(-1)).cuda() if prev is not None else None
+        self.state = torch.full((n * 8,), 7.0, dtype=torch.float64, device="cuda")
+        self.out = torch.full((p.height, p.width, 3), 7.0, dtype=torch.float64, device="cuda")
+        self.ws = torch.full((rt.temporal_workspace_bytes(p),), fill, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+
+    def call(self, cam, prev_cam=None, out=None, rows=None, stream=None):
+        self.rt.temporal_device(self.sums.data_ptr(), self.feat.data_ptr(), cam, self.p, self.state.data_ptr(),
+                                (self.out if out is None else out).data_ptr(), self.ws.data_ptr(),
+                                d_prev_ptr=self.prev.data_ptr() if self.prev is not None else None, prev_cam=prev_cam,
+                                d_row_ids_ptr=rows.data_ptr() if rows is not None else None, stream_ptr=stream)
+
+    def results(self, out=None):
+        self.torch.cuda.synchronize()
+        state = self.state.cpu().numpy().view(F.TEMPORAL_PIXEL_DTYPE).reshape(self.p.height, self.p.width)
+        return (self.out if out is None else out).cpu().numpy(), state

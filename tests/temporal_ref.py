@@ -11,6 +11,9 @@ import numpy as np
 
 from raytracer_2022_amd import _ffi as F
 
+from denoise_ref import display
+from features_ref import oracle_features
+
 # The camera paths of the end-to-end tests and of the grid: scene -> the step between two cameras, in world units along the
 # default view's u axis (about 1.5 pixels of image shift per frame at 48 x 48 for what the view looks at). Camera K-1 is the
 # scene's default view; the cameras before it lie on a line to its left. The last scene the grid never sees.
@@ -112,25 +115,6 @@ def restate(sums, feat, cam, p, prev=None, prev_cam=None, rows=None, geometry=Fa
     return (out, state, geo) if geometry else (out, state)
 
 
-def bits(a):
-    a = np.ascontiguousarray(a)
-    v = a.view(np.float64) if a.dtype in (F.TEMPORAL_PIXEL_DTYPE, F.FEATURE_DTYPE) else np.asarray(a, dtype=np.float64)
-    return np.where(np.isnan(v), np.float64(0), v).view(np.uint64), np.isnan(v)
-
-
-def assert_same_bits(got, ref, what=""):
-    (gb, gn), (rb, rn) = bits(got), bits(ref)
-    assert gb.shape == rb.shape, what
-    assert np.array_equal(gn, rn), (what, "NaN pattern")
-    bad = np.argwhere(gb != rb)
-    assert len(bad) == 0, (what, "first differing doubles", bad[:5].tolist(), len(bad))
-
-
-def display(sums, spp):
-    c = np.where(np.isnan(sums), 0.0, sums) / spp
-    return np.sqrt(np.clip(c, 0.0, 0.999))
-
-
 def mse(sums, spp, target):
     return float(np.mean((display(sums, spp) - target) ** 2))
 
@@ -158,7 +142,6 @@ def frame_params(rt, W, H, spp, bg, k):
 def oracle_path(rt, O, name, step, W=PATH_W, H=PATH_H, K=PATH_K, spp=PATH_SPP, threads=4, rows=None):
     """The oracle's frames along a scene's path: (cameras, [sums (H, W, 3)], [FEATURE_DTYPE records (H, W)]), in the order of
     `rows` (None: image order)."""
-    from test_features import oracle_features
     s = rt.HostScene(name, seed=2022)
     cam, bg = s.default_view(W / H)
     cams = camera_path(cam, step, K)

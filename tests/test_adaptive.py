@@ -7,24 +7,15 @@ import pytest
 
 import adaptive_ref as R
 from raytracer_2022_amd import _ffi as F
-from test_denoise import LONG_HEIGHTS, LONG_W, long_row_lists
+from compare import bits
+from denoise_ref import LONG_HEIGHTS, LONG_W, long_row_lists
+from gpu_first import torch_first  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 # 1 x 1: one lane; 64 x 1: one wave; 65 x 3: a wave and a bit, one workgroup; 257 x 33 = 8481 pixels: nine tiles of 1024 —
 # the block-totals level, with a last tile that is partly empty.
 SIZES = [(1, 1), (64, 1), (65, 3), (257, 33)]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def torch_first():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU: the HIP path has no fallback"
-    torch.zeros(1, device="cuda")
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
 def error_maps(w, h, max_units, g):

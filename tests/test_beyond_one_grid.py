@@ -25,25 +25,19 @@ from raytracer_2022_amd import _ffi as F
 import specular_ref as SP
 import surface_ref as S
 import trace_scenes as TS
-from test_features import assert_same_bits
-from test_features_pixels import check_counters as check_first_hit_counters, oracle_ids
-from test_query import (assert_prims_consistent, assert_records_equal, bounce_rays, camera_rays, counters, every_kind_scene, mixed_rays,
-                        oracle_hits, randomise_windows)
-from test_render_pixels import counters as render_counters, same_bits
-from test_specular import check_counters as check_specular_counters
-from test_surfaces import check_counters as check_surface_counters
+from compare import assert_same_bits, same_bits
+from features_ref import check_first_hit_counters, oracle_ids
+from gpu_first import torch_first  # noqa: F401
+from query_ref import (assert_prims_consistent, assert_records_equal, bounce_rays, camera_rays, mixed_rays, oracle_hits, query_counters,
+                       randomise_windows)
+from query_scenes import every_kind_scene
+from radiance_ref import render_counters
+from specular_ref import check_specular_counters
+from surface_ref import check_surface_counters
 
 pytestmark = pytest.mark.gpu
 
 M = 4099                                                   # the base batch: distinct work items, a prime
-
-
-@pytest.fixture(scope="module", autouse=True)
-def torch_first():
-    """Bring torch's HIP context up before the library's first call, as the other GPU test modules do."""
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU: the HIP path has no fallback"
-    torch.zeros(1, device="cuda")
 
 
 @pytest.fixture(scope="module")
@@ -128,8 +122,8 @@ def test_queries_beyond_one_grid(rt, O, lanes, which):
     got, st = dev.intersect(rays, want_stats=True)
     assert_records_equal(got, ref[idx], which)
     assert np.array_equal(got["prim"], small["prim"][idx])
-    nodes, prims, draws = counters(st_ref, ref)
-    assert st.rays == n and counters(st) == (k * nodes, [k * x for x in prims], k * draws)
+    nodes, prims, draws = query_counters(st_ref, ref)
+    assert st.rays == n and query_counters(st) == (k * nodes, [k * x for x in prims], k * draws)
     assert np.array_equal(dev.intersect(rays).view(np.uint8), got.view(np.uint8))          # the plain instance, prim included
     if which == "need 16":
         assert np.array_equal(dev.intersect(rays, any_hit=True)["hit"], ref["hit"][idx])

@@ -17,20 +17,13 @@ import pytest
 import brute_hits as B
 import brute_scenes as S
 import trace_scenes as T
+from gpu_first import torch_first  # noqa: F401
 from raytracer_2022_amd import _ffi as F
 
 pytestmark = pytest.mark.gpu
 
 REF_ORDER = 1 << 15                                      # rt2022_debug.h: tuning bit 15, the reference's child order
 NODE_CACHE = T.NODE_CACHE
-
-
-@pytest.fixture(scope="module", autouse=True)
-def torch_first():
-    """Bring torch's HIP context up before the library's first call, as the other GPU test modules do."""
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU: the HIP path has no fallback"
-    torch.zeros(1, device="cuda")
 
 
 def query_shell(d, need):

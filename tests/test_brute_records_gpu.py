@@ -14,6 +14,7 @@ import brute_hits as B
 import brute_records as BR
 import brute_scenes as S
 import trace_scenes as T
+from gpu_first import torch_first  # noqa: F401
 from raytracer_2022_amd import _ffi as F
 
 pytestmark = pytest.mark.gpu
@@ -24,14 +25,6 @@ NEW_CLASS_SHARE = 0.03
 GOLDEN, MASK64 = 0x9E3779B97F4A7C15, (1 << 64) - 1
 F64_MAX = float(np.finfo(np.float64).max)
 W, H, SPP = 48, 32, 2
-
-
-@pytest.fixture(scope="module", autouse=True)
-def torch_first():
-    """Bring torch's HIP context up before the library's first call, as the other GPU test modules do."""
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU: the HIP path has no fallback"
-    torch.zeros(1, device="cuda")
 
 
 def scene_of(name):
@@ -195,9 +188,9 @@ def test_textures_through_the_shade_pass(rt, name):
 
 
 # ---- rt_features and rt_features_pixels -----------------------------------------------------------------------------------------------
-def camera_rays(O, cam, p, frame=0):
+def frame_camera_rays(O, cam, p, frame=0):
     """The camera rays of a frame by the oracle's composition rto_path_key -> rto_rng_f64 -> rto_get_ray (the first half of
-    tests/test_features.py: oracle_sample; camera code is not under test here) → rays (H, W, SPP) with the window and the
+    tests/features_ref.py: oracle_sample; camera code is not under test here) → rays (H, W, SPP) with the window and the
     rng_state world.hit gets."""
     L = O.lib()
     rays = np.zeros((p.height, p.width, p.spp), dtype=B.RAY_DTYPE)
@@ -269,7 +262,7 @@ def test_features_against_reference_records(rt, O, name, surfaces):
     sc, sh = B.Scene(d), BR.Shading(d)
     assert surfaces or not sc.media
     p = rt.make_params(W, H, SPP, background=BACKGROUND, seed=77)
-    rays = camera_rays(O, cam, p)
+    rays = frame_camera_rays(O, cam, p)
     want, tol, keep, _ = reference_features(sc, sh, rays, BACKGROUND)
     assert (~keep).sum() <= NEW_CLASS_SHARE * keep.size, (name, int((~keep).sum()))            # (before the device is called)
     assert want[..., 7][keep].sum() >= 0.2 * SPP * keep.sum(), "the view sees too little of the scene"

@@ -12,6 +12,9 @@ import brute_scenes as S
 import bvh_cases as K
 import bvh_ref as R
 import bvh_scenes as BS
+from compare import same_bits
+from gpu_first import torch_first  # noqa: F401
+from query_ref import oracle_hits
 from raytracer_2022_amd import _ffi as F
 
 pytestmark = pytest.mark.gpu
@@ -19,14 +22,6 @@ pytestmark = pytest.mark.gpu
 SIZES = (1, 2, 3, 63, 64, 65, 257, 4099, 100000)
 BASE = 1000                                              # the device form's node_base
 FILL = 0xA5
-
-
-@pytest.fixture(scope="module", autouse=True)
-def torch_first():
-    """Bring torch's HIP context up before the library's first call, as the other GPU test modules do."""
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU: the HIP path has no fallback"
-    torch.zeros(1, device="cuda")
 
 
 @pytest.fixture(scope="module")
@@ -168,24 +163,6 @@ def test_torch_buffers_on_a_callers_stream(rt, workspace):
 
 
 # ---- scenes whose root tree the device built -----------------------------------------------------------------------------------------
-def bits(a):
-    a = np.ascontiguousarray(a, dtype=np.float64)
-    return np.where(np.isnan(a), 0, a).view(np.uint64), np.isnan(a)
-
-
-def oracle_hits(O, desc, rays):
-    out = np.zeros(len(rays), dtype=F.HIT_DTYPE)
-    for i, r in enumerate(rays):
-        rec = O.hit(desc, desc.root, r["origin"], r["direction"], tm=float(r["time"]), t_min=float(r["t_min"]), t_max=float(r["t_max"]),
-                    rng_state=int(r["rng_state"]))
-        o = out[i]
-        o["hit"], o["front_face"], o["rng_draws"] = rec.hit, rec.front_face, rec.rng_draws
-        if rec.hit:
-            o["t"], o["u"], o["v"], o["mat"] = rec.t, rec.u, rec.v, rec.mat
-            o["p"], o["normal"] = rec.p[:], rec.normal[:]
-    return out
-
-
 @pytest.mark.parametrize("name", BS.NAMES)
 def test_scene_on_a_built_tree(rt, O, name):
     d, cam, refs, boxes, base = BS.make(name)                                            # (the device builds the tree)
@@ -204,11 +181,11 @@ def test_scene_on_a_built_tree(rt, O, name):
         assert B.classify(sc, ans)[3].sum() <= S.AMBIGUOUS_SHARE * len(rays), (name, family)
         q = np.ascontiguousarray(rays, dtype=F.QUERY_RAY_DTYPE)
         got = dev.intersect(q)
-        ref = oracle_hits(O, d, q)
+        ref, _ = oracle_hits(O, d, q)
         assert np.array_equal(got["hit"], ref["hit"]) and np.array_equal(got["rng_draws"], ref["rng_draws"]), (name, family)
         h = ref["hit"] == 1
         for f in ("t", "u", "v", "p", "normal"):
-            assert all(np.array_equal(x, y) for x, y in zip(bits(got[f][h]), bits(ref[f][h]))), (name, family, f)
+            assert same_bits(got[f][h], ref[f][h]), (name, family, f)
         assert np.array_equal(got["front_face"][h], ref["front_face"][h]) and np.array_equal(got["mat"][h], ref["mat"][h])
         assert np.all(got["prim"][~h] == F.RT_REF_NONE)
         ta, _ = B.compare(sc, rays, got["hit"], got["t"], got["rng_draws"], got["prim"], ans=ans)
@@ -229,5 +206,5 @@ def test_scene_on_a_built_tree(rt, O, name):
     want, st_want = O.render_cpu(d, cam, p, rows, n_threads=4, want_stats=True)
     out, st = dev.render(cam, p, rows, want_stats=True)
     assert st.as_dict() == st_want.as_dict(), name
-    assert all(np.array_equal(x, y) for x, y in zip(bits(out), bits(want))), name
+    assert same_bits(out, want), name
     assert np.array_equal(rt.write_color(out, spp), O.write_color(want, spp)), name

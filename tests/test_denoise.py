@@ -1,9 +1,7 @@
 """Edge-avoiding denoiser (rt_denoise / rt_denoise_device) against a numpy restatement of its definition, bit for bit.
 
-`restate` below is include/rt2022.h's definition once more: the 25 taps one after the other in the header's order, the
-pixels of a tap vectorised, a skipped tap through np.where. numpy's element-wise + - * / on float64 are the IEEE
-operations and nothing is fused, so the kernels (built with -ffp-contract=off) must give the same doubles. Every comparison
-is on the uint64 view, the NaN patterns first."""
+`restate` (tests/denoise_ref.py) is include/rt2022.h's definition once more in numpy; the kernels (built with
+-ffp-contract=off) must give the same doubles. Every comparison is on the uint64 view, the NaN patterns first."""
 import ctypes as C
 import math
 
@@ -12,105 +10,11 @@ import pytest
 
 from raytracer_2022_amd import _ffi as F
 
+from compare import assert_same_bits
+from denoise_ref import LONG_HEIGHTS, LONG_W, buffers, display, long_row_lists, restate
+from gpu_first import torch_first  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-
-H5 = [1.0 / 16.0, 1.0 / 4.0, 3.0 / 8.0, 1.0 / 4.0, 1.0 / 16.0]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def torch_first():
-    """Bring torch's HIP context up before the library's first call, as the other GPU test modules do."""
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU: the HIP path has no fallback"
-    torch.zeros(1, device="cuda")
-
-
-def dist(p, q):
-    d0, d1, d2 = p[..., 0] - q[..., 0], p[..., 1] - q[..., 1], p[..., 2] - q[..., 2]
-    return (d0 * d0 + d1 * d1) + d2 * d2
-
-
-def restate(sums, feat, p, rows=None):
-    """The definition in numpy. sums (H, W, 3) and feat (H, W) FEATURE_DTYPE in buffer order -> filtered sums, buffer order."""
-    H, W = p.height, p.width
-    sums = np.asarray(sums, dtype=np.float64).reshape(H, W, 3)
-    feat = np.asarray(feat).reshape(H, W)
-    if rows is not None:                                   # buffer row i is image row rows[i]
-        inv = np.empty(H, dtype=np.int64)
-        inv[np.asarray(rows, dtype=np.int64)] = np.arange(H)
-        sums, feat = sums[inv], feat[inv]
-    one = np.float64(1.0)
-    with np.errstate(all="ignore"):
-        sp = np.float64(p.spp)
-        c = np.where(np.isnan(sums), np.float64(0.0), sums) / sp
-        a, n, z = feat["albedo"] / sp, feat["normal"] / sp, feat["depth"] / sp
-        floor = np.float64(p.albedo_floor)
-        m = np.ones_like(a) if p.flags & F.RT_DENOISE_NO_DEMODULATE else np.where(a > floor, a, floor)
-        e = c / m
-        inv_n = one / (np.float64(p.sigma_normal) * np.float64(p.sigma_normal))
-        inv_z = one / (np.float64(p.sigma_depth) * np.float64(p.sigma_depth))
-        inv_a = one / (np.float64(p.sigma_albedo) * np.float64(p.sigma_albedo))
-        ys, xs = np.meshgrid(np.arange(H, dtype=np.int64), np.arange(W, dtype=np.int64), indexing="ij")
-        for k in range(p.n_iter):
-            s = 1 << k
-            sigma_k = np.float64(p.sigma_color) * np.float64(2.0 ** -k)
-            inv_c = one / (sigma_k * sigma_k)
-            sw, sv = np.zeros((H, W)), np.zeros((H, W, 3))
-            for j in range(-2, 3):
-                for i in range(-2, 3):
-                    qx, qy = xs + i * s, ys + j * s
-                    ok = (qx >= 0) & (qx < W) & (qy >= 0) & (qy < H)
-                    qx, qy = np.clip(qx, 0, W - 1), np.clip(qy, 0, H - 1)
-                    dc, dn, da = dist(e, e[qy, qx]), dist(n, n[qy, qx]), dist(a, a[qy, qx])
-                    dz = z - z[qy, qx]
-                    den = (((one + dc * inv_c) * (one + dn * inv_n)) * (one + (dz * dz) * inv_z)) * (one + da * inv_a)
-                    w = np.float64(H5[j + 2] * H5[i + 2]) / den
-                    sw = np.where(ok, sw + w, sw)
-                    sv = np.where(ok[..., None], sv + w[..., None] * e[qy, qx], sv)
-            e = sv / sw[..., None]
-        out = (e * m) * sp
-    return out if rows is None else out[np.asarray(rows, dtype=np.int64)]
-
-
-def bits(a):
-    v = np.ascontiguousarray(a, dtype=np.float64)
-    return np.where(np.isnan(v), np.float64(0), v).view(np.uint64), np.isnan(v)
-
-
-def assert_same_bits(got, ref, what=""):
-    (gb, gn), (rb, rn) = bits(got), bits(ref)
-    assert gb.shape == rb.shape, what
-    assert np.array_equal(gn, rn), (what, "NaN pattern")
-    bad = np.argwhere(gb != rb)
-    assert len(bad) == 0, (what, "first differing doubles", bad[:5].tolist(), len(bad))
-
-
-def buffers(W, H, spp=4, seed=1, hostile=True, nan_albedo=True):
-    """Random sums and feature records; hostile: NaN radiance components, zero and NaN albedo, all-zero "miss" records, 1e30s."""
-    g = np.random.default_rng(seed)
-    sums = g.uniform(0.0, 2.0 * spp, (H, W, 3))
-    feat = np.zeros((H, W), dtype=F.FEATURE_DTYPE)
-    feat["albedo"] = g.uniform(0.0, 1.0 * spp, (H, W, 3))
-    nrm = g.normal(size=(H, W, 3))
-    feat["normal"] = nrm / np.linalg.norm(nrm, axis=-1, keepdims=True) * spp
-    feat["depth"] = g.uniform(1.0, 20.0, (H, W)) * spp
-    feat["hits"] = spp
-    # a few flat regions, so that some weights are large
-    feat["albedo"][: H // 2, : W // 2] = (0.5 * spp, 0.25 * spp, 0.125 * spp)
-    feat["normal"][: H // 2] = (0.0, 0.0, 1.0 * spp)
-    if hostile:
-        pick = lambda frac, shape: g.random(shape) < frac
-        sums[pick(0.03, (H, W, 3))] = np.nan
-        sums[pick(0.01, (H, W, 3))] = 1e30
-        sums[pick(0.01, (H, W, 3))] = -3.0
-        feat["albedo"][pick(0.03, (H, W))] = 0.0
-        feat["albedo"][pick(0.01, (H, W, 3))] = 1e30
-        feat["depth"][pick(0.01, (H, W))] = 1e30
-        if nan_albedo:
-            feat["albedo"][pick(0.004, (H, W, 3))] = np.nan
-        miss = pick(0.05, (H, W))
-        feat.view(np.float64).reshape(H, W, 8)[miss] = 0.0
-    return sums, feat
 
 
 def check(rt, sums, feat, p, rows=None, what=""):
@@ -230,29 +134,7 @@ def test_bad_row_lists_are_refused_with_the_output_untouched(rt):
         assert_same_bits(d_out.cpu().numpy(), restate(sums, feat, p, rows), "good rows after bad ones")
 
 
-# ---- row lists longer than the row kernel's block ---------------------------------------------------------------------------
-# dn_rows is ONE workgroup of 1024 threads striding over the list: thread t takes entries t, t + 1024, t + 2048, ... So a
-# thread's second trip starts at a height of 1025 (one entry on it) and 2500 rows give every thread two or three entries.
-LONG_W, LONG_HEIGHTS, ROW_BLOCK = 3, (1025, 2500), 1024
-
-
-def long_row_lists(H, seed):
-    """A shuffled list of H > 1024 rows and the lists dn_rows must refuse -> (rows, {fault: list}). A fault whose entries the
-    height does not hold is left out (1025 rows have no entry 1500 or 7 + 1024)."""
-    rows = np.random.default_rng(seed).permutation(H).astype(np.uint32)
-    assert H > ROW_BLOCK and rows.tolist() != list(range(H))
-    bad = {}
-    if H > 1500:                                           # a repeat across trips: entry 5 on a first trip, 1500 on thread 476's second
-        bad["repeat across trips"] = rows.copy()
-        bad["repeat across trips"][5] = rows[1500]
-    if H > 7 + ROW_BLOCK:                                  # a repeat inside one thread: entries 7 and 7 + 1024 are both thread 7's
-        bad["repeat inside one thread"] = rows.copy()
-        bad["repeat inside one thread"][7] = rows[7 + ROW_BLOCK]
-    bad["out of range on the last trip"] = rows.copy()
-    bad["out of range on the last trip"][H - 1] = H
-    return rows, bad
-
-
+# ---- row lists longer than the row kernel's block (denoise_ref.long_row_lists) ------------------------------------------------
 @pytest.mark.parametrize("H", LONG_HEIGHTS)
 def test_row_lists_longer_than_the_row_kernels_block(rt, H):
     """dn_rows' stride loop (pt_denoise.hip): a thread's second trip starts at 1025 rows. The host and the device form against
@@ -334,11 +216,6 @@ def test_device_form_on_torch_buffers_then_tonemap_on_the_same_stream(rt):
 
 
 # ---- end to end ------------------------------------------------------------------------------------------------------------
-def display(sums, spp):
-    c = np.where(np.isnan(sums), 0.0, sums) / spp
-    return np.sqrt(np.clip(c, 0.0, 0.999))
-
-
 @pytest.mark.parametrize("name, W, H", [("cornell_box", 48, 48), ("final_scene", 48, 48), ("random_scene", 60, 40)])
 def test_render_features_denoise_end_to_end(rt, name, W, H):
     """4 spp at seed 2022, rows shuffled, the issue's three views: the denoised sums are the restatement's bit for bit, and

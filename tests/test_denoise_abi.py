@@ -7,6 +7,8 @@ import re
 
 import numpy as np
 
+from denoise_ref import bad_params
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OFFSETS = {"width": 0, "height": 4, "spp": 8, "n_iter": 12, "sigma_color": 16, "sigma_normal": 24, "sigma_depth": 32,
            "sigma_albedo": 40, "albedo_floor": 48, "flags": 56, "_pad": 60}
@@ -50,27 +52,6 @@ def test_params_layout_header_bindings_and_library_agree(rt):
     assert (p.width, p.height, p.spp, p.n_iter, p.flags) == (7, 5, 4, 5, 0)
     assert (p.sigma_color, p.sigma_normal, p.sigma_albedo, p.albedo_floor) == (1.0, 0.3, 0.3, 1e-3) and p.sigma_depth == math.inf
     assert rt.denoise_params(7, 5, 4, demodulate=False).flags == F.RT_DENOISE_NO_DEMODULATE
-
-
-def bad_params(rt):
-    """(what, params) for every way a parameter block can be invalid."""
-    from raytracer_2022_amd import _ffi as F
-    cases = []
-    for field in ("width", "height", "spp"):
-        p = rt.denoise_params(8, 6, 4)
-        setattr(p, field, 0)
-        cases.append((field + " = 0", p))
-    cases.append(("n_iter", rt.denoise_params(8, 6, 4, n_iter=F.RT_DENOISE_MAX_ITER + 1)))
-    for field in ("sigma_color", "sigma_normal", "sigma_depth", "sigma_albedo", "albedo_floor"):
-        for v in (0.0, -1.0, math.nan, -math.inf):
-            cases.append(("%s = %r" % (field, v), rt.denoise_params(8, 6, 4, **{field: v})))
-    cases.append(("infinite floor", rt.denoise_params(8, 6, 4, albedo_floor=math.inf)))
-    for bits in (0x2, 0x80000000, 0x3):
-        p = rt.denoise_params(8, 6, 4)
-        p.flags = bits
-        cases.append(("flags %#x" % bits, p))
-    cases.append(("too many pixels", rt.denoise_params(1 << 20, (1 << 16) + 1, 4)))
-    return cases
 
 
 def test_workspace_bytes(rt):

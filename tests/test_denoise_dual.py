@@ -11,18 +11,12 @@ import pytest
 from raytracer_2022_amd import _ffi as F
 
 import denoise_dual_ref as R
-from denoise_dual_ref import assert_same_bits, restate_dual
-from test_denoise import LONG_HEIGHTS, LONG_W, buffers, long_row_lists, restate as restate_single
+from compare import assert_same_bits
+from denoise_dual_ref import restate_dual
+from denoise_ref import LONG_HEIGHTS, LONG_W, buffers, long_row_lists, restate as restate_single
+from gpu_first import torch_first  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module", autouse=True)
-def torch_first():
-    """Bring torch's HIP context up before the library's first call, as the other GPU test modules do."""
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU: the HIP path has no fallback"
-    torch.zeros(1, device="cuda")
 
 
 def halves(W, H, spp=4, seed=1, hostile=True, nan_albedo=True):

@@ -8,7 +8,7 @@ import re
 import numpy as np
 import pytest
 
-from test_denoise_abi import bad_params
+from denoise_ref import bad_params
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OFFSETS = {"var_iter": 0, "flags": 4, "var_floor": 8}

@@ -1,128 +1,22 @@
 """First-hit feature buffers (rt_features / rt_features_device) against the CPU oracle, bit for bit.
 
-The reference value of a sample is a composition of oracle calls: rto_path_key -> rto_rng_f64 (the two jitter draws) ->
-rto_get_ray (it returns the words it drew) -> rto_hit on the scene's root from the state key + (2 + draws) * 0x9E3779B97F4A7C15
-mod 2^64 (the render's RNG stream, continued) -> the material rule of include/rt2022.h with rto_texture_value. A pixel's
-record is 0 + f_0 + f_1 + ... in sample order with plain f64 adds. Every comparison is on the uint64 view of the doubles
-(NaN where the oracle has NaN)."""
+The reference value of a sample is the composition of oracle calls of tests/features_ref.py (oracle_features). Every
+comparison is on the uint64 view of the doubles (NaN where the oracle has NaN)."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
 from raytracer_2022_amd import _ffi as F
 
+from compare import assert_same_bits, nan_bits
+from features_ref import ASSETS, BUILDERS, check_view, oracle_features
+from gpu_first import torch_first  # noqa: F401
+from query_scenes import every_material_scene
+
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ASSETS = os.path.join(os.path.dirname(HERE), "assets")
-BUILDERS = ["cornell_box", "cornell_smoke", "earth", "final_scene", "random_scene", "simple_light", "two_perlin_spheres",
-            "two_spheres", "wwscene"]
-GOLDEN = 0x9E3779B97F4A7C15
-MASK64 = (1 << 64) - 1
-F64_MAX = float(np.finfo(np.float64).max)
 FIELDS = ("albedo", "normal", "depth", "hits")
-
-
-@pytest.fixture(scope="module", autouse=True)
-def torch_first():
-    """Bring torch's HIP context up before the library's first call, as the other GPU test modules do."""
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU: the HIP path has no fallback"
-    torch.zeros(1, device="cuda")
-
-
-class Seen:
-    """What the oracle composition met: (material kind, texture kind or -1, front_face) of every hit, material indices."""
-
-    def __init__(self):
-        self.kinds, self.mats, self.draws, self.medium_draws = set(), set(), 0, 0
-
-
-def oracle_sample(O, desc, cam, p, px, py, frame, s, st, seen):
-    """One sample's (albedo[3], normal[3], depth, hits) by the composition of oracle calls."""
-    L = O.lib()
-    key = L.rto_path_key(p.seed, frame, py * p.width + px, s)
-    uv = (C.c_double * 2)()
-    L.rto_rng_f64(key, uv, 2)
-    with np.errstate(all="ignore"):
-        u = float((np.float64(px) + np.float64(uv[0])) / np.float64(p.width - 1))
-        v = float((np.float64(py) + np.float64(uv[1])) / np.float64(p.height - 1))
-    ray = (C.c_double * 7)()
-    draws = L.rto_get_ray(C.byref(cam), u, v, (key + 2 * GOLDEN) & MASK64, ray)
-    rec = O.rto_hit_record()
-    L.rto_hit(C.byref(desc), desc.root, ray, p.t_min, F64_MAX, (key + (2 + draws) * GOLDEN) & MASK64, C.byref(rec), C.byref(st))
-    seen.draws += 2 + draws + rec.rng_draws
-    seen.medium_draws += rec.rng_draws
-    if not rec.hit:
-        return list(p.background) + [0.0, 0.0, 0.0, 0.0, 0.0]
-    m = desc.materials[rec.mat]
-    front = bool(rec.front_face)
-    tex_kind = desc.textures[m.tex].kind if m.kind in (F.RT_MAT_LAMBERTIAN, F.RT_MAT_ISOTROPIC, F.RT_MAT_DIFFUSE_LIGHT) else -1
-    seen.kinds.add((m.kind, tex_kind, front))
-    seen.mats.add(rec.mat)
-    if m.kind == F.RT_MAT_METAL:
-        alb = list(m.albedo)
-    elif m.kind == F.RT_MAT_DIELECTRIC:
-        alb = [1.0, 1.0, 1.0]
-    elif m.kind == F.RT_MAT_DIFFUSE_LIGHT and not front:
-        alb = [0.0, 0.0, 0.0]
-    else:
-        alb = list(O.texture_value(desc, m.tex, rec.u, rec.v, rec.p[:]))
-    return alb + list(rec.normal) + [rec.t, 1.0]
-
-
-def oracle_features(O, desc, cam, params, rows, pixels=None):
-    """The reference records of the pixels [(row index, px)] (default: all) → (FEATURE_DTYPE array of len(pixels), summed
-    rt_stats of the hits, Seen)."""
-    rows = np.asarray(rows, dtype=np.uint32)
-    if pixels is None:
-        pixels = [(i, px) for i in range(len(rows)) for px in range(params.width)]
-    out = np.zeros(len(pixels), dtype=F.FEATURE_DTYPE)
-    flat = out.view(np.float64).reshape(len(pixels), 8)
-    st, seen = F.rt_stats(), Seen()
-    for k, (i, px) in enumerate(pixels):
-        g = int(rows[i])
-        frame, py = divmod(g, params.height)
-        acc = [0.0] * 8
-        for s in range(params.spp):
-            f = oracle_sample(O, desc, cam, params, int(px), py, frame, s, st, seen)
-            acc = [a + float(b) for a, b in zip(acc, f)]               # plain f64 adds, in sample order
-        flat[k] = acc
-    return out, st, seen
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    v = a.view(np.float64) if a.dtype == F.FEATURE_DTYPE else np.asarray(a, dtype=np.float64)
-    return np.where(np.isnan(v), np.float64(0), v).view(np.uint64), np.isnan(v)
-
-
-def assert_same_bits(got, ref, what=""):
-    (gb, gn), (rb, rn) = bits(got), bits(ref)
-    assert gb.shape == rb.shape, what
-    assert np.array_equal(gn, rn), (what, "NaN pattern")
-    bad = np.argwhere(gb != rb)
-    assert len(bad) == 0, (what, "first differing doubles", bad[:5].tolist(), len(bad))
-
-
-def check_view(rt, O, desc, cam, params, rows, dev=None, counters=True):
-    dev = dev or rt.DeviceScene(desc)
-    got, st = dev.features(cam, params, rows, want_stats=True)
-    assert got.shape == (len(rows), params.width) and got.dtype == F.FEATURE_DTYPE
-    ref, st_ref, seen = oracle_features(O, desc, cam, params, rows)
-    assert_same_bits(got.reshape(-1), ref)
-    n = len(rows) * params.width * params.spp
-    assert st.paths == st.rays == n
-    if counters:
-        assert st.node_visits == st_ref.node_visits and list(st.prim_tests) == list(st_ref.prim_tests)
-        assert st.rng_draws == seen.draws
-    assert st.light_pdf_tests == 0 and st.passes == 0 and st.pool_slots == 0 and st.partial_bytes == 0 and st.spp_chunk == 0
-    assert st.trace_ms == 0 and st.shade_ms == 0 and st.ms > 0
-    plain = dev.features(cam, params, rows)                                # the plain (non-counter) kernel instance
-    assert_same_bits(plain.reshape(-1), ref, "plain instance")
-    return got, seen, dev
 
 
 # ---- 1. scene builders ------------------------------------------------------------------------------------------------
@@ -137,44 +31,9 @@ def test_every_scene_builder_matches_the_oracle(rt, O, name):
 
 
 # ---- 2. camera draws --------------------------------------------------------------------------------------------------
-def every_kind_scene(rt):
-    """Every material kind x every texture kind, a back-faced and a flipped light, movers at depth 4, a triangle, a ring,
-    media, a moving sphere; no light list (n_lights == 0)."""
-    b = rt.DescBuilder()
-    g = np.random.default_rng(11)
-    vec = g.normal(size=(256, 3))
-    vec /= np.linalg.norm(vec, axis=1, keepdims=True)
-    pl = b.perlin(vec, g.permutation(256), g.permutation(256), g.permutation(256))
-    img = (np.arange(8 * 4 * 3, dtype=np.uint8).reshape(4, 8, 3) * 7) % 251
-    textures = lambda: [b.solid((0.7, 0.3, 0.2)), b.checker(b.solid((0.2, 0.3, 0.1)), b.solid((0.9, 0.9, 0.9))), b.noise(pl, 4.0), b.image(img)]
-    mats = ([b.lambertian(tex=t) for t in textures()] + [b.diffuse_light(tex=t) for t in textures()] +
-            [b.metal((0.8, 0.7, 0.6), 0.3), b.dielectric(1.5)])
-    refs = []
-    for i, m in enumerate(mats):
-        refs.append(b.sphere(((i % 5 - 2) * 1.2, (i // 5) * 1.2, 0.0), 0.45, m))
-    glass = b.dielectric(1.5)
-    for i, t in enumerate(textures()):                                      # isotropic x every texture: dense media
-        refs.append(b.medium(b.sphere(((i - 1.5) * 1.2, 3.6, 0.0), 0.45, glass), 8.0, b.isotropic(tex=t)))
-    floor_tex = b.checker(b.noise(pl, 2.0), b.image(img))                   # a checker of a noise and an image
-    refs.append(b.rect(F.RT_RECT_XZ, -30, 30, -30, 30, -0.6, b.lambertian(tex=floor_tex)))
-    refs.append(b.rect(F.RT_RECT_XZ, -3, 3, -4, 2, 4.3, b.diffuse_light((8, 8, 8))))               # seen from below: back face
-    refs.append(b.rect(F.RT_RECT_XY, -6, -3.2, 0, 3, -1.0, b.diffuse_light((4, 5, 6)), flip=True))  # FlipFace ref
-    tri_mat, ring_mat, box_mat = b.metal((0.1, 0.9, 0.5), 0.0), b.lambertian((0.9, 0.1, 0.9)), b.lambertian((0.3, 0.6, 0.9))
-    refs.append(b.triangle((-4.2, -0.5, 1), (-3.0, -0.5, 1), (-3.6, 0.9, 1.5), tri_mat))
-    refs.append(b.translate(b.ring(0.9, 0.3, ring_mat), (3.6, -0.3, 3.0)))
-    deep = b.translate(b.rotate_y(b.zoom(b.translate(b.box((-0.4, 0, -0.4), (0.4, 0.8, 0.4), box_mat), (0.1, 0.0, 0.1)), 1.3),
-                                  0.5, 0.8660254037844386), (3.8, 1.0, 0.5))
-    refs.append(deep)
-    mover_mat = b.lambertian((0.5, 0.5, 0.1))
-    refs.append(b.moving_sphere((-3.8, 2.2, 0), (-3.8, 3.0, 0), 0, 1, 0.45, mover_mat))
-    b.set_root(b.list(refs))
-    named = {"triangle": tri_mat, "ring": ring_mat, "box": box_mat, "moving": mover_mat}
-    return b, b.desc(), named
-
-
 def test_lens_and_shutter_draws_on_moving_spheres(rt, O):
     """Aperture > 0 (the lens disk's rejection loop) and time0 < time1 on a scene with a moving sphere and media."""
-    b, d, named = every_kind_scene(rt)
+    b, d, named = every_material_scene(rt)
     assert d.n_lights == 0 and d.n_moving_spheres == 1
     W, H = 54, 36
     cam = rt.camera_new((0, 1.8, 10), (0, 1.6, 0), (0, 1, 0), 40.0, W / H, 0.4, 10.0, 0.0, 1.0)
@@ -199,7 +58,7 @@ def test_medium_draws_follow_the_cameras(rt, O, name):
 
 # ---- 3. material and texture kinds ------------------------------------------------------------------------------------
 def test_every_material_and_texture_kind(rt, O):
-    b, d, named = every_kind_scene(rt)
+    b, d, named = every_material_scene(rt)
     W, H = 60, 40
     cam = rt.camera_new((0, 1.8, 10), (0, 1.6, 0), (0, 1, 0), 40.0, W / H, 0.0, 10.0, 0.0, 1.0)
     p = rt.make_params(W, H, 2, 50, (0.25, 0.5, 0.75), seed=3)
@@ -231,7 +90,7 @@ def test_row_lists_frames_strips_and_orders(rt, O):
     p1 = rt.make_params(W, H, spp, 50, bg, seed=5)
     frame0 = dev.features(cam, p1, np.arange(H, dtype=np.uint32))          # n_frames = 1: frame 0 again
     assert_same_bits(frame0, dev.features(cam, p2, np.arange(H, dtype=np.uint32)))
-    assert not np.array_equal(bits(frame0)[0], bits(dev.features(cam, p2, np.arange(H, 2 * H, dtype=np.uint32)))[0])    # frame 1 has its own key
+    assert not np.array_equal(nan_bits(frame0)[0], nan_bits(dev.features(cam, p2, np.arange(H, 2 * H, dtype=np.uint32)))[0])    # frame 1 has its own key
     strip = np.array([7, 8, 9, 21], dtype=np.uint32)
     assert_same_bits(dev.features(cam, p1, strip), frame0[strip], "strip")
     order = np.random.default_rng(6).permutation(H).astype(np.uint32)

@@ -3,7 +3,7 @@ resolve against their numpy restatement (adaptive_features_ref.py); render_adapt
 
 Record e of a list is the record rt_features writes for column px of row id frame * height + py, id = frame * (width * height)
 + py * width + px — so with every row of every frame in order, it is record `id` of rt_features' flattened output. The oracle
-composition is test_features.py's (oracle_features), asked for the same pixels. Every comparison is on the uint64 view of the
+composition is features_ref.py's (oracle_features), asked for the same pixels. Every comparison is on the uint64 view of the
 doubles (NaN where the reference has NaN)."""
 import ctypes as C
 
@@ -12,49 +12,15 @@ import pytest
 
 import adaptive_features_ref as FR
 from raytracer_2022_amd import _ffi as F
-from test_features import ASSETS, BUILDERS, assert_same_bits, every_kind_scene, oracle_features
+
+from compare import assert_same_bits
+from features_ref import ASSETS, BUILDERS, all_rows, check_first_hit_counters, oracle_ids, shuffled_ids_with_repeats
+from gpu_first import torch_first  # noqa: F401
+from query_scenes import every_material_scene
 
 pytestmark = pytest.mark.gpu
 
 W0, H0, SPP0 = 24, 16, 3
-
-
-@pytest.fixture(scope="module", autouse=True)
-def torch_first():
-    """Bring torch's HIP context up before the library's first call, as the other GPU test modules do."""
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU: the HIP path has no fallback"
-    torch.zeros(1, device="cuda")
-
-
-def all_rows(height, n_frames):
-    return np.arange(height * n_frames, dtype=np.uint32)
-
-
-def shuffled_ids_with_repeats(n_ids, seed):
-    """Every id of [0, n_ids) shuffled, then 10 % of them once more at random places."""
-    g = np.random.default_rng(seed)
-    ids = g.permutation(n_ids).astype(np.uint64)
-    again = g.choice(ids, n_ids // 10, replace=False)
-    ids = np.insert(ids, g.integers(0, n_ids, again.size), again)
-    assert ids.size == n_ids + n_ids // 10
-    return np.ascontiguousarray(ids)
-
-
-def oracle_ids(O, desc, cam, p, ids):
-    """oracle_features for a list of ids: entry k is pixel (k, px_k) of a row list that holds entry k's row id."""
-    ids = [int(i) for i in ids]
-    ip = p.width * p.height
-    rows = np.array([(i // ip) * p.height + (i % ip) // p.width for i in ids], dtype=np.uint32)
-    return oracle_features(O, desc, cam, p, rows, pixels=[(k, (i % ip) % p.width) for k, i in enumerate(ids)])
-
-
-def check_counters(st, st_ref, seen, n, spp):
-    assert st.paths == st.rays == n * spp
-    assert st.node_visits == st_ref.node_visits and list(st.prim_tests) == list(st_ref.prim_tests)
-    assert st.rng_draws == seen.draws
-    assert st.light_pdf_tests == 0 and st.passes == 0 and st.pool_slots == 0 and st.partial_bytes == 0 and st.spp_chunk == 0
-    assert st.trace_ms == 0 and st.shade_ms == 0 and st.ms > 0
 
 
 # ---- 1. entry by entry against rt_features ----------------------------------------------------------------------------
@@ -79,7 +45,7 @@ def test_every_scene_builder_entry_by_entry(rt, name):
 # ---- 2. against the oracle composition, with its counters --------------------------------------------------------------
 def oracle_case(rt, which):
     if which == "every_kind":
-        b, d, _ = every_kind_scene(rt)
+        b, d, _ = every_material_scene(rt)
         cam = rt.camera_new((0, 1.8, 10), (0, 1.6, 0), (0, 1, 0), 40.0, W0 / H0, 0.0, 10.0, 0.0, 1.0)
         return b, d, cam, (0.25, 0.5, 0.75)
     s = rt.HostScene(which, seed=2022)
@@ -99,7 +65,7 @@ def test_oracle_composition_and_counters(rt, O, which):
     got, st = dev.features_pixels(cam, p, ids, want_stats=True)
     ref, st_ref, seen = oracle_ids(O, d, cam, p, ids)
     assert_same_bits(got, ref)
-    check_counters(st, st_ref, seen, ids.size, SPP0)
+    check_first_hit_counters(st, st_ref, seen, ids.size, SPP0)
     if which == "cornell_smoke":
         assert seen.medium_draws > 0
     if which == "random_scene":
@@ -152,7 +118,7 @@ def test_ids_past_32_bits_take_the_64_bit_decode(rt, O):
     got, st = dev.features_pixels(cam, big, ids, want_stats=True)
     ref, st_ref, seen = oracle_ids(O, s.desc, cam, big, ids)
     assert_same_bits(got, ref, "64-bit decode")
-    check_counters(st, st_ref, seen, ids.size, SPP0)
+    check_first_hit_counters(st, st_ref, seen, ids.size, SPP0)
     small = rt.make_params(W, H, SPP0, 50, bg, seed=12, n_frames=2)            # the same entries through the 32-bit decode
     assert_same_bits(dev.features_pixels(cam, small, low), got[:48], "32-bit decode")
     edge = rt.make_params(W, H, SPP0, 50, bg, seed=12, n_frames=(1 << 32) // (W * H))     # the largest view that still fits: ids < 2^32
@@ -273,7 +239,7 @@ def test_deep_stack_instance_on_single_pixels_of_the_full_view(rt, O):
     got, st = dev.features_pixels(cam, p, ids, want_stats=True)
     ref, st_ref, seen = oracle_ids(O, d, cam, p, ids)
     assert_same_bits(got, ref)
-    check_counters(st, st_ref, seen, ids.size, spp)
+    check_first_hit_counters(st, st_ref, seen, ids.size, spp)
     assert_same_bits(dev.features_pixels(cam, p, ids), ref, "plain instance")
     assert got["hits"].sum() > 100
 

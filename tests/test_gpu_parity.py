@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+from compare import bits
 from raytracer_2022_amd import _ffi as F
 from trace_scenes import median_split_bvh as _median_split_bvh
 
@@ -15,10 +16,6 @@ pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 INDEX = json.load(open(os.path.join(HERE, "golden", "golden_index.json")))
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
 def test_extension_is_loaded_and_device_visible(rt):

@@ -16,11 +16,9 @@ import os
 import numpy as np
 import pytest
 
+from compare import bits
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
 def test_the_own_build_shares_nothing(O):

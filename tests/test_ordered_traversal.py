@@ -10,28 +10,14 @@ import pytest
 
 import trace_scenes as T
 from raytracer_2022_amd import _ffi as F
+from compare import same_bits
+from gpu_first import torch_first  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 REF_ORDER = 1 << 15                                      # rt2022_debug.h: tuning bit 15
 W = H = 48
 OCTANTS = [(sx, sy, sz) for sx in (1, -1) for sy in (1, -1) for sz in (1, -1)]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def torch_first():
-    """Bring torch's HIP context up before the library's first call, as the other GPU test modules do."""
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU: the HIP path has no fallback"
-    torch.zeros(1, device="cuda")
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def same(a, ref):
-    return np.array_equal(np.isnan(a), np.isnan(ref)) and np.array_equal(bits(a), bits(ref))
 
 
 # ---- scenes over the reference's own BVH builder -------------------------------------------------------------------------
@@ -179,7 +165,7 @@ def test_ties_from_all_octants(rt, O, swap_log, kind, seed):
             dev.set_tuning(word)
             assert dev.child_order() == {"timed": ordered, "counting": False}
             out = dev.render(cam, p, rows)
-            assert same(out, ref), (kind, seed, octant, "ordered" if ordered else "reference order")
+            assert same_bits(out, ref, payloads=True), (kind, seed, octant, "ordered" if ordered else "reference order")
     swap_log[(kind, seed)] = swapped
     assert len(ranked) == 2
 
@@ -244,10 +230,10 @@ def test_medium_between_reorderable_subtrees(rt, O):
         for word, ordered in ((T.TUNING, True), (T.TUNING | REF_ORDER, False)):
             dev.set_tuning(word)
             assert dev.child_order()["timed"] == ordered
-            assert same(dev.render(cam, p, rows), ref), (look_from, ordered)
+            assert same_bits(dev.render(cam, p, rows), ref, payloads=True), (look_from, ordered)
         dev.set_tuning(T.TUNING)
         out, st = dev.render(cam, p, rows, want_stats=True)
-        assert same(out, ref)
+        assert same_bits(out, ref, payloads=True)
         assert st.as_dict()["rng_draws"] == st_ref.as_dict()["rng_draws"]
         assert st.as_dict() == st_ref.as_dict()
 
@@ -295,10 +281,10 @@ def test_instance_family(rt, O, family):
     for word, ordered in ((tuning, True), (tuning | REF_ORDER, False)):
         dev.set_tuning(word)
         assert dev.child_order() == {"timed": ordered, "counting": False}
-        assert same(dev.render(cam, p, rows), ref), (family, "ordered" if ordered else "reference order")
+        assert same_bits(dev.render(cam, p, rows), ref, payloads=True), (family, "ordered" if ordered else "reference order")
     dev.set_tuning(tuning)
     out, st = dev.render(cam, p, rows, want_stats=True)
-    assert same(out, ref)
+    assert same_bits(out, ref, payloads=True)
     got, exp = st.as_dict(), st_ref.as_dict()
     assert got["node_visits"] == exp["node_visits"] and list(got["prim_tests"]) == list(exp["prim_tests"])
     assert got == exp

@@ -10,115 +10,40 @@ import pytest
 
 from raytracer_2022_amd import _ffi as F
 
+from compare import same_bits
+from gpu_first import torch_first  # noqa: F401
+from query_ref import unit_vectors
+from query_scenes import every_kind_lit_scene
+from radiance_ref import oracle_radiance, radiance_camera_rays, radiance_counters
+
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ASSETS = os.path.join(os.path.dirname(HERE), "assets")
 INDEX = json.load(open(os.path.join(HERE, "golden", "golden_index.json")))
 BUILDERS = sorted({c["scene"] for c in INDEX.values()})
-COUNTERS = ("rays", "node_visits", "prim_tests", "light_pdf_tests", "rng_draws")
-
-
-@pytest.fixture(scope="module", autouse=True)
-def torch_first():
-    """Bring torch's HIP context up before the library's first call, as the other GPU test modules do."""
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU: the HIP path has no fallback"
-    torch.zeros(1, device="cuda")
-
-
-def oracle_radiance(O, desc, rays, spp, background=(0.0, 0.0, 0.0), t_min=0.001, depth=50):
-    """sum over s of rto_ray_color(ray, ..., rto_path_key(rng_state, 0, 0, s)) for every ray → ((n, 3) sums, summed rt_stats)."""
-    out = np.zeros((len(rays), 3))
-    st = F.rt_stats()
-    key = O.lib().rto_path_key
-    for i, r in enumerate(rays):
-        acc = np.zeros(3)                                                          # pixel_color = 0 (main.rs:143)
-        for s in range(spp):
-            acc = acc + O.ray_color(desc, r["origin"], r["direction"], tm=float(r["time"]), background=background, t_min=t_min,
-                                    depth=depth, rng_state=key(int(r["rng_state"]), 0, 0, s), stats=st)
-        out[i] = acc
-    return out, st
-
-
-def same_bits(a, b):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return np.array_equal(np.isnan(a), np.isnan(b)) and np.array_equal(np.where(np.isnan(a), 0, a).view(np.uint64),
-                                                                       np.where(np.isnan(b), 0, b).view(np.uint64))
-
-
-def counters(st):
-    d = st.as_dict()
-    return {k: d[k] for k in COUNTERS}
 
 
 def check(rt, O, dev, desc, rays, spp=1, background=(0.0, 0.0, 0.0), t_min=0.001, depth=50, what=""):
     got, st = dev.radiance(rays, spp=spp, background=background, t_min=t_min, max_depth=depth, want_stats=True)
     ref, st_ref = oracle_radiance(O, desc, rays, spp, background, t_min, depth)
     assert same_bits(got, ref), (what, np.argwhere(~((got == ref) | (np.isnan(got) & np.isnan(ref))))[:5])
-    assert counters(st) == counters(st_ref), what
+    assert radiance_counters(st) == radiance_counters(st_ref), what
     assert st.paths == len(rays) * spp and st.spp_chunk == 1, what
     plain = dev.radiance(rays, spp=spp, background=background, t_min=t_min, max_depth=depth)    # the plain kernel instances
     assert same_bits(plain, got), what
     return got, st
 
 
-def unit_vectors(g, n):
-    v = g.normal(size=(n, 3))
-    return v / np.linalg.norm(v, axis=1, keepdims=True)
-
-
-def camera_dirs(cam, n, g):
-    s, t = g.random(n), g.random(n)
-    o = np.array(cam.origin[:])
-    return o, np.array(cam.lower_left_corner[:]) + s[:, None] * np.array(cam.horizontal[:]) + t[:, None] * np.array(cam.vertical[:]) - o
-
-
-def camera_rays(rt, cam, n, g):
-    """Pinhole rays of the camera's view at random points of the image and shutter times, random RNG states."""
-    o, d = camera_dirs(cam, n, g)
-    return rt.radiance_rays(o, d, time=g.uniform(cam.time0, cam.time1, n), rng_state=g.integers(0, 2**63, n, dtype=np.uint64))
-
-
 def mixed_rays(rt, dev, cam, n, g):
     """Camera rays and bounce rays from the hits of rt_intersect (origin p, direction normal + a random unit vector)."""
-    first = camera_rays(rt, cam, n // 2, g)
+    first = radiance_camera_rays(rt, cam, n // 2, g)
     q = rt.query_rays(first["origin"], first["direction"], time=first["time"])
     h = dev.intersect(q)
     h = h[h["hit"] == 1][: n - len(first)]
     bounce = rt.radiance_rays(h["p"], h["normal"] + unit_vectors(g, len(h)), time=g.random(len(h)),
                               rng_state=g.integers(0, 2**63, len(h), dtype=np.uint64))
-    return np.concatenate([first, bounce, camera_rays(rt, cam, n - len(first) - len(bounce), g)])      # (camera rays fill up)
-
-
-def every_kind_scene(rt, lights=True):
-    """One of each hittable kind (movers, a list, a flipped light, a medium, a moving sphere) and every texture kind."""
-    b = rt.DescBuilder()
-    lam = b.lambertian((0.6, 0.5, 0.4))
-    img = (np.arange(8 * 4 * 3, dtype=np.uint8).reshape(4, 8, 3) * 7) % 251
-    g = np.random.default_rng(11)
-    pl = b.perlin(unit_vectors(g, 256), g.permutation(256), g.permutation(256), g.permutation(256))
-    rect_light = b.rect(F.RT_RECT_XZ, -1, 1, -1, 1, 6.0, b.diffuse_light((8, 8, 8)), flip=True)
-    ball_light = b.sphere((5, 6, -2), 0.7, b.diffuse_light((20, 18, 15)))
-    refs = [
-        b.sphere((0, -100, 0), 100.0, b.lambertian(tex=b.checker(b.solid((0.2, 0.3, 0.1)), b.solid((0.9, 0.9, 0.9))))),
-        b.sphere((0, 1, 0), 1.0, b.lambertian(tex=b.image(img))),
-        b.sphere((1.8, 0.6, 1.8), 0.6, b.lambertian(tex=b.noise(pl, 4.0))),
-        b.moving_sphere((2.5, 0.5, 0), (2.5, 1.0, 0), 0, 1, 0.5, b.metal((0.8, 0.7, 0.6), 0.3)),
-        b.sphere((-2.5, 1, 0), 1.0, b.dielectric(1.5)),
-        b.triangle((-1, 0.01, 2), (1, 0.01, 2), (0, 1.5, 2.5), lam),
-        b.translate(b.ring(1.5, 0.3, lam), (0, 0.5, -3)),
-        b.translate(b.rotate_y(b.zoom(b.box((-0.5, 0, -0.5), (0.5, 1, 0.5), lam), 1.5), 0.5, 0.8660254037844386), (4.5, 0, 2)),
-        b.list([rect_light, b.rect(F.RT_RECT_XY, -6, 6, 0, 4, -6.0, lam)]),
-        b.medium(b.sphere((-4, 1, 2), 1.0, b.dielectric(1.5)), 0.8, b.isotropic((0.3, 0.3, 0.9))),
-        ball_light,
-    ]
-    b.set_root(b.list(refs))
-    if lights:
-        b.light(rect_light)
-        b.light(ball_light)
-    cam = rt.camera_new((9, 4, 9), (0, 1, 0), (0, 1, 0), 35.0, 56 / 40, 0.0, 12.0, 0.0, 1.0)
-    return b, b.desc(), cam
+    return np.concatenate([first, bounce, radiance_camera_rays(rt, cam, n - len(first) - len(bounce), g)])      # (camera rays fill up)
 
 
 @pytest.mark.parametrize("name", BUILDERS)
@@ -140,14 +65,14 @@ def test_sample_order_and_the_ring(rt, O):
     d = s.desc
     cam, bg = s.default_view(1.0)
     dev = rt.DeviceScene(d)
-    rays = camera_rays(rt, cam, 64, np.random.default_rng(37))
+    rays = radiance_camera_rays(rt, cam, 64, np.random.default_rng(37))
     got, st = check(rt, O, dev, d, rays, spp=37, background=tuple(bg))
     assert st.partial_bytes == 64 * 37 * 24
     for planes in (1, 3):
         dev.set_partial_ring(planes)
         ring, st_r = dev.radiance(rays, spp=37, background=tuple(bg), want_stats=True)
         assert same_bits(ring, got), planes
-        assert st_r.partial_bytes == planes * 64 * 24 and counters(st_r) == counters(st), planes
+        assert st_r.partial_bytes == planes * 64 * 24 and radiance_counters(st_r) == radiance_counters(st), planes
     dev.set_partial_ring(0)
     # a ray's result depends neither on its place in the batch nor on the batch
     perm = np.random.default_rng(1).permutation(64)
@@ -157,7 +82,7 @@ def test_sample_order_and_the_ring(rt, O):
 
 @pytest.mark.parametrize("lights", [True, False])
 def test_every_object_kind_texture_and_depth(rt, O, lights):
-    b, d, cam = every_kind_scene(rt, lights=lights)
+    b, d, cam = every_kind_lit_scene(rt, lights=lights)
     assert (d.n_lights > 0) == lights
     dev = rt.DeviceScene(d)
     g = np.random.default_rng(3 + lights)
@@ -177,7 +102,7 @@ def test_every_object_kind_texture_and_depth(rt, O, lights):
 def test_hostile_rays(rt, O):
     """Rays no camera makes: zero direction components, a zero direction, +-inf and NaN components, origins inside the
     medium's boundary, inside the dielectric ball and inside the box."""
-    _, d, _ = every_kind_scene(rt)
+    _, d, _ = every_kind_lit_scene(rt)
     dev = rt.DeviceScene(d)
     rays = []
     for o in [(0, 1, 8), (0.0, 0.5, 0.0), (4.5, 0.5, 2.0), (-4, 1, 2), (-2.5, 1, 0), (0, 0, 0), (0, 3, 0)]:
@@ -196,7 +121,7 @@ def test_counters_and_stats(rt, O):
     d = s.desc
     cam, bg = s.default_view(1.0)
     dev = rt.DeviceScene(d)
-    rays = camera_rays(rt, cam, 200, np.random.default_rng(5))
+    rays = radiance_camera_rays(rt, cam, 200, np.random.default_rng(5))
     _, st = check(rt, O, dev, d, rays, spp=5, background=tuple(bg))
     assert st.light_pdf_tests > 0 and st.rng_draws > 0 and st.prim_tests[F.RT_KIND_MEDIUM] > 0
     assert st.ms > 0 and st.passes > 0 and st.pool_slots > 0 and st.partial_bytes == 200 * 5 * 24
@@ -273,7 +198,7 @@ def test_big_batches_on_the_timed_instances(rt, O, scene, param, assets, n):
     cam, bg = s.default_view(1.0)
     dev = rt.DeviceScene(d)
     g = np.random.default_rng(n)
-    rays = camera_rays(rt, cam, n, g)
+    rays = radiance_camera_rays(rt, cam, n, g)
     got, st = dev.radiance(rays, spp=1, background=tuple(bg), want_stats=True)
     assert st.paths == n and st.rays >= n
     pick = np.sort(g.choice(n, 2000, replace=False))

@@ -15,7 +15,9 @@ import numpy as np
 import pytest
 
 import radiometry_cases as RC
-from test_radiance import camera_rays, counters, every_kind_scene, oracle_radiance, same_bits
+from compare import same_bits
+from query_scenes import every_kind_lit_scene
+from radiance_ref import oracle_radiance, radiance_camera_rays, radiance_counters
 
 N_RAYS, SPP = 256, 1024
 THREADS = max(1, min(8, os.cpu_count() or 1))
@@ -101,11 +103,11 @@ def test_narrow_camera_sees_only_the_neighbourhood_of_P(rt):
 
 # ---- the batched oracle entry equals the established loop ------------------------------------------------------------------
 def test_rto_radiance_equals_the_ray_color_loop(rt, O):
-    """rto_radiance against the Python loop over rto_ray_color (test_radiance.oracle_radiance) on every_kind_scene: the same
+    """rto_radiance against the Python loop over rto_ray_color (radiance_ref.oracle_radiance) on every_kind_lit_scene: the same
     sums bit for bit and the same counters, for any number of worker threads."""
-    _, d, cam = every_kind_scene(rt)
+    _, d, cam = every_kind_lit_scene(rt)
     g = np.random.default_rng(5)
-    rays = camera_rays(rt, cam, 160, g)
+    rays = radiance_camera_rays(rt, cam, 160, g)
     up = rt.radiance_rays((0.0, 3.0, 0.0), g.normal(size=(40, 3)), time=g.random(40), rng_state=g.integers(0, 2 ** 63, 40, dtype=np.uint64))
     odd = rt.radiance_rays([(-4, 1, 2), (0, 1, 8), (0, 0, 0)], [(0, 0, 0), (np.nan, 0, -1), (1e-300, 0, -1)], time=0.3, rng_state=7)
     rays = np.concatenate([rays, up, odd])
@@ -114,7 +116,7 @@ def test_rto_radiance_equals_the_ray_color_loop(rt, O):
         for threads in (1, 3, 7):
             got, st = O.radiance(d, rays, spp=spp, background=bg, depth=depth, n_threads=threads, want_stats=True)
             assert same_bits(got, ref), (spp, threads)
-            assert counters(st) == counters(st_ref) and st.paths == len(rays) * spp, (spp, threads)
+            assert radiance_counters(st) == radiance_counters(st_ref) and st.paths == len(rays) * spp, (spp, threads)
     assert np.any(ref != 0) and st_ref.prim_tests[rt._ffi.RT_KIND_MEDIUM] > 0 and st_ref.light_pdf_tests > 0
     empty, st = O.radiance(d, rays[:0], spp=4, want_stats=True)
     assert empty.shape == (0, 3) and st.paths == 0 and st.rays == 0

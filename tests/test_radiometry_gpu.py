@@ -10,19 +10,12 @@ import numpy as np
 import pytest
 
 import radiometry_cases as RC
-from test_radiance import same_bits
+from compare import same_bits
+from gpu_first import torch_first  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 N_RAYS, SPP = 4096, 4096
-
-
-@pytest.fixture(scope="module", autouse=True)
-def torch_first():
-    """Bring torch's HIP context up before the library's first call, as the other GPU test modules do."""
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU: the HIP path has no fallback"
-    torch.zeros(1, device="cuda")
 
 
 _sums = {}

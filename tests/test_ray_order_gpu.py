@@ -9,9 +9,10 @@ import pytest
 
 import ray_order_cases as K
 import ray_order_ref as R
+from gpu_first import torch_first  # noqa: F401
+from query_ref import bounce_rays, camera_rays, mixed_rays, randomise_windows
 from query_scenes import every_kind_scene
 from raytracer_2022_amd import _ffi as F
-from test_query import bounce_rays, camera_rays, mixed_rays, randomise_windows
 
 pytestmark = pytest.mark.gpu
 
@@ -20,14 +21,6 @@ FILL = 0xA5
 M = 4099                                                   # the query batches: a prime, 65 waves
 REDUCE_THREADS = 1024 * 256                                # order_box_partial's grid at the most (kOrderReduceBlocks blocks of 256)
 MID_BITS = (10, 4)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def torch_first():
-    """Bring torch's HIP context up before the library's first call, as the other GPU test modules do."""
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU: the HIP path has no fallback"
-    torch.zeros(1, device="cuda")
 
 
 @pytest.fixture(scope="module")

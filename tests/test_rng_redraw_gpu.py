@@ -11,16 +11,14 @@ import pytest
 
 from raytracer_2022_amd import _ffi as F
 
+from compare import bits
+
 pytestmark = pytest.mark.gpu
 
 N = 4096
 GAMMA = 0x9E3779B97F4A7C15
 M64 = (1 << 64) - 1
 STATE = 0x2022_0BAD_5EED_0001
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
 def device(rt, mode, lo, hi, bound, n=N, state=STATE):

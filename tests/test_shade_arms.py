@@ -14,34 +14,20 @@ import shade_scenes as S
 import trace_scenes as T
 from raytracer_2022_amd import _ffi as F
 from raytracer_2022_amd import film
-from test_radiance import counters as radiance_counters
-from test_radiance import oracle_radiance
+from compare import same_bits
+from gpu_first import torch_first  # noqa: F401
+from radiance_ref import oracle_radiance, radiance_counters
 
 pytestmark = pytest.mark.gpu
+
+# Every comparison here is same_bits without payloads — bit for bit, a NaN wherever the oracle has one. A NaN's payload must not
+# be compared: 0 / 0 and inf * 0 need not agree on a sign.
 
 IDS = [c.name for c in S.CASES]
 # every material kind (and the textures that need u, v on each), the light list behind the LDS table, every tape case
 SPREAD = ["lambertian-checker-image-noise", "light-image", "isotropic-nested8", "metal-fuzz-1", "glass-outside", "lights-9",
           "tape-black-background", "tape-sky-background", "tape-depth-2", "tape-zero-light", "tape-inf-light"]
 SPP7 = 7
-
-
-@pytest.fixture(scope="module", autouse=True)
-def torch_first():
-    """Bring torch's HIP context up before the library's first call, as the other GPU test modules do."""
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU: the HIP path has no fallback"
-    torch.zeros(1, device="cuda")
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def same(a, ref):
-    """Bit for bit; a NaN wherever the oracle has one (its payload is not compared: 0 / 0 and inf * 0 need not agree on a sign)."""
-    nan = np.isnan(ref)
-    return a.shape == ref.shape and np.array_equal(np.isnan(a), nan) and np.array_equal(bits(a)[~nan], bits(ref)[~nan])
 
 
 def with_params(p, **kw):
@@ -85,9 +71,9 @@ def oracle_render(O):
 def check_render(rt, O, dev, ref, counters_ref, cam, p, rows, what):
     out, st = dev.render(cam, p, rows, want_stats=True)
     assert st.as_dict() == counters_ref, (what, "the device's paths took other turns than the oracle's")
-    assert same(out, ref), (what, "counting instance")
+    assert same_bits(out, ref), (what, "counting instance")
     assert np.array_equal(rt.write_color(out, max(p.spp, 1)), O.write_color(ref, max(p.spp, 1))), what
-    assert same(dev.render(cam, p, rows), ref), (what, "timed instance")
+    assert same_bits(dev.render(cam, p, rows), ref), (what, "timed instance")
     return st
 
 
@@ -139,11 +125,11 @@ def test_chunks_ring_and_frames(rt, O, scenes, oracle_render, name):
     ref, counters_ref = oracle_render(name, scene, q, strip)
     check_render(rt, O, dev, ref, counters_ref, cam, q, strip, (name, "two frames"))
     one = dev.render(cam, with_params(p, spp_chunk=1), strip[strip < S.H])
-    assert same(one, ref[strip < S.H]), "frame 0 of the strip is the frame rendered alone"
+    assert same_bits(one, ref[strip < S.H]), "frame 0 of the strip is the frame rendered alone"
 
 
 def radiance_same(a, ref):
-    return same(np.asarray(a), np.asarray(ref))
+    return same_bits(np.asarray(a), np.asarray(ref))
 
 
 @pytest.mark.parametrize("name", SPREAD + ["lambertian-image-rect"])

@@ -48,13 +48,10 @@ import numpy as np
 import pytest
 
 import shade_scenes as S
+from compare import bits
 from raytracer_2022_amd import _ffi as F
 
 IDS = [c.name for c in S.CASES]
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
 def render_with_census(O, scene, n_threads=4):

@@ -13,22 +13,16 @@ from raytracer_2022_amd import _ffi as F
 
 import specular_ref as SP
 import trace_scenes as TS
-from test_features import assert_same_bits, oracle_features
-from test_features_pixels import all_rows, shuffled_ids_with_repeats
-from test_surfaces import boundary_contents, same_stats
+from compare import assert_same_bits
+from features_ref import all_rows, oracle_features, shuffled_ids_with_repeats
+from gpu_first import torch_first  # noqa: F401
+from specular_ref import check_specular_counters
+from surface_ref import same_stats
 
 pytestmark = pytest.mark.gpu
 
 W0, H0, SPP0 = 32, 24, 2
 UNFOLLOWED = ["cornell_box", "cornell_smoke", "earth", "simple_light", "two_perlin_spheres", "two_spheres"]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def torch_first():
-    """Bring torch's HIP context up before the library's first call, as the other GPU test modules do."""
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU: the HIP path has no fallback"
-    torch.zeros(1, device="cuda")
 
 
 @pytest.fixture(scope="module")
@@ -43,25 +37,6 @@ def hall(rt, O):
     dev.close()
 
 
-def check_counters(st, st_ref, info, n_samples, d=None, surfaces=False):
-    """rt_stats of a flagged counter call against the restatement's: paths, the device's ray count, the words, and the traversal
-    counters — summed over all segments; with RT_FLAG_SURFACES the copy still tests its media's boundaries, so those kinds bound."""
-    assert st.paths == n_samples and st.rays == info.segments and st.rng_draws == info.words, (st.as_dict(), info.segments, info.words)
-    got, ref = list(st.prim_tests), list(st_ref.prim_tests)
-    if not surfaces:
-        assert got == ref and st.node_visits == st_ref.node_visits
-    else:
-        kinds, nodes_below = boundary_contents(d)
-        assert got[F.RT_KIND_MEDIUM] == 0
-        for k in range(len(got)):
-            assert got[k] <= ref[k]
-            if k != F.RT_KIND_MEDIUM and k not in kinds:
-                assert got[k] == ref[k], (k, got[k], ref[k])
-        assert st.node_visits <= st_ref.node_visits and (nodes_below or st.node_visits == st_ref.node_visits)
-    assert st.light_pdf_tests == 0 and st.passes == 0 and st.pool_slots == 0 and st.partial_bytes == 0 and st.spp_chunk == 0
-    assert st.trace_ms == 0 and st.shade_ms == 0 and st.ms > 0
-
-
 def check_against_restatement(rt, O, d, cam, p, rows, what, surfaces=False, dev=None):
     """The row form with counters and on the plain instance against the restatement -> (records, Info, the device scene)."""
     dev = dev or rt.DeviceScene(d)
@@ -69,7 +44,7 @@ def check_against_restatement(rt, O, d, cam, p, rows, what, surfaces=False, dev=
     got, st = dev.features(cam, p, rows, want_stats=True, surfaces=surfaces, specular=True)
     assert got.shape == (len(rows), p.width) and got.dtype == F.FEATURE_DTYPE
     assert_same_bits(got.reshape(-1), ref, what)
-    check_counters(st, st_ref, info, len(rows) * p.width * p.spp, d, surfaces)
+    check_specular_counters(st, st_ref, info, len(rows) * p.width * p.spp, d, surfaces)
     plain = dev.features(cam, p, rows, surfaces=surfaces, specular=True)
     assert_same_bits(plain.reshape(-1), ref, (what, "plain instance"))
     return got, info, dev
@@ -85,7 +60,7 @@ def test_mirror_hall_rows(rt, O, hall):
     order = (rows[:, None].astype(np.int64) * W + np.arange(W)).reshape(-1)
     got, st = dev.features(cam, p2, rows, want_stats=True, specular=True)
     assert_same_bits(got.reshape(-1), ref[order], "counter instance")
-    check_counters(st, st_ref, info, 2 * W * H * p2.spp)
+    check_specular_counters(st, st_ref, info, 2 * W * H * p2.spp)
     assert st.rays > st.paths
     plain, st0 = dev.features(cam, p2, rows, specular=True), F.rt_stats()
     assert_same_bits(plain.reshape(-1), ref[order], "plain instance")
@@ -118,7 +93,7 @@ def test_mirror_hall_pixel_lists_and_device_forms(rt, O, hall):
     ref200, st200, info200 = SP.oracle_specular_ids(O, d, cam, p2, some)
     assert_same_bits(ref200, ref[some], "the id form of the restatement")
     got200, stg = dev.features_pixels(cam, p2, some, want_stats=True, specular=True)
-    check_counters(stg, st200, info200, 200 * p2.spp)
+    check_specular_counters(stg, st200, info200, 200 * p2.spp)
     g = np.random.default_rng(9)
     for n in (1, 63, 64, 65):
         lst = g.integers(0, n_ids, n).astype(np.uint64)
@@ -151,7 +126,7 @@ def test_mirror_hall_pixel_lists_and_device_forms(rt, O, hall):
     std = F.rt_stats()
     dev.features_device(cam, p2, d_rows.data_ptr(), 2 * H, d_out.data_ptr(), stream.cuda_stream, stats=std, specular=True)
     assert_same_bits(d_out.cpu().numpy()[: n_ids * 8].view(F.FEATURE_DTYPE), ref[order], "rt_features_device with stats")
-    check_counters(std, st_ref, info, n_ids * p2.spp)
+    check_specular_counters(std, st_ref, info, n_ids * p2.spp)
     d_ids = torch.from_numpy(ids.view(np.int64)).cuda()
     d_pix = torch.full((ids.size * 8,), float("nan"), dtype=torch.float64, device="cuda")
     torch.cuda.synchronize()
@@ -219,7 +194,7 @@ def test_every_kernel_shape(rt, O, need):
     ref, st_ref, info_i = SP.oracle_specular_ids(O, d, cam, p, ids)
     out, st = dev.features_pixels(cam, p, ids, want_stats=True, specular=True)
     assert_same_bits(out, ref, "pixel list")
-    check_counters(st, st_ref, info_i, 300 * p.spp)
+    check_specular_counters(st, st_ref, info_i, 300 * p.spp)
     assert_same_bits(dev.features_pixels(cam, p, ids, specular=True), ref, "pixel list, plain instance")
     dev.close()
 
@@ -422,7 +397,7 @@ def test_one_pixel_wide_images(rt, O, hall, W, H):
     want, st_w, info_w = SP.oracle_specular_features(O, d, cam, p, rows)
     got, st = dev.features(cam, p, rows, want_stats=True, specular=True)
     assert_same_bits(got.reshape(-1), want, (W, H))
-    check_counters(st, st_w, info_w, W * H * 3)
+    check_specular_counters(st, st_w, info_w, W * H * 3)
     assert_same_bits(dev.features_pixels(cam, p, np.arange(W * H, dtype=np.uint64), specular=True), want, "pixel list")
     assert np.isnan(want.view(np.float64)).any() or (want["hits"] == 0).any()
 

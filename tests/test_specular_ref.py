@@ -11,7 +11,8 @@ import pytest
 from raytracer_2022_amd import _ffi as F
 
 import specular_ref as SP
-from test_features import assert_same_bits, oracle_features
+from compare import assert_same_bits
+from features_ref import oracle_features
 
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "rt2022.h")
 UNFOLLOWED = ["cornell_box", "cornell_smoke", "earth", "simple_light", "two_perlin_spheres", "two_spheres"]

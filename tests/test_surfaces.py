@@ -11,22 +11,16 @@ from raytracer_2022_amd import _ffi as F
 
 import surface_ref as S
 import trace_scenes as TS
-from query_scenes import composite_boundary_scene
-from test_features import assert_same_bits, every_kind_scene
-from test_features_pixels import all_rows, oracle_ids, shuffled_ids_with_repeats
+from compare import assert_same_bits
+from features_ref import all_rows, oracle_ids, shuffled_ids_with_repeats
+from gpu_first import torch_first  # noqa: F401
+from query_scenes import composite_boundary_scene, every_material_scene
+from surface_ref import check_surface_counters, same_stats
 
 pytestmark = pytest.mark.gpu
 
 W0, H0, SPP0 = 48, 32, 3
 MEDIA_FREE = ["cornell_box", "earth", "random_scene", "simple_light", "two_perlin_spheres", "two_spheres", "wwscene"]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def torch_first():
-    """Bring torch's HIP context up before the library's first call, as the other GPU test modules do."""
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU: the HIP path has no fallback"
-    torch.zeros(1, device="cuda")
 
 
 # ---- scenes ---------------------------------------------------------------------------------------------------------------
@@ -73,7 +67,7 @@ def case(rt, which):
         cam, bg = s.default_view(W0 / H0)
         return s, s.desc, cam, bg
     if which in ("every kind", "lens and shutter"):
-        b, d, _ = every_kind_scene(rt)
+        b, d, _ = every_material_scene(rt)
         aperture = 0.4 if which == "lens and shutter" else 0.0     # (time0 < time1: the shutter's word is drawn either way)
         return b, d, rt.camera_new((0, 1.8, 10), (0, 1.6, 0), (0, 1, 0), 40.0, W0 / H0, aperture, 10.0, 0.0, 1.0), (0.25, 0.5, 0.75)
     if which == "bvh boundary":
@@ -83,45 +77,6 @@ def case(rt, which):
 
 
 CASES = ["cornell_smoke", "final_scene", "every kind", "under movers", "bvh boundary", "list boundary", "medium root", "lens and shutter"]
-
-
-def boundary_contents(d):
-    """(the kinds reachable from any medium's boundary, whether a BVH node is among them)."""
-    kinds, todo, seen = set(), [d.media[i].boundary for i in range(d.n_media)], set()
-    while todo:
-        r = int(todo.pop()) & ~F.RT_REF_FLIP & 0xFFFFFFFF
-        if r in seen:
-            continue
-        seen.add(r)
-        k, i = F.ref_kind(r), F.ref_index(r)
-        kinds.add(k)
-        if k == F.RT_KIND_NODE:
-            todo += [d.nodes[i].left, d.nodes[i].right]
-        elif k == F.RT_KIND_LIST:
-            todo += [d.list_items[d.lists[i].first + j] for j in range(d.lists[i].count)]
-        elif k in (F.RT_KIND_TRANSLATE, F.RT_KIND_ROTATE_Y, F.RT_KIND_ZOOM):
-            todo.append(d.xforms[i].child)
-        elif k == F.RT_KIND_MEDIUM:
-            todo.append(d.media[i].boundary)
-    return kinds, F.RT_KIND_NODE in kinds
-
-
-def check_counters(st, st_copy, words, n_samples, d):
-    """The counters of a flagged call against the copy's: what the definition does, and no more than the copy does."""
-    assert st.paths == st.rays == n_samples
-    assert st.rng_draws == words                            # the cameras' words only
-    got, ref = list(st.prim_tests), list(st_copy.prim_tests)
-    assert got[F.RT_KIND_MEDIUM] == 0
-    kinds, nodes_below = boundary_contents(d)
-    for k in range(len(got)):
-        assert got[k] <= ref[k], (F.KIND_NAMES[k] if k < len(F.KIND_NAMES) else k, got[k], ref[k])
-        if k != F.RT_KIND_MEDIUM and k not in kinds:
-            assert got[k] == ref[k], (F.KIND_NAMES[k] if k < len(F.KIND_NAMES) else k, got[k], ref[k])
-    assert st.node_visits <= st_copy.node_visits
-    if not nodes_below:
-        assert st.node_visits == st_copy.node_visits
-    assert st.light_pdf_tests == 0 and st.passes == 0 and st.pool_slots == 0 and st.partial_bytes == 0 and st.spp_chunk == 0
-    assert st.trace_ms == 0 and st.shade_ms == 0 and st.ms > 0
 
 
 # ---- 1. against the oracle on the looked-through copy -----------------------------------------------------------------------
@@ -135,7 +90,7 @@ def test_flagged_rows_match_the_oracle_on_the_copy(rt, O, which):
     got, st = dev.features(cam, p, rows, want_stats=True, surfaces=True)             # the counter instance
     assert got.shape == (H0, W0) and got.dtype == F.FEATURE_DTYPE
     assert_same_bits(got.reshape(-1), ref, which)
-    check_counters(st, st_copy, words, W0 * H0 * SPP0, d)
+    check_surface_counters(st, st_copy, words, W0 * H0 * SPP0, d)
     assert_same_bits(dev.features(cam, p, rows, surfaces=True).reshape(-1), ref, "plain instance")
     assert d.n_media > 0 and not any(k[0] == F.RT_MAT_ISOTROPIC for k in seen.kinds)
     plain = dev.features(cam, p, rows)
@@ -166,7 +121,7 @@ def test_flagged_kernel_shapes_match_the_oracle(rt, O, shape):
     ref, st_copy, seen, words = S.oracle_surface_features(O, d, cam, p, rows)
     got, st = dev.features(cam, p, rows, want_stats=True, surfaces=True)
     assert_same_bits(got.reshape(-1), ref, shape)
-    check_counters(st, st_copy, words, len(rows) * p.width * p.spp, d)
+    check_surface_counters(st, st_copy, words, len(rows) * p.width * p.spp, d)
     assert_same_bits(dev.features(cam, p, rows, surfaces=True).reshape(-1), ref, "plain instance")
     need = dev.info()["stack_need"]
     assert {"whole": need <= TS.STACK_TINY, "mid": TS.STACK_SMALL < need <= TS.STACK_MID, "large": need > TS.STACK_MID}[shape]
@@ -174,13 +129,6 @@ def test_flagged_kernel_shapes_match_the_oracle(rt, O, shape):
 
 
 # ---- 2. nothing changes without media -----------------------------------------------------------------------------------------
-def same_stats(a, b):
-    da, db = a.as_dict(), b.as_dict()
-    for k in ("ms", "trace_ms", "shade_ms"):
-        da.pop(k, None), db.pop(k, None)
-    return da == db
-
-
 def flag_changes_nothing(dev, cam, p, rows, what):
     plain, st0 = dev.features(cam, p, rows, want_stats=True)
     got, st1 = dev.features(cam, p, rows, want_stats=True, surfaces=True)
@@ -239,7 +187,7 @@ def test_flagged_pixel_lists_entry_by_entry(rt, O):
         ref, st_copy, seen = oracle_ids(O, s.desc, cam, p, ids[:300])
     assert_same_bits(got[:300], ref, "the oracle on the copy")
     got300, st300 = dev.features_pixels(cam, p, ids[:300], want_stats=True, surfaces=True)
-    check_counters(st300, st_copy, S.camera_words(seen), 300 * SPP0, s.desc)
+    check_surface_counters(st300, st_copy, S.camera_words(seen), 300 * SPP0, s.desc)
     g = np.random.default_rng(9)
     for n in (1, 63, 64, 65):
         some = g.integers(0, 2 * W * H, n).astype(np.uint64)

@@ -15,7 +15,9 @@ import surface_ref as S
 import temporal_cases as T
 import temporal_far_ref as FR
 import temporal_ref as R
-from test_features import oracle_features
+from compare import assert_same_bits
+from features_ref import oracle_features
+from temporal_far_cases import far_cameras, more_misses, turned
 
 f64 = np.float64
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "rt2022.h")
@@ -116,30 +118,6 @@ def loop_restate(sums, feat, cam, p, prev, prev_cam):
     return out, state
 
 
-def turned(rt, W, H, angle, about="v"):
-    """T.camera(W, H) turned by `angle` about its own v axis (a pan) or u axis (a tilt), the origin kept."""
-    if about == "v":
-        return T.camera(rt, W, H, lookat=(math.sin(angle), 0.0, -math.cos(angle)))
-    return T.camera(rt, W, H, lookat=(0.0, math.sin(angle), -math.cos(angle)))
-
-
-def far_cameras(rt, W, H):
-    """T.cameras' pairs, and pairs that turn: a translation alone never moves a point at infinity."""
-    base = T.camera(rt, W, H)
-    pairs = dict(T.cameras(rt, W, H))
-    pairs["panned"] = (base, turned(rt, W, H, 0.21))
-    pairs["tilted and moved"] = (R.shifted_camera(turned(rt, W, H, -0.17, "u"), (0.3, -0.2, 0.1)), base)
-    return pairs
-
-
-def more_misses(feat, seed, frac=0.35):
-    """A copy of the records with `frac` of the pixels turned into all-zero miss records."""
-    f = feat.copy()
-    H, W = f.shape
-    f.view(np.float64).reshape(H, W, 8)[np.random.default_rng(seed).random((H, W)) < frac] = 0.0
-    return f
-
-
 @pytest.mark.parametrize("W, H", [(7, 5), (1, 6)])
 def test_far_restatement_equals_the_per_pixel_loop(rt, W, H):
     """Hostile records with many misses, a poisoned history (NaN, +-inf, zero and negative depths), every camera pair, both flag
@@ -154,15 +132,15 @@ def test_far_restatement_equals_the_per_pixel_loop(rt, W, H):
                 p = rt.temporal_params(W, H, 4, far_misses=far, **kw)
                 out0, st0 = FR.restate(s0, f0, prev_cam, p)
                 ref0 = loop_restate(s0, f0, prev_cam, p, None, None)
-                R.assert_same_bits(out0, ref0[0], (name, kw, far, "first frame"))
-                R.assert_same_bits(st0, ref0[1], (name, kw, far, "first frame, state"))
+                assert_same_bits(out0, ref0[0], (name, kw, far, "first frame"))
+                assert_same_bits(st0, ref0[1], (name, kw, far, "first frame, state"))
                 hist = T.poisoned(st0, seed)
                 hist["depth"][np.random.default_rng(seed).random((H, W)) < 0.1] = -np.inf
                 for history in (st0, hist):
                     out1, st1, geo = FR.restate(s1, f1, cam, p, history, prev_cam, geometry=True)
                     ref1 = loop_restate(s1, f1, cam, p, history, prev_cam)
-                    R.assert_same_bits(out1, ref1[0], (name, kw, far))
-                    R.assert_same_bits(st1, ref1[1], (name, kw, far, "state"))
+                    assert_same_bits(out1, ref1[0], (name, kw, far))
+                    assert_same_bits(st1, ref1[1], (name, kw, far, "state"))
                     miss = ~(f1["hits"] > 0)
                     if far:
                         accepted_far += int(geo["accepted"][miss].sum())
@@ -183,13 +161,13 @@ def test_without_the_flag_it_is_temporal_ref(rt, W, H):
         for kw in ({}, {"tol_depth": math.inf}, {"tol_normal": math.inf, "demodulate": False}, {"n_max": 1.0, "w_min": 1.0}):
             p = rt.temporal_params(W, H, 4, **kw)
             a0, b0 = FR.restate(s0, f0, prev_cam, p), R.restate(s0, f0, prev_cam, p)
-            R.assert_same_bits(a0[0], b0[0]), R.assert_same_bits(a0[1], b0[1])
+            assert_same_bits(a0[0], b0[0]), assert_same_bits(a0[1], b0[1])
             rows = np.random.default_rng(seed).permutation(H).astype(np.uint32)
             for history in (b0[1], T.poisoned(b0[1], seed)):
                 for r in (None, rows):
                     a1 = FR.restate(s1, f1, cam, p, history, prev_cam, rows=r, geometry=True)
                     b1 = R.restate(s1, f1, cam, p, history, prev_cam, rows=r, geometry=True)
-                    R.assert_same_bits(a1[0], b1[0], (name, kw)), R.assert_same_bits(a1[1], b1[1], (name, kw, "state"))
+                    assert_same_bits(a1[0], b1[0], (name, kw)), assert_same_bits(a1[1], b1[1], (name, kw, "state"))
                     assert np.array_equal(a1[2]["accepted"], b1[2]["accepted"])
 
 
@@ -328,7 +306,7 @@ def test_an_uncovered_pixel_takes_only_uncovered_taps(rt):
     assert np.abs(geo["sw"][inside] - sky_weight[inside]).max() <= 1e-12
     # and the other way round: a covered pixel never reads an uncovered tap (depth > 0 is required), flag or no flag
     _, st2 = FR.restate(s0, f0, cam, p, st0, prev_cam)
-    R.assert_same_bits(st2[~sky], R.restate(s0, f0, cam, rt.temporal_params(W, H, 4, demodulate=False, w_min=0.01), st0, prev_cam)[1][~sky])
+    assert_same_bits(st2[~sky], R.restate(s0, f0, cam, rt.temporal_params(W, H, 4, demodulate=False, w_min=0.01), st0, prev_cam)[1][~sky])
 
 
 # ---- the oracle on the looked-through copy ------------------------------------------------------------------------------------
@@ -344,7 +322,7 @@ def test_copy_equals_the_plain_composition_without_media(rt, O, name):
     assert s.desc.n_media == 0
     ref, st, seen = oracle_features(O, s.desc, cam, p, rows)
     got, st2, seen2, words = S.oracle_surface_features(O, s.desc, cam, p, rows)
-    R.assert_same_bits(got, ref, name)
+    assert_same_bits(got, ref, name)
     assert st2.as_dict() == st.as_dict() and words == seen.draws and seen.medium_draws == 0
 
 
@@ -367,13 +345,13 @@ def test_copy_has_no_medium_record(rt, O, name):
     assert medium_like(plain).sum() > len(left)            # pixels whose every hit was a medium's (1, 0, 0)
     with S.media_looked_through(d):
         again, _, seen_left = oracle_features(O, d, cam, p, rows, pixels=[pixels[k] for k in left])
-    R.assert_same_bits(again, got[left])
+    assert_same_bits(again, got[left])
     assert all(k[0] in (F.RT_MAT_LAMBERTIAN, F.RT_MAT_METAL, F.RT_MAT_DIELECTRIC, F.RT_MAT_DIFFUSE_LIGHT) for k in seen_left.kinds)
     changed = np.any(got.view(np.uint64).reshape(len(got), 8) != plain.view(np.uint64).reshape(len(got), 8), axis=1)
     assert changed.sum() > 0 and not medium_like(got)[changed & medium_like(plain) & ~np.isin(np.arange(len(got)), left)].any()
     assert words == seen.draws - seen.medium_draws and words >= 2 * p.width * p.height * p.spp        # the two jitter words at least
     assert np.isfinite(got.view(np.float64)).all()
-    R.assert_same_bits(oracle_features(O, d, cam, p, rows)[0], plain, "the scene is what it was")
+    assert_same_bits(oracle_features(O, d, cam, p, rows)[0], plain, "the scene is what it was")
 
 
 # ---- what it is for -----------------------------------------------------------------------------------------------------------

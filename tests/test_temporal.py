@@ -13,8 +13,10 @@ from raytracer_2022_amd import _ffi as F
 import denoise_dual_ref as D
 import temporal_cases as T
 import temporal_ref as R
-from temporal_ref import assert_same_bits
-from test_denoise import LONG_HEIGHTS, LONG_W, long_row_lists
+from compare import assert_same_bits
+from denoise_ref import LONG_HEIGHTS, LONG_W, long_row_lists
+from gpu_first import torch_first  # noqa: F401
+from temporal_cases import Device
 
 pytestmark = pytest.mark.gpu
 
@@ -24,14 +26,6 @@ INF = math.inf
 SWITCHES = {"n_max 1": dict(n_max=1.0), "depth test off": dict(tol_depth=INF), "normal test off": dict(tol_normal=INF),
             "both tests off": dict(tol_depth=INF, tol_normal=INF), "no demodulation": dict(demodulate=False), "w_min 1": dict(w_min=1.0),
             "tight": dict(tol_depth=0.02, tol_normal=0.05, n_max=2.5, w_min=0.6, albedo_floor=0.3)}
-
-
-@pytest.fixture(scope="module", autouse=True)
-def torch_first():
-    """Bring torch's HIP context up before the library's first call, as the other GPU test modules do."""
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU: the HIP path has no fallback"
-    torch.zeros(1, device="cuda")
 
 
 def check(rt, s, f, cam, p, prev=None, prev_cam=None, rows=None, what=""):
@@ -107,34 +101,7 @@ def test_other_sample_counts(rt, spp):
     check(rt, s1, f1, cam, p, st0, prev_cam)
 
 
-# ---- the device form on torch buffers -------------------------------------------------------------------------------------
-class Device:
-    """A frame's sums and records, two states, an output and a workspace as torch buffers; call() is rt_temporal_device."""
-
-    def __init__(self, rt, s, f, p, prev=None, fill=0):
-        import torch
-        self.rt, self.p, self.torch = rt, p, torch
-        n = p.width * p.height
-        self.sums = torch.from_numpy(np.ascontiguousarray(s)).cuda()
-        self.feat = torch.from_numpy(np.ascontiguousarray(f).view(np.float64).reshape(-1)).cuda()
-        self.prev = torch.from_numpy(np.ascontiguousarray(prev).view(np.float64).reshape(-1)).cuda() if prev is not None else None
-        self.state = torch.full((n * 8,), 7.0, dtype=torch.float64, device="cuda")
-        self.out = torch.full((p.height, p.width, 3), 7.0, dtype=torch.float64, device="cuda")
-        self.ws = torch.full((rt.temporal_workspace_bytes(p),), fill, dtype=torch.uint8, device="cuda")
-        torch.cuda.synchronize()
-
-    def call(self, cam, prev_cam=None, out=None, rows=None, stream=None):
-        self.rt.temporal_device(self.sums.data_ptr(), self.feat.data_ptr(), cam, self.p, self.state.data_ptr(),
-                                (self.out if out is None else out).data_ptr(), self.ws.data_ptr(),
-                                d_prev_ptr=self.prev.data_ptr() if self.prev is not None else None, prev_cam=prev_cam,
-                                d_row_ids_ptr=rows.data_ptr() if rows is not None else None, stream_ptr=stream)
-
-    def results(self, out=None):
-        self.torch.cuda.synchronize()
-        state = self.state.cpu().numpy().view(F.TEMPORAL_PIXEL_DTYPE).reshape(self.p.height, self.p.width)
-        return (self.out if out is None else out).cpu().numpy(), state
-
-
+# ---- the device form on torch buffers (temporal_cases.Device) --------------------------------------------------------------
 def two_frames(rt, W, H, seed, rows=None):
     """A first frame's state (the restatement's) and a second frame in the order of `rows`, with the `moved` cameras."""
     cam, prev_cam = T.cameras(rt, W, H)["moved"]

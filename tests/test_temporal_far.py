@@ -12,22 +12,15 @@ import surface_ref as S
 import temporal_cases as T
 import temporal_far_ref as FR
 import temporal_ref as R
-from temporal_ref import assert_same_bits
-from test_surfaces_ref import far_cameras, more_misses
-from test_temporal import Device
+from compare import assert_same_bits
+from gpu_first import torch_first  # noqa: F401
+from temporal_cases import Device
+from temporal_far_cases import far_cameras, more_misses
 
 pytestmark = pytest.mark.gpu
 
 SIZES = [(7, 5), (64, 4), (65, 5), (1, 6)]                  # below one workgroup, exactly one, one column and one row past it, one pixel wide
 FLAGS = [dict(far_misses=True), dict(far_misses=True, demodulate=False)]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def torch_first():
-    """Bring torch's HIP context up before the library's first call, as the other GPU test modules do."""
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU: the HIP path has no fallback"
-    torch.zeros(1, device="cuda")
 
 
 def check(rt, s, f, cam, p, prev=None, prev_cam=None, rows=None, what=""):

@@ -11,6 +11,7 @@ from raytracer_2022_amd import _ffi as F
 
 import temporal_cases as T
 import temporal_ref as R
+from compare import assert_same_bits
 
 f64 = np.float64
 
@@ -93,13 +94,13 @@ def test_restatement_equals_the_per_pixel_loop(rt, W, H):
             p = rt.temporal_params(W, H, 4, **kw)
             out0, st0 = R.restate(s0, f0, prev_cam, p)
             ref0 = loop_restate(s0, f0, prev_cam, p, None, None)
-            R.assert_same_bits(out0, ref0[0], (name, kw, "first frame"))
-            R.assert_same_bits(st0, ref0[1], (name, kw, "first frame, state"))
+            assert_same_bits(out0, ref0[0], (name, kw, "first frame"))
+            assert_same_bits(st0, ref0[1], (name, kw, "first frame, state"))
             for history in (st0, T.poisoned(st0, seed)):
                 out1, st1, geo = R.restate(s1, f1, cam, p, history, prev_cam, geometry=True)
                 ref1 = loop_restate(s1, f1, cam, p, history, prev_cam)
-                R.assert_same_bits(out1, ref1[0], (name, kw))
-                R.assert_same_bits(st1, ref1[1], (name, kw, "state"))
+                assert_same_bits(out1, ref1[0], (name, kw))
+                assert_same_bits(st1, ref1[1], (name, kw, "state"))
                 accepted += int(geo["accepted"].sum())
                 if name in ("previous camera facing away", "every tap outside") or W == 1:
                     sane = st1["depth"] <= T.Z_MID + 2.0    # (a hostile depth of 1e30 has no parallax and lands anywhere)
@@ -116,8 +117,8 @@ def test_rows_are_a_permutation_of_the_image_order_result(rt):
     out, st = R.restate(s1, f1, cam, p, st0, prev_cam)
     rows = np.array([3, 0, 4, 1, 2], dtype=np.uint32)
     out_r, st_r = R.restate(s1[rows], f1[rows], cam, p, st0, prev_cam, rows=rows)
-    R.assert_same_bits(out_r, out[rows], "sums come back in the rows' order")
-    R.assert_same_bits(st_r, st, "the state stays in image order")
+    assert_same_bits(out_r, out[rows], "sums come back in the rows' order")
+    assert_same_bits(st_r, st, "the state stays in image order")
 
 
 # ---- analytic cases -------------------------------------------------------------------------------------------------------

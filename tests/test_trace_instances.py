@@ -12,26 +12,12 @@ import pytest
 
 import trace_scenes as T
 from raytracer_2022_amd import _ffi as F
-from test_features import check_view
-from test_query import assert_prims_consistent, assert_records_equal, counters, oracle_hits
+from compare import same_bits
+from features_ref import check_view
+from gpu_first import torch_first  # noqa: F401
+from query_ref import assert_prims_consistent, assert_records_equal, oracle_hits, query_counters
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module", autouse=True)
-def torch_first():
-    """Bring torch's HIP context up before the library's first call, as the other GPU test modules do."""
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU: the HIP path has no fallback"
-    torch.zeros(1, device="cuda")
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def same(a, ref):
-    return np.array_equal(np.isnan(a), np.isnan(ref)) and np.array_equal(bits(a), bits(ref))
 
 
 def assert_variant(dev, d, tuning=T.TUNING):
@@ -85,15 +71,15 @@ def test_instance_matches_the_oracle(rt, matrix_reference, case):
     assert want["stack_entries"] == (16 if table != "plain" else {"mid": 30, "large": 64}.get(shape, 22))
     assert want["nodes_in_lds"] == {"plain": 0, "partial": T.NODE_CACHE}.get(table, d.n_nodes)
     assert want["f32_slabs"] == (sphere_only or (table == "plain" and feat in (1, 3))) and want["spheres_in_lds"] == (table == "prims")
-    assert same(dev.render(cam, p, rows), ref), "timed instance"
+    assert same_bits(dev.render(cam, p, rows), ref, payloads=True), "timed instance"
     out, st = dev.render(cam, p, rows, want_stats=True)
     assert st.as_dict() == counters_ref, "counting instance: the device paths took different branches than the oracle's"
-    assert same(out, ref), "counting instance"
+    assert same_bits(out, ref, payloads=True), "counting instance"
     dev.set_tuning(base | T.PROBE)
-    assert same(dev.render(cam, p, rows), ref), "probe instance"
+    assert same_bits(dev.render(cam, p, rows), ref, payloads=True), "probe instance"
     assert dev.pass_timing()["passes"] > 0
     dev.set_tuning(base | T.LITERAL_STEP)
-    assert same(dev.render(cam, p, rows), ref), "literal node step"
+    assert same_bits(dev.render(cam, p, rows), ref, payloads=True), "literal node step"
 
 
 MEGA_CASES = [c for c in T.matrix_cases() if c[1] in ("small", "large")]
@@ -114,8 +100,8 @@ def test_megakernel_matches_the_oracle(rt, matrix_reference, case):
     assert (need > T.STACK_MID) == (case[1] == "large") and (need <= T.STACK_SMALL) == (case[1] == "small")
     out, st = dev.render(cam, p, rows, want_stats=True)
     assert st.as_dict() == counters_ref
-    assert same(out, ref)
-    assert same(dev.render(cam, p, rows), ref)
+    assert same_bits(out, ref, payloads=True)
+    assert same_bits(dev.render(cam, p, rows), ref, payloads=True)
 
 
 @pytest.mark.parametrize("shape", ["small", "mid", "large"])
@@ -132,7 +118,7 @@ def test_query_and_feature_kernels_on_deep_stacks(rt, O, matrix_reference, shape
     ref, st_ref = oracle_hits(O, d, rays)
     assert_records_equal(got, ref, shape)
     assert_prims_consistent(d, got)
-    assert counters(st) == counters(st_ref, ref)
+    assert query_counters(st) == query_counters(st_ref, ref)
     assert_records_equal(dev.intersect(rays), ref, shape + ", plain instance")
     assert len(set(F.ref_kind(int(r)) for r in got["prim"][got["hit"] == 1])) >= 5
     pf = F.rt_params.from_buffer_copy(p)
@@ -159,10 +145,10 @@ def test_movers_media_and_lights_beyond_the_lds_tables(rt, O, mid):
         else:
             want, need = assert_variant(dev, d, tuning)
             assert want["stack_entries"] == (30 if mid else 22 if tuning & T.NO_TABLE else 16), label
-        assert same(dev.render(cam, p, rows), ref), label
+        assert same_bits(dev.render(cam, p, rows), ref, payloads=True), label
         out, st = dev.render(cam, p, rows, want_stats=True)
         assert st.as_dict() == st_ref.as_dict(), label
-        assert same(out, ref), label
+        assert same_bits(out, ref, payloads=True), label
 
 
 # ---- 3. either side of every threshold of the choice ---------------------------------------------------------------------------
@@ -173,7 +159,7 @@ def check_threshold(rt, O, scene, table, **facts):
     assert want["table"] == table
     for k, v in facts.items():
         assert want[k] == v, (k, want)
-    assert same(dev.render(cam, p, rows), O.render_cpu(d, cam, p, rows, n_threads=8))
+    assert same_bits(dev.render(cam, p, rows), O.render_cpu(d, cam, p, rows, n_threads=8), payloads=True)
     return need
 
 

@@ -5,7 +5,7 @@
 
 GPU renders are the oracle's bit for bit and the filter is its numpy restatement's (tests/denoise_dual_ref.py), so every
 number below is the number a GPU run gives. For the three views of the end-to-end tests — two frames of 2 spp at seed 2022
-from the oracle, the features by the oracle composition of tests/test_features.py, the target a 512 spp render at seed 7 —
+from the oracle, the features by the oracle composition of tests/features_ref.py, the target a 512 spp render at seed 7 —
 the display-value MSE sqrt(clip(c, 0, 0.999)) of the dual filter over the grid
 
     sigma_color in {0.5, 1, 2, 4}  x  var_iter in {1, 2, 3}  x  var_floor in {1e-6, 1e-4, 1e-2},
@@ -28,8 +28,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import raytracer_2022_amd as rt  # noqa: E402
 from oracle import oracle_ffi as O  # noqa: E402
 import denoise_dual_ref as R  # noqa: E402
-from test_denoise import restate as restate_single  # noqa: E402
-from test_features import oracle_features  # noqa: E402
+from denoise_ref import restate as restate_single  # noqa: E402
+from features_ref import oracle_features  # noqa: E402
 
 SIGMA_COLOR, VAR_ITER, VAR_FLOOR = (0.5, 1.0, 2.0, 4.0), (1, 2, 3), (1e-6, 1e-4, 1e-2)
 THREADS = min(8, os.cpu_count() or 1)
