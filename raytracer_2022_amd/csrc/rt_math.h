@@ -13,7 +13,8 @@
 // The transcendental kernels restate the published fdlibm / FreeBSD msun
 // algorithms (k_sin.c, k_cos.c, e_rem_pio2.c medium path, e_acos.c, s_atan.c,
 // e_atan2.c, e_log.c) with their coefficient tables; accuracy < 1 ulp in the
-// ranges the path uses, checked against libm in tests/test_math.py. Those
+// ranges the path uses, checked against libm in tests/test_math.py and, edge by
+// edge against a multiprecision reference, in tests/test_math_ref.py. Those
 // files carry this notice, which is preserved here as it asks:
 //
 //   ====================================================
@@ -35,9 +36,11 @@
 #include <hip/hip_runtime.h>
 #define RT_HD __host__ __device__ __forceinline__
 #define RT_HD_NOINLINE __host__ __device__ inline
+#define RT_HD_OUTOFLINE __host__ __device__ __attribute__((noinline)) inline
 #else
 #define RT_HD inline
 #define RT_HD_NOINLINE inline
+#define RT_HD_OUTOFLINE inline
 #endif
 
 namespace rtm {
@@ -99,6 +102,49 @@ constexpr double PIO2_3 = 2.02226624871116645580e-21, PIO2_3T = 8.47842766036889
 constexpr double P1 = 0x1.921fb54442d18p+0, P2 = 0x1.1a62633145c07p-54,
                  P3 = -0x1.f1976b7ed8fbcp-110, P4 = 0x1.4cf98e804177dp-164;
 
+// rem_pio2 for 2^20*pi/2 <= |x| < 2^52: fused Cody-Waite over the four pieces, on ax = |x| (the sign goes back on
+// at the end). A function of its own and, on the device, never inlined: almost no argument of a render comes
+// here, and inlined into sin_ / cos_ its values met those of the kernel around it at that kernel's register peak
+// (10 VGPRs and no stack as a callee; the kernels' counts: profiles/math_edges_kernel_resources.txt).
+//
+// The quotient is rounded in double precision and near 2^52 its ulp is 1/2, so fn may be the wrong neighbour:
+// |ax - fn*pi/2| < 0.95 * pi/2, which still leaves |ax - fn*P1| < 2. That difference is a multiple of 2^-52 (fn is
+// an integer, P1 a multiple of 2^-52), hence a double: the first fma is exact, and so is the step of one P1 that
+// brings the remainder back inside +-pi/4 (q is the remainder to 2^-53: enough to pick the side; INVPIO2 lies above
+// 2/pi, so it is the step down that arguments take — the step up is a guard).
+//
+// Then ax - fn*(P1+P2+P3+P4) = r - (ph + pl) - (qh + ql) - fn*P4 as hi + lo. Each product is split exactly by an
+// fma; each of the three subtractions from hi keeps its rounding error in lo, so that when r - ph cancels (ax next
+// to a multiple of pi/2) what is left keeps all its bits. The error term (a - s) - b is exact because a is a
+// multiple of b's ulp each time: r of 2^-52 >= ulp(ph); r - ph of ulp(ph) >= 2 |pl|; and all of these of
+// 2^-106 = ulp(fn) * ulp(P2) > ulp(qh). What is dropped lies below 2^-160.
+struct Pio2 { double y0, y1; int n; };
+RT_HD_OUTOFLINE Pio2 rem_pio2_large(double x) {
+    double ax = fabs_(x);
+    double fn = floor_(ax * INVPIO2 + 0.5);
+    double r = __builtin_fma(-fn, P1, ax);
+    double q = __builtin_fma(-fn, P2, r);
+    double step = q > 0x1.921fb54442d18p-1 ? 1.0 : q < -0x1.921fb54442d18p-1 ? -1.0 : 0.0;
+    fn += step;
+    r = __builtin_fma(-step, P1, r);
+    double ph = fn * P2;
+    double hi = r - ph;
+    double lo = (r - hi) - ph;
+    double pl = __builtin_fma(fn, P2, -ph);
+    r = hi - pl;
+    lo += (hi - r) - pl;
+    double qh = fn * P3;
+    hi = r - qh;
+    lo += (r - hi) - qh;
+    lo = __builtin_fma(-fn, P4, lo - __builtin_fma(fn, P3, -qh));
+    Pio2 o;
+    o.y0 = hi + lo;
+    o.y1 = (hi - o.y0) + lo;
+    o.n = (int)(lo32(fn + 0x1.0p52) & 3u);                          // fn is an integer in [2^20, 2^52): its low bits
+    if (x < 0.0) { o.y0 = -o.y0; o.y1 = -o.y1; o.n = -o.n & 3; }
+    return o;
+}
+
 // x -> (n mod 4, y0 + y1) with x = n*pi/2 + y0 + y1, |y0| <= ~pi/4.
 RT_HD int rem_pio2(double x, double &y0, double &y1) {
     int32_t hx = hi32(x);
@@ -132,14 +178,9 @@ RT_HD int rem_pio2(double x, double &y0, double &y1) {
     }
     if (ix >= 0x7ff00000) { y0 = x - x; y1 = 0.0; return 0; }       // inf / NaN -> NaN
     if (ix >= 0x43300000) { y0 = 0.0; y1 = 0.0; return 0; }         // |x| >= 2^52: no fraction left worth having
-    // 2^20*pi/2 <= |x| < 2^52: fused Cody-Waite over four pieces of pi/2.
-    double fn = (x * INVPIO2 + 0x1.8p52) - 0x1.8p52;
-    double r = __builtin_fma(-fn, P1, x);
-    double r2 = __builtin_fma(-fn, P2, r);
-    double r3 = __builtin_fma(-fn, P3, r2);
-    double r4 = __builtin_fma(-fn, P4, r3);
-    y0 = r4; y1 = 0.0;
-    return (int)((int64_t)fn & 3);
+    Pio2 o = rem_pio2_large(x);                                     // 2^20*pi/2 <= |x| < 2^52
+    y0 = o.y0; y1 = o.y1;
+    return o.n;
 }
 } // namespace detail
 
