@@ -472,7 +472,7 @@ typedef struct rt_radiance_params {   /* 48 B */
     double   t_min;                   /* 0.001 in main.rs:243, for every bounce */
     uint32_t max_depth;               /* ray_color's depth */
     uint32_t spp;                     /* samples per ray; 0 = zeros */
-    uint32_t flags;                   /* RT_FLAG_COUNTERS | RT_FLAG_KERNEL_TIMES only */
+    uint32_t flags;                   /* rt_radiance*: RT_FLAG_COUNTERS | RT_FLAG_KERNEL_TIMES only (rt_features_rays*: see there) */
     uint32_t _pad;
 } rt_radiance_params;
 
@@ -619,6 +619,52 @@ int rt_features_pixels(rt_scene *scene, const rt_camera *cam, const rt_params *p
                        rt_feature *out_features, rt_stats *stats);
 int rt_features_pixels_device(rt_scene *scene, const rt_camera *cam, const rt_params *params, const uint64_t *d_pixel_ids, uint64_t n_entries,
                               rt_feature *d_out_features, void *hip_stream, rt_stats *stats);
+
+/* The ray form: the feature records of rays the CALLER chooses instead of the camera's — rt_radiance's ray records and
+ * rt_radiance's params, so that one ray buffer and one rt_radiance_params serve rt_radiance_device and this call, as
+ * rt_params serves a render and rt_features. What the denoisers (rt_denoise*, rt_denoise_dual*) and rt_temporal* need beside
+ * the sums of other cameras (panoramas, orthographic, stereo), light probes, baking, integrators built on rt_intersect: they
+ * take no scene, only rt_feature records. New symbols only: the ABI version stays 3.
+ *
+ * For ray i and each sample s in [0, p->spp): rng = Rng(path_key(rays[i].rng_state, 0, 0, s)) — rt_radiance's keying; no
+ * camera word is drawn. r_0 = Ray(origin, direction, time), and rec = world.hit(r_0, p->t_min, f64::MAX) on the scene's root
+ * with that rng, so a ConstantMedium draws exactly the words the first segment of rt_radiance's sample s draws. The sample's
+ * features are rt_features' table above unchanged: the albedo rule by material kind, rec.normal, rec.t and 1 for a hit;
+ * p->background, zeros and 0 for a miss. RT_FLAG_SURFACES and RT_FLAG_SPECULAR mean what they mean for the other four
+ * feature calls with r_0 as here in place of the aimed ray (a followed Metal's ray has tm = 0.0, a Dielectric keeps r_k.tm).
+ * Record i is 0 + f_0 + ... + f_{spp-1} per field, added in sample order and not divided; the kernel makes these spp
+ * additions (on a scene without media and without RT_FLAG_SPECULAR all samples of a ray are equal, but spp * f is not the
+ * same bits as the sum). A ray's record does not depend on the batch or on its order. Ray contents are never validated: zero
+ * directions, zero, +-inf or NaN components, origins inside a medium's boundary or a dielectric, huge origins — NaN comes out
+ * where the oracle gives NaN. Every sum is the oracle's composition rto_path_key -> rto_hit -> rto_texture_value bit for bit.
+ * Two consequences make the call usable with the rest:
+ *   (a) with RT_FLAG_SPECULAR, albedo of ray i equals rt_radiance's out_rgb_sum of ray i bit for bit if the scene holds only
+ *       specular surfaces, lights and background, max_depth is at least 10 on the radiance side and no sample's chain reaches
+ *       the cap (RT_FEATURE_SPECULAR_BOUNCES vertices followed);
+ *   (b) with no flag, spp = 1 and a scene without media, the record of the ray that rt_features aims for a pixel's sample 0
+ *       (whatever its rng_state: nothing draws) equals that pixel's rt_features record at spp = 1.
+ *
+ * rt_radiance_params: used — background, t_min, spp, flags; IGNORED — max_depth. Flags: RT_FLAG_COUNTERS, RT_FLAG_SURFACES and
+ * RT_FLAG_SPECULAR in any combination; every other bit is RT_ERR_INVALID (RT_FLAG_KERNEL_TIMES, RT_FLAG_ASYNC and
+ * RT_FLAG_ANY_HIT included). rt_radiance* keeps refusing the two feature flags.
+ *
+ * Arguments: n_rays == 0 is RT_OK with nothing written and no device call; spp == 0 is RT_OK and writes zeros with no feature
+ * kernel. RT_ERR_INVALID with rt_last_error() set (prefixed by the function's name), before any device call: a null scene or
+ * params; a null ray or output buffer with n_rays > 0; n_rays > 2^40 (the entry index lives in the lane's two 32-bit words,
+ * like a pixel-list entry); a device ray buffer or device output that is not 16-byte aligned. There is no id list, so there
+ * is no checking kernel: with stats == NULL the device form is a pure enqueue with no host synchronisation; with stats it
+ * synchronises hip_stream like rt_features_device.
+ *
+ * rt_stats (may be NULL): paths = rays = n_rays * spp (RT_FLAG_SPECULAR: rays counts segments and is filled only with
+ * counters, as documented there); with RT_FLAG_COUNTERS node_visits, prim_tests[] and rng_draws are the oracle's sums — there
+ * are no camera words: rng_draws is the hits' words plus the followed vertices' scatter words; ms is the device time;
+ * everything else is 0. Scratch and independence are the feature calls' own: the same per-(scene, stream) scratch, neither
+ * engine, no pool; the call may run beside an RT_FLAG_ASYNC render or a query of the same scene, and rt_scene_destroy waits
+ * for it. No rt_scene_set form. One lane works one RAY through all its samples. */
+int rt_features_rays(rt_scene *scene, const rt_radiance_ray *rays, uint64_t n_rays, const rt_radiance_params *p,
+                     rt_feature *out_features, rt_stats *stats);
+int rt_features_rays_device(rt_scene *scene, const rt_radiance_ray *d_rays, uint64_t n_rays, const rt_radiance_params *p,
+                            rt_feature *d_out_features, void *hip_stream, rt_stats *stats);
 
 /* ---- edge-avoiding denoiser over the feature buffers ----------------------------------------------------
  * The consumer of rt_features*: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) on albedo-demodulated

@@ -282,6 +282,7 @@ ABI_SYMBOLS = [
     "rt_render_pixels", "rt_render_pixels_device", "rt_adaptive_workspace_bytes", "rt_adaptive_plan", "rt_adaptive_plan_device",
     "rt_adaptive_merge_device", "rt_adaptive_resolve_device", "rtb_adaptive_abi_sizes",
     "rt_features_pixels", "rt_features_pixels_device", "rt_adaptive_merge_features_device", "rt_adaptive_resolve_features_device",
+    "rt_features_rays", "rt_features_rays_device",
     "rtb_scene_build", "rtb_scene_free", "rtb_scene_desc", "rtb_scene_default_view", "rtb_camera_new",
     "rtb_shuffled_rows", "rtb_bvh_build", "rtb_fill_image", "rtb_write_ppm", "rtb_write_jpeg", "rtb_image_load",
     "rtb_last_error", "rtb_abi_sizes", "rtb_radiance_abi_sizes", "rtb_features_abi_sizes", "rtb_denoise_abi_sizes",
@@ -364,6 +365,8 @@ def lib():
     L.rtb_adaptive_abi_sizes.argtypes = [P(u32), u32]
     L.rt_features_pixels.argtypes = [vp, P(rt_camera), P(rt_params), vp, u64, vp, P(rt_stats)]
     L.rt_features_pixels_device.argtypes = [vp, P(rt_camera), P(rt_params), vp, u64, vp, vp, P(rt_stats)]
+    L.rt_features_rays.argtypes = [vp, vp, u64, P(rt_radiance_params), vp, P(rt_stats)]
+    L.rt_features_rays_device.argtypes = [vp, vp, u64, P(rt_radiance_params), vp, vp, P(rt_stats)]
     L.rt_adaptive_merge_features_device.argtypes = [vp, vp, vp, u64, vp, vp]
     L.rt_adaptive_resolve_features_device.argtypes = [vp, vp, u64, u32, vp, vp]
     L.rtb_scene_build.argtypes = [C.c_char_p, u64, C.c_char_p, i32, P(vp)]

@@ -266,12 +266,13 @@ struct FeatureArgs {
     double background[3];
     double t_min;
     uint64_t seed;
-    uint64_t n_pixels;                 // n_rows * width; pixel source: the entries of the list
+    uint64_t n_pixels;                 // n_rows * width; pixel source: the entries of the list; ray source: the rays
     union {                            // device (a union, and ids32 one above: the row instances' kernel arguments keep their layout)
         const uint32_t *row_ids;
         const uint64_t *pixel_ids;     // pixel source: n_pixels ids, frame * (width * height) + py * width + px, each < width * height * n_frames
+        const rt_radiance_ray *rays;   // ray source: n_pixels records, 16-byte aligned, never validated (cam, width, height, seed unused)
     };
-    rt_feature *out;                   // device, 16-byte aligned: n_pixels records in row_ids order (in list order)
+    rt_feature *out;                   // device, 16-byte aligned: n_pixels records in row_ids order (in list order, in the rays' order)
     unsigned long long *counter;       // pixels handed out so far (zeroed before launch)
     StatsDev *stats;                   // counter instances only
 };
@@ -282,8 +283,12 @@ hipError_t launch_features(const SceneDev &scene, const FeatureArgs &args, uint3
 // The pixel source (rt_features_pixels*): args.pixel_ids and args.ids32 in place of row_ids and n_rows.
 hipError_t launch_features_pixels(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, bool surfaces, bool specular,
                                   hipStream_t stream);
-// The RT_FLAG_SPECULAR instances (pt_features_specular.hip); `pixels`: the pixel source.
-hipError_t launch_features_specular(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, bool surfaces, bool pixels,
+// The ray source (rt_features_rays*): args.rays in place of row_ids; one record per ray, in the rays' order.
+hipError_t launch_features_rays(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, bool surfaces, bool specular,
+                                hipStream_t stream);
+// The RT_FLAG_SPECULAR instances (pt_features_specular.hip); `src`: the source of work items (kFeatRows, kFeatPixels or kFeatRays,
+// pt_features.hpp).
+hipError_t launch_features_specular(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, bool surfaces, int src,
                                     hipStream_t stream);
 
 // ---- edge-avoiding denoiser (pt_denoise.hip, rt_denoise*) ----------------------------

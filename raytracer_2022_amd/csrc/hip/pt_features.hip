@@ -19,6 +19,9 @@
 // (frame, pixel) ids, rt_render_pixels' (rt_features_pixels*). With a list the work item is ONE ENTRY, the lane's record is
 // out + entry, and f_camera decodes pixel_ids[entry] into frame, py and px where the row source reads row_ids[row]; all else
 // — traversal, f_albedo, the record's four pieces, the claim, the scheduler loop — is the same code.
+// A third source, the caller's rays (kFeatRays, rt_features_rays*): the work item is ONE RAY, the lane's record is out + entry, and
+// f_camera loads rays[entry] and keys the stream path_key(rng_state, 0, 0, sample) as rt_radiance does, drawing nothing; the world
+// ray is still not kept — f_world reads the 64-byte record again (L2-hot) where the other sources aim again.
 // RT_FLAG_SURFACES (SURF, instances of their own): a ConstantMedium answers None at once — its leaf is popped where the
 // medium arm would enter trav_medium, so no boundary is queried, no word drawn and nothing counted; an object that is also
 // some medium's boundary is still reached through its own reference. Instances and not a uniform switch in FeatureArgs: with
@@ -93,7 +96,7 @@ RT_DEV void f_done(const SceneDev &s, const FeatureArgs &a, FLane &L, unsigned l
 // mesh 169 / 333 / 291 Mrays/s, 1e5 spheres 143 / 299 / 278 (profiles/features_ab_occupancy.log).
 constexpr int feat_waves(int stack, int wg) { return wg > 256 ? 4 : stack > 32 ? 2 : 3; }
 // STACK: traversal stack entries; WG: threads per workgroup; CACHE: node records kept in LDS (0: none); STATS: counter instance;
-// SRC: kFeatRows or kFeatPixels; SURF: RT_FLAG_SURFACES (both defaulted: the earlier instances keep their names).
+// SRC: kFeatRows, kFeatPixels or kFeatRays; SURF: RT_FLAG_SURFACES (both defaulted: the earlier instances keep their names).
 template <int STACK, int WG, int CACHE, bool STATS, int SRC = kFeatRows, bool SURF = false>
 __global__ void __launch_bounds__(WG, feat_waves(STACK, WG)) pt_features(const SceneDev s, const FeatureArgs a) {
     __shared__ uint32_t stack_lds[STACK * WG];
@@ -176,14 +179,20 @@ hipError_t launch_features_src(const SceneDev &scene, const FeatureArgs &args, u
 
 hipError_t launch_features(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, bool surfaces, bool specular,
                            hipStream_t stream) {
-    if (specular) return launch_features_specular(scene, args, stack_need, counters, surfaces, false, stream);
+    if (specular) return launch_features_specular(scene, args, stack_need, counters, surfaces, kFeatRows, stream);
     return launch_features_src<kFeatRows>(scene, args, stack_need, counters, surfaces, stream);
 }
 
 hipError_t launch_features_pixels(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, bool surfaces, bool specular,
                                   hipStream_t stream) {
-    if (specular) return launch_features_specular(scene, args, stack_need, counters, surfaces, true, stream);
+    if (specular) return launch_features_specular(scene, args, stack_need, counters, surfaces, kFeatPixels, stream);
     return launch_features_src<kFeatPixels>(scene, args, stack_need, counters, surfaces, stream);
+}
+
+hipError_t launch_features_rays(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, bool surfaces, bool specular,
+                                hipStream_t stream) {
+    if (specular) return launch_features_specular(scene, args, stack_need, counters, surfaces, kFeatRays, stream);
+    return launch_features_src<kFeatRays>(scene, args, stack_need, counters, surfaces, stream);
 }
 
 } // namespace rt2022

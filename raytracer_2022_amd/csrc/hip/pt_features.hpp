@@ -1,5 +1,5 @@
 // pt_features.hpp — what the feature kernels share (pt_features.hip: first-hit records; pt_features_specular.hip: the
-// RT_FLAG_SPECULAR records): the lane's pixel, the two sources of work items, the camera ray of a sample, the first-hit
+// RT_FLAG_SPECULAR records): the lane's pixel, the three sources of work items, the camera ray of a sample, the first-hit
 // albedo rule and the add of one sample into the lane's own record. Each kernel writes its own done arm and scheduler loop.
 #ifndef RT2022_PT_FEATURES_HPP
 #define RT2022_PT_FEATURES_HPP
@@ -12,16 +12,24 @@ namespace {
 
 constexpr uint32_t kFHasPixel = 1u;    // lane flag: the lane carries a pixel (a sample of it is in flight)
 
-constexpr int kFeatRows = 0, kFeatPixels = 1;      // SRC: a row list, a list of (frame, pixel) ids
+constexpr int kFeatRows = 0, kFeatPixels = 1, kFeatRays = 2;      // SRC: a row list, a list of (frame, pixel) ids, the caller's rays
 
 struct FLane : TravLane {
-    uint32_t row, px;      // the pixel: entry of the row list, column (kFeatPixels: the low and the high word of the entry's index)
+    uint32_t row, px;      // the pixel: entry of the row list, column (kFeatPixels, kFeatRays: the low and the high word of the entry's index)
     uint32_t smp;          // the sample in flight
 };
 
 // The camera ray of (row, px, sample) and the RNG behind it, as wf_shade's fresh-path code aims it (main.rs:144-149).
+// kFeatRays: the caller's ray record in its place — four 16-byte loads, the stream keyed as rt_radiance keys sample smp of
+// the ray, and nothing drawn.
 template <int SRC>
 RT_DEV Ray f_camera(const FeatureArgs &a, uint32_t row, uint32_t px, uint32_t smp, Rng &rng) {
+    if constexpr (SRC == kFeatRays) {
+        const double2 *q = reinterpret_cast<const double2 *>(a.rays + ((uint64_t)row | ((uint64_t)px << 32)));
+        const double2 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
+        rng = Rng(rtm::path_key(rtm::d2u(q3.y), 0u, 0ull, smp));
+        return Ray(Vec3(q0.x, q0.y, q1.x), Vec3(q1.y, q2.x, q2.y), q3.x);
+    }
     uint32_t frame, py;
     if constexpr (SRC == kFeatPixels) {
         // id = frame * (width * height) + py * width + px. Two 32-bit divisions where every id of the view fits 32 bits (a
@@ -66,7 +74,7 @@ RT_DEV Vec3 f_albedo(const SceneDev &s, const HitRec &rec) {
 template <int SRC>
 RT_DEV void f_add(const FeatureArgs &a, const FLane &L, Vec3 alb, Vec3 n, double depth, double hits) {
     double2 *o;
-    if constexpr (SRC == kFeatPixels) o = reinterpret_cast<double2 *>(a.out + ((uint64_t)L.row | ((uint64_t)L.px << 32)));
+    if constexpr (SRC != kFeatRows) o = reinterpret_cast<double2 *>(a.out + ((uint64_t)L.row | ((uint64_t)L.px << 32)));
     else o = reinterpret_cast<double2 *>(a.out + ((uint64_t)L.row * a.width + L.px));
     double2 s0 = make_double2(0.0, 0.0), s1 = s0, s2 = s0, s3 = s0;
     if (L.smp > 0) { s0 = o[0]; s1 = o[1]; s2 = o[2]; s3 = o[3]; }
@@ -81,7 +89,7 @@ template <int SRC>
 RT_DEV bool f_take(const FeatureArgs &a, FLane &L, unsigned long long i) {
     const bool have = i < a.n_pixels;
     const unsigned long long ii = have ? i : 0ull;
-    if constexpr (SRC == kFeatPixels) {
+    if constexpr (SRC != kFeatRows) {
         L.row = (uint32_t)ii;
         L.px = (uint32_t)(ii >> 32);
     } else {

@@ -1,4 +1,4 @@
-// pt_features_specular.hip — RT_FLAG_SPECULAR on the four feature calls (include/rt2022.h): the records of the first
+// pt_features_specular.hip — RT_FLAG_SPECULAR on the six feature calls (include/rt2022.h): the records of the first
 // non-specular vertex of the sample's own path, behind glass and mirrors.
 //
 // The kernel is pt_features' shell (pt_features.hpp, pt_traverse.hpp: persistent wave64 grid, one lane per pixel, the lane owns
@@ -124,8 +124,9 @@ RT_DEV void s_done(const SceneDev &s, const FeatureArgs &a, SLane &L, unsigned l
 
 } // namespace
 
-// STACK: traversal stack entries (256-thread workgroups, no node prefix: see above); STATS: counter instance; SRC: kFeatRows or
-// kFeatPixels; SURF: RT_FLAG_SURFACES as well. Two waves per SIMD: the register budget that keeps the lane's state unspilled.
+// STACK: traversal stack entries (256-thread workgroups, no node prefix: see above); STATS: counter instance; SRC: kFeatRows,
+// kFeatPixels or kFeatRays (the caller's ray is the first segment, kept in L.wo / L.wd / L.wtm like every other); SURF:
+// RT_FLAG_SURFACES as well. Two waves per SIMD: the register budget that keeps the lane's state unspilled.
 template <int STACK, bool STATS, int SRC, bool SURF>
 __global__ void __launch_bounds__(kBlock, 2) pt_features_specular(const SceneDev s, const FeatureArgs a) {
     constexpr int WG = kBlock;
@@ -200,10 +201,14 @@ hipError_t launch_specular_src(const SceneDev &scene, const FeatureArgs &args, u
 
 } // namespace
 
-hipError_t launch_features_specular(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, bool surfaces, bool pixels,
+hipError_t launch_features_specular(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, bool surfaces, int src,
                                     hipStream_t stream) {
-    return pixels ? launch_specular_src<kFeatPixels>(scene, args, stack_need, counters, surfaces, stream)
-                  : launch_specular_src<kFeatRows>(scene, args, stack_need, counters, surfaces, stream);
+    switch (src) {
+        case kFeatRows: return launch_specular_src<kFeatRows>(scene, args, stack_need, counters, surfaces, stream);
+        case kFeatPixels: return launch_specular_src<kFeatPixels>(scene, args, stack_need, counters, surfaces, stream);
+        case kFeatRays: return launch_specular_src<kFeatRays>(scene, args, stack_need, counters, surfaces, stream);
+        default: return hipErrorInvalidValue;
+    }
 }
 
 } // namespace rt2022

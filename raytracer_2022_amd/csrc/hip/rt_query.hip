@@ -1,6 +1,6 @@
 // rt_query.hip — the closest-hit calls on a device scene: ray queries (rt_intersect*, and rt_intersect_ordered*: the same
 // launch between a gather and a scatter of pt_order.hip) and feature buffers (rt_features*,
-// rt_features_pixels*: first-hit records, and with RT_FLAG_SPECULAR the records behind glass and mirrors).
+// rt_features_pixels*, rt_features_rays*: first-hit records, and with RT_FLAG_SPECULAR the records behind glass and mirrors).
 #include "pt_order.hpp"
 #include "rt_internal.hpp"
 
@@ -100,8 +100,16 @@ void run_query_ordered(rt_scene *sc, const rt_query_ray *d_rays, const uint32_t 
     }
 }
 
-// The flag bits the four feature calls take.
+// The flag bits the six feature calls take, and the two checks they share.
 constexpr uint32_t kFeatureFlags = RT_FLAG_COUNTERS | RT_FLAG_SURFACES | RT_FLAG_SPECULAR;
+
+void require_feature_flags(uint32_t flags, const std::string &w) {
+    RT_REQUIRE(!(flags & ~kFeatureFlags), RT_ERR_INVALID, w + ": flag bits other than RT_FLAG_COUNTERS | RT_FLAG_SURFACES | RT_FLAG_SPECULAR");
+}
+
+void require_feature_out_aligned(const void *d_out, const std::string &w) {
+    RT_REQUIRE(!((uintptr_t)d_out & 15u), RT_ERR_INVALID, w + ": the output must be 16-byte aligned");
+}
 
 // paths and rays of a feature call of n samples. First-hit records: one camera path, one world.hit per sample; the kernel counts
 // neither. RT_FLAG_SPECULAR: a sample has a segment per vertex it follows — rays is what the counter instance counted (read_stats
@@ -118,14 +126,14 @@ void check_features(const rt_scene *scene, const rt_camera *cam, const rt_params
     const std::string w(who);
     RT_REQUIRE(p, RT_ERR_INVALID, w + ": null params");
     RT_REQUIRE(cam, RT_ERR_INVALID, w + ": null camera");
-    RT_REQUIRE(!(p->flags & ~kFeatureFlags), RT_ERR_INVALID, w + ": flag bits other than RT_FLAG_COUNTERS | RT_FLAG_SURFACES | RT_FLAG_SPECULAR");
+    require_feature_flags(p->flags, w);
     check_view(cam, p, w + ": ", " (width, height or n_frames is 0)");
     const bool need_rows = p->n_rows > 0 && p->spp > 0;
     RT_REQUIRE(p->n_rows == 0 || out, RT_ERR_INVALID, w + ": null output");
     RT_REQUIRE(!need_rows || p->row_ids, RT_ERR_INVALID, w + ": null row_ids");
     RT_REQUIRE((uint64_t)p->n_rows * p->width <= (1ull << 40), RT_ERR_INVALID, w + ": n_rows * width too large");
     if (device) {
-        RT_REQUIRE(p->n_rows == 0 || !((uintptr_t)out & 15u), RT_ERR_INVALID, w + ": the output must be 16-byte aligned");
+        if (p->n_rows > 0) require_feature_out_aligned(out, w);
         RT_REQUIRE(!need_rows || !((uintptr_t)p->row_ids & 3u), RT_ERR_INVALID, w + ": row_ids must be 4-byte aligned");
     } else if (need_rows) {
         for (uint32_t i = 0; i < p->n_rows; i++)
@@ -177,13 +185,13 @@ void check_features_pixels(const rt_scene *scene, const rt_camera *cam, const rt
     const std::string w(who);
     RT_REQUIRE(p, RT_ERR_INVALID, w + ": null params");
     RT_REQUIRE(cam, RT_ERR_INVALID, w + ": null camera");
-    RT_REQUIRE(!(p->flags & ~kFeatureFlags), RT_ERR_INVALID, w + ": flag bits other than RT_FLAG_COUNTERS | RT_FLAG_SURFACES | RT_FLAG_SPECULAR");
+    require_feature_flags(p->flags, w);
     check_view(cam, p, w + ": ", " (width, height or n_frames is 0)");
     RT_REQUIRE(n_entries == 0 || (ids && out), RT_ERR_INVALID, w + ": null id or output buffer");
     RT_REQUIRE(n_entries <= (1ull << 40), RT_ERR_INVALID, w + ": n_entries too large");
     if (device) {
         RT_REQUIRE(n_entries == 0 || !((uintptr_t)ids & 7u), RT_ERR_INVALID, w + ": the id buffer must be 8-byte aligned");
-        RT_REQUIRE(n_entries == 0 || !((uintptr_t)out & 15u), RT_ERR_INVALID, w + ": the output must be 16-byte aligned");
+        if (n_entries > 0) require_feature_out_aligned(out, w);
     } else {
         const uint64_t limit = (uint64_t)p->width * p->height * p->n_frames;      // (check_view: height * n_frames fits 32 bits)
         for (uint64_t i = 0; i < n_entries; i++)
@@ -227,6 +235,49 @@ void run_features_pixels(rt_scene *sc, const rt_camera *cam, const rt_params *p,
     a.pixel_ids = d_ids;
     run_counted(q, counters, stream, stats, [&] { return launch_features_pixels(sc->dev, a, sc->stack_need, counters, surfaces, specular, stream); });
     fill_feature_paths(stats, n_entries * p->spp, specular);
+}
+
+// The arguments of rt_features_rays* (host side only, the scene last, like check_features). `device`: rays and output are
+// rt_features_rays_device's. Ray contents are never looked at.
+void check_features_rays(const rt_scene *scene, const void *rays, uint64_t n_rays, const rt_radiance_params *p, const void *out, bool device,
+                         const char *who) {
+    const std::string w(who);
+    RT_REQUIRE(p, RT_ERR_INVALID, w + ": null params");
+    require_feature_flags(p->flags, w);
+    RT_REQUIRE(n_rays == 0 || (rays && out), RT_ERR_INVALID, w + ": null ray or output buffer");
+    RT_REQUIRE(n_rays <= (1ull << 40), RT_ERR_INVALID, w + ": n_rays too large");
+    if (device && n_rays > 0) {
+        RT_REQUIRE(!((uintptr_t)rays & 15u), RT_ERR_INVALID, w + ": the ray buffer must be 16-byte aligned");
+        require_feature_out_aligned(out, w);
+    }
+    RT_REQUIRE(scene, RT_ERR_INVALID, w + ": null scene");
+}
+
+// Enqueue one ray-list feature call on `stream`, like run_features (n_rays > 0). Nothing to check on the device: without stats
+// nothing here waits for the stream.
+void run_features_rays(rt_scene *sc, const rt_radiance_ray *d_rays, uint64_t n_rays, const rt_radiance_params *p, rt_feature *d_out,
+                       hipStream_t stream, rt_stats *stats) {
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (p->spp == 0) {                                     // no sample: zeros, no kernel
+        RT_HIP(hipMemsetAsync(d_out, 0, n_rays * sizeof(rt_feature), stream));
+        if (stats) RT_HIP(hipStreamSynchronize(stream));
+        return;
+    }
+    QueryScratch &q = scratch_for(sc, sc->fs, stream);
+    std::lock_guard<std::mutex> lock(q.mu);
+    const bool counters = stats && (p->flags & RT_FLAG_COUNTERS);
+    FeatureArgs a{};                                       // (cam, width, height and seed: unused by the ray source)
+    a.spp = p->spp;
+    std::memcpy(a.background, p->background, sizeof a.background);
+    a.t_min = p->t_min;
+    a.n_pixels = n_rays;
+    a.rays = d_rays;
+    a.out = d_out;
+    a.counter = q.counter;
+    a.stats = counters ? q.stats.p : nullptr;
+    const bool surfaces = (p->flags & RT_FLAG_SURFACES) != 0, specular = (p->flags & RT_FLAG_SPECULAR) != 0;
+    run_counted(q, counters, stream, stats, [&] { return launch_features_rays(sc->dev, a, sc->stack_need, counters, surfaces, specular, stream); });
+    fill_feature_paths(stats, n_rays * p->spp, specular);
 }
 
 } // namespace
@@ -395,6 +446,43 @@ int rt_features_pixels_device(rt_scene *scene, const rt_camera *cam, const rt_pa
         DeviceGuard guard(scene->device);
         run_features_pixels(scene, cam, params, d_pixel_ids, n_entries, d_out_features, (hipStream_t)hip_stream, stats, true,
                             "rt_features_pixels_device");
+        return RT_OK;
+    });
+}
+
+int rt_features_rays(rt_scene *scene, const rt_radiance_ray *rays, uint64_t n_rays, const rt_radiance_params *p, rt_feature *out_features,
+                     rt_stats *stats) {
+    return guarded([&]() -> int {
+        check_features_rays(scene, rays, n_rays, p, out_features, false, "rt_features_rays");
+        // (These early returns never read *scene, like rt_features_pixels': tests/test_features_rays_abi.py calls them with a
+        // handle that is no scene.)
+        if (n_rays == 0 || p->spp == 0) {                      // nothing, or zeros: nothing for the device to do
+            if (stats) std::memset(stats, 0, sizeof *stats);
+            if (n_rays) std::memset(out_features, 0, n_rays * sizeof(rt_feature));
+            return RT_OK;
+        }
+        DeviceGuard guard(scene->device);
+        DeviceBuf<rt_radiance_ray> d_rays(n_rays);             // (after the guard: freed with the scene's device current)
+        DeviceBuf<rt_feature> d_out(n_rays);
+        RT_HIP(hipMemcpy(d_rays, rays, n_rays * sizeof(rt_radiance_ray), hipMemcpyHostToDevice));
+        // Poison the output so an unwritten record cannot pass for a result.
+        RT_HIP(hipMemset(d_out, 0xFF, n_rays * sizeof(rt_feature)));
+        run_features_rays(scene, d_rays, n_rays, p, d_out, nullptr, stats);
+        RT_HIP(hipMemcpy(out_features, d_out, n_rays * sizeof(rt_feature), hipMemcpyDeviceToHost));
+        return RT_OK;
+    });
+}
+
+int rt_features_rays_device(rt_scene *scene, const rt_radiance_ray *d_rays, uint64_t n_rays, const rt_radiance_params *p,
+                            rt_feature *d_out_features, void *hip_stream, rt_stats *stats) {
+    return guarded([&]() -> int {
+        check_features_rays(scene, d_rays, n_rays, p, d_out_features, true, "rt_features_rays_device");
+        if (n_rays == 0) {
+            if (stats) std::memset(stats, 0, sizeof *stats);
+            return RT_OK;
+        }
+        DeviceGuard guard(scene->device);
+        run_features_rays(scene, d_rays, n_rays, p, d_out_features, (hipStream_t)hip_stream, stats);
         return RT_OK;
     });
 }

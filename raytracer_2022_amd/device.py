@@ -797,6 +797,30 @@ class DeviceScene:
         F.check(F.lib().rt_features_pixels_device(self._h, C.byref(cam), C.byref(p), C.c_void_p(d_ids_ptr), n_entries, C.c_void_p(d_out_ptr),
                                                   C.c_void_p(stream_ptr or 0), C.byref(stats) if stats is not None else None))
 
+    def features_rays(self, rays, spp=1, background=(0.0, 0.0, 0.0), t_min=0.001, want_stats=False, surfaces=False, specular=False):
+        """rt_features_rays with host buffers: the feature records of rays the caller chooses (RADIANCE_RAY_DTYPE, see
+        radiance_rays — the buffer radiance() takes) → (n,) array of FEATURE_DTYPE records: sums over the spp samples of ray i,
+        sample s drawing from path_key(rng_state, 0, 0, s) as radiance()'s does, not divided by spp [, rt_stats]. surfaces and
+        specular as for features(). What rt.denoise needs beside radiance()'s sums of a camera of the caller's own."""
+        r = np.ascontiguousarray(rays, dtype=F.RADIANCE_RAY_DTYPE)
+        flags = (F.RT_FLAG_COUNTERS if want_stats else 0) | (F.RT_FLAG_SURFACES if surfaces else 0) | (F.RT_FLAG_SPECULAR if specular else 0)
+        p = radiance_params(spp, background, t_min, 0, flags)
+        out = np.zeros(len(r), dtype=F.FEATURE_DTYPE)
+        st = F.rt_stats()
+        F.check(F.lib().rt_features_rays(self._h, r.ctypes.data if len(r) else None, len(r), C.byref(p), out.ctypes.data if len(r) else None,
+                                         C.byref(st)))
+        return (out, st) if want_stats else out
+
+    def features_rays_device(self, d_rays_ptr, n, d_out_ptr, params, stream_ptr=None, stats=None, surfaces=False, specular=False):
+        """rt_features_rays_device: device pointers in (n rt_radiance_ray records, room for n rt_feature records, both 16-byte
+        aligned), `params` an rt_radiance_params (radiance_params; its max_depth is ignored, its flags are replaced), enqueued on
+        `stream_ptr` (hipStream_t as int). stats=None is a pure enqueue with no host synchronisation; an rt_stats makes the call
+        synchronise the stream and fill it, counters included."""
+        p = F.rt_radiance_params.from_buffer_copy(params)
+        p.flags = (F.RT_FLAG_COUNTERS if stats is not None else 0) | (F.RT_FLAG_SURFACES if surfaces else 0) | (F.RT_FLAG_SPECULAR if specular else 0)
+        F.check(F.lib().rt_features_rays_device(self._h, C.c_void_p(d_rays_ptr), n, C.byref(p), C.c_void_p(d_out_ptr),
+                                                C.c_void_p(stream_ptr or 0), C.byref(stats) if stats is not None else None))
+
     def close(self):
         if self._h:
             F.lib().rt_scene_destroy(self._h)

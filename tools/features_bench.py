@@ -19,6 +19,13 @@ times the RT_FLAG_SURFACES call beside the plain one on the same view: three win
 does the same for the RT_FLAG_SPECULAR call ("specular_ms_windows", "specular_over_plain"), and adds what a counter call of each
 reports: "segments_per_sample" (rt_stats.rays / paths under the flag: the world.hit calls a sample makes) and the node visits of both,
 so the time ratio can be read against the extra traversal work the flag asks for.
+
+    python3 tools/features_bench.py --rays [--surfaces] [--specular] [--spp 4]
+
+times rt_features_rays_device on the camera rays of the view — one ray per pixel, as a batch of width * height rt_radiance_ray
+records at `spp` samples each — beside rt_features_device of the same view at the same spp, three windows of each, alternating
+("features_rays_ms_windows", "rays_over_rows"), and rt_intersect_device on the same rays once; with --surfaces / --specular the
+flagged forms of both calls as lines of their own.
 """
 import argparse
 import ctypes as C
@@ -93,6 +100,38 @@ def timed(torch, stream, call, steps, warmup):
     return e0.elapsed_time(e1) / steps
 
 
+def rays_lines(a, torch, label, name, param, dev, cam, bg, rows, stream):
+    """--rays: rt_features_rays_device on the view's camera rays (one per pixel, camera_rays at 1 spp with the pinhole direction;
+    a batch of width * height rays) beside rt_features_device of the same view at the same spp and rt_intersect_device on the same
+    rays. Three windows of each feature call, alternating; the reference of every line is rt_features_device of this build. The
+    ray call traces one ray per pixel spp times where the row call jitters each sample, so the work is close, not equal."""
+    q, _ = camera_rays(cam, rows, 1, a.seed)
+    n = len(q)
+    rays = rt.radiance_rays(q["origin"], q["direction"], time=q["time"], rng_state=q["rng_state"])
+    d_rows = torch.from_numpy(rows.view(np.int32)).cuda()
+    d_q = torch.from_numpy(q.view(np.uint8)).cuda()
+    d_rays = torch.from_numpy(rays.view(np.uint8)).cuda()
+    d_hits = torch.empty(n * 96, dtype=torch.uint8, device="cuda")
+    d_feat = torch.empty(n * 8, dtype=torch.float64, device="cuda")
+    sp = stream.cuda_stream
+    q_ms = timed(torch, stream, lambda: dev.intersect_device(d_q.data_ptr(), n, d_hits.data_ptr(), sp), a.steps, a.warmup)
+    for spp in [int(x) for x in a.spp.split(",")]:
+        p = rt.make_params(W, H, spp, 50, bg, seed=a.seed, spp_chunk=1)
+        rp = rt.radiance_params(spp, bg, p.t_min, 0)
+        for flag in [None] + (["surfaces"] if a.surfaces else []) + (["specular"] if a.specular else []):
+            kw = {flag: True} if flag else {}
+            rows_call = lambda: dev.features_device(cam, p, d_rows.data_ptr(), H, d_feat.data_ptr(), sp, **kw)
+            rays_call = lambda: dev.features_rays_device(d_rays.data_ptr(), n, d_feat.data_ptr(), rp, sp, **kw)
+            windows = [(timed(torch, stream, rows_call, a.steps, a.warmup), timed(torch, stream, rays_call, a.steps, a.warmup)) for _ in range(3)]
+            rows_ms, rays_ms = [w[0] for w in windows], [w[1] for w in windows]
+            print(json.dumps({"scene": label, "builder": name, "param": param, "spp": spp, "flag": flag or "none", "rays": n, "samples": n * spp,
+                              "features_ms_windows": [round(x, 3) for x in rows_ms], "features_rays_ms_windows": [round(x, 3) for x in rays_ms],
+                              "rays_over_rows": round(min(rays_ms) / min(rows_ms), 3), "rows_spread": round(max(rows_ms) / min(rows_ms) - 1.0, 3),
+                              "features_rays_msamples_per_s": round(n * spp / min(rays_ms) / 1e3, 1),
+                              "query_ms": round(q_ms, 3), "query_mrays_per_s": round(n / q_ms / 1e3, 1),
+                              "stack_need": dev.info()["stack_need"], "lib": os.path.basename(F.LIB_PATH)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scenes", default="final_scene,c2,c5,s1e5")
@@ -104,6 +143,7 @@ def main():
     ap.add_argument("--no-render", action="store_true")
     ap.add_argument("--surfaces", action="store_true", help="time the RT_FLAG_SURFACES call beside the plain one")
     ap.add_argument("--specular", action="store_true", help="time the RT_FLAG_SPECULAR call beside the plain one")
+    ap.add_argument("--rays", action="store_true", help="time rt_features_rays_device on the view's camera rays beside rt_features_device")
     a = ap.parse_args()
     import torch
     torch.zeros(1, device="cuda")
@@ -114,6 +154,9 @@ def main():
         cam, bg = s.default_view(W / H)
         rows = rt.shuffled_rows(H, a.seed)
         stream = torch.cuda.Stream()
+        if a.rays:
+            rays_lines(a, torch, label, name, param, dev, cam, bg, rows, stream)
+            continue
         d_rows = torch.from_numpy(rows.view(np.int32)).cuda()
         d_feat = torch.empty(H * W * 8, dtype=torch.float64, device="cuda")
         d_rgb = torch.empty(H * W * 3, dtype=torch.float64, device="cuda")
