@@ -276,20 +276,14 @@ struct FeatureArgs {
     unsigned long long *counter;       // pixels handed out so far (zeroed before launch)
     StatsDev *stats;                   // counter instances only
 };
+// The source of work items (the kernels' SRC): the rows of a row list (rt_features*: args.row_ids, args.n_rows), a list of (frame,
+// pixel) ids (rt_features_pixels*: args.pixel_ids and args.ids32 in their place), or the caller's rays (rt_features_rays*: args.rays;
+// one record per ray, in the rays' order).
+constexpr int kFeatRows = 0, kFeatPixels = 1, kFeatRays = 2;
 // `surfaces`: RT_FLAG_SURFACES, the instances that pop a medium leaf instead of entering it. `specular`: RT_FLAG_SPECULAR, the
 // instances of pt_features_specular.hip that follow a sample through glass and mirrors (with counters they count their rays).
-hipError_t launch_features(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, bool surfaces, bool specular,
-                           hipStream_t stream);
-// The pixel source (rt_features_pixels*): args.pixel_ids and args.ids32 in place of row_ids and n_rows.
-hipError_t launch_features_pixels(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, bool surfaces, bool specular,
-                                  hipStream_t stream);
-// The ray source (rt_features_rays*): args.rays in place of row_ids; one record per ray, in the rays' order.
-hipError_t launch_features_rays(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, bool surfaces, bool specular,
-                                hipStream_t stream);
-// The RT_FLAG_SPECULAR instances (pt_features_specular.hip); `src`: the source of work items (kFeatRows, kFeatPixels or kFeatRays,
-// pt_features.hpp).
-hipError_t launch_features_specular(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, bool surfaces, int src,
-                                    hipStream_t stream);
+hipError_t launch_features(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, int src, bool counters, bool surfaces,
+                           bool specular, hipStream_t stream);
 
 // ---- edge-avoiding denoiser (pt_denoise.hip, rt_denoise*) ----------------------------
 // Where the pieces of the caller's workspace lie (byte offsets, each a multiple of 16) — the one place that knows.

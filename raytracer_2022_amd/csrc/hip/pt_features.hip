@@ -29,6 +29,8 @@
 // are compiled from the code they had and keep every register (profiles/features_surfaces_kernel_resources.txt).
 // RT_FLAG_SPECULAR: a kernel of its own, pt_features_specular.hip, around the same pieces (pt_features.hpp); nothing of it is
 // compiled into the instances here.
+// One launcher serves the six calls (launch_features, at the end; the host side names the source as a number, pt_device.h): the
+// switch from `src` to SRC is written once here and once in pt_features_specular.hip, which takes the flagged calls.
 // One lane per pixel means a few-pixel x huge-spp job balances poorly; the intended use is a whole frame at modest spp.
 // All arithmetic is f64 through rt_math.h with -ffp-contract=off, so every sum is the CPU oracle's composition bit for bit.
 #include "pt_features.hpp"
@@ -177,22 +179,15 @@ hipError_t launch_features_src(const SceneDev &scene, const FeatureArgs &args, u
 
 } // namespace
 
-hipError_t launch_features(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, bool surfaces, bool specular,
-                           hipStream_t stream) {
-    if (specular) return launch_features_specular(scene, args, stack_need, counters, surfaces, kFeatRows, stream);
-    return launch_features_src<kFeatRows>(scene, args, stack_need, counters, surfaces, stream);
-}
-
-hipError_t launch_features_pixels(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, bool surfaces, bool specular,
-                                  hipStream_t stream) {
-    if (specular) return launch_features_specular(scene, args, stack_need, counters, surfaces, kFeatPixels, stream);
-    return launch_features_src<kFeatPixels>(scene, args, stack_need, counters, surfaces, stream);
-}
-
-hipError_t launch_features_rays(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, bool surfaces, bool specular,
-                                hipStream_t stream) {
-    if (specular) return launch_features_specular(scene, args, stack_need, counters, surfaces, kFeatRays, stream);
-    return launch_features_src<kFeatRays>(scene, args, stack_need, counters, surfaces, stream);
+hipError_t launch_features(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, int src, bool counters, bool surfaces,
+                           bool specular, hipStream_t stream) {
+    if (specular) return launch_features_specular(scene, args, stack_need, src, counters, surfaces, stream);
+    switch (src) {
+        case kFeatRows: return launch_features_src<kFeatRows>(scene, args, stack_need, counters, surfaces, stream);
+        case kFeatPixels: return launch_features_src<kFeatPixels>(scene, args, stack_need, counters, surfaces, stream);
+        case kFeatRays: return launch_features_src<kFeatRays>(scene, args, stack_need, counters, surfaces, stream);
+        default: return hipErrorInvalidValue;
+    }
 }
 
 } // namespace rt2022

@@ -12,8 +12,7 @@ namespace {
 
 constexpr uint32_t kFHasPixel = 1u;    // lane flag: the lane carries a pixel (a sample of it is in flight)
 
-constexpr int kFeatRows = 0, kFeatPixels = 1, kFeatRays = 2;      // SRC: a row list, a list of (frame, pixel) ids, the caller's rays
-
+// (SRC — kFeatRows, kFeatPixels, kFeatRays: pt_device.h)
 struct FLane : TravLane {
     uint32_t row, px;      // the pixel: entry of the row list, column (kFeatPixels, kFeatRays: the low and the high word of the entry's index)
     uint32_t smp;          // the sample in flight
@@ -101,6 +100,10 @@ RT_DEV bool f_take(const FeatureArgs &a, FLane &L, unsigned long long i) {
 }
 
 } // namespace
+
+// launch_features' RT_FLAG_SPECULAR half (pt_features_specular.hip).
+hipError_t launch_features_specular(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, int src, bool counters, bool surfaces,
+                                    hipStream_t stream);
 
 } // namespace rt2022
 #endif

@@ -201,7 +201,7 @@ hipError_t launch_specular_src(const SceneDev &scene, const FeatureArgs &args, u
 
 } // namespace
 
-hipError_t launch_features_specular(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, bool counters, bool surfaces, int src,
+hipError_t launch_features_specular(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, int src, bool counters, bool surfaces,
                                     hipStream_t stream) {
     switch (src) {
         case kFeatRows: return launch_specular_src<kFeatRows>(scene, args, stack_need, counters, surfaces, stream);

@@ -60,17 +60,33 @@ __global__ void __launch_bounds__(256) ids_bad_kernel(const Id *ids, uint64_t n,
     for (int d = 32; d > 0; d >>= 1) bad += (uint32_t)__shfl_xor((int)bad, d);
     if ((threadIdx.x & 63u) == 0 && bad) atomicAdd(out, bad);
 }
-// The range check of ids that came from the caller's HBM (the twin of the host-side loops over host ids): how many are out of
-// range is counted on the device and copied to a pinned word. Two halves, so that the check costs a call no synchronisation of
-// its own: begin() is enqueued with the call's other preparations, and end() looks at the answer behind the
-// synchronisation the call makes anyway before its first pass. (An id out of range cannot fault a kernel — it only mis-keys a
-// frame or a path — so nothing is lost by finding out a moment later.) Every begin() starts from zero: a call that fails at either
-// half leaves nothing the next call on the stream would trip over. Any nonzero count refuses the call.
+// The two kinds of id a call may list, told apart by the pointer's type: row ids, each < height * n_frames (check_view: that fits
+// 32 bits), and pixel ids, each < width * height * n_frames — the limit in a view, and what the call says of an id beyond it.
+inline uint64_t id_limit(const uint32_t *, uint32_t, uint32_t height, uint32_t n_frames) { return (uint64_t)height * n_frames; }
+inline uint64_t id_limit(const uint64_t *, uint32_t width, uint32_t height, uint32_t n_frames) { return (uint64_t)width * height * n_frames; }
+inline const char *id_message(const uint32_t *) { return ": row id out of range"; }
+inline const char *id_message(const uint64_t *) { return ": pixel id out of range (>= width * height * n_frames)"; }
+
+// The range check of ids in host memory, against the view of `p`.
 template <class Id>
+void check_host_ids(const Id *ids, uint64_t n, const rt_params *p, const std::string &who) {
+    const uint64_t limit = id_limit(ids, p->width, p->height, p->n_frames);
+    for (uint64_t i = 0; i < n; i++) RT_REQUIRE(ids[i] < limit, RT_ERR_INVALID, who + id_message(ids));
+}
+
+// The range check of ids that came from the caller's HBM (the twin of check_host_ids): how many are out of range is counted on
+// the device and copied to a pinned word. Two halves, so that the check costs a call no synchronisation of its own:
+// begin() is enqueued with the call's other preparations, and end() looks at the answer behind the synchronisation the call makes
+// anyway before its first pass. (An id out of range cannot fault a kernel — it only mis-keys a frame or a path — so nothing is
+// lost by finding out a moment later.) Every begin() starts from zero: a call that fails at either half leaves nothing the next
+// call on the stream would trip over. Any nonzero count refuses the call.
+// `job`: a RenderJob or a FeatureJob — check_ids, d_rows or d_pixel_ids (at most one), count, the view, and `who` for the message.
+// (Templates: only the files that check ids compile the counting kernel.)
 struct IdCheck {
     DeviceBuf<uint32_t> d_bad;        // device word: ids out of range in the call being checked (created on first use)
     PinnedBuf<uint32_t> h_bad;        // ... and the pinned word it is copied to
-    void begin(const Id *d_ids, uint64_t n, uint64_t limit, hipStream_t stream) {      // n > 0
+    template <class Id>
+    void count(const Id *d_ids, uint64_t n, uint64_t limit, hipStream_t stream) {      // n > 0
         if (!h_bad) {                                  // (keyed on the one created last: a failure half-way is made good by the next call)
             d_bad = DeviceBuf<uint32_t>(1);
             h_bad = PinnedBuf<uint32_t>(1);
@@ -81,8 +97,25 @@ struct IdCheck {
         RT_HIP(hipGetLastError());
         RT_HIP(hipMemcpyAsync(h_bad, d_bad, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     }
-    void end(const char *who, const char *message) const {      // (after a synchronisation of the stream)
-        RT_REQUIRE(*h_bad.p == 0, RT_ERR_INVALID, std::string(who) + message);
+    // Whether the job has ids to check; if so, the count of its bad ones is on its way.
+    template <class Job>
+    bool begin(const Job &job, hipStream_t stream) {
+        if (!job.check_ids || job.count == 0 || !(job.d_rows || job.d_pixel_ids)) return false;
+        if (job.d_rows) count(job.d_rows, job.count, id_limit(job.d_rows, job.width, job.height, job.n_frames), stream);
+        else count(job.d_pixel_ids, job.count, id_limit(job.d_pixel_ids, job.width, job.height, job.n_frames), stream);
+        return true;
+    }
+    template <class Job>
+    void end(const Job &job) const {                   // (begin() said true, and the stream has been synchronised since)
+        RT_REQUIRE(*h_bad.p == 0, RT_ERR_INVALID, std::string(job.who) + (job.d_rows ? id_message(job.d_rows) : id_message(job.d_pixel_ids)));
+    }
+    // The one synchronisation of `stream` a call makes before its first pass (`sync_anyway`; false: only if there is something
+    // to check), with the two halves around it.
+    template <class Job>
+    void sync_and_check(const Job &job, hipStream_t stream, bool sync_anyway) {
+        const bool check = begin(job, stream);
+        if (check || sync_anyway) RT_HIP(hipStreamSynchronize(stream));
+        if (check) end(job);
     }
 };
 
@@ -110,12 +143,11 @@ struct Workspace {
     Event ev0{hipEventDefault}, ev1{hipEventDefault};
     CallStats pending;                // of the call enqueued last, consumed by finish
     KernelTimes kt;                   // RT_FLAG_KERNEL_TIMES
-    IdCheck<uint32_t> rows;           // rt_render_device's row ids
+    IdCheck ids;                      // rt_render_device's row ids, rt_render_pixels_device's pixel ids
     // rt_radiance (host buffers): the device copies of the caller's rays and of the sums, grown as needed
     DeviceBuf<rt_radiance_ray> rad_rays;
     DeviceBuf<double> rad_out;
-    // rt_render_pixels*: the check of device ids, and rt_render_pixels' device copy of the caller's list (its sums go through rad_out)
-    IdCheck<uint64_t> pixels;
+    // rt_render_pixels' device copy of the caller's list (its sums go through rad_out)
     DeviceBuf<uint64_t> pix_ids;
     // RT_FLAG_ASYNC: the host thread that drives the passes of the call in flight on this (scene, stream), and what it ended with
     // (read by rt_render_wait after the join).
@@ -132,8 +164,7 @@ struct QueryScratch {
     DeviceBuf<unsigned long long> counter{1};
     DeviceBuf<StatsDev> stats{1};
     Event ev0{hipEventDefault}, ev1{hipEventDefault};
-    IdCheck<uint32_t> rows;           // rt_features_device's row ids
-    IdCheck<uint64_t> pixels;         // rt_features_pixels_device's ids
+    IdCheck ids;                      // rt_features_device's row ids, rt_features_pixels_device's pixel ids
 };
 
 } // namespace rt2022

@@ -1,6 +1,11 @@
 // rt_query.hip — the closest-hit calls on a device scene: ray queries (rt_intersect*, and rt_intersect_ordered*: the same
 // launch between a gather and a scatter of pt_order.hip) and feature buffers (rt_features*,
 // rt_features_pixels*, rt_features_rays*: first-hit records, and with RT_FLAG_SPECULAR the records behind glass and mirrors).
+// The six feature calls are one call with three sources of work items: one description of it (FeatureJob), one check of the
+// arguments (check_features), one enqueue (run_features) and one staged host form (features_staged), as rt_render.hip has one
+// RenderJob for its renders.
+#include <type_traits>
+
 #include "pt_order.hpp"
 #include "rt_internal.hpp"
 
@@ -100,184 +105,189 @@ void run_query_ordered(rt_scene *sc, const rt_query_ray *d_rays, const uint32_t 
     }
 }
 
-// The flag bits the six feature calls take, and the two checks they share.
-constexpr uint32_t kFeatureFlags = RT_FLAG_COUNTERS | RT_FLAG_SURFACES | RT_FLAG_SPECULAR;
+// ---- feature buffers: one job, one check, one enqueue, one staged host form for the six calls ----
 
-void require_feature_flags(uint32_t flags, const std::string &w) {
-    RT_REQUIRE(!(flags & ~kFeatureFlags), RT_ERR_INVALID, w + ": flag bits other than RT_FLAG_COUNTERS | RT_FLAG_SURFACES | RT_FLAG_SPECULAR");
+// One feature call: where its samples start — the rows of a view (kFeatRows), a list of (frame, pixel) ids of one (kFeatPixels) or
+// the caller's rays (kFeatRays): `src`, with at most one of the three device pointers, that source's, and `count` rows, ids or
+// rays — the view (which the ray source does not use: it stays zero), the sampling, and where the records and the stats go.
+// The row and the pixel source differ at spp == 0, where the call writes zeros and launches nothing. The row call, the older
+// one, then looks at nothing else: its row ids may be null or out of range. The pixel call took rt_render_pixels' rule that a
+// list of ids is checked whatever becomes of it: device ids are range-checked first, and a refused call has enqueued nothing
+// that writes the output. Nobody chose the difference; both are behaviour by now, and run_features keeps both.
+struct FeatureJob {
+    int src = kFeatRows;
+    const uint32_t *d_rows = nullptr;
+    const uint64_t *d_pixel_ids = nullptr;
+    const rt_radiance_ray *d_rays = nullptr;
+    uint64_t count = 0;
+    bool check_ids = false;           // the row or pixel ids came from the caller's HBM: range-check them (IdCheck)
+    const char *who = "";             // the entry point, for that check's message
+    rt_camera cam{};
+    uint32_t width = 0, height = 0, n_frames = 0;
+    uint64_t seed = 0;
+    uint32_t spp = 0, flags = 0;
+    double background[3] = {0.0, 0.0, 0.0}, t_min = 0.0;
+    rt_feature *d_out = nullptr;      // device: one record per pixel of the rows, per id or per ray
+    rt_stats *stats = nullptr;        // host: filled by run_features (null: not wanted)
+    uint64_t records() const { return src == kFeatRows ? count * width : count; }
+};
+
+// The job of a call on a view, rows or pixels (the caller adds the source's device pointer) ...
+FeatureJob view_job(int src, const rt_camera *cam, const rt_params *p, uint64_t count, rt_feature *d_out, rt_stats *stats, bool check_ids,
+                    const char *who) {
+    FeatureJob j;
+    j.src = src; j.count = count; j.check_ids = check_ids; j.who = who;
+    j.cam = *cam;
+    j.width = p->width; j.height = p->height; j.n_frames = p->n_frames; j.seed = p->seed;
+    j.spp = p->spp; j.flags = p->flags;
+    std::memcpy(j.background, p->background, sizeof j.background);
+    j.t_min = p->t_min;
+    j.d_out = d_out; j.stats = stats;
+    return j;
 }
 
-void require_feature_out_aligned(const void *d_out, const std::string &w) {
-    RT_REQUIRE(!((uintptr_t)d_out & 15u), RT_ERR_INVALID, w + ": the output must be 16-byte aligned");
+// ... and of a call on the caller's rays: no view, and nothing to check on the device.
+FeatureJob rays_job(const rt_radiance_ray *d_rays, uint64_t n_rays, const rt_radiance_params *p, rt_feature *d_out, rt_stats *stats, const char *who) {
+    FeatureJob j;
+    j.src = kFeatRays; j.d_rays = d_rays; j.count = n_rays; j.who = who;
+    j.spp = p->spp; j.flags = p->flags;
+    std::memcpy(j.background, p->background, sizeof j.background);
+    j.t_min = p->t_min;
+    j.d_out = d_out; j.stats = stats;
+    return j;
 }
 
-// paths and rays of a feature call of n samples. First-hit records: one camera path, one world.hit per sample; the kernel counts
-// neither. RT_FLAG_SPECULAR: a sample has a segment per vertex it follows — rays is what the counter instance counted (read_stats
-// put it there), 0 without counters.
-void fill_feature_paths(rt_stats *stats, uint64_t n_samples, bool specular) {
-    if (!stats) return;
-    stats->paths = n_samples;
-    if (!specular) stats->rays = n_samples;
-}
-
-// The arguments of rt_features* (host side only; the scene comes last so that a bad argument is reported as such whatever
-// the scene). `device`: rows and output are rt_features_device's — the rows are range-checked on the device later.
-void check_features(const rt_scene *scene, const rt_camera *cam, const rt_params *p, const void *out, bool device, const char *who) {
-    const std::string w(who);
-    RT_REQUIRE(p, RT_ERR_INVALID, w + ": null params");
-    RT_REQUIRE(cam, RT_ERR_INVALID, w + ": null camera");
-    require_feature_flags(p->flags, w);
-    check_view(cam, p, w + ": ", " (width, height or n_frames is 0)");
-    const bool need_rows = p->n_rows > 0 && p->spp > 0;
-    RT_REQUIRE(p->n_rows == 0 || out, RT_ERR_INVALID, w + ": null output");
-    RT_REQUIRE(!need_rows || p->row_ids, RT_ERR_INVALID, w + ": null row_ids");
-    RT_REQUIRE((uint64_t)p->n_rows * p->width <= (1ull << 40), RT_ERR_INVALID, w + ": n_rows * width too large");
-    if (device) {
-        if (p->n_rows > 0) require_feature_out_aligned(out, w);
-        RT_REQUIRE(!need_rows || !((uintptr_t)p->row_ids & 3u), RT_ERR_INVALID, w + ": row_ids must be 4-byte aligned");
-    } else if (need_rows) {
-        for (uint32_t i = 0; i < p->n_rows; i++)
-            RT_REQUIRE(p->row_ids[i] < (uint64_t)p->height * p->n_frames, RT_ERR_INVALID, w + ": row id out of range");
-    }
-    RT_REQUIRE(scene, RT_ERR_INVALID, w + ": null scene");
-}
-
-// Enqueue one feature call on `stream` (the scene's device is current, the arguments checked); with stats, wait for it and
-// fill them. `check_rows`: the row ids came from the caller's HBM — range-check them first (one synchronisation of the stream).
-void run_features(rt_scene *sc, const rt_camera *cam, const rt_params *p, const uint32_t *d_rows, rt_feature *d_out,
-                  hipStream_t stream, rt_stats *stats, bool check_rows, const char *who) {
-    if (stats) std::memset(stats, 0, sizeof *stats);
-    const uint64_t n_pixels = (uint64_t)p->n_rows * p->width;
-    if (n_pixels == 0) return;
-    if (p->spp == 0) {                                     // no sample: zeros, no kernel
-        RT_HIP(hipMemsetAsync(d_out, 0, n_pixels * sizeof(rt_feature), stream));
-        if (stats) RT_HIP(hipStreamSynchronize(stream));
-        return;
-    }
-    QueryScratch &q = scratch_for(sc, sc->fs, stream);
-    std::lock_guard<std::mutex> lock(q.mu);
-    if (check_rows) {
-        q.rows.begin(d_rows, p->n_rows, (uint64_t)p->height * p->n_frames, stream);
-        RT_HIP(hipStreamSynchronize(stream));
-        q.rows.end(who, ": row id out of range");
-    }
-    const bool counters = stats && (p->flags & RT_FLAG_COUNTERS);
+// FeatureArgs of `job` as the kernels take them: the one place that fills them.
+FeatureArgs feature_args(const FeatureJob &job, QueryScratch &q, bool counters) {
     FeatureArgs a{};
-    a.cam = *cam;
-    a.width = p->width; a.height = p->height; a.spp = p->spp; a.n_rows = p->n_rows;
-    std::memcpy(a.background, p->background, sizeof a.background);
-    a.t_min = p->t_min;
-    a.seed = p->seed;
-    a.n_pixels = n_pixels;
-    a.row_ids = d_rows;
-    a.out = d_out;
+    a.cam = job.cam;
+    a.width = job.width; a.height = job.height; a.spp = job.spp;
+    std::memcpy(a.background, job.background, sizeof a.background);
+    a.t_min = job.t_min;
+    a.seed = job.seed;
+    a.n_pixels = job.records();
+    switch (job.src) {                                     // (n_rows and ids32 share a word, the three pointers another)
+        case kFeatRows: a.n_rows = (uint32_t)job.count; a.row_ids = job.d_rows; break;
+        case kFeatPixels:
+            a.ids32 = id_limit(job.d_pixel_ids, job.width, job.height, job.n_frames) <= 0xFFFFFFFFull ? 1u : 0u;
+            a.pixel_ids = job.d_pixel_ids;
+            break;
+        default: a.rays = job.d_rays; break;
+    }
+    a.out = job.d_out;
     a.counter = q.counter;
     a.stats = counters ? q.stats.p : nullptr;
-    const bool surfaces = (p->flags & RT_FLAG_SURFACES) != 0, specular = (p->flags & RT_FLAG_SPECULAR) != 0;
-    run_counted(q, counters, stream, stats, [&] { return launch_features(sc->dev, a, sc->stack_need, counters, surfaces, specular, stream); });
-    fill_feature_paths(stats, n_pixels * p->spp, specular);
+    return a;
 }
 
-// The arguments of rt_features_pixels* (host side only, the scene last, like check_features). `device`: ids and output are
-// rt_features_pixels_device's — the ids are range-checked on the device later.
-void check_features_pixels(const rt_scene *scene, const rt_camera *cam, const rt_params *p, const uint64_t *ids, uint64_t n_entries,
-                           const void *out, bool device, const char *who) {
+// What the sources say where they share a rule of check_features but not its words (by src), and how their list is aligned.
+struct SourceWords {
+    const char *null_out, *null_in, *too_large, *in_misaligned;
+    uintptr_t in_mask;
+};
+constexpr SourceWords kSourceWords[3] = {
+    {": null output", ": null row_ids", ": n_rows * width too large", ": row_ids must be 4-byte aligned", 3u},
+    {": null id or output buffer", ": null id or output buffer", ": n_entries too large", ": the id buffer must be 8-byte aligned", 7u},
+    {": null ray or output buffer", ": null ray or output buffer", ": n_rays too large", ": the ray buffer must be 16-byte aligned", 15u},
+};
+
+// The arguments of the six feature calls (host side only; the scene comes last so that a bad argument is reported as such
+// whatever the scene). P: rt_params — a view, with a camera, for rows (whose list and length are p's own: `in` and `count` are
+// not looked at) and pixels — or rt_radiance_params for rays. `in`: the ids or rays, never read here but for host ids.
+// `device`: `in` and `out` are a *_device call's — read and written in aligned pieces, the ids range-checked on the device later.
+// The order of the rules is behaviour: of two faults, the one named is the one that comes first here.
+template <class P>
+void check_features(const rt_scene *scene, int src, const rt_camera *cam, const P *p, const void *in, uint64_t count, const void *out,
+                    bool device, const char *who) {
+    constexpr bool view = std::is_same<P, rt_params>::value;
     const std::string w(who);
+    const SourceWords &words = kSourceWords[src];
+    const bool rows = src == kFeatRows;
     RT_REQUIRE(p, RT_ERR_INVALID, w + ": null params");
-    RT_REQUIRE(cam, RT_ERR_INVALID, w + ": null camera");
-    require_feature_flags(p->flags, w);
-    check_view(cam, p, w + ": ", " (width, height or n_frames is 0)");
-    RT_REQUIRE(n_entries == 0 || (ids && out), RT_ERR_INVALID, w + ": null id or output buffer");
-    RT_REQUIRE(n_entries <= (1ull << 40), RT_ERR_INVALID, w + ": n_entries too large");
-    if (device) {
-        RT_REQUIRE(n_entries == 0 || !((uintptr_t)ids & 7u), RT_ERR_INVALID, w + ": the id buffer must be 8-byte aligned");
-        if (n_entries > 0) require_feature_out_aligned(out, w);
-    } else {
-        const uint64_t limit = (uint64_t)p->width * p->height * p->n_frames;      // (check_view: height * n_frames fits 32 bits)
-        for (uint64_t i = 0; i < n_entries; i++)
-            RT_REQUIRE(ids[i] < limit, RT_ERR_INVALID, w + ": pixel id out of range (>= width * height * n_frames)");
+    if constexpr (view) RT_REQUIRE(cam, RT_ERR_INVALID, w + ": null camera");
+    RT_REQUIRE(!(p->flags & ~(RT_FLAG_COUNTERS | RT_FLAG_SURFACES | RT_FLAG_SPECULAR)), RT_ERR_INVALID,
+               w + ": flag bits other than RT_FLAG_COUNTERS | RT_FLAG_SURFACES | RT_FLAG_SPECULAR");
+    uint64_t records = count;
+    if constexpr (view) {
+        check_view(cam, p, w + ": ", " (width, height or n_frames is 0)");
+        if (rows) { in = p->row_ids; count = p->n_rows; records = count * p->width; }
+    }
+    // (a row list is wanted only by a call that takes samples; a list of ids or rays by every call that has one)
+    const bool need_in = count > 0 && (!rows || p->spp > 0);
+    RT_REQUIRE(count == 0 || out, RT_ERR_INVALID, w + words.null_out);
+    RT_REQUIRE(!need_in || in, RT_ERR_INVALID, w + words.null_in);
+    RT_REQUIRE(records <= (1ull << 40), RT_ERR_INVALID, w + words.too_large);
+    const auto out_aligned = [&] { RT_REQUIRE(count == 0 || !((uintptr_t)out & 15u), RT_ERR_INVALID, w + ": the output must be 16-byte aligned"); };
+    if (device) {                                          // (the row call looks at its output first, the list calls at their list)
+        if (rows) out_aligned();
+        RT_REQUIRE(!need_in || !((uintptr_t)in & words.in_mask), RT_ERR_INVALID, w + words.in_misaligned);
+        if (!rows) out_aligned();
+    } else if constexpr (view) {
+        if (need_in && rows) check_host_ids(static_cast<const uint32_t *>(in), count, p, w);
+        if (need_in && !rows) check_host_ids(static_cast<const uint64_t *>(in), count, p, w);
     }
     RT_REQUIRE(scene, RT_ERR_INVALID, w + ": null scene");
 }
 
-// Enqueue one pixel-list feature call on `stream`, like run_features (n_entries > 0). `check_ids`: the ids came from the caller's
-// HBM — range-check them first (one synchronisation of the stream), whatever becomes of the list: a refused call has enqueued
-// nothing that writes the output.
-void run_features_pixels(rt_scene *sc, const rt_camera *cam, const rt_params *p, const uint64_t *d_ids, uint64_t n_entries, rt_feature *d_out,
-                         hipStream_t stream, rt_stats *stats, bool check_ids, const char *who) {
-    if (stats) std::memset(stats, 0, sizeof *stats);
-    const uint64_t limit = (uint64_t)p->width * p->height * p->n_frames;
+// Enqueue one feature call on `stream` (the scene's device is current, the arguments checked, there are records to write and the
+// stats are zeroed); with stats, wait for it and fill them. No samples: zeros and no kernel — behind the range check of a pixel
+// list, not of a row list (see FeatureJob). The ray source has nothing to check: without stats nothing here waits for the stream.
+void run_features(rt_scene *sc, const FeatureJob &job, hipStream_t stream) {
+    rt_stats *const stats = job.stats;
+    const uint64_t n = job.records();
+    const auto zeros = [&] {
+        RT_HIP(hipMemsetAsync(job.d_out, 0, n * sizeof(rt_feature), stream));
+        if (stats) RT_HIP(hipStreamSynchronize(stream));
+    };
+    if (job.spp == 0 && job.src != kFeatPixels) { zeros(); return; }
     QueryScratch &q = scratch_for(sc, sc->fs, stream);
     std::lock_guard<std::mutex> lock(q.mu);
-    if (check_ids) {
-        q.pixels.begin(d_ids, n_entries, limit, stream);
-        RT_HIP(hipStreamSynchronize(stream));
-        q.pixels.end(who, ": pixel id out of range (>= width * height * n_frames)");
+    q.ids.sync_and_check(job, stream, false);              // (ids from the caller's HBM: one synchronisation of the stream)
+    if (job.spp == 0) { zeros(); return; }
+    const bool counters = stats && (job.flags & RT_FLAG_COUNTERS);
+    const bool surfaces = (job.flags & RT_FLAG_SURFACES) != 0, specular = (job.flags & RT_FLAG_SPECULAR) != 0;
+    const FeatureArgs a = feature_args(job, q, counters);
+    run_counted(q, counters, stream, stats, [&] { return launch_features(sc->dev, a, sc->stack_need, job.src, counters, surfaces, specular, stream); });
+    // paths and rays of the call's n * spp samples. First-hit records: one camera path, one world.hit per sample; the kernel counts
+    // neither. RT_FLAG_SPECULAR: a sample has a segment per vertex it follows — rays is what the counter instance counted
+    // (read_stats put it there), 0 without counters.
+    if (stats) {
+        stats->paths = n * job.spp;
+        if (!specular) stats->rays = n * job.spp;
     }
-    if (p->spp == 0) {                                     // no sample: zeros, no kernel
-        RT_HIP(hipMemsetAsync(d_out, 0, n_entries * sizeof(rt_feature), stream));
-        if (stats) RT_HIP(hipStreamSynchronize(stream));
-        return;
-    }
-    const bool counters = stats && (p->flags & RT_FLAG_COUNTERS);
-    FeatureArgs a{};
-    a.cam = *cam;
-    a.width = p->width; a.height = p->height; a.spp = p->spp;
-    a.ids32 = limit <= 0xFFFFFFFFull ? 1u : 0u;
-    std::memcpy(a.background, p->background, sizeof a.background);
-    a.t_min = p->t_min;
-    a.seed = p->seed;
-    a.n_pixels = n_entries;
-    a.out = d_out;
-    a.counter = q.counter;
-    a.stats = counters ? q.stats.p : nullptr;
-    const bool surfaces = (p->flags & RT_FLAG_SURFACES) != 0, specular = (p->flags & RT_FLAG_SPECULAR) != 0;
-    a.pixel_ids = d_ids;
-    run_counted(q, counters, stream, stats, [&] { return launch_features_pixels(sc->dev, a, sc->stack_need, counters, surfaces, specular, stream); });
-    fill_feature_paths(stats, n_entries * p->spp, specular);
 }
 
-// The arguments of rt_features_rays* (host side only, the scene last, like check_features). `device`: rays and output are
-// rt_features_rays_device's. Ray contents are never looked at.
-void check_features_rays(const rt_scene *scene, const void *rays, uint64_t n_rays, const rt_radiance_params *p, const void *out, bool device,
-                         const char *who) {
-    const std::string w(who);
-    RT_REQUIRE(p, RT_ERR_INVALID, w + ": null params");
-    require_feature_flags(p->flags, w);
-    RT_REQUIRE(n_rays == 0 || (rays && out), RT_ERR_INVALID, w + ": null ray or output buffer");
-    RT_REQUIRE(n_rays <= (1ull << 40), RT_ERR_INVALID, w + ": n_rays too large");
-    if (device && n_rays > 0) {
-        RT_REQUIRE(!((uintptr_t)rays & 15u), RT_ERR_INVALID, w + ": the ray buffer must be 16-byte aligned");
-        require_feature_out_aligned(out, w);
-    }
-    RT_REQUIRE(scene, RT_ERR_INVALID, w + ": null scene");
+// A *_device call once its arguments are checked. Without records it returns before the scene is looked into (the ABI tests pass
+// a handle that is no scene).
+int features_device(rt_scene *scene, const FeatureJob &job, void *hip_stream) {
+    if (job.stats) std::memset(job.stats, 0, sizeof *job.stats);
+    if (job.records() == 0) return RT_OK;
+    DeviceGuard guard(scene->device);
+    run_features(scene, job, (hipStream_t)hip_stream);
+    return RT_OK;
 }
 
-// Enqueue one ray-list feature call on `stream`, like run_features (n_rays > 0). Nothing to check on the device: without stats
-// nothing here waits for the stream.
-void run_features_rays(rt_scene *sc, const rt_radiance_ray *d_rays, uint64_t n_rays, const rt_radiance_params *p, rt_feature *d_out,
-                       hipStream_t stream, rt_stats *stats) {
-    if (stats) std::memset(stats, 0, sizeof *stats);
-    if (p->spp == 0) {                                     // no sample: zeros, no kernel
-        RT_HIP(hipMemsetAsync(d_out, 0, n_rays * sizeof(rt_feature), stream));
-        if (stats) RT_HIP(hipStreamSynchronize(stream));
-        return;
+// The host form of a call: nothing, or zeros, with nothing for the device to do and the scene not looked into (as above); else
+// `in` — job.count row ids, pixel ids or rays — goes up to where job.*source then points, run_features fills a device copy of
+// the output — poisoned, so that an unwritten record cannot pass for a result — and that comes back.
+template <class T>
+int features_staged(rt_scene *scene, FeatureJob job, const T *FeatureJob::*source, const T *in, rt_feature *out) {
+    const uint64_t n = job.records();
+    if (job.stats) std::memset(job.stats, 0, sizeof *job.stats);
+    if (n == 0 || job.spp == 0) {
+        if (n) std::memset(out, 0, n * sizeof(rt_feature));
+        return RT_OK;
     }
-    QueryScratch &q = scratch_for(sc, sc->fs, stream);
-    std::lock_guard<std::mutex> lock(q.mu);
-    const bool counters = stats && (p->flags & RT_FLAG_COUNTERS);
-    FeatureArgs a{};                                       // (cam, width, height and seed: unused by the ray source)
-    a.spp = p->spp;
-    std::memcpy(a.background, p->background, sizeof a.background);
-    a.t_min = p->t_min;
-    a.n_pixels = n_rays;
-    a.rays = d_rays;
-    a.out = d_out;
-    a.counter = q.counter;
-    a.stats = counters ? q.stats.p : nullptr;
-    const bool surfaces = (p->flags & RT_FLAG_SURFACES) != 0, specular = (p->flags & RT_FLAG_SPECULAR) != 0;
-    run_counted(q, counters, stream, stats, [&] { return launch_features_rays(sc->dev, a, sc->stack_need, counters, surfaces, specular, stream); });
-    fill_feature_paths(stats, n_rays * p->spp, specular);
+    DeviceGuard guard(scene->device);
+    DeviceBuf<T> d_in(job.count);                              // (after the guard: freed with the scene's device current)
+    DeviceBuf<rt_feature> d_out(n);
+    RT_HIP(hipMemcpy(d_in, in, job.count * sizeof(T), hipMemcpyHostToDevice));
+    RT_HIP(hipMemset(d_out, 0xFF, n * sizeof(rt_feature)));
+    job.*source = d_in;
+    job.d_out = d_out;
+    run_features(scene, job, nullptr);
+    RT_HIP(hipMemcpy(out, d_out, n * sizeof(rt_feature), hipMemcpyDeviceToHost));
+    return RT_OK;
 }
 
 } // namespace
@@ -375,115 +385,60 @@ int rt_intersect_ordered(rt_scene *scene, const rt_query_ray *rays, const uint32
 
 int rt_features(rt_scene *scene, const rt_camera *cam, const rt_params *params, rt_feature *out_features, rt_stats *stats) {
     return guarded([&]() -> int {
-        check_features(scene, cam, params, out_features, false, "rt_features");
-        const uint64_t n_pixels = (uint64_t)params->n_rows * params->width;
-        if (n_pixels == 0) {
-            if (stats) std::memset(stats, 0, sizeof *stats);
-            return RT_OK;
-        }
-        if (params->spp == 0) {                                // zeros, and nothing for the device to do
-            if (stats) std::memset(stats, 0, sizeof *stats);
-            std::memset(out_features, 0, n_pixels * sizeof(rt_feature));
-            return RT_OK;
-        }
-        DeviceGuard guard(scene->device);
-        DeviceBuf<uint32_t> d_rows(params->n_rows);            // (after the guard: freed with the scene's device current)
-        DeviceBuf<rt_feature> d_out(n_pixels);
-        RT_HIP(hipMemcpy(d_rows, params->row_ids, params->n_rows * sizeof(uint32_t), hipMemcpyHostToDevice));
-        // Poison the output so an unwritten record cannot pass for a result.
-        RT_HIP(hipMemset(d_out, 0xFF, n_pixels * sizeof(rt_feature)));
-        run_features(scene, cam, params, d_rows, d_out, nullptr, stats, false, "rt_features");
-        RT_HIP(hipMemcpy(out_features, d_out, n_pixels * sizeof(rt_feature), hipMemcpyDeviceToHost));
-        return RT_OK;
+        const char *who = "rt_features";
+        check_features(scene, kFeatRows, cam, params, nullptr, 0, out_features, false, who);
+        return features_staged(scene, view_job(kFeatRows, cam, params, params->n_rows, nullptr, stats, false, who), &FeatureJob::d_rows,
+                               params->row_ids, out_features);
     });
 }
 
 int rt_features_device(rt_scene *scene, const rt_camera *cam, const rt_params *params, rt_feature *d_out_features, void *hip_stream,
                        rt_stats *stats) {
     return guarded([&]() -> int {
-        check_features(scene, cam, params, d_out_features, true, "rt_features_device");
-        if ((uint64_t)params->n_rows * params->width == 0) {
-            if (stats) std::memset(stats, 0, sizeof *stats);
-            return RT_OK;
-        }
-        DeviceGuard guard(scene->device);
-        run_features(scene, cam, params, params->row_ids, d_out_features, (hipStream_t)hip_stream, stats, true, "rt_features_device");
-        return RT_OK;
+        const char *who = "rt_features_device";
+        check_features(scene, kFeatRows, cam, params, nullptr, 0, d_out_features, true, who);
+        FeatureJob job = view_job(kFeatRows, cam, params, params->n_rows, d_out_features, stats, true, who);
+        job.d_rows = params->row_ids;
+        return features_device(scene, job, hip_stream);
     });
 }
 
 int rt_features_pixels(rt_scene *scene, const rt_camera *cam, const rt_params *params, const uint64_t *pixel_ids, uint64_t n_entries,
                        rt_feature *out_features, rt_stats *stats) {
     return guarded([&]() -> int {
-        check_features_pixels(scene, cam, params, pixel_ids, n_entries, out_features, false, "rt_features_pixels");
-        // (These early returns, here and in the device form, never read *scene: the checks above only compare the pointer with
-        // null. tests/test_features_pixels_abi.py calls them with a handle that is no scene; keep it that way.)
-        if (n_entries == 0 || params->spp == 0) {              // nothing, or zeros: nothing for the device to do
-            if (stats) std::memset(stats, 0, sizeof *stats);
-            if (n_entries) std::memset(out_features, 0, n_entries * sizeof(rt_feature));
-            return RT_OK;
-        }
-        DeviceGuard guard(scene->device);
-        DeviceBuf<uint64_t> d_ids(n_entries);                  // (after the guard: freed with the scene's device current)
-        DeviceBuf<rt_feature> d_out(n_entries);
-        RT_HIP(hipMemcpy(d_ids, pixel_ids, n_entries * sizeof(uint64_t), hipMemcpyHostToDevice));
-        // Poison the output so an unwritten record cannot pass for a result.
-        RT_HIP(hipMemset(d_out, 0xFF, n_entries * sizeof(rt_feature)));
-        run_features_pixels(scene, cam, params, d_ids, n_entries, d_out, nullptr, stats, false, "rt_features_pixels");
-        RT_HIP(hipMemcpy(out_features, d_out, n_entries * sizeof(rt_feature), hipMemcpyDeviceToHost));
-        return RT_OK;
+        const char *who = "rt_features_pixels";
+        check_features(scene, kFeatPixels, cam, params, pixel_ids, n_entries, out_features, false, who);
+        return features_staged(scene, view_job(kFeatPixels, cam, params, n_entries, nullptr, stats, false, who), &FeatureJob::d_pixel_ids,
+                               pixel_ids, out_features);
     });
 }
 
 int rt_features_pixels_device(rt_scene *scene, const rt_camera *cam, const rt_params *params, const uint64_t *d_pixel_ids, uint64_t n_entries,
                               rt_feature *d_out_features, void *hip_stream, rt_stats *stats) {
     return guarded([&]() -> int {
-        check_features_pixels(scene, cam, params, d_pixel_ids, n_entries, d_out_features, true, "rt_features_pixels_device");
-        if (n_entries == 0) {
-            if (stats) std::memset(stats, 0, sizeof *stats);
-            return RT_OK;
-        }
-        DeviceGuard guard(scene->device);
-        run_features_pixels(scene, cam, params, d_pixel_ids, n_entries, d_out_features, (hipStream_t)hip_stream, stats, true,
-                            "rt_features_pixels_device");
-        return RT_OK;
+        const char *who = "rt_features_pixels_device";
+        check_features(scene, kFeatPixels, cam, params, d_pixel_ids, n_entries, d_out_features, true, who);
+        FeatureJob job = view_job(kFeatPixels, cam, params, n_entries, d_out_features, stats, true, who);
+        job.d_pixel_ids = d_pixel_ids;
+        return features_device(scene, job, hip_stream);
     });
 }
 
 int rt_features_rays(rt_scene *scene, const rt_radiance_ray *rays, uint64_t n_rays, const rt_radiance_params *p, rt_feature *out_features,
                      rt_stats *stats) {
     return guarded([&]() -> int {
-        check_features_rays(scene, rays, n_rays, p, out_features, false, "rt_features_rays");
-        // (These early returns never read *scene, like rt_features_pixels': tests/test_features_rays_abi.py calls them with a
-        // handle that is no scene.)
-        if (n_rays == 0 || p->spp == 0) {                      // nothing, or zeros: nothing for the device to do
-            if (stats) std::memset(stats, 0, sizeof *stats);
-            if (n_rays) std::memset(out_features, 0, n_rays * sizeof(rt_feature));
-            return RT_OK;
-        }
-        DeviceGuard guard(scene->device);
-        DeviceBuf<rt_radiance_ray> d_rays(n_rays);             // (after the guard: freed with the scene's device current)
-        DeviceBuf<rt_feature> d_out(n_rays);
-        RT_HIP(hipMemcpy(d_rays, rays, n_rays * sizeof(rt_radiance_ray), hipMemcpyHostToDevice));
-        // Poison the output so an unwritten record cannot pass for a result.
-        RT_HIP(hipMemset(d_out, 0xFF, n_rays * sizeof(rt_feature)));
-        run_features_rays(scene, d_rays, n_rays, p, d_out, nullptr, stats);
-        RT_HIP(hipMemcpy(out_features, d_out, n_rays * sizeof(rt_feature), hipMemcpyDeviceToHost));
-        return RT_OK;
+        const char *who = "rt_features_rays";
+        check_features(scene, kFeatRays, nullptr, p, rays, n_rays, out_features, false, who);
+        return features_staged(scene, rays_job(nullptr, n_rays, p, nullptr, stats, who), &FeatureJob::d_rays, rays, out_features);
     });
 }
 
 int rt_features_rays_device(rt_scene *scene, const rt_radiance_ray *d_rays, uint64_t n_rays, const rt_radiance_params *p,
                             rt_feature *d_out_features, void *hip_stream, rt_stats *stats) {
     return guarded([&]() -> int {
-        check_features_rays(scene, d_rays, n_rays, p, d_out_features, true, "rt_features_rays_device");
-        if (n_rays == 0) {
-            if (stats) std::memset(stats, 0, sizeof *stats);
-            return RT_OK;
-        }
-        DeviceGuard guard(scene->device);
-        run_features_rays(scene, d_rays, n_rays, p, d_out_features, (hipStream_t)hip_stream, stats);
-        return RT_OK;
+        const char *who = "rt_features_rays_device";
+        check_features(scene, kFeatRays, nullptr, p, d_rays, n_rays, d_out_features, true, who);
+        return features_device(scene, rays_job(d_rays, n_rays, p, d_out_features, stats, who), hip_stream);
     });
 }
 

@@ -107,13 +107,7 @@ RenderJob image_job(const rt_camera *cam, const rt_params *p, const uint32_t *d_
 // The one synchronisation of `stream` a call makes before its first pass (`sync_anyway`; false: only if there is something to
 // check), with the two halves of the range check of the job's device ids (IdCheck) around it: no synchronisation of their own.
 void sync_and_check_ids(Workspace &w, const RenderJob &job, hipStream_t stream, bool sync_anyway) {
-    const bool rows = job.check_ids && job.count > 0 && job.d_rows, pixels = job.check_ids && job.count > 0 && job.d_pixel_ids;
-    const uint64_t row_limit = (uint64_t)job.height * job.n_frames;
-    if (rows) w.rows.begin(job.d_rows, job.count, row_limit, stream);
-    if (pixels) w.pixels.begin(job.d_pixel_ids, job.count, (uint64_t)job.width * row_limit, stream);
-    if (rows || pixels || sync_anyway) RT_HIP(hipStreamSynchronize(stream));
-    if (rows) w.rows.end(job.who, ": row id out of range");
-    if (pixels) w.pixels.end(job.who, ": pixel id out of range (>= width * height * n_frames)");
+    w.ids.sync_and_check(job, stream, sync_anyway);
 }
 
 // RenderArgs of `job` as the kernels take them — the one place that fills them, but for the two pointers that belong to an
@@ -278,12 +272,7 @@ void check_render_pixels(const rt_scene *scene, const rt_camera *cam, const rt_p
     const uint64_t n_chunks = plan_chunks(p->spp, p->spp_chunk).n_chunks;
     // (a division, not a product: n_entries * n_chunks itself may not fit 64 bits)
     RT_REQUIRE(n_entries <= RT_RADIANCE_MAX_ITEMS / n_chunks, RT_ERR_INVALID, w + ": n_entries * ceil(spp / spp_chunk) > RT_RADIANCE_MAX_ITEMS");
-    if (!device) {                                             // (device ids: the counting kernel, PixelCheck)
-        const uint64_t limit = (uint64_t)p->width * p->height * p->n_frames;
-        const uint64_t *host_ids = static_cast<const uint64_t *>(ids);
-        for (uint64_t i = 0; i < n_entries; i++)
-            RT_REQUIRE(host_ids[i] < limit, RT_ERR_INVALID, w + ": pixel id out of range (>= width * height * n_frames)");
-    }
+    if (!device) check_host_ids(static_cast<const uint64_t *>(ids), n_entries, p, w);      // (device ids: the counting kernel, IdCheck)
     RT_REQUIRE(scene, RT_ERR_INVALID, w + ": null scene");
     RT_REQUIRE(scene->engine == 1, RT_ERR_UNSUPPORTED, w + ": only the wavefront engine renders pixel lists (rt_debug_set_engine)");
 }
@@ -486,8 +475,7 @@ int rt_render(rt_scene *scene, const rt_camera *cam, const rt_params *params, do
     return guarded([&]() -> int {
         check_params(scene, cam, params);
         RT_REQUIRE(out_rgb_sum || params->n_rows == 0, RT_ERR_INVALID, "rt_render: output is null");
-        for (uint32_t i = 0; i < params->n_rows; i++)
-            RT_REQUIRE(params->row_ids[i] < (uint64_t)params->height * params->n_frames, RT_ERR_INVALID, "rt_render: row id out of range");
+        check_host_ids(params->row_ids, params->n_rows, params, "rt_render");
         uint64_t n_values = (uint64_t)params->n_rows * params->width * 3;
         DeviceGuard guard(scene->device);
         DeviceBuf<uint32_t> d_rows(params->n_rows ? params->n_rows : 1);     // (after the guard: freed with the scene's device current)

@@ -565,6 +565,21 @@ def ray_order_device(d_rays_ptr, n_rays, params, d_order_ptr, d_workspace_ptr, w
                                         workspace_bytes, C.c_void_p(stream_ptr or 0)))
 
 
+def _ref(stats):
+    """An optional rt_stats as the C calls take it: a reference, or a null pointer."""
+    return C.byref(stats) if stats is not None else None
+
+
+def _data(a):
+    """An array's buffer as the C calls take it: its address, or a null pointer for an empty one."""
+    return a.ctypes.data if a.size else None
+
+
+def _feature_flags(counters, surfaces, specular):
+    """The flag word of the six feature calls."""
+    return (F.RT_FLAG_COUNTERS if counters else 0) | (F.RT_FLAG_SURFACES if surfaces else 0) | (F.RT_FLAG_SPECULAR if specular else 0)
+
+
 class DeviceScene:
     """rt_scene: the flattened scene copied into HBM on the current HIP device."""
 
@@ -641,7 +656,7 @@ class DeviceScene:
         if asynchronous:
             p.flags |= F.RT_FLAG_ASYNC
         F.check(F.lib().rt_render_device(self._h, C.byref(cam), C.byref(p), C.c_void_p(d_out_ptr),
-                                         C.c_void_p(stream_ptr or 0), C.byref(stats) if stats is not None else None))
+                                         C.c_void_p(stream_ptr or 0), _ref(stats)))
 
     def wait(self, stream_ptr=None):
         F.check(F.lib().rt_render_wait(self._h, C.c_void_p(stream_ptr or 0)))
@@ -671,8 +686,8 @@ class DeviceScene:
             if o.shape != (len(r),):
                 raise ValueError("an order holds one entry per ray")
             # (the parameters are ignored beside an order; they only keep an empty batch, whose order is no pointer, valid)
-            F.check(F.lib().rt_intersect_ordered(self._h, p_rays, o.ctypes.data if len(r) else None, C.byref(ray_order_params()), len(r), flags,
-                                                 p_out, C.byref(st)))
+            F.check(F.lib().rt_intersect_ordered(self._h, p_rays, _data(o), C.byref(ray_order_params()), len(r), flags, p_out,
+                                                 C.byref(st)))
         return (out, st) if want_stats else out
 
     def intersect_ordered_device(self, d_rays_ptr, d_order_ptr, n, d_hits_ptr, d_workspace_ptr, workspace_bytes, stream_ptr=None,
@@ -686,7 +701,7 @@ class DeviceScene:
             flags |= F.RT_FLAG_COUNTERS
         F.check(F.lib().rt_intersect_ordered_device(self._h, C.c_void_p(d_rays_ptr), C.c_void_p(d_order_ptr), n, flags, C.c_void_p(d_hits_ptr),
                                                     C.c_void_p(d_workspace_ptr), workspace_bytes, C.c_void_p(stream_ptr or 0),
-                                                    C.byref(stats) if stats is not None else None))
+                                                    _ref(stats)))
 
     def intersect_device(self, d_rays_ptr, n, d_hits_ptr, stream_ptr=None, any_hit=False, stats=None):
         """rt_intersect_device: device pointers in (n rt_query_ray records, room for n rt_hit), enqueued on `stream_ptr`
@@ -696,7 +711,7 @@ class DeviceScene:
         if stats is not None:
             flags |= F.RT_FLAG_COUNTERS
         F.check(F.lib().rt_intersect_device(self._h, C.c_void_p(d_rays_ptr), n, flags, C.c_void_p(d_hits_ptr),
-                                            C.c_void_p(stream_ptr or 0), C.byref(stats) if stats is not None else None))
+                                            C.c_void_p(stream_ptr or 0), _ref(stats)))
 
     def radiance(self, rays, spp=1, background=(0.0, 0.0, 0.0), t_min=0.001, max_depth=50, want_stats=False, kernel_times=False):
         """rt_radiance: the sum over spp samples of ray_color for every ray of `rays` (RADIANCE_RAY_DTYPE, see radiance_rays)
@@ -706,8 +721,7 @@ class DeviceScene:
         flags = (F.RT_FLAG_COUNTERS if want_stats else 0) | (F.RT_FLAG_KERNEL_TIMES if kernel_times else 0)
         p = radiance_params(spp, background, t_min, max_depth, flags)
         st = F.rt_stats()
-        F.check(F.lib().rt_radiance(self._h, r.ctypes.data if len(r) else None, len(r), C.byref(p), out.ctypes.data if len(r) else None,
-                                    C.byref(st)))
+        F.check(F.lib().rt_radiance(self._h, _data(r), len(r), C.byref(p), _data(out), C.byref(st)))
         return (out, st) if want_stats else out
 
     def radiance_device(self, d_rays_ptr, n, d_out_ptr, params, stream_ptr=None, stats=None):
@@ -715,7 +729,7 @@ class DeviceScene:
         rt_radiance_params (radiance_params), run on `stream_ptr` (hipStream_t as int); returns when the sums are written.
         An rt_stats is filled (its counters with RT_FLAG_COUNTERS in params.flags)."""
         F.check(F.lib().rt_radiance_device(self._h, C.c_void_p(d_rays_ptr), n, C.byref(params), C.c_void_p(d_out_ptr),
-                                           C.c_void_p(stream_ptr or 0), C.byref(stats) if stats is not None else None))
+                                           C.c_void_p(stream_ptr or 0), _ref(stats)))
 
     def render_pixels(self, cam, params, ids, want_stats=False, kernel_times=False):
         """rt_render_pixels with host buffers: the render's sums of a list of (frame, pixel) ids (uint64, see pixel_ids; params.n_frames
@@ -727,8 +741,7 @@ class DeviceScene:
                   (F.RT_FLAG_KERNEL_TIMES if kernel_times else 0)
         out = np.zeros((len(e), 3), dtype=np.float64)
         st = F.rt_stats()
-        F.check(F.lib().rt_render_pixels(self._h, C.byref(cam), C.byref(p), e.ctypes.data if len(e) else None, len(e),
-                                         out.ctypes.data if len(e) else None, C.byref(st)))
+        F.check(F.lib().rt_render_pixels(self._h, C.byref(cam), C.byref(p), _data(e), len(e), _data(out), C.byref(st)))
         return (out, st) if want_stats else out
 
     def render_pixels_device(self, cam, params, d_ids_ptr, n_entries, d_out_ptr, stream_ptr=None, stats=None):
@@ -738,7 +751,7 @@ class DeviceScene:
         p = F.rt_params.from_buffer_copy(params)
         p.n_rows, p.row_ids, p.progress_cb = 0, None, None
         F.check(F.lib().rt_render_pixels_device(self._h, C.byref(cam), C.byref(p), C.c_void_p(d_ids_ptr), n_entries, C.c_void_p(d_out_ptr),
-                                                C.c_void_p(stream_ptr or 0), C.byref(stats) if stats is not None else None))
+                                                C.c_void_p(stream_ptr or 0), _ref(stats)))
 
     def features(self, cam, params, row_ids, want_stats=False, surfaces=False, specular=False):
         """rt_features with host buffers: the first-hit guide buffers of the camera rays a render of (cam, params, row_ids)
@@ -754,10 +767,10 @@ class DeviceScene:
         p.n_rows = len(rows)
         p.row_ids = rows.ctypes.data
         p.progress_cb = None
-        p.flags = (F.RT_FLAG_COUNTERS if want_stats else 0) | (F.RT_FLAG_SURFACES if surfaces else 0) | (F.RT_FLAG_SPECULAR if specular else 0)
+        p.flags = _feature_flags(want_stats, surfaces, specular)
         out = np.zeros((len(rows), p.width), dtype=F.FEATURE_DTYPE)
         st = F.rt_stats()
-        F.check(F.lib().rt_features(self._h, C.byref(cam), C.byref(p), out.ctypes.data if out.size else None, C.byref(st)))
+        F.check(F.lib().rt_features(self._h, C.byref(cam), C.byref(p), _data(out), C.byref(st)))
         return (out, st) if want_stats else out
 
     def features_device(self, cam, params, d_row_ids_ptr, n_rows, d_out_ptr, stream_ptr=None, stats=None, surfaces=False, specular=False):
@@ -768,9 +781,9 @@ class DeviceScene:
         p.n_rows = n_rows
         p.row_ids = d_row_ids_ptr
         p.progress_cb = None
-        p.flags = (F.RT_FLAG_COUNTERS if stats is not None else 0) | (F.RT_FLAG_SURFACES if surfaces else 0) | (F.RT_FLAG_SPECULAR if specular else 0)
+        p.flags = _feature_flags(stats is not None, surfaces, specular)
         F.check(F.lib().rt_features_device(self._h, C.byref(cam), C.byref(p), C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr or 0),
-                                           C.byref(stats) if stats is not None else None))
+                                           _ref(stats)))
 
     def features_pixels(self, cam, params, ids, want_stats=False, surfaces=False, specular=False):
         """rt_features_pixels with host buffers: the feature records of a list of (frame, pixel) ids (uint64, see pixel_ids;
@@ -779,11 +792,10 @@ class DeviceScene:
         e = np.ascontiguousarray(ids, dtype=np.uint64).ravel()
         p = F.rt_params.from_buffer_copy(params)
         p.n_rows, p.row_ids, p.progress_cb = 0, None, None
-        p.flags = (F.RT_FLAG_COUNTERS if want_stats else 0) | (F.RT_FLAG_SURFACES if surfaces else 0) | (F.RT_FLAG_SPECULAR if specular else 0)
+        p.flags = _feature_flags(want_stats, surfaces, specular)
         out = np.zeros(len(e), dtype=F.FEATURE_DTYPE)
         st = F.rt_stats()
-        F.check(F.lib().rt_features_pixels(self._h, C.byref(cam), C.byref(p), e.ctypes.data if len(e) else None, len(e),
-                                           out.ctypes.data if len(e) else None, C.byref(st)))
+        F.check(F.lib().rt_features_pixels(self._h, C.byref(cam), C.byref(p), _data(e), len(e), _data(out), C.byref(st)))
         return (out, st) if want_stats else out
 
     def features_pixels_device(self, cam, params, d_ids_ptr, n_entries, d_out_ptr, stream_ptr=None, stats=None, surfaces=False, specular=False):
@@ -793,9 +805,9 @@ class DeviceScene:
         synchronise the stream and fill it, counters included."""
         p = F.rt_params.from_buffer_copy(params)
         p.n_rows, p.row_ids, p.progress_cb = 0, None, None
-        p.flags = (F.RT_FLAG_COUNTERS if stats is not None else 0) | (F.RT_FLAG_SURFACES if surfaces else 0) | (F.RT_FLAG_SPECULAR if specular else 0)
+        p.flags = _feature_flags(stats is not None, surfaces, specular)
         F.check(F.lib().rt_features_pixels_device(self._h, C.byref(cam), C.byref(p), C.c_void_p(d_ids_ptr), n_entries, C.c_void_p(d_out_ptr),
-                                                  C.c_void_p(stream_ptr or 0), C.byref(stats) if stats is not None else None))
+                                                  C.c_void_p(stream_ptr or 0), _ref(stats)))
 
     def features_rays(self, rays, spp=1, background=(0.0, 0.0, 0.0), t_min=0.001, want_stats=False, surfaces=False, specular=False):
         """rt_features_rays with host buffers: the feature records of rays the caller chooses (RADIANCE_RAY_DTYPE, see
@@ -803,12 +815,11 @@ class DeviceScene:
         sample s drawing from path_key(rng_state, 0, 0, s) as radiance()'s does, not divided by spp [, rt_stats]. surfaces and
         specular as for features(). What rt.denoise needs beside radiance()'s sums of a camera of the caller's own."""
         r = np.ascontiguousarray(rays, dtype=F.RADIANCE_RAY_DTYPE)
-        flags = (F.RT_FLAG_COUNTERS if want_stats else 0) | (F.RT_FLAG_SURFACES if surfaces else 0) | (F.RT_FLAG_SPECULAR if specular else 0)
+        flags = _feature_flags(want_stats, surfaces, specular)
         p = radiance_params(spp, background, t_min, 0, flags)
         out = np.zeros(len(r), dtype=F.FEATURE_DTYPE)
         st = F.rt_stats()
-        F.check(F.lib().rt_features_rays(self._h, r.ctypes.data if len(r) else None, len(r), C.byref(p), out.ctypes.data if len(r) else None,
-                                         C.byref(st)))
+        F.check(F.lib().rt_features_rays(self._h, _data(r), len(r), C.byref(p), _data(out), C.byref(st)))
         return (out, st) if want_stats else out
 
     def features_rays_device(self, d_rays_ptr, n, d_out_ptr, params, stream_ptr=None, stats=None, surfaces=False, specular=False):
@@ -817,9 +828,9 @@ class DeviceScene:
         `stream_ptr` (hipStream_t as int). stats=None is a pure enqueue with no host synchronisation; an rt_stats makes the call
         synchronise the stream and fill it, counters included."""
         p = F.rt_radiance_params.from_buffer_copy(params)
-        p.flags = (F.RT_FLAG_COUNTERS if stats is not None else 0) | (F.RT_FLAG_SURFACES if surfaces else 0) | (F.RT_FLAG_SPECULAR if specular else 0)
+        p.flags = _feature_flags(stats is not None, surfaces, specular)
         F.check(F.lib().rt_features_rays_device(self._h, C.c_void_p(d_rays_ptr), n, C.byref(p), C.c_void_p(d_out_ptr),
-                                                C.c_void_p(stream_ptr or 0), C.byref(stats) if stats is not None else None))
+                                                C.c_void_p(stream_ptr or 0), _ref(stats)))
 
     def close(self):
         if self._h:
