@@ -423,6 +423,74 @@ int rt_intersect(rt_scene *scene, const rt_query_ray *rays, uint64_t n_rays, uin
 int rt_intersect_device(rt_scene *scene, const rt_query_ray *d_rays, uint64_t n_rays, uint32_t flags,
                         rt_hit *d_out_hits, void *hip_stream, rt_stats *stats);
 
+/* ---- scatter: one step of ray_color between two world.hit calls -------------------------------------
+ * The shading half of `ray_color` (main.rs:233-278) for a batch of hit records on the device scene: what lies between its
+ * `world.hit` and its recursive call. Entry i is shaded from rays[i] (direction, time and rng_state are read), hits[i] (the
+ * rt_hit of that ray, or any record the caller makes up) and the scene; the outputs are a record — weight, pdf, radiance,
+ * status — and the path's next ray as a ready rt_query_ray. So rt_intersect_device -> rt_scatter_device -> rt_intersect_device
+ * -> ... is a wavefront path tracer the caller drives with no kernel of their own (direct and indirect light kept apart,
+ * per-bounce AOVs, Russian roulette, other estimators), and unwound in the reference's order it is rt_radiance bit for bit.
+ *
+ * Stream: the step draws from Rng(rays[i].rng_state advanced by hits[i].rng_draws words); the state after k words is
+ * state + k * 0x9E3779B97F4A7C15 mod 2^64.
+ * prev: with prev != NULL an entry whose prev[i].status is neither RT_SCATTER_SPECULAR nor RT_SCATTER_DIFFUSE is
+ * RT_SCATTER_ENDED: nothing else of the entry is read but the ray's rng_state, and no word is drawn. prev == NULL: every entry
+ * is live.
+ * Status of a live entry:
+ *   - hits[i].hit == 0: MISS, radiance = background. Any non-zero `hit` word is a hit, any non-zero `front_face` word is true.
+ *   - mat >= the scene's n_materials: INVALID; the material pool is not read.
+ *   - DiffuseLight: EMITTED, radiance = front_face ? the texture's value : 0 (material/mod.rs:174-180).
+ *   - Metal, Dielectric, Isotropic: SPECULAR (mod.rs:85-96, 120-147, 207-213; Metal's next ray has time 0, mod.rs:91).
+ *   - Lambertian: DIFFUSE. With n_lights == 0 the cosine direction and its pdf; otherwise the mixture's choice
+ *     gen_range(0, 1) < 0.5, then HittableList::random over the lights or the cosine direction, and
+ *     pdf = 0.5 * lights' pdf_value + 0.5 * cosine pdf (pdf.rs:94-104). weight = attenuation * scattering_pdf.
+ * NaN and non-finite inputs come out where the CPU oracle's do; record contents are never validated beyond `mat`.
+ * Next ray: SPECULAR, DIFFUSE: origin = the record's p, the scattered direction and time, t_min = p->t_min,
+ * t_max = 1.7976931348623157e308 (f64::MAX, main.rs:243: not infinity), rng_state = the stream's state behind this step's
+ * words. Every other status: all fields 0 except rng_state = the input state advanced by hits[i].rng_draws words (ENDED: the
+ * input's rng_state unchanged).
+ * Radiance of a path with live records r_0 .. r_{k-1}: T = the first non-live record's radiance, or (0, 0, 0) when the depth
+ * ran out; L = T; for j = k-1 .. 0: L = 0 + (weight_j * L) / pdf_j, component-wise.
+ * Aliasing: out_next_rays may be rays itself, and out_recs may be prev itself (an entry is read before it is written). Any
+ * other overlap is the caller's error.
+ *
+ * rt_stats (may be NULL): with RT_FLAG_COUNTERS rng_draws = the sum of the records' rng_draws and light_pdf_tests = what the
+ * oracle counts (one per Sphere or rect entry of the light list that is not a FlipFace, per DIFFUSE record of a scene with
+ * lights); every other counter is 0; ms is the device time of the call. rt_scatter_device with stats == NULL is a pure
+ * enqueue, like rt_intersect_device; with stats it synchronises hip_stream.
+ *
+ * Arguments: n == 0 is RT_OK with no launch. RT_ERR_INVALID with rt_last_error() set (prefixed by the function's name),
+ * before any device call and with every output untouched: a null scene or params; a null ray, hit, record or next-ray buffer
+ * with n > 0 (prev may be null); a flag bit other than RT_FLAG_COUNTERS; a device buffer of
+ * rt_scatter_device that is not 16-byte aligned (prev included when given).
+ * Like the queries: the call makes the scene's device current and restores the caller's, owns its scratch per (scene,
+ * stream), may run beside an RT_FLAG_ASYNC render of the same scene, is awaited by rt_scene_destroy and does not depend on
+ * the engine selected. New symbols only: the ABI version stays 3. */
+typedef struct rt_scatter_params {    /* 40 B */
+    double   background[3];           /* what a miss returns (main.rs:275-276) */
+    double   t_min;                   /* copied into every next ray (0.001 in main.rs:243) */
+    uint32_t flags;                   /* RT_FLAG_COUNTERS only */
+    uint32_t _pad;
+} rt_scatter_params;
+
+enum rt_scatter_status { RT_SCATTER_MISS = 0, RT_SCATTER_EMITTED = 1, RT_SCATTER_SPECULAR = 2, RT_SCATTER_DIFFUSE = 3,
+                         RT_SCATTER_INVALID = 4, RT_SCATTER_ENDED = 5 };
+
+typedef struct rt_scatter_rec {       /* 64 B: four 16-byte pieces */
+    double   weight[3];               /* SPECULAR: attenuation; DIFFUSE: attenuation * scattering_pdf; else 0 */
+    double   pdf;                     /* SPECULAR: 1.0; DIFFUSE: the mixture pdf's value (may be 0 or NaN, as the reference's); else 0 */
+    double   radiance[3];             /* MISS: background; EMITTED: Material::emitted; else 0 */
+    uint32_t status;                  /* rt_scatter_status */
+    uint32_t rng_draws;               /* words this step drew (the hit's own words are rt_hit.rng_draws) */
+} rt_scatter_rec;
+
+/* Host buffers; synchronous. stats and prev may be NULL. */
+int rt_scatter(rt_scene *scene, const rt_query_ray *rays, const rt_hit *hits, const rt_scatter_rec *prev, uint64_t n,
+               const rt_scatter_params *p, rt_scatter_rec *out_recs, rt_query_ray *out_next_rays, rt_stats *stats);
+/* Device buffers, enqueued on hip_stream (NULL = default stream). */
+int rt_scatter_device(rt_scene *scene, const rt_query_ray *d_rays, const rt_hit *d_hits, const rt_scatter_rec *d_prev, uint64_t n,
+                      const rt_scatter_params *p, rt_scatter_rec *d_out_recs, rt_query_ray *d_out_next_rays, void *hip_stream, rt_stats *stats);
+
 /* ---- path-traced radiance of caller rays ----------------------------------------------------------
  * `ray_color(r, background, world, lights, depth)` (main.rs:233-278) for rays the caller chooses instead of the camera's:
  * other cameras (panoramas, orthographic, stereo), light probes and irradiance baking, progressive or adaptive sampling,

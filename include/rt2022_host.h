@@ -81,6 +81,8 @@ int rtb_denoise_dual_abi_sizes(uint32_t *out, uint32_t n);
 int rtb_adaptive_abi_sizes(uint32_t *out, uint32_t n);
 /* The same for the rt_temporal* structures: {rt_temporal_pixel, rt_temporal_params}; returns 2. */
 int rtb_temporal_abi_sizes(uint32_t *out, uint32_t n);
+/* The same for the rt_scatter* structures: {rt_scatter_params, rt_scatter_rec}; returns 2. */
+int rtb_scatter_abi_sizes(uint32_t *out, uint32_t n);
 
 #ifdef __cplusplus
 }

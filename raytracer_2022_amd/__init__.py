@@ -22,6 +22,8 @@ from .host import rebuild_bvh, ref_boxes, tree_leaves  # noqa: F401
 from .device import bvh_build, bvh_build_device, bvh_workspace_bytes  # noqa: F401
 from .device import (RAY_ORDER_DEFAULTS, intersect_ordered_workspace_bytes, ray_order, ray_order_device, ray_order_params,  # noqa: F401
                      ray_order_workspace_bytes)
+from .device import path_key, radiance_by_steps, scatter_params, unwind  # noqa: F401
+from ._ffi import SCATTER_REC_DTYPE  # noqa: F401
 
 __all__ = ["DescBuilder", "HostScene", "DeviceScene", "DeviceSceneSet", "camera_new", "fill_image", "make_params", "shuffled_rows",
            "write_color", "write_jpeg", "load_image", "RtError", "lib", "make_ref", "ref_kind", "ref_index", "query_rays",
@@ -34,4 +36,4 @@ __all__ = ["DescBuilder", "HostScene", "DeviceScene", "DeviceSceneSet", "camera_
            "temporal", "temporal_device", "temporal_params", "temporal_workspace_bytes", "TEMPORAL_DEFAULTS", "TEMPORAL_PIXEL_DTYPE",
            "ref_boxes", "rebuild_bvh", "tree_leaves", "bvh_build", "bvh_build_device", "bvh_workspace_bytes", "BVH_NODE_DTYPE",
            "ray_order", "ray_order_device", "ray_order_params", "ray_order_workspace_bytes", "intersect_ordered_workspace_bytes",
-           "RAY_ORDER_DEFAULTS"]
+           "RAY_ORDER_DEFAULTS", "scatter_params", "unwind", "radiance_by_steps", "path_key", "SCATTER_REC_DTYPE"]

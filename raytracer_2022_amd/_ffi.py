@@ -177,6 +177,22 @@ HIT_DTYPE = np.dtype([("t", "<f8"), ("u", "<f8"), ("v", "<f8"), ("p", "<f8", (3,
                       ("hit", "<u4"), ("front_face", "<u4"), ("mat", "<u4"), ("prim", "<u4"), ("rng_draws", "<u4"),
                       ("_pad", "<u4")])
 
+
+class rt_scatter_params(C.Structure):
+    _fields_ = [("background", d3), ("t_min", C.c_double), ("flags", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class rt_scatter_rec(C.Structure):
+    _fields_ = [("weight", d3), ("pdf", C.c_double), ("radiance", d3), ("status", C.c_uint32), ("rng_draws", C.c_uint32)]
+
+
+(RT_SCATTER_MISS, RT_SCATTER_EMITTED, RT_SCATTER_SPECULAR, RT_SCATTER_DIFFUSE, RT_SCATTER_INVALID, RT_SCATTER_ENDED) = range(6)
+# numpy twin of rt_scatter_rec (arrays of it come back from rt_scatter, and go in as `prev`, as they are)
+SCATTER_REC_DTYPE = np.dtype([("weight", "<f8", (3,)), ("pdf", "<f8"), ("radiance", "<f8", (3,)), ("status", "<u4"), ("rng_draws", "<u4")])
+# The rt_scatter* structures, in the order of rtb_scatter_abi_sizes (ABI_STRUCTS keeps its own list as it was).
+SCATTER_ABI_STRUCTS = [rt_scatter_params, rt_scatter_rec]
+
+
 class rt_radiance_ray(C.Structure):
     _fields_ = [("origin", d3), ("direction", d3), ("time", C.c_double), ("rng_state", C.c_uint64)]
 
@@ -283,6 +299,7 @@ ABI_SYMBOLS = [
     "rt_adaptive_merge_device", "rt_adaptive_resolve_device", "rtb_adaptive_abi_sizes",
     "rt_features_pixels", "rt_features_pixels_device", "rt_adaptive_merge_features_device", "rt_adaptive_resolve_features_device",
     "rt_features_rays", "rt_features_rays_device",
+    "rt_scatter", "rt_scatter_device", "rtb_scatter_abi_sizes",
     "rtb_scene_build", "rtb_scene_free", "rtb_scene_desc", "rtb_scene_default_view", "rtb_camera_new",
     "rtb_shuffled_rows", "rtb_bvh_build", "rtb_fill_image", "rtb_write_ppm", "rtb_write_jpeg", "rtb_image_load",
     "rtb_last_error", "rtb_abi_sizes", "rtb_radiance_abi_sizes", "rtb_features_abi_sizes", "rtb_denoise_abi_sizes",
@@ -367,6 +384,9 @@ def lib():
     L.rt_features_pixels_device.argtypes = [vp, P(rt_camera), P(rt_params), vp, u64, vp, vp, P(rt_stats)]
     L.rt_features_rays.argtypes = [vp, vp, u64, P(rt_radiance_params), vp, P(rt_stats)]
     L.rt_features_rays_device.argtypes = [vp, vp, u64, P(rt_radiance_params), vp, vp, P(rt_stats)]
+    L.rt_scatter.argtypes = [vp, vp, vp, vp, u64, P(rt_scatter_params), vp, vp, P(rt_stats)]
+    L.rt_scatter_device.argtypes = [vp, vp, vp, vp, u64, P(rt_scatter_params), vp, vp, vp, P(rt_stats)]
+    L.rtb_scatter_abi_sizes.argtypes = [P(u32), u32]
     L.rt_adaptive_merge_features_device.argtypes = [vp, vp, vp, u64, vp, vp]
     L.rt_adaptive_resolve_features_device.argtypes = [vp, vp, u64, u32, vp, vp]
     L.rtb_scene_build.argtypes = [C.c_char_p, u64, C.c_char_p, i32, P(vp)]

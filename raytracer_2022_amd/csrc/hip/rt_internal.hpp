@@ -156,8 +156,8 @@ struct Workspace {
     std::string async_err;
 };
 
-// Scratch of the closest-hit calls — queries (rt_intersect*) or feature buffers (rt_features*) — on one (scene, stream): the
-// work counter of the persistent grid, a counter block and two events, created when it is constructed. Nothing of a render's
+// Scratch of the closest-hit calls — queries (rt_intersect*) or feature buffers (rt_features*) — and of the scatter steps
+// (rt_scatter*, which leave the work counter alone) on one (scene, stream): the work counter of the persistent grid, a counter block and two events, created when it is constructed. Nothing of a render's
 // Workspace: such a call may run beside an asynchronous render of the same scene.
 struct QueryScratch {
     std::mutex mu;                    // one call at a time enqueues — and, with stats, reads back — on this (scene, stream)
@@ -187,9 +187,11 @@ struct rt_scene : rt2022::SceneFacts {               // (what check_scene found:
     int n_cus = 0;                    // compute units of `device`
     std::mutex mu;
     std::map<hipStream_t, rt2022::Workspace> ws;
-    std::mutex qmu;                   // guards `qs` and `fs`
-    // (two maps: a query and a feature call on one stream share no mutex and no counter, and run side by side)
+    std::mutex qmu;                   // guards `qs`, `fs` and `ss`
+    // (a map per family: a query, a feature call and a scatter step on one stream share no mutex and no counter, and run side by side)
     std::map<hipStream_t, std::unique_ptr<rt2022::QueryScratch>> qs, fs;    // of rt_intersect*, of rt_features*
+    std::map<hipStream_t, std::unique_ptr<rt2022::QueryScratch>> ss;        // of rt_scatter*
+    uint32_t n_materials = 0;         // records in dev.materials (rt_scatter* refuses a made-up record's index against it)
 };
 
 // One call, several GPUs: a scene per device of the mask.

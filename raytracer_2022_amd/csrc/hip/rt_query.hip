@@ -3,17 +3,20 @@
 // rt_features_pixels*, rt_features_rays*: first-hit records, and with RT_FLAG_SPECULAR the records behind glass and mirrors).
 // The six feature calls are one call with three sources of work items: one description of it (FeatureJob), one check of the
 // arguments (check_features), one enqueue (run_features) and one staged host form (features_staged), as rt_render.hip has one
-// RenderJob for its renders.
+// RenderJob for its renders. Beside them the scatter step on the records of a query (rt_scatter*, pt_scatter.hip), with the same
+// scratch, counting and staging.
 #include <type_traits>
 
+#include "../host/scatter_check.hpp"
 #include "pt_order.hpp"
+#include "pt_scatter.hpp"
 #include "rt_internal.hpp"
 
 using namespace rt2022;
 
 namespace {
 
-// The scratch of `stream` in sc->qs or sc->fs.
+// The scratch of `stream` in sc->qs, sc->fs or sc->ss.
 QueryScratch &scratch_for(rt_scene *sc, std::map<hipStream_t, std::unique_ptr<QueryScratch>> &of, hipStream_t stream) {
     std::lock_guard<std::mutex> lock(sc->qmu);
     std::unique_ptr<QueryScratch> &q = of[stream];
@@ -21,11 +24,12 @@ QueryScratch &scratch_for(rt_scene *sc, std::map<hipStream_t, std::unique_ptr<Qu
     return *q;
 }
 
-// One closest-hit call on `stream`, q locked: the counters reset, `launch()` — the kernel, on q.counter and, with `counters`,
-// q.stats — and with stats the wait for it and what read_stats makes of it.
+// One closest-hit or scatter call on `stream`, q locked: the counters reset, `launch()` — the kernel, on q.counter and, with
+// `counters`, q.stats — and with stats the wait for it and what read_stats makes of it. `work_counter`: the kernel is a
+// persistent grid that claims its work from q.counter (false: the scatter step, whose grid is sized to the batch).
 template <class Launch>
-void run_counted(QueryScratch &q, bool counters, hipStream_t stream, rt_stats *stats, Launch launch) {
-    RT_HIP(hipMemsetAsync(q.counter, 0, sizeof(unsigned long long), stream));
+void run_counted(QueryScratch &q, bool counters, hipStream_t stream, rt_stats *stats, Launch launch, bool work_counter = true) {
+    if (work_counter) RT_HIP(hipMemsetAsync(q.counter, 0, sizeof(unsigned long long), stream));
     if (counters) RT_HIP(hipMemsetAsync(q.stats, 0, sizeof(StatsDev), stream));
     if (stats) RT_HIP(hipEventRecord(q.ev0, stream));
     RT_HIP(launch());
@@ -290,9 +294,73 @@ int features_staged(rt_scene *scene, FeatureJob job, const T *FeatureJob::*sourc
     return RT_OK;
 }
 
+// ---- scatter: one step of ray_color on a batch of hit records ----
+
+void check_scatter(const rt_scene *scene, const rt_scatter_params *p, const void *rays, const void *hits, const void *prev, uint64_t n,
+                   const void *out_recs, const void *out_next, bool device, const char *who) {
+    const char *fault = scatter_fault(scene, p, rays, hits, prev, n, out_recs, out_next, device);
+    RT_REQUIRE(!fault, RT_ERR_INVALID, std::string(who) + ": " + (fault ? fault : ""));
+}
+
+// Enqueue one scatter step on `stream` (the scene's device is current, n > 0); with stats, wait for it and fill them.
+void run_scatter(rt_scene *sc, const rt_query_ray *d_rays, const rt_hit *d_hits, const rt_scatter_rec *d_prev, uint64_t n,
+                 const rt_scatter_params *p, rt_scatter_rec *d_recs, rt_query_ray *d_next, hipStream_t stream, rt_stats *stats) {
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    QueryScratch &q = scratch_for(sc, sc->ss, stream);
+    std::lock_guard<std::mutex> lock(q.mu);
+    const bool counters = stats && (p->flags & RT_FLAG_COUNTERS);
+    ScatterArgs a{};
+    a.rays = d_rays; a.hits = d_hits; a.prev = d_prev; a.n = n;
+    std::memcpy(a.background, p->background, sizeof a.background);
+    a.t_min = p->t_min;
+    a.out_recs = d_recs; a.out_next = d_next;
+    a.n_materials = sc->n_materials;
+    a.stats = counters ? q.stats.p : nullptr;
+    run_counted(q, counters, stream, stats, [&] { return launch_scatter(sc->dev, a, counters, stream); }, false);      // (no persistent grid)
+}
+
 } // namespace
 
 extern "C" {
+
+int rt_scatter(rt_scene *scene, const rt_query_ray *rays, const rt_hit *hits, const rt_scatter_rec *prev, uint64_t n,
+               const rt_scatter_params *p, rt_scatter_rec *out_recs, rt_query_ray *out_next_rays, rt_stats *stats) {
+    return guarded([&]() -> int {
+        check_scatter(scene, p, rays, hits, prev, n, out_recs, out_next_rays, false, "rt_scatter");
+        if (n == 0) {
+            if (stats) std::memset(stats, 0, sizeof *stats);
+            return RT_OK;
+        }
+        DeviceGuard guard(scene->device);
+        DeviceBuf<rt_query_ray> d_rays(n), d_next(n);          // (after the guard: freed with the scene's device current)
+        DeviceBuf<rt_hit> d_hits(n);
+        DeviceBuf<rt_scatter_rec> d_prev(prev ? n : 1), d_recs(n);
+        RT_HIP(hipMemcpy(d_rays, rays, n * sizeof(rt_query_ray), hipMemcpyHostToDevice));
+        RT_HIP(hipMemcpy(d_hits, hits, n * sizeof(rt_hit), hipMemcpyHostToDevice));
+        if (prev) RT_HIP(hipMemcpy(d_prev, prev, n * sizeof(rt_scatter_rec), hipMemcpyHostToDevice));
+        // (poisoned: an unwritten record cannot pass for a result)
+        RT_HIP(hipMemset(d_recs, 0xFF, n * sizeof(rt_scatter_rec)));
+        RT_HIP(hipMemset(d_next, 0xFF, n * sizeof(rt_query_ray)));
+        run_scatter(scene, d_rays, d_hits, prev ? d_prev.p : nullptr, n, p, d_recs, d_next, nullptr, stats);
+        RT_HIP(hipMemcpy(out_recs, d_recs, n * sizeof(rt_scatter_rec), hipMemcpyDeviceToHost));
+        RT_HIP(hipMemcpy(out_next_rays, d_next, n * sizeof(rt_query_ray), hipMemcpyDeviceToHost));
+        return RT_OK;
+    });
+}
+
+int rt_scatter_device(rt_scene *scene, const rt_query_ray *d_rays, const rt_hit *d_hits, const rt_scatter_rec *d_prev, uint64_t n,
+                      const rt_scatter_params *p, rt_scatter_rec *d_out_recs, rt_query_ray *d_out_next_rays, void *hip_stream, rt_stats *stats) {
+    return guarded([&]() -> int {
+        check_scatter(scene, p, d_rays, d_hits, d_prev, n, d_out_recs, d_out_next_rays, true, "rt_scatter_device");
+        if (n == 0) {
+            if (stats) std::memset(stats, 0, sizeof *stats);
+            return RT_OK;
+        }
+        DeviceGuard guard(scene->device);
+        run_scatter(scene, d_rays, d_hits, d_prev, n, p, d_out_recs, d_out_next_rays, (hipStream_t)hip_stream, stats);
+        return RT_OK;
+    });
+}
 
 int rt_intersect(rt_scene *scene, const rt_query_ray *rays, uint64_t n_rays, uint32_t flags, rt_hit *out_hits, rt_stats *stats) {
     return guarded([&]() -> int {

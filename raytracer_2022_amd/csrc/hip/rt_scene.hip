@@ -176,6 +176,7 @@ int rt_scene_create(const rt_scene_desc *desc, rt_scene **out) {
         s.n_spheres = desc->n_spheres;
         s.n_moving_spheres = desc->n_moving_spheres;
         s.n_rects = desc->n_rects;
+        sc->n_materials = desc->n_materials;
         *out = sc.release();
         return RT_OK;
     });

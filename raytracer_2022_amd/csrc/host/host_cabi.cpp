@@ -231,6 +231,15 @@ int rtb_temporal_abi_sizes(uint32_t *out, uint32_t n) {
     return (int)count;
 }
 
+// sizeof of the rt_scatter* structures: rt_scatter_params, rt_scatter_rec (a list of its own, like the others: the general
+// list still ends with the query records).
+int rtb_scatter_abi_sizes(uint32_t *out, uint32_t n) {
+    const uint32_t sizes[] = {sizeof(rt_scatter_params), sizeof(rt_scatter_rec)};
+    const uint32_t count = sizeof(sizes) / sizeof(sizes[0]);
+    for (uint32_t i = 0; i < n && i < count; i++) out[i] = sizes[i];
+    return (int)count;
+}
+
 int rtb_write_ppm(const char *path, const uint8_t *rgb8, uint32_t width, uint32_t height) {
     return guarded([&]() -> int {
         FILE *f = path ? std::fopen(path, "wb") : nullptr;

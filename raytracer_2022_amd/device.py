@@ -53,6 +53,98 @@ def radiance_params(spp=1, background=(0.0, 0.0, 0.0), t_min=0.001, max_depth=50
     return p
 
 
+def scatter_params(background=(0.0, 0.0, 0.0), t_min=0.001, flags=0):
+    """rt_scatter_params: what a miss returns, the t_min of every next ray (main.rs:243), RT_FLAG_COUNTERS or 0."""
+    p = F.rt_scatter_params()
+    p.background[:] = [float(c) for c in background]
+    p.t_min, p.flags = t_min, flags
+    return p
+
+
+def _mix64(z):
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def path_key(seed, frame, pixel, sample):
+    """The stream key of a path (rt_math.h: path_key): seed, frame, absolute pixel index, sample → the uint64 state its draws
+    start from. rt_radiance keys sample s of a ray as path_key(ray.rng_state, 0, 0, s). Scalars give a Python int; arrays
+    (broadcast against each other, taken modulo 2^64) give a uint64 array."""
+    args = [np.asarray(a) for a in (seed, frame, pixel, sample)]
+    scalar = all(a.ndim == 0 for a in args)
+    s, f, p, k = (np.atleast_1d(a if a.dtype == np.uint64 else np.array([int(x) & 0xFFFFFFFFFFFFFFFF for x in a.ravel()], dtype=np.uint64).reshape(a.shape))
+                  for a in args)
+    one = np.uint64(1)
+    with np.errstate(over="ignore"):
+        h = _mix64(s + np.uint64(0x9E3779B97F4A7C15) * (f + one))
+        h = _mix64(h ^ (np.uint64(0xD1B54A32D192ED03) * (p + one)))
+        h = _mix64(h ^ (np.uint64(0x8CB92BA72F3D8DD7) * (k + one)))
+    return int(h[0]) if scalar else h
+
+
+def unwind(recs_per_step, depth_terminal=(0.0, 0.0, 0.0)):
+    """The radiance of the paths whose scatter records are `recs_per_step`: a list over the steps of SCATTER_REC_DTYPE arrays of n
+    entries each (entry i of every step belongs to path i; the steps chained with prev) → (n, 3) float64.
+    Path i has the live records r_0 .. r_{k-1} (SPECULAR or DIFFUSE) up to its first record that is not live; T is that
+    record's radiance, or `depth_terminal` when every step is live (the depth ran out: ray_color returns (0, 0, 0)). Then
+    L = T and, for j = k-1 .. 0, L = 0 + (weight_j * L) / pdf_j component-wise, in plain float64: the engine's tape step."""
+    steps = [np.ascontiguousarray(r, dtype=F.SCATTER_REC_DTYPE) for r in recs_per_step]
+    n = len(steps[0]) if steps else 0
+    live = [(r["status"] == F.RT_SCATTER_SPECULAR) | (r["status"] == F.RT_SCATTER_DIFFUSE) for r in steps]
+    L = np.empty((n, 3), dtype=np.float64)
+    L[:] = np.asarray(depth_terminal, dtype=np.float64)
+    alive = np.ones(n, dtype=bool)                         # alive[i] at step j: every record of path i before j is live
+    ended_at = np.full(n, len(steps), dtype=np.int64)
+    for j, lv in enumerate(live):
+        stop = alive & ~lv
+        ended_at[stop] = j
+        L[stop] = steps[j]["radiance"][stop]
+        alive &= lv
+    with np.errstate(all="ignore"):
+        for j in range(len(steps) - 1, -1, -1):
+            on = ended_at > j
+            w, p = steps[j]["weight"][on], steps[j]["pdf"][on]
+            L[on] = 0.0 + (w * L[on]) / p[:, None]
+    return L
+
+
+def radiance_by_steps(dev, rays, spp=1, max_depth=50, background=(0.0, 0.0, 0.0), t_min=0.001, on_step=None, want_stats=False):
+    """rt_radiance's sums by the caller-driven loop intersect → scatter(prev=...), bit for bit: `rays` (RADIANCE_RAY_DTYPE) →
+    (n, 3) float64 sums over spp samples, not divided by spp. Sample s of ray i starts from path_key(rays[i].rng_state, 0, 0, s);
+    a sample takes up to max_depth steps and the loop stops early when no entry is live; the steps are unwound (unwind) and the
+    samples added in order from 0. on_step(k, rays, hits, recs) is called after step k of every sample with the step's query rays,
+    hit records and scatter records (a caller's AOVs). want_stats=True adds a dict: rng_draws and light_pdf_tests summed over
+    the steps (the hits' words included) and rays, the live entries of the intersect calls."""
+    r = np.ascontiguousarray(rays, dtype=F.RADIANCE_RAY_DTYPE)
+    n = len(r)
+    total = np.zeros((n, 3), dtype=np.float64)
+    stats = {"rng_draws": 0, "light_pdf_tests": 0, "rays": 0}
+    for s in range(spp):
+        q = query_rays(r["origin"], r["direction"], r["time"], t_min, np.finfo(np.float64).max,
+                       path_key(r["rng_state"], 0, 0, s)) if n else np.zeros(0, dtype=F.QUERY_RAY_DTYPE)
+        steps, prev = [], None
+        live = np.ones(n, dtype=bool)
+        for k in range(max_depth):
+            if not live.any():
+                break
+            hits = dev.intersect(q)
+            out = dev.scatter(q, hits, background, t_min, prev, want_stats=want_stats)
+            recs, nxt = out[0], out[1]
+            if want_stats:
+                stats["rays"] += int(live.sum())
+                stats["rng_draws"] += int(hits["rng_draws"][live].sum()) + out[2].rng_draws
+                stats["light_pdf_tests"] += out[2].light_pdf_tests
+            if on_step is not None:
+                on_step(k, q, hits, recs)
+            steps.append(recs)
+            live = (recs["status"] == F.RT_SCATTER_SPECULAR) | (recs["status"] == F.RT_SCATTER_DIFFUSE)
+            q, prev = nxt, recs
+        with np.errstate(all="ignore"):
+            total += unwind(steps) if steps else np.zeros((n, 3))
+    return (total, stats) if want_stats else total
+
+
 def denoise_params(width, height, spp, n_iter=5, sigma_color=1.0, sigma_normal=0.3, sigma_depth=np.inf, sigma_albedo=0.3,
                    albedo_floor=1e-3, demodulate=True):
     """rt_denoise_params: the image, the divisor of the sums, the a-trous iterations and the edge-stopping sigmas (+inf
@@ -730,6 +822,37 @@ class DeviceScene:
         An rt_stats is filled (its counters with RT_FLAG_COUNTERS in params.flags)."""
         F.check(F.lib().rt_radiance_device(self._h, C.c_void_p(d_rays_ptr), n, C.byref(params), C.c_void_p(d_out_ptr),
                                            C.c_void_p(stream_ptr or 0), _ref(stats)))
+
+    def scatter(self, rays, hits, background=(0.0, 0.0, 0.0), t_min=0.001, prev=None, want_stats=False):
+        """rt_scatter: one step of ray_color between two world.hit calls for every entry: `rays` (QUERY_RAY_DTYPE) and `hits`
+        (HIT_DTYPE: intersect's records of those rays, or made-up ones) → (array of SCATTER_REC_DTYPE records, array of
+        QUERY_RAY_DTYPE next rays, ready for intersect) [, rt_stats with rng_draws and light_pdf_tests]. prev: the records of
+        the step before (an entry that was not live there is RT_SCATTER_ENDED); None: every entry is live."""
+        r = np.ascontiguousarray(rays, dtype=F.QUERY_RAY_DTYPE)
+        h = np.ascontiguousarray(hits, dtype=F.HIT_DTYPE)
+        if h.shape != r.shape or r.ndim != 1:
+            raise ValueError("one hit record per ray")
+        pv = None
+        if prev is not None:
+            pv = np.ascontiguousarray(prev, dtype=F.SCATTER_REC_DTYPE)
+            if pv.shape != r.shape:
+                raise ValueError("one previous record per ray")
+        recs = np.zeros(len(r), dtype=F.SCATTER_REC_DTYPE)
+        nxt = np.zeros(len(r), dtype=F.QUERY_RAY_DTYPE)
+        p = scatter_params(background, t_min, F.RT_FLAG_COUNTERS if want_stats else 0)
+        st = F.rt_stats()
+        F.check(F.lib().rt_scatter(self._h, _data(r), _data(h), _data(pv) if pv is not None else None, len(r), C.byref(p), _data(recs),
+                                   _data(nxt), C.byref(st)))
+        return (recs, nxt, st) if want_stats else (recs, nxt)
+
+    def scatter_device(self, d_rays_ptr, d_hits_ptr, n, d_recs_ptr, d_next_rays_ptr, params, d_prev_ptr=None, stream_ptr=None, stats=None):
+        """rt_scatter_device: device pointers in (n rt_query_ray and n rt_hit records, optionally n rt_scatter_rec of the step
+        before; room for n rt_scatter_rec and n rt_query_ray — the next rays may be the rays, the records `prev`), `params` an
+        rt_scatter_params (scatter_params), enqueued on `stream_ptr` (hipStream_t as int). stats=None returns after the enqueue;
+        an rt_stats makes the call synchronise the stream and fill it (its counters with RT_FLAG_COUNTERS in params.flags)."""
+        F.check(F.lib().rt_scatter_device(self._h, C.c_void_p(d_rays_ptr), C.c_void_p(d_hits_ptr), C.c_void_p(d_prev_ptr or 0), n,
+                                          C.byref(params), C.c_void_p(d_recs_ptr), C.c_void_p(d_next_rays_ptr),
+                                          C.c_void_p(stream_ptr or 0), _ref(stats)))
 
     def render_pixels(self, cam, params, ids, want_stats=False, kernel_times=False):
         """rt_render_pixels with host buffers: the render's sums of a list of (frame, pixel) ids (uint64, see pixel_ids; params.n_frames

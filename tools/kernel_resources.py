@@ -50,7 +50,7 @@ def main():
     only = [a[7:] for a in sys.argv[1:] if a.startswith("--only=")]       # e.g. --only=pt_wavefront_trace.hip
     rows = []
     with tempfile.TemporaryDirectory() as tmp:
-        for src in ("pt_wavefront.hip", "pt_wavefront_shade.hip", "pt_wavefront_trace.hip", "pt_kernel.hip", "pt_query.hip", "pt_features.hip", "pt_features_specular.hip", "pt_denoise.hip", "pt_temporal.hip", "pt_adaptive.hip", "pt_order.hip",
+        for src in ("pt_wavefront.hip", "pt_wavefront_shade.hip", "pt_wavefront_trace.hip", "pt_kernel.hip", "pt_query.hip", "pt_features.hip", "pt_features_specular.hip", "pt_denoise.hip", "pt_temporal.hip", "pt_adaptive.hip", "pt_order.hip", "pt_scatter.hip",
                     "rt_scene.hip", "rt_render.hip", "rt_query.hip", "rt_post.hip", "rt_debug.hip"):
             if only and src not in only:
                 continue
