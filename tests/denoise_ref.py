@@ -89,6 +89,18 @@ def buffers(W, H, spp=4, seed=1, hostile=True, nan_albedo=True):
     return sums, feat
 
 
+# ---- the parameter sets of the switch tests: keywords of denoise_params, and the sample count --------------------------------
+INF = math.inf
+SWITCHES = {
+    "n_iter 0": dict(n_iter=0), "n_iter 1": dict(n_iter=1), "no demodulation": dict(demodulate=False),
+    "colour off": dict(sigma_color=INF), "normal off": dict(sigma_normal=INF), "depth off": dict(sigma_depth=INF),
+    "depth on": dict(sigma_depth=2.0), "depth alone off": dict(sigma_depth=INF, sigma_color=0.5, sigma_normal=0.2, sigma_albedo=0.2),
+    "albedo off": dict(sigma_albedo=INF), "all off": dict(sigma_color=INF, sigma_normal=INF, sigma_depth=INF, sigma_albedo=INF),
+    "tight": dict(sigma_color=0.3, sigma_normal=0.05, sigma_depth=0.1, sigma_albedo=0.01, albedo_floor=0.3),
+    "spp 1": dict(spp=1), "spp 7, 3 iterations": dict(spp=7, n_iter=3),
+}
+
+
 # ---- row lists longer than the row kernel's block ---------------------------------------------------------------------------
 # dn_rows is ONE workgroup of 1024 threads striding over the list: thread t takes entries t, t + 1024, t + 2048, ... So a
 # thread's second trip starts at a height of 1025 (one entry on it) and 2500 rows give every thread two or three entries.

@@ -3,7 +3,6 @@
 `restate` (tests/denoise_ref.py) is include/rt2022.h's definition once more in numpy; the kernels (built with
 -ffp-contract=off) must give the same doubles. Every comparison is on the uint64 view, the NaN patterns first."""
 import ctypes as C
-import math
 
 import numpy as np
 import pytest
@@ -11,7 +10,7 @@ import pytest
 from raytracer_2022_amd import _ffi as F
 
 from compare import assert_same_bits
-from denoise_ref import LONG_HEIGHTS, LONG_W, buffers, display, long_row_lists, restate
+from denoise_ref import LONG_HEIGHTS, LONG_W, SWITCHES, buffers, display, long_row_lists, restate
 from gpu_first import torch_first  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -51,18 +50,7 @@ def test_footprint_larger_than_the_image(rt, W, H):
     check(rt, sums, feat, big, what="16 iterations")
 
 
-# ---- switches --------------------------------------------------------------------------------------------------------------
-INF = math.inf
-SWITCHES = {
-    "n_iter 0": dict(n_iter=0), "n_iter 1": dict(n_iter=1), "no demodulation": dict(demodulate=False),
-    "colour off": dict(sigma_color=INF), "normal off": dict(sigma_normal=INF), "depth off": dict(sigma_depth=INF),
-    "depth on": dict(sigma_depth=2.0), "depth alone off": dict(sigma_depth=INF, sigma_color=0.5, sigma_normal=0.2, sigma_albedo=0.2),
-    "albedo off": dict(sigma_albedo=INF), "all off": dict(sigma_color=INF, sigma_normal=INF, sigma_depth=INF, sigma_albedo=INF),
-    "tight": dict(sigma_color=0.3, sigma_normal=0.05, sigma_depth=0.1, sigma_albedo=0.01, albedo_floor=0.3),
-    "spp 1": dict(spp=1), "spp 7, 3 iterations": dict(spp=7, n_iter=3),
-}
-
-
+# ---- switches (denoise_ref.SWITCHES) ---------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", list(SWITCHES))
 def test_switches(rt, name):
     W, H = 70, 9

@@ -12,24 +12,11 @@ from raytracer_2022_amd import _ffi as F
 
 import denoise_dual_ref as R
 from compare import assert_same_bits
-from denoise_dual_ref import restate_dual
-from denoise_ref import LONG_HEIGHTS, LONG_W, buffers, long_row_lists, restate as restate_single
+from denoise_dual_ref import ALL_OFF, SWITCHES, halves, restate_dual
+from denoise_ref import LONG_HEIGHTS, LONG_W, long_row_lists, restate as restate_single
 from gpu_first import torch_first  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-def halves(W, H, spp=4, seed=1, hostile=True, nan_albedo=True):
-    """Two halves of random buffers. hostile: each half has NaN, 1e30 and negative sums, zero / NaN albedo and all-zero miss
-    records of its own, and the top-left quarter of A's are B's as well (faults in one half only and in both)."""
-    sa, fa = buffers(W, H, spp=spp, seed=seed, hostile=hostile, nan_albedo=nan_albedo)
-    sb, fb = buffers(W, H, spp=spp, seed=seed + 100, hostile=hostile, nan_albedo=nan_albedo)
-    if hostile:
-        odd = ~np.isfinite(sa) | (sa == 1e30) | (sa == -3.0)
-        odd[H // 2:], odd[:, W // 2:] = False, False
-        sb[odd] = sa[odd]
-        fb[: H // 4, : W // 4] = fa[: H // 4, : W // 4]
-    return sa, sb, fa, fb
 
 
 def check(rt, h, p, q, rows=None, what=""):
@@ -73,17 +60,6 @@ def test_footprint_larger_than_the_image(rt, W, H):
 
 
 # ---- switches --------------------------------------------------------------------------------------------------------------
-INF = math.inf
-ALL_OFF = dict(sigma_color=INF, sigma_normal=INF, sigma_depth=INF, sigma_albedo=INF)
-SWITCHES = {
-    "colour off": dict(sigma_color=INF), "normal off": dict(sigma_normal=INF), "depth off": dict(sigma_depth=INF),
-    "depth on": dict(sigma_depth=2.0), "albedo off": dict(sigma_albedo=INF), "all off": dict(ALL_OFF),
-    "n_iter 0": dict(n_iter=0), "n_iter 0, no prefilter": dict(n_iter=0, var_iter=0), "n_iter 1": dict(n_iter=1),
-    "no prefilter": dict(var_iter=0), "no demodulation": dict(demodulate=False), "spp 1": dict(spp=1), "spp 7": dict(spp=7, n_iter=3),
-    "tight": dict(sigma_color=0.5, sigma_normal=0.05, sigma_depth=0.1, sigma_albedo=0.01, albedo_floor=0.3, var_floor=1e-2, var_iter=2),
-}
-
-
 @pytest.mark.parametrize("name", list(SWITCHES))
 def test_switches(rt, name):
     W, H = 70, 9
