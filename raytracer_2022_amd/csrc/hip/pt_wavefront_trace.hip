@@ -60,6 +60,8 @@ struct TLane {
     //   bits 25-30 (kOrderMask) the ray's side of the child order: bit 31 - k is set where a node of order k has its right child
     //              nearer to this ray (k = 1 + 2 * axis + sense, host/scene_check.hpp) — flags << k then has it in the sign bit,
     //              and a node of order 0 never does (bit 31 stays clear); set wherever inv is (t_flags)
+    //   kNaN       this ray has accepted a NaN distance (t_accept): for the rest of it kPlain and the order bits stay clear
+    //   kAgain     ... and had been visiting nodes in its own order until then: the ray is traversed once more (OP_SHADE)
     uint32_t flags;
 };
 
@@ -70,22 +72,24 @@ struct TStack {
     RT_DEV uint32_t pop(TLane &L) { if (L.sp > 0) { L.sp--; return col[L.sp * WG]; } return REF_EMPTY; }
 };
 
-constexpr uint32_t kPlain = 1u, kHasRay = 2u, kSubFound = 4u, kNeed64 = 8u, kOrderMask = 0x7E000000u;
+constexpr uint32_t kPlain = 1u, kHasRay = 2u, kSubFound = 4u, kNeed64 = 8u, kNaN = 16u, kAgain = 32u, kOrderMask = 0x7E000000u;
 RT_DEV void t_flag(TLane &L, uint32_t bit, bool on) { L.flags = on ? (L.flags | bit) : (L.flags & ~bit); asm volatile("" : "+v"(L.flags)); }
 RT_DEV bool t_finite(double x) { return (rtm::d2u(x) & 0x7FF0000000000000ull) != 0x7FF0000000000000ull; }
-// The fast node step applies (see there): every 1/d finite and non-zero, origin finite, boxes plain.
-// ... and the order bits (`order`: kOrderMask where the instance orders children and the tuning word lets it, else 0). Any choice is a valid one — the
-// closest hit does not depend on the order of the visits inside a subtree without media, ties go by rank (t_accept) — so a
-// zero or NaN component simply counts as pointing up its axis.
+// The fast node step applies (see there): every 1/d finite and non-zero, origin finite, boxes plain — and no NaN accepted so far.
+// ... and the order bits (`order`: kOrderMask where the instance orders children and the tuning word lets it, else 0). As long
+// as no accepted distance is a NaN any choice is a valid one — the closest hit does not depend on the order of the visits inside
+// a subtree without media, ties go by rank (t_accept) — so a zero or NaN component simply counts as pointing up its axis. A ray
+// that has accepted a NaN (kNaN) has no order bits: from then on the LAST leaf visited wins (see t_accept).
 RT_DEV void t_flags(TLane &L, bool boxes_plain, uint32_t order) {
-    const bool plain = boxes_plain && t_finite(L.inv.x) && t_finite(L.inv.y) && t_finite(L.inv.z) && L.inv.x != 0.0 && L.inv.y != 0.0 &&
+    const uint32_t sane = ((L.flags / kNaN) & 1u) - 1u;             // (all ones while no NaN has been accepted)
+    const bool plain = boxes_plain && sane != 0u && t_finite(L.inv.x) && t_finite(L.inv.y) && t_finite(L.inv.z) && L.inv.x != 0.0 && L.inv.y != 0.0 &&
               L.inv.z != 0.0 && t_finite(L.cur.o.x) && t_finite(L.cur.o.y) && t_finite(L.cur.o.z);
     uint32_t m = 0;
     if (order) {                                                  // (kOrderMask or 0: one scalar register, known 0 where nothing is ordered)
 #pragma unroll
         for (int i = 0; i < 3; i++) m |= (L.inv[i] < 0.0 ? 0x40000000u : 0x20000000u) >> (2 * i);
     }
-    L.flags = (L.flags & ~kOrderMask) | (m & order);
+    L.flags = (L.flags & ~kOrderMask) | (m & order & sane);
     t_flag(L, kPlain, plain);
 }
 // A node's children as a kernel takes them from the last 16 bytes of its record {left, right, push ref, left}: the last two
@@ -166,8 +170,30 @@ RT_DEV double t_hi(const TLane &L) { return L.med_ref ? L.sub_closest : L.closes
 // ORDER (the kernels that may visit a node's right child first): the reference accepts t == t_max, so among candidates of exactly
 // equal t the one it visits LAST wins. Visited in another order, the same one wins when a tie between two different primitives
 // goes to the higher rank in the reference's depth-first order (SceneDev::prim_rank; read here only, in a branch next to never taken).
+//
+// A NaN distance. sphere_t, rect_t and the box's faces accept one: `root < t_min || t_max < root` is false for it (inf - inf under
+// the root of a sphere 1e200 away, 0 / 0 for a ray lying in a rect's plane or a MovingSphere with time0 == time1, any NaN
+// component of the ray). With a NaN for its upper end the window rejects nothing any more and AABB::hit culls nothing
+// (`t1 < t_max` and `t_max <= t_min` are false): every sphere and rect VISITED from then on accepts, and the one visited last
+// wins — the result depends on the order of the visits, and on entering every node. So from the first NaN on the lane takes the
+// reference's own steps only: no fast node step (its v_min_f64 drops a NaN operand where the reference keeps it), no order bits
+// (kNaN clears both, for good). A lane that had order bits until then may have visited other leaves than the reference up to
+// this point: it drops its stack and is traversed once more from the root (kAgain; OP_SHADE), in the reference's order and with
+// its steps from the start. A medium's sub-query is treated alike. Costs an accepted hit one compare; rays that meet no NaN
+// nothing else.
+// `tainted` (the box arm): a box's own closest-so-far may have been a NaN between two of its faces — a face in whose plane the ray
+// lies, 0 / 0 — and the face accepted after it then ignored the window: a finite t, possibly beyond the closest hit, which wins
+// all the same. Whether it does depends on what was visited before, like a NaN itself: a lane with order bits is taken again.
+// Only a ray that is not plain can meet it (finite o, finite non-zero d and finite corners — check_scene — give finite or
+// infinite face distances), so the arm passes `not plain`, and no box test pays for it.
 template <bool ORDER>
-RT_DEV void t_accept(const SceneDev &s, TLane &L, double t, uint32_t face, uint32_t mat_word) {
+RT_DEV void t_accept(const SceneDev &s, TLane &L, double t, uint32_t face, uint32_t mat_word, bool tainted = false) {
+    const bool nan = t != t;
+    if (nan || tainted) {
+        const bool again = ORDER && (L.flags & kOrderMask) != 0u;
+        if (nan || again) L.flags = (L.flags & ~(kPlain | kOrderMask)) | kNaN | (again ? kAgain : 0u);
+        if (again) { L.sp = 0; return; }                              // (the arm's T_NEXT finds the stack empty: OP_SHADE)
+    }
     if (L.med_ref) { L.sub_closest = t; t_flag(L, kSubFound, true); return; }
     if (ORDER && t == L.closest && L.win_leaf != REF_EMPTY && ((L.win_leaf ^ L.top) << 1) != 0u && s.prim_rank) {
         const uint32_t mine = s.prim_rank[s.prim_rank[RT_REF_KIND(L.top) & 7u] + RT_REF_INDEX(L.top)];
@@ -685,7 +711,10 @@ __global__ void __launch_bounds__(trace_wg(TABLE), trace_waves_per_simd(STACK, S
                     const double lo = sorted ? t0 : __builtin_fmin(t0, t1), hi = sorted ? t1 : __builtin_fmax(t0, t1);
                     // fmax / fmin of a value that is not an arithmetic result of the same block first "canonicalises" it (a
                     // v_max_f64 x, x) — per node step, for the window's two ends, which never change in here. Written as the
-                    // instruction fmax / fmin compile to; no operand is a NaN on this path (see above), so it is the same value.
+                    // instruction fmax / fmin compile to. No operand is a NaN on this path, so it is the same value: the slab products
+                    // are none for a plain ray (see above), the lower end is t_min or a boundary distance + 0.0001, and a lane whose
+                    // upper end — the closest hit — has become a NaN is no longer plain (t_accept: v_min_f64 would return the OTHER
+                    // operand for it and cull by the slabs alone, where the reference's `t1 < t_max ? t1 : t_max` keeps the NaN).
                     asm("v_max_f64 %0, %1, %2" : "=v"(tmn) : "v"(i == 0 ? tlo_c : tmn), "v"(lo));
                     asm("v_min_f64 %0, %1, %2" : "=v"(tmx) : "v"(i == 0 ? thi_c : tmx), "v"(hi));
                 }
@@ -885,7 +914,7 @@ __global__ void __launch_bounds__(trace_wg(TABLE), trace_waves_per_simd(STACK, S
             double t;
             uint32_t face = 0;
             bool h = t_box(b0.x, b0.y, b1.x, b1.y, b2.x, b2.y, L.cur, L.t_lo, t_hi(L), t, face);
-            if (h) t_accept<kOrder>(s, L, t, face, mat_word);
+            if (h) t_accept<kOrder>(s, L, t, face, mat_word, (L.flags & kPlain) == 0u);
             T_NEXT();
             }
         } else if ((FEAT & kFeatVolumes) && best == OP_MEDIUM) {      // ConstantMedium::hit, constantmedium.rs:49-83
@@ -1064,7 +1093,10 @@ __global__ void __launch_bounds__(trace_wg(TABLE), trace_waves_per_simd(STACK, S
         } else if (best == OP_SHADE) {
             // OP_SHADE here = "this lane's traversal is finished (or it has no ray yet)":
             // publish the winner, then pull the next ray from the block's list.
-            if (L.flags & kHasRay) {
+            // (kAgain: the ray accepted a NaN distance after visits in another order than the reference's — t_accept. Nothing of it
+            // is published; the lane takes the same list entry once more, kNaN still set: literal steps, the reference's order)
+            const bool again = kOrder && (L.flags & kAgain) != 0u;
+            if ((L.flags & kHasRay) && !again) {
                 uint32_t slot = L.slot;
                 bool found = L.win_leaf != REF_EMPTY;
                 uint32_t kind = SK_MISS;
@@ -1077,11 +1109,11 @@ __global__ void __launch_bounds__(trace_wg(TABLE), trace_waves_per_simd(STACK, S
                 if (L.rng.draws) { pv.store_rng(slot, L.rng.s); cnt.draws(L.rng.draws); }
                 t_flag(L, kHasRay, false);
             }
-            const unsigned long long m = wballot(true);
+            const unsigned long long m = wballot(!again);
             const int leader = __ffsll((long long)m) - 1;
             uint32_t need = (uint32_t)__popcll(m);
             uint32_t rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-            uint32_t entry_idx = 0xFFFFFFFFu;                         // index into pool.list of the entry this lane takes
+            uint32_t entry_idx = again ? L.entry : 0xFFFFFFFFu;       // index into pool.list of the entry this lane takes
             const u32x4 cs_now = *cs;
             uint32_t ch_base = cs_now.x, ch_n = cs_now.y, ch_taken = cs_now.z;
             bool drained = cs_now.w != 0;
@@ -1115,6 +1147,7 @@ __global__ void __launch_bounds__(trace_wg(TABLE), trace_waves_per_simd(STACK, S
                 Ray wr = pv.load_ray(L.slot, rs);
                 L.tm = wr.tm;
                 L.rng = Rng(rs);
+                L.flags &= (kOrder && (L.flags & kAgain)) ? ~kAgain : ~(kAgain | kNaN);   // (a ray taken again keeps its kNaN)
                 t_set_cur(L, XRay{wr.orig, wr.dir}, boxes_plain, order_on);
                 T_SLABS();
                 if (FEAT & kFeatMovers) L.stash_level = 0xFFFFFFFFu;

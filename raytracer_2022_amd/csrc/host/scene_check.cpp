@@ -48,13 +48,17 @@ struct Validator {
         if (kind >= RT_KIND_TRANSLATE && kind <= RT_KIND_ZOOM)
             RT_REQUIRE(d.xforms[idx].kind == kind, RT_ERR_INVALID, std::string(where) + ": mover ref kind does not match its record");
     }
-    // Node boxes as the reference builds them (min / max of real coordinates): finite and ordered.
+    // Node boxes as the reference builds them (min / max of real coordinates): finite and ordered. And the corners of every
+    // Boxes object finite: a plain ray then meets no NaN between two faces of one (wf_trace: t_accept, `tainted`).
     bool boxes_plain() const {
         for (uint32_t i = 0; i < d.n_nodes; i++)
             for (int a = 0; a < 3; a++) {
                 double lo = d.nodes[i].bmin[a], hi = d.nodes[i].bmax[a];
                 if (!(std::isfinite(lo) && std::isfinite(hi) && lo <= hi)) return false;
             }
+        for (uint32_t i = 0; i < d.n_boxes; i++)
+            for (int a = 0; a < 3; a++)
+                if (!(std::isfinite(d.boxes[i].p0[a]) && std::isfinite(d.boxes[i].p1[a]))) return false;
         return true;
     }
     void check_mat(uint32_t mat, const char *where) const {

@@ -12,7 +12,7 @@ struct SceneFacts {
     uint32_t stack_need;               // stack entries a traversal needs (<= kStackLarge)
     int32_t xdepth;                    // deepest nesting of movers (<= RT_MAX_XFORM_DEPTH)
     bool general_boundaries;           // some medium boundary is more than a primitive under movers
-    bool boxes_plain;                  // every node box finite with min <= max: the short node step applies
+    bool boxes_plain;                  // every node box finite with min <= max, every Boxes corner finite: the short node step applies
     unsigned features;                 // kFeat* arms of the traversal kernel the scene can reach
 };
 // Every index, ref, chain and cycle of `d` checked: throws Fail (RT_ERR_INVALID, RT_ERR_UNSUPPORTED) or returns the facts.
