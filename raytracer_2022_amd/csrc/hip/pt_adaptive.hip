@@ -3,7 +3,8 @@
 //
 // A plan turns an error map into a list of (frame, pixel) ids for rt_render_pixels*: pixel b gets units[b] entries, one per
 // unit of `spp` samples, at offsets[b] of the list — an exclusive prefix sum of the units over the image. The scan is the one
-// kernel here that is more than a lane per pixel. It takes three launches on the caller's workspace (adaptive_layout):
+// kernel here that is more than a lane per pixel. It takes three launches on the caller's workspace (adaptive_layout of
+// host/post_check.hpp; a row list has been through the row kernel of pt_rows.hip before them, its count is beside the totals):
 //   ad_totals   a workgroup per tile of kAdTile pixels: the tile's units, summed, into totals[tile]
 //   ad_offsets  ONE workgroup: the exclusive scan of the tile totals in place, kAdBlock at a time with a running carry,
 //               and the grand total behind them
@@ -19,6 +20,7 @@
 //   ad_resolve  a lane per pixel: accumulator -> sums of spp_out samples
 //   ad_merge_features / ad_resolve_features  the same two for rt_feature records: eight doubles a pixel, moved as four
 //               16-byte pieces, every field linear (the sample count is the radiance merge's acc_n)
+#include "../host/post_check.hpp"
 #include "pt_device.h"
 
 namespace rt2022 {
@@ -28,6 +30,7 @@ namespace {
 constexpr int kAdBlock = 256;          // 4 waves
 constexpr int kAdPer = 4;              // consecutive pixels per thread
 constexpr uint32_t kAdTile = kAdBlock * kAdPer;
+static_assert(kAdTile == kAdaptiveTile, "the layout's tiles (host/post_check.hpp) are the scan's");
 
 #define AD_DEV __device__ __forceinline__
 
@@ -187,24 +190,12 @@ __global__ void __launch_bounds__(kAdBlock) ad_resolve_features(const double2 *a
 
 } // namespace
 
-AdaptiveLayout adaptive_layout(uint32_t width, uint32_t height) {
-    const uint64_t n = (uint64_t)width * height, n_tiles = (n + kAdTile - 1) / kAdTile;
-    AdaptiveLayout l;
-    l.n_tiles = n_tiles;
-    l.totals = 0;
-    l.bad_rows = ((n_tiles + 1) * sizeof(unsigned long long) + 15u) / 16u * 16u;
-    l.inv_rows = l.bad_rows + 16u;
-    l.bytes = l.inv_rows + ((uint64_t)height * sizeof(uint32_t) + 15u) / 16u * 16u;
-    return l;
-}
-
 hipError_t launch_adaptive_plan(const AdaptivePlanArgs &p, hipStream_t stream) {
     const AdaptiveLayout l = adaptive_layout(p.width, p.height);
     const uint64_t n = (uint64_t)p.width * p.height;
     unsigned long long *const totals = reinterpret_cast<unsigned long long *>(p.ws + l.totals);
-    uint32_t *const bad = reinterpret_cast<uint32_t *>(p.ws + l.bad_rows);
+    const uint32_t *const bad = reinterpret_cast<const uint32_t *>(p.ws + l.rows.bad);
     hipError_t e;
-    if (p.rows && (e = launch_row_list_check(p.rows, p.height, reinterpret_cast<uint32_t *>(p.ws + l.inv_rows), bad, stream)) != hipSuccess) return e;
     hipLaunchKernelGGL(ad_totals, dim3((unsigned)l.n_tiles), dim3(kAdBlock), 0, stream, p.err, n, p.scale, p.max_units, totals);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL(ad_offsets, dim3(1), dim3(kAdBlock), 0, stream, totals, l.n_tiles);

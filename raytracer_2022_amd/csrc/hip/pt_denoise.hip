@@ -1,10 +1,8 @@
 // pt_denoise.hip — edge-avoiding a-trous denoiser over a render's sums and its feature buffers (rt_denoise*,
 // include/rt2022.h has the definition: every + - * / below is one of its operations, in its order; -ffp-contract=off).
 //
-// Three kernels, all on the caller's workspace (denoise_layout):
-//   dn_rows     one workgroup: the inverse of the caller's row list (image row -> buffer row) and the count of ids that
-//               are out of range or repeated. An id's slot is written by plain stores and read back behind a barrier: the
-//               entry that lost the race to a repeated id finds another's index there. The count is the only atomic.
+// Two kernels on the caller's workspace (denoise_layout, host/post_check.hpp). A row list has been through the row kernel of
+// pt_rows.hip before them: its map is a.inv. The pixel front end and the tap loop are pt_post.hpp's.
 //   dn_prepare  buffer order -> image order: NaN -> 0, / sp, demodulation; writes the packed guides and colour plane 0
 //               (with no iteration: the output).
 //   dn_atrous   one launch per iteration, plane k & 1 -> plane ~k & 1; the last one remodulates and writes the output in
@@ -27,21 +25,17 @@
 // prefilter's v are planes of single doubles. A colour tap is five 16-byte loads and one 8-byte load (88 bytes, all used;
 // a wave reads 5 x 1 KiB + 512 B contiguous) and two divisions; a prefilter tap is three 16-byte and two 8-byte loads
 // (64 bytes) and one division. The centre pixel stays in registers.
-#include "pt_device.h"
+#include "../host/post_check.hpp"
+#include "pt_post.hpp"
 
 namespace rt2022 {
 
 namespace {
 
-constexpr int kDnBlock = 256;          // 4 waves: rows y .. y+3 of a 64-pixel column strip
-constexpr uint32_t kDnNoRow = 0xFFFFFFFFu;
-
-#define DN_DEV __device__ __forceinline__
-
 struct DnPixel { double e[3], n[3], a[3], z; };
 
 // The pixel at index i of five planes `stride` apart (guides: g, colour: c).
-DN_DEV DnPixel dn_load(const double2 *g, const double2 *c, uint64_t stride, uint64_t i) {
+POST_DEV DnPixel dn_load(const double2 *g, const double2 *c, uint64_t stride, uint64_t i) {
     const double2 g0 = g[i], g1 = g[stride + i], g2 = g[2 * stride + i], c0 = c[i], c1 = c[stride + i];
     DnPixel p;
     p.n[0] = g0.x; p.n[1] = g0.y; p.n[2] = g1.x; p.z = g1.y; p.a[0] = g2.x; p.a[1] = g2.y;
@@ -49,65 +43,32 @@ DN_DEV DnPixel dn_load(const double2 *g, const double2 *c, uint64_t stride, uint
     return p;
 }
 
-DN_DEV double dn_dist(const double p[3], const double q[3]) {
+POST_DEV double dn_dist(const double p[3], const double q[3]) {
     const double d0 = p[0] - q[0], d1 = p[1] - q[1], d2 = p[2] - q[2];
     return (d0 * d0 + d1 * d1) + d2 * d2;
 }
 
-constexpr double dn_h(int t) { return (t == 0 || t == 4) ? 1.0 / 16.0 : t == 2 ? 3.0 / 8.0 : 1.0 / 4.0; }
-
-DN_DEV double dn_modulation(const DenoiseArgs &a, double albedo) {
-    return a.demodulate ? (albedo > a.albedo_floor ? albedo : a.albedo_floor) : 1.0;
-}
-
-// The workgroup's pixel strip: columns x0 .. x0+63, rows y0 .. y0+3.
-DN_DEV void dn_block_origin(const DenoiseArgs &a, uint32_t &x0, uint32_t &y0) {
-    const uint32_t nbx = (a.width + 63u) / 64u;
-    const uint32_t by = blockIdx.x / nbx, bx = blockIdx.x - by * nbx;
-    x0 = bx * 64u; y0 = by * 4u;
-}
-
-__global__ void __launch_bounds__(1024) dn_rows(const uint32_t *rows, uint32_t height, uint32_t *inv, uint32_t *bad) {
-    for (uint32_t i = threadIdx.x; i < height; i += blockDim.x) inv[i] = kDnNoRow;
-    if (threadIdx.x == 0) *bad = 0u;
-    __syncthreads();
-    uint32_t n_bad = 0;
-    for (uint32_t i = threadIdx.x; i < height; i += blockDim.x) {
-        const uint32_t g = rows[i];
-        if (g < height) inv[g] = i; else n_bad++;
-    }
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < height; i += blockDim.x) {
-        const uint32_t g = rows[i];
-        if (g < height && inv[g] != i) n_bad++;
-    }
-    if (n_bad) atomicAdd(bad, n_bad);
-}
-
-__global__ void __launch_bounds__(kDnBlock) dn_prepare(const DenoiseArgs a, double2 *guides, double2 *colour, const uint32_t *inv, bool final) {
-    uint32_t x0, y0;
-    dn_block_origin(a, x0, y0);
-    const uint32_t x = x0 + (threadIdx.x & 63u), y = y0 + (threadIdx.x >> 6);
+__global__ void __launch_bounds__(kPostBlock) dn_prepare(const DenoiseArgs a, double2 *guides, double2 *colour, bool final) {
+    uint32_t x, y;
+    post_pixel(a.width, x, y);
     if (x >= a.width || y >= a.height) return;
     const uint64_t n = (uint64_t)a.width * a.height, i = (uint64_t)y * a.width + x;
-    const uint64_t src = (uint64_t)(inv ? inv[y] : y) * a.width + x;
-    const double2 *f = reinterpret_cast<const double2 *>(a.feat + src);
-    const double2 f0 = f[0], f1 = f[1], f2 = f[2], f3 = f[3];           // {a0, a1} {a2, n0} {n1, n2} {depth, hits}
-    const double alb[3] = {f0.x / a.sp, f0.y / a.sp, f1.x / a.sp};
-    double e[3], m[3];
+    const uint64_t src = post_src(a.inv, a.width, x, y);
+    const PostRecord r = post_load(a.feat, src);
+    double alb[3], e[3], m[3];
+    post_albedo(r, a.sp, alb);
 #pragma unroll
     for (int c = 0; c < 3; c++) {
-        const double s = a.sum[3 * src + c];
-        m[c] = dn_modulation(a, alb[c]);
-        e[c] = ((s != s ? 0.0 : s) / a.sp) / m[c];
+        m[c] = post_modulation(a.demodulate, a.albedo_floor, alb[c]);
+        e[c] = post_colour(a.sum[3 * src + c], a.sp, m[c]);
     }
     if (final) {                                           // no iteration: e0 goes straight back out
 #pragma unroll
         for (int c = 0; c < 3; c++) a.out[3 * src + c] = (e[c] * m[c]) * a.sp;
         return;
     }
-    guides[i] = make_double2(f1.y / a.sp, f2.x / a.sp);
-    guides[n + i] = make_double2(f2.y / a.sp, f3.x / a.sp);
+    guides[i] = make_double2(r.f1.y / a.sp, r.f2.x / a.sp);
+    guides[n + i] = make_double2(r.f2.y / a.sp, r.f3.x / a.sp);
     guides[2 * n + i] = make_double2(alb[0], alb[1]);
     colour[i] = make_double2(e[0], e[1]);
     colour[n + i] = make_double2(e[2], alb[2]);
@@ -116,41 +77,31 @@ __global__ void __launch_bounds__(kDnBlock) dn_prepare(const DenoiseArgs a, doub
 // One iteration at step s. LAST: the result is remodulated and written to a.out in buffer order instead of the other
 // colour plane.
 template <bool LAST>
-__global__ void __launch_bounds__(kDnBlock) dn_atrous(const DenoiseArgs a, const double2 *guides, const double2 *cin, double2 *cout,
-                                                      const uint32_t *inv, uint32_t s, double inv_c) {
-    uint32_t x0, y0;
-    dn_block_origin(a, x0, y0);
-    const uint32_t x = x0 + (threadIdx.x & 63u), y = y0 + (threadIdx.x >> 6);
+__global__ void __launch_bounds__(kPostBlock) dn_atrous(const DenoiseArgs a, const double2 *guides, const double2 *cin, double2 *cout, uint32_t s,
+                                                        double inv_c) {
+    uint32_t x, y;
+    post_pixel(a.width, x, y);
     if (x >= a.width || y >= a.height) return;
-    const int64_t W = a.width, H = a.height, step = s;
-    const uint64_t n = (uint64_t)a.width * a.height;
-    const DnPixel p = dn_load(guides, cin, n, (uint64_t)y * a.width + x);
+    const uint64_t n = (uint64_t)a.width * a.height, ip = (uint64_t)y * a.width + x;
+    const DnPixel p = dn_load(guides, cin, n, ip);
     double sw = 0.0, sv[3] = {0.0, 0.0, 0.0};
+    dn_for_taps(x, y, s, a.width, a.height, [&](double h, uint64_t iq) {
+        const DnPixel q = dn_load(guides, cin, n, iq);
+        const double dc = dn_dist(p.e, q.e), dn = dn_dist(p.n, q.n), da = dn_dist(p.a, q.a), dz = p.z - q.z;
+        const double den = (((1.0 + dc * inv_c) * (1.0 + dn * a.inv_n)) * (1.0 + (dz * dz) * a.inv_z)) * (1.0 + da * a.inv_a);
+        const double w = h / den;
+        sw = sw + w;
 #pragma unroll
-    for (int j = -2; j <= 2; j++) {
-        const int64_t qy = (int64_t)y + (int64_t)j * step;
-#pragma unroll
-        for (int i = -2; i <= 2; i++) {
-            const int64_t qx = (int64_t)x + (int64_t)i * step;
-            if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
-            const DnPixel q = dn_load(guides, cin, n, (uint64_t)qy * a.width + (uint64_t)qx);
-            const double dc = dn_dist(p.e, q.e), dn = dn_dist(p.n, q.n), da = dn_dist(p.a, q.a), dz = p.z - q.z;
-            const double den = (((1.0 + dc * inv_c) * (1.0 + dn * a.inv_n)) * (1.0 + (dz * dz) * a.inv_z)) * (1.0 + da * a.inv_a);
-            const double w = (dn_h(j + 2) * dn_h(i + 2)) / den;
-            sw = sw + w;
-#pragma unroll
-            for (int c = 0; c < 3; c++) sv[c] = sv[c] + w * q.e[c];
-        }
-    }
+        for (int c = 0; c < 3; c++) sv[c] = sv[c] + w * q.e[c];
+    });
     const double e[3] = {sv[0] / sw, sv[1] / sw, sv[2] / sw};
     if (LAST) {
-        const uint64_t dst = (uint64_t)(inv ? inv[y] : y) * a.width + x;
+        const uint64_t dst = post_src(a.inv, a.width, x, y);
 #pragma unroll
-        for (int c = 0; c < 3; c++) a.out[3 * dst + c] = (e[c] * dn_modulation(a, p.a[c])) * a.sp;
+        for (int c = 0; c < 3; c++) a.out[3 * dst + c] = (e[c] * post_modulation(a.demodulate, a.albedo_floor, p.a[c])) * a.sp;
     } else {
-        const uint64_t i = (uint64_t)y * a.width + x;
-        cout[i] = make_double2(e[0], e[1]);
-        cout[n + i] = make_double2(e[2], p.a[2]);
+        cout[ip] = make_double2(e[0], e[1]);
+        cout[n + ip] = make_double2(e[2], p.a[2]);
     }
 }
 
@@ -158,12 +109,12 @@ __global__ void __launch_bounds__(kDnBlock) dn_atrous(const DenoiseArgs a, const
 struct DnDualPixel { double e[3], u, n[3], a[3], z; };
 
 // The three guide pieces and the a2 plane at index i.
-DN_DEV void dn_dual_guides(const double2 *g, const double *a2, uint64_t stride, uint64_t i, double n[3], double a[3], double &z) {
+POST_DEV void dn_dual_guides(const double2 *g, const double *a2, uint64_t stride, uint64_t i, double n[3], double a[3], double &z) {
     const double2 g0 = g[i], g1 = g[stride + i], g2 = g[2 * stride + i];
     n[0] = g0.x; n[1] = g0.y; n[2] = g1.x; z = g1.y; a[0] = g2.x; a[1] = g2.y; a[2] = a2[i];
 }
 
-DN_DEV DnDualPixel dn_dual_load(const double2 *g, const double *a2, const double2 *c, uint64_t stride, uint64_t i) {
+POST_DEV DnDualPixel dn_dual_load(const double2 *g, const double *a2, const double2 *c, uint64_t stride, uint64_t i) {
     DnDualPixel p;
     dn_dual_guides(g, a2, stride, i, p.n, p.a, p.z);
     const double2 c0 = c[i], c1 = c[stride + i];
@@ -174,7 +125,7 @@ DN_DEV DnDualPixel dn_dual_load(const double2 *g, const double *a2, const double
 // Where the prepare kernel and the last prefilter pass leave the variance.
 enum : int { kDnVarPlane = 0, kDnVarColour = 1, kDnVarOut = 2 };        // a v plane / colour plane 0's u / a.out_var
 
-DN_DEV void dn_dual_store_var(const DenoiseDualArgs &d, int to, double *vplane, double2 *colour0, uint64_t n, uint64_t i, uint64_t buf, double v) {
+POST_DEV void dn_dual_store_var(const DenoiseDualArgs &d, int to, double *vplane, double2 *colour0, uint64_t n, uint64_t i, uint64_t buf, double v) {
     if (to == kDnVarPlane) vplane[i] = v;
     else if (to == kDnVarColour) reinterpret_cast<double *>(colour0 + n + i)[1] = v;
     else if (d.out_var) d.out_var[buf] = v;
@@ -182,25 +133,21 @@ DN_DEV void dn_dual_store_var(const DenoiseDualArgs &d, int to, double *vplane, 
 
 // Buffer order -> image order for both halves. `final` (no colour iteration): the mean goes straight back out. `var_to`:
 // where v0 goes — the first v plane (a prefilter follows), colour plane 0 (none does) or the output (nothing follows).
-__global__ void __launch_bounds__(kDnBlock) dn_dual_prepare(const DenoiseDualArgs d, double2 *guides, double *a2, double2 *colour, double *vplane,
-                                                            const uint32_t *inv, bool final, int var_to) {
+__global__ void __launch_bounds__(kPostBlock) dn_dual_prepare(const DenoiseDualArgs d, double2 *guides, double *a2, double2 *colour, double *vplane,
+                                                              bool final, int var_to) {
     const DenoiseArgs &a = d.a;
-    uint32_t x0, y0;
-    dn_block_origin(a, x0, y0);
-    const uint32_t x = x0 + (threadIdx.x & 63u), y = y0 + (threadIdx.x >> 6);
+    uint32_t x, y;
+    post_pixel(a.width, x, y);
     if (x >= a.width || y >= a.height) return;
     const uint64_t n = (uint64_t)a.width * a.height, i = (uint64_t)y * a.width + x;
-    const uint64_t src = (uint64_t)(inv ? inv[y] : y) * a.width + x;
-    const double2 *fa = reinterpret_cast<const double2 *>(a.feat + src), *fb = reinterpret_cast<const double2 *>(d.feat_b + src);
-    const double2 p0 = fa[0], p1 = fa[1], p2 = fa[2], p3 = fa[3];       // {a0, a1} {a2, n0} {n1, n2} {depth, hits}
-    const double2 q0 = fb[0], q1 = fb[1], q2 = fb[2], q3 = fb[3];
-    const double alb[3] = {(p0.x + q0.x) / d.sp2, (p0.y + q0.y) / d.sp2, (p1.x + q1.x) / d.sp2};
-    double e[3], h[3], m[3];
+    const uint64_t src = post_src(a.inv, a.width, x, y);
+    const PostRecord r = post_add(post_load(a.feat, src), post_load(d.feat_b, src));     // the guides are the two halves' mean
+    double alb[3], e[3], h[3], m[3];
+    post_albedo(r, d.sp2, alb);
 #pragma unroll
     for (int c = 0; c < 3; c++) {
-        const double sa = a.sum[3 * src + c], sb = d.sum_b[3 * src + c];
-        const double ca = (sa != sa ? 0.0 : sa) / a.sp, cb = (sb != sb ? 0.0 : sb) / a.sp;
-        m[c] = dn_modulation(a, alb[c]);
+        const double ca = post_mean(a.sum[3 * src + c], a.sp), cb = post_mean(d.sum_b[3 * src + c], a.sp);
+        m[c] = post_modulation(a.demodulate, a.albedo_floor, alb[c]);
         e[c] = ((ca + cb) * 0.5) / m[c];
         h[c] = ((ca - cb) * 0.5) / m[c];
     }
@@ -213,8 +160,8 @@ __global__ void __launch_bounds__(kDnBlock) dn_dual_prepare(const DenoiseDualArg
             return;
         }
     }
-    guides[i] = make_double2((p1.y + q1.y) / d.sp2, (p2.x + q2.x) / d.sp2);
-    guides[n + i] = make_double2((p2.y + q2.y) / d.sp2, (p3.x + q3.x) / d.sp2);
+    guides[i] = make_double2(r.f1.y / d.sp2, r.f2.x / d.sp2);
+    guides[n + i] = make_double2(r.f2.y / d.sp2, r.f3.x / d.sp2);
     guides[2 * n + i] = make_double2(alb[0], alb[1]);
     a2[i] = alb[2];
     colour[i] = make_double2(e[0], e[1]);
@@ -224,147 +171,79 @@ __global__ void __launch_bounds__(kDnBlock) dn_dual_prepare(const DenoiseDualArg
 
 // One prefilter pass over the variance at step s: the guides' weights alone. `var_to`: where the result goes (a v plane;
 // after the last pass colour plane 0's u, or with no colour iteration the output, in buffer order).
-__global__ void __launch_bounds__(kDnBlock) dn_dual_prefilter(const DenoiseDualArgs d, const double2 *guides, const double *a2, const double *vin,
-                                                              double *vout, double2 *colour0, const uint32_t *inv, uint32_t s, int var_to) {
+__global__ void __launch_bounds__(kPostBlock) dn_dual_prefilter(const DenoiseDualArgs d, const double2 *guides, const double *a2, const double *vin,
+                                                                double *vout, double2 *colour0, uint32_t s, int var_to) {
     const DenoiseArgs &a = d.a;
-    uint32_t x0, y0;
-    dn_block_origin(a, x0, y0);
-    const uint32_t x = x0 + (threadIdx.x & 63u), y = y0 + (threadIdx.x >> 6);
+    uint32_t x, y;
+    post_pixel(a.width, x, y);
     if (x >= a.width || y >= a.height) return;
-    const int64_t W = a.width, H = a.height, step = s;
     const uint64_t n = (uint64_t)a.width * a.height, ip = (uint64_t)y * a.width + x;
     double pn[3], pa[3], pz;
     dn_dual_guides(guides, a2, n, ip, pn, pa, pz);
     double sw = 0.0, sx = 0.0;
-#pragma unroll
-    for (int j = -2; j <= 2; j++) {
-        const int64_t qy = (int64_t)y + (int64_t)j * step;
-#pragma unroll
-        for (int i = -2; i <= 2; i++) {
-            const int64_t qx = (int64_t)x + (int64_t)i * step;
-            if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
-            const uint64_t iq = (uint64_t)qy * a.width + (uint64_t)qx;
-            double qn[3], qa[3], qz;
-            dn_dual_guides(guides, a2, n, iq, qn, qa, qz);
-            const double dn = dn_dist(pn, qn), da = dn_dist(pa, qa), dz = pz - qz;
-            const double g = ((1.0 + dn * a.inv_n) * (1.0 + (dz * dz) * a.inv_z)) * (1.0 + da * a.inv_a);
-            const double w = (dn_h(j + 2) * dn_h(i + 2)) / g;
-            sw = sw + w;
-            sx = sx + w * vin[iq];
-        }
-    }
-    dn_dual_store_var(d, var_to, vout, colour0, n, ip, (uint64_t)(inv ? inv[y] : y) * a.width + x, sx / sw);
+    dn_for_taps(x, y, s, a.width, a.height, [&](double h, uint64_t iq) {
+        double qn[3], qa[3], qz;
+        dn_dual_guides(guides, a2, n, iq, qn, qa, qz);
+        const double dn = dn_dist(pn, qn), da = dn_dist(pa, qa), dz = pz - qz;
+        const double g = ((1.0 + dn * a.inv_n) * (1.0 + (dz * dz) * a.inv_z)) * (1.0 + da * a.inv_a);
+        const double w = h / g;
+        sw = sw + w;
+        sx = sx + w * vin[iq];
+    });
+    dn_dual_store_var(d, var_to, vout, colour0, n, ip, post_src(a.inv, a.width, x, y), sx / sw);
 }
 
 // One variance-aware iteration at step s. LAST: the colour is remodulated and written to a.out, the variance to d.out_var,
 // both in buffer order, instead of the other colour plane.
 template <bool LAST>
-__global__ void __launch_bounds__(kDnBlock) dn_dual_atrous(const DenoiseDualArgs d, const double2 *guides, const double *a2, const double2 *cin,
-                                                           double2 *cout, const uint32_t *inv, uint32_t s) {
+__global__ void __launch_bounds__(kPostBlock) dn_dual_atrous(const DenoiseDualArgs d, const double2 *guides, const double *a2, const double2 *cin,
+                                                             double2 *cout, uint32_t s) {
     const DenoiseArgs &a = d.a;
-    uint32_t x0, y0;
-    dn_block_origin(a, x0, y0);
-    const uint32_t x = x0 + (threadIdx.x & 63u), y = y0 + (threadIdx.x >> 6);
+    uint32_t x, y;
+    post_pixel(a.width, x, y);
     if (x >= a.width || y >= a.height) return;
-    const int64_t W = a.width, H = a.height, step = s;
-    const uint64_t n = (uint64_t)a.width * a.height;
-    const DnDualPixel p = dn_dual_load(guides, a2, cin, n, (uint64_t)y * a.width + x);
+    const uint64_t n = (uint64_t)a.width * a.height, ip = (uint64_t)y * a.width + x;
+    const DnDualPixel p = dn_dual_load(guides, a2, cin, n, ip);
     double sw = 0.0, su = 0.0, sv[3] = {0.0, 0.0, 0.0};
+    dn_for_taps(x, y, s, a.width, a.height, [&](double h, uint64_t iq) {
+        const DnDualPixel q = dn_dual_load(guides, a2, cin, n, iq);
+        const double dc = dn_dist(p.e, q.e), dn = dn_dist(p.n, q.n), da = dn_dist(p.a, q.a), dz = p.z - q.z;
+        const double r = (dc * d.inv_c) / ((p.u + q.u) + d.var_floor);
+        const double den = (((1.0 + r) * (1.0 + dn * a.inv_n)) * (1.0 + (dz * dz) * a.inv_z)) * (1.0 + da * a.inv_a);
+        const double w = h / den;
+        sw = sw + w;
 #pragma unroll
-    for (int j = -2; j <= 2; j++) {
-        const int64_t qy = (int64_t)y + (int64_t)j * step;
-#pragma unroll
-        for (int i = -2; i <= 2; i++) {
-            const int64_t qx = (int64_t)x + (int64_t)i * step;
-            if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
-            const DnDualPixel q = dn_dual_load(guides, a2, cin, n, (uint64_t)qy * a.width + (uint64_t)qx);
-            const double dc = dn_dist(p.e, q.e), dn = dn_dist(p.n, q.n), da = dn_dist(p.a, q.a), dz = p.z - q.z;
-            const double r = (dc * d.inv_c) / ((p.u + q.u) + d.var_floor);
-            const double den = (((1.0 + r) * (1.0 + dn * a.inv_n)) * (1.0 + (dz * dz) * a.inv_z)) * (1.0 + da * a.inv_a);
-            const double w = (dn_h(j + 2) * dn_h(i + 2)) / den;
-            sw = sw + w;
-#pragma unroll
-            for (int c = 0; c < 3; c++) sv[c] = sv[c] + w * q.e[c];
-            su = su + (w * w) * q.u;
-        }
-    }
+        for (int c = 0; c < 3; c++) sv[c] = sv[c] + w * q.e[c];
+        su = su + (w * w) * q.u;
+    });
     const double e[3] = {sv[0] / sw, sv[1] / sw, sv[2] / sw};
     const double u = su / (sw * sw);
     if (LAST) {
-        const uint64_t dst = (uint64_t)(inv ? inv[y] : y) * a.width + x;
+        const uint64_t dst = post_src(a.inv, a.width, x, y);
 #pragma unroll
-        for (int c = 0; c < 3; c++) a.out[3 * dst + c] = (e[c] * dn_modulation(a, p.a[c])) * d.sp2;
+        for (int c = 0; c < 3; c++) a.out[3 * dst + c] = (e[c] * post_modulation(a.demodulate, a.albedo_floor, p.a[c])) * d.sp2;
         if (d.out_var) d.out_var[dst] = u;
     } else {
-        const uint64_t i = (uint64_t)y * a.width + x;
-        cout[i] = make_double2(e[0], e[1]);
-        cout[n + i] = make_double2(e[2], u);
+        cout[ip] = make_double2(e[0], e[1]);
+        cout[n + ip] = make_double2(e[2], u);
     }
 }
 
 } // namespace
 
-DenoiseLayout denoise_layout(uint32_t width, uint32_t height) {
-    const uint64_t n = (uint64_t)width * height;
-    DenoiseLayout l;
-    l.guides = 0;
-    l.colour[0] = 3 * n * sizeof(double2);
-    l.colour[1] = l.colour[0] + 2 * n * sizeof(double2);
-    l.inv_rows = l.colour[1] + 2 * n * sizeof(double2);
-    l.bad_rows = l.inv_rows + ((uint64_t)height * sizeof(uint32_t) + 15u) / 16u * 16u;
-    l.bytes = l.bad_rows + 16u;
-    return l;
-}
-
-hipError_t launch_row_list_check(const uint32_t *rows, uint32_t height, uint32_t *inv, uint32_t *bad, hipStream_t stream) {
-    hipLaunchKernelGGL(dn_rows, dim3(1), dim3(1024), 0, stream, rows, height, inv, bad);
-    return hipGetLastError();
-}
-
-hipError_t launch_denoise_rows(const DenoiseArgs &a, hipStream_t stream) {
-    const DenoiseLayout l = denoise_layout(a.width, a.height);
-    hipLaunchKernelGGL(dn_rows, dim3(1), dim3(1024), 0, stream, a.rows, a.height, reinterpret_cast<uint32_t *>(a.ws + l.inv_rows),
-                       reinterpret_cast<uint32_t *>(a.ws + l.bad_rows));
-    return hipGetLastError();
-}
-
 hipError_t launch_denoise(const DenoiseArgs &a, uint32_t n_iter, const double *inv_c, hipStream_t stream) {
     const DenoiseLayout l = denoise_layout(a.width, a.height);
     double2 *const guides = reinterpret_cast<double2 *>(a.ws + l.guides);
     double2 *const colour[2] = {reinterpret_cast<double2 *>(a.ws + l.colour[0]), reinterpret_cast<double2 *>(a.ws + l.colour[1])};
-    const uint32_t *const inv = a.rows ? reinterpret_cast<const uint32_t *>(a.ws + l.inv_rows) : nullptr;
-    const dim3 grid((a.width + 63u) / 64u * ((a.height + 3u) / 4u)), block(kDnBlock);
-    hipLaunchKernelGGL(dn_prepare, grid, block, 0, stream, a, guides, colour[0], inv, n_iter == 0);
+    const dim3 grid = post_grid(a.width, a.height), block(kPostBlock);
+    hipLaunchKernelGGL(dn_prepare, grid, block, 0, stream, a, guides, colour[0], n_iter == 0);
     hipError_t e = hipGetLastError();
     for (uint32_t k = 0; k < n_iter && e == hipSuccess; k++) {
-        const uint32_t s = 1u << k;
         hipLaunchKernelGGL(k + 1 == n_iter ? dn_atrous<true> : dn_atrous<false>, grid, block, 0, stream, a, guides, colour[k & 1u], colour[~k & 1u],
-                           inv, s, inv_c[k]);
+                           1u << k, inv_c[k]);
         e = hipGetLastError();
     }
     return e;
-}
-
-DenoiseDualLayout denoise_dual_layout(uint32_t width, uint32_t height) {
-    const uint64_t n = (uint64_t)width * height, n2 = (n + 1u) / 2u * 2u;   // (a plane of doubles ends on a 16-byte piece)
-    DenoiseDualLayout l;
-    l.guides = 0;
-    l.a2 = 3 * n * sizeof(double2);
-    l.colour[0] = l.a2 + n2 * sizeof(double);
-    l.colour[1] = l.colour[0] + 2 * n * sizeof(double2);
-    l.var[0] = l.colour[1] + 2 * n * sizeof(double2);
-    l.var[1] = l.var[0] + n2 * sizeof(double);
-    l.inv_rows = l.var[1] + n2 * sizeof(double);
-    l.bad_rows = l.inv_rows + ((uint64_t)height * sizeof(uint32_t) + 15u) / 16u * 16u;
-    l.bytes = l.bad_rows + 16u;
-    return l;
-}
-
-hipError_t launch_denoise_dual_rows(const DenoiseDualArgs &d, hipStream_t stream) {
-    const DenoiseDualLayout l = denoise_dual_layout(d.a.width, d.a.height);
-    hipLaunchKernelGGL(dn_rows, dim3(1), dim3(1024), 0, stream, d.a.rows, d.a.height, reinterpret_cast<uint32_t *>(d.a.ws + l.inv_rows),
-                       reinterpret_cast<uint32_t *>(d.a.ws + l.bad_rows));
-    return hipGetLastError();
 }
 
 hipError_t launch_denoise_dual(const DenoiseDualArgs &d, uint32_t var_iter, uint32_t n_iter, hipStream_t stream) {
@@ -374,19 +253,18 @@ hipError_t launch_denoise_dual(const DenoiseDualArgs &d, uint32_t var_iter, uint
     double *const a2 = reinterpret_cast<double *>(a.ws + l.a2);
     double2 *const colour[2] = {reinterpret_cast<double2 *>(a.ws + l.colour[0]), reinterpret_cast<double2 *>(a.ws + l.colour[1])};
     double *const var[2] = {reinterpret_cast<double *>(a.ws + l.var[0]), reinterpret_cast<double *>(a.ws + l.var[1])};
-    const uint32_t *const inv = a.rows ? reinterpret_cast<const uint32_t *>(a.ws + l.inv_rows) : nullptr;
-    const dim3 grid((a.width + 63u) / 64u * ((a.height + 3u) / 4u)), block(kDnBlock);
+    const dim3 grid = post_grid(a.width, a.height), block(kPostBlock);
     const int var_end = n_iter ? kDnVarColour : kDnVarOut;                // where the variance the colour passes start from goes
-    hipLaunchKernelGGL(dn_dual_prepare, grid, block, 0, stream, d, guides, a2, colour[0], var[0], inv, n_iter == 0, var_iter ? kDnVarPlane : var_end);
+    hipLaunchKernelGGL(dn_dual_prepare, grid, block, 0, stream, d, guides, a2, colour[0], var[0], n_iter == 0, var_iter ? kDnVarPlane : var_end);
     hipError_t e = hipGetLastError();
     for (uint32_t t = 0; t < var_iter && e == hipSuccess; t++) {
-        hipLaunchKernelGGL(dn_dual_prefilter, grid, block, 0, stream, d, guides, a2, var[t & 1u], var[~t & 1u], colour[0], inv, 1u << t,
+        hipLaunchKernelGGL(dn_dual_prefilter, grid, block, 0, stream, d, guides, a2, var[t & 1u], var[~t & 1u], colour[0], 1u << t,
                            t + 1 == var_iter ? var_end : kDnVarPlane);
         e = hipGetLastError();
     }
     for (uint32_t k = 0; k < n_iter && e == hipSuccess; k++) {
         hipLaunchKernelGGL(k + 1 == n_iter ? dn_dual_atrous<true> : dn_dual_atrous<false>, grid, block, 0, stream, d, guides, a2, colour[k & 1u],
-                           colour[~k & 1u], inv, 1u << k);
+                           colour[~k & 1u], 1u << k);
         e = hipGetLastError();
     }
     return e;

@@ -285,16 +285,11 @@ constexpr int kFeatRows = 0, kFeatPixels = 1, kFeatRays = 2;
 hipError_t launch_features(const SceneDev &scene, const FeatureArgs &args, uint32_t stack_need, int src, bool counters, bool surfaces,
                            bool specular, hipStream_t stream);
 
+// ---- the calls on a render's buffers: where the pieces of their workspaces lie is host/post_check.hpp's to know ----
+// The row kernel (pt_rows.hip) on a list of `height` ids: inv[image row] = buffer row, *bad = ids out of range or repeated.
+hipError_t launch_row_list_check(const uint32_t *rows, uint32_t height, uint32_t *inv, uint32_t *bad, hipStream_t stream);
+
 // ---- edge-avoiding denoiser (pt_denoise.hip, rt_denoise*) ----------------------------
-// Where the pieces of the caller's workspace lie (byte offsets, each a multiple of 16) — the one place that knows.
-struct DenoiseLayout {
-    uint64_t guides;                   // 3 planes of n_pixels double2: {n0, n1} {n2, z} {a0, a1}, image order
-    uint64_t colour[2];                // ping-pong, each 2 planes of n_pixels double2: {e0, e1} {e2, a2}
-    uint64_t inv_rows;                 // height x uint32: image row -> buffer row
-    uint64_t bad_rows;                 // one uint32: bad or repeated row ids of the call's list
-    uint64_t bytes;
-};
-DenoiseLayout denoise_layout(uint32_t width, uint32_t height);
 struct DenoiseArgs {
     uint32_t width, height;
     double sp;                         // (double)spp
@@ -303,28 +298,14 @@ struct DenoiseArgs {
     bool demodulate;
     const double *sum;                 // device: the render's sums, buffer order
     const rt_feature *feat;            // device, 16-byte aligned, buffer order
-    const uint32_t *rows;              // device: buffer row -> image row (null: the identity)
+    const uint32_t *inv;               // device: image row -> buffer row (null: the identity)
     double *out;                       // device: the filtered sums, buffer order (may be `sum`)
-    char *ws;                          // the workspace, 16-byte aligned
+    char *ws;                          // the workspace, 16-byte aligned, laid out by denoise_layout
 };
-// The row kernel on a.rows (not null): the inverse map and the count of bad ids, both in the workspace.
-hipError_t launch_denoise_rows(const DenoiseArgs &a, hipStream_t stream);
 // prepare + n_iter a-trous passes; inv_c[k] = 1 / sigma_k^2.
 hipError_t launch_denoise(const DenoiseArgs &a, uint32_t n_iter, const double *inv_c, hipStream_t stream);
 
 // ---- variance-guided denoiser over two half-sample renders (pt_denoise.hip, rt_denoise_dual*) ----
-// The dual filter's workspace (byte offsets, each a multiple of 16). A pixel's eleven doubles are five 16-byte pieces and
-// one 8-byte piece, each a plane of its own.
-struct DenoiseDualLayout {
-    uint64_t guides;                   // 3 planes of n_pixels double2: {n0, n1} {n2, z} {a0, a1}, image order
-    uint64_t a2;                       // 1 plane of n_pixels double: the albedo's third component
-    uint64_t colour[2];                // ping-pong, each 2 planes of n_pixels double2: {e0, e1} {e2, u}
-    uint64_t var[2];                   // ping-pong of the prefilter, each 1 plane of n_pixels double: v
-    uint64_t inv_rows;                 // height x uint32: image row -> buffer row
-    uint64_t bad_rows;                 // one uint32: bad or repeated row ids of the call's list
-    uint64_t bytes;
-};
-DenoiseDualLayout denoise_dual_layout(uint32_t width, uint32_t height);
 struct DenoiseDualArgs {
     DenoiseArgs a;                     // half A's buffers; sp = (double)spp of ONE half; ws laid out by denoise_dual_layout
     const double *sum_b;               // device: half B's sums, buffer order
@@ -334,16 +315,11 @@ struct DenoiseDualArgs {
     double inv_c;                      // 1 / sigma_color^2, every iteration's
     double var_floor;
 };
-// The row kernel on a.a.rows (not null), into the dual layout's map and count.
-hipError_t launch_denoise_dual_rows(const DenoiseDualArgs &a, hipStream_t stream);
 // dual prepare + var_iter prefilter passes + n_iter variance-aware a-trous passes.
 hipError_t launch_denoise_dual(const DenoiseDualArgs &a, uint32_t var_iter, uint32_t n_iter, hipStream_t stream);
 
-// The denoisers' row kernel (dn_rows) on a list of `height` ids: inv[image row] = buffer row, *bad = ids out of range or repeated.
-hipError_t launch_row_list_check(const uint32_t *rows, uint32_t height, uint32_t *inv, uint32_t *bad, hipStream_t stream);
-
 // ---- temporal accumulation with reprojection (pt_temporal.hip, rt_temporal*) ------------------------------
-// One kernel, one lane per pixel; the workspace holds nothing but the row kernel's map (host/temporal_check.hpp).
+// One kernel, one lane per pixel; the workspace holds nothing but the row kernel's map.
 struct TemporalArgs {
     uint32_t width, height;
     double sp;                         // (double)spp
@@ -364,27 +340,18 @@ struct TemporalArgs {
 hipError_t launch_temporal(const TemporalArgs &a, hipStream_t stream);
 
 // ---- adaptive sampling: planner, merge, resolve (pt_adaptive.hip, rt_adaptive_*) -----------------------
-// The planner's workspace (byte offsets, each a multiple of 16).
-struct AdaptiveLayout {
-    uint64_t n_tiles;                  // workgroups of the scan (tiles of 1024 pixels)
-    uint64_t totals;                   // (n_tiles + 1) x uint64: the tiles' units, then their exclusive scan; the last word: the total
-    uint64_t bad_rows;                 // one uint32: bad or repeated row ids of the call's list
-    uint64_t inv_rows;                 // height x uint32: image row -> buffer row (the row kernel's by-product)
-    uint64_t bytes;
-};
-AdaptiveLayout adaptive_layout(uint32_t width, uint32_t height);
 struct AdaptivePlanArgs {
     uint32_t width, height, first_frame, max_units;
     double scale;
     const double *err;                 // device, buffer order
-    const uint32_t *rows;              // device: buffer row -> image row (null: the identity)
+    const uint32_t *rows;              // device: buffer row -> image row (null: the identity), already through the row kernel
     uint32_t *units;                   // device: [n]
     uint64_t *offsets;                 // device: [n + 1]
     uint64_t *entries;                 // device: [capacity] (null with capacity 0)
     uint64_t capacity;
-    char *ws;                          // the workspace, 16-byte aligned
+    char *ws;                          // the workspace, 16-byte aligned, laid out by adaptive_layout
 };
-// The row kernel (with rows) and the scan's three launches; the total is then at ws + totals + 8 * n_tiles, the bad-row count at ws + bad_rows.
+// The scan's three launches; the total is then at ws + totals + 8 * n_tiles. With rows, ad_emit reads the row kernel's count at ws + rows.bad.
 hipError_t launch_adaptive_plan(const AdaptivePlanArgs &p, hipStream_t stream);
 hipError_t launch_adaptive_merge(const double *sums, const uint32_t *units, const uint64_t *offsets, uint64_t n, uint32_t spp, double *acc,
                                  double *acc_n, hipStream_t stream);

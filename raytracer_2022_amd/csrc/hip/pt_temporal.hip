@@ -1,49 +1,43 @@
 // pt_temporal.hip — temporal accumulation with reprojection (rt_temporal*, include/rt2022.h has the definition: every
 // + - * / below is one of its operations, in its order; -ffp-contract=off).
 //
-// One kernel, tp_accumulate: one lane per pixel in the 64 x 4 tiles of the dn_* kernels (a wave is 64 consecutive pixels of
-// one image row). A lane reads its sums (24 B) and its feature record (four 16-byte pieces) at the pixel's place in buffer
-// order, finds the mean first-hit point from the record's depth, projects it into the previous camera by Cramer's rule and
-// gathers the four bilinear taps of the previous state: records are 64 B and the two taps of a row are neighbours, so a
-// lane reads two 128-byte spans of d_prev as 16-byte pieces. It writes its own state record (four 16-byte pieces, image
-// order) and its three sums (buffer order). Nothing is staged: no LDS, and no workspace but the row kernel's map (dn_rows of
-// pt_denoise.hip, through launch_row_list_check). fx / fy become integers only after the range test, so a tap's address is
+// One kernel, tp_accumulate: one lane per pixel in the 64 x 4 tiles of pt_post.hpp (a wave is 64 consecutive pixels of one
+// image row). A lane reads its sums (24 B) and its feature record (four 16-byte pieces) at the pixel's place in buffer order
+// through that header's front end, finds the mean first-hit point from the record's depth, projects it into the previous
+// camera by Cramer's rule and gathers the four bilinear taps of the previous state: records are 64 B and the two taps of a
+// row are neighbours, so a lane reads two 128-byte spans of d_prev as 16-byte pieces. It writes its own state record (four
+// 16-byte pieces, image order) and its three sums (buffer order). Nothing is staged: no LDS, and no workspace but the row
+// kernel's map (pt_rows.hip; a.inv). fx / fy become integers only after the range test, so a tap's address is
 // computed from numbers in [-1, width] x [-1, height] and is used only when it lies inside the image. A far miss
 // (RT_TEMPORAL_FAR_MISSES) takes the same path with another right-hand side and another tap rule: the same four taps.
-#include "pt_device.h"
+#include "pt_post.hpp"
 
 namespace rt2022 {
 
 namespace {
 
-constexpr int kTpBlock = 256;          // 4 waves: rows y .. y+3 of a 64-pixel column strip
+POST_DEV double tp_dot(const double u[3], const double v[3]) { return (u[0] * v[0] + u[1] * v[1]) + u[2] * v[2]; }
 
-#define TP_DEV __device__ __forceinline__
-
-TP_DEV double tp_dot(const double u[3], const double v[3]) { return (u[0] * v[0] + u[1] * v[1]) + u[2] * v[2]; }
-
-TP_DEV void tp_cross(const double u[3], const double v[3], double w[3]) {
+POST_DEV void tp_cross(const double u[3], const double v[3], double w[3]) {
     w[0] = u[1] * v[2] - u[2] * v[1];
     w[1] = u[2] * v[0] - u[0] * v[2];
     w[2] = u[0] * v[1] - u[1] * v[0];
 }
 
-__global__ void __launch_bounds__(kTpBlock) tp_accumulate(const TemporalArgs a) {
-    const uint32_t nbx = (uint32_t)(((uint64_t)a.width + 63u) / 64u);
-    const uint32_t by = blockIdx.x / nbx, bx = blockIdx.x - by * nbx;
-    const uint32_t x = bx * 64u + (threadIdx.x & 63u), y = by * 4u + (threadIdx.x >> 6);
+__global__ void __launch_bounds__(kPostBlock) tp_accumulate(const TemporalArgs a) {
+    uint32_t x, y;
+    post_pixel(a.width, x, y);
     if (x >= a.width || y >= a.height) return;
     const uint64_t i = (uint64_t)y * a.width + x;
-    const uint64_t src = (uint64_t)(a.inv ? a.inv[y] : y) * a.width + x;
-    const double2 *f = reinterpret_cast<const double2 *>(a.feat + src);
-    const double2 f0 = f[0], f1 = f[1], f2 = f[2], f3 = f[3];           // {a0, a1} {a2, n0} {n1, n2} {depth, hits}
-    const double alb[3] = {f0.x / a.sp, f0.y / a.sp, f1.x / a.sp};
-    double e[3], m[3];
+    const uint64_t src = post_src(a.inv, a.width, x, y);
+    const PostRecord r = post_load(a.feat, src);
+    const double2 f1 = r.f1, f2 = r.f2, f3 = r.f3;
+    double alb[3], e[3], m[3];
+    post_albedo(r, a.sp, alb);
 #pragma unroll
     for (int c = 0; c < 3; c++) {
-        const double s = a.sum[3 * src + c];
-        m[c] = a.demodulate ? (alb[c] > a.albedo_floor ? alb[c] : a.albedo_floor) : 1.0;
-        e[c] = ((s != s ? 0.0 : s) / a.sp) / m[c];
+        m[c] = post_modulation(a.demodulate, a.albedo_floor, alb[c]);
+        e[c] = post_colour(a.sum[3 * src + c], a.sp, m[c]);
     }
     const double hits = f3.y;
     const bool covered = hits > 0.0;
@@ -126,8 +120,7 @@ __global__ void __launch_bounds__(kTpBlock) tp_accumulate(const TemporalArgs a) 
 } // namespace
 
 hipError_t launch_temporal(const TemporalArgs &a, hipStream_t stream) {
-    const dim3 grid((uint32_t)(((uint64_t)a.width + 63u) / 64u * (((uint64_t)a.height + 3u) / 4u))), block(kTpBlock);
-    hipLaunchKernelGGL(tp_accumulate, grid, block, 0, stream, a);
+    hipLaunchKernelGGL(tp_accumulate, post_grid(a.width, a.height), dim3(kPostBlock), 0, stream, a);
     return hipGetLastError();
 }
 

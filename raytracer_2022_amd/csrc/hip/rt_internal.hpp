@@ -27,6 +27,20 @@ int guarded(F &&f) {
     }
 }
 
+// A *_fault function's verdict (host/*_check.hpp; null: nothing wrong) as the call's refusal: "<who>: <fault>".
+inline void require_no_fault(const char *fault, const std::string &who) { if (fault) throw Fail{RT_ERR_INVALID, who + ": " + fault}; }
+
+// The shells of the host-buffer forms: `count` elements of host memory on the device (null or 0: an empty buffer, whose
+// pointer is null), and back (null or 0: nothing is copied). Blocking copies on the null stream.
+template <class T>
+DeviceBuf<T> uploaded(const T *host, uint64_t count) {
+    DeviceBuf<T> d(host ? count : 0);
+    if (d.n) RT_HIP(hipMemcpy(d, host, count * sizeof(T), hipMemcpyHostToDevice));
+    return d;
+}
+template <class T>
+void download(T *host, const DeviceBuf<T> &d, uint64_t count) { if (host && count) RT_HIP(hipMemcpy(host, d, count * sizeof(T), hipMemcpyDeviceToHost)); }
+
 // The scene's buffers, pools and streams live on the device that was current at rt_scene_create. Every entry
 // point that touches them makes that device current for the call and puts the caller's back afterwards, so one
 // process may hold scenes on several GPUs (one host thread per scene and stream) whatever its current device is.

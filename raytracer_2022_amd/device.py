@@ -162,20 +162,33 @@ def denoise_workspace_bytes(params):
     return int(F.lib().rt_denoise_workspace_bytes(C.byref(params)))
 
 
+def _row_list(row_ids, height):
+    """A host row list as the C ABI takes it: contiguous uint32, one entry per image row (None: no list)."""
+    if row_ids is None:
+        return None
+    rows = np.ascontiguousarray(row_ids, dtype=np.uint32)
+    if rows.size != height:
+        raise ValueError("row_ids must hold one entry per image row")
+    return rows
+
+
+def _hold_pixels(params, message, *buffers):
+    """width * height of params' image, once every (array, values per pixel) of `buffers` holds that many pixels; else
+    ValueError(message)."""
+    n = params.width * params.height
+    if any(a.size != per_pixel * n for a, per_pixel in buffers):
+        raise ValueError(message)
+    return n
+
+
 def denoise(rgb_sum, features, params, row_ids=None, want_ms=False):
     """rt_denoise with host buffers: a render's sums (height, width, 3) and its FEATURE_DTYPE records (height, width), both
     in the order of `row_ids` (None: image order; else the frame's row list, a permutation of the image's rows) -> the
     filtered sums, same shape and order [, device ms]."""
     s = np.ascontiguousarray(rgb_sum, dtype=np.float64)
     f = np.ascontiguousarray(features, dtype=F.FEATURE_DTYPE)
-    n = params.width * params.height
-    if s.size != 3 * n or f.size != n:
-        raise ValueError("rgb_sum and features must hold width * height pixels")
-    rows = None
-    if row_ids is not None:
-        rows = np.ascontiguousarray(row_ids, dtype=np.uint32)
-        if rows.size != params.height:
-            raise ValueError("row_ids must hold one entry per image row")
+    _hold_pixels(params, "rgb_sum and features must hold width * height pixels", (s, 3), (f, 1))
+    rows = _row_list(row_ids, params.height)
     out = np.empty_like(s)
     ms = C.c_double()
     F.check(F.lib().rt_denoise(s.ctypes.data, f.ctypes.data, rows.ctypes.data if rows is not None else None, C.byref(params),
@@ -222,16 +235,10 @@ def denoise_dual(sum_a, sum_b, feat_a, feat_b, params, dual_params=None, row_ids
     width) of params.spp samples each, in the order of `row_ids` (None: image order) -> the filtered sums of 2 * spp samples,
     same shape and order [, the residual variance (height, width)] [, device ms]. params.sigma_color counts estimated
     standard deviations: DUAL_DEFAULTS["sigma_color"] is the tuned value."""
-    n = params.width * params.height
     s = [np.ascontiguousarray(x, dtype=np.float64) for x in (sum_a, sum_b)]
     f = [np.ascontiguousarray(x, dtype=F.FEATURE_DTYPE) for x in (feat_a, feat_b)]
-    if any(x.size != 3 * n for x in s) or any(x.size != n for x in f):
-        raise ValueError("both halves' rgb_sum and features must hold width * height pixels")
-    rows = None
-    if row_ids is not None:
-        rows = np.ascontiguousarray(row_ids, dtype=np.uint32)
-        if rows.size != params.height:
-            raise ValueError("row_ids must hold one entry per image row")
+    n = _hold_pixels(params, "both halves' rgb_sum and features must hold width * height pixels", (s[0], 3), (s[1], 3), (f[0], 1), (f[1], 1))
+    rows = _row_list(row_ids, params.height)
     q = dual_params if dual_params is not None else denoise_dual_params()
     out = np.empty_like(s[0])
     var = np.empty(s[0].shape[:-1] if s[0].ndim > 1 else (n,), dtype=np.float64) if want_variance else None
@@ -286,19 +293,12 @@ def temporal(sums, features, cam, params, prev=None, prev_cam=None, row_ids=None
     image order) [, device ms]."""
     s = np.ascontiguousarray(sums, dtype=np.float64)
     f = np.ascontiguousarray(features, dtype=F.FEATURE_DTYPE)
-    n = params.width * params.height
-    if s.size != 3 * n or f.size != n:
-        raise ValueError("sums and features must hold width * height pixels")
+    _hold_pixels(params, "sums and features must hold width * height pixels", (s, 3), (f, 1))
     pv = None
     if prev is not None:
         pv = np.ascontiguousarray(prev, dtype=F.TEMPORAL_PIXEL_DTYPE)
-        if pv.size != n:
-            raise ValueError("prev must hold width * height pixels")
-    rows = None
-    if row_ids is not None:
-        rows = np.ascontiguousarray(row_ids, dtype=np.uint32)
-        if rows.size != params.height:
-            raise ValueError("row_ids must hold one entry per image row")
+        _hold_pixels(params, "prev must hold width * height pixels", (pv, 1))
+    rows = _row_list(row_ids, params.height)
     out = np.empty_like(s)
     state = np.empty((params.height, params.width), dtype=F.TEMPORAL_PIXEL_DTYPE)
     ms = C.c_double()
@@ -387,14 +387,8 @@ def adaptive_plan(err, params, row_ids=None, capacity=None):
     (units uint32 (height, width), offsets uint64 (n + 1), entries uint64 (total) or None, total). capacity=None sizes the
     list by the plan's own formula; a capacity below the total gives entries None."""
     e = np.ascontiguousarray(err, dtype=np.float64)
-    n = params.width * params.height
-    if e.size != n:
-        raise ValueError("err must hold width * height pixels")
-    rows = None
-    if row_ids is not None:
-        rows = np.ascontiguousarray(row_ids, dtype=np.uint32)
-        if rows.size != params.height:
-            raise ValueError("row_ids must hold one entry per image row")
+    n = _hold_pixels(params, "err must hold width * height pixels", (e, 1))
+    rows = _row_list(row_ids, params.height)
     if capacity is None:
         capacity = int(plan_units(e, params.scale, params.max_units).sum(dtype=np.uint64))
     units = np.zeros(e.shape, dtype=np.uint32)

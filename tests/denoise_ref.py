@@ -102,13 +102,13 @@ SWITCHES = {
 
 
 # ---- row lists longer than the row kernel's block ---------------------------------------------------------------------------
-# dn_rows is ONE workgroup of 1024 threads striding over the list: thread t takes entries t, t + 1024, t + 2048, ... So a
+# post_rows (csrc/hip/pt_rows.hip) is ONE workgroup of 1024 threads striding over the list: thread t takes entries t, t + 1024, t + 2048, ... So a
 # thread's second trip starts at a height of 1025 (one entry on it) and 2500 rows give every thread two or three entries.
 LONG_W, LONG_HEIGHTS, ROW_BLOCK = 3, (1025, 2500), 1024
 
 
 def long_row_lists(H, seed):
-    """A shuffled list of H > 1024 rows and the lists dn_rows must refuse -> (rows, {fault: list}). A fault whose entries the
+    """A shuffled list of H > 1024 rows and the lists post_rows must refuse -> (rows, {fault: list}). A fault whose entries the
     height does not hold is left out (1025 rows have no entry 1500 or 7 + 1024)."""
     rows = np.random.default_rng(seed).permutation(H).astype(np.uint32)
     assert H > ROW_BLOCK and rows.tolist() != list(range(H))

@@ -147,7 +147,7 @@ def test_totals_beyond_32_bits(rt, w, h, max_units):
 
 @pytest.mark.parametrize("h", LONG_HEIGHTS)
 def test_row_lists_longer_than_the_row_kernels_block(rt, h):
-    """dn_rows' stride loop (pt_denoise.hip, one workgroup of 1024 threads): a thread's second trip starts at 1025 rows. Both
+    """post_rows' stride loop (pt_rows.hip, one workgroup of 1024 threads): a thread's second trip starts at 1025 rows. Both
     forms of the planner against adaptive_ref.plan under a shuffled list; the device form refuses a repeat across trips, a
     repeat inside one thread and an id out of range on the last trip with nothing written, and takes the good list on the
     same workspace afterwards."""

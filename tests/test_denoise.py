@@ -125,7 +125,7 @@ def test_bad_row_lists_are_refused_with_the_output_untouched(rt):
 # ---- row lists longer than the row kernel's block (denoise_ref.long_row_lists) ------------------------------------------------
 @pytest.mark.parametrize("H", LONG_HEIGHTS)
 def test_row_lists_longer_than_the_row_kernels_block(rt, H):
-    """dn_rows' stride loop (pt_denoise.hip): a thread's second trip starts at 1025 rows. The host and the device form against
+    """post_rows' stride loop (pt_rows.hip): a thread's second trip starts at 1025 rows. The host and the device form against
     the restatement; the device form refuses a repeat across trips, a repeat inside one thread and an id out of range on the
     last trip with the output untouched, and takes the good list on the same workspace afterwards."""
     import torch

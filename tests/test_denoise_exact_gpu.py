@@ -1,5 +1,5 @@
 """The denoiser kernels themselves (rt_denoise*, rt_denoise_dual*: dn_prepare, dn_atrous, dn_dual_prepare, dn_dual_prefilter,
-dn_dual_atrous and dn_rows in csrc/hip/pt_denoise.hip) held to what shares no code with them: every value inside the 53-bit
+dn_dual_atrous in csrc/hip/pt_denoise.hip and post_rows in pt_rows.hip) held to what shares no code with them: every value inside the 53-bit
 interval enclosure of tests/denoise_exact.py, and every closed form and exact invariant of tests/denoise_cases.py — through
 the host form, and through the device form on torch buffers. tests/test_denoise_ref.py holds the numpy restatements to the
 same on the CPU, so two further shapes are compared with the restatements bit for bit, where the enclosure would be slow.

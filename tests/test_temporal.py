@@ -156,7 +156,7 @@ def test_bad_row_lists_are_refused_with_both_outputs_untouched(rt):
 
 @pytest.mark.parametrize("H", LONG_HEIGHTS)
 def test_row_lists_longer_than_the_row_kernels_block(rt, H):
-    """dn_rows' stride loop (pt_denoise.hip, one workgroup of 1024 threads): a thread's second trip starts at 1025 rows. One
+    """post_rows' stride loop (pt_rows.hip, one workgroup of 1024 threads): a thread's second trip starts at 1025 rows. One
     chained pair of frames, each in a shuffled order of its own, against the restatement; the device form refuses a repeat
     across trips, a repeat inside one thread and an id out of range on the last trip with both outputs untouched, and takes
     the good list on the same workspace afterwards."""
